@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — canonical k-mers/s (load+scan) of the MI355X path on BASELINE.json's config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` and what the steps themselves report).
+`--full` adds everything else the line has carried: the bracketed steps behind the timed ones (kernel times, `roofline`), the CPU
+baselines, the device ceilings, the host-input / Stage 3 / command-line legs, configs 3, 5 and 4 at full size and, with `--scaling
+strong`, the digests compared with tests/golden/fullsize.json (`outputs_check`); the `--no-*` options switch single legs of it off.
+`--dump-outputs DIR` writes what the last timed step handed back (see dump_outputs) as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 A step = one pass of the hot path (Bloom load pass + junction scan pass) over the whole synthetic read set,
 which is resident in HBM before the timed region starts.  N = 1: BASELINE.json configs[1] — 10 M synthetic
@@ -43,6 +50,15 @@ from faucet_amd import api, sharded  # noqa: E402
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 FALLBACKS = []      # steps in which the lazy-flag self-check fired and the scan was repeated with eager flags
 METRIC = "canonical k-mers/s (load+scan) at k=31, 100bp reads; % HBM roofline"
+# --dump-outputs: the reference's counters of the two passes (the walk's own bookkeeping is left out: it is no result), and the sizes of
+# the fixed, seeded samples taken where an output is larger than the dump may be (64 MB in all)
+LOAD_COUNTERS = ("reads_processed", "unambiguous_reads", "kmers", "to_bloo2")
+SCAN_COUNTERS = ("reads_processed", "unambiguous_reads", "reads_no_errors", "nb_jcheck_kmer", "nb_no_juncs", "nb_processed", "nb_skipped",
+                 "n_junctions", "kmers")
+DUMP_SEED = 20261015
+DUMP_JUNCTIONS = 1 << 19        # junctions written whole up to this many, else this many of them, in creation order
+DUMP_BLOOM_BYTES = 1 << 20      # bytes of bloo2 written at seeded positions
+DUMP_BLOOM_BLOCK = 1024         # ... beside the popcount of every block of this many bytes
 
 
 # ---------------------------------------------------------------------------------------------- synthetic data
@@ -160,6 +176,49 @@ def step_multi(shard, batches, rank, world):
         keys, recs = ctx.junctions(pinned=True)                            # pass-2 output final in host memory
     ctx.bloom_download_wait()
     return lst, sst, bloo2, keys, recs
+
+
+def dump_outputs(out_dir, lst, sst, bloo2, keys, recs, rank, world):
+    """--dump-outputs: what one step handed its caller, as .npy files of float32 / float64 that hold every value exactly.
+      load_counters, scan_counters   float64  the passes' counters in the order of LOAD_COUNTERS / SCAN_COUNTERS
+      bloo2_block_popcount           float32  set bits of bloo2 per DUMP_BLOOM_BLOCK bytes (the whole filter)
+      bloo2_sample_bytes             float32  bloo2's bytes at DUMP_BLOOM_BYTES seeded positions (in increasing order)
+      junction_keys                  float64  (n, 2): high and low 32 bits of each junction key, in creation order
+      junction_records               float32  (n, 14): cov[4], dist[5], linked[5] of the same junctions
+    Beyond DUMP_JUNCTIONS junctions both junction files hold the same seeded sample of them, creation order kept.  With N > 1 ranks rank 0
+    writes bloo2's files, the last rank the junctions', and every rank its own counters (suffix _rank<r>)."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+    sfx = "" if world == 1 else f"_rank{rank}"
+    save("load_counters" + sfx, np.array([lst[n] for n in LOAD_COUNTERS], dtype=np.float64))
+    save("scan_counters" + sfx, np.array([sst[n] for n in SCAN_COUNTERS], dtype=np.float64))
+    if bloo2 is not None:
+        b = np.asarray(bloo2, dtype=np.uint8).reshape(-1)
+        n_blocks = -(-b.size // DUMP_BLOOM_BLOCK)
+        pop = np.zeros(n_blocks, dtype=np.float32)
+        chunk = DUMP_BLOOM_BLOCK * 65536
+        for lo in range(0, b.size, chunk):
+            part = b[lo:lo + chunk]
+            full = part.size // DUMP_BLOOM_BLOCK * DUMP_BLOOM_BLOCK
+            counts = np.bitwise_count(part)
+            i0 = lo // DUMP_BLOOM_BLOCK
+            pop[i0:i0 + full // DUMP_BLOOM_BLOCK] = counts[:full].reshape(-1, DUMP_BLOOM_BLOCK).sum(axis=1)
+            if full < part.size:                          # a last, shorter block
+                pop[i0 + full // DUMP_BLOOM_BLOCK] = counts[full:].sum()
+        save("bloo2_block_popcount", pop)
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, b.size, min(DUMP_BLOOM_BYTES, b.size)))
+        save("bloo2_sample_bytes", b[pos].astype(np.float32))
+    if keys is not None:
+        keys = np.asarray(keys, dtype=np.uint64)
+        n = keys.size
+        idx = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(n, DUMP_JUNCTIONS, replace=False)) if n > DUMP_JUNCTIONS else slice(None)
+        k = keys[idx]
+        save("junction_keys", np.stack([(k >> np.uint64(32)).astype(np.float64), (k & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1))
+        r = np.asarray(recs)[idx]
+        save("junction_records", np.concatenate([r["cov"], r["dist"], r["linked"]], axis=1).astype(np.float32))
 
 
 # ---------------------------------------------------------------------------------------------- CPU legs (oracle)
@@ -588,7 +647,16 @@ def main():
     ap.add_argument("--cpu-workers", type=int, default=0, help="replicas of the all-cores CPU leg (0 = min(host cores, 16))")
     ap.add_argument("--no-profile", action="store_true",
                     help="timed steps WITHOUT HIP events around every kernel (A/B of what FGPU_FLAG_PROFILE costs; no roofline / kernel times in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: bracketed steps (kernel times, roofline), CPU baselines, ceilings, the host-input / Stage 3 / "
+                         "command-line legs, configs 3, 5 and 4 at full size, the digest checks of --scaling strong (the --no-* options drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:       # a plain run: set-up, warm-up, the timed steps and the line -- every other leg is --full's
+        args.no_cpu = args.no_ceilings = args.no_host_leg = args.no_full_size = args.no_profile = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))
@@ -707,9 +775,12 @@ def main():
     kmers_local = lst["kmers"]
     stage_ms = sharded.CLOCK.report() if (world > 1 or force_sharded) else None      # this rank's stages of the last timed step
     sharded.CLOCK.enable(False)
+    # (before anything else runs: the outputs are views of the context's page-locked buffers, which the next step writes again)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lst, sst, bloo2, keys, recs, rank, world)
     # ---- did the sharded run produce the sequential run's outputs?  (strong scaling on the fixture's reads: digests of tests/golden/fullsize.json)
     checks = None
-    if strong:
+    if strong and args.full:
         import hashlib
         mine = {}
         if bloo2 is not None:          # (rank 0 holds pass 1's output, the last rank pass 2's)

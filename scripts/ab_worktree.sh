@@ -4,6 +4,7 @@
 #   afterwards:                    git worktree remove --force ab_old
 #   full-size legs included: configs 2, 5, 4 and the CLI legs from one bench run each
 root=${GRAFT_REPO_ROOT:-$(pwd)}
+out=${1:-$(mktemp -d)}      # where the bench lines are kept (first argument; a new temporary folder by default)
 show() {
 python3 -c "
 import json,sys
@@ -20,7 +21,8 @@ print(' | '.join(o))
 for i in 1 2; do
   for t in new old; do
     d=$root; [ $t = old ] && d=$root/ab_old
-    (cd $d && python3 bench.py --no-cpu > $root/gpurun_out/ab_$t$i.json 2> /dev/null)
-    show $root/gpurun_out/ab_$t$i.json "$t run $i"
+    full=; grep -q -- '"--full"' $d/bench.py && full=--full      # (a tree from before --full runs every leg without it)
+    (cd $d && python3 bench.py $full --no-cpu > $out/ab_$t$i.json 2> /dev/null)
+    show $out/ab_$t$i.json "$t run $i"
   done
 done

@@ -4,7 +4,7 @@ out=gpurun_out/$1; shift
 mkdir -p $out
 for v in "$@"; do
   name=$(echo "$v" | tr ' =-' '___')
-  timeout -k 10 200 python bench.py --steps 5 --warmup 2 --no-cpu --no-ceilings --no-host-leg $v > $out/$name.json 2> $out/$name.err || echo "FAILED $v"
+  timeout -k 10 200 python bench.py --full --steps 5 --warmup 2 --no-cpu --no-ceilings --no-host-leg $v > $out/$name.json 2> $out/$name.err || echo "FAILED $v"
   python - "$out/$name.json" "$v" <<'PY'
 import json, sys
 try:

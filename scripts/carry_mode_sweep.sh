@@ -4,7 +4,7 @@ run() { # name, extra bench args...
   for mode in set sweep; do
     for ratio in 1/1 1/2; do
       if [ $mode = set ] && [ $ratio != 1/1 ]; then continue; fi
-      FGPU_CARRY_MODE=$mode FGPU_SWEEP_RATIO=$ratio timeout -k 10 300 python bench.py "$@" --steps 1 --warmup 1 --no-cpu --no-ceilings --no-host-leg > /tmp/cs.json 2>/dev/null
+      FGPU_CARRY_MODE=$mode FGPU_SWEEP_RATIO=$ratio timeout -k 10 300 python bench.py --full "$@" --steps 1 --warmup 1 --no-cpu --no-ceilings --no-host-leg > /tmp/cs.json 2>/dev/null
       python - <<PY
 import json
 d = json.loads(open("/tmp/cs.json").read().strip().splitlines()[-1]); k = d["kernel_ms_per_step_rank0"]

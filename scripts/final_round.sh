@@ -7,7 +7,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/final_$tag
 mkdir -p "$out"
 cd "$root"
-python3 bench.py --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err" || { tail -5 "$out/bench.err"; exit 1; }
+python3 bench.py --full --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err" || { tail -5 "$out/bench.err"; exit 1; }
 echo "bench: $(cut -c1-200 "$out/bench.json")"
 bash scripts/profile_round.sh "$tag" > "$out/profile_round.log" 2>&1 || { tail -5 "$out/profile_round.log"; exit 1; }
 echo "profiles done"

@@ -4,7 +4,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 args="--reads 50000000 --read-len 150 --genome 150000000 --estimated-kmers 2000000000 --singletons 1000000000 --err 0.05 --batch-reads 2000000 --steps 1 --warmup 1 --no-cpu --no-ceilings --no-host-leg"
 one() {
-  env "$@" timeout -k 10 200 python bench.py $args > /tmp/ks.json 2>/dev/null
+  env "$@" timeout -k 10 200 python bench.py --full $args > /tmp/ks.json 2>/dev/null
   python - "$*" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ks.json").read().strip().splitlines()[-1]); k = d["kernel_ms_per_step_rank0"]

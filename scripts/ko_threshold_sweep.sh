@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 for t in off 64 32 16 8; do
   if [ $t = off ]; then env="FGPU_WALK_KO=0"; else env="FGPU_WALK_KO=$t FGPU_WALK_KO_ALWAYS=1"; fi
-  env $env timeout -k 10 200 python bench.py --steps 5 --warmup 2 --no-cpu --no-ceilings --no-host-leg > /tmp/ko_$t.json 2>/dev/null
+  env $env timeout -k 10 200 python bench.py --full --steps 5 --warmup 2 --no-cpu --no-ceilings --no-host-leg > /tmp/ko_$t.json 2>/dev/null
   python - <<PY
 import json
 d = json.loads(open("/tmp/ko_$t.json").read().strip().splitlines()[-1])

@@ -33,7 +33,7 @@ run_c3 FGPU_OVW_FOLLOWERS=0 FGPU_WALK_KO_AVG=8 FGPU_WALK_KO_AVG_MIN=16
 run_c3 FGPU_WALK_KO=8 FGPU_WALK_KO_WEIGHT=32
 rm -f /dev/shm/c3_reads.fq /dev/shm/c3_out.* /dev/shm/c3_args.txt
 for v in "FGPU_WALK_KO=32 FGPU_WALK_KO_ALWAYS=1 FGPU_WALK_KO_WEIGHT=128" "FGPU_WALK_KO=32 FGPU_WALK_KO_ALWAYS=1 FGPU_WALK_KO_WEIGHT=128 FGPU_WALK_KO_AVG=8 FGPU_WALK_KO_AVG_MIN=16" "FGPU_WALK_KO=32 FGPU_WALK_KO_ALWAYS=1 FGPU_WALK_KO_WEIGHT=128 FGPU_WALK_KO_AVG=6 FGPU_WALK_KO_AVG_MIN=12"; do
-  env $v python3 bench.py --steps 10 --warmup 3 --no-cpu --no-ceilings --no-host-leg --no-full-size > /tmp/b.json 2> /tmp/b.err
+  env $v python3 bench.py --full --steps 10 --warmup 3 --no-cpu --no-ceilings --no-host-leg --no-full-size > /tmp/b.json 2> /tmp/b.err
   python3 - "$v" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/b.json").read().strip().splitlines()[-1])

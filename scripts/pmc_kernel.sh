@@ -8,8 +8,8 @@ out=$root/gpurun_out/pmc_$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --kernel-include-regex "$regex" --output-format csv -d "$out/sq1" -o run -- python3 "$root/bench.py" --steps 1 --warmup 0 --no-cpu --no-ceilings > "$out/b1.json" 2> "$out/b1.err"
-rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_FLAT SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_THREAD_CYCLES_VALU SQ_INSTS_LDS --kernel-include-regex "$regex" --output-format csv -d "$out/sq2" -o run -- python3 "$root/bench.py" --steps 1 --warmup 0 --no-cpu --no-ceilings > "$out/b2.json" 2> "$out/b2.err"
+rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --kernel-include-regex "$regex" --output-format csv -d "$out/sq1" -o run -- python3 "$root/bench.py" --full --steps 1 --warmup 0 --no-cpu --no-ceilings > "$out/b1.json" 2> "$out/b1.err"
+rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_FLAT SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_THREAD_CYCLES_VALU SQ_INSTS_LDS --kernel-include-regex "$regex" --output-format csv -d "$out/sq2" -o run -- python3 "$root/bench.py" --full --steps 1 --warmup 0 --no-cpu --no-ceilings > "$out/b2.json" 2> "$out/b2.err"
 find "$out" \( -name "*.db" \) -delete
 python3 - "$out" <<'PY'
 import csv, glob, os, sys

@@ -24,8 +24,8 @@ done
 # the product kernel: config 2 (2 GiB of first-set times) and config 4's per-GPU shape (25 M reads, 2^33-bit filters: 32 GiB of times)
 i=0
 for s in "${sets[@]:0:4}"; do
-  rocprofv3 --pmc $s --kernel-include-regex "k_load_mark" --output-format csv -d "$out/c2_$i" -o run -- python3 "$root/bench.py" --steps 1 --warmup 0 --no-cpu --no-ceilings --no-host-leg > "$out/c2_$i.json" 2> "$out/c2_$i.err" || echo "c2 set $i failed"
-  rocprofv3 --pmc $s --kernel-include-regex "k_load_mark" --output-format csv -d "$out/c4_$i" -o run -- python3 "$root/bench.py" --reads 25000000 --genome 400000000 --estimated-kmers 1000000000 --singletons 200000000 --batch-reads 2500000 --steps 1 --warmup 0 --no-cpu --no-ceilings --no-host-leg > "$out/c4_$i.json" 2> "$out/c4_$i.err" || echo "c4 set $i failed"
+  rocprofv3 --pmc $s --kernel-include-regex "k_load_mark" --output-format csv -d "$out/c2_$i" -o run -- python3 "$root/bench.py" --full --steps 1 --warmup 0 --no-cpu --no-ceilings --no-host-leg > "$out/c2_$i.json" 2> "$out/c2_$i.err" || echo "c2 set $i failed"
+  rocprofv3 --pmc $s --kernel-include-regex "k_load_mark" --output-format csv -d "$out/c4_$i" -o run -- python3 "$root/bench.py" --full --reads 25000000 --genome 400000000 --estimated-kmers 1000000000 --singletons 200000000 --batch-reads 2500000 --steps 1 --warmup 0 --no-cpu --no-ceilings --no-host-leg > "$out/c4_$i.json" 2> "$out/c4_$i.err" || echo "c4 set $i failed"
   i=$((i+1))
 done
 find "$out" \( -name "*.db" \) -delete

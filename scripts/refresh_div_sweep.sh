@@ -4,7 +4,7 @@
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 for d in ${DIVS:-4 16 48 128}; do
   echo "=== FGPU_REFRESH_DIV=$d"
-  FGPU_REFRESH_DIV=$d python3 "$root/bench.py" --steps 10 --warmup 3 --no-cpu --no-host-leg --no-ceilings --no-full-size | python3 -c "
+  FGPU_REFRESH_DIV=$d python3 "$root/bench.py" --full --steps 10 --warmup 3 --no-cpu --no-host-leg --no-ceilings --no-full-size | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_ms_per_step_rank0']
 print('config 2: step', round(d['ms_per_step'],2), 'ms; walk_stage', k.get('walk_stage'), 'need_lookup', k.get('need_lookup'))"

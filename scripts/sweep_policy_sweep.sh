@@ -5,7 +5,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 run() {
   echo "=== $*"
   env "$@" python3 "$root/scripts/shard_load_times.py" 8 2>/dev/null | grep "own load with shard times run 1\|load keep_carry=False run 2" | cut -c1-200
-  env "$@" python3 "$root/bench.py" --steps 10 --warmup 3 --no-cpu --no-host-leg --no-ceilings --no-full-size | python3 -c "
+  env "$@" python3 "$root/bench.py" --full --steps 10 --warmup 3 --no-cpu --no-host-leg --no-ceilings --no-full-size | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_ms_per_step_rank0']
 print('config 2: step', round(d['ms_per_step'],2), 'ms; load_mark', k.get('load_mark'), 'carry_update', k.get('carry_update'), 'load_resolve', k.get('load_resolve'))"

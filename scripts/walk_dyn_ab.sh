@@ -6,7 +6,7 @@ cd $root
 c4="--reads 25000000 --genome 400000000 --estimated-kmers 1000000000 --singletons 200000000 --batch-reads 2500000"
 for v in "FGPU_WALK_STATIC=1" "FGPU_X=0" "FGPU_WALK_DYN_GRID=1024" "FGPU_WALK_DYN_GRID=4096"; do
   for shape in "" "$c4"; do
-    env $v FGPU_PROFILE_WALK=1 python3 bench.py --steps 6 --warmup 2 --no-cpu --no-ceilings --no-host-leg --no-full-size $shape > /tmp/b.json 2> /tmp/b.err
+    env $v FGPU_PROFILE_WALK=1 python3 bench.py --full --steps 6 --warmup 2 --no-cpu --no-ceilings --no-host-leg --no-full-size $shape > /tmp/b.json 2> /tmp/b.err
     python3 - "$v" "$shape" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/b.json").read().strip().splitlines()[-1])

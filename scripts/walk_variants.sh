@@ -4,7 +4,7 @@ out=gpurun_out/$1; shift
 mkdir -p $out
 for v in "$@"; do
   name=$(echo "$v" | tr ' =' '__')
-  env $v FGPU_NO_OVERLAP=1 timeout -k 10 200 python bench.py --profile-walk --steps 3 --warmup 1 --no-cpu --no-ceilings > $out/$name.json 2> $out/$name.err || echo "FAILED $v"
+  env $v FGPU_NO_OVERLAP=1 timeout -k 10 200 python bench.py --full --profile-walk --steps 3 --warmup 1 --no-cpu --no-ceilings > $out/$name.json 2> $out/$name.err || echo "FAILED $v"
   python - "$out/$name.json" "$v" <<'PY'
 import json, sys
 try:

@@ -57,12 +57,17 @@ def test_committed_bench_line_has_the_contract_keys():
     assert abs(d["value"] - d["kmers_per_step"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
 
 
-def test_batch_bounds_cover_the_reads_once_in_order():
-    """bench.py's batching (host logic): contiguous, complete, in file order; the ramp starts and ends small"""
+def _bench_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
+    return bench
+
+
+def test_batch_bounds_cover_the_reads_once_in_order():
+    """bench.py's batching (host logic): contiguous, complete, in file order; the ramp starts and ends small"""
+    bench = _bench_module()
     for n, batch, ramp in ((10_000_000, 1_000_000, 2), (10_000_000, 1_000_000, 0), (10_000_003, 1_000_000, 3), (3_000_000, 1_000_000, 2),
                            (999, 1000, 2), (25_000_000, 1_000_000, 5), (7, 2, 1)):
         b = bench.batch_bounds(n, batch, ramp)
@@ -70,6 +75,50 @@ def test_batch_bounds_cover_the_reads_once_in_order():
         assert max(hi - lo for lo, hi in b) <= batch
     sizes = [hi - lo for lo, hi in bench.batch_bounds(10_000_000, 1_000_000, 2)]
     assert sizes[:3] == [250_000, 250_000, 500_000] and sizes[-2:] == [500_000, 250_000] and sizes.count(1_000_000) == 8
+
+
+def test_dump_outputs_are_exact_floats_under_64_mb(tmp_path):
+    """bench.py --dump-outputs on outputs of config 2's size (64 MiB bloo2, a million junctions): float32 / float64 files under 64 MB in
+    all that give back the integers exactly, the same sample on every call"""
+    import numpy as np
+    from faucet_amd import api
+    bench = _bench_module()
+    rng = np.random.default_rng(5)
+    bloo2 = rng.integers(0, 256, 64 << 20, dtype=np.uint8)
+    n = 1_000_003
+    keys = rng.integers(0, 1 << 62, n, dtype=np.uint64)
+    recs = np.zeros(n, dtype=api.JUNC_DTYPE)
+    for f, w in (("cov", 4), ("dist", 5), ("linked", 5)):
+        recs[f] = rng.integers(0, 256, (n, w), dtype=np.uint8)
+    lst = {c: 10 ** 9 + i for i, c in enumerate(bench.LOAD_COUNTERS)}
+    sst = {c: 2 ** 40 + i for i, c in enumerate(bench.SCAN_COUNTERS)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), lst, sst, bloo2, keys, recs, 0, 1)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(["load_counters.npy", "scan_counters.npy", "bloo2_block_popcount.npy", "bloo2_sample_bytes.npy",
+                            "junction_keys.npy", "junction_records.npy"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 * 10 ** 6
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert np.load(tmp_path / "b" / f).tobytes() == got[f[:-4]].tobytes(), f
+        assert got[f[:-4]].dtype in (np.float32, np.float64), f
+    assert got["load_counters"].tolist() == [lst[c] for c in bench.LOAD_COUNTERS]
+    assert got["scan_counters"].tolist() == [sst[c] for c in bench.SCAN_COUNTERS]
+    pop = got["bloo2_block_popcount"]
+    assert pop.size == bloo2.size // bench.DUMP_BLOOM_BLOCK and pop.sum(dtype=np.float64) == np.unpackbits(bloo2).sum()
+    assert pop[7] == np.unpackbits(bloo2[7 * bench.DUMP_BLOOM_BLOCK:8 * bench.DUMP_BLOOM_BLOCK]).sum()
+    k = got["junction_keys"]
+    assert k.shape == (bench.DUMP_JUNCTIONS, 2)
+    back = k[:, 0].astype(np.uint64) << np.uint64(32) | k[:, 1].astype(np.uint64)
+    pos = np.searchsorted(keys, back, sorter=np.argsort(keys))
+    idx = np.argsort(keys)[pos]
+    assert np.array_equal(keys[idx], back) and np.all(np.diff(idx) > 0)          # a sample of the keys, creation order kept
+    r = got["junction_records"]
+    assert r.shape == (bench.DUMP_JUNCTIONS, 14) and np.array_equal(r[:, 4:9], recs["dist"][idx].astype(np.float32))
+    # few junctions: all of them; a filter that is not a whole number of blocks: the last block is counted too
+    bench.dump_outputs(str(tmp_path / "c"), lst, sst, bloo2[:5000], keys[:10], recs[:10], 0, 1)
+    assert np.array_equal(np.load(tmp_path / "c" / "junction_keys.npy")[:, 1], (keys[:10] & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    assert np.load(tmp_path / "c" / "bloo2_block_popcount.npy").sum() == np.unpackbits(bloo2[:5000]).sum()
 
 
 def test_design_md_quotes_the_committed_bench_line():

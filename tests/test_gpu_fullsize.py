@@ -294,7 +294,7 @@ def test_bench_sharded_path_over_rccl_gives_config2s_digests():
     mode on BASELINE config 2's fixture reads: bloo2, the junction keys in creation order, the records and the scan's counters equal the
     oracle's digests in tests/golden/fullsize.json."""
     d = _bench_line(["--scaling", "strong", "--fixture", "config2", "--batch-reads", "1000000", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-ceilings",
-                     "--no-host-leg", "--no-full-size", "--no-profile"], {"FAUCET_FORCE_SHARDED": "1"})
+                     "--no-host-leg", "--no-full-size", "--no-profile", "--full"], {"FAUCET_FORCE_SHARDED": "1"})
     assert d["n_gpus"] == 1 and d["scaling"] == "strong" and d["kmers_per_step"] == FULL["config2"]["kmers"]
     assert d["rccl_ranks"] == 1 and d["dist_backend"] == "nccl" and d["hbm_per_rank"][0]["used_bytes_after_the_steps"] > 0
     chk = d["outputs_check"]
@@ -309,7 +309,7 @@ def test_bench_strong_scaling_three_ranks_equal_one():
     size: three ranks in separate processes sharing this GPU (gloo as the transport) give the digests of the one-GPU run of the same reads --
     bloo2, junction keys in creation order, records -- and report every rank's stage times."""
     size = ["--scaling", "strong", "--fixture", "config2", "--reads", "3000000", "--genome", "6000000", "--estimated-kmers", "30000000", "--singletons", "6000000",
-            "--batch-reads", "250000", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-ceilings", "--no-host-leg", "--no-full-size", "--no-profile"]
+            "--batch-reads", "250000", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-ceilings", "--no-host-leg", "--no-full-size", "--no-profile", "--full"]
     one = _bench_line(size, {})
     # (round 6) started the way the driver starts N = 1: no launcher around it -- the parent spawns its ranks before any GPU call
     three = _bench_line(size, {"FAUCET_SHARE_GPU": "1", "FAUCET_DIST_BACKEND": "gloo", "GLOO_SOCKET_IFNAME": "lo"}, self_launch=3)
@@ -328,7 +328,7 @@ def test_bench_falls_back_to_gloo_when_the_run_over_rccl_fails():
     comes up: the parent's limit ends that) -- and the parent runs the same pipeline over gloo, says so in the line, and the outputs are the
     one-GPU run's."""
     size = ["--scaling", "strong", "--fixture", "config2", "--reads", "2000000", "--genome", "4000000", "--estimated-kmers", "20000000", "--singletons", "4000000",
-            "--batch-reads", "250000", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-ceilings", "--no-host-leg", "--no-full-size", "--no-profile"]
+            "--batch-reads", "250000", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-ceilings", "--no-host-leg", "--no-full-size", "--no-profile", "--full"]
     one = _bench_line(size, {})
     two = _bench_line(size, {"FAUCET_SHARE_GPU": "1", "GLOO_SOCKET_IFNAME": "lo", "FAUCET_BENCH_RANKS_TIMEOUT": "120"}, self_launch=2)
     assert two["n_gpus"] == 2 and two["dist_backend"] == "gloo" and two["rccl_ranks"] == 0
