@@ -345,7 +345,7 @@ class Context:
         """scanInputRead's lists of the next scanned batch: (batch number, structured array) or None when none is left"""
         n, seq = C.c_uint64(0), C.c_int64(0)
         rc = self.lib.fgpu_scan_take_stops(self.h, None, 0, C.byref(n), C.byref(seq))
-        if rc not in (L.OK, L.ERR_CAPACITY):
+        if rc not in (L.OK, L.ERR_CAPACITY) or (rc == L.ERR_CAPACITY and seq.value < 0):     # (no batch: the junction table is full)
             self._c(rc)
         if seq.value < 0:
             return None

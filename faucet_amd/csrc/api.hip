@@ -110,11 +110,11 @@ static int check_errors(fgpu_ctx* ctx) {
         // A batch created more records than the table had room for (it is kept below a quarter full BETWEEN batches).  While the scan's batches
         // are all in the journal the library absorbs that itself (round 6): the next entry point scans the journal again
         // on a table four times the size (scan_replay) -- the reference's unordered_map simply grows (utils/JunctionMap.h:61).
-        if (ctx->journal_on && ctx->phase == 2 && !ctx->in_replay && ctx->jcap < (1ULL << 31)) {
+        if (fgpu_overflow_absorbable(ctx)) {
             ctx->lazy_failed = ctx->capacity_failed = true;
             return FGPU_OK;
         }
-        ctx->err = "junction table full: raise fgpu_params.junction_capacity";
+        ctx->err = FGPU_TABLE_FULL_MSG;
         return FGPU_ERR_CAPACITY;
     }
     if (ctx->counters_host->error_flags & 2ULL) { ctx->err = "window table full"; return FGPU_ERR_CAPACITY; }
@@ -872,7 +872,8 @@ static int scan_replay(fgpu_ctx* ctx) {
         }
         int rc = scan_replay_once(ctx);
         // the replay itself ran out of room (its batches are walked with the table kept below a quarter full between them, so this takes a
-        // single batch that creates more than three times what the whole table held): once more, larger again
+        // single batch that creates more than three times what the whole table held): once more, larger again.  (Noticed at the end of the
+        // replay or where it harvests the lists of a batch it has walked: fgpu_scan_harvest applies none of them once the flag is up.)
         if (rc == FGPU_ERR_CAPACITY && (ctx->counters_host->error_flags & 1ULL) && ctx->jcap < (1ULL << 31) && attempt < 6) {
             ctx->capacity_failed = true;
             continue;
@@ -940,7 +941,10 @@ static int scan_replay_once(fgpu_ctx* ctx) {
     for (size_t i = 0; i < ctx->journal.size() && !rc; i++) {
         JournalBatch* j = ctx->journal[i];
         BatchBufs* b = acquire_batch(ctx);
-        if (b->stops_pending && (rc = fgpu_scan_harvest(ctx, b))) break;   // lists of the replayed batch these buffers held two batches ago
+        if (b->stops_pending && (rc = fgpu_scan_harvest(ctx, b))) {   // lists of the replayed batch these buffers held two batches ago
+            ctx->pool.push_back(b);      // (FGPU_ERR_CAPACITY: a walk of this replay outgrew the table -- nothing of it applied; scan_replay goes again)
+            break;
+        }
         if (b->walk_pending) {
             FGPU_HIP(fgpu_sync_event(ctx, b->walk_done));
             b->walk_pending = false;

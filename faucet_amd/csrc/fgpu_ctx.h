@@ -468,6 +468,13 @@ static inline unsigned fgpu_grid(uint64_t n, unsigned per_block) {
     return (unsigned)(b < FGPU_GRID_BLOCKS ? (b ? b : 1) : FGPU_GRID_BLOCKS);
 }
 
+// A walk outgrew the junction table (error bit 1): can the library absorb it (scan the journal again on a table four times the size,
+// scan_replay) or is it the caller's FGPU_ERR_CAPACITY?  One rule for the synchronising calls (check_errors) and for fgpu_scan_harvest.
+static inline bool fgpu_overflow_absorbable(const fgpu_ctx* ctx) {
+    return ctx->journal_on && ctx->phase == 2 && !ctx->in_replay && ctx->jcap < (1ULL << 31);
+}
+#define FGPU_TABLE_FULL_MSG "junction table full: raise fgpu_params.junction_capacity"
+
 // stage entry points implemented in the .hip files
 int fgpu_text_streams(fgpu_ctx* ctx);
 void fgpu_touch_load();

@@ -3767,8 +3767,18 @@ int fgpu_scan_harvest(fgpu_ctx* ctx, BatchBufs* b) {
         FGPU_HIP(hipMemcpyAsync(&ctx->fb_host[4], count_c + np_count - 1, 4, hipMemcpyDeviceToHost, ctx->stream));
         FGPU_HIP(hipMemcpyAsync(&ctx->fb_host[5], offset_c + np_count - 1, 4, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (check) FGPU_HIP(hipMemcpyAsync(&ctx->counters_host->error_flags, &ctx->counters->error_flags, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (np_count || check) FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    // (the flags always: the one synchronisation is there anyway whenever the batch has pieces)
+    FGPU_HIP(hipMemcpyAsync(&ctx->counters_host->error_flags, &ctx->counters->error_flags, 8, hipMemcpyDeviceToHost, ctx->stream));
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    if (ctx->counters_host->error_flags & 1ULL) {
+        // A walk up to this one outgrew the junction table and dropped records: these lists are wrong, and nothing of them may reach the
+        // caller or a pair filter.  The flag is cumulative, so a clean one here means every walk up to this batch was good.
+        // Absorbable: replayed on a larger table first (as check_errors decides); inside a replay: scan_replay grows the table and goes again.
+        ctx->to_harvest.insert(ctx->to_harvest.begin(), b);
+        if (fgpu_overflow_absorbable(ctx)) { ctx->lazy_failed = ctx->capacity_failed = true; return FGPU_INTERNAL_REPLAY; }
+        ctx->err = FGPU_TABLE_FULL_MSG;
+        return FGPU_ERR_CAPACITY;
+    }
     if (check && (ctx->counters_host->error_flags & 4ULL)) { ctx->lazy_failed = true; ctx->to_harvest.insert(ctx->to_harvest.begin(), b); return FGPU_INTERNAL_REPLAY; }
     b->stops_pending = false;
     if (b->seq < ctx->stops_delivered) return FGPU_OK;   // scanned again by a replay: the caller has this batch's lists already

@@ -838,7 +838,7 @@ int main(int argc, char** argv) {
                     uint64_t n_stops = 0;
                     int64_t seq = -1;
                     int trc = fgpu_scan_take_stops(ctx, stops.data(), stops.size(), &n_stops, &seq);
-                    if (trc == FGPU_ERR_CAPACITY) { stops.resize((size_t)(n_stops + n_stops / 4 + 16)); continue; }
+                    if (trc == FGPU_ERR_CAPACITY && seq >= 0) { stops.resize((size_t)(n_stops + n_stops / 4 + 16)); continue; }
                     if (trc != FGPU_OK) return failed("fgpu_scan_take_stops", trc);
                     if (seq < 0) return 0;
                     hlp.batch(stops.data(), n_stops, batch_reads[(size_t)seq]);

@@ -56,7 +56,9 @@ typedef struct {
                                  * it is absorbed by the library while the scan's batches are in its journal (see fgpu_scan_set_eager:
                                  * the journal is scanned again on a table four times the size; fgpu_diag_scan_replays counts it); only a
                                  * scan without a journal -- FGPU_FLAG_EAGER_FLAGS, fgpu_scan_set_eager(1), or beyond the journal's
-                                 * budget of an eighth of the device memory -- ends with FGPU_ERR_CAPACITY there. */
+                                 * budget of an eighth of the device memory -- ends with FGPU_ERR_CAPACITY there.  Either way no list
+                                 * of a walk that overflowed reaches fgpu_scan_take_stops or a pair filter: the replay comes first, or
+                                 * the call that would have handed them out returns FGPU_ERR_CAPACITY. */
     uint64_t max_batch_bases;   /* largest batch (bases + one separator per read); 0 = default 2^30 */
     void*    stream;            /* hipStream_t to run on, or NULL for a private stream */
     uint64_t walk_window_span;  /* stream positions per scheduling window of the ordered walk; 0 = adaptive.
@@ -294,7 +296,8 @@ int fgpu_scan_long_pairs_download(fgpu_ctx* ctx, uint8_t* out, uint64_t n_bytes,
  * one per call: *batch_seq = number of the batch within the scan, or -1 (and *n_out = 0) when none is left.  The
  * call waits for the ordered walk of that batch only, so calling it once after every fgpu_scan_batch (it then returns
  * the previous batch) keeps the walk of the newest batch overlapped; after fgpu_scan_end call it until -1.
- * FGPU_ERR_CAPACITY: *n_out = elements needed, nothing consumed. */
+ * FGPU_ERR_CAPACITY with *batch_seq >= 0: *n_out = elements needed, nothing consumed; with *batch_seq = -1: the junction table is full
+ * (a walk outgrew it where the library cannot absorb that, see fgpu_params.junction_capacity) and no list of the scan is handed out. */
 int fgpu_scan_take_stops(fgpu_ctx* ctx, fgpu_stop* out, uint64_t cap, uint64_t* n_out, int64_t* batch_seq);
 /* Junction map after the scan, in CREATION order (inserting the records in this order into a
  * std::unordered_map<kmer_type,Junction> reproduces the reference's dump order,

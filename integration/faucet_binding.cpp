@@ -245,7 +245,7 @@ void gpu_scan_paired(JunctionMap* junctionMap, std::string read_scan_file, bool 
                 uint64_t n_stops = 0;
                 int64_t seq = -1;
                 const int trc = fgpu_scan_take_stops(g_ctx, stops.data(), stops.size(), &n_stops, &seq);
-                if (trc == FGPU_ERR_CAPACITY) { stops.resize((size_t)(n_stops + n_stops / 4 + 16)); continue; }
+                if (trc == FGPU_ERR_CAPACITY && seq >= 0) { stops.resize((size_t)(n_stops + n_stops / 4 + 16)); continue; }
                 if (trc != FGPU_OK || seq < 0) return trc;
                 hlp.batch(stops.data(), n_stops, batch_reads[(size_t)seq]);
                 if (!all) return FGPU_OK;

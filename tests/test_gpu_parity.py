@@ -1550,7 +1550,8 @@ def test_junction_table_grows_between_batches():
 def test_a_batch_that_outgrows_the_junction_table_is_absorbed():
     """VERDICT r5 item 6a.  One batch, far more records than slots (utils/JunctionMap.h:61: the reference's unordered_map just grows): the library
     scans its journal again on a larger table -- twice here, 2^12 -> 2^14 -> 2^16 slots for ~10^4 records -- and the caller sees an ordinary scan with the
-    oracle's map.  Also with the overflow in a LATER batch (the batches before it are replayed with it), with lists recorded, and -- no journal:
+    oracle's map.  Also with the overflow in a LATER batch (the batches before it are replayed with it), with lists recorded (the oracle's
+    lists, also when taken after every batch: none from a walk that overflowed), and -- no journal:
     eager flags -- still the prompt FGPU_ERR_CAPACITY with the advice, not a crawl through a saturated table."""
     k, bases, offs, tai, nh = _saturated_filter_case(30_000, 78)
     b1, b2 = po.Bloom(tai, nh), po.Bloom(tai, nh)
@@ -1560,13 +1561,20 @@ def test_a_batch_that_outgrows_the_junction_table_is_absorbed():
     okeys, orecs = osc.junctions("creation")
     ost = osc.stats()
     assert len(okeys) > 4 * (1 << 12)
-    for n_batches, record_stops in ((1, False), (3, False), (2, True)):
+    _, want = _oracle_lists(bases, offs, k, 1, 100, b2.bits(), tai, nh)
+    # (3, True, True): lists taken after every batch -- the first batch's walk overflows, and its lists are asked for while its flag is up
+    for n_batches, record_stops, take_during in ((1, False, False), (3, False, False), (2, True, False), (3, True, True)):
         ctx = api.Context(k, tai, nh, junction_capacity=1 << 12, record_stops=record_stops)
         batches = chunks(bases, offs, n_batches)
         api.load_two_filters(api.Bloom(ctx, L.BLOO1), api.Bloom(ctx, L.BLOO2), batches)
         ctx.scan_begin()
+        taken = []
         for b in batches:
             ctx.scan_batch(b)
+            if take_during:
+                t = ctx.take_stops()
+                if t is not None:
+                    taken.append(t)
         sst = ctx.scan_end()
         keys, recs = ctx.junctions()
         assert np.array_equal(keys, okeys) and np.array_equal(recs["dist"], orecs["dist"]) and np.array_equal(recs["cov"], orecs["cov"]) and \
@@ -1574,14 +1582,21 @@ def test_a_batch_that_outgrows_the_junction_table_is_absorbed():
         for key in ("n_junctions", "nb_jcheck_kmer", "nb_no_juncs", "nb_processed", "nb_skipped", "reads_no_errors", "reads_processed"):
             assert int(sst[key]) == int(ost[key]), (key, n_batches)
         assert ctx.diag_scan_replays() >= 1
-        if record_stops:      # every batch's lists exactly once, whatever was scanned twice
-            seen = []
+        if record_stops:      # every batch's lists exactly once, whatever was scanned twice -- and the oracle's lists
             while True:
                 t = ctx.take_stops()
                 if t is None:
                     break
-                seen.append(t[0])
+                taken.append(t)
+            seen = [seq for seq, _ in taken]
             assert seen == list(range(n_batches))
+            got = []
+            for seq, st in taken:
+                lists = [[] for _ in range(batches[seq].n_reads)]
+                for e in st:
+                    lists[int(e["read"])].append(int(e["ext"]))
+                got.extend(lists)
+            assert got == want, (n_batches, take_during)
         ctx.close()
     ctx = api.Context(k, tai, nh, junction_capacity=1 << 12, eager_flags=True)
     batch = chunks(bases, offs, 1)
