@@ -226,6 +226,49 @@ int main(int argc, char** argv) {
                    (unsigned long long)E, (unsigned long long)S, (double)fp, p1, (unsigned long long)tai, nh_eff);
         }
     }
+    /* ---- sizing past four hash functions: small -fp from reads (p1 path) and on a -bloom_file restart (create_bloom_filter_optimal(E, fp)),
+     *      5..10 hash functions and the wrap to the default 4 beyond 10 (utils/Bloom.cpp:229-247); kinds of their own, after the rows above ---- */
+    {
+        struct C { uint64_t e, s; float fp; };
+        C cs[] = {{100000, 20000, .006f}, {100000, 20000, .0036f}, {100000, 20000, .0015f}, {100000, 20000, .0006f}, {100000, 20000, .00025f},
+                  {100000, 20000, .0001f}, {100000, 20000, .00004f}, {10000000, 2000000, .0015f}, {1000000, 200000, .0001f},
+                  {100000, 95000, .04f}, {1000000, 950000, .04f}};
+        float restart[] = {.04f, .01f, .005f, .002f, .001f, .0005f, .0002f, .00005f};
+        fflush(stdout);
+        FILE* sav = stdout;
+        stdout = fopen("/dev/null", "w");
+        std::streambuf* cb = std::cout.rdbuf();
+        std::cout.rdbuf(nullptr);
+        std::vector<std::string> rows;
+        char line[512];
+        for (auto& c : cs) {
+            estimated_kmers = c.e;
+            singletons = c.s;
+            fpRate = c.fp;
+            std::function<double(double)> f = my_func;
+            double p1 = brents_fun(f, c.fp, 0.50, 0.0001, 1000);
+            Bloom* b = nullptr;
+            b = b->create_bloom_filter_optimal(c.e, p1);
+            snprintf(line, sizeof line, "{\"kat\":\"sizing_fp\",\"E\":%llu,\"S\":%llu,\"fp\":%.9g,\"p1\":%.17g,\"tai\":%llu,\"n_hash\":%d}\n",
+                     (unsigned long long)c.e, (unsigned long long)c.s, (double)c.fp, p1, (unsigned long long)b->tai, b->getNumHash());
+            rows.push_back(line);
+            delete b;
+        }
+        for (uint64_t E : {200000ULL, 100000000ULL}) {
+            for (float fp : restart) {
+                Bloom* b = nullptr;
+                b = b->create_bloom_filter_optimal(E, fp);
+                snprintf(line, sizeof line, "{\"kat\":\"sizing_restart\",\"E\":%llu,\"fp\":%.9g,\"tai\":%llu,\"n_hash\":%d}\n", (unsigned long long)E,
+                         (double)fp, (unsigned long long)b->tai, b->getNumHash());
+                rows.push_back(line);
+                delete b;
+            }
+        }
+        std::cout.rdbuf(cb);
+        fclose(stdout);
+        stdout = sav;
+        for (auto& r : rows) fputs(r.c_str(), stdout);
+    }
     /* ---- ReadscanTest.cpp cases (k=5, j=0, maxSpacerDist=8, fake Bloom) ---- */
     scan_case("singleReadNoJunctions", 5, 0, 8,
               {"ACGGG", "CGGGC", "GGGCG", "GGCGA", "GCGAA", "CGAAC", "GAACT", "AACTT", "ACTTT", "CTTTC", "TTTCA", "TTCAT", "TCATA",

@@ -7,12 +7,24 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ["c1_k21", "ragged_k31", "twohash_k31_L150", "j2_spacer20_k15", "j0_k15", "pe_fastq_k21", "mercy_k21", "nomercy_k21", "se_cleaning_k21",
-         "pe_repeats_k25", "pe_fasta_highcov_k31", "pe_mercy_k21", "pe_twohash_k27"]      # (the last four: tests/golden/make_pairs_golden.py, round 4)
+         "pe_repeats_k25", "pe_fasta_highcov_k31", "pe_mercy_k21", "pe_twohash_k27",      # (these four: tests/golden/make_pairs_golden.py, round 4)
+         "se_fp7_k21", "pe_mercy_fp6_k21", "onehash_k25", "j6_k21", "j8_k23"]             # (tests/golden/make_shapes_golden.py: 7, 6, 1 hash functions, -j 6 / 8)
 
 
 def _gz(path):
     with gzip.open(path, "rb") as f:
         return f.read()
+
+
+def fp_for(E, S, nh, n_hash_of):
+    """an -fp at which a sizing from reads gives `nh` hash functions (n_hash_of(E, S, fp) -> hash count: the product's or the oracle's), the
+    geometric middle of the band of fp values between 0.04 and 5e-5 that give it; None if no fp in that range does at this E / S"""
+    fps = [float(f) for f in np.geomspace(0.04, 0.00005, 160) if n_hash_of(E, S, float(f)) == nh]
+    if not fps:
+        return None
+    fp = float(f"{(fps[0] * fps[-1]) ** 0.5:.3g}")
+    assert n_hash_of(E, S, fp) == nh
+    return fp
 
 
 def kat(kind):

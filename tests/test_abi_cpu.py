@@ -42,6 +42,28 @@ def test_product_sizing_matches_reference(d):
     assert tai == d["tai"] and nh == d["n_hash"]
 
 
+@pytest.mark.parametrize("d", kat("sizing_fp"), ids=lambda d: f"E{d['E']}_S{d['S']}_fp{d['fp']:.2g}")
+def test_product_sizing_past_four_hash_functions_matches_reference(d):
+    """small -fp from reads: 5..10 hash functions, the wrap to 4 beyond 10, and one hash function at S/E = 0.95"""
+    p1 = api.solve_p1(d["E"], d["S"], d["fp"])
+    assert p1 == d["p1"]
+    _, tai, nh = api.size_optimal(d["E"], np.float32(p1))
+    assert tai == d["tai"] and nh == d["n_hash"]
+    assert api.load_filter_shape(d["E"], d["S"], d["fp"]) == (tai, nh)
+
+
+def test_sizing_rows_reach_every_hash_count():
+    assert {d["n_hash"] for d in kat("sizing_fp")} == {1, 4, 5, 6, 7, 8, 9, 10}
+    assert {d["n_hash"] for d in kat("sizing_restart")} == {4, 6, 7, 8, 9, 10}
+
+
+@pytest.mark.parametrize("d", kat("sizing_restart"), ids=lambda d: f"E{d['E']}_fp{d['fp']:.2g}")
+def test_product_restart_sizing_matches_reference(d):
+    """-bloom_file: the filter is sized from -fp alone (create_bloom_filter_optimal(E, fp)); 0.01 gives 6 hash functions"""
+    _, tai, nh = api.size_optimal(d["E"], np.float32(d["fp"]))
+    assert tai == d["tai"] and nh == d["n_hash"]
+
+
 def test_tai_rounding_matches_reference():
     (d,) = kat("tai")
     for req, tai in d["cases"]:

@@ -66,7 +66,7 @@ def test_hash_random_vs_oracle():
 def test_load_matches_reference_bloom(name, n_batches):
     c = Case(name)
     bases, offs = po.reads_from_lines(c.lines())
-    tai, nh = api.load_filter_shape(c.E, c.S)
+    tai, nh = api.load_filter_shape(c.E, c.S, c.fp)
     ctx = api.Context(c.k, tai, nh, j=c.j, max_spacer_dist=c.spacer, mercy=c.mercy)
     st = api.load_two_filters(api.Bloom(ctx, L.BLOO1), api.Bloom(ctx, L.BLOO2), chunks(bases, offs, n_batches))
     got2 = ctx.bloom_download(L.BLOO2)
@@ -81,7 +81,7 @@ def test_load_matches_reference_bloom(name, n_batches):
 
 
 def _scan_and_compare(c, bases, offs, n_batches, span, eager=False):
-    tai, nh = api.load_filter_shape(c.E, c.S)
+    tai, nh = api.load_filter_shape(c.E, c.S, c.fp)
     ctx = api.Context(c.k, tai, nh, j=c.j, max_spacer_dist=c.spacer, walk_window_span=span, eager_flags=eager)
     ctx.bloom_upload(L.BLOO2, c.bloom())
     sc = api.ReadScanner(ctx)
@@ -256,7 +256,7 @@ def test_scan_eager_flags_mode_gives_the_same_result(name):
 def test_scan_prepare_then_walk_equals_scan_batch(name):
     c = Case(name)
     bases, offs = po.reads_from_lines(c.lines())
-    tai, nh = api.load_filter_shape(c.E, c.S)
+    tai, nh = api.load_filter_shape(c.E, c.S, c.fp)
     ctx = api.Context(c.k, tai, nh, j=c.j, max_spacer_dist=c.spacer)
     ctx.bloom_upload(L.BLOO2, c.bloom())
     ctx.scan_begin()
@@ -310,7 +310,7 @@ def test_load_then_scan_end_to_end_on_device():
     """bloo2 stays resident between the passes (no upload), as in the CLI."""
     c = Case("c1_k21")
     bases, offs = po.reads_from_lines(c.lines())
-    tai, nh = api.load_filter_shape(c.E, c.S)
+    tai, nh = api.load_filter_shape(c.E, c.S, c.fp)
     ctx = api.Context(c.k, tai, nh)
     api.load_two_filters(api.Bloom(ctx, L.BLOO1), api.Bloom(ctx, L.BLOO2), [api.ReadBatch(bases, offs)])
     sc = api.ReadScanner(ctx)
@@ -480,7 +480,7 @@ def test_two_shard_load_prefix_or_is_exact():
     prefix-OR as the carried-in state of the later shard, OR of the shards' bloo2."""
     c = Case("ragged_k31")
     bases, offs = po.reads_from_lines(c.lines())
-    tai, nh = api.load_filter_shape(c.E, c.S)
+    tai, nh = api.load_filter_shape(c.E, c.S, c.fp)
     parts = chunks(bases, offs, 2)
     ctxs = [api.Context(c.k, tai, nh) for _ in parts]
     for ctx, part in zip(ctxs, parts):
@@ -506,7 +506,7 @@ def test_two_shard_scan_table_handover_is_exact():
     import torch
     c = Case("c1_k21")
     bases, offs = po.reads_from_lines(c.lines())
-    tai, nh = api.load_filter_shape(c.E, c.S)
+    tai, nh = api.load_filter_shape(c.E, c.S, c.fp)
     parts = chunks(bases, offs, 2)
     a = api.Context(c.k, tai, nh)
     b = api.Context(c.k, tai, nh)
@@ -554,7 +554,7 @@ def test_cli_writes_the_reference_files(name, how, tmp_path):
     assert "Weights after load: %s, %s" % tuple(cn["weights_after_load"]) in r.stdout
 
 
-@pytest.mark.parametrize("name", ["restart_bloomfile_k21", "restart_bloomfile_twohash_k21"])
+@pytest.mark.parametrize("name", ["restart_bloomfile_k21", "restart_bloomfile_twohash_k21", "restart_bloomfile_fp6_k21"])
 def test_cli_restarts_from_a_bloom_file_like_the_reference(name, tmp_path):
     """-bloom_file (src/Faucet.cpp:97-100,185-195,257-258): pass 1 is skipped, the filter is loaded from a file into a Bloom sized with
     create_bloom_filter_optimal(estimated_kmers, fpRate) -- fpRate, NOT the p1 a load from reads is sized with -- or, with --two_hash,
@@ -1030,7 +1030,7 @@ def _load_split(ctx, text, fastq, chunk):
 def test_device_record_splitting_reproduces_the_reference_bloom(name, chunk):
     c = Case(name)
     text = c.reads_text()
-    tai, nh = api.load_filter_shape(c.E, c.S)
+    tai, nh = api.load_filter_shape(c.E, c.S, c.fp)
     ctx = api.Context(c.k, tai, nh, j=c.j, max_spacer_dist=c.spacer)
     st, n_reads = _load_split(ctx, text, c.fastq, chunk)
     assert n_reads == len(c.lines()) == st["reads_processed"]
@@ -1221,7 +1221,7 @@ def test_the_library_absorbs_a_failed_lazy_check(tmp_path, monkeypatch):
         "from tests.test_gpu_parity import chunks\n"
         "c = Case('ragged_k31')\n"
         "bases, offs = po.reads_from_lines(c.lines())\n"
-        "tai, nh = api.load_filter_shape(c.E, c.S)\n"
+        "tai, nh = api.load_filter_shape(c.E, c.S, c.fp)\n"
         "want = sorted(c.junction_lines())\n"
         "for mode in ('stream', 'prepared'):\n"
         "    ctx = api.Context(c.k, tai, nh, walk_window_span=512)\n"
@@ -1320,7 +1320,7 @@ def test_mercy_load_matches_the_reference(n_batches):
     c = Case("mercy_k21")
     assert c.mercy and not np.array_equal(c.bloom(), Case("nomercy_k21").bloom())
     bases, offs = po.reads_from_lines(c.lines())
-    tai, nh = api.load_filter_shape(c.E, c.S)
+    tai, nh = api.load_filter_shape(c.E, c.S, c.fp)
     ctx = api.Context(c.k, tai, nh, mercy=True)
     st = api.load_two_filters(api.Bloom(ctx, L.BLOO1), api.Bloom(ctx, L.BLOO2), chunks(bases, offs, n_batches))
     assert np.array_equal(ctx.bloom_download(L.BLOO2), c.bloom())
@@ -1390,7 +1390,7 @@ def test_walk_evaluates_the_junction_tests_the_preview_left_out():
             "from tests.golden_util import Case\n"
             "c = Case('c1_k21')\n"
             "bases, offs = po.reads_from_lines(c.lines())\n"
-            "tai, nh = api.load_filter_shape(c.E, c.S)\n"
+            "tai, nh = api.load_filter_shape(c.E, c.S, c.fp)\n"
             "ctx = api.Context(c.k, tai, nh)\n"
             "ctx.bloom_upload(L.BLOO2, c.bloom())\n"
             "st = api.ReadScanner(ctx).scanReads([api.ReadBatch(bases, offs)])\n"
@@ -1486,7 +1486,7 @@ def test_page_locked_and_overlapped_downloads_equal_the_plain_ones():
     waits for it instead of rewriting the filter under the copy."""
     c = Case("ragged_k31")
     bases, offs = po.reads_from_lines(c.lines())
-    tai, nh = api.load_filter_shape(c.E, c.S)
+    tai, nh = api.load_filter_shape(c.E, c.S, c.fp)
     ctx = api.Context(c.k, tai, nh, j=c.j, max_spacer_dist=c.spacer)
     batches = chunks(bases, offs, 3)
     api.load_two_filters(api.Bloom(ctx, L.BLOO1), api.Bloom(ctx, L.BLOO2), batches)

@@ -31,10 +31,10 @@ def stdout_lines(text):
     return out
 
 
-@pytest.mark.parametrize("seed", range(100, 112))
-def test_cli_equals_the_compiled_reference_on_a_random_run(seed, tmp_path, cli_extra=()):
-    from tests.test_oracle_vs_reference_fuzz import random_run
-    path, fastq, args = random_run(seed, tmp_path)
+def cli_against_reference(path, args, tmp_path, cli_extra=(), env=None, writes=(".bloom", ".junctions")):
+    """`faucet` and the compiled reference on the reads at `path` with `args` (`cli_extra`, `env`: the command line's only): every file the
+    command line writes (`writes` among them), the reference wrote too with the same bytes; the scan's counters and the log line for line.
+    Returns both stdouts."""
     outs = {}
     for tag, exe in (("ref", REF_BIN), ("gpu", EXE)):
         d = tmp_path / tag
@@ -43,13 +43,13 @@ def test_cli_equals_the_compiled_reference_on_a_random_run(seed, tmp_path, cli_e
         # (with -gpus N: the library checks the in-map planes a shard's walk MERGES with the new keys against planes made again, FGPU_DEBUG_DELTA_CHECK)
         r = subprocess.run(["stdbuf", "-o0", exe, "-read_load_file", path, "-read_scan_file", path, "-file_prefix", str(d / "out")] + args +
                            (list(cli_extra) if tag == "gpu" else []), capture_output=True, text=True, errors="replace", timeout=600,
-                           env=dict(os.environ, FGPU_DEBUG_DELTA_CHECK="1") if tag == "gpu" and cli_extra else None)
+                           env=dict(os.environ, **(dict(FGPU_DEBUG_DELTA_CHECK="1") if cli_extra else {}), **(env or {})) if tag == "gpu" else None)
         outs[tag] = (r, d)
     (rr, dr), (rg, dg) = outs["ref"], outs["gpu"]
     assert rg.returncode == (0 if "--no_cleaning" in args else 3), rg.stderr[-2000:]      # (the reference goes on into its contig graph and may crash there)
     assert "merged in-map planes differ" not in rg.stderr, rg.stderr[-2000:]
     mine = sorted(os.listdir(dg))
-    assert any(f.endswith(".bloom") for f in mine) and any(f.endswith(".junctions") for f in mine)
+    assert all(any(f.endswith(ext) for f in mine) for ext in writes), mine
     for f in mine:                                   # every file this build writes, the reference wrote too, with the same bytes
         assert os.path.exists(dr / f), f
         assert (dg / f).read_bytes() == (dr / f).read_bytes(), f
@@ -63,6 +63,14 @@ def test_cli_equals_the_compiled_reference_on_a_random_run(seed, tmp_path, cli_e
     a = [ln.replace(str(dr), "<prefix>") for ln in stdout_lines(rr.stdout)]
     b = [ln.replace(str(dg), "<prefix>") for ln in stdout_lines(rg.stdout)]
     assert b and b[-1].startswith("Number of junctions:") and a[:len(b)] == b, [x for x in zip(a, b) if x[0] != x[1]][:5]
+    return rr.stdout, rg.stdout
+
+
+@pytest.mark.parametrize("seed", range(100, 112))
+def test_cli_equals_the_compiled_reference_on_a_random_run(seed, tmp_path, cli_extra=()):
+    from tests.test_oracle_vs_reference_fuzz import random_run
+    path, fastq, args = random_run(seed, tmp_path)
+    cli_against_reference(path, args, tmp_path, cli_extra)
 
 
 @pytest.mark.parametrize("gpus", [2, 3])
@@ -131,19 +139,24 @@ def test_restart_modes_equal_the_compiled_reference(seed, tmp_path):
 BOUND = os.path.join(ROOT, "oracle", "_ref", "faucet_ref_gpu")
 
 
-def binding_differences(seed, tmp):
+def binding_differences(seed, tmp, extra=(), stdouts=None):
     """the compiled reference with integration/faucet_binding.cpp linked in (its two hot-path call sites on libfaucet_gpu.so, everything else --
-    the contig graph included -- the reference as compiled) against the pure reference on a random run: [] if exit status and every file,
-    contig files included, are the same"""
+    the contig graph included -- the reference as compiled) against the pure reference on a random run (`extra`: arguments after the drawn
+    ones; `stdouts`: a dict that receives both runs' stdout): [] if exit status and every file, contig files included, are the same"""
     from tests.test_gpu_binding import normalised
     from tests.test_oracle_vs_reference_fuzz import random_run
     path, fastq, args = random_run(seed, tmp)
+    if "-fp" in extra:
+        args = [a for i, a in enumerate(args) if a != "-fp" and (i == 0 or args[i - 1] != "-fp")]
+    args = args + list(extra)
     res = {}
     for tag, exe in (("ref", REF_BIN), ("bound", BOUND)):
         (tmp / tag).mkdir()
         res[tag] = subprocess.run(["stdbuf", "-o0", exe, "-read_load_file", path, "-read_scan_file", path, "-file_prefix", str(tmp / tag / "out")] + args,
                                   capture_output=True, text=True, errors="replace", timeout=600)
     rr, rb = res["ref"], res["bound"]
+    if stdouts is not None:
+        stdouts.update(ref=rr.stdout, bound=rb.stdout)
     fr, fb = sorted(os.listdir(tmp / "ref")), sorted(os.listdir(tmp / "bound"))
     notes = []
     if rr.returncode != rb.returncode:

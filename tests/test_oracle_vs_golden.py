@@ -134,6 +134,15 @@ def test_end_to_end_vs_reference(name):
     check_oracle_against_case(Case(name))
 
 
+def test_goldens_reach_their_filter_shapes_and_stay_inside_the_references_jcheck_buffers():
+    """tests/golden/make_shapes_golden.py: 7, 6 and 1 hash functions as the reference printed them, and -j 6 / 8 runs whose largest jcheck
+    level (replayed by the maker on the reference's .bloom) stays far below the 1000 k-mers JChecker keeps per level"""
+    assert [Case(n).counters["n_hash"] for n in ("se_fp7_k21", "pe_mercy_fp6_k21", "onehash_k25")] == [7, 6, 1]
+    for name, j in (("j6_k21", 6), ("j8_k23", 8)):
+        c = Case(name)
+        assert c.j == j and c.counters["n_hash"] == 3 and 0 < c.meta["max_jcheck_level"] < 100
+
+
 def test_file_reader_matches_line_splitter(tmp_path):
     for name in ("ragged_k31", "pe_fastq_k21"):
         c = Case(name)

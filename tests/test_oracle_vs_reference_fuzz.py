@@ -26,8 +26,14 @@ def _write(path, lines, fastq):
                 f.write(b">r%d\n" % i + s + b"\n")
 
 
-def random_run(seed, tmp_path):
-    """(path of the reads file, fastq, arguments) of a run drawn from `seed`"""
+def _n_hash_from_reads(E, S, fp):
+    from oracle import pyoracle as po
+    return po.sizing_from_cli(E, S, fp)[1]
+
+
+def random_run(seed, tmp_path, shapes=False):
+    """(path of the reads file, fastq, arguments) of a run drawn from `seed`; `shapes`: also a filter of 1 or 5..10 hash functions
+    (-singletons near -estimated_kmers, or a small -fp) or -j 5..8, drawn after everything else"""
     from faucet_amd import synth
     rng = np.random.default_rng(9000 + seed)
     k = int(os.environ.get("FUZZ_K") or rng.choice([15, 21, 25, 31]))       # (FUZZ_K: scripts that draw other k, e.g. even ones)
@@ -78,6 +84,17 @@ def random_run(seed, tmp_path):
             args.append("--two_hash")            # sizes a filter restarted from a .bloom file; from reads it must not change anything
         if rng.integers(0, 3) == 0:
             args += ["-fp", str(float(rng.choice([0.02, 0.05, 0.1])))]
+    if shapes:
+        from tests.golden_util import fp_for
+        args = [a for i, a in enumerate(args) if a not in ("-j", "-fp") and (i == 0 or args[i - 1] not in ("-j", "-fp"))]
+        nh = int(rng.choice([1, 5, 6, 7, 8, 9, 10, 3]))
+        if nh == 1:
+            args[args.index("-singletons") + 1] = str(E * 95 // 100)
+        elif nh > 3:
+            fp = next(f for f in (fp_for(E, S, n, _n_hash_from_reads) for n in sorted(range(5, 11), key=lambda n: abs(n - nh))) if f)   # (the nearest count this E / S reaches)
+            args += ["-fp", str(fp)]
+        if nh != 1 and rng.integers(0, 2) == 0:      # (a sparse filter: no jcheck level comes near the reference's 1000 k-mers)
+            args += ["-j", str(int(rng.integers(5, 9)))]
     path = str(tmp_path / ("in.fq" if fastq else "in.fa"))
     _write(path, lines, fastq)
     return path, fastq, args
@@ -91,3 +108,33 @@ def test_oracle_equals_the_compiled_reference_on_a_random_run(seed, tmp_path):
     path, fastq, args = random_run(seed, tmp_path)
     G.run_case("case", path, fastq, args, tolerate_crash=True, out_root=str(tmp_path))
     check_oracle_against_case(Case(str(tmp_path / "case")))
+
+
+SHAPE_SEEDS = range(16, 40)
+
+
+def test_shape_draws_reach_every_hash_count_and_deep_jcheck(tmp_path, monkeypatch):
+    from oracle import pyoracle as po
+    monkeypatch.delenv("FUZZ_MORE_FLAGS", raising=False)      # (the seeds' default draws)
+    nhs, js = set(), set()
+    for seed in SHAPE_SEEDS:
+        _, _, a = random_run(seed, tmp_path, shapes=True)
+        opt = lambda f, d: type(d)(a[a.index(f) + 1]) if f in a else d      # noqa: E731
+        nhs.add(po.sizing_from_cli(opt("-estimated_kmers", 0), opt("-singletons", 0), opt("-fp", 0.04))[1])
+        js.add(opt("-j", 1))
+    assert {1, 5, 6, 7, 8, 9, 10} <= nhs and {5, 6, 7, 8} <= js
+
+
+@pytest.mark.parametrize("seed", SHAPE_SEEDS)
+def test_oracle_equals_the_compiled_reference_at_other_filter_shapes(seed, tmp_path):
+    """the same with filters of 1 or 5..10 hash functions and -j 5..8: the reference's printed hash count is the one its final arguments size for"""
+    import make_golden as G
+    from oracle import pyoracle as po
+    from tests.golden_util import Case
+    from tests.test_oracle_vs_golden import check_oracle_against_case
+    path, fastq, args = random_run(seed, tmp_path, shapes=True)
+    G.run_case("case", path, fastq, args, tolerate_crash=True, out_root=str(tmp_path))
+    c = Case(str(tmp_path / "case"))
+    opt = lambda f, d: type(d)(args[args.index(f) + 1]) if f in args else d      # noqa: E731
+    assert c.counters["n_hash"] == po.sizing_from_cli(opt("-estimated_kmers", 0), opt("-singletons", 0), opt("-fp", 0.04))[1]
+    check_oracle_against_case(c)
