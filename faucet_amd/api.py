@@ -197,6 +197,34 @@ class Context:
         self._c(self.lib.fgpu_load_fixup_state(self.h, C.byref(ready), C.byref(budget)))
         return bool(ready.value), int(budget.value)
 
+    # pass 1 by filter slices: the whole stream into the bits [bit_lo, bit_hi) (faucet_gpu.h, fgpu_load_slice_*)
+    def load_slice_begin(self, bit_lo: int, bit_hi: int):
+        self._c(self.lib.fgpu_load_slice_begin(self.h, bit_lo, bit_hi))
+
+    def load_slice_batch(self, batch: ReadBatch):
+        s = batch.c_struct()
+        self._c(self.lib.fgpu_load_slice_batch(self.h, C.byref(s)))
+
+    def load_slice_plane(self, i: int):
+        """(device pointer, bytes) of the fail plane of the i-th non-empty batch: to be ORed across the ranks in place"""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._c(self.lib.fgpu_load_slice_plane(self.h, i, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def load_slice_commit(self):
+        self._c(self.lib.fgpu_load_slice_commit(self.h))
+
+    def load_slice_end(self) -> dict:
+        st = L.LoadStats()
+        self._c(self.lib.fgpu_load_slice_end(self.h, C.byref(st)))
+        return st.as_dict()
+
+    def load_slice_state(self):
+        """(inside a sliced pass that is not committed yet?, device bytes of the slice state, planes load_slice_plane can hand out)"""
+        ready, wb, nb = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        self._c(self.lib.fgpu_load_slice_state(self.h, C.byref(ready), C.byref(wb), C.byref(nb)))
+        return bool(ready.value), int(wb.value), int(nb.value)
+
     def load_batch(self, batch: ReadBatch):
         s = batch.c_struct()
         self._c(self.lib.fgpu_load_batch(self.h, C.byref(s)))

@@ -362,7 +362,7 @@ void fgpu_destroy(fgpu_ctx* ctx) {
     for (DevBuf* b : ctx->owned) if (b->p) hipFree(b->p);
     if (ctx->lp.flips_host) hipHostFree(ctx->lp.flips_host);
     if (ctx->lp.ev_open) hipEventDestroy(ctx->lp.ev_open);
-    void* ptrs[] = {ctx->lp.bits, ctx->lp.first, ctx->short_pf, ctx->bloo1, ctx->bloo2, ctx->first, ctx->pair, ctx->rec, ctx->jkeys, ctx->jrecs, ctx->jstamps, ctx->jfilter, ctx->wkeys,
+    void* ptrs[] = {ctx->lp.bits, ctx->lp.first, ctx->short_pf, ctx->bloo1, ctx->bloo2, ctx->first, ctx->pair, ctx->rec, ctx->slice_first, ctx->slice_pair, ctx->jkeys, ctx->jrecs, ctx->jstamps, ctx->jfilter, ctx->wkeys,
                     ctx->wbits, ctx->uf_parent, ctx->cl_count, ctx->cl_offset, ctx->cl_fill, ctx->cl_fail, ctx->ko_hk, ctx->ko_occ, ctx->ko_piece, ctx->cl_members, ctx->cl_roots, ctx->counters,
                     ctx->wdesc};
     for (void* p : ptrs) if (p) hipFree(p);
@@ -396,6 +396,35 @@ int fgpu_synchronize(fgpu_ctx* ctx) {
 }
 
 // ---- pass 1 --------------------------------------------------------------------------------------------------
+// What a plain and a sliced load pass share at their beginning: how the carry is kept up to date and when an epoch is closed ...
+static void load_pass_policy(fgpu_ctx* ctx) {
+    static const char* carry_env = getenv("FGPU_CARRY_MODE");   // "sweep" / "set": measurement aid
+    ctx->carry_by_set = carry_env ? carry_env[0] == 's' && carry_env[1] == 'e' : ctx->prm.tai == (1ULL << 31);
+    ctx->epoch_positions = ctx->swept_positions = 0;
+    ctx->sweep_num = ctx->sweep_den = 1;
+    const char* sweep_env = getenv("FGPU_SWEEP_RATIO");   // "num/den"; "0/1" = after every batch: measurement aid
+    if (sweep_env) {
+        unsigned n = 1, d = 1;
+        if (sscanf(sweep_env, "%u/%u", &n, &d) == 2 && d > 0) { ctx->sweep_num = n; ctx->sweep_den = d; }
+    }
+    {   // a sweep streams tai x 4 bytes whatever the epoch holds: not before the epoch's accesses are tai / 16 (FGPU_SWEEP_MIN_FRAC; 0 = no such
+        // bar, rounds 1-4).  The first sweeps of a pass on large filters came after a quarter-size ramp batch and brought the carry almost nothing:
+        // one rank's own load of config 4 on 8 GPUs 350 -> 337 ms (6 sweeps -> 4), configs 2, 4, 5 whole unchanged (profiles/r05_sweep_policy.txt)
+        const char* e = getenv("FGPU_SWEEP_MIN_FRAC");
+        const double frac = e ? atof(e) : 16.0;
+        ctx->sweep_min = frac > 0.0 ? (uint64_t)((double)ctx->prm.tai / frac / (double)std::max(1, ctx->prm.n_hash)) : 0;
+    }
+}
+// ... and the counters of the pass
+static int load_pass_counters(fgpu_ctx* ctx) {
+    FGPU_HIP(hipMemsetAsync(ctx->counters, 0, sizeof(DevCounters), ctx->stream));
+    memset(&ctx->load_stats, 0, sizeof(ctx->load_stats));
+    ctx->host_waits = 0;
+    ctx->host_wait_ms = 0;
+    ctx->wait_sites.clear();
+    return FGPU_OK;
+}
+
 int fgpu_load_begin(fgpu_ctx* ctx, int keep_carry) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 0) { ctx->err = "load_begin while another pass is open"; return FGPU_ERR_STATE; }
@@ -440,8 +469,6 @@ int fgpu_load_begin(fgpu_ctx* ctx, int keep_carry) {
     // except at 2^31 bits.  (One rank's passes of the 8-rank shape, 2^32 bits, same box, re-hashing / sweeping: the presence protocol's
     // load on a carried-in state 88-97 / 95 ms, the fix-up protocol's own load 146-163 / 143 ms.  Round 2 re-hashed from 2^31 bits up;
     // it had only measured short passes.)
-    static const char* carry_env = getenv("FGPU_CARRY_MODE");   // "sweep" / "set": measurement aid
-    ctx->carry_by_set = carry_env ? carry_env[0] == 's' && carry_env[1] == 'e' : ctx->prm.tai == (1ULL << 31);
     ctx->shard_times = (keep_carry & FGPU_LOAD_SHARD_TIMES) != 0;
     // ONE predicate for the fail planes: they exist for at most 4 hash functions (load.hip MISS_PLANES).  With more the flag is
     // accepted and the pass is a plain load -- nothing is sized for or copied from planes that are never made -- and fgpu_load_fixup answers
@@ -451,31 +478,14 @@ int fgpu_load_begin(fgpu_ctx* ctx, int keep_carry) {
     ctx->pass_positions = ctx->pass_batches = 0;
     ctx->pass_empty_carry = !(keep_carry & FGPU_LOAD_KEEP_CARRY);
     keep_carry &= FGPU_LOAD_KEEP_CARRY;
-    ctx->epoch_positions = ctx->swept_positions = 0;
-    ctx->sweep_num = ctx->sweep_den = 1;
-    const char* sweep_env = getenv("FGPU_SWEEP_RATIO");   // "num/den"; "0/1" = after every batch: measurement aid
-    if (sweep_env) {
-        unsigned n = 1, d = 1;
-        if (sscanf(sweep_env, "%u/%u", &n, &d) == 2 && d > 0) { ctx->sweep_num = n; ctx->sweep_den = d; }
-    }
-    {   // a sweep streams tai x 4 bytes whatever the epoch holds: not before the epoch's accesses are tai / 16 (FGPU_SWEEP_MIN_FRAC; 0 = no such
-        // bar, rounds 1-4).  The first sweeps of a pass on large filters came after a quarter-size ramp batch and brought the carry almost nothing:
-        // one rank's own load of config 4 on 8 GPUs 350 -> 337 ms (6 sweeps -> 4), configs 2, 4, 5 whole unchanged (profiles/r05_sweep_policy.txt)
-        const char* e = getenv("FGPU_SWEEP_MIN_FRAC");
-        const double frac = e ? atof(e) : 16.0;
-        ctx->sweep_min = frac > 0.0 ? (uint64_t)((double)ctx->prm.tai / frac / (double)std::max(1, ctx->prm.n_hash)) : 0;
-    }
+    load_pass_policy(ctx);
     if (!ctx->rec_layout) FGPU_HIP(hipMemsetAsync(ctx->first, 0xFF, ctx->prm.tai * 4, ctx->stream));   // (records: k_rec_init, fgpu_load_pair_begin)
     fgpu_resident_reset(ctx, true);
     if (!keep_carry) FGPU_HIP(hipMemsetAsync(ctx->bloo1, 0, ctx->bloom_bytes, ctx->stream));
     FGPU_HIP(hipMemsetAsync(ctx->bloo2, 0, ctx->bloom_bytes, ctx->stream));
     int rc = fgpu_load_pair_begin(ctx);
     if (rc) return rc;
-    FGPU_HIP(hipMemsetAsync(ctx->counters, 0, sizeof(DevCounters), ctx->stream));
-    memset(&ctx->load_stats, 0, sizeof(ctx->load_stats));
-    ctx->host_waits = 0;
-    ctx->host_wait_ms = 0;
-    ctx->wait_sites.clear();
+    if ((rc = load_pass_counters(ctx))) return rc;
     ctx->phase = 1;
     return FGPU_OK;
 }
@@ -554,11 +564,126 @@ int fgpu_load_fixup(fgpu_ctx* ctx, const void* prefix_dev, fgpu_load_stats* stat
     return FGPU_OK;
 }
 
+// ---- pass 1 by filter slices: the whole stream into one slice of the bit positions ------------------------------
+int fgpu_load_slice_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 0) { ctx->err = "load_slice_begin while another pass is open"; return FGPU_ERR_STATE; }
+    if (ctx->prm.flags & FGPU_FLAG_MERCY) {
+        ctx->err = "load_slice_begin: --mercy needs time-aware membership tests of the other slices' bits; not available under filter slices";
+        return FGPU_ERR_STATE;
+    }
+    if ((bit_lo & 511) || (bit_hi & 511) || bit_lo > bit_hi || bit_hi > ctx->prm.tai) {
+        ctx->err = "load_slice_begin: a slice is [bit_lo, bit_hi) with both bounds multiples of 512, bit_lo <= bit_hi <= tai";
+        return FGPU_ERR_ARG;
+    }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    if (int rc = fgpu_bloom_download_wait(ctx)) return rc;
+    // the working state is sized by the SLICE (4 bytes of time + 2 x 1/8 byte of filter per own bit), always in the pair layout
+    const uint64_t n = bit_hi - bit_lo, fbytes = n * 4, pbytes = n / 4;
+    if (ctx->slice_first_bytes < fbytes || ctx->slice_pair_bytes < pbytes) {
+        FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+        if (ctx->slice_first) (void)hipFree(ctx->slice_first);
+        if (ctx->slice_pair) (void)hipFree(ctx->slice_pair);
+        ctx->slice_first = nullptr;
+        ctx->slice_pair = nullptr;
+        ctx->slice_first_bytes = ctx->slice_pair_bytes = 0;
+        hipError_t e = hipMalloc(&ctx->slice_first, fbytes);
+        if (e == hipSuccess) e = hipMalloc(&ctx->slice_pair, pbytes);
+        if (e != hipSuccess) {
+            ctx->err = std::string("hipMalloc of the slice state (4.25 bytes per own filter bit) failed: ") + hipGetErrorString(e);
+            if (ctx->slice_first) (void)hipFree(ctx->slice_first);
+            ctx->slice_first = nullptr;
+            ctx->slice_pair = nullptr;
+            return FGPU_ERR_NOMEM;
+        }
+        ctx->slice_first_bytes = fbytes;
+        ctx->slice_pair_bytes = pbytes;
+    }
+    ctx->slice_lo = bit_lo;
+    ctx->slice_n = n;
+    ctx->slice_committed = false;
+    ctx->shard_times = ctx->shard_planes = ctx->fixup_ready = false;
+    ctx->rec_layout = false;
+    ctx->pass_positions = ctx->pass_batches = 0;
+    ctx->pass_empty_carry = true;
+    // carry and sweeps as in a plain pass (load_pass_policy).  The bar on an epoch's size, sweep_min, is taken over unchanged: a sweep of the
+    // slice streams 1/N of what a whole-filter sweep streams, and the epoch's accesses INTO the slice are 1/N as well, so the ratio the bar
+    // stands for is the same -- but the value was measured on whole filters only; for slices it is an unmeasured choice.
+    load_pass_policy(ctx);
+    fgpu_resident_reset(ctx, true);
+    int rc = fgpu_slice_pair_begin(ctx);
+    if (rc) return rc;
+    if ((rc = load_pass_counters(ctx))) return rc;
+    ctx->phase = 3;
+    return FGPU_OK;
+}
+
+int fgpu_load_slice_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 3) { ctx->err = "load_slice_batch outside load_slice_begin/load_slice_end"; return FGPU_ERR_STATE; }
+    if (ctx->slice_committed) { ctx->err = "load_slice_batch after load_slice_commit: the pass can only be ended"; return FGPU_ERR_STATE; }
+    int rc = check_reads(ctx, reads);
+    if (rc) return rc;
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    if ((rc = fgpu_stage_pack(ctx, reads))) return rc;
+    if ((rc = fgpu_stage_slice_load(ctx))) return rc;
+    if (ctx->cur->T) ctx->pass_batches++;
+    ctx->load_stats.reads_processed += reads->n_reads;
+    return fgpu_host_batch_done(ctx, reads);
+}
+
+int fgpu_load_slice_plane(fgpu_ctx* ctx, uint64_t batch, void** fail_dev, uint64_t* nbytes) {
+    if (!ctx || !fail_dev) return FGPU_ERR_ARG;
+    if (ctx->phase != 3) { ctx->err = "load_slice_plane outside load_slice_begin/load_slice_end"; return FGPU_ERR_STATE; }
+    if (batch >= ctx->resident_count) { ctx->err = "load_slice_plane: no such batch (empty batches keep no plane)"; return FGPU_ERR_ARG; }
+    const ResidentBatch& r = *ctx->resident[batch];
+    *fail_dev = r.fail.p;
+    if (nbytes) *nbytes = (r.n_words * 8 + 15) & ~15ULL;
+    return FGPU_OK;
+}
+
+int fgpu_load_slice_commit(fgpu_ctx* ctx) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 3) { ctx->err = "load_slice_commit outside load_slice_begin/load_slice_end"; return FGPU_ERR_STATE; }
+    if (ctx->slice_committed) { ctx->err = "load_slice_commit twice in one pass"; return FGPU_ERR_STATE; }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    int rc = fgpu_stage_slice_commit(ctx);
+    if (rc) return rc;
+    ctx->slice_committed = true;
+    return FGPU_OK;
+}
+
+int fgpu_load_slice_end(fgpu_ctx* ctx, fgpu_load_stats* stats) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 3) { ctx->err = "load_slice_end without load_slice_begin"; return FGPU_ERR_STATE; }
+    if (!ctx->slice_committed) { ctx->err = "load_slice_end before load_slice_commit"; return FGPU_ERR_STATE; }
+    int rc = fgpu_slice_sweep(ctx);          // bits set since the last sweep join the slice of bloo1
+    if (!rc) rc = fgpu_slice_pair_end(ctx);
+    if (!rc) rc = pull_counters(ctx);
+    ctx->phase = 0;
+    if (rc) return rc;
+    ctx->load_stats.kmers = ctx->counters_host->kmers;
+    ctx->load_stats.to_bloo2 = ctx->counters_host->to_bloo2;
+    ctx->load_mark_hits = 0;
+    ctx->load_mark_pending = ctx->counters_host->mark_pending;
+    ctx->load_stats.unambiguous_reads = ctx->counters_host->segments;
+    if (stats) *stats = ctx->load_stats;
+    return FGPU_OK;
+}
+
+int fgpu_load_slice_state(fgpu_ctx* ctx, int* ready, uint64_t* working_bytes, uint64_t* n_batches) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ready) *ready = ctx->phase == 3 && !ctx->slice_committed ? 1 : 0;
+    if (working_bytes) *working_bytes = ctx->slice_first_bytes + ctx->slice_pair_bytes;
+    if (n_batches) *n_batches = ctx->phase == 3 ? ctx->resident_count : 0;
+    return FGPU_OK;
+}
+
 static uint32_t* bloom_ptr(fgpu_ctx* ctx, int which) { return which == FGPU_BLOO1 ? ctx->bloo1 : which == FGPU_BLOO2 ? ctx->bloo2 : nullptr; }
 
 int fgpu_bloom_download(fgpu_ctx* ctx, int which, uint8_t* host_out, uint64_t nbytes) {
     if (!ctx || !host_out || !bloom_ptr(ctx, which) || nbytes != ctx->bloom_bytes) return FGPU_ERR_ARG;
-    if (ctx->phase == 1) { ctx->err = "bloom_download inside a load pass: the filters are interleaved until load_end"; return FGPU_ERR_STATE; }
+    if (ctx->phase == 1 || ctx->phase == 3) { ctx->err = "bloom_download inside a load pass: the filters are interleaved until load_end"; return FGPU_ERR_STATE; }
     FGPU_HIP(hipMemcpyAsync(host_out, bloom_ptr(ctx, which), nbytes, hipMemcpyDeviceToHost, ctx->stream));
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
     return FGPU_OK;
@@ -574,7 +699,7 @@ int fgpu_bloom_download_wait(fgpu_ctx* ctx) {
 
 int fgpu_bloom_download_begin(fgpu_ctx* ctx, int which, uint8_t* host_out, uint64_t nbytes) {
     if (!ctx || !host_out || !bloom_ptr(ctx, which) || nbytes != ctx->bloom_bytes) return FGPU_ERR_ARG;
-    if (ctx->phase == 1) { ctx->err = "bloom_download_begin inside a load pass: the filters are interleaved until load_end"; return FGPU_ERR_STATE; }
+    if (ctx->phase == 1 || ctx->phase == 3) { ctx->err = "bloom_download_begin inside a load pass: the filters are interleaved until load_end"; return FGPU_ERR_STATE; }
     if (int rc = fgpu_bloom_download_wait(ctx)) return rc;
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     if (!ctx->copy_stream) {
@@ -600,7 +725,7 @@ int fgpu_bloom_upload(fgpu_ctx* ctx, int which, const uint8_t* host_in, uint64_t
 
 int fgpu_bloom_weight(fgpu_ctx* ctx, int which, float* weight) {
     if (!ctx || !weight || !bloom_ptr(ctx, which)) return FGPU_ERR_ARG;
-    if (ctx->phase == 1) { ctx->err = "bloom_weight inside a load pass: the filters are interleaved until load_end"; return FGPU_ERR_STATE; }
+    if (ctx->phase == 1 || ctx->phase == 3) { ctx->err = "bloom_weight inside a load pass: the filters are interleaved until load_end"; return FGPU_ERR_STATE; }
     FGPU_HIP(hipMemsetAsync(&ctx->counters->pad, 0, 8, ctx->stream));
     int rc = fgpu_util_popcount(ctx, bloom_ptr(ctx, which), ctx->bloom_bytes, &ctx->counters->pad);
     if (rc) return rc;

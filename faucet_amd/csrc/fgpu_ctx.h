@@ -232,7 +232,13 @@ struct fgpu_ctx {
     uint32_t* rec = nullptr;         // the same state as 256-byte records {bloo1 word, bloo2 word, ..., 32 first-set times} (load.hip, Filt<1>):
     bool rec_layout = false;         // filters of 2^32 bits and more; `pair` and `first` are not used (nor allocated) then
     uint64_t bloom_bytes = 0;
-    int phase = 0;                   // 0 idle, 1 loading, 2 scanning
+    int phase = 0;                   // 0 idle, 1 loading, 2 scanning, 3 loading one slice of the filter bits (fgpu_load_slice_*)
+    // the filter-sliced pass: own bit positions [slice_lo, slice_lo + slice_n), its working state sized by the slice (load.hip, Slice)
+    uint64_t slice_lo = 0, slice_n = 0;
+    uint32_t* slice_first = nullptr; // first-set time per OWN bit, 4 * slice_n bytes
+    uint2* slice_pair = nullptr;     // {carry word, bloo2 word} per 32 own bits
+    uint64_t slice_first_bytes = 0, slice_pair_bytes = 0;   // as allocated
+    bool slice_committed = false;    // fgpu_load_slice_commit has run in this pass
     std::vector<ResidentBatch*> resident;  // load batches kept for the scan, in load order (buffers recycled across passes)
     uint64_t resident_count = 0;     // entries of `resident` that hold the current load pass
     uint64_t resident_bytes = 0, resident_budget = 0;
@@ -488,6 +494,11 @@ int fgpu_stage_load(fgpu_ctx* ctx);
 int fgpu_load_sweep(fgpu_ctx* ctx);
 int fgpu_stage_fixup(fgpu_ctx* ctx, const uint32_t* prefix);
 int fgpu_stage_presence(fgpu_ctx* ctx);
+int fgpu_stage_slice_load(fgpu_ctx* ctx);
+int fgpu_stage_slice_commit(fgpu_ctx* ctx);
+int fgpu_slice_sweep(fgpu_ctx* ctx);
+int fgpu_slice_pair_begin(fgpu_ctx* ctx);
+int fgpu_slice_pair_end(fgpu_ctx* ctx);
 int fgpu_load_pair_begin(fgpu_ctx* ctx);
 int fgpu_load_pair_end(fgpu_ctx* ctx);
 void fgpu_resident_reset(fgpu_ctx* ctx, bool keep_going);

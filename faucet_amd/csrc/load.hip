@@ -589,6 +589,150 @@ __global__ void __launch_bounds__(256) k_load_fixup_times(const uint64_t* __rest
     block_add(&cnt->to_bloo2, n_pass);
 }
 
+// ---- filter slices: one rank, the WHOLE stream, a slice [lo, lo + n) of the filter's bit positions ------------------
+// "Bit b was first set at time t" is a property of bit b alone (the min over all occurrences that hash to it), so the rank that owns b finds it
+// from the stream without the other slices.  What it cannot decide alone is the routing of an occurrence -- that needs ALL of its bits -- so the
+// pass writes, per stream position, "one of MY bits of this occurrence was not set before it" (the fail plane); the OR of the ranks' planes is the
+// sequential run's decision, and k_slice_commit sets the own bloo2 bits of the occurrences nobody failed.  The working state is sized by the
+// slice and indexed by h - lo: first[] 4 bytes per own bit, pair[] 8 bytes per 32 own bits (lo, n multiples of 512: (h - lo) & 31 == h & 31).
+struct Slice {
+    uint2* pair;
+    uint32_t* first;
+    uint64_t lo, n;
+    __device__ __forceinline__ bool owns(uint64_t o) const { return o < n; }   // o = h - lo, unsigned
+};
+
+__global__ void __launch_bounds__(256) k_slice_mark(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ bad, uint64_t T, uint64_t n_words,
+                                                    FdParams fp, Slice s, uint32_t tb, uint64_t* __restrict__ pending, uint64_t plane_stride,
+                                                    uint64_t* __restrict__ fail, DevCounters* cnt) {
+    unsigned long long n_ok = 0, n_pend = 0;
+    const uint64_t total = n_words * 64;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (uint64_t)gridDim.x * blockDim.x) {
+        const bool ok = p < T && fd_window_ok(bad, p, fp.k);
+        uint32_t missing = 0;
+        if (ok) {
+            n_ok++;
+            uint64_t hA, hB;
+            fd_hash_pair(fd_canon(fd_kmer_at(codes, p, fp.k), fp.k), fp.tai_mask, hA, hB);
+            // the carry words of the own positions (independent loads in flight); an occurrence without an own bit touches no memory
+            uint64_t h = hA;
+            for (int i = 0; i < fp.n_hash; i++) {
+                const uint64_t o = h - s.lo;
+                if (s.owns(o) && !((s.pair[o >> 5].x >> (o & 31)) & 1u)) missing |= 1u << i;
+                h = (h + hB) & fp.tai_mask;
+            }
+            if (missing) {
+                n_pend++;
+                h = hA;
+                for (int i = 0; i < fp.n_hash; i++) {
+                    if (missing & (1u << i)) atomicMin(s.first + (h - s.lo), tb + (uint32_t)p);
+                    h = (h + hB) & fp.tai_mask;
+                }
+            }
+        }
+        const uint64_t pm = __ballot(missing != 0);
+        uint64_t mm[MISS_PLANES];
+#pragma unroll
+        for (int i = 0; i < MISS_PLANES; i++) mm[i] = __ballot((missing >> i) & 1u);
+        if (fd_lane() == 0) {
+            pending[p >> 6] = pm;
+            fail[p >> 6] = 0;        // k_slice_resolve fills in the words that have pending occurrences
+            if (pm) {
+#pragma unroll
+                for (int i = 0; i < MISS_PLANES; i++) pending[(i + 1) * plane_stride + (p >> 6)] = mm[i];
+            }
+        }
+    }
+    block_add(&cnt->kmers, n_ok);
+    block_add(&cnt->mark_pending, n_pend);
+}
+
+// own bits that were missing from the carry: set before the occurrence iff first[bit] < its time.  One that was not -> the fail bit.
+__global__ void __launch_bounds__(256) k_slice_resolve(const uint64_t* __restrict__ codes, uint64_t n_words, FdParams fp, Slice s, uint32_t tb,
+                                                       const uint64_t* __restrict__ pending, uint64_t plane_stride, uint64_t* __restrict__ fail) {
+    const uint64_t total = n_words * 64;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t pw = pending[p >> 6];   // wave-uniform: the 64 lanes of a wave cover one word
+        if (!pw) continue;
+        bool failed = false;
+        if ((pw >> (p & 63)) & 1ULL) {
+            uint32_t missing = 0;
+#pragma unroll
+            for (int i = 0; i < MISS_PLANES; i++)
+                missing |= (uint32_t)((pending[(i + 1) * plane_stride + (p >> 6)] >> (p & 63)) & 1ULL) << i;
+            uint64_t hA, hB;
+            fd_hash_pair(fd_canon(fd_kmer_at(codes, p, fp.k), fp.k), fp.tai_mask, hA, hB);
+            uint64_t h = hA;
+            for (int i = 0; i < fp.n_hash; i++) {
+                const uint64_t o = h - s.lo;
+                // hash functions beyond the planes are tested against the carry again (it does not change between the two kernels)
+                const bool was_missing = i < MISS_PLANES ? ((missing >> i) & 1u) != 0 : s.owns(o) && !((s.pair[o >> 5].x >> (o & 31)) & 1u);
+                if (was_missing && !(s.first[o] < tb + (uint32_t)p)) { failed = true; break; }
+                h = (h + hB) & fp.tai_mask;
+            }
+        }
+        const uint64_t fm = __ballot(failed);
+        if (fd_lane() == 0) fail[p >> 6] = fm;
+    }
+}
+
+// carry |= own bits of the batch's occurrences (the re-hashing alternative to a sweep of the slice's first[], see k_carry_set).  Every valid
+// occurrence leaves all of its bits set in bloo1, and the ones whose own bits were all in the carry already are not pending: only those are hashed.
+__global__ void __launch_bounds__(256) k_slice_carry_set(const uint64_t* __restrict__ codes, uint64_t n_words, FdParams fp, Slice s,
+                                                         const uint64_t* __restrict__ pending, uint64_t plane_stride) {
+    const uint64_t total = n_words * 64;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t pw = pending[p >> 6];
+        if (!((pw >> (p & 63)) & 1ULL)) continue;
+        uint64_t hA, hB;
+        fd_hash_pair(fd_canon(fd_kmer_at(codes, p, fp.k), fp.k), fp.tai_mask, hA, hB);
+        uint64_t h = hA;
+        for (int i = 0; i < fp.n_hash; i++) {
+            const uint64_t o = h - s.lo;
+            if (s.owns(o)) {
+                const uint32_t bit = 1u << (o & 31);
+                if (!(s.pair[o >> 5].x & bit)) atomicOr(&s.pair[o >> 5].x, bit);
+            }
+            h = (h + hB) & fp.tai_mask;
+        }
+    }
+}
+
+// After the ranks' fail planes have been ORed in place: a valid window whose fail bit is 0 is an occurrence the sequential run routes to bloo2.
+// Its OWN bits are set here; `sure` = valid & ~fail is the global routing decision (what the scan of the same reads reuses), and the count is the
+// global one -- the same on every rank.
+__global__ void __launch_bounds__(256) k_slice_commit(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ bad, uint64_t T, uint64_t n_words,
+                                                      FdParams fp, Slice s, const uint64_t* __restrict__ fail, uint64_t* __restrict__ sure,
+                                                      DevCounters* cnt) {
+    unsigned long long n_go = 0;
+    const uint64_t total = n_words * 64;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (uint64_t)gridDim.x * blockDim.x) {
+        const bool go = p < T && fd_window_ok(bad, p, fp.k) && !((fail[p >> 6] >> (p & 63)) & 1ULL);
+        if (go) {
+            n_go++;
+            uint64_t hA, hB;
+            fd_hash_pair(fd_canon(fd_kmer_at(codes, p, fp.k), fp.k), fp.tai_mask, hA, hB);
+            uint32_t b2_missing = 0;
+            uint64_t h = hA;
+            for (int i = 0; i < fp.n_hash; i++) {
+                const uint64_t o = h - s.lo;
+                if (s.owns(o) && !((s.pair[o >> 5].y >> (o & 31)) & 1u)) b2_missing |= 1u << i;
+                h = (h + hB) & fp.tai_mask;
+            }
+            if (b2_missing) {   // a stale 0 only costs a redundant atomic; bits are never cleared
+                h = hA;
+                for (int i = 0; i < fp.n_hash; i++) {
+                    if (b2_missing & (1u << i)) atomicOr(&s.pair[(h - s.lo) >> 5].y, 1u << (h & 31));
+                    h = (h + hB) & fp.tai_mask;
+                }
+            }
+        }
+        const uint64_t sm = __ballot(go);
+        if (fd_lane() == 0) sure[p >> 6] = sm;
+    }
+    block_add(&cnt->to_bloo2, n_go);
+}
+
 // multi-GPU helper: OR the bits of every k-mer into a bitmap, no ordering
 __global__ void __launch_bounds__(256) k_presence(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ bad,
                                                   uint64_t T, uint64_t n_words, FdParams fp, uint32_t* bitmap, DevCounters* cnt) {
@@ -725,6 +869,20 @@ int fgpu_load_sweep(fgpu_ctx* ctx) {
     return FGPU_OK;
 }
 
+// The epoch clock and the sweep policy, shared by the plain pass (sweep = fgpu_load_sweep) and the sliced one (fgpu_slice_sweep): see the
+// comment in fgpu_stage_load.  Before a batch: a sweep if the 32-bit clock of the epoch would wrap in it.  After it: the batch joins the epoch,
+// and the epoch is closed once it has grown to sweep_num / sweep_den of what the carry covers and holds sweep_min positions.
+static int epoch_before_batch(fgpu_ctx* ctx, uint64_t span, int (*sweep)(fgpu_ctx*)) {
+    if (!ctx->carry_by_set && !ctx->shard_times && ctx->epoch_positions + span >= 0xFFFFFFF0ULL) return sweep(ctx);
+    return FGPU_OK;
+}
+static int epoch_after_batch(fgpu_ctx* ctx, uint64_t span, int (*sweep)(fgpu_ctx*)) {
+    if (ctx->carry_by_set) return FGPU_OK;
+    ctx->epoch_positions += span;
+    if (ctx->epoch_positions * ctx->sweep_den >= ctx->swept_positions * ctx->sweep_num && ctx->epoch_positions >= ctx->sweep_min) return sweep(ctx);
+    return FGPU_OK;
+}
+
 int fgpu_stage_load(fgpu_ctx* ctx) {
     BatchBufs& bb = *ctx->cur;
     if (bb.T == 0) return FGPU_OK;
@@ -741,7 +899,7 @@ int fgpu_stage_load(fgpu_ctx* ctx) {
     // holds a few coverages of the genome nearly every k-mer that will ever be in it already is: sweeps are made when an epoch
     // has grown to sweep_num/sweep_den of what the carry already covers (after batches 0, 1, 3, 7 ... of equal batches).
     const uint64_t span = bb.n_words * 64;
-    if (!ctx->carry_by_set && !ctx->shard_times && ctx->epoch_positions + span >= 0xFFFFFFF0ULL && (rc = fgpu_load_sweep(ctx))) return rc;
+    if ((rc = epoch_before_batch(ctx, span, fgpu_load_sweep))) return rc;
     if (ctx->shard_times && ctx->pass_positions + span >= 0xFFFFFFF0ULL) {
         ctx->err = "FGPU_LOAD_SHARD_TIMES: the pass exceeds 2^32 stream positions (FGPU_LOAD_SHARD_PLANES has no such limit)";
         return FGPU_ERR_CAPACITY;
@@ -792,11 +950,7 @@ int fgpu_stage_load(fgpu_ctx* ctx) {
     }
 #undef FGPU_LOAD_BATCH
     // carry := carry | bits set during this batch -- or later: the carry may lag behind (see fgpu_load_sweep)
-    if (!ctx->carry_by_set) {
-        ctx->epoch_positions += span;
-        if (ctx->epoch_positions * ctx->sweep_den >= ctx->swept_positions * ctx->sweep_num && ctx->epoch_positions >= ctx->sweep_min &&
-            (rc = fgpu_load_sweep(ctx))) return rc;
-    }
+    if ((rc = epoch_after_batch(ctx, span, fgpu_load_sweep))) return rc;
     return fgpu_resident_keep(ctx);
 }
 
@@ -829,6 +983,93 @@ int fgpu_stage_fixup(fgpu_ctx* ctx, const uint32_t* prefix) {
                         r.n_words, ctx->fd, prefix, f, r.tb, ctx->bloo2, (unsigned long long*)r.sure.p, ctx->counters);
         }
     }
+    return FGPU_OK;
+}
+
+// ---- the filter-sliced pass (fgpu_load_slice_*) ----------------------------------------------------------------------------------------
+static Slice slice_of(const fgpu_ctx* ctx) { return Slice{ctx->slice_pair, ctx->slice_first, ctx->slice_lo, ctx->slice_n}; }
+
+// the epoch machinery of fgpu_load_sweep on the slice: one streaming pass over the slice's first[]
+int fgpu_slice_sweep(fgpu_ctx* ctx) {
+    if (ctx->epoch_positions == 0) return FGPU_OK;
+    if (ctx->slice_n) FGPU_LAUNCH("slice_carry_update", k_carry_from_first, 4096, 256, ctx->slice_pair, (const uint4*)ctx->slice_first, ctx->slice_n);
+    ctx->swept_positions += ctx->epoch_positions;
+    ctx->epoch_positions = 0;
+    return FGPU_OK;
+}
+
+// mark + resolve of one batch against the slice.  The batch is kept in HBM first (codes, bad, its fail plane, room for `sure`): the commit
+// needs every batch again once the planes have been ORed across the ranks, so a batch that cannot be kept is an error, not a silent skip.
+int fgpu_stage_slice_load(fgpu_ctx* ctx) {
+    BatchBufs& bb = *ctx->cur;
+    if (bb.T == 0) return FGPU_OK;
+    const uint64_t plane_stride = bb.n_words + FGPU_PADW;
+    const uint64_t cb = 2 * plane_stride * 8, pb = plane_stride * 8;
+    if (!ctx->resident_open || ctx->resident_bytes + cb + 3 * pb > ctx->resident_budget) {
+        ctx->err = "load_slice_batch: the batch does not fit the budget for resident batches (" + std::to_string(ctx->resident_budget) +
+                   " bytes, " + std::to_string(ctx->resident_bytes) + " in use; FGPU_FLAG_NO_RESIDENT sets it to 0): a sliced pass keeps every batch";
+        return FGPU_ERR_NOMEM;
+    }
+    int rc = fgpu_ensure_b(ctx, &bb.pending, (MISS_PLANES + 1) * plane_stride * 8);
+    if (rc) return rc;
+    if (ctx->resident_count == ctx->resident.size()) ctx->resident.push_back(new ResidentBatch());
+    ResidentBatch& r = *ctx->resident[ctx->resident_count];
+    if ((rc = fgpu_ensure_b(ctx, &r.codes, cb)) || (rc = fgpu_ensure_b(ctx, &r.bad, pb)) || (rc = fgpu_ensure_b(ctx, &r.sure, pb)) ||
+        (rc = fgpu_ensure_b(ctx, &r.fail, pb))) {
+        ctx->err = "load_slice_batch: no device memory to keep the batch resident (budget " + std::to_string(ctx->resident_budget) + " bytes): " + ctx->err;
+        return FGPU_ERR_NOMEM;
+    }
+    if ((rc = fgpu_util_count_segments(ctx, ctx->fd.k))) return rc;
+    // times are positions within the epoch, as in fgpu_stage_load: a sweep before the 32-bit clock would wrap
+    const uint64_t span = bb.n_words * 64;
+    if ((rc = epoch_before_batch(ctx, span, fgpu_slice_sweep))) return rc;
+    const uint32_t tb = ctx->carry_by_set ? 0u : (uint32_t)ctx->epoch_positions;
+    const unsigned grid = fgpu_grid(span, 256);
+    const Slice s = slice_of(ctx);
+    uint64_t* fail = (uint64_t*)r.fail.p;
+    FGPU_HIP(hipMemsetAsync(fail + bb.n_words, 0, FGPU_PADW * 8, ctx->stream));   // the plane is ORed in 16-byte granules: zero past its last word
+    FGPU_LAUNCH("slice_mark", k_slice_mark, grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p, bb.T, bb.n_words, ctx->fd, s, tb,
+                (uint64_t*)bb.pending.p, plane_stride, fail, ctx->counters);
+    FGPU_LAUNCH("slice_resolve", k_slice_resolve, grid, 256, (const uint64_t*)bb.codes.p, bb.n_words, ctx->fd, s, tb, (const uint64_t*)bb.pending.p,
+                plane_stride, fail);
+    if (ctx->carry_by_set)
+        FGPU_LAUNCH("slice_carry_update", k_slice_carry_set, grid, 256, (const uint64_t*)bb.codes.p, bb.n_words, ctx->fd, s,
+                    (const uint64_t*)bb.pending.p, plane_stride);
+    if ((rc = epoch_after_batch(ctx, span, fgpu_slice_sweep))) return rc;
+    r.T = bb.T;
+    r.n_words = bb.n_words;
+    r.tb = tb;
+    FGPU_HIP(hipMemcpyAsync(r.codes.p, bb.codes.p, cb, hipMemcpyDeviceToDevice, ctx->stream));
+    FGPU_HIP(hipMemcpyAsync(r.bad.p, bb.bad.p, pb, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->resident_count++;
+    ctx->resident_bytes += cb + 3 * pb;
+    return FGPU_OK;
+}
+
+int fgpu_stage_slice_commit(fgpu_ctx* ctx) {
+    const Slice s = slice_of(ctx);
+    for (uint64_t i = 0; i < ctx->resident_count; i++) {
+        ResidentBatch& r = *ctx->resident[i];
+        FGPU_LAUNCH("slice_commit", k_slice_commit, fgpu_grid(r.n_words * 64, 256), 256, (const uint64_t*)r.codes.p, (const uint64_t*)r.bad.p, r.T,
+                    r.n_words, ctx->fd, s, (const uint64_t*)r.fail.p, (uint64_t*)r.sure.p, ctx->counters);
+    }
+    return FGPU_OK;
+}
+
+// the slice's working state: an empty carry, an empty bloo2, every time "never"
+int fgpu_slice_pair_begin(fgpu_ctx* ctx) {
+    if (!ctx->slice_n) return FGPU_OK;
+    FGPU_HIP(hipMemsetAsync(ctx->slice_pair, 0, ctx->slice_n / 4, ctx->stream));
+    FGPU_HIP(hipMemsetAsync(ctx->slice_first, 0xFF, ctx->slice_n * 4, ctx->stream));
+    return FGPU_OK;
+}
+// bloo1 / bloo2 := the own slice at its place in the tai/8-byte arrays, zero outside it
+int fgpu_slice_pair_end(fgpu_ctx* ctx) {
+    FGPU_HIP(hipMemsetAsync(ctx->bloo1, 0, ctx->bloom_bytes, ctx->stream));
+    FGPU_HIP(hipMemsetAsync(ctx->bloo2, 0, ctx->bloom_bytes, ctx->stream));
+    if (ctx->slice_n)
+        FGPU_LAUNCH("pair_split", k_pair_split, 2048, 256, (const uint2*)ctx->slice_pair, ctx->bloo1 + ctx->slice_lo / 32, ctx->bloo2 + ctx->slice_lo / 32,
+                    ctx->slice_n / 32);
     return FGPU_OK;
 }
 

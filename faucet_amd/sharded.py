@@ -165,10 +165,11 @@ def load_sharded(backend, batches, rank: int, world: int):
     return load_sharded_presence(backend, batches, rank, world)
 
 
-def _slices(nbytes: int, world: int):
-    """[lo, hi) byte ranges of the `world` slices of a bitmap: equal, 16-byte aligned (the OR kernel's granule), the last one short"""
+def _slices(nbytes: int, world: int, align: int = 16):
+    """[lo, hi) byte ranges of the `world` slices of a bitmap: equal, `align`-byte aligned (16: the OR kernel's granule; 64: filter slices,
+    512 bit positions), the last one short"""
     step = -(-nbytes // world)
-    step = (step + 15) & ~15
+    step = (step + align - 1) & ~(align - 1)
     return [(min(q * step, nbytes), min((q + 1) * step, nbytes)) for q in range(world)]
 
 
@@ -297,6 +298,44 @@ def load_sharded_presence(backend, batches, rank: int, world: int):
     or_allreduce(backend, backend.bloom_tensor(L.BLOO2), rank, world)
     backend.fence()
     CLOCK.mark("pass1_or_allreduce")
+    return stats
+
+
+def _gather_slices(backend, bitmap, sl, rank: int, world: int):
+    """every rank holds slice `rank` of `bitmap`; afterwards every rank holds all of them (the all-gather step of or_allreduce)"""
+    if world == 1:
+        return
+    lo, hi = sl[rank]
+    others = [q for q in range(world) if q != rank]
+    backend.fence()
+    _exchange([(bitmap[lo:hi], q) for q in others] if hi > lo else [],
+              [(bitmap[sl[q][0]:sl[q][1]], q) for q in others if sl[q][1] > sl[q][0]])
+
+
+def load_sliced(backend, batches, rank: int, world: int):
+    """Pass 1 by FILTER SLICES: `batches` is the WHOLE stream -- the same batches, in file order, on every rank --
+    and rank r owns slice r of the filters' bit positions (64-byte boundaries: 512 bits).  Every rank finds the first-set times of its own
+    bits from the stream alone and writes, per stream position, whether one of ITS bits of the occurrence was not set before it (the fail
+    plane); the OR of the planes over the ranks is the sequential run's routing decision, after which every rank sets its own bloo2 bits
+    and the slices are gathered.  No presence pass, no prefix-OR, no fix-up.  Returns the load stats -- the whole run's, the same on every
+    rank; afterwards every rank holds the global bloo1 and bloo2.  A function of its own beside load_sharded: it takes the stream, not a shard."""
+    nbytes = backend.bloom_tensor(L.BLOO1).numel()
+    sl = _slices(nbytes, world, 64)
+    lo, hi = sl[rank]
+    CLOCK.mark("pass1_begin")
+    backend.slice_load(batches, lo * 8, hi * 8)
+    CLOCK.mark("pass1_slice_load")
+    for plane in backend.slice_planes():
+        or_allreduce(backend, plane, rank, world)
+    backend.fence()      # the reduced planes are in place before the library's commit kernels read them
+    CLOCK.mark("pass1_fail_or")
+    backend.slice_commit()
+    stats = backend.slice_end()
+    CLOCK.mark("pass1_commit")
+    for which in (L.BLOO1, L.BLOO2):
+        _gather_slices(backend, backend.bloom_tensor(which), sl, rank, world)
+    backend.fence()
+    CLOCK.mark("pass1_gather")
     return stats
 
 
@@ -514,7 +553,10 @@ def run_in_turn(make_backend, shards, protocol: str = "presence", after_load=Non
 
         make_backend()   -> a backend with GpuShard's methods (and close())
         shards           -> the ranks' batch lists, in file order
-        protocol         -> "presence" | "fixup" (pass 1)
+        protocol         -> "presence" | "fixup" | "slices" (pass 1).  "slices" (load_sliced): the concatenation of `shards` is the stream
+                            every rank loads into its slice of the filter bits; the N contexts are open AT ONCE (4.25 bytes per own bit each:
+                            they fit one device side by side), the phases run rank after rank, and after_load is called once, with
+                            r = world - 1 and the final filters
         after_load(r, stats, bloo1, bloo2): bloo1 / bloo2 = the SEQUENTIAL run's filters after shard r (tensors; valid during the call)
         after_scan(r, stats, backend):      backend.junctions() = the sequential run's map after shard r
 
@@ -533,7 +575,39 @@ def run_in_turn(make_backend, shards, protocol: str = "presence", after_load=Non
             b.fence()
             pres.append(b.bloom_tensor(L.BLOO1).clone())
             close(b)
+    if protocol == "slices":
+        stream = [batch for sh in shards for batch in sh]
+        backs = [make_backend() for _ in range(world)]
+        sl = _slices(backs[0].bloom_tensor(L.BLOO1).numel(), world, 64)
+        for r, b in enumerate(backs):
+            b.slice_load(stream, sl[r][0] * 8, sl[r][1] * 8)
+            b.fence()
+        planes = [b.slice_planes() for b in backs]
+        for i in range(len(planes[0])):                  # the OR-allreduce of every fail plane: reduced on rank 0, copied to the others
+            for r in range(1, world):
+                _or_by_slices(backs[0], planes[0][i], planes[r][i], world)
+            backs[0].fence()
+            for r in range(1, world):
+                planes[r][i].copy_(planes[0][i])
+        for b in backs:
+            b.fence()
+            b.slice_commit()
+            load_stats.append(b.slice_end())
+            b.fence()
+        running, acc2 = torch.zeros_like(backs[0].bloom_tensor(L.BLOO1)), torch.zeros_like(backs[0].bloom_tensor(L.BLOO2))
+        for r, b in enumerate(backs):                    # the all-gather: every rank's byte range into place
+            lo, hi = sl[r]
+            running[lo:hi].copy_(b.bloom_tensor(L.BLOO1)[lo:hi])
+            acc2[lo:hi].copy_(b.bloom_tensor(L.BLOO2)[lo:hi])
+        backs[-1].fence()
+        if after_load:
+            after_load(world - 1, load_stats[-1], running, acc2)
+        del planes
+        for b in backs:
+            close(b)
     for r in range(world):
+        if protocol == "slices":       # (loaded above, all ranks at once)
+            break
         b = make_backend()
         b.clear_filters()
         b1 = b.bloom_tensor(L.BLOO1)
@@ -729,6 +803,23 @@ class GpuShard:
 
     def or_tensor(self, dst, src):
         self.ctx.bitmap_or(dst.data_ptr(), src.data_ptr(), dst.numel())
+
+    # pass 1 by filter slices (load_sliced)
+    def slice_load(self, batches, bit_lo, bit_hi):
+        """the whole stream against the own bits [bit_lo, bit_hi); the batches and their fail planes stay in HBM"""
+        self.ctx.load_slice_begin(bit_lo, bit_hi)
+        for b in batches:
+            self.ctx.load_slice_batch(b)
+
+    def slice_planes(self):
+        """the fail planes of the pass' non-empty batches, in batch order, as device tensors (to be ORed across the ranks in place)"""
+        return [torch.as_tensor(_DevView(*self.ctx.load_slice_plane(i)), device=self.device) for i in range(self.ctx.load_slice_state()[2])]
+
+    def slice_commit(self):
+        self.ctx.load_slice_commit()
+
+    def slice_end(self):
+        return self.ctx.load_slice_end()
 
     def load_fixup(self, prefix):
         return self.ctx.load_fixup(prefix.data_ptr())

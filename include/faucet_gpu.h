@@ -197,6 +197,45 @@ int fgpu_load_fixup(fgpu_ctx* ctx, const void* prefix_dev, fgpu_load_stats* stat
  * load batches resident in; a shard's batches need about one byte per base (codes, bad, sure, and up to four fail planes). */
 int fgpu_load_fixup_state(fgpu_ctx* ctx, int* ready, uint64_t* resident_budget_bytes);
 
+/* ---- pass 1 by FILTER SLICES: every rank loads the WHOLE stream into its slice of the bit positions ----------------
+ * The transposed partition of the multi-GPU pass: instead of a shard of the reads and all of the filter, a rank sees every batch (the same
+ * batches, in file order, on every rank) and owns the filter bits [bit_lo, bit_hi) -- both multiples of 512, bit_hi <= tai, any number of
+ * slices, an empty one included.  Exact because "bit b was first set at time t" is a property of bit b alone: the owner finds it from the
+ * stream, and occurrence t goes to bloo2 iff NO rank reports "one of my bits of occurrence t was not set before t".  That report is one bit
+ * per stream position per rank, the FAIL PLANE of a batch; the caller ORs the planes of all ranks in place (fgpu_bitmap_or, or any transport),
+ * then fgpu_load_slice_commit sets the own bloo2 bits of the occurrences nobody failed.  No presence pass, no prefix-OR, no fix-up.
+ *
+ *     fgpu_load_slice_begin(lo, hi);  fgpu_load_slice_batch(b) ...;               every rank, the same batches
+ *     for every batch i: fgpu_load_slice_plane(i, &p, &n);  p := OR over ranks     the exchange (caller)
+ *     fgpu_load_slice_commit();  fgpu_load_slice_end(&stats);
+ *
+ * Working state: 4.25 bytes per OWN bit (first-set times + the interleaved {carry, bloo2} pair), always the pair layout
+ * (FGPU_LOAD_LAYOUT=records is not used here).  Every batch stays resident in HBM (packed codes, bad mask, fail plane, later the `sure`
+ * plane): 5 bits per stream position; a batch that cannot be kept -- FGPU_FLAG_NO_RESIDENT, or beyond the budget
+ * (fgpu_load_fixup_state) -- makes fgpu_load_slice_batch return FGPU_ERR_NOMEM.  Stream-ordered on the context's stream like the rest.
+ * FGPU_ERR_STATE: _begin while a pass is open or with FGPU_FLAG_MERCY (the mercy rule needs time-aware tests of other slices' bits);
+ * _batch / _plane / _commit / _end outside a sliced pass; _batch after _commit; _commit twice; _end before _commit; fgpu_load_batch inside
+ * a sliced pass; fgpu_load_fixup after one.  FGPU_ERR_ARG: bounds that are not multiples of 512, bit_lo > bit_hi, bit_hi > tai, a batch index
+ * out of range. */
+int fgpu_load_slice_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi);
+/* mark + resolve of one batch against the slice; the batch and its fail plane stay in HBM */
+int fgpu_load_slice_batch(fgpu_ctx* ctx, const fgpu_reads* reads);
+/* The fail plane of the i-th NON-EMPTY batch of the pass: one bit per stream position of the batch's packed stream (64 positions per word, LSB =
+ * lowest position), *nbytes padded with zero words to a multiple of 16 (fgpu_bitmap_or's granule).  The layout follows from the batch alone:
+ * identical batches give identical layouts on every rank, which is what makes the OR across ranks meaningful.  To be ORed IN PLACE.  Does not
+ * synchronise: the plane is complete in stream order behind the fgpu_load_slice_batch that made it. */
+int fgpu_load_slice_plane(fgpu_ctx* ctx, uint64_t batch, void** fail_dev, uint64_t* nbytes);
+/* After the planes hold the OR over all ranks: the own bloo2 bits of every occurrence whose fail bit is 0, the batches' `sure` planes
+ * (= valid & ~fail, the global routing decision: a scan of the same reads in this context reuses them as after a plain load). */
+int fgpu_load_slice_commit(fgpu_ctx* ctx);
+/* bloo1 / bloo2 of the context (fgpu_bloom_devptr, tai/8 bytes) then hold the own slice and are ZERO outside it: the all-gather is a copy of the
+ * byte ranges [bit_lo/8, bit_hi/8) or a plain fgpu_bitmap_or.  stats: reads_processed, unambiguous_reads, kmers as a plain load of the whole
+ * stream; to_bloo2 = the GLOBAL count, the same on every rank. */
+int fgpu_load_slice_end(fgpu_ctx* ctx, fgpu_load_stats* stats);
+/* *ready (may be NULL): 1 inside a sliced pass that has not been committed yet.  *working_bytes (may be NULL): device bytes allocated for the
+ * slice state (first-set times + pair).  *n_batches (may be NULL): planes fgpu_load_slice_plane can hand out (0 outside a sliced pass). */
+int fgpu_load_slice_state(fgpu_ctx* ctx, int* ready, uint64_t* working_bytes, uint64_t* n_batches);
+
 /* filters: raw bit arrays, tai/8 bytes, exactly the .bloom file body (utils/Bloom.cpp:571-587) */
 int fgpu_bloom_download(fgpu_ctx* ctx, int which, uint8_t* host_out, uint64_t nbytes);
 /* The same copy, started now and finished by fgpu_bloom_download_wait: it runs on its own copy stream behind the work
