@@ -82,6 +82,10 @@ SIGNATURES = {
     "fgpu_load_slice_commit": (C.c_int, [_vp]),
     "fgpu_load_slice_end": (C.c_int, [_vp, _P(LoadStats)]),
     "fgpu_load_slice_state": (C.c_int, [_vp, _P(C.c_int), _P(_u64), _P(_u64)]),
+    "fgpu_load_slice_mercy_begin": (C.c_int, [_vp, _u64, _u64]),
+    "fgpu_load_slice_mercy_probe": (C.c_int, [_vp]),
+    "fgpu_load_slice_mercy_planes": (C.c_int, [_vp, _u64, _P(_vp), _P(_u64)]),
+    "fgpu_diag_slice_mercy": (C.c_int, [_vp, _P(_u64)]),
     "fgpu_scan_dump_order": (C.c_int, [_vp, _P(C.c_uint64), _P(C.c_uint64), C.c_uint64, C.c_uint64, _P(C.c_uint32)]),
     "fgpu_bloom_download": (C.c_int, [_vp, C.c_int, _vp, _u64]),
     "fgpu_bloom_download_begin": (C.c_int, [_vp, C.c_int, _vp, _u64]),

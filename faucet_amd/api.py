@@ -225,6 +225,27 @@ class Context:
         self._c(self.lib.fgpu_load_slice_state(self.h, C.byref(ready), C.byref(wb), C.byref(nb)))
         return bool(ready.value), int(wb.value), int(nb.value)
 
+    # ... under --mercy: batch, exchange of its fail plane, probe, in lockstep; the miss planes are exchanged before the commit
+    def load_slice_mercy_begin(self, bit_lo: int, bit_hi: int):
+        self._c(self.lib.fgpu_load_slice_mercy_begin(self.h, bit_lo, bit_hi))
+
+    def load_slice_mercy_probe(self):
+        """the latest batch, after its fail plane has been ORed across the ranks: its four miss planes, then the batch joins the carry"""
+        self._c(self.lib.fgpu_load_slice_mercy_probe(self.h))
+
+    def load_slice_mercy_planes(self, i: int):
+        """(device pointer, bytes) of the four miss planes of the i-th non-empty batch, one block: to be ORed across the ranks in place"""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._c(self.lib.fgpu_load_slice_mercy_planes(self.h, i, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def diag_slice_mercy(self):
+        """the last mercy pass by slices: [positions this rank probed, high->low tests answered "junction", runs opened, low->high tests
+        answered "junction", runs added, k-mers added by runs] -- all but the first the same on every rank"""
+        out = (C.c_uint64 * 6)()
+        self._c(self.lib.fgpu_diag_slice_mercy(self.h, out))
+        return [int(x) for x in out]
+
     def load_batch(self, batch: ReadBatch):
         s = batch.c_struct()
         self._c(self.lib.fgpu_load_batch(self.h, C.byref(s)))

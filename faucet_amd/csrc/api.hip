@@ -565,11 +565,17 @@ int fgpu_load_fixup(fgpu_ctx* ctx, const void* prefix_dev, fgpu_load_stats* stat
 }
 
 // ---- pass 1 by filter slices: the whole stream into one slice of the bit positions ------------------------------
-int fgpu_load_slice_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi) {
+// `mercy`: the pass is opened by fgpu_load_slice_mercy_begin (batch, exchange, probe in lockstep; four miss planes per batch)
+static int slice_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi, bool mercy) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 0) { ctx->err = "load_slice_begin while another pass is open"; return FGPU_ERR_STATE; }
-    if (ctx->prm.flags & FGPU_FLAG_MERCY) {
-        ctx->err = "load_slice_begin: --mercy needs time-aware membership tests of the other slices' bits; not available under filter slices";
+    if (!mercy && (ctx->prm.flags & FGPU_FLAG_MERCY)) {
+        ctx->err = "load_slice_begin: --mercy needs time-aware membership tests of the other slices' bits: a probe of every batch between its "
+                   "exchange and the next batch -- open the pass with fgpu_load_slice_mercy_begin and drive the five-step protocol";
+        return FGPU_ERR_STATE;
+    }
+    if (mercy && !(ctx->prm.flags & FGPU_FLAG_MERCY)) {
+        ctx->err = "load_slice_mercy_begin: the context was created without FGPU_FLAG_MERCY (fgpu_load_slice_begin opens the plain sliced pass)";
         return FGPU_ERR_STATE;
     }
     if ((bit_lo & 511) || (bit_hi & 511) || bit_lo > bit_hi || bit_hi > ctx->prm.tai) {
@@ -602,6 +608,9 @@ int fgpu_load_slice_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi) {
     ctx->slice_lo = bit_lo;
     ctx->slice_n = n;
     ctx->slice_committed = false;
+    ctx->slice_mercy = mercy;
+    ctx->slice_probe_owed = false;
+    ctx->slice_owed_span = 0;
     ctx->shard_times = ctx->shard_planes = ctx->fixup_ready = false;
     ctx->rec_layout = false;
     ctx->pass_positions = ctx->pass_batches = 0;
@@ -618,10 +627,18 @@ int fgpu_load_slice_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi) {
     return FGPU_OK;
 }
 
+int fgpu_load_slice_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi) { return slice_begin(ctx, bit_lo, bit_hi, false); }
+int fgpu_load_slice_mercy_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi) { return slice_begin(ctx, bit_lo, bit_hi, true); }
+
 int fgpu_load_slice_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 3) { ctx->err = "load_slice_batch outside load_slice_begin/load_slice_end"; return FGPU_ERR_STATE; }
     if (ctx->slice_committed) { ctx->err = "load_slice_batch after load_slice_commit: the pass can only be ended"; return FGPU_ERR_STATE; }
+    if (ctx->slice_probe_owed) {
+        ctx->err = "load_slice_batch: the previous batch of this mercy pass has not been probed (fgpu_load_slice_mercy_probe, after its fail plane "
+                   "has been ORed): its first-set times must be read before the next batch is marked";
+        return FGPU_ERR_STATE;
+    }
     int rc = check_reads(ctx, reads);
     if (rc) return rc;
     FGPU_HIP(hipSetDevice(ctx->prm.device));
@@ -642,10 +659,39 @@ int fgpu_load_slice_plane(fgpu_ctx* ctx, uint64_t batch, void** fail_dev, uint64
     return FGPU_OK;
 }
 
+int fgpu_load_slice_mercy_probe(fgpu_ctx* ctx) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 3 || !ctx->slice_mercy) { ctx->err = "load_slice_mercy_probe outside a pass opened by load_slice_mercy_begin"; return FGPU_ERR_STATE; }
+    if (!ctx->slice_probe_owed) return FGPU_OK;      // an empty batch, or nothing since the last probe
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    return fgpu_stage_slice_mercy_probe(ctx);
+}
+
+int fgpu_load_slice_mercy_planes(fgpu_ctx* ctx, uint64_t batch, void** miss_dev, uint64_t* nbytes) {
+    if (!ctx || !miss_dev) return FGPU_ERR_ARG;
+    if (ctx->phase != 3 || !ctx->slice_mercy) { ctx->err = "load_slice_mercy_planes outside a pass opened by load_slice_mercy_begin"; return FGPU_ERR_STATE; }
+    if (batch >= ctx->resident_count) { ctx->err = "load_slice_mercy_planes: no such batch (empty batches keep no planes)"; return FGPU_ERR_ARG; }
+    if (ctx->slice_probe_owed && batch == ctx->resident_count - 1) {
+        ctx->err = "load_slice_mercy_planes: this batch has not been probed yet (fgpu_load_slice_mercy_probe)";
+        return FGPU_ERR_STATE;
+    }
+    const ResidentBatch& r = *ctx->resident[batch];
+    *miss_dev = r.miss.p;
+    if (nbytes) *nbytes = 4 * (r.n_words + FGPU_PADW) * 8;      // four planes of the fail plane's padded stride, one block
+    return FGPU_OK;
+}
+
+int fgpu_diag_slice_mercy(fgpu_ctx* ctx, uint64_t out[6]) {
+    if (!ctx || !out) return FGPU_ERR_ARG;
+    for (int i = 0; i < 6; i++) out[i] = ctx->slice_mercy_diag[i];
+    return FGPU_OK;
+}
+
 int fgpu_load_slice_commit(fgpu_ctx* ctx) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 3) { ctx->err = "load_slice_commit outside load_slice_begin/load_slice_end"; return FGPU_ERR_STATE; }
     if (ctx->slice_committed) { ctx->err = "load_slice_commit twice in one pass"; return FGPU_ERR_STATE; }
+    if (ctx->slice_probe_owed) { ctx->err = "load_slice_commit: the last batch of this mercy pass has not been probed (fgpu_load_slice_mercy_probe)"; return FGPU_ERR_STATE; }
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     int rc = fgpu_stage_slice_commit(ctx);
     if (rc) return rc;
@@ -665,6 +711,7 @@ int fgpu_load_slice_end(fgpu_ctx* ctx, fgpu_load_stats* stats) {
     ctx->load_stats.kmers = ctx->counters_host->kmers;
     ctx->load_stats.to_bloo2 = ctx->counters_host->to_bloo2;
     ctx->load_mark_hits = 0;
+    for (int i = 0; i < 6; i++) ctx->slice_mercy_diag[i] = ctx->slice_mercy ? ctx->counters_host->slice_mercy[i] : 0;
     ctx->load_mark_pending = ctx->counters_host->mark_pending;
     ctx->load_stats.unambiguous_reads = ctx->counters_host->segments;
     if (stats) *stats = ctx->load_stats;

@@ -77,6 +77,7 @@ struct BatchBufs {
 struct ResidentBatch {
     DevBuf codes, bad, sure;
     DevBuf fail;                 // read shards: the resolve kernel's "bit i was not set before the occurrence" planes (fgpu_load_fixup)
+    DevBuf miss;                 // sliced pass under --mercy: four planes "an own bit of candidate nt was not set by this position" (k_slice_mercy_probe)
     uint64_t T = 0, n_words = 0;
     uint32_t tb = 0;             // time base of the batch's first-set times (FGPU_LOAD_SHARD_TIMES: position within the pass)
 };
@@ -183,6 +184,9 @@ struct DevCounters {
     unsigned long long ovw_fill;        // ... the most event-table entries a round of any window has held (k_ovw_commit counts them): the host grows the tables on it
     unsigned long long late_n[3];       // ([2] noted positions the check has passed over: every one of [0], once)
     unsigned long long late[2 * FGPU_LATE_CAP];
+    // sliced pass under --mercy (fgpu_diag_slice_mercy): positions this rank probed; high->low tests answered "junction", runs opened,
+    // low->high tests answered "junction", runs added, k-mers added by runs (the five of k_slice_mercy_commit: the same on every rank)
+    unsigned long long slice_mercy[6];
 };
 
 // (three sets since round 6: with two, the split of chunk c + 1 could only begin when batch c - 1 had finished, and the batch cut out of it was queued
@@ -239,6 +243,10 @@ struct fgpu_ctx {
     uint2* slice_pair = nullptr;     // {carry word, bloo2 word} per 32 own bits
     uint64_t slice_first_bytes = 0, slice_pair_bytes = 0;   // as allocated
     bool slice_committed = false;    // fgpu_load_slice_commit has run in this pass
+    bool slice_mercy = false;        // the pass was opened by fgpu_load_slice_mercy_begin: batch, exchange, probe in lockstep
+    bool slice_probe_owed = false;   // ... and its latest batch has not been probed (nor folded into the carry) yet
+    uint64_t slice_owed_span = 0;    // stream positions of that batch: what the deferred fold adds to the epoch
+    uint64_t slice_mercy_diag[6] = {0, 0, 0, 0, 0, 0};   // DevCounters::slice_mercy of the last mercy pass, as of fgpu_load_slice_end
     std::vector<ResidentBatch*> resident;  // load batches kept for the scan, in load order (buffers recycled across passes)
     uint64_t resident_count = 0;     // entries of `resident` that hold the current load pass
     uint64_t resident_bytes = 0, resident_budget = 0;
@@ -496,6 +504,7 @@ int fgpu_stage_fixup(fgpu_ctx* ctx, const uint32_t* prefix);
 int fgpu_stage_presence(fgpu_ctx* ctx);
 int fgpu_stage_slice_load(fgpu_ctx* ctx);
 int fgpu_stage_slice_commit(fgpu_ctx* ctx);
+int fgpu_stage_slice_mercy_probe(fgpu_ctx* ctx);
 int fgpu_slice_sweep(fgpu_ctx* ctx);
 int fgpu_slice_pair_begin(fgpu_ctx* ctx);
 int fgpu_slice_pair_end(fgpu_ctx* ctx);

@@ -733,6 +733,137 @@ __global__ void __launch_bounds__(256) k_slice_commit(const uint64_t* __restrict
     block_add(&cnt->to_bloo2, n_go);
 }
 
+// ---- --mercy under filter slices -------------------------------------------------------------------------------------
+// isJunction asks bloo1, as of occurrence t, about k-mers whose bits lie in any slice.  "Bit b was set by time t" (in the carry, or
+// first[b] <= t: bloo1_contains_at) concerns b alone, so its owner answers it, and a candidate is contained iff NO rank finds an own bit of it
+// unset: one miss bit per (position, nt) per rank, ORed over the ranks, is "the candidate was not in bloo1".  Which tests the reference makes
+// depends on earlier answers; a miss bit where no test is made is never read, so the probe evaluates a superset that follows from `bad` and the
+// ORed fail plane alone: every window but the first of its segment that is not contained, or is contained behind one that is not.  The
+// direction is the reference's (mercy_is_junction): a contained window extends its reverse complement (the low -> high test), any other the
+// k-mer itself.  Must run while first[] still answers "<= t" for this batch: before the batch is folded into the carry.
+constexpr int MERCY_NT = 4;   // planes of the probe: one per candidate nucleotide
+__global__ void __launch_bounds__(256) k_slice_mercy_probe(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ bad, uint64_t T,
+                                                           uint64_t n_words, FdParams fp, Slice s, uint32_t tb, const uint64_t* __restrict__ fail,
+                                                           uint64_t* __restrict__ miss, uint64_t plane_stride, DevCounters* cnt) {
+    unsigned long long n_probed = 0;
+    const uint64_t total = n_words * 64;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t missed = 0;
+        // not the first window of its segment: position p - 1 is good, so window p - 1 is valid and its fail bit is its routing
+        if (p && p < T && fd_window_ok(bad, p, fp.k) && !((bad[(p - 1) >> 6] >> ((p - 1) & 63)) & 1ULL)) {
+            const bool contained = !((fail[p >> 6] >> (p & 63)) & 1ULL);
+            const bool prev_contained = !((fail[(p - 1) >> 6] >> ((p - 1) & 63)) & 1ULL);
+            if (!contained || !prev_contained) {
+                n_probed++;
+                const uint64_t km = fd_kmer_at(codes, p, fp.k), rc = fd_revcomp(km, fp.k);
+                const uint64_t real_ext = ((rc << 2) | (uint64_t)(fd_base_at(codes, p - 1) ^ 2)) & fp.kmask;
+                const uint64_t from = contained ? rc : km;
+                const uint32_t t = tb + (uint32_t)p;
+                for (int nt = 0; nt < MERCY_NT; nt++) {
+                    const uint64_t e = ((from << 2) | (uint64_t)nt) & fp.kmask;
+                    if (e == real_ext) continue;
+                    uint64_t hA, hB;
+                    fd_hash_pair(fd_canon(e, fp.k), fp.tai_mask, hA, hB);
+                    uint64_t h = hA;
+                    for (int i = 0; i < fp.n_hash; i++) {
+                        const uint64_t o = h - s.lo;   // a candidate without an own bit touches no memory
+                        if (s.owns(o) && !((s.pair[o >> 5].x >> (o & 31)) & 1u) && !(s.first[o] <= t)) {
+                            missed |= 1u << nt;
+                            break;
+                        }
+                        h = (h + hB) & fp.tai_mask;
+                    }
+                }
+            }
+        }
+        uint64_t mm[MERCY_NT];
+#pragma unroll
+        for (int nt = 0; nt < MERCY_NT; nt++) mm[nt] = __ballot((missed >> nt) & 1u);
+        if (fd_lane() == 0) {
+#pragma unroll
+            for (int nt = 0; nt < MERCY_NT; nt++) miss[nt * plane_stride + (p >> 6)] = mm[nt];
+        }
+    }
+    block_add(&cnt->slice_mercy[0], n_probed);
+}
+
+// After the ranks' miss planes have been ORed in place and k_slice_commit has written `sure` = valid & ~fail: the state machine of k_load_mercy,
+// one thread per 64-position word for the segments that START in it, with isJunction answered as "some nt != real_ext whose ORed miss bit is 0".
+// The OWN bloo2 bits of the k-mers of every accepted run are set; the five counts are global ones, the same on every rank.
+__global__ void __launch_bounds__(256) k_slice_mercy_commit(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ bad, uint64_t n_words,
+                                                            FdParams fp, Slice s, const uint64_t* __restrict__ sure,
+                                                            const uint64_t* __restrict__ miss, uint64_t plane_stride, DevCounters* cnt) {
+    unsigned long long n_hl_junction = 0, n_opened = 0, n_lh_junction = 0, n_added = 0, n_kmers = 0;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t good = ~bad[w];
+        const uint64_t prev_good = w ? (~bad[w - 1]) >> 63 : 0;
+        uint64_t starts = good & ~((good << 1) | prev_good);
+        while (starts) {
+            const uint64_t p = w * 64 + __builtin_ctzll(starts);
+            starts &= starts - 1;
+            uint64_t len = 0;                       // segment length: bad padding past the end terminates the scan
+            for (;;) {
+                const uint64_t v = fd_bits_at(bad, p + len);
+                if (v) { len += __builtin_ctzll(v); break; }
+                len += 64;
+            }
+            if (len < (uint64_t)fp.k) continue;
+            const uint64_t n = len - fp.k + 1;      // windows p .. p+n-1, processed in this order (utils/Bloom.cpp:303)
+            bool have_last = false;
+            int64_t hv_lo = -1;                     // first window of the current run, -1 = none
+            uint64_t sbits = 0;
+            for (uint64_t i = 0; i < n; i++) {
+                if ((i & 63) == 0) sbits = fd_bits_at(sure, p + i);
+                const bool contained = (sbits >> (i & 63)) & 1ULL;
+                const bool test = contained ? hv_lo >= 0 : have_last && hv_lo < 0;
+                if (contained) have_last = true;
+                if (!test) continue;
+                const uint64_t pos = p + i;         // (i > 0: both tests need an earlier window of the segment)
+                const uint64_t km = fd_kmer_at(codes, pos, fp.k), rc = fd_revcomp(km, fp.k);
+                const uint64_t real_ext = ((rc << 2) | (uint64_t)(fd_base_at(codes, pos - 1) ^ 2)) & fp.kmask;
+                const uint64_t from = contained ? rc : km;
+                bool junction = false;
+                for (int nt = 0; nt < MERCY_NT; nt++) {
+                    const uint64_t e = ((from << 2) | (uint64_t)nt) & fp.kmask;
+                    if (e != real_ext && !((miss[nt * plane_stride + (pos >> 6)] >> (pos & 63)) & 1ULL)) junction = true;
+                }
+                if (contained) {                    // came from low to high (:311-318)
+                    if (junction) {
+                        n_lh_junction++;
+                    } else {
+                        n_added++;
+                        for (uint64_t q = p + (uint64_t)hv_lo; q < pos; q++) {
+                            n_kmers++;
+                            uint64_t hA, hB;
+                            fd_hash_pair(fd_canon(fd_kmer_at(codes, q, fp.k), fp.k), fp.tai_mask, hA, hB);
+                            uint64_t h = hA;
+                            for (int b = 0; b < fp.n_hash; b++) {
+                                const uint64_t o = h - s.lo;
+                                if (s.owns(o)) {
+                                    const uint32_t bit = 1u << (o & 31);
+                                    if (!(s.pair[o >> 5].y & bit)) atomicOr(&s.pair[o >> 5].y, bit);
+                                }
+                                h = (h + hB) & fp.tai_mask;
+                            }
+                        }
+                    }
+                    hv_lo = -1;
+                } else if (junction) {              // came from high to low (:322-326); later low k-mers just join the run
+                    n_hl_junction++;
+                } else {
+                    n_opened++;
+                    hv_lo = (int64_t)i;
+                }
+            }
+        }
+    }
+    block_add(&cnt->slice_mercy[1], n_hl_junction);
+    block_add(&cnt->slice_mercy[2], n_opened);
+    block_add(&cnt->slice_mercy[3], n_lh_junction);
+    block_add(&cnt->slice_mercy[4], n_added);
+    block_add(&cnt->slice_mercy[5], n_kmers);
+}
+
 // multi-GPU helper: OR the bits of every k-mer into a bitmap, no ordering
 __global__ void __launch_bounds__(256) k_presence(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ bad,
                                                   uint64_t T, uint64_t n_words, FdParams fp, uint32_t* bitmap, DevCounters* cnt) {
@@ -998,6 +1129,16 @@ int fgpu_slice_sweep(fgpu_ctx* ctx) {
     return FGPU_OK;
 }
 
+// The batch joins the carry: by re-hashing its pending occurrences (their planes are still those of the batch in hand) or, once the epoch has
+// grown enough, by a sweep.  Right behind mark + resolve in a plain sliced pass, behind the probe in a mercy one.
+static int slice_fold_batch(fgpu_ctx* ctx, uint64_t span) {
+    BatchBufs& bb = *ctx->cur;
+    if (ctx->carry_by_set)
+        FGPU_LAUNCH("slice_carry_update", k_slice_carry_set, fgpu_grid(span, 256), 256, (const uint64_t*)bb.codes.p, bb.n_words, ctx->fd, slice_of(ctx),
+                    (const uint64_t*)bb.pending.p, bb.n_words + FGPU_PADW);
+    return epoch_after_batch(ctx, span, fgpu_slice_sweep);
+}
+
 // mark + resolve of one batch against the slice.  The batch is kept in HBM first (codes, bad, its fail plane, room for `sure`): the commit
 // needs every batch again once the planes have been ORed across the ranks, so a batch that cannot be kept is an error, not a silent skip.
 int fgpu_stage_slice_load(fgpu_ctx* ctx) {
@@ -1005,9 +1146,12 @@ int fgpu_stage_slice_load(fgpu_ctx* ctx) {
     if (bb.T == 0) return FGPU_OK;
     const uint64_t plane_stride = bb.n_words + FGPU_PADW;
     const uint64_t cb = 2 * plane_stride * 8, pb = plane_stride * 8;
-    if (!ctx->resident_open || ctx->resident_bytes + cb + 3 * pb > ctx->resident_budget) {
+    // a mercy pass keeps the four miss planes of the probe too: 9 instead of 5 bits per stream position
+    const uint64_t mb = ctx->slice_mercy ? MERCY_NT * pb : 0;
+    if (!ctx->resident_open || ctx->resident_bytes + cb + 3 * pb + mb > ctx->resident_budget) {
         ctx->err = "load_slice_batch: the batch does not fit the budget for resident batches (" + std::to_string(ctx->resident_budget) +
-                   " bytes, " + std::to_string(ctx->resident_bytes) + " in use; FGPU_FLAG_NO_RESIDENT sets it to 0): a sliced pass keeps every batch";
+                   " bytes, " + std::to_string(ctx->resident_bytes) + " in use; FGPU_FLAG_NO_RESIDENT sets it to 0): a sliced pass keeps every batch" +
+                   (ctx->slice_mercy ? ", under --mercy with four miss planes (9 bits per stream position)" : "");
         return FGPU_ERR_NOMEM;
     }
     int rc = fgpu_ensure_b(ctx, &bb.pending, (MISS_PLANES + 1) * plane_stride * 8);
@@ -1015,7 +1159,7 @@ int fgpu_stage_slice_load(fgpu_ctx* ctx) {
     if (ctx->resident_count == ctx->resident.size()) ctx->resident.push_back(new ResidentBatch());
     ResidentBatch& r = *ctx->resident[ctx->resident_count];
     if ((rc = fgpu_ensure_b(ctx, &r.codes, cb)) || (rc = fgpu_ensure_b(ctx, &r.bad, pb)) || (rc = fgpu_ensure_b(ctx, &r.sure, pb)) ||
-        (rc = fgpu_ensure_b(ctx, &r.fail, pb))) {
+        (rc = fgpu_ensure_b(ctx, &r.fail, pb)) || (mb && (rc = fgpu_ensure_b(ctx, &r.miss, mb)))) {
         ctx->err = "load_slice_batch: no device memory to keep the batch resident (budget " + std::to_string(ctx->resident_budget) + " bytes): " + ctx->err;
         return FGPU_ERR_NOMEM;
     }
@@ -1032,18 +1176,35 @@ int fgpu_stage_slice_load(fgpu_ctx* ctx) {
                 (uint64_t*)bb.pending.p, plane_stride, fail, ctx->counters);
     FGPU_LAUNCH("slice_resolve", k_slice_resolve, grid, 256, (const uint64_t*)bb.codes.p, bb.n_words, ctx->fd, s, tb, (const uint64_t*)bb.pending.p,
                 plane_stride, fail);
-    if (ctx->carry_by_set)
-        FGPU_LAUNCH("slice_carry_update", k_slice_carry_set, grid, 256, (const uint64_t*)bb.codes.p, bb.n_words, ctx->fd, s,
-                    (const uint64_t*)bb.pending.p, plane_stride);
-    if ((rc = epoch_after_batch(ctx, span, fgpu_slice_sweep))) return rc;
+    if (ctx->slice_mercy) {
+        // the fold is left to fgpu_stage_slice_mercy_probe: until then first[] answers "set by time t" for this batch's positions
+        ctx->slice_probe_owed = true;
+        ctx->slice_owed_span = span;
+    } else if ((rc = slice_fold_batch(ctx, span))) {
+        return rc;
+    }
     r.T = bb.T;
     r.n_words = bb.n_words;
     r.tb = tb;
     FGPU_HIP(hipMemcpyAsync(r.codes.p, bb.codes.p, cb, hipMemcpyDeviceToDevice, ctx->stream));
     FGPU_HIP(hipMemcpyAsync(r.bad.p, bb.bad.p, pb, hipMemcpyDeviceToDevice, ctx->stream));
     ctx->resident_count++;
-    ctx->resident_bytes += cb + 3 * pb;
+    ctx->resident_bytes += cb + 3 * pb + mb;
     return FGPU_OK;
+}
+
+// The probe of the latest batch of a mercy pass, then the fold that fgpu_stage_slice_load left out.  The batch's fail plane holds the OR over
+// the ranks by now (the caller's exchange, ordered before this call).
+int fgpu_stage_slice_mercy_probe(fgpu_ctx* ctx) {
+    ResidentBatch& r = *ctx->resident[ctx->resident_count - 1];
+    const uint64_t plane_stride = r.n_words + FGPU_PADW;
+    uint64_t* miss = (uint64_t*)r.miss.p;
+    for (int nt = 0; nt < MERCY_NT; nt++)     // the planes are ORed in 16-byte granules: zero past their last word
+        FGPU_HIP(hipMemsetAsync(miss + nt * plane_stride + r.n_words, 0, FGPU_PADW * 8, ctx->stream));
+    FGPU_LAUNCH("slice_mercy_probe", k_slice_mercy_probe, fgpu_grid(r.n_words * 64, 256), 256, (const uint64_t*)r.codes.p, (const uint64_t*)r.bad.p,
+                r.T, r.n_words, ctx->fd, slice_of(ctx), r.tb, (const uint64_t*)r.fail.p, miss, plane_stride, ctx->counters);
+    ctx->slice_probe_owed = false;
+    return slice_fold_batch(ctx, ctx->slice_owed_span);
 }
 
 int fgpu_stage_slice_commit(fgpu_ctx* ctx) {
@@ -1052,6 +1213,10 @@ int fgpu_stage_slice_commit(fgpu_ctx* ctx) {
         ResidentBatch& r = *ctx->resident[i];
         FGPU_LAUNCH("slice_commit", k_slice_commit, fgpu_grid(r.n_words * 64, 256), 256, (const uint64_t*)r.codes.p, (const uint64_t*)r.bad.p, r.T,
                     r.n_words, ctx->fd, s, (const uint64_t*)r.fail.p, (uint64_t*)r.sure.p, ctx->counters);
+        if (ctx->slice_mercy)     // the runs between solid k-mers, from the ORed miss planes and the `sure` plane just written
+            FGPU_LAUNCH("slice_mercy_commit", k_slice_mercy_commit, fgpu_grid(r.n_words, 256), 256, (const uint64_t*)r.codes.p,
+                        (const uint64_t*)r.bad.p, r.n_words, ctx->fd, s, (const uint64_t*)r.sure.p, (const uint64_t*)r.miss.p,
+                        r.n_words + FGPU_PADW, ctx->counters);
     }
     return FGPU_OK;
 }

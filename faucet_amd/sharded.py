@@ -323,12 +323,29 @@ def load_sliced(backend, batches, rank: int, world: int):
     sl = _slices(nbytes, world, 64)
     lo, hi = sl[rank]
     CLOCK.mark("pass1_begin")
-    backend.slice_load(batches, lo * 8, hi * 8)
-    CLOCK.mark("pass1_slice_load")
-    for plane in backend.slice_planes():
-        or_allreduce(backend, plane, rank, world)
-    backend.fence()      # the reduced planes are in place before the library's commit kernels read them
-    CLOCK.mark("pass1_fail_or")
+    if getattr(backend, "mercy", False):
+        # --mercy: isJunction asks bloo1 as of time t about bits of every slice, and a slice's first-set times answer that only until the
+        # batch joins the carry -- so batch, exchange of ITS fail plane and probe go in lockstep; the miss planes travel once, at the end
+        backend.slice_mercy_begin(lo * 8, hi * 8)
+        for b in batches:
+            plane = backend.slice_mercy_batch(b)
+            if plane is None:
+                continue
+            or_allreduce(backend, plane, rank, world)
+            backend.fence()  # the reduced plane is in place before the probe reads it
+            backend.slice_mercy_probe()
+        CLOCK.mark("pass1_slice_load")
+        for block in backend.slice_mercy_planes():
+            or_allreduce(backend, block, rank, world)
+        backend.fence()
+        CLOCK.mark("pass1_miss_or")
+    else:
+        backend.slice_load(batches, lo * 8, hi * 8)
+        CLOCK.mark("pass1_slice_load")
+        for plane in backend.slice_planes():
+            or_allreduce(backend, plane, rank, world)
+        backend.fence()      # the reduced planes are in place before the library's commit kernels read them
+        CLOCK.mark("pass1_fail_or")
     backend.slice_commit()
     stats = backend.slice_end()
     CLOCK.mark("pass1_commit")
@@ -579,16 +596,37 @@ def run_in_turn(make_backend, shards, protocol: str = "presence", after_load=Non
         stream = [batch for sh in shards for batch in sh]
         backs = [make_backend() for _ in range(world)]
         sl = _slices(backs[0].bloom_tensor(L.BLOO1).numel(), world, 64)
-        for r, b in enumerate(backs):
-            b.slice_load(stream, sl[r][0] * 8, sl[r][1] * 8)
-            b.fence()
-        planes = [b.slice_planes() for b in backs]
-        for i in range(len(planes[0])):                  # the OR-allreduce of every fail plane: reduced on rank 0, copied to the others
+
+        def or_across(per_rank):                         # an OR-allreduce in this process: reduced on rank 0, copied to the others
             for r in range(1, world):
-                _or_by_slices(backs[0], planes[0][i], planes[r][i], world)
+                _or_by_slices(backs[0], per_rank[0], per_rank[r], world)
             backs[0].fence()
             for r in range(1, world):
-                planes[r][i].copy_(planes[0][i])
+                per_rank[r].copy_(per_rank[0])
+
+        if getattr(backs[0], "mercy", False):            # --mercy: batch, exchange, probe in lockstep (load_sliced); then the miss planes
+            for r, b in enumerate(backs):
+                b.slice_mercy_begin(sl[r][0] * 8, sl[r][1] * 8)
+            for batch in stream:
+                planes = [b.slice_mercy_batch(batch) for b in backs]
+                if planes[0] is None:
+                    continue
+                for b in backs:
+                    b.fence()
+                or_across(planes)
+                for b in backs:
+                    b.fence()
+                    b.slice_mercy_probe()
+            for b in backs:
+                b.fence()
+            planes = [b.slice_mercy_planes() for b in backs]
+        else:
+            for r, b in enumerate(backs):
+                b.slice_load(stream, sl[r][0] * 8, sl[r][1] * 8)
+                b.fence()
+            planes = [b.slice_planes() for b in backs]
+        for i in range(len(planes[0])):                  # the OR-allreduce of every fail plane (--mercy: of every block of miss planes)
+            or_across([planes[r][i] for r in range(world)])
         for b in backs:
             b.fence()
             b.slice_commit()
@@ -817,6 +855,29 @@ class GpuShard:
 
     def slice_commit(self):
         self.ctx.load_slice_commit()
+
+    # ... under --mercy (load_sliced's lockstep)
+    @property
+    def mercy(self) -> bool:
+        return bool(getattr(self.ctx, "mercy", False))
+
+    def slice_mercy_begin(self, bit_lo, bit_hi):
+        self.ctx.load_slice_mercy_begin(bit_lo, bit_hi)
+
+    def slice_mercy_batch(self, batch):
+        """mark + resolve of one batch, not folded yet; returns its fail plane as a device tensor, None for an empty batch"""
+        n = self.ctx.load_slice_state()[2]
+        self.ctx.load_slice_batch(batch)
+        if self.ctx.load_slice_state()[2] == n:
+            return None
+        return torch.as_tensor(_DevView(*self.ctx.load_slice_plane(n)), device=self.device)
+
+    def slice_mercy_probe(self):
+        self.ctx.load_slice_mercy_probe()
+
+    def slice_mercy_planes(self):
+        """the miss planes of the pass' non-empty batches, four to a block, in batch order (to be ORed across the ranks in place)"""
+        return [torch.as_tensor(_DevView(*self.ctx.load_slice_mercy_planes(i)), device=self.device) for i in range(self.ctx.load_slice_state()[2])]
 
     def slice_end(self):
         return self.ctx.load_slice_end()

@@ -213,7 +213,8 @@ int fgpu_load_fixup_state(fgpu_ctx* ctx, int* ready, uint64_t* resident_budget_b
  * (FGPU_LOAD_LAYOUT=records is not used here).  Every batch stays resident in HBM (packed codes, bad mask, fail plane, later the `sure`
  * plane): 5 bits per stream position; a batch that cannot be kept -- FGPU_FLAG_NO_RESIDENT, or beyond the budget
  * (fgpu_load_fixup_state) -- makes fgpu_load_slice_batch return FGPU_ERR_NOMEM.  Stream-ordered on the context's stream like the rest.
- * FGPU_ERR_STATE: _begin while a pass is open or with FGPU_FLAG_MERCY (the mercy rule needs time-aware tests of other slices' bits);
+ * FGPU_ERR_STATE: _begin while a pass is open or with FGPU_FLAG_MERCY (the mercy rule needs time-aware tests of other slices' bits: the
+ * five-step protocol below, opened by fgpu_load_slice_mercy_begin);
  * _batch / _plane / _commit / _end outside a sliced pass; _batch after _commit; _commit twice; _end before _commit; fgpu_load_batch inside
  * a sliced pass; fgpu_load_fixup after one.  FGPU_ERR_ARG: bounds that are not multiples of 512, bit_lo > bit_hi, bit_hi > tai, a batch index
  * out of range. */
@@ -235,6 +236,39 @@ int fgpu_load_slice_end(fgpu_ctx* ctx, fgpu_load_stats* stats);
 /* *ready (may be NULL): 1 inside a sliced pass that has not been committed yet.  *working_bytes (may be NULL): device bytes allocated for the
  * slice state (first-set times + pair).  *n_batches (may be NULL): planes fgpu_load_slice_plane can hand out (0 outside a sliced pass). */
 int fgpu_load_slice_state(fgpu_ctx* ctx, int* ready, uint64_t* working_bytes, uint64_t* n_batches);
+
+/* ---- the sliced pass under --mercy: FIVE steps, a lockstep per batch -----------------------------------------------------------------------
+ * load_two_filters(..., mercy = true) asks bloo1, as it stood at occurrence t, about the four extensions of a k-mer (isJunction), and their
+ * bits lie in any slice.  "Bit b was set by time t" concerns b alone, so its owner answers it from the carry and its first-set times; a
+ * candidate is contained iff NO rank finds an own bit of it unset.  Each rank therefore writes four MISS PLANES per batch -- bit (position, nt):
+ * an own bit of candidate nt at this position was not set by then -- for a superset of the positions the reference tests (every window but
+ * the first of its segment that is not contained, or is contained behind one that is not; known from the ORed fail plane alone), the caller
+ * ORs them across the ranks like the fail planes, and the commit runs the reference's per-segment state machine on the ORed answers, setting
+ * the own bloo2 bits of every accepted run.  The first-set times answer "<= t" only until the batch joins the carry, so the probe of a batch
+ * comes after the exchange of ITS fail plane and before the next batch:
+ *
+ *     fgpu_load_slice_mercy_begin(lo, hi);
+ *     for every batch b, every rank:   fgpu_load_slice_batch(b);                                               1  mark + resolve, no fold
+ *                                      fgpu_load_slice_plane(i, &p, &n);  p := OR over ranks                    2  the exchange (caller)
+ *                                      fgpu_load_slice_mercy_probe();                                          3  miss planes, then the fold
+ *     for every batch i:               fgpu_load_slice_mercy_planes(i, &m, &n);  m := OR over ranks              4  the exchange (caller)
+ *     fgpu_load_slice_commit();  fgpu_load_slice_end(&stats);                                                  5
+ *
+ * bloo1, bloo2, `sure` and the stats come out as the plain --mercy pass leaves them (to_bloo2 = contained occurrences).  Resident state: 9 bits
+ * per stream position instead of 5.  FGPU_ERR_STATE: _mercy_begin on a context without FGPU_FLAG_MERCY or while a pass is open; _batch or
+ * _commit while the latest batch has not been probed; _mercy_probe / _mercy_planes outside a mercy pass; _mercy_planes of the batch whose
+ * probe is owed.  FGPU_ERR_ARG as fgpu_load_slice_begin / fgpu_load_slice_plane. */
+int fgpu_load_slice_mercy_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi);
+/* The latest batch: reads its fail plane (ORed in place, ordered before this call), writes its four miss planes, then folds the batch into the
+ * carry.  Nothing owed (an empty batch, or called twice): FGPU_OK, nothing done. */
+int fgpu_load_slice_mercy_probe(fgpu_ctx* ctx);
+/* The four miss planes of the i-th non-empty batch as ONE block, to be ORed in place: plane nt starts at nt * *nbytes / 4, each has the fail
+ * plane's layout and is zero past its last word; *nbytes is a multiple of 16. */
+int fgpu_load_slice_mercy_planes(fgpu_ctx* ctx, uint64_t batch, void** miss_dev, uint64_t* nbytes);
+/* Counts of the last finished mercy pass (zero after a plain sliced pass): [0] positions THIS rank probed; then, from the commit and the same on
+ * every rank: [1] high->low tests answered "junction", [2] runs opened, [3] low->high tests answered "junction", [4] runs added to bloo2,
+ * [5] k-mers of those runs. */
+int fgpu_diag_slice_mercy(fgpu_ctx* ctx, uint64_t out[6]);
 
 /* filters: raw bit arrays, tai/8 bytes, exactly the .bloom file body (utils/Bloom.cpp:571-587) */
 int fgpu_bloom_download(fgpu_ctx* ctx, int which, uint8_t* host_out, uint64_t nbytes);
