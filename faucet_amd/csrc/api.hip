@@ -1,7 +1,7 @@
 // api.hip — the extern "C" entry points of include/faucet_gpu.h.
 //
 // Thin: argument checks, state machine (idle -> loading -> idle -> scanning -> idle), buffer management and the
-// order in which the stages of pack.hip / load.hip / scan_pure.hip / scan_walk.hip are put on the stream.
+// order in which the stages of pack.hip / load.hip / scan_pure.hip / scan_walk.hip / scan_harvest.hip are put on the stream.
 // There is no CPU path in this library: with no usable gfx950 device fgpu_create fails with FGPU_ERR_HIP.
 #include <cstdio>
 #include <algorithm>
@@ -310,6 +310,8 @@ int fgpu_create(const fgpu_params* p, fgpu_ctx** out) {
                 if ((he = hipEventCreateWithFlags(&ctx->ev_uf_reset[q], hipEventDisableTiming)) != hipSuccess) return bad("hipEventCreate", he);
             fgpu_touch_scan_pure();
             fgpu_touch_scan_walk();
+            fgpu_touch_scan_table();
+            fgpu_touch_scan_harvest();
             (void)hipGetLastError();
         });
     }

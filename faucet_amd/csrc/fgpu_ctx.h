@@ -205,7 +205,7 @@ struct fgpu_ctx {
     hipStream_t wstream = nullptr;         // walk stream: the ordered walk of batch b overlaps the pure stage of batch b+1
     hipStream_t cstream = nullptr;         // clean stream: the window table of window w is emptied while w is clustered and walked
     hipEvent_t ev_walked = nullptr, ev_uf_reset[2] = {nullptr, nullptr};
-    hipStream_t ostream = nullptr;         // optimistic stream: the rounds of the large clusters' walk run beside k_walk (disjoint clusters)
+    hipStream_t ostream = nullptr;         // optimistic stream: the rounds of the large clusters' walk run beside k_walk_dyn (disjoint clusters)
     hipEvent_t ev_listed = nullptr, ev_settled = nullptr;   // walk stream: the large clusters' pieces are listed; optimistic stream: their logs are applied
     hipStream_t launch_stream = nullptr;   // where FGPU_LAUNCH puts kernels (and profiling events) right now
     bool own_stream = false;
@@ -255,7 +255,7 @@ struct fgpu_ctx {
 
     // pass 2 state: junction table (open addressing on the canonical k-mer)
     uint64_t jcap = 0;               // slots (power of two)
-    uint64_t* jkeys = nullptr;       // canon | present bits in 63,62 ; EMPTY = ~0
+    uint64_t* jkeys = nullptr;       // canon | present bits in 63,62 ; EMPTY = ~0  (layout and look-ups: walk_tables.h)
     uint8_t* jrecs = nullptr;        // [slot][orient] 16-byte records
     uint64_t* jstamps = nullptr;     // [slot][orient] creation stamp
     uint32_t* jfilter = nullptr;     // presence filter in front of jkeys (2 bits per slot)
@@ -496,6 +496,8 @@ void fgpu_touch_pack();
 void fgpu_touch_text();
 void fgpu_touch_scan_pure();
 void fgpu_touch_scan_walk();
+void fgpu_touch_scan_table();
+void fgpu_touch_scan_harvest();
 int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads);
 int fgpu_host_batch_done(fgpu_ctx* ctx, const fgpu_reads* reads);
 int fgpu_stage_load(fgpu_ctx* ctx);

@@ -1,5 +1,5 @@
 // pairs.hip — the long pair filter on the device: scanReads' paired-end loop (src/ReadScanner.cpp:317-343) over the lists
-// scanInputRead returns (the stops the harvest builds, scan_walk.hip), with Bloom::containsPair / addPair (utils/Bloom.cpp:127-154).
+// scanInputRead returns (the stops the harvest builds, scan_harvest.hip), with Bloom::containsPair / addPair (utils/Bloom.cpp:127-154).
 //
 // The reference, per read pair (records 2p and 2p+1 of the scan file), when both lists are non-empty:
 //     for pair1 in list(2p):   if no pair2 in list(2p+1) has containsPair(pair1, pair2):   addPair(pair1, list(2p+1).front())

@@ -16,11 +16,12 @@
 //                      was taken (lists kept by k_delta_collect: the batches walked since, this batch's earlier windows)
 //   B  k_walk_link     every position: probe the window table; a hit unions the piece with the candidate's owner
 //   C  k_walk_cluster  flatten the union-find; list each cluster's members in ascending piece order
-//   D  k_walk          one thread per cluster replays its pieces IN ORDER against the live table; clusters are
+//   D  k_walk_dyn      one thread per cluster replays its pieces IN ORDER against the live table; clusters are
 //                      disjoint in the keys they touch, so they run concurrently without changing any result
+//                      (the waves of a fixed grid draw the clusters from the window's list of leaders)
 //   D' k_walk_ko       clusters of 64 pieces and more (repeats at high coverage), once a scan has shown one: one piece per wave, the
 //                      ACCESSES ordered per junction k-mer by turn counters (k_ko_prepare, k_ko_rank), so the pieces of a cluster
-//                      overlap; k_walk leaves those clusters alone.  (k_walk_par, off: the out-of-order walk of clusters whose
+//                      overlap; k_walk_dyn leaves those clusters alone.  (k_walk_par, off: the out-of-order walk of clusters whose
 //                      pieces change nothing another piece reads -- exact, measured, does not pay.)
 //   E  k_delta_collect the keys the window created go to the batch's list; k_walk_reset_uf (side stream) resets the union-find arrays
 //                      and the window table's presence filter of this parity (the table itself needs no cleaning: epoch-tagged entries)
@@ -28,140 +29,15 @@
 // The result is the reference's map, record for record; creation stamps (global piece number, half-step)
 // give the reference's insertion order back for the dump.
 //
-// Junction table: open addressing on the CANONICAL k-mer; one slot serves both orientations of the key
-// (orientation 0: key == canon, orientation 1: key == revcomp(canon)).
-//   jkeys[slot]  = canon | present(orient0) << 62 | present(orient1) << 63 ; empty = ~0
-//   jrecs[slot][orient] 16 bytes : dist[5] cov[4] linked(bitmask) pad[6]
-//   jstamps[slot][orient]         : creation stamp
+// The junction table and the window table as the kernels see them: walk_tables.h.  The table's life cycle (growing, export / import, download,
+// dump order): scan_table.hip.  scanInputRead's lists from the visits marked here: scan_harvest.hip.
 #include <cstring>
 #include <algorithm>
 
-#include "fgpu_ctx.h"
 #include "fgpu_flags.h"
-
-#include <rocprim/rocprim.hpp>
+#include "walk_tables.h"
 
 namespace {
-
-constexpr uint64_t J_EMPTY = ~0ULL;
-constexpr uint64_t J_KEYMASK = (1ULL << 62) - 1;
-constexpr uint32_t U_INF = 0xFFFFFFFFu;
-constexpr uint64_t J_PROBE_LIMIT = 1ULL << 14;
-// creation stamp = (global piece number << STAMP_SHIFT) | half-step of the visit (STAMP_FAKE for add_fake_junction's record, which
-// is created after every half-step of its piece): half-steps run to 2 x windows, so a piece may span up to 2^19 - 1 windows
-// (fgpu_stage_scan_walk refuses longer reads with FGPU_ERR_CAPACITY); 44 bits are left for the piece number.
-constexpr int STAMP_SHIFT = 20;
-constexpr uint64_t STAMP_FAKE = (1ULL << STAMP_SHIFT) - 1;
-
-struct JTable {
-    uint64_t* keys;
-    uint8_t* recs;
-    uint64_t* stamps;
-    uint64_t mask;         // capacity - 1
-    uint32_t* filter;      // presence filter: one bit per hashed canonical k-mer that owns a slot (2 bits per slot of capacity)
-    uint64_t filter_mask;  // filter bits - 1
-};
-
-// The 32-bit hash of a canonical k-mer that every table of the walk stage works from: h32 = low half of fd_mix(canon).  It is computed
-// ONCE per position and batch (k_need_lookup writes the plane `kh`, 4 bytes per position); the per-window kernels read it back
-// instead of extracting, reverse-complementing and mixing the k-mer again (which, measured, was NOT what bounded them: they wait on
-// dependent loads and on the window table's atomics -- but it is what lets k_walk_register and k_walk_link work without the k-mers).
-__device__ __forceinline__ uint32_t jt_h32(uint64_t canon) { return (uint32_t)fd_mix(canon); }
-// junction-table slot (capacities up to 2^32) and filter bit (a multiplicative scramble: other bits than the slot's low ones decide)
-__device__ __forceinline__ uint64_t jt_filter_bit_h(const JTable& jt, uint32_t h32) {
-    return (((uint64_t)(h32 * 0x9E3779B1u) << 16) ^ (uint64_t)(h32 >> 7)) & jt.filter_mask;
-}
-__device__ __forceinline__ uint64_t jt_filter_bit(const JTable& jt, uint64_t canon) { return jt_filter_bit_h(jt, jt_h32(canon)); }
-
-struct WTable {
-    uint64_t* keys;      // epoch << 56 | h32 << 24 | owner (see wt_register)
-    uint32_t* bits;      // presence filter of 2^(32 - fshift) bits in front of the table (zeroed by k_walk_reset_uf of the window two before)
-    uint64_t mask;
-    uint64_t epoch;      // number of the window (1..255) << 56: entries of any other epoch count as empty slots
-    uint32_t fshift;     // 32 - log2(bits of the presence filter)
-};
-
-// scheduling window = all pieces whose first window lies in [lo, hi); filled by k_walk_setup
-struct WinDesc {
-    uint32_t first_piece;   // index in the batch's piece list
-    uint32_t n;             // pieces in the window
-    uint64_t lo, hi;
-};
-
-struct Planes {
-    const uint64_t* codes;
-    const uint64_t* pm;
-    const uint64_t* ps;
-    const uint32_t* prefix;
-    const uint64_t *ff, *fb, *cf0, *cf1, *cb0, *cb1;
-    uint64_t *inF, *inB;
-    const uint2* pieces;
-    uint64_t* lk;
-    const uint64_t* need;
-    unsigned long long *sF, *sB;   // junction visits (FGPU_FLAG_RECORD_STOPS), else nullptr
-    const uint32_t* kh;            // 32-bit hash of the canonical k-mer of every position inside a piece (k_need_lookup)
-    unsigned long long* cr;        // positions at which this batch's walk created a junction record (either facing): the delta of later windows
-};
-
-__device__ __forceinline__ uint64_t ld_agent(const uint64_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- junction table ---------------------------------------------------------------------------
-// read-only lookup (snapshot kernels): plain loads
-__device__ __forceinline__ uint32_t jt_present_snapshot(const JTable& jt, uint64_t canon) {
-    uint64_t s = fd_mix(canon) & jt.mask;
-    for (uint64_t n = 0; n <= jt.mask; n++) {
-        uint64_t w = jt.keys[s];
-        if (w == J_EMPTY) return 0;
-        if ((w & J_KEYMASK) == canon) return (uint32_t)(w >> 62);
-        s = (s + 1) & jt.mask;
-    }
-    return 0;
-}
-
-// live lookup inside the walk: agent-scope loads (L1 bypass), see DESIGN.md "visibility"
-__device__ __forceinline__ bool jt_find_live(const JTable& jt, uint64_t canon, uint64_t& slot, uint32_t& present) {
-    uint64_t s = fd_mix(canon) & jt.mask;
-    for (uint64_t n = 0; n <= jt.mask; n++) {
-        uint64_t w = ld_agent(&jt.keys[s]);
-        if (w == J_EMPTY) return false;
-        if ((w & J_KEYMASK) == canon) { slot = s; present = (uint32_t)(w >> 62); return true; }
-        s = (s + 1) & jt.mask;
-    }
-    return false;
-}
-
-// find or claim the slot of canon; returns false when the table is full.  `w_first` is the (already loaded) key word of the
-// home slot, so that the caller can have the record of the home slot in flight at the same time.
-__device__ __forceinline__ bool jt_find_or_claim(const JTable& jt, uint64_t canon, uint64_t home, uint64_t w_first, uint64_t& slot,
-                                                 uint32_t& present, DevCounters* cnt) {
-    uint64_t s = home;
-    // The host keeps the table below a quarter full between batches (fgpu_scan_grow); a probe sequence this long means one batch
-    // has outgrown it: report "full" now instead of crawling through a saturated table (16 M slots x millions of pieces)
-    const uint64_t limit = jt.mask < J_PROBE_LIMIT ? jt.mask : J_PROBE_LIMIT;
-    for (uint64_t n = 0; n <= limit; n++) {
-        // once some walk has reported the overflow this scan is void: the others stop crawling.  Looked at only on long probe
-        // sequences -- a load of that one word from every piece walk queues up in its L2 channel (+8 ms per step, measured)
-        if ((n & 255) == 255 && (ld_agent((const uint64_t*)&cnt->error_flags) & 1ULL)) return false;
-        uint64_t w = n == 0 ? w_first : ld_agent(&jt.keys[s]);
-        if (w == J_EMPTY) {
-            unsigned long long old = atomicCAS((unsigned long long*)&jt.keys[s], (unsigned long long)J_EMPTY, (unsigned long long)canon);
-            if (old == J_EMPTY) {
-                slot = s;
-                present = 0;
-                return true;
-            }
-            w = old;
-        }
-        if ((w & J_KEYMASK) == canon) { slot = s; present = (uint32_t)(w >> 62); return true; }
-        s = (s + 1) & jt.mask;
-    }
-    return false;
-}
 
 // ---- union-find over the pieces of one window --------------------------------------------------
 __device__ __forceinline__ uint32_t uf_find(uint32_t* parent, uint32_t x) {
@@ -335,7 +211,7 @@ __global__ void __launch_bounds__(256) k_walk_link(Planes pl, FdParams fp, WTabl
     // a fixed grid strides over the window, 1024 positions per block and round: the loads of four positions per thread (hash, then
     // filter word) are in flight together -- one position per thread left this kernel waiting on two dependent loads per 256-thread block
     const WinDesc wd = make_window(pl, lo, hi);
-    if (roots_state && blockIdx.x == 0 && threadIdx.x == 0) { roots_state[0] = 0; roots_state[1] = 0; }   // roots listed / handed out (k_walk_cluster, k_walk)
+    if (roots_state && blockIdx.x == 0 && threadIdx.x == 0) { roots_state[0] = 0; roots_state[1] = 0; }   // roots listed / handed out (k_walk_cluster, k_walk_dyn)
     const uint64_t base0 = wd.lo & ~63ULL;
     constexpr int U = 4;
     for (uint64_t base = base0 + (uint64_t)blockIdx.x * (256 * U); base < pos_end; base += (uint64_t)gridDim.x * (256 * U)) {
@@ -493,7 +369,7 @@ __global__ void __launch_bounds__(256) k_walk_cluster(const uint32_t* __restrict
             next[i] = atomicExch(&head[r], i);
             atomicAdd(&count[r], 1u);
         }
-        {   // the clusters' leaders, as a list k_walk hands out (one reservation per wave)
+        {   // the clusters' leaders, as a list k_walk_dyn hands out (one reservation per wave)
             const bool is_root = r == i;
             const unsigned long long m = __ballot(is_root);
             if (m) {
@@ -518,10 +394,10 @@ __global__ void __launch_bounds__(256) k_walk_cluster(const uint32_t* __restrict
 
 // Which clusters the key-ordered walk takes: those of at least `heavy` pieces, and -- heavy_w != 0: callers that expect repeats
 // (FGPU_FLAG_KEY_ORDER_FROM_START) -- those whose pieces hold at least heavy_w lk positions between them.  A piece inside a repeat at high
-// coverage makes a junction visit at nearly every position: a dozen such pieces on their cluster's one thread (k_walk) are a longer chain
-// than seventy ordinary ones, and the longest chain is what a window's k_walk takes (BASELINE config 3's shape through the CLI: k_walk
+// coverage makes a junction visit at nearly every position: a dozen such pieces on their cluster's one thread (k_walk_dyn) are a longer chain
+// than seventy ordinary ones, and the longest chain is what a window's k_walk_dyn takes (BASELINE config 3's shape through the CLI: k_walk_dyn
 // 237 ms of pass 2 beside k_walk_ko's 238 ms, all of it clusters of fewer than 32 repeat pieces).
-// (measured, FGPU_WALK_KO_WEIGHT: on config 3's shape k_walk + k_walk_ko take 381 / 293 / 249 ms at 256 / 128 / 48 positions; on config 2,
+// (measured, FGPU_WALK_KO_WEIGHT: on config 3's shape k_walk_dyn + k_walk_ko take 381 / 293 / 249 ms at 256 / 128 / 48 positions; on config 2,
 // where a piece holds 2-5 of them, the walk stage grows from 42.9 ms to 45.0 / 63.4 / 80.1 ms at 128 / 64 / 48.  Hence two bars: heavy_w
 // positions in all, or three eighths of that where the pieces hold a dozen each -- which ordinary pieces never do.)
 // heavy_w packs the rule by weight: bits 0-15 the bar for a cluster's lk positions in all, bits 16-23 the positions per piece that make its
@@ -580,7 +456,7 @@ constexpr unsigned long long KO_WAIT_LIMIT_TICKS = (unsigned long long)FGPU_KO_W
 
 // A piece's lk positions and the positions looked up and found absent (per facing: not events after all), 64 windows per word, in LDS: the
 // one walking lane of the block indexes them by chunk at run time (registers picked by an index end up in scratch memory, see pv_codes).
-constexpr uint32_t KO_CHUNKS = 8;              // pieces of up to 512 windows; longer ones keep their cluster with k_walk
+constexpr uint32_t KO_CHUNKS = 8;              // pieces of up to 512 windows; longer ones keep their cluster with k_walk_dyn
 __device__ __forceinline__ uint64_t* ko_masks() {
     __shared__ uint64_t s_ko[3 * KO_CHUNKS];
     return s_ko;
@@ -620,6 +496,13 @@ struct WalkCtx {
     int fail;           // WALK_PROBE: why this piece cannot be walked out of order (see k_walk_par): 1 would create, 2 would raise a distance, 3 untested positions
     int dbg;            // FGPU_DEBUG_WALK bits (timing experiments only; results are wrong when non-zero)
 };
+// a walk's context at the start of a kernel: what the kernel was given, the accumulators at zero (wc.ko is the key-ordered walk's to set)
+__device__ __forceinline__ void walk_ctx_init(WalkCtx& wc, const Planes& pl, const FdParams& fp, const JTable& jt, DevCounters* cnt, const uint32_t* bloom,
+                                              uint32_t win_seq, int dbg) {
+    wc.pl = pl; wc.fp = fp; wc.jt = jt; wc.cnt = cnt; wc.bloom = bloom; wc.win_seq = win_seq;
+    wc.nb_processed = wc.nb_skipped = wc.nb_jcheck = wc.nb_no_juncs = wc.n_created = wc.n_filled = 0;
+    wc.created_now = false; wc.fail = 0; wc.dbg = dbg;
+}
 
 // How a piece is walked.  WALK_SEQ: in its cluster's order by the cluster's one thread, reading and writing the junction table (the
 // reference's semantics as they stand).  WALK_PROBE / WALK_COMMIT: the two halves of the out-of-order walk of a large cluster, one thread
@@ -634,13 +517,6 @@ enum { WALK_SEQ = 0, WALK_PROBE = 1, WALK_COMMIT = 2, WALK_KO = 3, WALK_OVW = 4 
 #define KO_T1(cnt, i) do {} while (0)
 #endif
 
-
-__device__ __forceinline__ uint64_t chunk_mask(uint32_t nwin, uint32_t c) {
-    uint32_t base = c * 64;
-    if (base >= nwin) return 0;
-    uint32_t rem = nwin - base;
-    return rem >= 64 ? ~0ULL : ((1ULL << rem) - 1);
-}
 
 // plane word for windows [64c, 64c+64) of the piece
 __device__ __forceinline__ uint64_t pv_word(const PieceView& v, uint64_t r0, uint64_t r1, const uint64_t* plane, uint32_t c) {
@@ -711,7 +587,7 @@ __device__ __forceinline__ int pv_base(const PieceView& v, const uint64_t* codes
 // lk positions, and every piece it occurs on is in this thread's cluster: what the look-up sees is what the sequential run has.
 // Out of line and fed by value on purpose: the rare path stays out of the walk's register allocation.
 // (the table as two scalars, not the 48-byte JTable: a struct handed to an out-of-line function by value travels through SCRATCH memory --
-// three 16-byte stores before every call and as many loads behind it, on the path of nearly every piece of k_walk)
+// three 16-byte stores before every call and as many loads behind it, on the path of nearly every piece of k_walk_dyn)
 __device__ __noinline__ uint4 live_bits_impl(const uint64_t* __restrict__ codes, int k, uint64_t p, uint64_t where, uint64_t* jkeys, uint64_t jmask) {
     JTable jt;
     jt.keys = jkeys;
@@ -720,7 +596,7 @@ __device__ __noinline__ uint4 live_bits_impl(const uint64_t* __restrict__ codes,
     uint64_t mF = 0, mB = 0;
     // Four candidate positions at a time, their loads in flight TOGETHER: first the four k-mers, then the key words of their four home slots.
     // One position after the other this was two dependent round trips per position -- a piece holds 2-5 such positions, i.e. 4-10 of the 8-10
-    // round trips that make a piece's place in its cluster's chain (round 4; k_walk is the longest chain of a window, not throughput).
+    // round trips that make a piece's place in its cluster's chain (round 4; k_walk_dyn is the longest chain of a window, not throughput).
     while (where) {
         uint32_t idx[4];
         bool on[4];
@@ -1383,78 +1259,50 @@ __device__ __forceinline__ void walk_piece(WalkCtx& wc, uint64_t p0, uint32_t nw
 }
 
 constexpr uint32_t LOCAL_MEMBERS = 16;
-__global__ void __launch_bounds__(64) k_walk(Planes pl, FdParams fp, JTable jt, const uint32_t* __restrict__ root,
-                                             const uint32_t* __restrict__ count, const uint32_t* __restrict__ head,
-                                             const uint32_t* __restrict__ next, uint32_t* pool, const WinDesc* __restrict__ wdp,
-                                             uint64_t piece_seq_base, const uint32_t* __restrict__ bloom, DevCounters* cnt, int dbg,
-                                             const uint32_t* __restrict__ par_fail, uint32_t heavy, const uint32_t* __restrict__ ko_bad,
-                                             const uint32_t* __restrict__ ko_state, uint32_t ko_heavy, uint32_t win_seq, uint32_t ko_heavy_w) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    WalkCtx wc;
-    wc.pl = pl; wc.fp = fp; wc.jt = jt; wc.cnt = cnt; wc.bloom = bloom; wc.win_seq = win_seq;
-    wc.nb_processed = wc.nb_skipped = wc.nb_jcheck = wc.nb_no_juncs = wc.n_created = wc.n_filled = 0;
-    wc.created_now = false; wc.fail = 0; wc.dbg = dbg; 
-    const WinDesc wd = *wdp;
-    const uint32_t n = wd.n, first_piece = wd.first_piece;
-    // the large-cluster tables did not hold this window (its clusters are walked here, in order): the host shrinks the windows that follow
-    if (ko_heavy && blockIdx.x == 0 && threadIdx.x == 0 && (ko_state[1] & 1u)) atomicAdd(&cnt->ko_overflows, 1ULL);
-    unsigned long long n_follow = 0, biggest = 0;
-    // everything the thread needs to start is requested at once (no dependent loads before the plane burst)
-    const uint32_t ii = i < n ? i : 0;
-    const uint32_t my_root = root[ii], my_count = count[ii], my_head = head[ii];
-    const uint2 my_piece = pl.pieces[first_piece + ii];
 
-    // a large cluster whose pieces k_walk_par found to be order-free is walked there, one thread per piece
-    const bool walked_out_of_order = (heavy && my_count + 1 >= heavy && !par_fail[ii]) ||
-                                     (ko_heavy && ko_cluster(my_count, par_fail[ii], ko_heavy, ko_heavy_w) && !ko_bad[ii] && !(ko_state[1] & 1u));   // k_walk_ko has them (par_fail = the weights then)
-    if (i < n && my_root == i && !walked_out_of_order) {
-        const uint32_t nm = (dbg & 2) ? 0 : my_count;
-        uint32_t local_mem[LOCAL_MEMBERS];
-        uint32_t* mem = local_mem;
-        if (nm) {   // followers: off the linked list, into ascending piece order (the leader is the smallest index of the cluster)
-            n_follow = nm;
-            biggest = nm + 1;
-            if (nm > LOCAL_MEMBERS) mem = pool + atomicAdd(&cnt->pad2, (unsigned long long)nm);   // rare: giant cluster, list in global memory
-            uint32_t j = 0;
-            for (uint32_t m = my_head; m != U_INF && j < nm; m = next[m]) mem[j++] = m;
-            for (uint32_t gap = nm / 2; gap > 0; gap /= 2)          // shell sort: fine for 2 members and for 10^5
-                for (uint32_t a = gap; a < nm; a++) {
-                    uint32_t v = mem[a];
-                    uint32_t b = a;
-                    while (b >= gap && mem[b - gap] > v) { mem[b] = mem[b - gap]; b -= gap; }
-                    mem[b] = v;
-                }
+// The followers of the cluster led by piece i (nm of them, nm > 0): off the linked list, into ascending piece order (the leader is the
+// smallest index of the cluster).  They go to the lane's own array, or -- rare: a giant cluster -- to a stretch of the pool in global memory.
+__device__ __forceinline__ uint32_t* cluster_followers(uint32_t* local_mem, uint32_t* pool, DevCounters* cnt, const uint32_t* __restrict__ head,
+                                                       const uint32_t* __restrict__ next, uint32_t i, uint32_t nm) {
+    uint32_t* mem = local_mem;
+    if (nm > LOCAL_MEMBERS) mem = pool + atomicAdd(&cnt->pad2, (unsigned long long)nm);
+    uint32_t j = 0;
+    for (uint32_t m = head[i]; m != U_INF && j < nm; m = next[m]) mem[j++] = m;
+    for (uint32_t gap = nm / 2; gap > 0; gap /= 2)          // shell sort: fine for 2 members and for 10^5
+        for (uint32_t a = gap; a < nm; a++) {
+            uint32_t v = mem[a];
+            uint32_t b = a;
+            while (b >= gap && mem[b - gap] > v) { mem[b] = mem[b - gap]; b -= gap; }
+            mem[b] = v;
         }
-        for (uint32_t a = 0; a <= nm; a++) {
-            const uint32_t m = a == 0 ? i : mem[a - 1];
-            const uint2 pc = a == 0 ? my_piece : pl.pieces[first_piece + m];
-            walk_piece<WALK_SEQ>(wc, pc.x, pc.y, piece_seq_base + first_piece + m);
-        }
-    }
-    // wave-level reduction of the counters
-    unsigned long long v[7] = {wc.nb_processed, wc.nb_skipped, wc.nb_jcheck, wc.nb_no_juncs, wc.n_created, n_follow, wc.n_filled};
-    for (int c = 0; c < 7; c++)
-        for (int o = 32; o > 0; o >>= 1) v[c] += __shfl_down(v[c], o, 64);
-    for (int o = 32; o > 0; o >>= 1) { unsigned long long t = __shfl_down(biggest, o, 64); biggest = t > biggest ? t : biggest; }
-    if (fd_lane() == 0) {
-        if (v[5]) atomicAdd(&cnt->followers, v[5]);
-        if (biggest) atomicMax(&cnt->max_cluster, biggest);
-        if (v[0]) atomicAdd(&cnt->nb_processed, v[0]);
-        if (v[1]) atomicAdd(&cnt->nb_skipped, v[1]);
-        if (v[2]) atomicAdd(&cnt->nb_jcheck, v[2]);
-        if (v[3]) atomicAdd(&cnt->nb_no_juncs, v[3]);
-        if (v[4]) atomicAdd(&cnt->n_junctions, v[4]);
-        if (v[6]) atomicAdd(&cnt->flags_filled, v[6]);
-    }
+    return mem;
 }
 
-// The same walk with the clusters handed out DYNAMICALLY (round 4).  k_walk gives lane i the cluster led by piece i: lanes whose piece is a
-// follower idle, lanes with a small cluster idle while a neighbour walks a large one, and a wave lives as long as its longest cluster --
-// 7.6 of 64 lanes active per vector instruction on config 2, 13 on config 4's thin windows, a fifth of the wave slots occupied
-// (profiles/r04_walk_counters.txt).  Here the waves of a fixed grid draw clusters from the window's list of leaders (k_walk_cluster) whenever a
-// lane has none, one reservation per wave and round, and every round every lane that holds a cluster walks ONE piece of it: the lanes stay
-// aligned piece by piece, a finished lane is refilled at once, and the grid drains when the list does.  Clusters are independent of each
-// other (that is what makes them clusters), so the order in which they are handed out changes nothing.
+// ---- the walk kernels' epilogue: what the lanes of a wave counted, added to the context's counters by lane 0 (a sum of zero costs no atomic)
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;   // (lane 0 holds the sum)
+}
+__device__ __forceinline__ void wave_add(unsigned long long* total, unsigned long long v) {
+    v = wave_sum(v);
+    if (fd_lane() == 0 && v) atomicAdd(total, v);
+}
+// the reference's four scan statistics (ReadScanner's NbProcessed, NbSkipped, NbJCheckKmer, NbNoJuncs)
+__device__ __forceinline__ void walk_counters_flush(DevCounters* cnt, unsigned long long processed, unsigned long long skipped, unsigned long long jcheck,
+                                                    unsigned long long no_juncs) {
+    wave_add(&cnt->nb_processed, processed);
+    wave_add(&cnt->nb_skipped, skipped);
+    wave_add(&cnt->nb_jcheck, jcheck);
+    wave_add(&cnt->nb_no_juncs, no_juncs);
+}
+
+// The walk by cluster, the clusters handed out DYNAMICALLY (round 4).  Its predecessor gave lane i the cluster led by piece i: lanes whose piece
+// is a follower idled, lanes with a small cluster idled while a neighbour walked a large one, and a wave lived as long as its longest cluster --
+// 7.6 of 64 lanes active per vector instruction on config 2, 13 on config 4's thin windows, a fifth of the wave slots occupied; 22.9 ms per step
+// against 16.6 ms on config 4's per-GPU shape, level on config 2 (profiles/r04_walk_counters.txt).  Here the waves of a fixed grid draw clusters
+// from the window's list of leaders (k_walk_cluster) whenever a lane has none, one reservation per wave and round, and every round every lane
+// that holds a cluster walks ONE piece of it: the lanes stay aligned piece by piece, a finished lane is refilled at once, and the grid drains
+// when the list does.  Clusters are independent of each other (that is what makes them clusters), so the order of the hand-out changes nothing.
 __global__ void __launch_bounds__(64) k_walk_dyn(Planes pl, FdParams fp, JTable jt, const uint32_t* __restrict__ root_list, uint32_t* roots_state,
                                                  const uint32_t* __restrict__ count, const uint32_t* __restrict__ head,
                                                  const uint32_t* __restrict__ next, uint32_t* pool, const WinDesc* __restrict__ wdp,
@@ -1462,9 +1310,7 @@ __global__ void __launch_bounds__(64) k_walk_dyn(Planes pl, FdParams fp, JTable 
                                                  const uint32_t* __restrict__ par_fail, uint32_t heavy, const uint32_t* __restrict__ ko_bad,
                                                  const uint32_t* __restrict__ ko_state, uint32_t ko_heavy, uint32_t win_seq, uint32_t ko_heavy_w) {
     WalkCtx wc;
-    wc.pl = pl; wc.fp = fp; wc.jt = jt; wc.cnt = cnt; wc.bloom = bloom; wc.win_seq = win_seq;
-    wc.nb_processed = wc.nb_skipped = wc.nb_jcheck = wc.nb_no_juncs = wc.n_created = wc.n_filled = 0;
-    wc.created_now = false; wc.fail = 0; wc.dbg = dbg;
+    walk_ctx_init(wc, pl, fp, jt, cnt, bloom, win_seq, dbg);
     const WinDesc wd = *wdp;
     const uint32_t first_piece = wd.first_piece;
     if (ko_heavy && blockIdx.x == 0 && threadIdx.x == 0 && (ko_state[1] & 1u)) atomicAdd(&cnt->ko_overflows, 1ULL);
@@ -1498,19 +1344,10 @@ __global__ void __launch_bounds__(64) k_walk_dyn(Planes pl, FdParams fp, JTable 
                         at = 0;
                         nm = (dbg & 2) ? 0 : my_count;
                         mem = local_mem;
-                        if (nm) {   // followers: off the linked list, into ascending piece order (the leader is the smallest index of the cluster)
+                        if (nm) {
                             n_follow += nm;
                             if (nm + 1 > biggest) biggest = nm + 1;
-                            if (nm > LOCAL_MEMBERS) mem = pool + atomicAdd(&cnt->pad2, (unsigned long long)nm);   // rare: giant cluster, list in global memory
-                            uint32_t j = 0;
-                            for (uint32_t m = head[i]; m != U_INF && j < nm; m = next[m]) mem[j++] = m;
-                            for (uint32_t gap = nm / 2; gap > 0; gap /= 2)          // shell sort: fine for 2 members and for 10^5
-                                for (uint32_t a = gap; a < nm; a++) {
-                                    uint32_t v = mem[a];
-                                    uint32_t b = a;
-                                    while (b >= gap && mem[b - gap] > v) { mem[b] = mem[b - gap]; b -= gap; }
-                                    mem[b] = v;
-                                }
+                            mem = cluster_followers(local_mem, pool, cnt, head, next, i, nm);
                         }
                     }
                 }
@@ -1527,20 +1364,12 @@ __global__ void __launch_bounds__(64) k_walk_dyn(Planes pl, FdParams fp, JTable 
             if (at++ == nm) leader = U_INF;
         }
     }
-    unsigned long long v[7] = {wc.nb_processed, wc.nb_skipped, wc.nb_jcheck, wc.nb_no_juncs, wc.n_created, n_follow, wc.n_filled};
-    for (int c = 0; c < 7; c++)
-        for (int o = 32; o > 0; o >>= 1) v[c] += __shfl_down(v[c], o, 64);
+    wave_add(&cnt->followers, n_follow);
     for (int o = 32; o > 0; o >>= 1) { unsigned long long t = __shfl_down(biggest, o, 64); biggest = t > biggest ? t : biggest; }
-    if (fd_lane() == 0) {
-        if (v[5]) atomicAdd(&cnt->followers, v[5]);
-        if (biggest) atomicMax(&cnt->max_cluster, biggest);
-        if (v[0]) atomicAdd(&cnt->nb_processed, v[0]);
-        if (v[1]) atomicAdd(&cnt->nb_skipped, v[1]);
-        if (v[2]) atomicAdd(&cnt->nb_jcheck, v[2]);
-        if (v[3]) atomicAdd(&cnt->nb_no_juncs, v[3]);
-        if (v[4]) atomicAdd(&cnt->n_junctions, v[4]);
-        if (v[6]) atomicAdd(&cnt->flags_filled, v[6]);
-    }
+    if (fd_lane() == 0 && biggest) atomicMax(&cnt->max_cluster, biggest);
+    walk_counters_flush(cnt, wc.nb_processed, wc.nb_skipped, wc.nb_jcheck, wc.nb_no_juncs);
+    wave_add(&cnt->n_junctions, wc.n_created);
+    wave_add(&cnt->flags_filled, wc.n_filled);
 }
 
 // The out-of-order walk of large clusters.  A cluster is the set of pieces of a window that share a junction k-mer; its one thread walks
@@ -1551,11 +1380,11 @@ __global__ void __launch_bounds__(64) k_walk_dyn(Planes pl, FdParams fp, JTable 
 // all earlier reads -- are not raised.  What is left of scan_forward then is a coverage count and two link flags per visit
 // (Junction::addCoverage saturating at 255, linked[] = true: JunctionMap.cpp:551-561), and those commute.  So, for clusters of at least
 // `heavy` pieces, one thread per PIECE:
-//   PROBE  (before k_walk)  walk read-only; par_fail[root] is set if any piece of the cluster would create a junction, raise a distance,
+//   PROBE  (before k_walk_dyn)  walk read-only; par_fail[root] is set if any piece of the cluster would create a junction, raise a distance,
 //          or needs junction tests the preview left out.  If nobody sets it, no distance and no key of the cluster changes during this
 //          window, so every piece reads exactly what it would read in file order: the paths found here are the sequential paths.
-//   k_walk walks the clusters that failed (and all small ones) in order, as before.
-//   COMMIT (after k_walk)   the pieces of the clusters that passed walk the same path again and apply coverage and links with atomics,
+//   k_walk_dyn walks the clusters that failed (and all small ones) in order, as before.
+//   COMMIT (after k_walk_dyn)   the pieces of the clusters that passed walk the same path again and apply coverage and links with atomics,
 //          mark their visits for scanInputRead's lists and add their counters.
 // Keys are exclusive to a cluster (that is what makes it a cluster), so the three kernels never touch each other's records.
 template <int MODE>
@@ -1564,9 +1393,7 @@ __global__ void __launch_bounds__(64) k_walk_par(Planes pl, FdParams fp, JTable 
                                                  uint32_t heavy) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     WalkCtx wc;
-    wc.pl = pl; wc.fp = fp; wc.jt = jt; wc.cnt = cnt; wc.bloom = bloom; wc.win_seq = 0;
-    wc.nb_processed = wc.nb_skipped = wc.nb_jcheck = wc.nb_no_juncs = wc.n_created = wc.n_filled = 0;
-    wc.created_now = false; wc.fail = 0; wc.dbg = 0; 
+    walk_ctx_init(wc, pl, fp, jt, cnt, bloom, 0, 0);
     const WinDesc wd = *wdp;
     unsigned long long walked = 0;
     if (i < wd.n) {
@@ -1583,16 +1410,8 @@ __global__ void __launch_bounds__(64) k_walk_par(Planes pl, FdParams fp, JTable 
         }
     }
     if (MODE == WALK_COMMIT) {
-        unsigned long long v[5] = {wc.nb_processed, wc.nb_skipped, wc.nb_jcheck, wc.nb_no_juncs, walked};
-        for (int c = 0; c < 5; c++)
-            for (int o = 32; o > 0; o >>= 1) v[c] += __shfl_down(v[c], o, 64);
-        if (fd_lane() == 0) {
-            if (v[0]) atomicAdd(&cnt->nb_processed, v[0]);
-            if (v[1]) atomicAdd(&cnt->nb_skipped, v[1]);
-            if (v[2]) atomicAdd(&cnt->nb_jcheck, v[2]);
-            if (v[3]) atomicAdd(&cnt->nb_no_juncs, v[3]);
-            if (v[4]) atomicAdd(&cnt->walk_parallel, v[4]);
-        }
+        walk_counters_flush(cnt, wc.nb_processed, wc.nb_skipped, wc.nb_jcheck, wc.nb_no_juncs);
+        wave_add(&cnt->walk_parallel, walked);
     }
 }
 
@@ -1728,15 +1547,13 @@ __global__ void __launch_bounds__(64) k_walk_ko(Planes pl, FdParams fp, JTable j
                                                 KoTables kt, uint32_t heavy, uint32_t KO_TICKET, const uint32_t* __restrict__ weight, uint32_t heavy_w,
                                                 const uint32_t* __restrict__ ovw_state, const uint32_t* __restrict__ ovw_longp, int ovw_rounds) {
     const WinDesc wd = *wdp;
-    if (kt.state[1] & 1u) return;                                      // a table overflowed: k_walk takes every cluster
+    if (kt.state[1] & 1u) return;                                      // a table overflowed: k_walk_dyn takes every cluster
     // the optimistic walk has settled and applied the clusters without long pieces: only the others are left
     const bool ovw_done = ovw_state && ovw_settled_round(ovw_state, ovw_rounds) >= 0;
     if (ovw_done && !ovw_state[3]) return;
     WalkCtx wc;
     KoState& ko = wc.ko;
-    wc.pl = pl; wc.fp = fp; wc.jt = jt; wc.cnt = cnt; wc.bloom = bloom; wc.win_seq = 0;
-    wc.nb_processed = wc.nb_skipped = wc.nb_jcheck = wc.nb_no_juncs = wc.n_created = wc.n_filled = 0;
-    wc.created_now = false; wc.fail = 0; wc.dbg = 0;
+    walk_ctx_init(wc, pl, fp, jt, cnt, bloom, 0, 0);
     ko.kt = kt;
     ko.cnt = cnt;
     unsigned long long walked = 0;
@@ -1750,7 +1567,7 @@ __global__ void __launch_bounds__(64) k_walk_ko(Planes pl, FdParams fp, JTable j
     // same-address atomic per 64 pieces cost 0.2 ms per window -- so that a ticket holds about one of them.  Where they are dense (a small
     // genome at high coverage: EVERY piece of the reference's own 1 000-read example is in one cluster) a ticket of 64 would put 64
     // consecutive pieces of the cluster on one lane, one after the other, and the waves would follow each other through the window: the
-    // whole walk one serial chain (33 ms for those 1 000 reads, twice what the cluster's single thread in k_walk needs).  So the ticket
+    // whole walk one serial chain (33 ms for those 1 000 reads, twice what the cluster's single thread in k_walk_dyn needs).  So the ticket
     // shrinks with the density, down to one piece: the pieces of a cluster then spread over the waves and overlap as their k-mers allow.
     uint32_t span = KO_TICKET;
     {
@@ -1770,7 +1587,7 @@ __global__ void __launch_bounds__(64) k_walk_ko(Planes pl, FdParams fp, JTable j
             if (i < wd.n && (uint32_t)fd_lane() < span) {
                 const uint32_t r = root[i];
                 mine = ko_cluster(count[r], weight[r], heavy, heavy_w) && !kt.bad[r] && !(ovw_done && !ovw_longp[r]);
-                if (mine && r == i) {                     // the statistics k_walk keeps per cluster
+                if (mine && r == i) {                     // the statistics k_walk_dyn keeps per cluster
                     atomicAdd(&cnt->followers, (unsigned long long)count[r]);
                     atomicMax(&cnt->max_cluster, (unsigned long long)count[r] + 1);
                 }
@@ -2291,7 +2108,7 @@ __global__ void __launch_bounds__(64) k_ovw_round(Planes pl, FdParams fp, JTable
     const WinDesc wd = *wdp;
     for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += gridDim.x * blockDim.x) {
         const uint32_t li = ot.list[idx];
-        if (ot.longp[root[li]] || kt.bad[root[li]]) continue;      // (a cluster with a piece of more than 512 windows stays with k_walk, all of it)
+        if (ot.longp[root[li]] || kt.bad[root[li]]) continue;      // (a cluster with a piece of more than 512 windows stays with k_walk_dyn, all of it)
         const uint2 pc = pl.pieces[wd.first_piece + li];
         const uint64_t lk0 = fd_bits_at(pl.lk, pc.x) & chunk_mask(pc.y, 0), lk1 = pc.y > 64 ? fd_bits_at(pl.lk, pc.x + 64) & chunk_mask(pc.y, 1) : 0ULL;
         uint4* const log = ot.log + 2ULL * kt.piece_base[li];
@@ -2313,9 +2130,7 @@ __global__ void __launch_bounds__(64) k_ovw_round(Planes pl, FdParams fp, JTable
             }
         }
         WalkCtx wc;
-        wc.pl = pl; wc.fp = fp; wc.jt = jt; wc.cnt = cnt; wc.bloom = bloom; wc.win_seq = 0;
-        wc.nb_processed = wc.nb_skipped = wc.nb_jcheck = wc.nb_no_juncs = wc.n_created = wc.n_filled = 0;
-        wc.created_now = false; wc.fail = 0; wc.dbg = 0;
+        walk_ctx_init(wc, pl, fp, jt, cnt, bloom, 0, 0);
         OvwWalk ow;
         ow.prev = ot.prev; ow.cur = ot.cur;
         ow.have_prev = round > 0;
@@ -2342,8 +2157,7 @@ __global__ void __launch_bounds__(64) k_ovw_round(Planes pl, FdParams fp, JTable
     }
     if (__ballot(changed) && fd_lane() == 0) atomicOr(&ot.state[8 + round], 1u);
     if (__ballot(failed) && fd_lane() == 0) atomicOr(&ot.state[1], 1u);
-    for (int o = 32; o > 0; o >>= 1) kept += __shfl_down(kept, o, 64);
-    if (kept && fd_lane() == 0) atomicAdd(&cnt->ovw_kept, kept);
+    wave_add(&cnt->ovw_kept, kept);
 }
 
 // Junction::addCoverage / update / the link flags of one log entry, on a record other pieces update at the same time
@@ -2445,15 +2259,12 @@ __global__ void __launch_bounds__(64) k_ovw_commit(Planes pl, FdParams fp, JTabl
             }
         }
     }
-    for (int c = 0; c < 8; c++)
-        for (int o = 32; o > 0; o >>= 1) v[c] += __shfl_down(v[c], o, 64);
+    walk_counters_flush(cnt, v[0], v[1], v[2], v[3]);
+    wave_add(&cnt->n_junctions, v[4]);
+    wave_add(&cnt->flags_filled, v[5]);
+    v[6] = wave_sum(v[6]);
+    v[7] = wave_sum(v[7]);
     if (fd_lane() == 0) {
-        if (v[0]) atomicAdd(&cnt->nb_processed, v[0]);
-        if (v[1]) atomicAdd(&cnt->nb_skipped, v[1]);
-        if (v[2]) atomicAdd(&cnt->nb_jcheck, v[2]);
-        if (v[3]) atomicAdd(&cnt->nb_no_juncs, v[3]);
-        if (v[4]) atomicAdd(&cnt->n_junctions, v[4]);
-        if (v[5]) atomicAdd(&cnt->flags_filled, v[5]);
         if (v[6]) { atomicAdd(&cnt->walk_parallel, v[6]); atomicAdd(&cnt->ovw[0], v[6]); }
         if (v[7]) { atomicAdd(&cnt->ovw[1], v[7]); atomicAdd(&cnt->ovw[2], 1ULL); }
         if (blockIdx.x == 0 && settled < 0 && kt.state[3]) atomicAdd(&cnt->ovw[3], 1ULL);   // a window left to the key-ordered walk
@@ -2558,12 +2369,6 @@ __global__ void __launch_bounds__(256) k_fill_u64(uint64_t* p, uint64_t n, uint6
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) p[i] = v;
 }
-__global__ void __launch_bounds__(256) k_iota_u32(uint32_t* p, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) p[i] = (uint32_t)i;
-}
-
 // FGPU_DEBUG_NEED_DROP=1 (tests): after the flags kernel, forget the evaluation of about half of the windows whose tests came out
 // false -- need bit and NbJCheckKmer bits cleared -- so that the walk has to evaluate them itself wherever it scans them.  =2: see below.
 // FGPU_DEBUG_WALK_STALL_US (tests): the walk stream held up for that long before every batch's walk, so that the pure stage gets as far ahead of
@@ -2629,12 +2434,6 @@ __global__ void __launch_bounds__(256) k_need_lookup(const uint64_t* __restrict_
         if (fd_lane() == 0) { nF[p >> 6] = mF; nB[p >> 6] = mB; }
     }
 }
-
-// the two bits of a key in the filter of NEW keys (fgpu_scan_import_table; k_refresh_lookup probes it with the same rule): one word, two bits
-__device__ __forceinline__ uint64_t delta_word(uint32_t h32, uint64_t bits_mask) {
-    return ((((uint64_t)(h32 * 0x9E3779B1u) << 16) ^ (uint64_t)(h32 >> 7)) & bits_mask) >> 5;
-}
-__device__ __forceinline__ uint32_t delta_bits(uint32_t h32) { return (1u << (h32 & 31)) | (1u << ((h32 >> 22) & 31)); }
 
 // The same planes made AGAIN for a batch whose hash plane exists (prepared batches of a read shard, right before their walk: the table has been
 // replaced since the pure stage made them): the hash is read back instead of being extracted, mixed and written a second time (4 bytes per
@@ -2762,80 +2561,6 @@ __global__ void __launch_bounds__(256) k_need_prewalk(const uint64_t* __restrict
     }
 }
 
-// ---- export: compact the present records ------------------------------------------------------------------
-struct ExportEntry {   // FGPU_TABLE_ENTRY_BYTES = 32
-    uint64_t key;      // oriented k-mer
-    uint64_t stamp;
-    uint8_t rec[16];
-};
-
-__global__ void __launch_bounds__(256) k_export(JTable jt, FdParams fp, ExportEntry* out, uint64_t* stamps_out, unsigned long long* n_out) {
-    // Every block owns a contiguous range of slots and reserves its output space ONCE: a first pass over the key words counts the
-    // records of the range, one atomic claims that many entries, a second pass writes them (ranks from ballots and wave totals).
-    // One same-address atomic per 256 slots, as before, cost 5 ms at 2^27 slots -- they serialise at ~10 ns each -- and the export is
-    // on the path of every hand-over between ranks; the key words read twice are 1 GiB of streaming there.
-    __shared__ unsigned wave_total[4];
-    __shared__ unsigned long long block_base;
-    const uint64_t n_slots = jt.mask + 1;
-    const uint64_t per_block = ((n_slots + gridDim.x - 1) / gridDim.x + 255) & ~255ULL;
-    const uint64_t lo = (uint64_t)blockIdx.x * per_block;
-    const uint64_t hi = lo + per_block < n_slots ? lo + per_block : n_slots;
-    const int wave = (int)(threadIdx.x >> 6);
-    unsigned long long mine = 0;
-    for (uint64_t s = lo + threadIdx.x; s < hi; s += 256) {
-        const uint64_t w = jt.keys[s];
-        if (w != J_EMPTY) mine += ((w >> 62) & 1ULL) + ((w >> 63) & 1ULL);
-    }
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
-    if (fd_lane() == 0) wave_total[wave] = (unsigned)mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long total = (unsigned long long)wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
-        block_base = total ? atomicAdd(n_out, total) : 0ULL;
-    }
-    __syncthreads();
-    unsigned long long base = block_base;
-    for (uint64_t s0 = lo; s0 < hi; s0 += 256) {     // uniform trip count: hi - lo is a multiple of 256 except in the last block
-        const uint64_t s = s0 + threadIdx.x;
-        const uint64_t w = s < hi ? jt.keys[s] : J_EMPTY;
-        const bool has0 = w != J_EMPTY && ((w >> 62) & 1ULL), has1 = w != J_EMPTY && ((w >> 63) & 1ULL);
-        const uint64_t m0 = __ballot(has0), m1 = __ballot(has1);
-        const uint64_t below = (1ULL << fd_lane()) - 1;
-        unsigned rank = (unsigned)(__popcll(m0 & below) + __popcll(m1 & below));
-        __syncthreads();                               // the totals of the previous chunk have been read by everybody
-        if (fd_lane() == 0) wave_total[wave] = (unsigned)(__popcll(m0) + __popcll(m1));
-        __syncthreads();
-        for (int q = 0; q < wave; q++) rank += wave_total[q];
-        unsigned long long idx = base + rank;
-        base += (unsigned long long)wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
-        const uint64_t canon = w & J_KEYMASK;
-        for (int o = 0; o < 2; o++) {
-            if (!(o == 0 ? has0 : has1)) continue;
-            ExportEntry e;
-            e.key = o == 0 ? canon : fd_revcomp(canon, fp.k);
-            e.stamp = jt.stamps[s * 2 + o];
-            const uint64_t* r = (const uint64_t*)(jt.recs + (s * 2 + o) * 16);
-            ((uint64_t*)e.rec)[0] = r[0];
-            ((uint64_t*)e.rec)[1] = r[1];
-            out[idx] = e;
-            stamps_out[idx] = e.stamp;
-            idx++;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) k_gather_sorted(const ExportEntry* in, const uint32_t* order, uint64_t n, uint64_t* keys,
-                                                       fgpu_junction* recs) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    ExportEntry e = in[order[i]];
-    keys[i] = e.key;
-    fgpu_junction r;
-    for (int c = 0; c < 4; c++) r.cov[c] = e.rec[5 + c];
-    for (int c = 0; c < 5; c++) { r.dist[c] = e.rec[c]; r.linked[c] = (e.rec[9] >> c) & 1; }
-    recs[i] = r;
-}
-
 // the keys a batch of this shard has just created join the filter of new keys: the batches behind it were prepared before ANY of this shard was
 // walked, and their planes are only merged with what the filter names (the full refresh sees the table as it stands; this is its equal)
 __global__ void __launch_bounds__(256) k_delta_filter_add(const uint32_t* __restrict__ list, const unsigned long long* __restrict__ count, uint32_t* dfilter,
@@ -2845,77 +2570,6 @@ __global__ void __launch_bounds__(256) k_delta_filter_add(const uint32_t* __rest
         const uint32_t h32 = list[i];
         atomicOr(&dfilter[delta_word(h32, dmask)], delta_bits(h32));
     }
-}
-
-// what an import has to know about its entries beyond putting them into the table: the largest creation stamp (piece number) among them, and --
-// when a preview is being replaced by a later state of the same table -- which keys are newer than the preview: counted, and put into the filter
-__global__ void __launch_bounds__(256) k_import_probe(const ExportEntry* in, uint64_t n, FdParams fp, uint64_t after_seq, uint32_t* dfilter,
-                                                      uint64_t dmask, unsigned long long* out) {
-    // out[2], out[3]: a digest (XOR and sum of the mixed keys) of the entries that are NOT newer -- of a preview: of all its keys.  A table that is
-    // a later state of a preview holds the preview's keys with their stamps, so its not-newer entries give the preview's digest (the
-    // count alone could agree by coincidence for a table that is NOT such a state, e.g. after the sender replayed its scan)
-    unsigned long long mx = 0, newer = 0, dx = 0, dsum = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const ExportEntry e = in[i];
-        const unsigned long long seq = e.stamp >> STAMP_SHIFT;
-        mx = seq > mx ? seq : mx;
-        if (seq <= after_seq) {
-            const unsigned long long m = fd_mix(e.key ^ 0x9E3779B97F4A7C15ULL);
-            dx ^= m;
-            dsum += m;
-        }
-        if (seq > after_seq) {
-            newer++;
-            if (dfilter) {
-                const uint64_t rc = fd_revcomp(e.key, fp.k);
-                const uint32_t h32 = jt_h32(e.key < rc ? e.key : rc);
-                atomicOr(&dfilter[delta_word(h32, dmask)], delta_bits(h32));
-            }
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_down(mx, o, 64);
-        mx = t > mx ? t : mx;
-        newer += __shfl_down(newer, o, 64);
-        dx ^= __shfl_down(dx, o, 64);
-        dsum += __shfl_down(dsum, o, 64);
-    }
-    if (fd_lane() == 0) {
-        if (mx) atomicMax(&out[0], mx);
-        if (newer) atomicAdd(&out[1], newer);
-        if (dx) atomicXor(&out[2], dx);
-        if (dsum) atomicAdd(&out[3], dsum);
-    }
-}
-
-__global__ void __launch_bounds__(256) k_import(JTable jt, FdParams fp, const ExportEntry* in, uint64_t n, DevCounters* cnt) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    ExportEntry e = in[i];
-    uint64_t rc = fd_revcomp(e.key, fp.k);
-    uint64_t canon = e.key < rc ? e.key : rc;
-    int orient = e.key == canon ? 0 : 1;
-    uint64_t slot;
-    uint32_t present;
-    const uint64_t home = fd_mix(canon) & jt.mask;
-    if (!jt_find_or_claim(jt, canon, home, ld_agent(&jt.keys[home]), slot, present, cnt)) { atomicOr(&cnt->error_flags, 1ULL); return; }
-    uint64_t* r = (uint64_t*)(jt.recs + (slot * 2 + orient) * 16);
-    r[0] = ((const uint64_t*)e.rec)[0];
-    r[1] = ((const uint64_t*)e.rec)[1];
-    jt.stamps[slot * 2 + orient] = e.stamp;
-    atomicOr((unsigned long long*)&jt.keys[slot], 1ULL << (62 + orient));
-    const uint64_t hb = jt_filter_bit(jt, canon);
-    atomicOr(&jt.filter[hb >> 5], 1u << (hb & 31));
-}
-
-static uint64_t jfilter_bits(fgpu_ctx* ctx) {
-    static const int lg = getenv("FGPU_JFILTER_LOG2") ? atoi(getenv("FGPU_JFILTER_LOG2")) : 0;   // measurement aid
-    const uint64_t full = ctx->jcap * 2;
-    return lg >= 10 && (1ULL << lg) < full ? 1ULL << lg : full;
-}
-JTable make_jt(fgpu_ctx* ctx) { return JTable{ctx->jkeys, ctx->jrecs, ctx->jstamps, ctx->jcap - 1, ctx->jfilter, jfilter_bits(ctx) - 1}; }
-WTable make_wt(fgpu_ctx* ctx, uint64_t epoch, int parity) {
-    return WTable{ctx->wkeys, ctx->wbits + parity * ((1ULL << ctx->wbits_log2) / 32), ctx->wcap - 1, epoch << 56, (uint32_t)(32 - ctx->wbits_log2)};
 }
 
 }  // namespace
@@ -2987,84 +2641,9 @@ int fgpu_scan_alloc(fgpu_ctx* ctx) {
     }
 }
 
-int fgpu_scan_export_impl(fgpu_ctx* ctx, void* dev_entries, uint64_t cap_entries, uint64_t* d_stamps, uint64_t* n_entries);
-int fgpu_scan_import_impl(fgpu_ctx* ctx, const void* dev_entries, uint64_t n);
-
-// Rehash the junction table into new_cap slots.  Both streams are drained first; records, creation stamps and presence bits
-// travel through the export format of the multi-GPU hand-over (k_export / k_import), so nothing about a junction changes.
-int fgpu_scan_grow(fgpu_ctx* ctx, uint64_t new_cap) {
-    if (new_cap <= ctx->jcap) return FGPU_OK;
-    if (ctx->wstream) FGPU_HIP(fgpu_sync_stream(ctx, ctx->wstream));
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    FGPU_HIP(hipMemcpyAsync(&ctx->counters_host->n_junctions, &ctx->counters->n_junctions, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FGPU_HIP(hipMemcpyAsync(&ctx->counters_host->error_flags, &ctx->counters->error_flags, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    if (ctx->counters_host->error_flags & 1ULL) return FGPU_OK;   // already overflowed: the scan is void, the caller reports it
-    const uint64_t n_max = ctx->counters_host->n_junctions + ctx->scan_imported;
-    int rc;
-    if ((rc = fgpu_ensure(ctx, &ctx->dl_entries, (n_max + 1) * sizeof(ExportEntry))) || (rc = fgpu_ensure(ctx, &ctx->dl_stamps, (n_max + 1) * 8))) return rc;
-    uint64_t n = 0;
-    if (n_max && (rc = fgpu_scan_export_impl(ctx, ctx->dl_entries.p, n_max, (uint64_t*)ctx->dl_stamps.p, &n))) return rc;
-    if (n != n_max) { ctx->err = "junction count mismatch between counters and table (grow)"; return FGPU_ERR_STATE; }
-    uint64_t* nk = nullptr; uint8_t* nr = nullptr; uint64_t* ns = nullptr; uint32_t* nf = nullptr;
-    if (hipMalloc(&nk, new_cap * 8) != hipSuccess || hipMalloc(&nr, new_cap * 32) != hipSuccess || hipMalloc(&ns, new_cap * 16) != hipSuccess ||
-        hipMalloc(&nf, new_cap * 2 / 8) != hipSuccess) {
-        (void)hipGetLastError();
-        hipFree(nk); hipFree(nr); hipFree(ns); hipFree(nf);
-        ctx->err = "junction table: no memory to grow to " + std::to_string(new_cap) + " slots";
-        return FGPU_ERR_NOMEM;
-    }
-    hipFree(ctx->jkeys); hipFree(ctx->jrecs); hipFree(ctx->jstamps); hipFree(ctx->jfilter);
-    ctx->jkeys = nk; ctx->jrecs = nr; ctx->jstamps = ns; ctx->jfilter = nf;
-    ctx->jcap = new_cap;
-    FGPU_HIP(hipMemsetAsync(ctx->jkeys, 0xFF, ctx->jcap * 8, ctx->stream));
-    FGPU_HIP(hipMemsetAsync(ctx->jrecs, 0, ctx->jcap * 32, ctx->stream));
-    FGPU_HIP(hipMemsetAsync(ctx->jfilter, 0, ctx->jcap * 2 / 8, ctx->stream));
-    if ((rc = fgpu_scan_import_impl(ctx, ctx->dl_entries.p, n))) return rc;
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));   // the walk stream starts on the new table
-    ctx->scan_grown++;
-    return FGPU_OK;
-}
-
-// A batch outgrew the table (error bit 1): the scan's attempt is void and is made again from the journal -- on a table with new_cap slots, EMPTY
-// (nothing of the void attempt is kept).  Both streams idle.  The reference's unordered_map just grows (utils/JunctionMap.h:61).
-int fgpu_scan_regrow_empty(fgpu_ctx* ctx, uint64_t new_cap) {
-    if (new_cap <= ctx->jcap) return FGPU_OK;
-    uint64_t* nk = nullptr; uint8_t* nr = nullptr; uint64_t* ns = nullptr; uint32_t* nf = nullptr;
-    if (hipMalloc(&nk, new_cap * 8) != hipSuccess || hipMalloc(&nr, new_cap * 32) != hipSuccess || hipMalloc(&ns, new_cap * 16) != hipSuccess ||
-        hipMalloc(&nf, new_cap * 2 / 8) != hipSuccess) {
-        (void)hipGetLastError();
-        hipFree(nk); hipFree(nr); hipFree(ns); hipFree(nf);
-        ctx->err = "junction table full, and no memory to grow it to " + std::to_string(new_cap) + " slots";
-        return FGPU_ERR_NOMEM;
-    }
-    hipFree(ctx->jkeys); hipFree(ctx->jrecs); hipFree(ctx->jstamps); hipFree(ctx->jfilter);
-    ctx->jkeys = nk; ctx->jrecs = nr; ctx->jstamps = ns; ctx->jfilter = nf;
-    ctx->jcap = new_cap;
-    ctx->scan_grown++;
-    return fgpu_scan_clear_table(ctx);
-}
-
-// empty junction table (a preview is being replaced by the real state); both streams idle
-int fgpu_scan_clear_table(fgpu_ctx* ctx) {
-    FGPU_HIP(hipMemsetAsync(ctx->jkeys, 0xFF, ctx->jcap * 8, ctx->stream));
-    FGPU_HIP(hipMemsetAsync(ctx->jrecs, 0, ctx->jcap * 32, ctx->stream));
-    FGPU_HIP(hipMemsetAsync(ctx->jfilter, 0, ctx->jcap * 2 / 8, ctx->stream));
-    return FGPU_OK;
-}
-
-// called where the host holds a fresh count of the records (batch boundaries): keep the table below a quarter full
-int fgpu_scan_reserve(fgpu_ctx* ctx, uint64_t records) {
-    if (!ctx->jkeys || records * 4 <= ctx->jcap) return FGPU_OK;
-    uint64_t want = ctx->jcap;
-    while (want < records * 16 && want < (1ULL << 31)) want <<= 1;
-    return fgpu_scan_grow(ctx, want);
-}
-
+// a new scan: the junction table empty, the window tables and the large-cluster walks' tables clean
 int fgpu_scan_reset(fgpu_ctx* ctx) {
-    FGPU_HIP(hipMemsetAsync(ctx->jkeys, 0xFF, ctx->jcap * 8, ctx->stream));
-    FGPU_HIP(hipMemsetAsync(ctx->jrecs, 0, ctx->jcap * 32, ctx->stream));
-    FGPU_HIP(hipMemsetAsync(ctx->jfilter, 0, ctx->jcap * 2 / 8, ctx->stream));
+    if (int rc = fgpu_scan_clear_table(ctx)) return rc;
     if (!ctx->wt_epoch) FGPU_HIP(hipMemsetAsync(ctx->wkeys, 0, ctx->wcap * 8, ctx->stream));   // a new table: epoch 0 = no window's entry
     FGPU_HIP(hipMemsetAsync(ctx->wbits, 0, 2 * (1ULL << ctx->wbits_log2) / 8, ctx->stream));        // (a scan that broke off may have left bits behind)
     FGPU_LAUNCH("iota", k_iota_u32, 64, 256, ctx->uf_parent, (uint64_t)ctx->wmax);
@@ -3146,28 +2725,486 @@ int fgpu_stage_scan_debug_drop(fgpu_ctx* ctx) {
     return FGPU_OK;
 }
 
+// ---- the walk stage on the host -------------------------------------------------------------------------------------------------------------
+// The stage's measurement aids and test switches, read from the environment once per process.  (The knobs that size tables or pick the
+// large-cluster walks -- FGPU_WALK_KO*, FGPU_OVW_ROUNDS, FGPU_OVW_EV_LOG2, FGPU_WALK_HEAVY, FGPU_WBITS_LOG2 -- live in the context: fgpu_scan_alloc.)
+static int env_int(const char* name, int absent) { const char* e = getenv(name); return e ? atoi(e) : absent; }
+static bool env_is_one(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
+struct WalkKnobs {
+    const int dbg_walk = env_int("FGPU_DEBUG_WALK", 0);                // bits for timing experiments only; results are wrong when non-zero
+    const bool serial_clean = env_is_one("FGPU_SERIAL_CLEAN");          // the walk stream waits for each window's union-find reset (measurement aid)
+    const bool no_overlap = env_is_one("FGPU_NO_OVERLAP");              // the whole stage on the main stream, nothing beside the pure stage (measurement aid)
+    const bool no_whole_batch = getenv("FGPU_NO_WHOLE_BATCH") != nullptr;   // a prepared batch with a candidate plane is cut into windows like any other
+    const unsigned cluster_grid = (unsigned)std::max(1, env_int("FGPU_CLUSTER_GRID", 256));              // the most blocks k_walk_cluster gets
+    const uint64_t refresh_div = (uint64_t)std::max(1, env_int("FGPU_REFRESH_DIV", 4));                  // a window's planes are made again when the delta exceeds its positions / this
+    const unsigned delta_per_block = (unsigned)std::max(1, env_int("FGPU_DELTA_PER_BLOCK", 1024));       // created keys per block of k_walk_register's delta part
+    const int ko_avg = getenv("FGPU_WALK_KO_AVG") ? std::min(255, std::max(0, env_int("FGPU_WALK_KO_AVG", 0))) : -1;   // lk positions per piece that make "repeat pieces" (-1: large_cluster_rule decides)
+    const int ko_avg_min = getenv("FGPU_WALK_KO_AVG_MIN") ? std::min(255, std::max(1, env_int("FGPU_WALK_KO_AVG_MIN", 0))) : -1;   // the bar in all for clusters of repeat pieces (-1: likewise)
+    const uint32_t ko_ticket = (uint32_t)std::max(64, env_int("FGPU_KO_TICKET", 64) / 64 * 64);          // pieces per ticket of k_walk_ko at the most, a multiple of 64
+    const int ovw_followers = env_int("FGPU_OVW_FOLLOWERS", 0);         // 1: the optimistic walk's pieces count as queueing ones for the window-size controller
+    const bool ovw_beside = !env_is_one("FGPU_OVW_SERIAL");             // FGPU_OVW_SERIAL=1: the optimistic rounds behind k_walk_dyn on one stream instead of beside it
+    // waves of k_walk_dyn (the walk alone on config 2 / config 4's per-GPU shape, ms per step: 1024 waves 19.6 / 16.6; 2048 20.5 / 17.7; 4096 23.3 / 18.8;
+    // one lane per leading piece -- retired -- 19.3 / 22.9)
+    const unsigned walk_dyn_grid = (unsigned)std::max(1, env_int("FGPU_WALK_DYN_GRID", 1024));
+    const bool dbg_span = getenv("FGPU_DEBUG_SPAN") != nullptr;         // every look of the window-size controller on stderr
+};
+static const WalkKnobs& walk_knobs() { static const WalkKnobs knobs; return knobs; }
+
+// what every window of a batch's walk works with
+struct WalkBatch {
+    BatchBufs& bb;
+    Planes pl;
+    JTable jt;
+    uint64_t T, ext, seq_base;    // positions of the batch; how far a piece may reach beyond its window; global number of the batch's first piece
+    hipStream_t walk_stream, ovw_stream;   // the stage's stream; the optimistic rounds' (the walk stream itself: they run behind k_walk_dyn)
+    bool cand_ok;                 // the batch's candidate plane covers every position its first window's link pass can find (see k_walk_link_sparse)
+    DeltaList* created;           // the list this batch's created keys go to
+};
+
+// one scheduling window: the pieces whose first window lies in [lo, hi)
+struct WalkWindow {
+    uint64_t lo, hi, pos_end;     // pos_end: how far its pieces reach at the most
+    int parity;                   // which of the two sets of union-find / list arrays and presence filters it uses (consecutive windows alternate)
+    uint64_t max_pieces;          // bound of its pieces: the grids are sized for THIS window
+    uint32_t *uf_parent, *cl_count, *cl_offset, *cl_fail;   // the parity's set: union-find, followers per root, list heads, k_walk_par's flags / the weights
+    WTable wt;
+    uint32_t *roots_state, *root_list;   // the clusters' leaders: [0] listed, [1] handed out; the list
+};
+
+// who walks the large clusters of a window
+struct LargeClusterRule {
+    uint32_t ko_heavy;     // clusters of at least this many pieces go to the large-cluster walks (0: none do)
+    uint32_t ko_heavy_w;   // the rule by weight, packed (see ko_cluster; 0: off)
+    uint32_t heavy;        // the out-of-order walk's bar (k_walk_par; 0: off)
+    int ovw_rounds;        // rounds of the optimistic walk per window
+    bool ovw_on;           // ... and whether this window issues them
+};
+
+constexpr int OVW_MARK_LOG2 = 22;
+
+// Tests (FGPU_DEBUG_DELTA_CHECK=1): planes that a cheap pass has made against the same planes as the full pass makes them, word by word.
+// full(scratch) issues the full pass so that afterwards scratch (n_words words per plane) and `planes` hold the two versions; the words
+// that differ are added to refresh_mismatch (fgpu_diag_prepared_refresh).
+template <class FullPass>
+static int walk_dbg_compare(fgpu_ctx* ctx, hipStream_t st, const uint64_t* plane0, const uint64_t* plane1, uint64_t n_words, FullPass full, const char* what,
+                            uint64_t batch, uint64_t lo) {
+    uint64_t* scratch = nullptr;
+    unsigned long long* out = nullptr;
+    FGPU_HIP(hipMalloc(&scratch, 2 * n_words * 8));
+    FGPU_HIP(hipMalloc(&out, 32));
+    FGPU_HIP(hipMemsetAsync(out, 0, 32, st));
+    FGPU_HIP(full(scratch));
+    hipLaunchKernelGGL(k_dbg_diff, dim3(64), dim3(256), 0, st, (const uint64_t*)scratch, plane0, n_words, out, 0);
+    if (plane1) hipLaunchKernelGGL(k_dbg_diff, dim3(64), dim3(256), 0, st, (const uint64_t*)(scratch + n_words), plane1, n_words, out, 1);
+    unsigned long long h[4] = {0, 0, 0, 0};
+    FGPU_HIP(hipMemcpyAsync(h, out, 32, hipMemcpyDeviceToHost, st));
+    FGPU_HIP(hipStreamSynchronize(st));
+    ctx->refresh_mismatch += h[0] + h[1];
+    if (h[0] + h[1]) fprintf(stderr, "[fgpu] %s: %llu + %llu words differ, batch %llu window at %llu\n", what, h[0], h[1], (unsigned long long)batch, (unsigned long long)lo);
+    (void)hipFree(scratch); (void)hipFree(out);
+    return FGPU_OK;
+}
+
+// Batches that were prepared before their turn (multi-GPU shards; scan_prepare / scan_walk_prepared) carry snapshot planes of a table that has
+// since been replaced or walked on by an unknown number of batches: made again here, behind the previous batch's walk.  (The preview -- need
+// plane and junction tests -- stays what it was: it is checked by the walk, not trusted.)  *cand_ok: see WalkBatch.
+static int walk_refresh_prepared(fgpu_ctx* ctx, BatchBufs& bb, const JTable& jt, hipStream_t walk_stream, bool* cand_ok) {
+    *cand_ok = false;
+    if (!(ctx->delta_ready && bb.planes_gen == ctx->hint_gen)) {
+        FGPU_LAUNCH("walk_lookup", k_refresh_lookup, fgpu_grid(bb.n_words * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p, bb.n_words,
+                    ctx->fd, jt, (const uint32_t*)jt.filter, jt.filter_mask, (uint64_t*)bb.nF.p, (uint64_t*)bb.nB.p, (const uint32_t*)bb.kh.p, 0, (uint64_t*)nullptr);
+        ctx->refresh_full++;
+        return FGPU_OK;
+    }
+    // the planes speak of the newest preview and the table is a later state of it: only the keys created since are looked for and merged in
+    // (and the candidate plane of the sparse link pass, made against the same preview, gains the positions that hit the filter: k_walk_link_sparse)
+    *cand_ok = !ctx->no_sparse_link && bb.cand.p && bb.cand_gen == ctx->hint_gen;      // (FGPU_NO_SPARSE_LINK: every window in full, as until round 6)
+    if (ctx->delta_keys || ctx->refresh_delta)      // (nothing new in the table and nothing walked yet: the planes stand)
+        FGPU_LAUNCH("walk_lookup", k_refresh_lookup, fgpu_grid(bb.n_words * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p, bb.n_words,
+                    ctx->fd, jt, (const uint32_t*)ctx->delta_filter.p, ctx->delta_filter_bits - 1, (uint64_t*)bb.nF.p, (uint64_t*)bb.nB.p,
+                    (const uint32_t*)bb.kh.p, 1, *cand_ok ? (uint64_t*)bb.cand.p : (uint64_t*)nullptr);
+    ctx->refresh_delta++;
+    if (!ctx->dbg_delta_check) return FGPU_OK;
+    const auto full = [&](uint64_t* scratch) {
+        hipLaunchKernelGGL(k_refresh_lookup, dim3(fgpu_grid(bb.n_words * 64, 256)), dim3(256), 0, walk_stream, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,
+                           bb.n_words, ctx->fd, jt, (const uint32_t*)jt.filter, jt.filter_mask, scratch, scratch + bb.n_words, (const uint32_t*)bb.kh.p, 0,
+                           (uint64_t*)nullptr);
+        return hipSuccess;
+    };
+    return walk_dbg_compare(ctx, walk_stream, (const uint64_t*)bb.nF.p, (const uint64_t*)bb.nB.p, bb.n_words, full, "merged in-map planes against planes made again",
+                            bb.seq, 0);
+}
+
+// The window's turn on the walk stream: its parity's arrays have been reset since the window before last used them, and the window table gets
+// its epoch -- entries carry the window's, everything older counts as empty (the table is wiped once every 255 windows).
+static int walk_window_begin(fgpu_ctx* ctx, const WalkBatch& wb, uint64_t lo, uint64_t hi, WalkWindow* w) {
+    const int parity = (int)(ctx->scan_windows & 1);
+    const uint64_t set = parity * (uint64_t)ctx->wmax;
+    FGPU_HIP(hipStreamWaitEvent(wb.walk_stream, ctx->ev_uf_reset[parity], 0));
+    if (++ctx->wt_epoch > 255) {
+        FGPU_HIP(hipMemsetAsync(ctx->wkeys, 0, ctx->wcap * 8, wb.walk_stream));
+        ctx->wt_epoch = 1;
+    }
+    // grids sized for THIS window (a window of w positions holds at most w/(k+1)+2 piece starts): small windows -- high
+    // coverage data -- must not pay for the launch of the thousands of empty blocks the largest window would need
+    const uint64_t max_pieces = std::min<uint64_t>((hi - lo) / (uint64_t)(ctx->fd.k + 1) + 2, ctx->wmax);
+    *w = WalkWindow{lo, hi, std::min<uint64_t>(wb.T, hi + wb.ext), parity, max_pieces, ctx->uf_parent + set, ctx->cl_count + set, ctx->cl_offset + set, ctx->cl_fail + set,
+                    make_wt(ctx, ctx->wt_epoch, parity),     // (its presence filter was zeroed by the reset kernel of the window before last)
+                    ctx->cl_roots, ctx->cl_roots + 16};
+    return FGPU_OK;
+}
+
+// Step A: the window's candidates register, and with them its delta -- or the window's planes are made again and no delta is registered.
+static int walk_register(fgpu_ctx* ctx, const WalkKnobs& kn, const WalkBatch& wb, const WalkWindow& w) {
+    const BatchBufs& bb = wb.bb;
+    DeltaSrc ds;
+    memset(&ds, 0, sizeof(ds));
+    // The delta of this window: keys created since the batch's snapshot planes were made -- by the batches walked since (their lists)
+    // and by this batch's earlier windows (its own list so far).  Registering it costs one atomic pair per key and WINDOW; where the
+    // windows are small and the delta is not (very high coverage: thousands of windows per batch, a million keys created by the
+    // first of them) it is cheaper to make the snapshot planes of the window's own positions again -- what the look-up kernel of
+    // round 1 did for every window -- and register no delta at all.  The host's estimate of the delta is an upper bound of what it
+    // has seen counted; being wrong only picks the dearer of two exact ways.
+    // (earlier batches: records counted between their walks' issue times; this batch: at most ~3 creations per piece walked so far)
+    const uint64_t delta_est = ctx->delta_ring_keys + (uint64_t)(3.0 * (double)bb.n_pieces * (double)w.lo / (double)wb.T);
+    // (FGPU_REFRESH_DIV: the 4 below.  Swept in round 5 on configs 2, 5 and 4 at full size: 1, 2, 4 within noise of each other, 16 and more --
+    // planes made again more readily -- slower everywhere: config 4's walk stage 1 202 -> 1 258 / 1 343 ms, config 2's step 119.7 -> 122.1 / 125.7 ms;
+    // profiles/r05_refresh_div_sweep.txt)
+    const bool refresh_window = !ctx->refresh_snapshot && delta_est > (w.pos_end - w.lo) / kn.refresh_div;
+    if (refresh_window) {
+        const uint64_t w_first = w.lo >> 6, w_last = std::min<uint64_t>(bb.n_words, (w.pos_end + 63) / 64);
+        FGPU_LAUNCH("walk_lookup", k_need_lookup, fgpu_grid((w_last - w_first) * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p, w_last,
+                    ctx->fd, wb.jt, (uint64_t*)bb.nF.p, (uint64_t*)bb.nB.p, (uint32_t*)bb.kh.p, w_first);
+    } else {
+        if (!ctx->refresh_snapshot)      // (a batch whose planes were just made again needs no earlier batch's keys)
+            for (int r = 1; r < FGPU_DELTA_RING && (uint64_t)r <= ctx->delta_next; r++) {
+                const DeltaList& dl = ctx->delta_ring[(ctx->delta_next - r) % FGPU_DELTA_RING];
+                ds.list[r - 1] = (const uint32_t*)dl.list.p;
+                ds.count[r - 1] = (const unsigned long long*)dl.count.p;
+            }
+        if (w.lo) {
+            ds.list[FGPU_DELTA_RING - 1] = (const uint32_t*)wb.created->list.p;
+            ds.count[FGPU_DELTA_RING - 1] = (const unsigned long long*)wb.created->count.p;
+        }
+    }
+    const unsigned word_blocks = fgpu_blocks((w.pos_end - (w.lo & ~63ULL) + 63) / 64, 256);
+    const unsigned piece_blocks = fgpu_blocks(w.max_pieces, 256);
+    // the delta's share of the grid by its size: 64 blocks took a batch's worth of created keys (millions per window while a large map is
+    // being built: config 4's first shards) 500 dependent atomics per thread, the kernel's tail.  One block per 1024 keys: walk stage of
+    // config 4 1 216 -> 1 150-1 177 ms, config 5 298 -> 278-282 ms, the steps' wall time within noise (the pure stage beside it bounds pass 2);
+    // config 2 unchanged (its delta never exceeds 64 blocks' worth).  profiles/r05_walk_grid_sweep.txt
+    const unsigned delta_blocks = refresh_window ? 64u : (unsigned)std::min<uint64_t>(4096, std::max<uint64_t>(64, delta_est / kn.delta_per_block));
+    FGPU_LAUNCH("walk_lookup", k_walk_register, word_blocks + piece_blocks + delta_blocks, 256, wb.pl, ctx->fd, w.wt, w.uf_parent, w.lo, w.hi, w.pos_end, ctx->counters,
+                word_blocks, piece_blocks, ds);
+    return FGPU_OK;
+}
+
+// Step B: every position against the window table -- or, for the first window of a prepared batch with a candidate plane, the plane's positions only.
+static int walk_link(fgpu_ctx* ctx, const WalkBatch& wb, const WalkWindow& w) {
+    const BatchBufs& bb = wb.bb;
+    const unsigned full_grid = std::min(fgpu_blocks(w.pos_end - (w.lo & ~63ULL), 1024), 4096u);
+    if (!(wb.cand_ok && w.lo == 0)) {      // (lo > 0: the window registers what this batch's earlier windows created -- positions the plane does not know)
+        FGPU_LAUNCH("walk_link", k_walk_link, full_grid, 256, wb.pl, ctx->fd, w.wt, w.uf_parent, w.lo, w.hi, w.pos_end, w.roots_state);
+        if (ctx->refresh_snapshot) ctx->full_links++;
+        return FGPU_OK;
+    }
+    const uint64_t link_words = ((w.pos_end + 63) >> 6) - (w.lo >> 6);
+    uint64_t* const lk = (uint64_t*)bb.lk.p + (w.lo >> 6);
+    FGPU_LAUNCH("walk_link", k_walk_link_sparse, std::min(fgpu_blocks(link_words, 256), 4096u), 256, wb.pl, ctx->fd, w.wt, w.uf_parent, w.lo, w.hi, w.pos_end,
+                w.roots_state, (const uint64_t*)bb.cand.p, (uint64_t*)bb.lk.p);
+    ctx->sparse_links++;
+    if (!ctx->dbg_delta_check) return FGPU_OK;
+    const auto full = [&](uint64_t* scratch) {      // the sparse pass's plane is kept; the full pass makes its own in place (its unions are the same ones again)
+        const hipError_t e = hipMemcpyAsync(scratch, lk, link_words * 8, hipMemcpyDeviceToDevice, wb.walk_stream);
+        hipLaunchKernelGGL(k_walk_link, dim3(full_grid), dim3(256), 0, wb.walk_stream, wb.pl, ctx->fd, w.wt, w.uf_parent, w.lo, w.hi, w.pos_end, (uint32_t*)nullptr);
+        return e;
+    };
+    return walk_dbg_compare(ctx, wb.walk_stream, (const uint64_t*)lk, (const uint64_t*)nullptr, link_words, full, "sparse link pass: lk plane against the full pass's",
+                            bb.seq, w.lo);
+}
+
+// Who walks a window's large clusters: a rule of the host's, from the knobs and from what the scan has shown so far -- the counters as the
+// host last saw them (every batch's pure stage brings them along).  Launches nothing; whatever it answers, the results are the same.
+static LargeClusterRule large_cluster_rule(fgpu_ctx* ctx, const WalkKnobs& kn) {
+    const DevCounters& seen = *ctx->counters_host;
+    LargeClusterRule r;
+    // The key-ordered walk costs four small launches per window whether or not the window holds a large cluster, so it is switched on by
+    // what the scan has shown so far: the largest cluster among the windows whose counters the host has seen.  Data without such clusters
+    // never pays; data with them walks its first batch by cluster.  FGPU_WALK_KO_ALWAYS=1: from the first window (tests).
+    r.ko_heavy = (kn.dbg_walk || !ctx->walk_ko || !(ctx->walk_ko_always || seen.max_cluster >= ctx->walk_ko)) ? 0u : ctx->walk_ko;
+    // ... and, for callers that expect repeats, the clusters whose pieces hold many lk positions between them (ko_cluster): the weights
+    // are summed by k_walk_cluster into cl_fail, which the out-of-order walk (k_walk_par, the other way of taking clusters out of k_walk_dyn)
+    // does not use then
+    // The rule by weight has two bars: lk positions of a cluster in all (ko_total), and -- for clusters of "repeat pieces", pieces that hold
+    // many of them -- positions per piece and a lower bar in all.  Ordinary pieces hold 2-5, some 8 and more; pieces inside a repeat at high
+    // coverage 40 and more.  Once a scan HAS shown repeats (2 % of the pieces walked so far went to the large-cluster walks) the second bar
+    // drops from (12 per piece, 48 in all) to (8, 16): measured on config 3's shape through the CLI pass 2 goes from 245-250 ms to 190 ms
+    // (the windows grow from 62 to 22: what is left to k_walk_dyn no longer queues), while config 2 with the CLI's settings would pay 10 ms per
+    // step for the lower bar (walk stage 52.6 -> 62.6 ms; scripts/ovw_thresholds.sh, gpurun_out/r04_ovw_thresholds2.txt).
+    const bool repeats_seen = seen.walk_parallel * 50 > seen.walked_pieces ||
+                              (ctx->walk_ko_always && seen.walked_pieces < (1ULL << 17) && ctx->delta_next >= 2 && ctx->repeats_seen_before);   // (same lag: keep what the scan had found)
+    if (repeats_seen) ctx->repeats_seen_before = true;
+    const uint32_t ko_total = std::min<uint32_t>(ctx->walk_ko_weight, 0xFFFFu);
+    const uint32_t ko_avg = kn.ko_avg >= 0 ? (uint32_t)kn.ko_avg : repeats_seen ? 8u : 12u;
+    const uint32_t ko_total_rep = kn.ko_avg_min > 0 ? (uint32_t)kn.ko_avg_min : repeats_seen ? 16u : std::min<uint32_t>(255u, 3 * ko_total / 8);
+    r.ko_heavy_w = (r.ko_heavy && ko_total) ? (ko_total | (ko_avg << 16) | (ko_total_rep << 24)) : 0u;
+    r.heavy = (kn.dbg_walk || r.ko_heavy) ? 0u : ctx->walk_heavy;   // (one way of taking large clusters out of k_walk_dyn at a time)
+    // The optimistic walk (k_ovw_round) takes the large clusters first; the key-ordered walk runs behind it for what it leaves.  Its
+    // rounds are launches whether or not the window holds such a cluster, so -- like the key-ordered walk itself -- it is switched on by
+    // what the scan has shown: pieces of large clusters among the pieces walked so far (callers that expect repeats: from the first window).
+    r.ovw_rounds = !r.ko_heavy ? 0 : std::min(ctx->ovw_rounds, OVW_MAX_ROUNDS);
+    // (a caller that expects repeats gets it for the scan's first two batches; after that the scan's own counters decide: on ordinary data the
+    // few large clusters cost less with the key-ordered walk alone than with a dozen launches more per window -- config 2 with the CLI's
+    // settings: walk stage 52.6 ms with the rounds always issued, scripts/ovw_config2.sh)
+    // (the counters are the host's snapshot of the previous pure stage's end: when the walk lags two batches behind at that moment --
+    // it happens, by the timing of the machine -- they do not show a single large cluster yet.  A caller that expects repeats therefore
+    // keeps the rounds until the counters have SEEN enough pieces to say otherwise: round 4 met runs of config 3's shape in which the
+    // third batch went without them and pass 2 took 310-360 instead of 160 ms)
+    const bool ovw_seen_enough = seen.walked_pieces >= (1ULL << 17);
+    r.ovw_on = r.ovw_rounds > 0 && ((ctx->walk_ko_always && (ctx->delta_next < 2 || !ovw_seen_enough)) || seen.walk_parallel * 256 > seen.walked_pieces);
+    return r;
+}
+
+// The tables of the large-cluster walks for this window: the key-ordered walk's are the context's; the optimistic walk's follow what the scan
+// has shown, are allocated when a window first wants them, and are wiped when their epochs run out.
+static int walk_large_tables(fgpu_ctx* ctx, const WalkBatch& wb, const LargeClusterRule& rule, KoTables& kt, OvwTables& ot) {
+    kt.hk_key = ctx->ko_hk;
+    kt.hk_head = ctx->ko_hk + ctx->ko_hk_cap;
+    kt.hk_turn = ctx->ko_hk + 2 * (size_t)ctx->ko_hk_cap;
+    kt.hk_mask = ctx->ko_hk_cap - 1;
+    kt.occ_id = (uint64_t*)ctx->ko_occ;
+    kt.occ_entry = (uint32_t*)(kt.occ_id + ctx->ko_occ_cap);
+    kt.occ_rank = kt.occ_entry + ctx->ko_occ_cap;
+    kt.occ_next = kt.occ_rank + ctx->ko_occ_cap;
+    kt.occ_cap = ctx->ko_occ_cap;
+    kt.trace = nullptr;
+#ifdef FGPU_KO_TRACE
+    if (!ctx->ko_trace.p) {
+        if (int trc = fgpu_ensure(ctx, &ctx->ko_trace, ((1ULL << 23) + 4096 * 1024) * 8)) return trc;
+        FGPU_HIP(hipMemsetAsync(ctx->ko_trace.p, 0, 32, ctx->stream));
+    }
+    kt.trace = (unsigned long long*)ctx->ko_trace.p;
+#endif
+    kt.state = ctx->ko_piece;                 // 16 words in front of the per-piece arrays
+    kt.piece_base = ctx->ko_piece + 16;
+    kt.bad = kt.piece_base + ctx->wmax;
+    memset(&ot, 0, sizeof(ot));
+    {   // the event tables follow what the scan has shown (weak 9 of VERDICT r4): once a round of some window has filled a quarter of a table,
+        // the next windows get tables eight times that round's entries -- before a window overflows them and is left to the key-ordered walk
+        const uint64_t fill = ctx->counters_host->ovw_fill;
+        int want = ctx->ovw_ev_log2;
+        while (want < 27 && fill * 4 > (1ULL << want)) want++;
+        if (want != ctx->ovw_ev_log2) {
+            while (want < 27 && fill * 8 > (1ULL << want)) want++;
+            if (ctx->ovw_ev.p) {     // rounds of the window before may still be reading the tables that are about to be replaced
+                FGPU_HIP(fgpu_sync_stream(ctx, wb.walk_stream));
+                if (ctx->ostream) FGPU_HIP(fgpu_sync_stream(ctx, ctx->ostream));
+            }
+            ctx->ovw_ev_log2 = want;
+        }
+    }
+    if (!rule.ovw_on) return FGPU_OK;
+    int rc;
+    const int ev_log2 = ctx->ovw_ev_log2;
+    const uint32_t filt_words = 1u << (ev_log2 + 1 - 5), list_cap = (uint32_t)std::min<uint64_t>(ctx->wmax, 1u << 20);   // (a round's filter: two bits per entry of its table)
+    const bool fresh = !ctx->ovw_ev.p || ctx->ovw_ev_log2_alloc != ev_log2;     // (grown since the last window: other table boundaries, wipe)
+    ctx->ovw_ev_log2_alloc = ev_log2;
+    if ((rc = fgpu_ensure(ctx, &ctx->ovw_ev, 4ULL * 8 * (1ULL << ev_log2))) || (rc = fgpu_ensure(ctx, &ctx->ovw_filt, 3ULL * 4 * filt_words)) ||
+        (rc = fgpu_ensure(ctx, &ctx->ovw_log, 2ULL * ctx->ko_occ_cap * sizeof(uint4))) || (rc = fgpu_ensure(ctx, &ctx->ovw_res, 32ULL * list_cap)) ||
+        (rc = fgpu_ensure(ctx, &ctx->ovw_marks, 3ULL * 4 * (1ULL << OVW_MARK_LOG2))) ||
+        (rc = fgpu_ensure(ctx, &ctx->ovw_list, 4ULL * list_cap)) || (rc = fgpu_ensure(ctx, &ctx->ovw_state, 4ULL * (8 + OVW_MAX_ROUNDS) + 64)) ||
+        (rc = fgpu_ensure(ctx, &ctx->ovw_longp, 4ULL * ctx->wmax)))
+        return rc;
+    if (fresh || ctx->ovw_epoch + (uint32_t)rule.ovw_rounds > 255) {   // event entries carry their round's epoch: a wiped table holds none
+        FGPU_HIP(hipMemsetAsync(ctx->ovw_ev.p, 0, 4ULL * 8 * (1ULL << ev_log2), wb.walk_stream));
+        ctx->ovw_epoch = 0;
+    }
+    ot.list = (uint32_t*)ctx->ovw_list.p;
+    ot.list_cap = list_cap;
+    ot.state = (uint32_t*)ctx->ovw_state.p;
+    ot.longp = (uint32_t*)ctx->ovw_longp.p;
+    ot.filt_words = filt_words;
+    return FGPU_OK;
+}
+
+// The large clusters are listed (k_ko_prepare) and the optimistic walk takes them first: its rounds and its commit.
+// The rounds run on a stream of their own BESIDE k_walk_dyn: the two walk disjoint clusters (a key belongs to the one cluster every piece that
+// holds it is in), so neither reads a record the other writes; slot claims, counters, planes and filters change by atomics on both sides.
+// The walk stream waits for them in walk_clusters (ev_settled).
+static int walk_large_first(fgpu_ctx* ctx, const WalkKnobs& kn, const WalkBatch& wb, const WalkWindow& w, const LargeClusterRule& rule, const KoTables& kt,
+                            OvwTables& ot) {
+    const int ev_log2 = ctx->ovw_ev_log2;
+    const uint32_t filt_words = ot.filt_words;                           // (these two: set where the window issues the rounds)
+    uint32_t* const ovw_filt = rule.ovw_on ? (uint32_t*)ctx->ovw_filt.p : nullptr;
+    if (rule.ko_heavy) {
+        FGPU_LAUNCH("walk_ko_prepare", k_ko_reset, 256, 256, kt, (uint32_t)ctx->wmax, (uint32_t)w.parity);
+        if (rule.ovw_on) FGPU_LAUNCH("walk_ko_prepare", k_ovw_reset, 64, 256, ot.state, ovw_filt, 3 * filt_words, ot.longp, (uint32_t)w.max_pieces,
+                                     (uint32_t*)ctx->ovw_marks.p, 3u << OVW_MARK_LOG2);
+        FGPU_LAUNCH("walk_ko_prepare", k_ko_prepare, fgpu_blocks(w.max_pieces, 256), 256, wb.pl, (const uint32_t*)ctx->cl_fill, (const uint32_t*)w.cl_count,
+                    (const WinDesc*)ctx->wdesc, kt, rule.ko_heavy, (uint32_t)w.parity, (const uint32_t*)w.cl_fail, rule.ko_heavy_w, ot);
+    }
+    if (!rule.ovw_on) return FGPU_OK;
+    if (wb.ovw_stream != wb.walk_stream) {
+        FGPU_HIP(hipEventRecord(ctx->ev_listed, wb.walk_stream));
+        FGPU_HIP(hipStreamWaitEvent(wb.ovw_stream, ctx->ev_listed, 0));
+        ctx->launch_stream = wb.ovw_stream;
+    }
+    unsigned long long* const evb = (unsigned long long*)ctx->ovw_ev.p;
+    uint32_t* const marks = (uint32_t*)ctx->ovw_marks.p;
+    ot.log = (uint4*)ctx->ovw_log.p;
+    ot.res = (uint32_t*)ctx->ovw_res.p;
+    ot.mark_mask = (1u << OVW_MARK_LOG2) - 1;
+    const unsigned ovw_grid = (unsigned)std::min<uint64_t>(fgpu_blocks(std::min<uint64_t>(w.max_pieces, ot.list_cap), 64), 2048);
+    const auto table = [&](int r, uint64_t epoch) {
+        OvwEv ev;
+        ev.key = evb + (uint64_t)(r & 1) * 2 * (1ULL << ev_log2);
+        ev.val = ev.key + (1ULL << ev_log2);
+        ev.bits = ovw_filt + (uint64_t)(r % 3) * filt_words;
+        ev.mask = (1ULL << ev_log2) - 1;
+        ev.epoch = epoch << 56;
+        ev.fshift = 32 - (ev_log2 + 1);
+        return ev;
+    };
+    const uint64_t epoch_first = (uint64_t)ctx->ovw_epoch + 1;
+    for (int r = 0; r < rule.ovw_rounds; r++) {
+        ctx->ovw_epoch++;
+        ot.cur = table(r, ctx->ovw_epoch);
+        ot.prev = table(r + 1, ctx->ovw_epoch - 1);           // (the other table, the filter of round r - 1: (r + 2) % 3 == (r - 1) % 3)
+        ot.prev.bits = ovw_filt + (uint64_t)((r + 2) % 3) * filt_words;
+        ot.filt_next = ovw_filt + (uint64_t)((r + 1) % 3) * filt_words;
+        ot.mark_cur = marks + ((uint64_t)(r % 3) << OVW_MARK_LOG2);
+        ot.mark_prev = marks + ((uint64_t)((r + 2) % 3) << OVW_MARK_LOG2);
+        ot.mark_next = marks + ((uint64_t)((r + 1) % 3) << OVW_MARK_LOG2);
+        FGPU_LAUNCH("walk_ovw", k_ovw_round, ovw_grid, 64, wb.pl, ctx->fd, wb.jt, (const uint32_t*)ctx->cl_fill, (const WinDesc*)ctx->wdesc, kt, ot, (uint32_t)r,
+                    (const uint32_t*)ctx->bloo2, ctx->counters);
+    }
+    // (the pieces it walks do not queue behind one another, so they do not count as followers for the window-size controller -- the key-ordered
+    // walk's did: 68 windows instead of 22 on config 3's shape -- unless FGPU_OVW_FOLLOWERS=1 says so)
+    FGPU_LAUNCH("walk_ovw", k_ovw_commit, ovw_grid, 64, wb.pl, ctx->fd, wb.jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)w.cl_count, (const WinDesc*)ctx->wdesc,
+                wb.seq_base, kt, ot, rule.ovw_rounds, ctx->counters, kn.ovw_followers, (const unsigned long long*)evb, (uint64_t)1 << ev_log2, epoch_first);
+    if (wb.ovw_stream != wb.walk_stream) {
+        FGPU_HIP(hipEventRecord(ctx->ev_settled, wb.ovw_stream));
+        ctx->launch_stream = wb.walk_stream;
+    }
+    return FGPU_OK;
+}
+
+// Step D: the walks.  k_walk_dyn takes every cluster nobody else does; behind it (and behind the optimistic walk, whose settled logs are in the
+// map by then) the key-ordered walk takes what the optimistic walk left; k_walk_par's two halves bracket them where the out-of-order walk is on.
+static int walk_clusters(fgpu_ctx* ctx, const WalkKnobs& kn, const WalkBatch& wb, const WalkWindow& w, const LargeClusterRule& rule, const KoTables& kt,
+                         const OvwTables& ot) {
+    const unsigned walk_grid_w = fgpu_blocks(w.max_pieces, 64);
+#ifdef FGPU_KO_ONE_XCD
+    const unsigned ko_grid = 4096;
+#else
+    const unsigned ko_grid = 512;
+#endif
+    if (rule.heavy)
+        FGPU_LAUNCH("walk_probe", k_walk_par<WALK_PROBE>, walk_grid_w, 64, wb.pl, ctx->fd, wb.jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)w.cl_count, w.cl_fail,
+                    (const WinDesc*)ctx->wdesc, (const uint32_t*)ctx->bloo2, ctx->counters, rule.heavy);
+    FGPU_LAUNCH("walk", k_walk_dyn, std::min(walk_grid_w, kn.walk_dyn_grid), 64, wb.pl, ctx->fd, wb.jt, (const uint32_t*)w.root_list, w.roots_state,
+                (const uint32_t*)w.cl_count, (const uint32_t*)w.cl_offset, (const uint32_t*)ctx->cl_members, ctx->cl_members + ctx->wmax, (const WinDesc*)ctx->wdesc,
+                wb.seq_base, (const uint32_t*)ctx->bloo2, ctx->counters, kn.dbg_walk, (const uint32_t*)w.cl_fail, rule.heavy, (const uint32_t*)kt.bad,
+                (const uint32_t*)kt.state, rule.ko_heavy, (uint32_t)ctx->scan_windows, rule.ko_heavy_w);
+    if (rule.ovw_on && wb.ovw_stream != wb.walk_stream) FGPU_HIP(hipStreamWaitEvent(wb.walk_stream, ctx->ev_settled, 0));   // the settled logs are in the map
+    if (rule.ko_heavy) {     // (ranks of the occurrences per k-mer: only the key-ordered walk needs them, and only for what the optimistic walk left)
+        FGPU_LAUNCH("walk_ko_prepare", k_ko_rank, 256, 256, kt, (const uint32_t*)ot.state, rule.ovw_rounds);
+        FGPU_LAUNCH("walk_ko", k_walk_ko, ko_grid, 64, wb.pl, ctx->fd, wb.jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)w.cl_count, (const WinDesc*)ctx->wdesc,
+                    wb.seq_base, (const uint32_t*)ctx->bloo2, ctx->counters, kt, rule.ko_heavy, kn.ko_ticket, (const uint32_t*)w.cl_fail, rule.ko_heavy_w,
+                    (const uint32_t*)ot.state, (const uint32_t*)ot.longp, rule.ovw_rounds);
+    }
+    if (rule.heavy)
+        FGPU_LAUNCH("walk_commit", k_walk_par<WALK_COMMIT>, walk_grid_w, 64, wb.pl, ctx->fd, wb.jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)w.cl_count, w.cl_fail,
+                    (const WinDesc*)ctx->wdesc, (const uint32_t*)ctx->bloo2, ctx->counters, rule.heavy);
+    return FGPU_OK;
+}
+
+// Step E: the keys this window created join the batch's list (and leave the plane): the next window's delta.  The window's set of arrays is
+// reset on the side stream while the next window (the other set) is looked up and linked.
+static int walk_collect_and_reset(fgpu_ctx* ctx, const WalkKnobs& kn, const WalkBatch& wb, const WalkWindow& w) {
+    const BatchBufs& bb = wb.bb;
+    const uint64_t w_first = w.lo >> 6, w_last = std::min<uint64_t>(bb.n_words, (w.pos_end + 63) / 64);
+    FGPU_LAUNCH("walk_delta", k_delta_collect, (unsigned)std::min<uint64_t>(fgpu_blocks(w_last - w_first, 256), 256), 256, (unsigned long long*)bb.cr.p,
+                (const uint32_t*)bb.kh.p, w_first, w_last, (uint32_t*)wb.created->list.p, (unsigned long long*)wb.created->count.p, wb.pl,
+                (const WinDesc*)ctx->wdesc, ctx->counters, (uint32_t)ctx->scan_windows);
+    FGPU_HIP(hipEventRecord(ctx->ev_walked, wb.walk_stream));
+    FGPU_HIP(hipStreamWaitEvent(ctx->cstream, ctx->ev_walked, 0));
+    ctx->launch_stream = ctx->cstream;
+    FGPU_LAUNCH("walk_clean", k_walk_reset_uf, std::min(256u, fgpu_blocks(w.max_pieces, 256)), 256, w.uf_parent, w.cl_count, w.cl_offset, w.cl_fail, (uint32_t)w.max_pieces,
+                (uint4*)w.wt.bits, (uint32_t)((1u << ctx->wbits_log2) / 128));
+    ctx->launch_stream = wb.walk_stream;
+    FGPU_HIP(hipEventRecord(ctx->ev_uf_reset[w.parity], ctx->cstream));
+    if (kn.serial_clean) FGPU_HIP(hipStreamWaitEvent(wb.walk_stream, ctx->ev_uf_reset[w.parity], 0));
+    return FGPU_OK;
+}
+
+// Calibration: at the start of a scan (and again whenever a batch came out with most of its pieces queueing) the host
+// waits for the window it has just issued and looks at the share of pieces that had to queue behind an earlier piece of
+// their cluster.  High coverage makes clusters percolate -- 250x reads of a small genome were 20x slower with the 4 M
+// position windows that suit 50x data -- and a whole batch is too long to walk with the wrong size.
+// *span_now: the span of the windows that follow.
+static int walk_span_look(fgpu_ctx* ctx, const WalkKnobs& kn, hipStream_t walk_stream, uint64_t* span_now) {
+    if (ctx->calib_left <= 0 || ctx->prm.walk_window_span) return FGPU_OK;
+    FGPU_HIP(hipMemcpyAsync(ctx->fb_host, &ctx->counters->followers, 8, hipMemcpyDeviceToHost, walk_stream));
+    FGPU_HIP(hipMemcpyAsync(ctx->fb_host + 1, &ctx->counters->walked_pieces, 8, hipMemcpyDeviceToHost, walk_stream));
+    FGPU_HIP(hipMemcpyAsync(ctx->fb_host + 2, &ctx->counters->ko_overflows, 8, hipMemcpyDeviceToHost, walk_stream));
+    FGPU_HIP(fgpu_sync_stream(ctx, walk_stream));
+    uint64_t span = *span_now;
+    const uint64_t f = ctx->fb_host[0] - ctx->calib_f, p = ctx->fb_host[1] - ctx->calib_p;
+    if (ctx->fb_host[2] > ctx->calib_ovf && span > 4096) {
+        // the window's large clusters outgrew the tables of the large-cluster walks (their pieces do not queue, so the share of
+        // followers says nothing about them) and were walked by one thread each: far too large a window for this data -- a quarter,
+        // and the next windows are looked at as well (round 4: read pairs inside repeats at 600x, a 36 MB file whose windows grew to
+        // 2^23 positions within its three batches: pass 2 2.0 s, 0.8 s with windows of 2^20)
+        ctx->calib_ovf = ctx->fb_host[2];
+        ctx->calib_f = ctx->fb_host[0];
+        ctx->calib_p = ctx->fb_host[1];
+        span = std::max<uint64_t>(4096, span / 4);
+        ctx->proven_span = std::min(ctx->proven_span, span);
+        ctx->calib_left = std::max(ctx->calib_left, 4);
+        ctx->span_ceiling = std::min(ctx->span_ceiling, span * 2);     // (this scan does not grow to that size again)
+        if (kn.dbg_span) fprintf(stderr, "[span] look: the large-cluster walks' tables overflowed -> span %llu, looks left %d\n", (unsigned long long)span, ctx->calib_left);
+    } else if (p >= 64) {
+        ctx->calib_f = ctx->fb_host[0];
+        ctx->calib_p = ctx->fb_host[1];
+        bool shrunk = false;
+        const uint64_t ceiling = std::min<uint64_t>(ctx->max_span, ctx->span_ceiling), usual = std::min<uint64_t>(ceiling, FGPU_USUAL_SPAN);
+        if (f * 2 > p && span > 4096) { span /= 2; shrunk = true; }
+        else if (f * 3 < p && span < usual) span = std::min<uint64_t>(span * 4, usual);
+        else if (f * 16 < p && span < ceiling) span = std::min<uint64_t>(span * 4, ceiling);
+        else ctx->calib_left = 1;          // settled
+        ctx->calib_left--;
+        // waiting for a window keeps the host from feeding the pure stage of the next batch: worth it while windows are small
+        // (a fraction of a millisecond each, and the wrong size hurts most there); from 2^22 positions on the per-batch
+        // controller (adapt_window, no waiting) takes over unless the last look said "too large"
+        if (!shrunk && span >= (1ULL << 22)) ctx->calib_left = 0;
+        if (kn.dbg_span) fprintf(stderr, "[span] look: followers %llu of %llu pieces -> span %llu, looks left %d\n", (unsigned long long)f, (unsigned long long)p,
+                                 (unsigned long long)span, ctx->calib_left);
+    }
+    *span_now = span;
+    return FGPU_OK;
+}
+
 // Walk the pieces of the current batch, scheduling window after scheduling window (position ranges of
 // ctx->window_span stream positions).  No host round trip: window extents are derived on the device.
 int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
     if (!n_pieces) return FGPU_OK;
+    const WalkKnobs& kn = walk_knobs();
     BatchBufs& bb = *ctx->cur;
+    int rc;
+    const uint64_t wbytes = (bb.n_words + FGPU_PADW) * 8;      // a plane of the batch
     Planes pl{(const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p, (const uint64_t*)bb.ps.p, (const uint32_t*)bb.ps_prefix.p,
               (const uint64_t*)bb.ff.p, (const uint64_t*)bb.fb.p, (const uint64_t*)bb.cf0.p, (const uint64_t*)bb.cf1.p,
               (const uint64_t*)bb.cb0.p, (const uint64_t*)bb.cb1.p, (uint64_t*)bb.nF.p, (uint64_t*)bb.nB.p, (const uint2*)bb.pieces.p,
               (uint64_t*)bb.lk.p, (const uint64_t*)bb.need.p, nullptr, nullptr, (const uint32_t*)bb.kh.p, nullptr};
-    {   // in-map planes of the walk = the pure stage's snapshot planes nF / nB (see k_walk_register); creation plane of this batch
-        const uint64_t wb = (bb.n_words + FGPU_PADW) * 8;
-        if (int rc = fgpu_ensure_b(ctx, &bb.cr, wb)) return rc;
-        pl.cr = (unsigned long long*)bb.cr.p;
-    }
+    // in-map planes of the walk = the pure stage's snapshot planes nF / nB (see k_walk_register); creation plane of this batch
+    if ((rc = fgpu_ensure_b(ctx, &bb.cr, wbytes))) return rc;
+    pl.cr = (unsigned long long*)bb.cr.p;
     if (ctx->record_stops) {
-        const uint64_t wb = (bb.n_words + FGPU_PADW) * 8;
-        int rc;
-        if ((rc = fgpu_ensure_b(ctx, &bb.sF, wb)) || (rc = fgpu_ensure_b(ctx, &bb.sB, wb))) return rc;
+        if ((rc = fgpu_ensure_b(ctx, &bb.sF, wbytes)) || (rc = fgpu_ensure_b(ctx, &bb.sB, wbytes))) return rc;
         pl.sF = (unsigned long long*)bb.sF.p;
         pl.sB = (unsigned long long*)bb.sB.p;
     }
-    JTable jt = make_jt(ctx);
     const uint64_t span = ctx->window_span;
     const uint64_t ext = bb.max_piece_span;          // a piece that starts inside the window may reach this far beyond it
     if (ctx->max_span + ext + 64 > ctx->wcap) {      // the per-position slot list of a window is sized for 4 x the largest span
@@ -3178,66 +3215,23 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
         ctx->err = "a read of " + std::to_string(ext) + " bases is longer than the junction creation stamps allow (2^19 windows)";
         return FGPU_ERR_CAPACITY;
     }
-    const uint64_t T = bb.T;
-    const uint64_t seq_base = ctx->scan_piece_base;
-    static const int dbg_walk = getenv("FGPU_DEBUG_WALK") ? atoi(getenv("FGPU_DEBUG_WALK")) : 0;
-    static const bool serial_clean = getenv("FGPU_SERIAL_CLEAN") && getenv("FGPU_SERIAL_CLEAN")[0] == '1';   // measurement aid: union-find reset in line
-    // the whole stage goes to the walk stream, behind the completion of this batch's pure stage
-    static const bool no_overlap = getenv("FGPU_NO_OVERLAP") && getenv("FGPU_NO_OVERLAP")[0] == '1';   // measurement aid
-    hipStream_t walk_stream = no_overlap ? ctx->stream : ctx->wstream;
+    // the whole stage goes to the walk stream, behind the completion of this batch's pure stage; the optimistic rounds to a stream of their own
+    hipStream_t walk_stream = kn.no_overlap ? ctx->stream : ctx->wstream;
+    hipStream_t ovw_stream = (kn.ovw_beside && !kn.no_overlap && ctx->ostream) ? ctx->ostream : walk_stream;
+    // the list this batch's created keys go to: the oldest of the ring (its readers -- the windows of the batches in between -- are
+    // behind us on this stream)
+    WalkBatch wb{bb, pl, make_jt(ctx), bb.T, ext, ctx->scan_piece_base, walk_stream, ovw_stream, false, &ctx->delta_ring[ctx->delta_next % FGPU_DELTA_RING]};
+    const uint64_t T = wb.T;
     ctx->launch_stream = walk_stream;
     if (bb.pure_done) FGPU_HIP(hipStreamWaitEvent(walk_stream, bb.pure_done, 0));
-    const int stall_us = ctx->dbg_stall_us;
-    if (stall_us) FGPU_LAUNCH("debug_stall", k_debug_stall, 1, 1, (unsigned long long)stall_us * 100ULL);
-    bool cand_ok = false;      // this batch's candidate plane covers every position its windows' link passes can find (see k_walk_link_sparse)
-    if (ctx->refresh_snapshot) {
-        // batches that were prepared before their turn (multi-GPU shards; scan_prepare / scan_walk_prepared) carry snapshot planes of a table
-        // that has since been replaced or walked on by an unknown number of batches: made again here, behind the previous batch's walk
-        // (the preview -- need plane and junction tests -- stays what it was: it is checked by the walk, not trusted)
-        static const bool old_refresh = getenv("FGPU_REFRESH_OLD") != nullptr;      // measurement aid: the pure stage's kernel, as until round 5
-        if (old_refresh)
-            FGPU_LAUNCH("walk_lookup", k_need_lookup, fgpu_grid(bb.n_words * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p, bb.n_words,
-                        ctx->fd, jt, (uint64_t*)bb.nF.p, (uint64_t*)bb.nB.p, (uint32_t*)bb.kh.p, (uint64_t)0);
-        else if (ctx->delta_ready && bb.planes_gen == ctx->hint_gen) {
-            // the planes speak of the newest preview and the table is a later state of it: only the keys created since are looked for and merged in
-            // (and the candidate plane of the sparse link pass, made against the same preview, gains the positions that hit the filter: k_walk_link_sparse)
-            cand_ok = !ctx->no_sparse_link && bb.cand.p && bb.cand_gen == ctx->hint_gen;      // (FGPU_NO_SPARSE_LINK: every window in full, as until round 6)
-            if (ctx->delta_keys || ctx->refresh_delta)      // (nothing new in the table and nothing walked yet: the planes stand)
-                FGPU_LAUNCH("walk_lookup", k_refresh_lookup, fgpu_grid(bb.n_words * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p, bb.n_words,
-                            ctx->fd, jt, (const uint32_t*)ctx->delta_filter.p, ctx->delta_filter_bits - 1, (uint64_t*)bb.nF.p, (uint64_t*)bb.nB.p,
-                            (const uint32_t*)bb.kh.p, 1, cand_ok ? (uint64_t*)bb.cand.p : (uint64_t*)nullptr);
-            ctx->refresh_delta++;
-            if (ctx->dbg_delta_check) {      // tests (FGPU_DEBUG_DELTA_CHECK=1): the merged planes against planes made again in full, word by word
-                uint64_t *cF = nullptr, *cB = nullptr;
-                unsigned long long* out = nullptr;
-                FGPU_HIP(hipMalloc(&cF, bb.n_words * 8));
-                FGPU_HIP(hipMalloc(&cB, bb.n_words * 8));
-                FGPU_HIP(hipMalloc(&out, 32));
-                FGPU_HIP(hipMemsetAsync(out, 0, 32, walk_stream));
-                hipLaunchKernelGGL(k_refresh_lookup, dim3(fgpu_grid(bb.n_words * 64, 256)), dim3(256), 0, walk_stream, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,
-                                   bb.n_words, ctx->fd, jt, (const uint32_t*)jt.filter, jt.filter_mask, cF, cB, (const uint32_t*)bb.kh.p, 0, (uint64_t*)nullptr);
-                hipLaunchKernelGGL(k_dbg_diff, dim3(64), dim3(256), 0, walk_stream, (const uint64_t*)cF, (const uint64_t*)bb.nF.p, bb.n_words, out, 0);
-                hipLaunchKernelGGL(k_dbg_diff, dim3(64), dim3(256), 0, walk_stream, (const uint64_t*)cB, (const uint64_t*)bb.nB.p, bb.n_words, out, 1);
-                unsigned long long h[4] = {0, 0, 0, 0};
-                FGPU_HIP(hipMemcpyAsync(h, out, 32, hipMemcpyDeviceToHost, walk_stream));
-                FGPU_HIP(hipStreamSynchronize(walk_stream));
-                ctx->refresh_mismatch += h[0] + h[1];
-                if (h[0] + h[1]) fprintf(stderr, "[fgpu] merged in-map planes differ from planes made again: batch %llu, %llu + %llu words\n", (unsigned long long)bb.seq, h[0], h[1]);
-                (void)hipFree(cF); (void)hipFree(cB); (void)hipFree(out);
-            }
-        } else {
-            FGPU_LAUNCH("walk_lookup", k_refresh_lookup, fgpu_grid(bb.n_words * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p, bb.n_words,
-                        ctx->fd, jt, (const uint32_t*)jt.filter, jt.filter_mask, (uint64_t*)bb.nF.p, (uint64_t*)bb.nB.p, (const uint32_t*)bb.kh.p, 0, (uint64_t*)nullptr);
-            ctx->refresh_full++;
-        }
-    }
+    if (ctx->dbg_stall_us) FGPU_LAUNCH("debug_stall", k_debug_stall, 1, 1, (unsigned long long)ctx->dbg_stall_us * 100ULL);
+    if (ctx->refresh_snapshot && (rc = walk_refresh_prepared(ctx, bb, wb.jt, walk_stream, &wb.cand_ok))) return rc;
     if (ctx->record_stops) {
-        const uint64_t wb = (bb.n_words + FGPU_PADW) * 8;
-        FGPU_HIP(hipMemsetAsync(bb.sF.p, 0, wb, walk_stream));
-        FGPU_HIP(hipMemsetAsync(bb.sB.p, 0, wb, walk_stream));
+        FGPU_HIP(hipMemsetAsync(bb.sF.p, 0, wbytes, walk_stream));
+        FGPU_HIP(hipMemsetAsync(bb.sB.p, 0, wbytes, walk_stream));
     }
-    FGPU_HIP(hipMemsetAsync(bb.cr.p, 0, (bb.n_words + FGPU_PADW) * 8, walk_stream));
-    {   // host-side estimate of the delta (see the per-window decision below): records counted when this batch's planes were made, and
+    FGPU_HIP(hipMemsetAsync(bb.cr.p, 0, wbytes, walk_stream));
+    {   // host-side estimate of the delta (see walk_register): records counted when this batch's planes were made, and
         // how many the batches in the ring added
         const uint64_t now = ctx->counters_host->n_junctions;
         ctx->delta_hist[ctx->delta_next % FGPU_DELTA_RING] = now;
@@ -3245,14 +3239,8 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
         ctx->delta_ring_keys = now > back ? now - back : 0;
         ctx->delta_batch_base = now;
     }
-    // the list this batch's created keys go to: the oldest of the ring (its readers -- the windows of the batches in between -- are
-    // behind us on this stream)
-    DeltaList& mine_list = ctx->delta_ring[ctx->delta_next % FGPU_DELTA_RING];
-    {
-        int rc;
-        if ((rc = fgpu_ensure_b(ctx, &mine_list.list, (bb.n_words + FGPU_PADW) * 64 * 4)) || (rc = fgpu_ensure(ctx, &mine_list.count, 64))) return rc;
-        FGPU_HIP(hipMemsetAsync(mine_list.count.p, 0, 8, walk_stream));
-    }
+    if ((rc = fgpu_ensure_b(ctx, &wb.created->list, (bb.n_words + FGPU_PADW) * 64 * 4)) || (rc = fgpu_ensure(ctx, &wb.created->count, 64))) return rc;
+    FGPU_HIP(hipMemsetAsync(wb.created->count.p, 0, 8, walk_stream));
     // thousands of tiny launches: by default one event pair around the whole stage
     const int stage_tok = fgpu_prof_begin(ctx, "walk_stage");
     ctx->prof_suppress = !ctx->prof_walk_detail;
@@ -3262,359 +3250,27 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
     // slower on the whole batch (hop of config 4 on 8 shards, 23 windows -> 14: k_walk_dyn 22.3 -> 22.6 ms, the link passes 12.7 -> 8.7, the hop
     // 69.1 -> 64.9 ms: profiles/r06_hop_sparse_link.txt).  The controller's own span is left as it is (it goes on voting from the counters; once it
     // asks for less than half a batch this rule no longer applies).  FGPU_NO_WHOLE_BATCH=1: off (measurement aid).
-    static const bool no_whole = getenv("FGPU_NO_WHOLE_BATCH") != nullptr;
-    const bool whole_batch = cand_ok && !no_whole && !ctx->prm.walk_window_span && ctx->calib_left <= 0 && span * 2 >= T && span < T && T <= ctx->max_span &&
+    const bool whole_batch = wb.cand_ok && !kn.no_whole_batch && !ctx->prm.walk_window_span && ctx->calib_left <= 0 && span * 2 >= T && span < T && T <= ctx->max_span &&
                              bb.n_pieces <= ctx->wmax;
     for (uint64_t lo = 0, step = 0; lo < T; lo += step) {
         step = whole_batch ? T : span_now;
-        const uint64_t hi = std::min<uint64_t>(T, lo + step);
-        const uint64_t pos_end = std::min<uint64_t>(T, hi + ext);
-        const int parity = (int)(ctx->scan_windows & 1);
-        // grids sized for THIS window (a window of w positions holds at most w/(k+1)+2 piece starts): small windows -- high
-        // coverage data -- must not pay for the launch of the thousands of empty blocks the largest window would need
-        const uint64_t max_pieces = std::min<uint64_t>((hi - lo) / (uint64_t)(ctx->fd.k + 1) + 2, ctx->wmax);
-        const unsigned walk_grid_w = fgpu_blocks(max_pieces, 64);
-        static const unsigned cluster_cap = getenv("FGPU_CLUSTER_GRID") ? (unsigned)std::max(1, atoi(getenv("FGPU_CLUSTER_GRID"))) : 256u;
-        const unsigned cluster_grid = std::min(cluster_cap, fgpu_blocks(max_pieces, 256));
-        const unsigned piece_blocks_ko = fgpu_blocks(max_pieces, 256);
-#ifdef FGPU_KO_ONE_XCD
-        const unsigned ko_grid = 4096;
-#else
-        const unsigned ko_grid = 512;
-#endif
-        uint32_t* const uf_parent = ctx->uf_parent + parity * (uint64_t)ctx->wmax;     // this window's set of the union-find / list arrays
-        uint32_t* const cl_count = ctx->cl_count + parity * (uint64_t)ctx->wmax;
-        uint32_t* const cl_offset = ctx->cl_offset + parity * (uint64_t)ctx->wmax;
-        uint32_t* const cl_fail = ctx->cl_fail + parity * (uint64_t)ctx->wmax;
-        FGPU_HIP(hipStreamWaitEvent(walk_stream, ctx->ev_uf_reset[parity], 0));        // reset since the window before last used it
-        // the window table of this window: entries carry the window's epoch, everything older counts as empty (wiped every 255 windows)
-        if (++ctx->wt_epoch > 255) {
-            FGPU_HIP(hipMemsetAsync(ctx->wkeys, 0, ctx->wcap * 8, walk_stream));
-            ctx->wt_epoch = 1;
-        }
-        const WTable wt = make_wt(ctx, ctx->wt_epoch, parity);   // its presence filter was zeroed by the reset kernel of the window before last
-        {
-            DeltaSrc ds;
-            memset(&ds, 0, sizeof(ds));
-            // The delta of this window: keys created since the batch's snapshot planes were made -- by the batches walked since (their lists)
-            // and by this batch's earlier windows (its own list so far).  Registering it costs one atomic pair per key and WINDOW; where the
-            // windows are small and the delta is not (very high coverage: thousands of windows per batch, a million keys created by the
-            // first of them) it is cheaper to make the snapshot planes of the window's own positions again -- what the look-up kernel of
-            // round 1 did for every window -- and register no delta at all.  The host's estimate of the delta is an upper bound of what it
-            // has seen counted; being wrong only picks the dearer of two exact ways.
-            // (earlier batches: records counted between their walks' issue times; this batch: at most ~3 creations per piece walked so far)
-            const uint64_t delta_est = ctx->delta_ring_keys + (uint64_t)(3.0 * (double)bb.n_pieces * (double)lo / (double)T);
-            // (FGPU_REFRESH_DIV: the 4 below.  Swept in round 5 on configs 2, 5 and 4 at full size: 1, 2, 4 within noise of each other, 16 and more --
-            // planes made again more readily -- slower everywhere: config 4's walk stage 1 202 -> 1 258 / 1 343 ms, config 2's step 119.7 -> 122.1 / 125.7 ms;
-            // profiles/r05_refresh_div_sweep.txt)
-            static const uint64_t refresh_div = getenv("FGPU_REFRESH_DIV") ? std::max(1, atoi(getenv("FGPU_REFRESH_DIV"))) : 4;
-            const bool refresh_window = !ctx->refresh_snapshot && delta_est > (pos_end - lo) / refresh_div;
-            if (refresh_window) {
-                const uint64_t w_first = lo >> 6, w_last = std::min<uint64_t>(bb.n_words, (pos_end + 63) / 64);
-                FGPU_LAUNCH("walk_lookup", k_need_lookup, fgpu_grid((w_last - w_first) * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p, w_last,
-                            ctx->fd, jt, (uint64_t*)bb.nF.p, (uint64_t*)bb.nB.p, (uint32_t*)bb.kh.p, w_first);
-            } else {
-                if (!ctx->refresh_snapshot)      // (a batch whose planes were just made again needs no earlier batch's keys)
-                    for (int r = 1; r < FGPU_DELTA_RING && (uint64_t)r <= ctx->delta_next; r++) {
-                        const DeltaList& dl = ctx->delta_ring[(ctx->delta_next - r) % FGPU_DELTA_RING];
-                        ds.list[r - 1] = (const uint32_t*)dl.list.p;
-                        ds.count[r - 1] = (const unsigned long long*)dl.count.p;
-                    }
-                if (lo) {
-                    ds.list[FGPU_DELTA_RING - 1] = (const uint32_t*)mine_list.list.p;
-                    ds.count[FGPU_DELTA_RING - 1] = (const unsigned long long*)mine_list.count.p;
-                }
-            }
-            const unsigned word_blocks = fgpu_blocks((pos_end - (lo & ~63ULL) + 63) / 64, 256);
-            const unsigned piece_blocks = fgpu_blocks(max_pieces, 256);
-            // the delta's share of the grid by its size: 64 blocks took a batch's worth of created keys (millions per window while a large map is
-            // being built: config 4's first shards) 500 dependent atomics per thread, the kernel's tail.  One block per 1024 keys: walk stage of
-            // config 4 1 216 -> 1 150-1 177 ms, config 5 298 -> 278-282 ms, the steps' wall time within noise (the pure stage beside it bounds pass 2);
-            // config 2 unchanged (its delta never exceeds 64 blocks' worth).  profiles/r05_walk_grid_sweep.txt
-            static const unsigned delta_per_block = getenv("FGPU_DELTA_PER_BLOCK") ? (unsigned)std::max(1, atoi(getenv("FGPU_DELTA_PER_BLOCK"))) : 1024u;
-            const unsigned delta_blocks = refresh_window ? 64u : (unsigned)std::min<uint64_t>(4096, std::max<uint64_t>(64, delta_est / delta_per_block));
-            FGPU_LAUNCH("walk_lookup", k_walk_register, word_blocks + piece_blocks + delta_blocks, 256, pl, ctx->fd, wt, uf_parent, lo, hi, pos_end, ctx->counters,
-                        word_blocks, piece_blocks, ds);
-        }
-        uint32_t* const roots_state = ctx->cl_roots;               // [0] leaders listed, [1] handed out; the list follows (16 words in)
-        uint32_t* const root_list = ctx->cl_roots + 16;
-        if (cand_ok && lo == 0) {      // (lo > 0: the window registers what this batch's earlier windows created -- positions the plane does not know)
-            const uint64_t link_words = ((pos_end + 63) >> 6) - (lo >> 6);
-            FGPU_LAUNCH("walk_link", k_walk_link_sparse, std::min(fgpu_blocks(link_words, 256), 4096u), 256, pl, ctx->fd, wt, uf_parent, lo, hi, pos_end, roots_state,
-                        (const uint64_t*)bb.cand.p, (uint64_t*)bb.lk.p);
-            ctx->sparse_links++;
-            if (ctx->dbg_delta_check) {      // tests: the full pass behind it (its unions are the same ones again), the two lk planes word by word
-                uint64_t* copy = nullptr;
-                unsigned long long* out = nullptr;
-                FGPU_HIP(hipMalloc(&copy, link_words * 8));
-                FGPU_HIP(hipMalloc(&out, 32));
-                FGPU_HIP(hipMemsetAsync(out, 0, 32, walk_stream));
-                FGPU_HIP(hipMemcpyAsync(copy, (const uint64_t*)bb.lk.p + (lo >> 6), link_words * 8, hipMemcpyDeviceToDevice, walk_stream));
-                hipLaunchKernelGGL(k_walk_link, dim3(std::min(fgpu_blocks(pos_end - (lo & ~63ULL), 1024), 4096u)), dim3(256), 0, walk_stream, pl, ctx->fd, wt, uf_parent, lo, hi, pos_end,
-                                   (uint32_t*)nullptr);
-                hipLaunchKernelGGL(k_dbg_diff, dim3(64), dim3(256), 0, walk_stream, (const uint64_t*)copy, (const uint64_t*)bb.lk.p + (lo >> 6), link_words, out, 0);
-                unsigned long long h[4] = {0, 0, 0, 0};
-                FGPU_HIP(hipMemcpyAsync(h, out, 32, hipMemcpyDeviceToHost, walk_stream));
-                FGPU_HIP(hipStreamSynchronize(walk_stream));
-                ctx->refresh_mismatch += h[0];
-                if (h[0]) fprintf(stderr, "[fgpu] sparse link pass: %llu lk words differ from the full pass's, batch %llu window at %llu\n", h[0], (unsigned long long)bb.seq, (unsigned long long)lo);
-                (void)hipFree(copy); (void)hipFree(out);
-            }
-        } else {
-            FGPU_LAUNCH("walk_link", k_walk_link, std::min(fgpu_blocks(pos_end - (lo & ~63ULL), 1024), 4096u), 256, pl, ctx->fd, wt, uf_parent, lo, hi, pos_end, roots_state);
-            if (ctx->refresh_snapshot) ctx->full_links++;
-        }
-        // The key-ordered walk costs four small launches per window whether or not the window holds a large cluster, so it is switched on by
-        // what the scan has shown so far: the largest cluster among the windows whose counters the host has seen (every batch's pure stage
-        // brings them along).  Data without such clusters never pays; data with them walks its first batch by cluster.  Either way the
-        // results are the same.  FGPU_WALK_KO_ALWAYS=1: from the first window (tests).
-        const uint32_t ko_heavy = (dbg_walk || !ctx->walk_ko || !(ctx->walk_ko_always || ctx->counters_host->max_cluster >= ctx->walk_ko)) ? 0u : ctx->walk_ko;
-        // ... and, for callers that expect repeats, the clusters whose pieces hold many lk positions between them (ko_cluster): the weights
-        // are summed by k_walk_cluster into cl_fail, which the out-of-order walk (k_walk_par, the other way of taking clusters out of k_walk)
-        // does not use then
-        // The rule by weight has two bars: lk positions of a cluster in all (ko_total), and -- for clusters of "repeat pieces", pieces that hold
-        // many of them -- positions per piece and a lower bar in all.  Ordinary pieces hold 2-5, some 8 and more; pieces inside a repeat at high
-        // coverage 40 and more.  Once a scan HAS shown repeats (2 % of the pieces walked so far went to the large-cluster walks) the second bar
-        // drops from (12 per piece, 48 in all) to (8, 16): measured on config 3's shape through the CLI pass 2 goes from 245-250 ms to 190 ms
-        // (the windows grow from 62 to 22: what is left to k_walk no longer queues), while config 2 with the CLI's settings would pay 10 ms per
-        // step for the lower bar (walk stage 52.6 -> 62.6 ms; scripts/ovw_thresholds.sh, gpurun_out/r04_ovw_thresholds2.txt).
-        static const int ko_avg_env = getenv("FGPU_WALK_KO_AVG") ? std::min(255, std::max(0, atoi(getenv("FGPU_WALK_KO_AVG")))) : -1;
-        static const int ko_avg_min_env = getenv("FGPU_WALK_KO_AVG_MIN") ? std::min(255, std::max(1, atoi(getenv("FGPU_WALK_KO_AVG_MIN")))) : -1;
-        const bool repeats_seen = ctx->counters_host->walk_parallel * 50 > ctx->counters_host->walked_pieces ||
-                                  (ctx->walk_ko_always && ctx->counters_host->walked_pieces < (1ULL << 17) && ctx->delta_next >= 2 && ctx->repeats_seen_before);   // (same lag: keep what the scan had found)
-        if (repeats_seen) ctx->repeats_seen_before = true;
-        const uint32_t ko_total = std::min<uint32_t>(ctx->walk_ko_weight, 0xFFFFu);
-        const uint32_t ko_avg = ko_avg_env >= 0 ? (uint32_t)ko_avg_env : repeats_seen ? 8u : 12u;
-        const uint32_t ko_total_rep = ko_avg_min_env > 0 ? (uint32_t)ko_avg_min_env : repeats_seen ? 16u : std::min<uint32_t>(255u, 3 * ko_total / 8);
-        const uint32_t ko_heavy_w = (ko_heavy && ko_total) ? (ko_total | (ko_avg << 16) | (ko_total_rep << 24)) : 0u;
-        // cl_count = followers per root, cl_offset = list heads, cl_fill = flat roots, cl_members = [next links | pool]
-        FGPU_LAUNCH("walk_cluster", k_walk_cluster, cluster_grid, 256, (const uint32_t*)uf_parent, cl_count, cl_offset, ctx->cl_fill,
-                    ctx->cl_members, pl, lo, hi, (WinDesc*)ctx->wdesc, ctx->counters, cl_fail, ko_heavy_w, root_list, roots_state);
-        static const uint32_t ko_ticket = getenv("FGPU_KO_TICKET") ? (uint32_t)std::max(64, atoi(getenv("FGPU_KO_TICKET")) / 64 * 64) : 64u;
-        const uint32_t heavy = (dbg_walk || ko_heavy) ? 0u : ctx->walk_heavy;   // (one way of taking large clusters out of k_walk at a time)
+        WalkWindow w;
         KoTables kt;
-        kt.hk_key = ctx->ko_hk;
-        kt.hk_head = ctx->ko_hk + ctx->ko_hk_cap;
-        kt.hk_turn = ctx->ko_hk + 2 * (size_t)ctx->ko_hk_cap;
-        kt.hk_mask = ctx->ko_hk_cap - 1;
-        kt.occ_id = (uint64_t*)ctx->ko_occ;
-        kt.occ_entry = (uint32_t*)(kt.occ_id + ctx->ko_occ_cap);
-        kt.occ_rank = kt.occ_entry + ctx->ko_occ_cap;
-        kt.occ_next = kt.occ_rank + ctx->ko_occ_cap;
-        kt.occ_cap = ctx->ko_occ_cap;
-        kt.trace = nullptr;
-#ifdef FGPU_KO_TRACE
-        if (!ctx->ko_trace.p) {
-            if (int trc = fgpu_ensure(ctx, &ctx->ko_trace, ((1ULL << 23) + 4096 * 1024) * 8)) return trc;
-            FGPU_HIP(hipMemsetAsync(ctx->ko_trace.p, 0, 32, ctx->stream));
-        }
-        kt.trace = (unsigned long long*)ctx->ko_trace.p;
-#endif
-        kt.state = ctx->ko_piece;                 // 16 words in front of the per-piece arrays
-        kt.piece_base = ctx->ko_piece + 16;
-        kt.bad = kt.piece_base + ctx->wmax;
-        // The optimistic walk (k_ovw_round) takes the large clusters first; the key-ordered walk runs behind it for what it leaves.  Its
-        // rounds are launches whether or not the window holds such a cluster, so -- like the key-ordered walk itself -- it is switched on by
-        // what the scan has shown: pieces of large clusters among the pieces walked so far (callers that expect repeats: from the first window).
-        const int ovw_rounds = !ko_heavy ? 0 : std::min(ctx->ovw_rounds, OVW_MAX_ROUNDS);
-        // the pieces it walks do not queue behind one another, so they do not count as followers for the window-size controller (the key-ordered
-        // walk's did: 68 windows instead of 22 on config 3's shape); FGPU_OVW_FOLLOWERS=1 counts them (measurement aid)
-        static const int ovw_followers = getenv("FGPU_OVW_FOLLOWERS") ? atoi(getenv("FGPU_OVW_FOLLOWERS")) : 0;
-        // (a caller that expects repeats gets it for the scan's first two batches; after that the scan's own counters decide: on ordinary data the
-        // few large clusters cost less with the key-ordered walk alone than with a dozen launches more per window -- config 2 with the CLI's
-        // settings: walk stage 52.6 ms with the rounds always issued, scripts/ovw_config2.sh)
-        // (the counters are the host's snapshot of the previous pure stage's end: when the walk lags two batches behind at that moment --
-        // it happens, by the timing of the machine -- they do not show a single large cluster yet.  A caller that expects repeats therefore
-        // keeps the rounds until the counters have SEEN enough pieces to say otherwise: round 4 met runs of config 3's shape in which the
-        // third batch went without them and pass 2 took 310-360 instead of 160 ms)
-        const bool ovw_seen_enough = ctx->counters_host->walked_pieces >= (1ULL << 17);
-        static const bool dbg_ovw_gap = getenv("FGPU_DEBUG_OVW_GAP") != nullptr;   // measurement aid: the rounds withheld from a scan's third and fourth batch
-        const bool ovw_on = ovw_rounds > 0 && !(dbg_ovw_gap && (ctx->delta_next == 2 || ctx->delta_next == 3)) &&
-                            ((ctx->walk_ko_always && (ctx->delta_next < 2 || !ovw_seen_enough)) ||
-                             ctx->counters_host->walk_parallel * 256 > ctx->counters_host->walked_pieces);
         OvwTables ot;
-        memset(&ot, 0, sizeof(ot));
-        {   // the event tables follow what the scan has shown (weak 9 of VERDICT r4): once a round of some window has filled a quarter of a table,
-            // the next windows get tables eight times that round's entries -- before a window overflows them and is left to the key-ordered walk
-            const uint64_t fill = ctx->counters_host->ovw_fill;
-            int want = ctx->ovw_ev_log2;
-            while (want < 27 && fill * 4 > (1ULL << want)) want++;
-            if (want != ctx->ovw_ev_log2) {
-                while (want < 27 && fill * 8 > (1ULL << want)) want++;
-                if (ctx->ovw_ev.p) {     // rounds of the window before may still be reading the tables that are about to be replaced
-                    FGPU_HIP(fgpu_sync_stream(ctx, walk_stream));
-                    if (ctx->ostream) FGPU_HIP(fgpu_sync_stream(ctx, ctx->ostream));
-                }
-                ctx->ovw_ev_log2 = want;
-            }
-        }
-        const int kEvLog2 = ctx->ovw_ev_log2, kFiltLog2 = kEvLog2 + 1;
-        constexpr int kMarkLog2 = 22;
-        const uint32_t filt_words = 1u << (kFiltLog2 - 5);
-        const uint32_t list_cap = (uint32_t)std::min<uint64_t>(ctx->wmax, 1u << 20);
-        uint32_t* ovw_filt = nullptr;
-        if (ovw_on) {
-            int rc;
-            const bool fresh = !ctx->ovw_ev.p || ctx->ovw_ev_log2_alloc != kEvLog2;     // (grown since the last window: other table boundaries, wipe)
-            ctx->ovw_ev_log2_alloc = kEvLog2;
-            if ((rc = fgpu_ensure(ctx, &ctx->ovw_ev, 4ULL * 8 * (1ULL << kEvLog2))) || (rc = fgpu_ensure(ctx, &ctx->ovw_filt, 3ULL * 4 * filt_words)) ||
-                (rc = fgpu_ensure(ctx, &ctx->ovw_log, 2ULL * ctx->ko_occ_cap * sizeof(uint4))) || (rc = fgpu_ensure(ctx, &ctx->ovw_res, 32ULL * list_cap)) ||
-                (rc = fgpu_ensure(ctx, &ctx->ovw_marks, 3ULL * 4 * (1ULL << kMarkLog2))) ||
-                (rc = fgpu_ensure(ctx, &ctx->ovw_list, 4ULL * list_cap)) || (rc = fgpu_ensure(ctx, &ctx->ovw_state, 4ULL * (8 + OVW_MAX_ROUNDS) + 64)) ||
-                (rc = fgpu_ensure(ctx, &ctx->ovw_longp, 4ULL * ctx->wmax)))
-                return rc;
-            if (fresh || ctx->ovw_epoch + (uint32_t)ovw_rounds > 255) {   // event entries carry their round's epoch: a wiped table holds none
-                FGPU_HIP(hipMemsetAsync(ctx->ovw_ev.p, 0, 4ULL * 8 * (1ULL << kEvLog2), walk_stream));
-                ctx->ovw_epoch = 0;
-            }
-            ovw_filt = (uint32_t*)ctx->ovw_filt.p;
-            ot.list = (uint32_t*)ctx->ovw_list.p;
-            ot.list_cap = list_cap;
-            ot.state = (uint32_t*)ctx->ovw_state.p;
-            ot.longp = (uint32_t*)ctx->ovw_longp.p;
-            ot.filt_words = filt_words;
-        }
-        if (ko_heavy) {
-            FGPU_LAUNCH("walk_ko_prepare", k_ko_reset, 256, 256, kt, (uint32_t)ctx->wmax, (uint32_t)parity);
-            if (ovw_on) FGPU_LAUNCH("walk_ko_prepare", k_ovw_reset, 64, 256, ot.state, ovw_filt, 3 * filt_words, ot.longp, (uint32_t)max_pieces,
-                                    (uint32_t*)ctx->ovw_marks.p, 3u << kMarkLog2);
-            FGPU_LAUNCH("walk_ko_prepare", k_ko_prepare, piece_blocks_ko, 256, pl, (const uint32_t*)ctx->cl_fill, (const uint32_t*)cl_count,
-                        (const WinDesc*)ctx->wdesc, kt, ko_heavy, (uint32_t)parity, (const uint32_t*)cl_fail, ko_heavy_w, ot);
-        }
-        // The rounds run on a stream of their own BESIDE k_walk: the two walk disjoint clusters (a key belongs to the one cluster every piece that
-        // holds it is in), so neither reads a record the other writes; slot claims, counters, planes and filters change by atomics on both sides.
-        static const bool ovw_beside = !(getenv("FGPU_OVW_SERIAL") && getenv("FGPU_OVW_SERIAL")[0] == '1');   // measurement aid: behind k_walk, one stream
-        hipStream_t ovw_stream = (ovw_beside && !no_overlap && ctx->ostream) ? ctx->ostream : walk_stream;
-        if (ovw_on && ovw_stream != walk_stream) {
-            FGPU_HIP(hipEventRecord(ctx->ev_listed, walk_stream));
-            FGPU_HIP(hipStreamWaitEvent(ovw_stream, ctx->ev_listed, 0));
-            ctx->launch_stream = ovw_stream;
-        }
-        if (ovw_on) {
-            unsigned long long* const evb = (unsigned long long*)ctx->ovw_ev.p;
-            uint32_t* const marks = (uint32_t*)ctx->ovw_marks.p;
-            ot.log = (uint4*)ctx->ovw_log.p;
-            ot.res = (uint32_t*)ctx->ovw_res.p;
-            ot.mark_mask = (1u << kMarkLog2) - 1;
-            const unsigned ovw_grid = (unsigned)std::min<uint64_t>(fgpu_blocks(std::min<uint64_t>(max_pieces, list_cap), 64), 2048);
-            auto table = [&](int r, uint64_t epoch) {
-                OvwEv ev;
-                ev.key = evb + (uint64_t)(r & 1) * 2 * (1ULL << kEvLog2);
-                ev.val = ev.key + (1ULL << kEvLog2);
-                ev.bits = ovw_filt + (uint64_t)(r % 3) * filt_words;
-                ev.mask = (1ULL << kEvLog2) - 1;
-                ev.epoch = epoch << 56;
-                ev.fshift = 32 - kFiltLog2;
-                return ev;
-            };
-            const uint64_t epoch_first = (uint64_t)ctx->ovw_epoch + 1;
-            for (int r = 0; r < ovw_rounds; r++) {
-                ctx->ovw_epoch++;
-                ot.cur = table(r, ctx->ovw_epoch);
-                ot.prev = table(r + 1, ctx->ovw_epoch - 1);           // (the other table, the filter of round r - 1: (r + 2) % 3 == (r - 1) % 3)
-                ot.prev.bits = ovw_filt + (uint64_t)((r + 2) % 3) * filt_words;
-                ot.filt_next = ovw_filt + (uint64_t)((r + 1) % 3) * filt_words;
-                ot.mark_cur = marks + ((uint64_t)(r % 3) << kMarkLog2);
-                ot.mark_prev = marks + ((uint64_t)((r + 2) % 3) << kMarkLog2);
-                ot.mark_next = marks + ((uint64_t)((r + 1) % 3) << kMarkLog2);
-                FGPU_LAUNCH("walk_ovw", k_ovw_round, ovw_grid, 64, pl, ctx->fd, jt, (const uint32_t*)ctx->cl_fill, (const WinDesc*)ctx->wdesc, kt, ot, (uint32_t)r,
-                            (const uint32_t*)ctx->bloo2, ctx->counters);
-            }
-            FGPU_LAUNCH("walk_ovw", k_ovw_commit, ovw_grid, 64, pl, ctx->fd, jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)cl_count, (const WinDesc*)ctx->wdesc,
-                        seq_base, kt, ot, ovw_rounds, ctx->counters, ovw_followers, (const unsigned long long*)evb, (uint64_t)1 << kEvLog2, epoch_first);
-        }
-        if (ovw_on && ovw_stream != walk_stream) {
-            FGPU_HIP(hipEventRecord(ctx->ev_settled, ovw_stream));
-            ctx->launch_stream = walk_stream;
-        }
-        if (heavy)
-            FGPU_LAUNCH("walk_probe", k_walk_par<WALK_PROBE>, walk_grid_w, 64, pl, ctx->fd, jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)cl_count, cl_fail,
-                        (const WinDesc*)ctx->wdesc, (const uint32_t*)ctx->bloo2, ctx->counters, heavy);
-        static const bool walk_static = getenv("FGPU_WALK_STATIC") && getenv("FGPU_WALK_STATIC")[0] == '1';   // measurement aid: lane i walks the cluster led by piece i
-        static const unsigned walk_dyn_grid = getenv("FGPU_WALK_DYN_GRID") ? (unsigned)std::max(1, atoi(getenv("FGPU_WALK_DYN_GRID"))) : 1024u;   // (k_walk alone on config 2 / config 4's per-GPU shape, ms per step: static 19.3 / 22.9; 1024 waves 19.6 / 16.6; 2048 20.5 / 17.7; 4096 23.3 / 18.8)
-        if (walk_static)
-            FGPU_LAUNCH("walk", k_walk, walk_grid_w, 64, pl, ctx->fd, jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)cl_count,
-                        (const uint32_t*)cl_offset, (const uint32_t*)ctx->cl_members, ctx->cl_members + ctx->wmax, (const WinDesc*)ctx->wdesc,
-                        seq_base, (const uint32_t*)ctx->bloo2, ctx->counters, dbg_walk, (const uint32_t*)cl_fail, heavy, (const uint32_t*)kt.bad,
-                        (const uint32_t*)kt.state, ko_heavy, (uint32_t)ctx->scan_windows, ko_heavy_w);
-        else
-            FGPU_LAUNCH("walk", k_walk_dyn, std::min(walk_grid_w, walk_dyn_grid), 64, pl, ctx->fd, jt, (const uint32_t*)root_list, roots_state, (const uint32_t*)cl_count,
-                        (const uint32_t*)cl_offset, (const uint32_t*)ctx->cl_members, ctx->cl_members + ctx->wmax, (const WinDesc*)ctx->wdesc,
-                        seq_base, (const uint32_t*)ctx->bloo2, ctx->counters, dbg_walk, (const uint32_t*)cl_fail, heavy, (const uint32_t*)kt.bad,
-                        (const uint32_t*)kt.state, ko_heavy, (uint32_t)ctx->scan_windows, ko_heavy_w);
-        if (ovw_on && ovw_stream != walk_stream) FGPU_HIP(hipStreamWaitEvent(walk_stream, ctx->ev_settled, 0));   // the settled logs are in the map
-        if (ko_heavy)      // (ranks of the occurrences per k-mer: only the key-ordered walk needs them, and only for what the optimistic walk left)
-            FGPU_LAUNCH("walk_ko_prepare", k_ko_rank, 256, 256, kt, (const uint32_t*)ot.state, ovw_rounds);
-        if (ko_heavy)
-            FGPU_LAUNCH("walk_ko", k_walk_ko, ko_grid, 64, pl, ctx->fd, jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)cl_count, (const WinDesc*)ctx->wdesc,
-                        seq_base, (const uint32_t*)ctx->bloo2, ctx->counters, kt, ko_heavy, ko_ticket, (const uint32_t*)cl_fail, ko_heavy_w,
-                        (const uint32_t*)ot.state, (const uint32_t*)ot.longp, ovw_rounds);
-        if (heavy)
-            FGPU_LAUNCH("walk_commit", k_walk_par<WALK_COMMIT>, walk_grid_w, 64, pl, ctx->fd, jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)cl_count, cl_fail,
-                        (const WinDesc*)ctx->wdesc, (const uint32_t*)ctx->bloo2, ctx->counters, heavy);
-        {   // the keys this window created join the batch's list (and leave the plane): the next window's delta
-            const uint64_t w_first = lo >> 6, w_last = std::min<uint64_t>(bb.n_words, (pos_end + 63) / 64);
-            FGPU_LAUNCH("walk_delta", k_delta_collect, (unsigned)std::min<uint64_t>(fgpu_blocks(w_last - w_first, 256), 256), 256, (unsigned long long*)bb.cr.p,
-                        (const uint32_t*)bb.kh.p, w_first, w_last, (uint32_t*)mine_list.list.p, (unsigned long long*)mine_list.count.p, pl,
-                        (const WinDesc*)ctx->wdesc, ctx->counters, (uint32_t)ctx->scan_windows);
-        }
-        // this window's set is reset on the side stream while the next window (the other set) is looked up and linked
-        FGPU_HIP(hipEventRecord(ctx->ev_walked, walk_stream));
-        FGPU_HIP(hipStreamWaitEvent(ctx->cstream, ctx->ev_walked, 0));
-        ctx->launch_stream = ctx->cstream;
-        FGPU_LAUNCH("walk_clean", k_walk_reset_uf, std::min(256u, fgpu_blocks(max_pieces, 256)), 256, uf_parent, cl_count, cl_offset, cl_fail, (uint32_t)max_pieces, (uint4*)wt.bits, (uint32_t)((1u << ctx->wbits_log2) / 128));
-        ctx->launch_stream = walk_stream;
-        FGPU_HIP(hipEventRecord(ctx->ev_uf_reset[parity], ctx->cstream));
-        if (serial_clean) FGPU_HIP(hipStreamWaitEvent(walk_stream, ctx->ev_uf_reset[parity], 0));
+        if ((rc = walk_window_begin(ctx, wb, lo, std::min<uint64_t>(T, lo + step), &w))) return rc;
+        if ((rc = walk_register(ctx, kn, wb, w)) || (rc = walk_link(ctx, wb, w))) return rc;
+        const LargeClusterRule rule = large_cluster_rule(ctx, kn);
+        // clusters -> member lists: cl_count = followers per root, cl_offset = list heads, cl_fill = flat roots, cl_members = [next links | pool]
+        FGPU_LAUNCH("walk_cluster", k_walk_cluster, std::min(kn.cluster_grid, fgpu_blocks(w.max_pieces, 256)), 256, (const uint32_t*)w.uf_parent, w.cl_count, w.cl_offset,
+                    ctx->cl_fill, ctx->cl_members, pl, lo, w.hi, (WinDesc*)ctx->wdesc, ctx->counters, w.cl_fail, rule.ko_heavy_w, w.root_list, w.roots_state);
+        if ((rc = walk_large_tables(ctx, wb, rule, kt, ot)) || (rc = walk_large_first(ctx, kn, wb, w, rule, kt, ot)) || (rc = walk_clusters(ctx, kn, wb, w, rule, kt, ot)) ||
+            (rc = walk_collect_and_reset(ctx, kn, wb, w)))
+            return rc;
         ctx->scan_windows++;
-        // Calibration: at the start of a scan (and again whenever a batch came out with most of its pieces queueing) the host
-        // waits for the window it has just issued and looks at the share of pieces that had to queue behind an earlier piece of
-        // their cluster.  High coverage makes clusters percolate -- 250x reads of a small genome were 20x slower with the 4 M
-        // position windows that suit 50x data -- and a whole batch is too long to walk with the wrong size.
-        if (ctx->calib_left > 0 && !ctx->prm.walk_window_span) {
-            FGPU_HIP(hipMemcpyAsync(ctx->fb_host, &ctx->counters->followers, 8, hipMemcpyDeviceToHost, walk_stream));
-            FGPU_HIP(hipMemcpyAsync(ctx->fb_host + 1, &ctx->counters->walked_pieces, 8, hipMemcpyDeviceToHost, walk_stream));
-            FGPU_HIP(hipMemcpyAsync(ctx->fb_host + 2, &ctx->counters->ko_overflows, 8, hipMemcpyDeviceToHost, walk_stream));
-            FGPU_HIP(fgpu_sync_stream(ctx, walk_stream));
-            const uint64_t f = ctx->fb_host[0] - ctx->calib_f, p = ctx->fb_host[1] - ctx->calib_p;
-            if (ctx->fb_host[2] > ctx->calib_ovf && span_now > 4096) {
-                // the window's large clusters outgrew the tables of the large-cluster walks (their pieces do not queue, so the share of
-                // followers says nothing about them) and were walked by one thread each: far too large a window for this data -- a quarter,
-                // and the next windows are looked at as well (round 4: read pairs inside repeats at 600x, a 36 MB file whose windows grew to
-                // 2^23 positions within its three batches: pass 2 2.0 s, 0.8 s with windows of 2^20)
-                ctx->calib_ovf = ctx->fb_host[2];
-                ctx->calib_f = ctx->fb_host[0];
-                ctx->calib_p = ctx->fb_host[1];
-                span_now = std::max<uint64_t>(4096, span_now / 4);
-                ctx->proven_span = std::min(ctx->proven_span, span_now);
-                ctx->calib_left = std::max(ctx->calib_left, 4);
-                ctx->span_ceiling = std::min(ctx->span_ceiling, span_now * 2);     // (this scan does not grow to that size again)
-                static const bool dbg_span_o = getenv("FGPU_DEBUG_SPAN") != nullptr;
-                if (dbg_span_o) fprintf(stderr, "[span] look: the large-cluster walks' tables overflowed -> span %llu, looks left %d\n", (unsigned long long)span_now, ctx->calib_left);
-            } else
-            if (p >= 64) {
-                ctx->calib_f = ctx->fb_host[0];
-                ctx->calib_p = ctx->fb_host[1];
-                bool shrunk = false;
-                if (f * 2 > p && span_now > 4096) { span_now /= 2; shrunk = true; }
-                else if (f * 3 < p && span_now < std::min<uint64_t>(std::min<uint64_t>(ctx->max_span, FGPU_USUAL_SPAN), ctx->span_ceiling))
-                    span_now = std::min<uint64_t>(span_now * 4, std::min<uint64_t>(std::min<uint64_t>(ctx->max_span, FGPU_USUAL_SPAN), ctx->span_ceiling));
-                else if (f * 16 < p && span_now < std::min<uint64_t>(ctx->max_span, ctx->span_ceiling))
-                    span_now = std::min<uint64_t>(span_now * 4, std::min<uint64_t>(ctx->max_span, ctx->span_ceiling));
-                else ctx->calib_left = 1;          // settled
-                ctx->calib_left--;
-                // waiting for a window keeps the host from feeding the pure stage of the next batch: worth it while windows are small
-                // (a fraction of a millisecond each, and the wrong size hurts most there); from 2^22 positions on the per-batch
-                // controller (adapt_window, no waiting) takes over unless the last look said "too large"
-                if (!shrunk && span_now >= (1ULL << 22)) ctx->calib_left = 0;
-                static const bool dbg_span = getenv("FGPU_DEBUG_SPAN") != nullptr;
-                if (dbg_span) fprintf(stderr, "[span] look: followers %llu of %llu pieces -> span %llu, looks left %d\n", (unsigned long long)f, (unsigned long long)p,
-                                      (unsigned long long)span_now, ctx->calib_left);
-            }
-        }
+        if ((rc = walk_span_look(ctx, kn, walk_stream, &span_now))) return rc;
     }
     if (ctx->delta_ready)      // (read shards, planes merged instead of made again: see k_delta_filter_add)
-        FGPU_LAUNCH("walk_delta", k_delta_filter_add, 256, 256, (const uint32_t*)mine_list.list.p, (const unsigned long long*)mine_list.count.p,
+        FGPU_LAUNCH("walk_delta", k_delta_filter_add, 256, 256, (const uint32_t*)wb.created->list.p, (const unsigned long long*)wb.created->count.p,
                     (uint32_t*)ctx->delta_filter.p, ctx->delta_filter_bits - 1);
     ctx->delta_next++;
     ctx->window_span = span_now;
@@ -3626,357 +3282,5 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
     }
     ctx->launch_stream = ctx->stream;
     ctx->scan_piece_base += n_pieces;
-    return FGPU_OK;
-}
-
-// ---- scanInputRead's lists (FGPU_FLAG_RECORD_STOPS) ---------------------------------------------------------------
-namespace {
-__device__ __forceinline__ uint64_t piece_chunk(const unsigned long long* plane, uint64_t p0, uint32_t nwin, uint32_t c) {
-    return fd_bits_at((const uint64_t*)plane, p0 + 64ULL * c) & chunk_mask(nwin, c);
-}
-
-// elements of the list of every piece: one per junction visit, or the single fake junction (ReadScanner.cpp:195-200)
-__global__ void __launch_bounds__(256) k_stop_count(const uint2* __restrict__ pieces, uint64_t n_pieces, const unsigned long long* sF,
-                                                    const unsigned long long* sB, uint32_t* __restrict__ count) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_pieces) return;
-    const uint2 pc = pieces[i];
-    uint32_t n = 0;
-    for (uint32_t c = 0; c * 64 < pc.y; c++) n += __popcll(piece_chunk(sF, pc.x, pc.y, c)) + __popcll(piece_chunk(sB, pc.x, pc.y, c));
-    count[i] = n ? n : 1u;
-}
-
-__global__ void __launch_bounds__(256) k_stop_fill(const uint2* __restrict__ pieces, uint64_t n_pieces, const unsigned long long* sF,
-                                                   const unsigned long long* sB, const uint32_t* __restrict__ offset,
-                                                   const uint32_t* __restrict__ piece_read, const uint64_t* __restrict__ codes, FdParams fp,
-                                                   fgpu_stop* __restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_pieces) return;
-    const uint2 pc = pieces[i];
-    const uint64_t p0 = pc.x;
-    const uint32_t nwin = pc.y, rd = piece_read[i];
-    fgpu_stop* o = out + offset[i];
-    uint32_t n = 0;
-    for (uint32_t c = 0; c * 64 < nwin; c++) {
-        const uint64_t wF = piece_chunk(sF, p0, nwin, c), wB = piece_chunk(sB, p0, nwin, c);
-        uint64_t any = wF | wB;
-        while (any) {
-            const int b = __builtin_ctzll(any);
-            any &= any - 1;
-            const uint32_t q = c * 64 + b;
-            if ((wB >> b) & 1ULL) {   // half-step 2q: facing BACKWARD, the extension is the reverse complement of the window before
-                fgpu_stop e;
-                e.ext = fd_revcomp(fd_kmer_at(codes, p0 + q - 1, fp.k), fp.k);
-                e.read = rd;
-                e.info = q | (n == 0 ? FGPU_STOP_FIRST : 0u);
-                o[n++] = e;
-            }
-            if ((wF >> b) & 1ULL) {   // half-step 2q+1: facing FORWARD, the extension is the next window
-                fgpu_stop e;
-                e.ext = fd_kmer_at(codes, p0 + q + 1, fp.k);
-                e.read = rd;
-                e.info = q | FGPU_STOP_FORWARD | (n == 0 ? FGPU_STOP_FIRST : 0u);
-                o[n++] = e;
-            }
-        }
-    }
-    if (n == 0) {   // add_fake_junction: middle k-mer facing FORWARD (ReadScanner.cpp:92-104)
-        const uint32_t m = (nwin + (uint32_t)fp.k - 1) / 2 - (uint32_t)fp.k / 2;
-        fgpu_stop e;
-        e.ext = fd_kmer_at(codes, p0 + m + 1, fp.k);
-        e.read = rd;
-        e.info = m | FGPU_STOP_FORWARD | FGPU_STOP_FIRST | FGPU_STOP_FAKE;
-        o[0] = e;
-    }
-}
-
-// Bloom::addPair(JuncPair) (utils/Bloom.cpp:127-139): the two canonical k-mers, the smaller under seed 0 and the larger under seed 1
-struct PairFilterDev {
-    uint32_t* bits;
-    uint64_t mask;
-    int n_hash;
-};
-__device__ __forceinline__ void pf_add_pair(const PairFilterDev& pf, uint64_t k1, uint64_t k2, int k) {
-    const uint64_t e1 = fd_canon(k1, k), e2 = fd_canon(k2, k);
-    uint64_t h0 = fd_old_hash(e1 < e2 ? e1 : e2, FD_SEED0) & pf.mask;
-    const uint64_t h1 = fd_old_hash(e1 < e2 ? e2 : e1, FD_SEED1) & pf.mask;
-    for (int i = 0; i < pf.n_hash; i++) {
-        atomicOr(&pf.bits[h0 >> 5], 1u << (h0 & 31));
-        h0 = (h0 + h1) & pf.mask;
-    }
-}
-
-// What scan_forward does with its result list when cleaning is on (src/ReadScanner.cpp:208-225), one thread per valid piece: a list of two
-// is paired by facing (an outward-facing pair by first backward / last forward junction, two junctions facing the same way as they stand),
-// a longer list pairs every element with the next but one.  Adding is order-free, so the device's order is as good as the file's.
-__global__ void __launch_bounds__(256) k_short_pairs(const fgpu_stop* __restrict__ stops, const uint32_t* __restrict__ count,
-                                                     const uint32_t* __restrict__ offset, uint64_t n_pieces, PairFilterDev pf, int k) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_pieces) return;
-    const uint32_t n = count[i];
-    const fgpu_stop* s = stops + offset[i];
-    if (n == 2) {
-        bool have_first_back = false, have_last_fwd = false;
-        uint32_t rev_pos = 0, for_pos = 0;
-        uint64_t first_back = 0, last_fwd = 0;
-        for (int t = 0; t < 2; t++) {
-            const uint32_t info = s[t].info, pos = info & FGPU_STOP_POS_MASK;
-            if (info & FGPU_STOP_FAKE) continue;
-            if (!(info & FGPU_STOP_FORWARD)) {
-                if (!have_first_back) { have_first_back = true; first_back = s[t].ext; rev_pos = pos; }
-            } else {
-                if (!have_last_fwd) { have_last_fwd = true; for_pos = pos; }
-                last_fwd = s[t].ext;
-            }
-        }
-        if (have_first_back && have_last_fwd && !(rev_pos > for_pos)) pf_add_pair(pf, first_back, last_fwd, k);
-        if (have_first_back != have_last_fwd) pf_add_pair(pf, s[0].ext, s[1].ext, k);
-    } else if (n > 2) {
-        for (uint32_t t = 0; t + 2 < n; t++) pf_add_pair(pf, s[t].ext, s[t + 2].ext, k);
-    }
-}
-}  // namespace
-
-// Bring the stops of a walked batch to the host queue (waits for that batch's walk only).
-int fgpu_scan_harvest(fgpu_ctx* ctx, BatchBufs* b) {
-    for (size_t i = 0; i < ctx->to_harvest.size(); i++)
-        if (ctx->to_harvest[i] == b) { ctx->to_harvest.erase(ctx->to_harvest.begin() + i); break; }
-    if (!b->stops_pending) return FGPU_OK;
-    // ONE wait of the host per harvested batch (round 5; there were three: for the walk's event, for the error flags, for the lists' total):
-    // the main stream waits for the walk by itself, and what the host has to see -- the flags of the walk (a walk that went wrong must not hand
-    // out lists), how many elements the lists hold -- comes back with one synchronisation.
-    if (b->walk_pending) {
-        FGPU_HIP(hipStreamWaitEvent(ctx->stream, b->walk_done, 0));
-        b->walk_pending = false;
-    }
-    const bool check = ctx->journal_on && !ctx->in_replay;
-    const uint64_t np_count = b->n_pieces;
-    uint32_t* count_c = nullptr;
-    uint32_t* offset_c = nullptr;
-    if (np_count) {
-        if (int rc0 = fgpu_ensure_b(ctx, &b->stop_off, (2 * np_count + 2) * 4)) return rc0;
-        count_c = (uint32_t*)b->stop_off.p;
-        offset_c = count_c + np_count + 1;
-        hipLaunchKernelGGL(k_stop_count, dim3(fgpu_blocks(np_count, 256)), dim3(256), 0, ctx->stream, (const uint2*)b->pieces.p, np_count,
-                           (const unsigned long long*)b->sF.p, (const unsigned long long*)b->sB.p, count_c);
-        size_t tmp_bytes = 0;
-        FGPU_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, count_c, offset_c, 0u, np_count, rocprim::plus<uint32_t>(), ctx->stream));
-        DevBuf& tmp = ctx->probe_buf;
-        if (int rc0 = fgpu_ensure_b(ctx, &tmp, tmp_bytes + 16)) return rc0;
-        FGPU_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, count_c, offset_c, 0u, np_count, rocprim::plus<uint32_t>(), ctx->stream));
-        FGPU_HIP(hipMemcpyAsync(&ctx->fb_host[4], count_c + np_count - 1, 4, hipMemcpyDeviceToHost, ctx->stream));
-        FGPU_HIP(hipMemcpyAsync(&ctx->fb_host[5], offset_c + np_count - 1, 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    // (the flags always: the one synchronisation is there anyway whenever the batch has pieces)
-    FGPU_HIP(hipMemcpyAsync(&ctx->counters_host->error_flags, &ctx->counters->error_flags, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    if (ctx->counters_host->error_flags & 1ULL) {
-        // A walk up to this one outgrew the junction table and dropped records: these lists are wrong, and nothing of them may reach the
-        // caller or a pair filter.  The flag is cumulative, so a clean one here means every walk up to this batch was good.
-        // Absorbable: replayed on a larger table first (as check_errors decides); inside a replay: scan_replay grows the table and goes again.
-        ctx->to_harvest.insert(ctx->to_harvest.begin(), b);
-        if (fgpu_overflow_absorbable(ctx)) { ctx->lazy_failed = ctx->capacity_failed = true; return FGPU_INTERNAL_REPLAY; }
-        ctx->err = FGPU_TABLE_FULL_MSG;
-        return FGPU_ERR_CAPACITY;
-    }
-    if (check && (ctx->counters_host->error_flags & 4ULL)) { ctx->lazy_failed = true; ctx->to_harvest.insert(ctx->to_harvest.begin(), b); return FGPU_INTERNAL_REPLAY; }
-    b->stops_pending = false;
-    if (b->seq < ctx->stops_delivered) return FGPU_OK;   // scanned again by a replay: the caller has this batch's lists already
-    // the lists come to the host unless their consumers on the device said otherwise (fgpu_scan_short_pairs' lists_to_host; a scan that only
-    // feeds the long pair filter on the device, fgpu_scan_long_pairs, hands none out)
-    const bool to_host = ctx->short_pf ? ctx->short_pf_lists_to_host : !ctx->lp.mode;
-    if (to_host) {
-        ctx->stop_queue.emplace_back();
-        ctx->stop_queue.back().seq = b->seq;
-    } else {
-        ctx->stops_delivered = b->seq + 1;                // nobody takes them: the lists end in the device's pair filter
-    }
-    const uint64_t np = b->n_pieces;
-    // the long pair filter takes every batch exactly once, whoever else reads the lists: with lists_to_host a replay harvests the batches the
-    // caller has not taken yet again, and a second pass of the check-then-insert loop over them would count and insert twice
-    const bool lp_due = b->seq >= ctx->lp_applied_seq;
-    if (!np) {
-        if (!lp_due) return FGPU_OK;
-        const int rc0 = fgpu_long_pairs_batch(ctx, nullptr, 0, b->n_reads);   // (its reads still count as ends of pairs)
-        if (!rc0) ctx->lp_applied_seq = b->seq + 1;
-        return rc0;
-    }
-    int rc;
-    uint32_t* count = count_c;
-    uint32_t* offset = offset_c;
-    const uint64_t total = (uint64_t)(uint32_t)ctx->fb_host[4] + (uint64_t)(uint32_t)ctx->fb_host[5];
-    if ((rc = fgpu_ensure_b(ctx, &b->stop_out, total * sizeof(fgpu_stop)))) return rc;
-    hipLaunchKernelGGL(k_stop_fill, dim3(fgpu_blocks(np, 256)), dim3(256), 0, ctx->stream, (const uint2*)b->pieces.p, np,
-                       (const unsigned long long*)b->sF.p, (const unsigned long long*)b->sB.p, (const uint32_t*)offset,
-                       (const uint32_t*)b->piece_read.p, (const uint64_t*)b->codes.p, ctx->fd, (fgpu_stop*)b->stop_out.p);
-    if (ctx->short_pf)
-        hipLaunchKernelGGL(k_short_pairs, dim3(fgpu_blocks(np, 256)), dim3(256), 0, ctx->stream, (const fgpu_stop*)b->stop_out.p, (const uint32_t*)count,
-                           (const uint32_t*)offset, np, PairFilterDev{ctx->short_pf, ctx->short_pf_tai - 1, ctx->short_pf_hashes}, ctx->fd.k);
-    // scanReads' paired-end loop over the same lists (pairs.hip): check-then-insert in file order, exact, on the device
-    if (lp_due) {
-        if ((rc = fgpu_long_pairs_batch(ctx, (const fgpu_stop*)b->stop_out.p, total, b->n_reads))) return rc;
-        ctx->lp_applied_seq = b->seq + 1;
-    }
-    if (to_host) {
-        StopBatch& sb = ctx->stop_queue.back();
-        if (total) {
-            size_t best = ctx->stop_pool.size();                       // the smallest free buffer that is large enough
-            for (size_t i = 0; i < ctx->stop_pool.size(); i++)
-                if (ctx->stop_pool[i].cap >= total && (best == ctx->stop_pool.size() || ctx->stop_pool[i].cap < ctx->stop_pool[best].cap)) best = i;
-            if (best < ctx->stop_pool.size()) {
-                sb.data = ctx->stop_pool[best].data;
-                sb.cap = ctx->stop_pool[best].cap;
-                ctx->stop_pool.erase(ctx->stop_pool.begin() + (ptrdiff_t)best);
-            } else {
-                const size_t cap = (size_t)(total + total / 4);
-                FGPU_HIP(hipHostMalloc((void**)&sb.data, cap * sizeof(fgpu_stop)));
-                sb.cap = cap;
-            }
-            FGPU_HIP(hipMemcpyAsync(sb.data, b->stop_out.p, total * sizeof(fgpu_stop), hipMemcpyDeviceToHost, ctx->stream));
-            FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-        }
-        sb.n = total;
-    }
-    return FGPU_OK;
-}
-
-// ---- junction download / export / import -------------------------------------------------------------------------
-int fgpu_scan_export_impl(fgpu_ctx* ctx, void* dev_entries, uint64_t cap_entries, uint64_t* d_stamps, uint64_t* n_entries) {
-    unsigned long long* d_n = &ctx->counters->pad;
-    FGPU_HIP(hipMemsetAsync(d_n, 0, 8, ctx->stream));
-    (void)cap_entries;
-    FGPU_LAUNCH("export", k_export, (unsigned)std::min<uint64_t>(fgpu_blocks(ctx->jcap, 256), 4096), 256, make_jt(ctx), ctx->fd, (ExportEntry*)dev_entries,
-                d_stamps, d_n);
-    FGPU_HIP(hipMemcpyAsync(&ctx->counters_host->pad, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    *n_entries = ctx->counters_host->pad;
-    return FGPU_OK;
-}
-
-int fgpu_scan_import_impl(fgpu_ctx* ctx, const void* dev_entries, uint64_t n) {
-    if (!n) return FGPU_OK;
-    FGPU_LAUNCH("import", k_import, fgpu_blocks(n, 256), 256, make_jt(ctx), ctx->fd, (const ExportEntry*)dev_entries, n, ctx->counters);
-    return FGPU_OK;
-}
-
-int fgpu_scan_import_probe(fgpu_ctx* ctx, const void* dev_entries, uint64_t n, uint64_t after_seq, uint32_t* dfilter, uint64_t dfilter_bits,
-                           uint64_t* max_seq, uint64_t* n_newer, uint64_t digest[2]) {
-    *max_seq = *n_newer = 0;
-    digest[0] = digest[1] = 0;
-    if (!n) return FGPU_OK;
-    if (int rc = fgpu_ensure(ctx, &ctx->import_probe, 32)) return rc;
-    FGPU_HIP(hipMemsetAsync(ctx->import_probe.p, 0, 32, ctx->stream));
-    FGPU_LAUNCH("import", k_import_probe, (unsigned)std::min<uint64_t>(fgpu_blocks(n, 256), 4096), 256, (const ExportEntry*)dev_entries, n, ctx->fd, after_seq, dfilter,
-                dfilter_bits ? dfilter_bits - 1 : 0, (unsigned long long*)ctx->import_probe.p);
-    unsigned long long out[4] = {0, 0, 0, 0};
-    FGPU_HIP(hipMemcpyAsync(out, ctx->import_probe.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    *max_seq = out[0];
-    *n_newer = out[1];
-    digest[0] = out[2];
-    digest[1] = out[3];
-    return FGPU_OK;
-}
-
-// ---- the reference's dump order on the device (host/junction_order.h: the closed form of what std::unordered_map does to its node list) -----
-namespace {
-// stretch j of the insertion sequence: position t holds node list[t] (t < c: the list as the last rehash found it) or node t itself (t >= c:
-// inserted since); its bucket is key % B.  first[b] = the earliest position of bucket b.
-__global__ void __launch_bounds__(256) k_dump_first(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ list, uint64_t c, uint64_t m, uint64_t B,
-                                                    uint32_t* __restrict__ bucket, uint32_t* first) {
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < m; t += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t node = t < c ? list[t] : (uint32_t)t;
-        const uint32_t b = (uint32_t)(keys[node] % B);
-        bucket[t] = b;
-        atomicMin(&first[b], (uint32_t)t);
-    }
-}
-// sort key: (first time of the node's bucket, own time), both descending
-__global__ void __launch_bounds__(256) k_dump_key(const uint32_t* __restrict__ list, uint64_t c, uint64_t m, const uint32_t* __restrict__ bucket,
-                                                  const uint32_t* __restrict__ first, uint64_t* __restrict__ sortkey, uint32_t* __restrict__ node_out) {
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < m; t += (uint64_t)gridDim.x * blockDim.x) {
-        node_out[t] = t < c ? list[t] : (uint32_t)t;
-        sortkey[t] = ((uint64_t)(0xFFFFFFFFu - first[bucket[t]]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)t);
-    }
-}
-}  // namespace
-
-// order_host[i] = index (in creation order) of the i-th junction of the reference's dump; d_keys: the junction keys in creation order on the device
-int fgpu_scan_dump_order_impl(fgpu_ctx* ctx, const uint64_t* d_keys, const uint64_t* counts, const uint64_t* buckets, uint64_t n_phases, uint64_t n,
-                              uint32_t* order_host) {
-    if (!n) return FGPU_OK;
-    uint64_t max_b = 1;
-    for (uint64_t j = 0; j < n_phases; j++) max_b = std::max(max_b, buckets[j]);
-    DevBuf list_a, list_b, bucket, first, key_a, key_b, tmp;
-    struct FreeAll { DevBuf* b[7]; ~FreeAll() { for (DevBuf* x : b) if (x->p) (void)hipFree(x->p); } } free_all{{&list_a, &list_b, &bucket, &first, &key_a, &key_b, &tmp}};
-    auto alloc = [&](DevBuf& b, uint64_t bytes) -> int {
-        if (hipMalloc(&b.p, bytes) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; ctx->err = "fgpu_scan_dump_order: out of device memory"; return FGPU_ERR_NOMEM; }
-        b.bytes = bytes;
-        return FGPU_OK;
-    };
-    int rc;
-    if ((rc = alloc(list_a, n * 4)) || (rc = alloc(list_b, n * 4)) || (rc = alloc(bucket, n * 4)) || (rc = alloc(first, max_b * 4)) || (rc = alloc(key_a, n * 8)) ||
-        (rc = alloc(key_b, n * 8)))
-        return rc;
-    size_t tmp_bytes = 0;
-    FGPU_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint64_t*)key_a.p, (uint64_t*)key_b.p, (uint32_t*)list_a.p, (uint32_t*)list_b.p, n, 0, 64, ctx->stream));
-    if ((rc = alloc(tmp, tmp_bytes + 16))) return rc;
-    uint32_t* list = (uint32_t*)list_a.p;      // the list as the last stretch left it
-    uint32_t* other = (uint32_t*)list_b.p;
-    bool any = false;
-    for (uint64_t j = 0; j < n_phases; j++) {
-        const uint64_t c = counts[j], m = j + 1 < n_phases ? counts[j + 1] : n, B = buckets[j];
-        if (m == 0) continue;
-        if (c > m || m > n || !B) { ctx->err = "fgpu_scan_dump_order: rehash counts must ascend to n, bucket counts must not be zero"; return FGPU_ERR_ARG; }
-        FGPU_HIP(hipMemsetAsync(first.p, 0xFF, B * 4, ctx->stream));
-        hipLaunchKernelGGL(k_dump_first, dim3(fgpu_grid(m, 256)), dim3(256), 0, ctx->stream, d_keys, (const uint32_t*)list, c, m, B, (uint32_t*)bucket.p, (uint32_t*)first.p);
-        hipLaunchKernelGGL(k_dump_key, dim3(fgpu_grid(m, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)list, c, m, (const uint32_t*)bucket.p, (const uint32_t*)first.p,
-                           (uint64_t*)key_a.p, other);
-        // (`other` holds the nodes in sequence order now; sorted into `list`)
-        size_t tb = tmp_bytes;
-        FGPU_HIP(rocprim::radix_sort_pairs(tmp.p, tb, (uint64_t*)key_a.p, (uint64_t*)key_b.p, other, list, m, 0, 64, ctx->stream));
-        any = true;
-    }
-    if (!any) { ctx->err = "fgpu_scan_dump_order: empty schedule"; return FGPU_ERR_ARG; }
-    FGPU_HIP(hipMemcpyAsync(order_host, list, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    return FGPU_OK;
-}
-
-// creation-ordered download: export, radix-sort the stamps (rocPRIM; not a hot step), gather
-int fgpu_scan_download_impl(fgpu_ctx* ctx, uint64_t* keys_host, fgpu_junction* recs_host, uint64_t cap, uint64_t* n_out) {
-    uint64_t n_max = ctx->scan_stats.n_junctions;
-    FGPU_HIP(hipMemcpyAsync(&ctx->counters_host->n_junctions, &ctx->counters->n_junctions, 8, hipMemcpyDeviceToHost, ctx->stream));
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    n_max = ctx->counters_host->n_junctions + ctx->scan_imported;
-    *n_out = n_max;
-    if (!n_max || !keys_host || !recs_host) return FGPU_OK;
-    if (cap < n_max) { ctx->err = "junction buffer too small"; return FGPU_ERR_CAPACITY; }
-    // scratch lives with the context: eight hipMalloc / hipFree pairs per call cost more than the sort they served
-    int rc;
-    if ((rc = fgpu_ensure(ctx, &ctx->dl_entries, n_max * sizeof(ExportEntry))) || (rc = fgpu_ensure(ctx, &ctx->dl_stamps, n_max * 8)) ||
-        (rc = fgpu_ensure(ctx, &ctx->dl_stamps_sorted, n_max * 8)) || (rc = fgpu_ensure(ctx, &ctx->dl_idx, n_max * 4)) ||
-        (rc = fgpu_ensure(ctx, &ctx->dl_idx_sorted, n_max * 4)) || (rc = fgpu_ensure(ctx, &ctx->dl_keys, n_max * 8)) ||
-        (rc = fgpu_ensure(ctx, &ctx->dl_recs, n_max * sizeof(fgpu_junction))))
-        return rc;
-    ExportEntry* d_entries = (ExportEntry*)ctx->dl_entries.p;
-    uint64_t *d_stamps = (uint64_t*)ctx->dl_stamps.p, *d_stamps_sorted = (uint64_t*)ctx->dl_stamps_sorted.p, *d_keys = (uint64_t*)ctx->dl_keys.p;
-    uint32_t *d_idx = (uint32_t*)ctx->dl_idx.p, *d_idx_sorted = (uint32_t*)ctx->dl_idx_sorted.p;
-    fgpu_junction* d_recs = (fgpu_junction*)ctx->dl_recs.p;
-    uint64_t n = 0;
-    if ((rc = fgpu_scan_export_impl(ctx, d_entries, n_max, d_stamps, &n))) return rc;
-    if (n != n_max) { ctx->err = "junction count mismatch between counters and table"; return FGPU_ERR_STATE; }
-    hipLaunchKernelGGL(k_iota_u32, dim3(256), dim3(256), 0, ctx->stream, d_idx, n);
-    size_t tmp_bytes = 0;
-    FGPU_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_stamps, d_stamps_sorted, d_idx, d_idx_sorted, n, 0, 64, ctx->stream));
-    if ((rc = fgpu_ensure(ctx, &ctx->dl_tmp, tmp_bytes ? tmp_bytes : 16))) return rc;
-    FGPU_HIP(rocprim::radix_sort_pairs(ctx->dl_tmp.p, tmp_bytes, d_stamps, d_stamps_sorted, d_idx, d_idx_sorted, n, 0, 64, ctx->stream));
-    hipLaunchKernelGGL(k_gather_sorted, dim3(fgpu_blocks(n, 256)), dim3(256), 0, ctx->stream, (const ExportEntry*)d_entries,
-                       (const uint32_t*)d_idx_sorted, n, d_keys, d_recs);
-    // page-locked destinations (fgpu_host_alloc) receive this at link speed; pageable ones through the runtime's staging
-    FGPU_HIP(hipMemcpyAsync(keys_host, d_keys, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    FGPU_HIP(hipMemcpyAsync(recs_host, d_recs, n * sizeof(fgpu_junction), hipMemcpyDeviceToHost, ctx->stream));
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    ctx->dl_keys_n = n;              // dl_keys holds the keys in creation order (fgpu_scan_dump_order works from them)
     return FGPU_OK;
 }
