@@ -36,6 +36,11 @@ class Reads(C.Structure):
                 ("total_bases", C.c_uint32), ("starts", C.c_void_p)]
 
 
+class Packed(C.Structure):
+    """fgpu_packed: one packed batch of a sliced pass as a device block"""
+    _fields_ = [("block_dev", C.c_void_p), ("nbytes", C.c_uint64), ("T", C.c_uint64), ("n_reads", C.c_uint64)]
+
+
 class LoadStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("reads_processed", "unambiguous_reads", "kmers", "to_bloo2")]
 
@@ -86,6 +91,10 @@ SIGNATURES = {
     "fgpu_load_slice_mercy_probe": (C.c_int, [_vp]),
     "fgpu_load_slice_mercy_planes": (C.c_int, [_vp, _u64, _P(_vp), _P(_u64)]),
     "fgpu_diag_slice_mercy": (C.c_int, [_vp, _P(_u64)]),
+    "fgpu_load_slice_pack": (C.c_int, [_vp, _P(Reads), _P(Packed)]),
+    "fgpu_load_slice_expect": (C.c_int, [_vp, _u64, _u64, _P(Packed)]),
+    "fgpu_load_slice_batch_packed": (C.c_int, [_vp, _P(Packed)]),
+    "fgpu_scan_resident_base": (C.c_int, [_vp, _u64]),
     "fgpu_scan_dump_order": (C.c_int, [_vp, _P(C.c_uint64), _P(C.c_uint64), C.c_uint64, C.c_uint64, _P(C.c_uint32)]),
     "fgpu_bloom_download": (C.c_int, [_vp, C.c_int, _vp, _u64]),
     "fgpu_bloom_download_begin": (C.c_int, [_vp, C.c_int, _vp, _u64]),
@@ -159,6 +168,7 @@ SIGNATURES = {
     "fgpu_group_barrier": (C.c_int, [_vp, C.c_int]),
     "fgpu_group_or_allreduce": (C.c_int, [_vp, C.c_int, _vp, _u64]),
     "fgpu_group_exclusive_prefix_or": (C.c_int, [_vp, C.c_int, _vp, _vp, _u64]),
+    "fgpu_group_allgather": (C.c_int, [_vp, C.c_int, _vp, _u64, _P(_u64)]),
     "fgpu_group_send": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _u64]),
     "fgpu_group_send_async": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _u64]),
     "fgpu_group_flush": (C.c_int, [_vp, C.c_int]),

@@ -246,6 +246,27 @@ class Context:
         self._c(self.lib.fgpu_diag_slice_mercy(self.h, out))
         return [int(x) for x in out]
 
+    # ... from packed batches: packed once (here or on a peer), moved device to device, loaded from the packed form
+    def load_slice_pack(self, batch: ReadBatch) -> "L.Packed":
+        """pack the batch into a block of the sliced pass (digest and T in its trailer); to be sent to the peers and loaded by load_slice_batch_packed"""
+        s, pk = batch.c_struct(), L.Packed()
+        self._c(self.lib.fgpu_load_slice_pack(self.h, C.byref(s), C.byref(pk)))
+        return pk
+
+    def load_slice_expect(self, T: int, n_reads: int) -> "L.Packed":
+        """an empty block for a batch of T stream positions that is packed elsewhere: the caller fills its nbytes before loading it"""
+        pk = L.Packed()
+        self._c(self.lib.fgpu_load_slice_expect(self.h, T, n_reads, C.byref(pk)))
+        return pk
+
+    def load_slice_batch_packed(self, pk: "L.Packed"):
+        """mark + resolve of a packed batch against the slice: what load_slice_batch does behind its packing"""
+        self._c(self.lib.fgpu_load_slice_batch_packed(self.h, C.byref(pk)))
+
+    def scan_resident_base(self, first_batch: int):
+        """between the passes: batch i of the next scan pairs with the load pass' resident batch first_batch + i"""
+        self._c(self.lib.fgpu_scan_resident_base(self.h, first_batch))
+
     def load_batch(self, batch: ReadBatch):
         s = batch.c_struct()
         self._c(self.lib.fgpu_load_batch(self.h, C.byref(s)))
@@ -608,6 +629,13 @@ class Bloom:
 
     def oldContains(self, canon_kmers):              # Bloom::oldContains (utils/Bloom.h:162-173), batched
         return self.ctx.probe_contains(self.which, canon_kmers)
+
+
+def group_allgather(group, rank: int, buf_dev_ptr, nbytes: int, bounds) -> int:
+    """fgpu_group_allgather on a group made with fgpu_group_create: rank q holds the bytes [bounds[q], bounds[q+1]) of the buffer, afterwards every
+    rank holds all of them.  Returns the status (the caller reads fgpu_group_last_error)."""
+    arr = (C.c_uint64 * len(bounds))(*[int(b) for b in bounds])
+    return L.load().fgpu_group_allgather(group, rank, buf_dev_ptr, nbytes, arr)
 
 
 def load_two_filters(bloo1: Bloom, bloo2: Bloom, batches) -> dict:

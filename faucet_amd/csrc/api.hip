@@ -119,6 +119,11 @@ static int check_errors(fgpu_ctx* ctx) {
     }
     if (ctx->counters_host->error_flags & 2ULL) { ctx->err = "window table full"; return FGPU_ERR_CAPACITY; }
     if (ctx->counters_host->error_flags & 32ULL) { ctx->err = "fgpu_reads.total_bases does not match the batch's offsets"; return FGPU_ERR_ARG; }
+    if (ctx->counters_host->error_flags & 64ULL) {
+        ctx->err = "fgpu_load_slice_batch_packed: a packed block's content does not match the digest and length in its trailer (a block filled "
+                   "with another batch's bytes, or damaged on its way)";
+        return FGPU_ERR_ARG;
+    }
     // FGPU_DEBUG_LAZY_FAIL=1 pretends the self-check of the lazy flags fired (tests of the callers' fall-back to eager flags)
     // (= n > 1: only once n batches of the scan have been prepared, so that the replay finds batches whose lists have been harvested already)
     static const long lazy_fail_knob = getenv("FGPU_DEBUG_LAZY_FAIL") ? atol(getenv("FGPU_DEBUG_LAZY_FAIL")) : 0;
@@ -382,6 +387,7 @@ void fgpu_destroy(fgpu_ctx* ctx) {
     for (int q = 0; q < 2; q++) if (ctx->ev_uf_reset[q]) hipEventDestroy(ctx->ev_uf_reset[q]);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
     for (ResidentBatch* r : ctx->resident) delete r;
+    for (PackedBlock* b : ctx->packed) delete b;
     for (JournalBatch* j : ctx->journal) delete j;
     for (JournalBatch* j : ctx->journal_pool) delete j;
     for (BatchBufs* b : ctx->all_batches) {
@@ -477,6 +483,7 @@ int fgpu_load_begin(fgpu_ctx* ctx, int keep_carry) {
     // FGPU_ERR_STATE as faucet_gpu.h says (hosts then take the presence protocol: sharded.fixup_possible, shard_host.h)
     ctx->shard_planes = (keep_carry & FGPU_LOAD_SHARD_PLANES) != 0 && !ctx->shard_times && ctx->prm.n_hash <= 4;
     ctx->fixup_ready = false;
+    ctx->scan_resident_base = 0;
     ctx->pass_positions = ctx->pass_batches = 0;
     ctx->pass_empty_carry = !(keep_carry & FGPU_LOAD_KEEP_CARRY);
     keep_carry &= FGPU_LOAD_KEEP_CARRY;
@@ -613,6 +620,8 @@ static int slice_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi, bool mer
     ctx->slice_mercy = mercy;
     ctx->slice_probe_owed = false;
     ctx->slice_owed_span = 0;
+    ctx->scan_resident_base = 0;
+    for (PackedBlock* b : ctx->packed) b->state = 0;      // blocks of earlier passes: their buffers serve this one
     ctx->shard_times = ctx->shard_planes = ctx->fixup_ready = false;
     ctx->rec_layout = false;
     ctx->pass_positions = ctx->pass_batches = 0;
@@ -649,6 +658,79 @@ int fgpu_load_slice_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (ctx->cur->T) ctx->pass_batches++;
     ctx->load_stats.reads_processed += reads->n_reads;
     return fgpu_host_batch_done(ctx, reads);
+}
+
+// ---- packed batches of a sliced pass: made here or by a peer, loaded from the packed form (faucet_gpu.h) --------------------------------
+static int slice_open_for(fgpu_ctx* ctx, const char* who) {
+    if (ctx->phase != 3) { ctx->err = std::string(who) + " outside load_slice_begin/load_slice_end"; return FGPU_ERR_STATE; }
+    if (ctx->slice_committed) { ctx->err = std::string(who) + " after load_slice_commit: the pass can only be ended"; return FGPU_ERR_STATE; }
+    return FGPU_OK;
+}
+
+static void packed_describe(const PackedBlock* b, uint64_t n_reads, fgpu_packed* out) {
+    out->block_dev = b ? b->buf.p : nullptr;
+    out->nbytes = b ? fgpu_packed_bytes(b->n_words) : 0;
+    out->T = b ? b->T : 0;
+    out->n_reads = n_reads;
+}
+
+int fgpu_load_slice_pack(fgpu_ctx* ctx, const fgpu_reads* reads, fgpu_packed* out) {
+    if (!ctx || !out) return FGPU_ERR_ARG;
+    int rc = slice_open_for(ctx, "load_slice_pack");
+    if (rc || (rc = check_reads(ctx, reads))) return rc;
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    PackedBlock* b = nullptr;
+    if ((rc = fgpu_stage_pack_block(ctx, reads, &b))) return rc;
+    packed_describe(b, reads->n_reads, out);
+    return fgpu_host_batch_done(ctx, reads);
+}
+
+int fgpu_load_slice_expect(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, fgpu_packed* out) {
+    if (!ctx || !out) return FGPU_ERR_ARG;
+    if (int rc = slice_open_for(ctx, "load_slice_expect")) return rc;
+    // a stream holds one separator per read: T >= n_reads, and T = 0 exactly for a batch without reads
+    if (n_reads > T || (T && !n_reads) || T > ctx->prm.max_batch_bases || T >= 0xFFFFFF00ULL) {
+        ctx->err = "load_slice_expect: T stream positions (bases + one separator per read, at most max_batch_bases) of n_reads <= T reads";
+        return FGPU_ERR_ARG;
+    }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    PackedBlock* b = nullptr;
+    if (T)
+        if (int rc = fgpu_packed_acquire(ctx, T, n_reads, 2, "load_slice_expect", &b)) return rc;
+    packed_describe(b, n_reads, out);
+    return FGPU_OK;
+}
+
+int fgpu_load_slice_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk) {
+    if (!ctx || !pk) return FGPU_ERR_ARG;
+    if (int rc = slice_open_for(ctx, "load_slice_batch_packed")) return rc;
+    if (ctx->slice_probe_owed) {
+        ctx->err = "load_slice_batch_packed: the previous batch of this mercy pass has not been probed (fgpu_load_slice_mercy_probe, after its fail "
+                   "plane has been ORed): its first-set times must be read before the next batch is marked";
+        return FGPU_ERR_STATE;
+    }
+    if (!pk->block_dev) {                        // a batch without reads has no block
+        if (pk->T || pk->nbytes || pk->n_reads) { ctx->err = "load_slice_batch_packed: a description without a block must be empty"; return FGPU_ERR_ARG; }
+        return FGPU_OK;
+    }
+    PackedBlock* b = nullptr;
+    for (PackedBlock* q : ctx->packed)
+        if (q->buf.p == pk->block_dev) b = q;
+    if (!b || (b->state != 1 && b->state != 2)) {
+        ctx->err = !b ? "load_slice_batch_packed: not a block of fgpu_load_slice_pack / fgpu_load_slice_expect"
+                      : b->state == 3 ? "load_slice_batch_packed: the block has been loaded already"
+                                      : "load_slice_batch_packed: the block belongs to an earlier pass";
+        return FGPU_ERR_STATE;
+    }
+    if (pk->T != b->T || pk->nbytes != fgpu_packed_bytes(b->n_words) || pk->n_reads != b->n_reads) {
+        ctx->err = "load_slice_batch_packed: T, nbytes or n_reads are not those the block was made with";
+        return FGPU_ERR_ARG;
+    }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    if (int rc = fgpu_stage_slice_load_packed(ctx, b)) return rc;
+    ctx->pass_batches++;
+    ctx->load_stats.reads_processed += b->n_reads;
+    return FGPU_OK;
 }
 
 int fgpu_load_slice_plane(fgpu_ctx* ctx, uint64_t batch, void** fail_dev, uint64_t* nbytes) {
@@ -797,6 +879,13 @@ int fgpu_bitmap_or(fgpu_ctx* ctx, void* dst_dev, const void* src_dev, uint64_t n
 }
 
 // ---- pass 2 --------------------------------------------------------------------------------------------------
+int fgpu_scan_resident_base(fgpu_ctx* ctx, uint64_t first_batch) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 0) { ctx->err = "scan_resident_base while a pass is open: between the load pass and fgpu_scan_begin"; return FGPU_ERR_STATE; }
+    ctx->scan_resident_base = first_batch;
+    return FGPU_OK;
+}
+
 int fgpu_scan_begin(fgpu_ctx* ctx) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 0) { ctx->err = "scan_begin while another pass is open"; return FGPU_ERR_STATE; }

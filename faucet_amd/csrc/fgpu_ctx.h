@@ -80,7 +80,21 @@ struct ResidentBatch {
     DevBuf miss;                 // sliced pass under --mercy: four planes "an own bit of candidate nt was not set by this position" (k_slice_mercy_probe)
     uint64_t T = 0, n_words = 0;
     uint32_t tb = 0;             // time base of the batch's first-set times (FGPU_LOAD_SHARD_TIMES: position within the pass)
+    // a batch loaded from a packed block (fgpu_load_slice_batch_packed): the block IS the batch's codes / bad -- no second copy; null otherwise
+    void *packed_codes = nullptr, *packed_bad = nullptr;
+    const void* codes_p() const { return packed_codes ? packed_codes : codes.p; }
+    const void* bad_p() const { return packed_bad ? packed_bad : bad.p; }
 };
+
+// A packed batch of a sliced pass as ONE device buffer (fgpu_packed): codes plane (2 x stride words), bad plane (stride words), stride =
+// n_words + FGPU_PADW, then the 16-byte trailer {digest, T}.  Made by fgpu_load_slice_pack (packed here) or fgpu_load_slice_expect (filled by
+// the caller, e.g. from a peer), loaded once by fgpu_load_slice_batch_packed; the buffers are recycled by the next sliced pass.
+struct PackedBlock {
+    DevBuf buf;
+    uint64_t T = 0, n_words = 0, n_reads = 0;
+    int state = 0;               // 0 free, 1 packed here, 2 expected from elsewhere (its digest is checked when it is loaded), 3 loaded
+};
+static inline uint64_t fgpu_packed_bytes(uint64_t n_words) { return 3 * (n_words + FGPU_PADW) * 8 + 16; }
 
 // hashes of the junction keys one batch's walk created (k_delta_collect): what later batches register as the delta of their snapshot
 struct DeltaList {
@@ -158,7 +172,7 @@ struct DevCounters {
     unsigned long long table_slots_used;
     unsigned long long followers;
     unsigned long long max_cluster;
-    unsigned long long error_flags;     // bit 0: junction table full, bit 1: window table full
+    unsigned long long error_flags;     // bit 0: junction table full, bit 1: window table full, ... bit 6: a packed block's digest or length is not its trailer's
     unsigned long long max_read_len;    // longest read of the batches packed so far (bounds how far a piece reaches)
     unsigned long long wt_used;         // slots claimed in the window table during the current window
     unsigned long long pad;
@@ -251,7 +265,10 @@ struct fgpu_ctx {
     uint64_t resident_count = 0;     // entries of `resident` that hold the current load pass
     uint64_t resident_bytes = 0, resident_budget = 0;
     bool resident_open = false;      // the current load pass is still keeping its batches
-    uint64_t scan_batch_index = 0;   // scan batch i pairs with resident[i]
+    uint64_t scan_batch_index = 0;   // scan batch i pairs with resident[scan_resident_base + i]
+    uint64_t scan_resident_base = 0; // fgpu_scan_resident_base: the scan's first batch within the resident batches (0 again at the next load pass)
+    std::vector<PackedBlock*> packed;      // packed blocks of the current sliced pass (and free ones of earlier passes)
+    DevBuf packed_digest;            // one word: the digest of the block being loaded, before it is compared with the block's trailer
 
     // pass 2 state: junction table (open addressing on the canonical k-mer)
     uint64_t jcap = 0;               // slots (power of two)
@@ -499,6 +516,10 @@ void fgpu_touch_scan_walk();
 void fgpu_touch_scan_table();
 void fgpu_touch_scan_harvest();
 int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads);
+int fgpu_stage_pack_block(fgpu_ctx* ctx, const fgpu_reads* reads, PackedBlock** out);
+int fgpu_packed_acquire(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, int state, const char* who, PackedBlock** out);
+int fgpu_packed_digest(fgpu_ctx* ctx, const PackedBlock* b, bool verify);
+int fgpu_stage_slice_load_packed(fgpu_ctx* ctx, PackedBlock* b);
 int fgpu_host_batch_done(fgpu_ctx* ctx, const fgpu_reads* reads);
 int fgpu_stage_load(fgpu_ctx* ctx);
 int fgpu_load_sweep(fgpu_ctx* ctx);

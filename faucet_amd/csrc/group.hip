@@ -432,6 +432,24 @@ int fgpu_group_or_allreduce(fgpu_group* g, int rank, void* bitmap_dev, uint64_t 
     return exchange(g, rank, sends, recvs);
 }
 
+int fgpu_group_allgather(fgpu_group* g, int rank, void* buf_dev, uint64_t nbytes, const uint64_t* bounds) {
+    if (int rc = check_rank(g, rank)) return rc;
+    if (!buf_dev || !bounds) return gfail(g, rank, FGPU_ERR_ARG, "allgather: a device buffer and n_ranks + 1 byte offsets");
+    for (int q = 0; q < g->n; q++)
+        if (bounds[q] > bounds[q + 1] || bounds[q + 1] > nbytes) return gfail(g, rank, FGPU_ERR_ARG, "allgather: the offsets must ascend and stay inside the buffer");
+    if (g->n == 1) return FGPU_OK;
+    char* buf = (char*)buf_dev;
+    const uint64_t mine = bounds[rank + 1] - bounds[rank];
+    // the own range to everybody, theirs straight into place (an empty range is neither sent nor received: every rank knows the bounds)
+    std::vector<Xfer> sends, recvs;
+    for (int q = 0; q < g->n; q++) {
+        if (q == rank) continue;
+        if (mine) sends.push_back(Xfer{q, buf + bounds[rank], mine});
+        if (bounds[q + 1] > bounds[q]) recvs.push_back(Xfer{q, buf + bounds[q], bounds[q + 1] - bounds[q]});
+    }
+    return exchange(g, rank, sends, recvs);
+}
+
 int fgpu_group_exclusive_prefix_or(fgpu_group* g, int rank, const void* bitmap_dev, void* out_dev, uint64_t nbytes) {
     if (int rc = check_rank(g, rank)) return rc;
     if (!bitmap_dev || !out_dev || (nbytes & 15)) return gfail(g, rank, FGPU_ERR_ARG, "exclusive_prefix_or: device bitmaps of a multiple of 16 bytes");

@@ -981,6 +981,7 @@ static int fgpu_resident_keep(fgpu_ctx* ctx) {
     r.T = bb.T;
     r.n_words = bb.n_words;
     r.tb = ctx->cur_tb;
+    r.packed_codes = r.packed_bad = nullptr;
     FGPU_HIP(hipMemcpyAsync(r.codes.p, bb.codes.p, cb, hipMemcpyDeviceToDevice, ctx->stream));
     FGPU_HIP(hipMemcpyAsync(r.bad.p, bb.bad.p, pb, hipMemcpyDeviceToDevice, ctx->stream));
     FGPU_HIP(hipMemcpyAsync(r.sure.p, bb.sure.p, pb, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1131,12 +1132,44 @@ int fgpu_slice_sweep(fgpu_ctx* ctx) {
 
 // The batch joins the carry: by re-hashing its pending occurrences (their planes are still those of the batch in hand) or, once the epoch has
 // grown enough, by a sweep.  Right behind mark + resolve in a plain sliced pass, behind the probe in a mercy one.
-static int slice_fold_batch(fgpu_ctx* ctx, uint64_t span) {
-    BatchBufs& bb = *ctx->cur;
+static int slice_fold_batch(fgpu_ctx* ctx, const void* codes, uint64_t n_words, uint64_t span) {
     if (ctx->carry_by_set)
-        FGPU_LAUNCH("slice_carry_update", k_slice_carry_set, fgpu_grid(span, 256), 256, (const uint64_t*)bb.codes.p, bb.n_words, ctx->fd, slice_of(ctx),
-                    (const uint64_t*)bb.pending.p, bb.n_words + FGPU_PADW);
+        FGPU_LAUNCH("slice_carry_update", k_slice_carry_set, fgpu_grid(span, 256), 256, (const uint64_t*)codes, n_words, ctx->fd, slice_of(ctx),
+                    (const uint64_t*)ctx->cur->pending.p, n_words + FGPU_PADW);
     return epoch_after_batch(ctx, span, fgpu_slice_sweep);
+}
+
+// mark + resolve of a packed stream (codes, bad: T positions) against the slice, into the fail plane of resident slot r; the pending planes
+// are the scratch of the batch in hand
+static int slice_mark_resolve(fgpu_ctx* ctx, const void* codes, const void* bad, uint64_t T, uint64_t n_words, ResidentBatch& r) {
+    const uint64_t plane_stride = n_words + FGPU_PADW;
+    int rc = fgpu_ensure_b(ctx, &ctx->cur->pending, (MISS_PLANES + 1) * plane_stride * 8);
+    if (rc) return rc;
+    FGPU_LAUNCH("count_segments", k_count_segments, std::min(fgpu_grid(n_words, 256), 256u), 256, (const uint64_t*)bad, n_words, ctx->fd.k,
+                &ctx->counters->segments);
+    // times are positions within the epoch, as in fgpu_stage_load: a sweep before the 32-bit clock would wrap
+    const uint64_t span = n_words * 64;
+    if ((rc = epoch_before_batch(ctx, span, fgpu_slice_sweep))) return rc;
+    const uint32_t tb = ctx->carry_by_set ? 0u : (uint32_t)ctx->epoch_positions;
+    const unsigned grid = fgpu_grid(span, 256);
+    const Slice s = slice_of(ctx);
+    uint64_t* pending = (uint64_t*)ctx->cur->pending.p;
+    uint64_t* fail = (uint64_t*)r.fail.p;
+    FGPU_HIP(hipMemsetAsync(fail + n_words, 0, FGPU_PADW * 8, ctx->stream));   // the plane is ORed in 16-byte granules: zero past its last word
+    FGPU_LAUNCH("slice_mark", k_slice_mark, grid, 256, (const uint64_t*)codes, (const uint64_t*)bad, T, n_words, ctx->fd, s, tb, pending, plane_stride,
+                fail, ctx->counters);
+    FGPU_LAUNCH("slice_resolve", k_slice_resolve, grid, 256, (const uint64_t*)codes, n_words, ctx->fd, s, tb, (const uint64_t*)pending, plane_stride, fail);
+    if (ctx->slice_mercy) {
+        // the fold is left to fgpu_stage_slice_mercy_probe: until then first[] answers "set by time t" for this batch's positions
+        ctx->slice_probe_owed = true;
+        ctx->slice_owed_span = span;
+    } else if ((rc = slice_fold_batch(ctx, codes, n_words, span))) {
+        return rc;
+    }
+    r.T = T;
+    r.n_words = n_words;
+    r.tb = tb;
+    return FGPU_OK;
 }
 
 // mark + resolve of one batch against the slice.  The batch is kept in HBM first (codes, bad, its fail plane, room for `sure`): the commit
@@ -1154,8 +1187,7 @@ int fgpu_stage_slice_load(fgpu_ctx* ctx) {
                    (ctx->slice_mercy ? ", under --mercy with four miss planes (9 bits per stream position)" : "");
         return FGPU_ERR_NOMEM;
     }
-    int rc = fgpu_ensure_b(ctx, &bb.pending, (MISS_PLANES + 1) * plane_stride * 8);
-    if (rc) return rc;
+    int rc;
     if (ctx->resident_count == ctx->resident.size()) ctx->resident.push_back(new ResidentBatch());
     ResidentBatch& r = *ctx->resident[ctx->resident_count];
     if ((rc = fgpu_ensure_b(ctx, &r.codes, cb)) || (rc = fgpu_ensure_b(ctx, &r.bad, pb)) || (rc = fgpu_ensure_b(ctx, &r.sure, pb)) ||
@@ -1163,33 +1195,35 @@ int fgpu_stage_slice_load(fgpu_ctx* ctx) {
         ctx->err = "load_slice_batch: no device memory to keep the batch resident (budget " + std::to_string(ctx->resident_budget) + " bytes): " + ctx->err;
         return FGPU_ERR_NOMEM;
     }
-    if ((rc = fgpu_util_count_segments(ctx, ctx->fd.k))) return rc;
-    // times are positions within the epoch, as in fgpu_stage_load: a sweep before the 32-bit clock would wrap
-    const uint64_t span = bb.n_words * 64;
-    if ((rc = epoch_before_batch(ctx, span, fgpu_slice_sweep))) return rc;
-    const uint32_t tb = ctx->carry_by_set ? 0u : (uint32_t)ctx->epoch_positions;
-    const unsigned grid = fgpu_grid(span, 256);
-    const Slice s = slice_of(ctx);
-    uint64_t* fail = (uint64_t*)r.fail.p;
-    FGPU_HIP(hipMemsetAsync(fail + bb.n_words, 0, FGPU_PADW * 8, ctx->stream));   // the plane is ORed in 16-byte granules: zero past its last word
-    FGPU_LAUNCH("slice_mark", k_slice_mark, grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p, bb.T, bb.n_words, ctx->fd, s, tb,
-                (uint64_t*)bb.pending.p, plane_stride, fail, ctx->counters);
-    FGPU_LAUNCH("slice_resolve", k_slice_resolve, grid, 256, (const uint64_t*)bb.codes.p, bb.n_words, ctx->fd, s, tb, (const uint64_t*)bb.pending.p,
-                plane_stride, fail);
-    if (ctx->slice_mercy) {
-        // the fold is left to fgpu_stage_slice_mercy_probe: until then first[] answers "set by time t" for this batch's positions
-        ctx->slice_probe_owed = true;
-        ctx->slice_owed_span = span;
-    } else if ((rc = slice_fold_batch(ctx, span))) {
-        return rc;
-    }
-    r.T = bb.T;
-    r.n_words = bb.n_words;
-    r.tb = tb;
+    r.packed_codes = r.packed_bad = nullptr;
+    if ((rc = slice_mark_resolve(ctx, bb.codes.p, bb.bad.p, bb.T, bb.n_words, r))) return rc;
     FGPU_HIP(hipMemcpyAsync(r.codes.p, bb.codes.p, cb, hipMemcpyDeviceToDevice, ctx->stream));
     FGPU_HIP(hipMemcpyAsync(r.bad.p, bb.bad.p, pb, hipMemcpyDeviceToDevice, ctx->stream));
     ctx->resident_count++;
     ctx->resident_bytes += cb + 3 * pb + mb;
+    return FGPU_OK;
+}
+
+// The same for a packed block (fgpu_load_slice_batch_packed): the block becomes the resident batch's codes / bad -- no copy --, and its
+// share of the budget was taken when it was made (fgpu_packed_acquire).  A block that was filled by the caller is checked against its
+// trailer first (error flag 64, reported by the pass' next synchronising call).
+int fgpu_stage_slice_load_packed(fgpu_ctx* ctx, PackedBlock* b) {
+    const uint64_t plane_stride = b->n_words + FGPU_PADW, pb = plane_stride * 8;
+    const uint64_t mb = ctx->slice_mercy ? MERCY_NT * pb : 0;
+    int rc;
+    if (b->state == 2 && (rc = fgpu_packed_digest(ctx, b, true))) return rc;
+    if (ctx->resident_count == ctx->resident.size()) ctx->resident.push_back(new ResidentBatch());
+    ResidentBatch& r = *ctx->resident[ctx->resident_count];
+    if ((rc = fgpu_ensure_b(ctx, &r.sure, pb)) || (rc = fgpu_ensure_b(ctx, &r.fail, pb)) || (mb && (rc = fgpu_ensure_b(ctx, &r.miss, mb)))) {
+        ctx->err = "load_slice_batch_packed: no device memory for the batch's planes (budget " + std::to_string(ctx->resident_budget) + " bytes): " + ctx->err;
+        return FGPU_ERR_NOMEM;
+    }
+    uint64_t* words = (uint64_t*)b->buf.p;
+    r.packed_codes = words;
+    r.packed_bad = words + 2 * plane_stride;
+    if ((rc = slice_mark_resolve(ctx, r.packed_codes, r.packed_bad, b->T, b->n_words, r))) return rc;
+    b->state = 3;
+    ctx->resident_count++;
     return FGPU_OK;
 }
 
@@ -1201,21 +1235,21 @@ int fgpu_stage_slice_mercy_probe(fgpu_ctx* ctx) {
     uint64_t* miss = (uint64_t*)r.miss.p;
     for (int nt = 0; nt < MERCY_NT; nt++)     // the planes are ORed in 16-byte granules: zero past their last word
         FGPU_HIP(hipMemsetAsync(miss + nt * plane_stride + r.n_words, 0, FGPU_PADW * 8, ctx->stream));
-    FGPU_LAUNCH("slice_mercy_probe", k_slice_mercy_probe, fgpu_grid(r.n_words * 64, 256), 256, (const uint64_t*)r.codes.p, (const uint64_t*)r.bad.p,
+    FGPU_LAUNCH("slice_mercy_probe", k_slice_mercy_probe, fgpu_grid(r.n_words * 64, 256), 256, (const uint64_t*)r.codes_p(), (const uint64_t*)r.bad_p(),
                 r.T, r.n_words, ctx->fd, slice_of(ctx), r.tb, (const uint64_t*)r.fail.p, miss, plane_stride, ctx->counters);
     ctx->slice_probe_owed = false;
-    return slice_fold_batch(ctx, ctx->slice_owed_span);
+    return slice_fold_batch(ctx, r.codes_p(), r.n_words, ctx->slice_owed_span);
 }
 
 int fgpu_stage_slice_commit(fgpu_ctx* ctx) {
     const Slice s = slice_of(ctx);
     for (uint64_t i = 0; i < ctx->resident_count; i++) {
         ResidentBatch& r = *ctx->resident[i];
-        FGPU_LAUNCH("slice_commit", k_slice_commit, fgpu_grid(r.n_words * 64, 256), 256, (const uint64_t*)r.codes.p, (const uint64_t*)r.bad.p, r.T,
+        FGPU_LAUNCH("slice_commit", k_slice_commit, fgpu_grid(r.n_words * 64, 256), 256, (const uint64_t*)r.codes_p(), (const uint64_t*)r.bad_p(), r.T,
                     r.n_words, ctx->fd, s, (const uint64_t*)r.fail.p, (uint64_t*)r.sure.p, ctx->counters);
         if (ctx->slice_mercy)     // the runs between solid k-mers, from the ORed miss planes and the `sure` plane just written
-            FGPU_LAUNCH("slice_mercy_commit", k_slice_mercy_commit, fgpu_grid(r.n_words, 256), 256, (const uint64_t*)r.codes.p,
-                        (const uint64_t*)r.bad.p, r.n_words, ctx->fd, s, (const uint64_t*)r.sure.p, (const uint64_t*)r.miss.p,
+            FGPU_LAUNCH("slice_mercy_commit", k_slice_mercy_commit, fgpu_grid(r.n_words, 256), 256, (const uint64_t*)r.codes_p(),
+                        (const uint64_t*)r.bad_p(), r.n_words, ctx->fd, s, (const uint64_t*)r.sure.p, (const uint64_t*)r.miss.p,
                         r.n_words + FGPU_PADW, ctx->counters);
     }
     return FGPU_OK;

@@ -235,8 +235,18 @@ int fgpu_host_batch_done(fgpu_ctx* ctx, const fgpu_reads* reads) {
     return FGPU_OK;
 }
 
-int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads) {
-    BatchBufs& bb = *ctx->cur;
+namespace {
+// where a batch's characters and offsets lie on the device, and how many bases it holds
+struct PackSrc {
+    const unsigned char* d_bases;
+    const uint64_t* d_offs;
+    const uint64_t* d_starts;
+    uint64_t total;
+};
+}  // namespace
+
+// The batch on the device: a device batch as it is (its total from fgpu_text_split, the caller, or read back), a host batch through a staging set
+static int pack_source(fgpu_ctx* ctx, const fgpu_reads* reads, PackSrc* src) {
     const uint64_t n = reads->n_reads;
     const unsigned char* d_bases;
     const uint64_t* d_offs;
@@ -299,11 +309,35 @@ int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads) {
         ctx->err = "batch exceeds max_batch_bases";
         return FGPU_ERR_CAPACITY;
     }
+    *src = PackSrc{d_bases, d_offs, d_starts, total};
+    return FGPU_OK;
+}
+
+// k_pack + k_pack_fix of n >= 1 reads into `codes` (2 x (n_words + FGPU_PADW) words) and `bad` (n_words + FGPU_PADW words); `readflag` is scratch
+static int pack_run(fgpu_ctx* ctx, const PackSrc& src, uint64_t n, uint64_t n_words, void* codes, void* bad, DevBuf* readflag) {
+    const uint64_t T = src.total + n;
+    int rc;
+    if ((rc = fgpu_ensure_b(ctx, readflag, n + 16))) return rc;
+    FGPU_HIP(hipMemsetAsync(readflag->p, 0, n, ctx->stream));
+    // four trips of 64 x 32 positions per wave: the bisection that opens a wave's run is paid once per 8192 positions
+    FGPU_LAUNCH("pack", k_pack, fgpu_grid((n_words + FGPU_PADW) / 2 + 1, 256), 256, src.d_bases, src.d_offs, src.d_starts, n, T, n_words, (uint64_t*)codes,
+                (uint32_t*)bad, (unsigned char*)readflag->p);
+    FGPU_LAUNCH("pack_fix", k_pack_fix, fgpu_blocks(n, 256), 256, src.d_bases, src.d_offs, src.d_starts, n, (unsigned long long*)codes,
+                (unsigned long long*)bad, (const unsigned char*)readflag->p, &ctx->counters->max_read_len, src.total, &ctx->counters->error_flags);
+    return FGPU_OK;
+}
+
+int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads) {
+    BatchBufs& bb = *ctx->cur;
+    const uint64_t n = reads->n_reads;
+    PackSrc src;
+    int rc = pack_source(ctx, reads, &src);
+    if (rc) return rc;
+    const uint64_t T = src.total + n;
     bb.T = T;
     bb.n_words = (T + 63) / 64;
     bb.n_reads = n;
-    bb.d_offs = d_offs;
-    int rc;
+    bb.d_offs = src.d_offs;
     if (n == 0) {   // nothing to pack; later stages see an empty stream
         if ((rc = fgpu_ensure_b(ctx, &bb.codes, 64))) return rc;
         if ((rc = fgpu_ensure_b(ctx, &bb.bad, 64))) return rc;
@@ -313,12 +347,106 @@ int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads) {
     }
     if ((rc = fgpu_ensure_b(ctx, &bb.codes, (2 * (bb.n_words + FGPU_PADW)) * 8))) return rc;
     if ((rc = fgpu_ensure_b(ctx, &bb.bad, (bb.n_words + FGPU_PADW) * 8))) return rc;
-    if ((rc = fgpu_ensure_b(ctx, &bb.readflag, n + 16))) return rc;
-    FGPU_HIP(hipMemsetAsync(bb.readflag.p, 0, n, ctx->stream));
-    // four trips of 64 x 32 positions per wave: the bisection that opens a wave's run is paid once per 8192 positions
-    FGPU_LAUNCH("pack", k_pack, fgpu_grid((bb.n_words + FGPU_PADW) / 2 + 1, 256), 256, d_bases, d_offs, d_starts, n, T, bb.n_words, (uint64_t*)bb.codes.p,
-                (uint32_t*)bb.bad.p, (unsigned char*)bb.readflag.p);
-    FGPU_LAUNCH("pack_fix", k_pack_fix, fgpu_blocks(n, 256), 256, d_bases, d_offs, d_starts, n, (unsigned long long*)bb.codes.p,
-                (unsigned long long*)bb.bad.p, (const unsigned char*)bb.readflag.p, &ctx->counters->max_read_len, total, &ctx->counters->error_flags);
+    return pack_run(ctx, src, n, bb.n_words, bb.codes.p, bb.bad.p, &bb.readflag);
+}
+
+// ---- packed blocks of a sliced pass (fgpu_load_slice_pack / _expect / _batch_packed) -------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ uint64_t digest_mix(uint64_t word, uint64_t index) {      // splitmix64's finaliser over the word and its place
+    uint64_t x = word ^ ((index + 1) * 0x9E3779B97F4A7C15ULL);
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+    return x ^ (x >> 31);
+}
+
+// sum over the block's words of mix(word, index): one lane per word (grid-stride), a wave-64 reduction, one atomic per wave.  A sum, so
+// any grid gives the same value.
+__global__ void __launch_bounds__(256) k_packed_digest(const uint64_t* __restrict__ words, uint64_t n, unsigned long long* __restrict__ sum) {
+    uint64_t acc = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) acc += digest_mix(words[i], i);
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(sum, (unsigned long long)acc);
+}
+
+// a block packed here: its trailer's length (the digest has been summed into trailer[0])
+__global__ void k_packed_seal(unsigned long long* trailer, uint64_t T) { trailer[1] = T; }
+
+// a block that came from elsewhere: the digest of what arrived and the length the caller expects against the trailer that travelled with it
+__global__ void k_packed_verify(const unsigned long long* __restrict__ trailer, const unsigned long long* __restrict__ sum, uint64_t T,
+                                unsigned long long* error_flags) {
+    if (trailer[0] != *sum || trailer[1] != T) atomicOr(error_flags, 64ULL);
+}
+
+}  // namespace
+
+// A block for a batch of T stream positions out of the pass' pool (its buffer recycled from an earlier pass where there is one), counted
+// against the resident budget NOW with everything the loaded batch will keep beside it (fail, sure, under --mercy four miss planes).
+int fgpu_packed_acquire(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, int state, const char* who, PackedBlock** out) {
+    const uint64_t n_words = (T + 63) / 64, pb = (n_words + FGPU_PADW) * 8;
+    const uint64_t need = 5 * pb + (ctx->slice_mercy ? 4 * pb : 0);
+    if (!ctx->resident_open || ctx->resident_bytes + need > ctx->resident_budget) {
+        ctx->err = std::string(who) + ": a batch of " + std::to_string(T) + " stream positions needs " + std::to_string(need) +
+                   " bytes of the budget for resident batches (" + std::to_string(ctx->resident_budget) + " bytes, " + std::to_string(ctx->resident_bytes) +
+                   " in use; FGPU_FLAG_NO_RESIDENT sets it to 0): a sliced pass keeps every batch" +
+                   (ctx->slice_mercy ? ", under --mercy with four miss planes (9 bits per stream position)" : "");
+        return FGPU_ERR_NOMEM;
+    }
+    PackedBlock* b = nullptr;
+    const uint64_t bytes = fgpu_packed_bytes(n_words);
+    for (PackedBlock* q : ctx->packed)          // the smallest free buffer that holds it, else any free one (fgpu_ensure grows it)
+        if (q->state == 0 && (!b || (q->buf.bytes >= bytes && (b->buf.bytes < bytes || q->buf.bytes < b->buf.bytes)))) b = q;
+    if (!b) {
+        b = new PackedBlock();
+        ctx->packed.push_back(b);
+    }
+    if (int rc = fgpu_ensure(ctx, &b->buf, bytes)) {
+        ctx->err = std::string(who) + ": no device memory for the packed block (budget " + std::to_string(ctx->resident_budget) + " bytes): " + ctx->err;
+        return rc;
+    }
+    b->T = T;
+    b->n_words = n_words;
+    b->n_reads = n_reads;
+    b->state = state;
+    ctx->resident_bytes += need;
+    *out = b;
+    return FGPU_OK;
+}
+
+// verify == false: sum the digest into the block's trailer and write its length; true: sum it aside and compare both with the trailer
+int fgpu_packed_digest(fgpu_ctx* ctx, const PackedBlock* b, bool verify) {
+    const uint64_t n = 3 * (b->n_words + FGPU_PADW);
+    unsigned long long* trailer = (unsigned long long*)b->buf.p + n;
+    unsigned long long* sum = trailer;
+    if (verify) {
+        if (int rc = fgpu_ensure(ctx, &ctx->packed_digest, 64)) return rc;
+        sum = (unsigned long long*)ctx->packed_digest.p;
+    }
+    FGPU_HIP(hipMemsetAsync(sum, 0, 8, ctx->stream));
+    FGPU_LAUNCH("packed_digest", k_packed_digest, fgpu_grid(n, 256), 256, (const uint64_t*)b->buf.p, n, sum);
+    if (verify) FGPU_LAUNCH("packed_verify", k_packed_verify, 1, 1, (const unsigned long long*)trailer, (const unsigned long long*)sum, b->T, &ctx->counters->error_flags);
+    else FGPU_LAUNCH("packed_seal", k_packed_seal, 1, 1, trailer, b->T);
+    return FGPU_OK;
+}
+
+// fgpu_load_slice_pack: the batch packed straight into a block of the pass; *out = nullptr for a batch without reads.  Nothing of the batch
+// in hand (ctx->cur) is touched: a mercy pass may still owe its latest batch the probe.
+int fgpu_stage_pack_block(fgpu_ctx* ctx, const fgpu_reads* reads, PackedBlock** out) {
+    *out = nullptr;
+    const uint64_t n = reads->n_reads;
+    if (n == 0) return FGPU_OK;
+    PackSrc src;
+    int rc = pack_source(ctx, reads, &src);
+    if (rc) return rc;
+    PackedBlock* b = nullptr;
+    if ((rc = fgpu_packed_acquire(ctx, src.total + n, n, 1, "load_slice_pack", &b))) return rc;
+    uint64_t* words = (uint64_t*)b->buf.p;
+    if ((rc = pack_run(ctx, src, n, b->n_words, words, words + 2 * (b->n_words + FGPU_PADW), &ctx->cur->readflag)) ||
+        (rc = fgpu_packed_digest(ctx, b, false))) {
+        b->state = 0;
+        return rc;
+    }
+    *out = b;
     return FGPU_OK;
 }

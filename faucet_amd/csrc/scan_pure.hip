@@ -572,15 +572,17 @@ int fgpu_stage_scan_pure(fgpu_ctx* ctx, uint64_t* n_pieces) {
     const unsigned wgrid = fgpu_grid(bb.n_words, 256);            // kernels with one thread per 64-position word
     if ((rc = fgpu_util_count_segments(ctx, ctx->fd.k + 2 * ctx->fd.j + 1))) return rc;
     // the load pass' batch of the same index, if it was kept and has the same shape: compare the streams on the device
-    const ResidentBatch* kept = ctx->scan_batch_index < ctx->resident_count ? ctx->resident[ctx->scan_batch_index] : nullptr;
+    // (of the index fgpu_scan_resident_base moved it to: a rank whose scan shard begins in the middle of the batches its sliced pass loaded)
+    const uint64_t kept_index = ctx->scan_resident_base + ctx->scan_batch_index;
+    const ResidentBatch* kept = kept_index < ctx->resident_count ? ctx->resident[kept_index] : nullptr;
     ctx->scan_batch_index++;
     if (kept && (kept->T != bb.T || kept->n_words != bb.n_words)) kept = nullptr;
     if (kept) {
         if ((rc = fgpu_ensure_b(ctx, &bb.same, 64))) return rc;
         FGPU_HIP(hipMemsetAsync(bb.same.p, 0x01, 4, ctx->stream));
         const uint64_t ncw = 2 * bb.n_words;   // 32 bases per code word
-        FGPU_LAUNCH("scan_same", k_scan_same, fgpu_grid(ncw, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)kept->codes.p, ncw,
-                    (const uint64_t*)bb.bad.p, (const uint64_t*)kept->bad.p, bb.n_words, (uint32_t*)bb.same.p);
+        FGPU_LAUNCH("scan_same", k_scan_same, fgpu_grid(ncw, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)kept->codes_p(), ncw,
+                    (const uint64_t*)bb.bad.p, (const uint64_t*)kept->bad_p(), bb.n_words, (uint32_t*)bb.same.p);
     }
     FGPU_LAUNCH("scan_valid", k_scan_valid, grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p, bb.T, bb.n_words, ctx->fd,
                 (const uint32_t*)ctx->bloo2, kept ? (const uint64_t*)kept->sure.p : (const uint64_t*)nullptr,

@@ -546,7 +546,7 @@ int main_sharded(const Options& o, const fgpu_params& prm, uint64_t tai, PhaseCl
         printf("Weights before load: %f, %f \n", 0.0f, 0.0f);
         ShardLoadResult lr;
         if (int rc = run.load(o.read_load_file, &lr)) { fprintf(stderr, "load pass failed (%d): %s\n", rc, run.error().c_str()); return 2; }
-        clk.mark(lr.fixup ? "pass 1 (shards, fix-up protocol)" : "pass 1 (shards, presence protocol)");
+        clk.mark(lr.slices ? "pass 1 (shards, filter slices)" : lr.fixup ? "pass 1 (shards, fix-up protocol)" : "pass 1 (shards, presence protocol)");
         fprintf(stdout, "\rreads consumed: %lld", (long long)lr.stats.reads_processed);
         printf("\n");
         printf("Weights after load: %f, %f \n", lr.w1, lr.w2);

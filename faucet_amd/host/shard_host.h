@@ -11,7 +11,10 @@
 //   pass 1   fix-up protocol (a shard that stays in HBM, at most 4 hash functions): every rank loads its shard alone
 //            (FGPU_LOAD_SHARD_TIMES) -> exclusive prefix-OR of the shards' bloo1 over ranks -> fgpu_load_fixup against that prefix on
 //            ranks > 0 -> OR-allreduce of bloo2;  presence protocol (otherwise, and with --mercy): presence bitmap of the shard ->
-//            exclusive prefix-OR = the carried-in bloo1 -> ordered load on it -> OR-allreduce of bloo2
+//            exclusive prefix-OR = the carried-in bloo1 -> ordered load on it -> OR-allreduce of bloo2;  filter slices
+//            (FAUCET_SHARD_PROTOCOL=slices, opt-in): every rank packs its own shard's batches and sends the packed blocks to the others, all
+//            load the whole stream into their slice of the bit positions -> OR-allreduce of the batches' fail (miss) planes -> commit ->
+//            all-gather of both filters by the slices' byte ranges (load_slices below)
 //   pass 2   rank 0 streams its shard and shows the others its junction table after a quarter of it (the preview their pure stage uses);
 //            ranks > 0 run the pure stage of their shard meanwhile (fgpu_scan_prepare), then take the table, the counters and the two
 //            pair filters from the rank below, walk, and hand all four on.  The last rank holds the run's junction map and pair filters.
@@ -26,8 +29,24 @@
 #include <thread>
 #include <vector>
 
+#include "batch_board.h"
 #include "faucet_gpu.h"
 #include "text_source.h"
+
+// The sliced pass' entry points are referred to WEAKLY: a library that defines them (libfaucet_gpu.so) resolves them as usual; linked against
+// an implementation of the ABI that answers only the read-shard protocols they are null, and FAUCET_SHARD_PROTOCOL=slices is refused.
+#pragma weak fgpu_load_slice_begin
+#pragma weak fgpu_load_slice_mercy_begin
+#pragma weak fgpu_load_slice_pack
+#pragma weak fgpu_load_slice_expect
+#pragma weak fgpu_load_slice_batch_packed
+#pragma weak fgpu_load_slice_plane
+#pragma weak fgpu_load_slice_mercy_probe
+#pragma weak fgpu_load_slice_mercy_planes
+#pragma weak fgpu_load_slice_commit
+#pragma weak fgpu_load_slice_end
+#pragma weak fgpu_group_allgather
+#pragma weak fgpu_scan_resident_base
 
 namespace faucet_host {
 
@@ -47,6 +66,7 @@ struct ShardLoadResult {
     fgpu_load_stats stats;                // summed over the shards = the sequential run's
     float w1 = 0, w2 = 0;                 // Bloom::weight of the run's bloo1 / bloo2
     bool fixup = false;
+    bool slices = false;                  // the pass ran by filter slices (FAUCET_SHARD_PROTOCOL=slices)
 };
 
 struct ShardScanResult {
@@ -140,6 +160,9 @@ public:
             if (fgpu_load_fixup_state(ctx_[(size_t)r], nullptr, &b) != FGPU_OK) b = 0;
             budget = std::min(budget, b);
         }
+        if (const char* e = getenv("FAUCET_SHARD_PROTOCOL"))
+            if (!strcmp(e, "slices")) return load_slices(path, cuts, budget, out);
+        sliced_counts_.clear();
         const char* force_planes = getenv("FAUCET_SHARD_PLANES");
         const bool short_shards = largest < 0xFFF00000ULL - (1ULL << 24) && !(force_planes && force_planes[0] == '1' && o_.prm.n_hash <= 4);   // a shard's positions (<= its bytes) fit one 32-bit clock
         bool fixup = !o_.mercy && (short_shards || o_.prm.n_hash <= 4) && largest + (64ULL << 20) < budget;
@@ -224,6 +247,158 @@ public:
         return FGPU_OK;
     }
 
+    // ---- pass 1 by FILTER SLICES ("the sliced pass in the C++ host"): rank r owns the filter bits of slice r and loads the
+    // WHOLE stream into them.  Each batch is read, split and packed by the owner of its read shard only (fgpu_load_slice_pack) and travels to the
+    // other ranks in its packed form, 3 bits per stream position; the board (batch_board.h) tells every rank what to expect from whom, in file
+    // order, so that all ranks load the same batches and make the same sequence of collectives.
+    int load_slices(const std::string& path, const std::vector<uint64_t>& cuts, uint64_t budget, ShardLoadResult* out) {
+        const int n = o_.n_ranks;
+        if (!slices_linked()) {
+            error_ = "FAUCET_SHARD_PROTOCOL=slices: the library this program is linked against lacks the entry points of the sliced pass "
+                     "(fgpu_load_slice_*, fgpu_group_allgather, fgpu_scan_resident_base)";
+            return FGPU_ERR_STATE;
+        }
+        if (const char* e = getenv("FAUCET_DEBUG_SLICES_BUDGET")) budget = strtoull(e, nullptr, 10);      // tests: "the ranks keep this many bytes resident"
+        // every rank keeps every batch: 5 bits per stream position (codes, bad, fail, sure), 9 with the four miss planes of --mercy; a stream
+        // position per input byte is the upper bound (headers and quality lines only lower it)
+        const uint64_t input = cuts.back(), bits = o_.mercy ? 9 : 5, need = input / 8 * bits + (input % 8 * bits + 7) / 8;
+        if (need > budget) {
+            error_ = "FAUCET_SHARD_PROTOCOL=slices: every rank keeps the whole input resident in its packed form: " + std::to_string(input) +
+                     " bytes of input x " + (o_.mercy ? "9/8 (--mercy)" : "5/8") + " = " + std::to_string(need) + " bytes, the ranks' smallest budget for resident batches is " +
+                     std::to_string(budget) + " bytes";
+            return FGPU_ERR_NOMEM;
+        }
+        // slice bounds: tai bits over n ranks in units of 512 bits (64 bytes), the last ones short or empty
+        const uint64_t nbytes = o_.prm.tai / 8;
+        std::vector<uint64_t> bounds((size_t)n + 1);
+        {
+            uint64_t step = (nbytes + (uint64_t)n - 1) / (uint64_t)n;
+            step = (step + 63) & ~63ULL;
+            for (int q = 0; q <= n; q++) bounds[(size_t)q] = std::min<uint64_t>((uint64_t)q * step, nbytes);
+        }
+        BatchBoard board(n);
+        std::vector<fgpu_load_stats> st((size_t)n);
+        std::vector<uint64_t> counts((size_t)n, 0);
+        float w1 = 0, w2 = 0;
+        int rc = run_ranks([&](int r) -> int {
+            const int rc_rank = slice_rank(r, path, cuts, bounds, &board, &st[(size_t)r], r == 0 ? &counts : nullptr, &w1, &w2);
+            if (rc_rank != FGPU_OK) board.abort();           // (ranks that wait for a batch of this one wake up and fail)
+            return rc_rank;
+        });
+        if (rc != FGPU_OK) return rc;
+        sliced_counts_ = counts;
+        out->stats = st[0];                                  // the stats of a sliced pass are the whole run's on every rank: one rank's, not a sum
+        out->w1 = w1;
+        out->w2 = w2;
+        out->fixup = false;
+        out->slices = true;
+        return FGPU_OK;
+    }
+
+private:
+    static bool slices_linked() {
+        return fgpu_load_slice_begin && fgpu_load_slice_mercy_begin && fgpu_load_slice_pack && fgpu_load_slice_expect && fgpu_load_slice_batch_packed &&
+               fgpu_load_slice_plane && fgpu_load_slice_mercy_probe && fgpu_load_slice_mercy_planes && fgpu_load_slice_commit && fgpu_load_slice_end &&
+               fgpu_group_allgather && fgpu_scan_resident_base;
+    }
+
+    // one rank of load_slices
+    int slice_rank(int r, const std::string& path, const std::vector<uint64_t>& cuts, const std::vector<uint64_t>& bounds, BatchBoard* board,
+                   fgpu_load_stats* stats, std::vector<uint64_t>* counts, float* w1, float* w2) {
+        fgpu_ctx* c = ctx_[(size_t)r];
+        const int n = o_.n_ranks;
+        const double t0 = now_ms();
+        // 1  open the pass on the own slice
+        RANK_CHECK(o_.mercy ? fgpu_load_slice_mercy_begin(c, bounds[(size_t)r] * 8, bounds[(size_t)r + 1] * 8)
+                            : fgpu_load_slice_begin(c, bounds[(size_t)r] * 8, bounds[(size_t)r + 1] * 8));
+        // 2  publish: pack the own shard's batches, post them, send them.  Nothing here waits for another rank.  Under --mercy the sends wait
+        //    for the batch's turn in step 3: there every batch is followed by collectives, and point-to-point calls pair up per (source,
+        //    destination) in the order they are made -- a block sent now would meet the receive of an earlier batch's plane.
+        std::vector<fgpu_packed> own;
+        RANK_TRY(for_each_batch(r, path, cuts, [&](const fgpu_reads* b) -> int {
+            fgpu_packed pk;
+            const int rc = fgpu_load_slice_pack(c, b, &pk);
+            if (rc != FGPU_OK) return rc;
+            own.push_back(pk);
+            BoardBatch bb;
+            bb.T = pk.T;
+            bb.n_reads = pk.n_reads;
+            if (!board->post(r, bb)) { err_[(size_t)r] = "the run was aborted (another rank failed)"; return FGPU_ERR_STATE; }
+            if (!o_.mercy && pk.block_dev)
+                for (int q = 0; q < n; q++)
+                    if (q != r) GROUP_CHECK(fgpu_group_send_async(group_, r, q, pk.block_dev, pk.nbytes));
+            return FGPU_OK;
+        }, nullptr));
+        board->close(r);
+        const double t1 = now_ms();
+        // 3  consume in file order: shard 0's batches, shard 1's, ...; a peer's batch is received into a block of its size
+        double t_exchange = 0;
+        uint64_t loaded = 0;                                  // non-empty batches so far = the index of the next one's planes
+        for (int s = 0; s < n; s++) {
+            uint64_t in_shard = 0;
+            for (uint64_t j = 0;; j++) {
+                BoardBatch bb;
+                const BatchBoard::Wait w = board->wait(s, j, &bb);
+                if (w == BatchBoard::ABORTED) { err_[(size_t)r] = "the run was aborted while this rank waited for a batch of shard " + std::to_string(s); return FGPU_ERR_STATE; }
+                if (w == BatchBoard::CLOSED) break;
+                fgpu_packed pk;
+                if (s == r) {
+                    pk = own[(size_t)j];
+                    if (o_.mercy && pk.block_dev)
+                        for (int q = 0; q < n; q++)
+                            if (q != r) GROUP_CHECK(fgpu_group_send_async(group_, r, q, pk.block_dev, pk.nbytes));
+                } else {
+                    RANK_CHECK(fgpu_load_slice_expect(c, bb.T, bb.n_reads, &pk));
+                    if (pk.block_dev) GROUP_CHECK(fgpu_group_recv(group_, r, s, pk.block_dev, pk.nbytes));
+                }
+                RANK_CHECK(fgpu_load_slice_batch_packed(c, &pk));
+                if (!pk.block_dev) continue;
+                if (o_.mercy) {                               // the lockstep of a mercy pass: the batch's fail plane over all ranks, then its probe
+                    const double tx = now_ms();
+                    void* plane = nullptr;
+                    uint64_t pb = 0;
+                    RANK_CHECK(fgpu_load_slice_plane(c, loaded, &plane, &pb));
+                    GROUP_CHECK(fgpu_group_or_allreduce(group_, r, plane, pb));
+                    RANK_CHECK(fgpu_load_slice_mercy_probe(c));
+                    t_exchange += now_ms() - tx;
+                }
+                loaded++;
+                in_shard++;
+            }
+            if (counts) (*counts)[(size_t)s] = in_shard;
+        }
+        const double t2 = now_ms();
+        // 4  the planes over all ranks (the same batches on every rank: the same sequence of collectives), commit, the filters by slices
+        for (uint64_t i = 0; i < loaded; i++) {
+            void* plane = nullptr;
+            uint64_t pb = 0;
+            RANK_CHECK(o_.mercy ? fgpu_load_slice_mercy_planes(c, i, &plane, &pb) : fgpu_load_slice_plane(c, i, &plane, &pb));
+            GROUP_CHECK(fgpu_group_or_allreduce(group_, r, plane, pb));
+        }
+        const double t3 = now_ms();
+        RANK_CHECK(fgpu_load_slice_commit(c));
+        RANK_CHECK(fgpu_load_slice_end(c, stats));
+        const double t4 = now_ms();
+        for (int which = FGPU_BLOO1; which <= FGPU_BLOO2; which++) {
+            void* bits = nullptr;
+            uint64_t nb = 0;
+            RANK_CHECK(fgpu_bloom_devptr(c, which, &bits, &nb));
+            GROUP_CHECK(fgpu_group_allgather(group_, r, bits, nb, bounds.data()));
+        }
+        GROUP_CHECK(fgpu_group_flush(group_, r));
+        if (r == n - 1) {
+            RANK_CHECK(fgpu_bloom_weight(c, FGPU_BLOO1, w1));
+            RANK_CHECK(fgpu_bloom_weight(c, FGPU_BLOO2, w2));
+        } else {
+            RANK_CHECK(fgpu_synchronize(c));
+        }
+        tell(r, "pass 1 (filter slices): pack + publish %.1f ms, load %.1f ms, exchange of the planes %.1f ms, commit %.1f ms, gather of the filters %.1f ms",
+             t1 - t0, t2 - t1 - t_exchange, t_exchange + (t3 - t2), t4 - t3, now_ms() - t4);
+        return FGPU_OK;
+    }
+
+public:
+
     // ---- pass 2 (ReadScanner::scanReads, src/ReadScanner.cpp:284-359): afterwards the last rank holds the junction map and the pair filters
     int scan(const std::string& path, ShardScanResult* out) {
         std::vector<uint64_t> cuts;
@@ -247,6 +422,12 @@ public:
             if (short_pairs) RANK_CHECK(fgpu_scan_short_pairs(c, o_.short_tai, o_.short_hashes, 0));
             if (o_.paired_ends)
                 RANK_CHECK(long_filter ? fgpu_scan_long_pairs(c, o_.long_tai, o_.long_hashes, FGPU_LONG_PAIRS_FILTER) : fgpu_scan_long_pairs(c, 0, 0, FGPU_LONG_PAIRS_COUNT));
+            if (!sliced_counts_.empty()) {
+                // after a sliced pass 1 this rank holds the batches of the whole stream: its own shard's begin behind those of the shards below
+                uint64_t below = 0;
+                for (int q = 0; q < r; q++) below += sliced_counts_[(size_t)q];
+                RANK_CHECK(fgpu_scan_resident_base(c, below));
+            }
             RANK_CHECK(fgpu_scan_begin(c));
             fgpu_scan_stats st;
             memset(&st, 0, sizeof(st));
@@ -294,7 +475,7 @@ public:
                 if (!shown) RANK_TRY(show());                 // (a shard without batches still owes the others their preview)
                 if (!shown_late) RANK_TRY(show_late());
                 RANK_CHECK(fgpu_scan_end(c, &st));
-                tell(r, "pass 2: first shard streamed in %.1f ms", now_ms() - t0);
+                tell(r, "pass 2: first shard streamed in %.1f ms; valid_reused %llu", now_ms() - t0, (unsigned long long)st.valid_reused);
             } else {
                 // pure stage while the lower shards walk.  It does not wait for the preview: batches prepared before it arrives see an empty table
                 // (every junction test evaluated), the others the preview.
@@ -340,7 +521,8 @@ public:
                 RANK_CHECK(fgpu_scan_import_table(c, table_in, n_in, &carried));   // (takes the place of the preview)
                 RANK_CHECK(fgpu_scan_walk_prepared(c));
                 RANK_CHECK(fgpu_scan_end(c, &st));
-                tell(r, "pass 2: pure stage %.1f ms, waited %.1f ms for the table, import + walk %.1f ms", t1 - t0, t2 - t1, now_ms() - t2);
+                tell(r, "pass 2: pure stage %.1f ms, waited %.1f ms for the table, import + walk %.1f ms; valid_reused %llu", t1 - t0, t2 - t1, now_ms() - t2,
+                     (unsigned long long)st.valid_reused);
             }
             if (o_.paired_ends) RANK_CHECK(fgpu_scan_long_pairs_download(c, nullptr, 0, &empty[(size_t)r], &not_empty[(size_t)r]));
             if (r < n - 1) {
@@ -517,6 +699,7 @@ private:
     std::vector<Announce> chain_;
     std::vector<Announce> late_;      // the table a rank was handed, passed on to the rank above as a fresher preview
     std::vector<std::vector<void*>> graveyard_{64};
+    std::vector<uint64_t> sliced_counts_;   // after a sliced pass 1: non-empty batches per read shard (pass 2 finds its own among the resident ones)
     int vote_count_ = 0;
     bool vote_all_ = true, vote_result_ = false;
     uint64_t vote_gen_ = 0;

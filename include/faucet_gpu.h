@@ -270,6 +270,41 @@ int fgpu_load_slice_mercy_planes(fgpu_ctx* ctx, uint64_t batch, void** miss_dev,
  * [5] k-mers of those runs. */
 int fgpu_diag_slice_mercy(fgpu_ctx* ctx, uint64_t out[6]);
 
+/* ---- the sliced pass from PACKED batches: made once, moved device to device, loaded from the packed form ------------------------------------
+ * Under filter slices every rank needs every batch, but only one rank should read, split and pack it.  A packed block is ONE contiguous
+ * device buffer: the codes plane (2 bits per stream position, 2 x (n_words + 8) 64-bit words), the bad plane (1 bit per position, n_words + 8
+ * words), n_words = ceil(T / 64), and a 16-byte trailer {digest, T} -- nbytes is a function of T alone, so a peer that knows T can receive it.
+ *
+ *     owner of the batch:   fgpu_load_slice_pack(reads, &p);           send p.block_dev, p.nbytes to the peers (fgpu_group_send_async, ...)
+ *     every other rank:     fgpu_load_slice_expect(T, n_reads, &p);    fill p.block_dev (fgpu_group_recv, fgpu_device_copy, ...)
+ *     every rank, in the stream's file order:   fgpu_load_slice_batch_packed(&p);   = fgpu_load_slice_batch of the same reads
+ *
+ * All three only inside a sliced pass (plain or mercy) before its commit, stream-ordered on the context's stream, none waits for the device;
+ * they may be mixed with fgpu_load_slice_batch.  The block becomes the resident batch's codes / bad -- no second copy: 5 (9 under --mercy)
+ * bits per position as before --, is counted against the resident budget when it is MADE, and stays the pass' until the next sliced pass begins.
+ * The digest is an order-independent 64-bit sum over the block's words; _batch_packed recomputes it for a block from _expect and compares it
+ * and T with the trailer that travelled with the block: in a protocol that pairs sends and receives by order, a block in the wrong slot would
+ * otherwise be a silently wrong filter.  A mismatch is reported as FGPU_ERR_ARG by the pass' next synchronising call (fgpu_load_slice_end at
+ * the latest), as a wrong fgpu_reads.total_bases is.
+ * FGPU_ERR_STATE: outside a sliced pass or after its commit; _batch_packed of a block that is not of this pass' _pack / _expect, or has been
+ * loaded already, or while a mercy pass owes its latest batch the probe.  FGPU_ERR_ARG: null arguments; _expect with n_reads > T, T > 0 without
+ * reads or T beyond max_batch_bases; a description whose T / nbytes / n_reads are not the block's.  FGPU_ERR_NOMEM: the batch does not fit the
+ * resident budget (fgpu_load_fixup_state; the message names the numbers) or the device has no memory for it. */
+typedef struct {
+    void*    block_dev;   /* the block on the context's device; NULL for a batch without reads (nbytes = T = 0) */
+    uint64_t nbytes;      /* 24 * (ceil(T / 64) + 8) + 16 */
+    uint64_t T;           /* stream positions: bases + one separator per read */
+    uint64_t n_reads;
+} fgpu_packed;
+/* Packs now, loads later: k_pack / k_pack_fix straight into a block of the pass, its digest and T into the trailer.  T has to be known without
+ * asking the device for the call not to wait: batches from fgpu_text_split, or with total_bases (host batches: always). */
+int fgpu_load_slice_pack(fgpu_ctx* ctx, const fgpu_reads* reads, fgpu_packed* out);
+/* An empty block of the same layout for a batch that is packed elsewhere; the caller fills all of its nbytes before it is loaded. */
+int fgpu_load_slice_expect(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, fgpu_packed* out);
+/* mark + resolve of that batch against the slice, exactly as fgpu_load_slice_batch behind its packing: segment count, epochs, fail plane, a
+ * mercy pass' "probe owed"; the batch is the pass' next one (fgpu_load_slice_plane counts it), reads_processed grows by n_reads. */
+int fgpu_load_slice_batch_packed(fgpu_ctx* ctx, const fgpu_packed* b);
+
 /* filters: raw bit arrays, tai/8 bytes, exactly the .bloom file body (utils/Bloom.cpp:571-587) */
 int fgpu_bloom_download(fgpu_ctx* ctx, int which, uint8_t* host_out, uint64_t nbytes);
 /* The same copy, started now and finished by fgpu_bloom_download_wait: it runs on its own copy stream behind the work
@@ -313,6 +348,12 @@ int fgpu_text_split(fgpu_ctx* ctx, const char* text, uint64_t nbytes, int text_o
  * positions) for filters of 2^32 bits and more.  The larger windows only buy speed on thin coverage: where a quarter of the free device
  * memory does not hold them (several contexts on one device, a smaller device) the bound is halved, down to 2^26 positions, before
  * FGPU_ERR_NOMEM is returned. */
+/* Between the passes: batch i of the next scan pairs with the load pass' resident batch first_batch + i instead of i, for the reuse of the
+ * `sure` planes (fgpu_scan_stats.valid_reused).  After a sliced pass a rank holds the batches of the WHOLE stream while its scan shard begins in
+ * the middle of them; without this call the scan compares against the wrong batches -- safely (the streams are compared word for word before
+ * anything is reused), but the reuse is lost.  Empty batches are not counted (they keep nothing).  0 again at the next load pass.
+ * FGPU_ERR_STATE while a pass is open. */
+int fgpu_scan_resident_base(fgpu_ctx* ctx, uint64_t first_batch);
 int fgpu_scan_begin(fgpu_ctx* ctx);
 /* Pure stage + ordered walk for one batch, in file order. */
 int fgpu_scan_batch(fgpu_ctx* ctx, const fgpu_reads* reads);
@@ -458,6 +499,11 @@ int         fgpu_group_barrier(fgpu_group* g, int rank);       /* host threads o
  * slice q of everybody and reduces it with the OR kernel -- then all-gather of the reduced slices: 2 (N-1)/N of a bitmap crosses each
  * rank's links per call.  RCCL has no bitwise-OR reduction (rccl.h: ncclSum/Prod/Max/Min/Avg).  bloo2 after pass 1. */
 int fgpu_group_or_allreduce(fgpu_group* g, int rank, void* bitmap_dev, uint64_t nbytes);
+/* buf := every rank's part of it, in place: bounds[0..N] are byte offsets into buf, ascending, bounds[N] <= nbytes, the same on all ranks; rank q
+ * holds [bounds[q], bounds[q+1]) and afterwards every rank holds [bounds[0], bounds[N]).  Empty ranges are allowed; no alignment is asked for.  The
+ * all-gather half of fgpu_group_or_allreduce with the caller's ranges: the filters after a sliced pass 1, by the slices' byte ranges.
+ * FGPU_ERR_ARG: null arguments, bounds that descend or pass nbytes. */
+int fgpu_group_allgather(fgpu_group* g, int rank, void* buf_dev, uint64_t nbytes, const uint64_t* bounds);
 /* out := OR of the bitmaps of all ranks below `rank` (zero on rank 0); bitmap is left as it is.  The carried-in bloo1 of a read shard
  * (what the sequential run has in bloo1 when it reaches the shard). */
 int fgpu_group_exclusive_prefix_or(fgpu_group* g, int rank, const void* bitmap_dev, void* out_dev, uint64_t nbytes);
