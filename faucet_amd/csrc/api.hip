@@ -2,6 +2,7 @@
 //
 // Thin: argument checks, state machine (idle -> loading -> idle -> scanning -> idle), buffer management and the
 // order in which the stages of pack.hip / load.hip / scan_pure.hip / scan_walk.hip / scan_harvest.hip are put on the stream.
+// (The fgpu_load_slice_* entry points of the filter-sliced pass 1 live with its stages, in load_slices.hip.)
 // There is no CPU path in this library: with no usable gfx950 device fgpu_create fails with FGPU_ERR_HIP.
 #include <cstdio>
 #include <algorithm>
@@ -154,7 +155,7 @@ static int sync_all(fgpu_ctx* ctx) {
     return FGPU_OK;
 }
 
-static int pull_counters(fgpu_ctx* ctx) {
+int fgpu_pull_counters(fgpu_ctx* ctx) {
     if (int rc = fgpu_bg_join(ctx)) return rc;
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->wstream));
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->cstream));
@@ -183,6 +184,60 @@ static bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 static void journal_recycle(fgpu_ctx* ctx);
 static int journal_add(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads);
 static int scan_replay(fgpu_ctx* ctx);
+
+// ---- pass 1: what the plain pass' entry points (below) and the sliced pass' (load_slices.hip) share -----------------------------------------
+int fgpu_check_reads(fgpu_ctx* ctx, const fgpu_reads* r) {
+    if (!r || (r->n_reads && (!r->bases || !r->offsets))) { ctx->err = "null read batch"; return FGPU_ERR_ARG; }
+    return FGPU_OK;
+}
+
+// What a plain and a sliced load pass share at their beginning: how the carry is kept up to date and when an epoch is closed ...
+void fgpu_load_pass_policy(fgpu_ctx* ctx) {
+    static const char* carry_env = getenv("FGPU_CARRY_MODE");   // "sweep" / "set": measurement aid
+    ctx->carry_by_set = carry_env ? carry_env[0] == 's' && carry_env[1] == 'e' : ctx->prm.tai == (1ULL << 31);
+    ctx->epoch_positions = ctx->swept_positions = 0;
+    ctx->sweep_num = ctx->sweep_den = 1;
+    const char* sweep_env = getenv("FGPU_SWEEP_RATIO");   // "num/den"; "0/1" = after every batch: measurement aid
+    if (sweep_env) {
+        unsigned n = 1, d = 1;
+        if (sscanf(sweep_env, "%u/%u", &n, &d) == 2 && d > 0) { ctx->sweep_num = n; ctx->sweep_den = d; }
+    }
+    {   // a sweep streams tai x 4 bytes whatever the epoch holds: not before the epoch's accesses are tai / 16 (FGPU_SWEEP_MIN_FRAC; 0 = no such
+        // bar, rounds 1-4).  The first sweeps of a pass on large filters came after a quarter-size ramp batch and brought the carry almost nothing:
+        // one rank's own load of config 4 on 8 GPUs 350 -> 337 ms (6 sweeps -> 4), configs 2, 4, 5 whole unchanged (profiles/r05_sweep_policy.txt)
+        const char* e = getenv("FGPU_SWEEP_MIN_FRAC");
+        const double frac = e ? atof(e) : 16.0;
+        ctx->sweep_min = frac > 0.0 ? (uint64_t)((double)ctx->prm.tai / frac / (double)std::max(1, ctx->prm.n_hash)) : 0;
+    }
+}
+// ... and the counters of the pass
+int fgpu_load_pass_counters(fgpu_ctx* ctx) {
+    FGPU_HIP(hipMemsetAsync(ctx->counters, 0, sizeof(DevCounters), ctx->stream));
+    memset(&ctx->load_stats, 0, sizeof(ctx->load_stats));
+    ctx->host_waits = 0;
+    ctx->host_wait_ms = 0;
+    ctx->wait_sites.clear();
+    return FGPU_OK;
+}
+
+// The end of a load pass, plain or sliced: the open epoch joins bloo1, the filters go back to the two raw bit arrays of the .bloom format, the
+// counters become the pass' stats.  (A sliced pass never has shard_times or shard_planes: no fix-up follows it.)
+int fgpu_load_pass_end(fgpu_ctx* ctx, fgpu_load_stats* stats) {
+    int rc = fgpu_load_sweep(ctx);          // bits set since the last sweep join bloo1
+    if (!rc) rc = fgpu_load_pair_end(ctx);
+    if (!rc) rc = fgpu_pull_counters(ctx);
+    ctx->phase = 0;
+    if (rc) return rc;
+    ctx->load_stats.kmers = ctx->counters_host->kmers;
+    ctx->load_stats.to_bloo2 = ctx->counters_host->to_bloo2;
+    ctx->load_mark_hits = ctx->counters_host->mark_hits;      // (0 after a sliced pass: its mark kernel routes nothing by itself)
+    ctx->load_mark_pending = ctx->counters_host->mark_pending;
+    ctx->load_stats.unambiguous_reads = ctx->counters_host->segments;
+    if (stats) *stats = ctx->load_stats;
+    ctx->fixup_ready = (ctx->shard_times || ctx->shard_planes) && ctx->pass_empty_carry &&
+                       ctx->resident_count == ctx->pass_batches && !(ctx->prm.flags & FGPU_FLAG_MERCY);
+    return FGPU_OK;
+}
 
 extern "C" {
 
@@ -243,6 +298,7 @@ int fgpu_create(const fgpu_params* p, fgpu_ctx** out) {
         fgpu_touch_text();
         fgpu_touch_pack();
         fgpu_touch_load();
+        fgpu_touch_load_slices();
         (void)fgpu_text_streams(ctx);
         (void)hipGetLastError();
     });
@@ -404,41 +460,12 @@ int fgpu_synchronize(fgpu_ctx* ctx) {
 }
 
 // ---- pass 1 --------------------------------------------------------------------------------------------------
-// What a plain and a sliced load pass share at their beginning: how the carry is kept up to date and when an epoch is closed ...
-static void load_pass_policy(fgpu_ctx* ctx) {
-    static const char* carry_env = getenv("FGPU_CARRY_MODE");   // "sweep" / "set": measurement aid
-    ctx->carry_by_set = carry_env ? carry_env[0] == 's' && carry_env[1] == 'e' : ctx->prm.tai == (1ULL << 31);
-    ctx->epoch_positions = ctx->swept_positions = 0;
-    ctx->sweep_num = ctx->sweep_den = 1;
-    const char* sweep_env = getenv("FGPU_SWEEP_RATIO");   // "num/den"; "0/1" = after every batch: measurement aid
-    if (sweep_env) {
-        unsigned n = 1, d = 1;
-        if (sscanf(sweep_env, "%u/%u", &n, &d) == 2 && d > 0) { ctx->sweep_num = n; ctx->sweep_den = d; }
-    }
-    {   // a sweep streams tai x 4 bytes whatever the epoch holds: not before the epoch's accesses are tai / 16 (FGPU_SWEEP_MIN_FRAC; 0 = no such
-        // bar, rounds 1-4).  The first sweeps of a pass on large filters came after a quarter-size ramp batch and brought the carry almost nothing:
-        // one rank's own load of config 4 on 8 GPUs 350 -> 337 ms (6 sweeps -> 4), configs 2, 4, 5 whole unchanged (profiles/r05_sweep_policy.txt)
-        const char* e = getenv("FGPU_SWEEP_MIN_FRAC");
-        const double frac = e ? atof(e) : 16.0;
-        ctx->sweep_min = frac > 0.0 ? (uint64_t)((double)ctx->prm.tai / frac / (double)std::max(1, ctx->prm.n_hash)) : 0;
-    }
-}
-// ... and the counters of the pass
-static int load_pass_counters(fgpu_ctx* ctx) {
-    FGPU_HIP(hipMemsetAsync(ctx->counters, 0, sizeof(DevCounters), ctx->stream));
-    memset(&ctx->load_stats, 0, sizeof(ctx->load_stats));
-    ctx->host_waits = 0;
-    ctx->host_wait_ms = 0;
-    ctx->wait_sites.clear();
-    return FGPU_OK;
-}
-
 int fgpu_load_begin(fgpu_ctx* ctx, int keep_carry) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 0) { ctx->err = "load_begin while another pass is open"; return FGPU_ERR_STATE; }
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     if (int rc = fgpu_bloom_download_wait(ctx)) return rc;   // a download still in flight reads the filters this pass rewrites
-    // Where the pass keeps its state (load.hip, Filt): the interleaved pair + first[], or -- FGPU_LOAD_LAYOUT=records: measured in round 5, a
+    // Where the pass keeps its state (load_common.h, Filt): the interleaved pair + first[], or -- FGPU_LOAD_LAYOUT=records: measured in round 5, a
     // faster marking kernel on filters of 2^32 bits and more but no faster pass, not the default -- 256-byte records.  Records need 8 bytes per
     // filter bit: where they cannot be had the pass falls back to the pair layout (4.25 bytes per bit).
     static const char* layout_env = getenv("FGPU_LOAD_LAYOUT");
@@ -478,7 +505,7 @@ int fgpu_load_begin(fgpu_ctx* ctx, int keep_carry) {
     // load on a carried-in state 88-97 / 95 ms, the fix-up protocol's own load 146-163 / 143 ms.  Round 2 re-hashed from 2^31 bits up;
     // it had only measured short passes.)
     ctx->shard_times = (keep_carry & FGPU_LOAD_SHARD_TIMES) != 0;
-    // ONE predicate for the fail planes: they exist for at most 4 hash functions (load.hip MISS_PLANES).  With more the flag is
+    // ONE predicate for the fail planes: they exist for at most 4 hash functions (load_common.h MISS_PLANES).  With more the flag is
     // accepted and the pass is a plain load -- nothing is sized for or copied from planes that are never made -- and fgpu_load_fixup answers
     // FGPU_ERR_STATE as faucet_gpu.h says (hosts then take the presence protocol: sharded.fixup_possible, shard_host.h)
     ctx->shard_planes = (keep_carry & FGPU_LOAD_SHARD_PLANES) != 0 && !ctx->shard_times && ctx->prm.n_hash <= 4;
@@ -487,27 +514,22 @@ int fgpu_load_begin(fgpu_ctx* ctx, int keep_carry) {
     ctx->pass_positions = ctx->pass_batches = 0;
     ctx->pass_empty_carry = !(keep_carry & FGPU_LOAD_KEEP_CARRY);
     keep_carry &= FGPU_LOAD_KEEP_CARRY;
-    load_pass_policy(ctx);
+    fgpu_load_pass_policy(ctx);
     if (!ctx->rec_layout) FGPU_HIP(hipMemsetAsync(ctx->first, 0xFF, ctx->prm.tai * 4, ctx->stream));   // (records: k_rec_init, fgpu_load_pair_begin)
     fgpu_resident_reset(ctx, true);
     if (!keep_carry) FGPU_HIP(hipMemsetAsync(ctx->bloo1, 0, ctx->bloom_bytes, ctx->stream));
     FGPU_HIP(hipMemsetAsync(ctx->bloo2, 0, ctx->bloom_bytes, ctx->stream));
     int rc = fgpu_load_pair_begin(ctx);
     if (rc) return rc;
-    if ((rc = load_pass_counters(ctx))) return rc;
+    if ((rc = fgpu_load_pass_counters(ctx))) return rc;
     ctx->phase = 1;
-    return FGPU_OK;
-}
-
-static int check_reads(fgpu_ctx* ctx, const fgpu_reads* r) {
-    if (!r || (r->n_reads && (!r->bases || !r->offsets))) { ctx->err = "null read batch"; return FGPU_ERR_ARG; }
     return FGPU_OK;
 }
 
 int fgpu_load_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 1) { ctx->err = "load_batch outside load_begin/load_end"; return FGPU_ERR_STATE; }
-    int rc = check_reads(ctx, reads);
+    int rc = fgpu_check_reads(ctx, reads);
     if (rc) return rc;
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     if ((rc = fgpu_stage_pack(ctx, reads))) return rc;
@@ -520,7 +542,7 @@ int fgpu_load_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
 int fgpu_presence_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 0) { ctx->err = "presence_batch while a pass is open"; return FGPU_ERR_STATE; }
-    int rc = check_reads(ctx, reads);
+    int rc = fgpu_check_reads(ctx, reads);
     if (rc) return rc;
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     if ((rc = fgpu_stage_pack(ctx, reads))) return rc;
@@ -531,20 +553,7 @@ int fgpu_presence_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
 int fgpu_load_end(fgpu_ctx* ctx, fgpu_load_stats* stats) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 1) { ctx->err = "load_end without load_begin"; return FGPU_ERR_STATE; }
-    int rc = fgpu_load_sweep(ctx);          // bits set since the last sweep join bloo1
-    if (!rc) rc = fgpu_load_pair_end(ctx);   // bloo1 / bloo2 back as the two raw bit arrays of the .bloom format
-    if (!rc) rc = pull_counters(ctx);
-    ctx->phase = 0;
-    if (rc) return rc;
-    ctx->load_stats.kmers = ctx->counters_host->kmers;
-    ctx->load_stats.to_bloo2 = ctx->counters_host->to_bloo2;
-    ctx->load_mark_hits = ctx->counters_host->mark_hits;
-    ctx->load_mark_pending = ctx->counters_host->mark_pending;
-    ctx->load_stats.unambiguous_reads = ctx->counters_host->segments;
-    if (stats) *stats = ctx->load_stats;
-    ctx->fixup_ready = (ctx->shard_times || ctx->shard_planes) && ctx->pass_empty_carry &&
-                       ctx->resident_count == ctx->pass_batches && !(ctx->prm.flags & FGPU_FLAG_MERCY);
-    return FGPU_OK;
+    return fgpu_load_pass_end(ctx, stats);
 }
 
 int fgpu_load_fixup_state(fgpu_ctx* ctx, int* ready, uint64_t* resident_budget_bytes) {
@@ -565,248 +574,11 @@ int fgpu_load_fixup(fgpu_ctx* ctx, const void* prefix_dev, fgpu_load_stats* stat
     if (int rc = fgpu_bloom_download_wait(ctx)) return rc;
     int rc = fgpu_stage_fixup(ctx, (const uint32_t*)prefix_dev);
     if (!rc) rc = fgpu_util_or(ctx, ctx->bloo1, prefix_dev, ctx->bloom_bytes);
-    if (!rc) rc = pull_counters(ctx);
+    if (!rc) rc = fgpu_pull_counters(ctx);
     if (rc) return rc;
     ctx->fixup_ready = false;                       // once per pass: the planes now speak about the global filter
     ctx->load_stats.to_bloo2 = ctx->counters_host->to_bloo2;
     if (stats) *stats = ctx->load_stats;
-    return FGPU_OK;
-}
-
-// ---- pass 1 by filter slices: the whole stream into one slice of the bit positions ------------------------------
-// `mercy`: the pass is opened by fgpu_load_slice_mercy_begin (batch, exchange, probe in lockstep; four miss planes per batch)
-static int slice_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi, bool mercy) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 0) { ctx->err = "load_slice_begin while another pass is open"; return FGPU_ERR_STATE; }
-    if (!mercy && (ctx->prm.flags & FGPU_FLAG_MERCY)) {
-        ctx->err = "load_slice_begin: --mercy needs time-aware membership tests of the other slices' bits: a probe of every batch between its "
-                   "exchange and the next batch -- open the pass with fgpu_load_slice_mercy_begin and drive the five-step protocol";
-        return FGPU_ERR_STATE;
-    }
-    if (mercy && !(ctx->prm.flags & FGPU_FLAG_MERCY)) {
-        ctx->err = "load_slice_mercy_begin: the context was created without FGPU_FLAG_MERCY (fgpu_load_slice_begin opens the plain sliced pass)";
-        return FGPU_ERR_STATE;
-    }
-    if ((bit_lo & 511) || (bit_hi & 511) || bit_lo > bit_hi || bit_hi > ctx->prm.tai) {
-        ctx->err = "load_slice_begin: a slice is [bit_lo, bit_hi) with both bounds multiples of 512, bit_lo <= bit_hi <= tai";
-        return FGPU_ERR_ARG;
-    }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    if (int rc = fgpu_bloom_download_wait(ctx)) return rc;
-    // the working state is sized by the SLICE (4 bytes of time + 2 x 1/8 byte of filter per own bit), always in the pair layout
-    const uint64_t n = bit_hi - bit_lo, fbytes = n * 4, pbytes = n / 4;
-    if (ctx->slice_first_bytes < fbytes || ctx->slice_pair_bytes < pbytes) {
-        FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-        if (ctx->slice_first) (void)hipFree(ctx->slice_first);
-        if (ctx->slice_pair) (void)hipFree(ctx->slice_pair);
-        ctx->slice_first = nullptr;
-        ctx->slice_pair = nullptr;
-        ctx->slice_first_bytes = ctx->slice_pair_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->slice_first, fbytes);
-        if (e == hipSuccess) e = hipMalloc(&ctx->slice_pair, pbytes);
-        if (e != hipSuccess) {
-            ctx->err = std::string("hipMalloc of the slice state (4.25 bytes per own filter bit) failed: ") + hipGetErrorString(e);
-            if (ctx->slice_first) (void)hipFree(ctx->slice_first);
-            ctx->slice_first = nullptr;
-            ctx->slice_pair = nullptr;
-            return FGPU_ERR_NOMEM;
-        }
-        ctx->slice_first_bytes = fbytes;
-        ctx->slice_pair_bytes = pbytes;
-    }
-    ctx->slice_lo = bit_lo;
-    ctx->slice_n = n;
-    ctx->slice_committed = false;
-    ctx->slice_mercy = mercy;
-    ctx->slice_probe_owed = false;
-    ctx->slice_owed_span = 0;
-    ctx->scan_resident_base = 0;
-    for (PackedBlock* b : ctx->packed) b->state = 0;      // blocks of earlier passes: their buffers serve this one
-    ctx->shard_times = ctx->shard_planes = ctx->fixup_ready = false;
-    ctx->rec_layout = false;
-    ctx->pass_positions = ctx->pass_batches = 0;
-    ctx->pass_empty_carry = true;
-    // carry and sweeps as in a plain pass (load_pass_policy).  The bar on an epoch's size, sweep_min, is taken over unchanged: a sweep of the
-    // slice streams 1/N of what a whole-filter sweep streams, and the epoch's accesses INTO the slice are 1/N as well, so the ratio the bar
-    // stands for is the same -- but the value was measured on whole filters only; for slices it is an unmeasured choice.
-    load_pass_policy(ctx);
-    fgpu_resident_reset(ctx, true);
-    int rc = fgpu_slice_pair_begin(ctx);
-    if (rc) return rc;
-    if ((rc = load_pass_counters(ctx))) return rc;
-    ctx->phase = 3;
-    return FGPU_OK;
-}
-
-int fgpu_load_slice_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi) { return slice_begin(ctx, bit_lo, bit_hi, false); }
-int fgpu_load_slice_mercy_begin(fgpu_ctx* ctx, uint64_t bit_lo, uint64_t bit_hi) { return slice_begin(ctx, bit_lo, bit_hi, true); }
-
-int fgpu_load_slice_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 3) { ctx->err = "load_slice_batch outside load_slice_begin/load_slice_end"; return FGPU_ERR_STATE; }
-    if (ctx->slice_committed) { ctx->err = "load_slice_batch after load_slice_commit: the pass can only be ended"; return FGPU_ERR_STATE; }
-    if (ctx->slice_probe_owed) {
-        ctx->err = "load_slice_batch: the previous batch of this mercy pass has not been probed (fgpu_load_slice_mercy_probe, after its fail plane "
-                   "has been ORed): its first-set times must be read before the next batch is marked";
-        return FGPU_ERR_STATE;
-    }
-    int rc = check_reads(ctx, reads);
-    if (rc) return rc;
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    if ((rc = fgpu_stage_pack(ctx, reads))) return rc;
-    if ((rc = fgpu_stage_slice_load(ctx))) return rc;
-    if (ctx->cur->T) ctx->pass_batches++;
-    ctx->load_stats.reads_processed += reads->n_reads;
-    return fgpu_host_batch_done(ctx, reads);
-}
-
-// ---- packed batches of a sliced pass: made here or by a peer, loaded from the packed form (faucet_gpu.h) --------------------------------
-static int slice_open_for(fgpu_ctx* ctx, const char* who) {
-    if (ctx->phase != 3) { ctx->err = std::string(who) + " outside load_slice_begin/load_slice_end"; return FGPU_ERR_STATE; }
-    if (ctx->slice_committed) { ctx->err = std::string(who) + " after load_slice_commit: the pass can only be ended"; return FGPU_ERR_STATE; }
-    return FGPU_OK;
-}
-
-static void packed_describe(const PackedBlock* b, uint64_t n_reads, fgpu_packed* out) {
-    out->block_dev = b ? b->buf.p : nullptr;
-    out->nbytes = b ? fgpu_packed_bytes(b->n_words) : 0;
-    out->T = b ? b->T : 0;
-    out->n_reads = n_reads;
-}
-
-int fgpu_load_slice_pack(fgpu_ctx* ctx, const fgpu_reads* reads, fgpu_packed* out) {
-    if (!ctx || !out) return FGPU_ERR_ARG;
-    int rc = slice_open_for(ctx, "load_slice_pack");
-    if (rc || (rc = check_reads(ctx, reads))) return rc;
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    PackedBlock* b = nullptr;
-    if ((rc = fgpu_stage_pack_block(ctx, reads, &b))) return rc;
-    packed_describe(b, reads->n_reads, out);
-    return fgpu_host_batch_done(ctx, reads);
-}
-
-int fgpu_load_slice_expect(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, fgpu_packed* out) {
-    if (!ctx || !out) return FGPU_ERR_ARG;
-    if (int rc = slice_open_for(ctx, "load_slice_expect")) return rc;
-    // a stream holds one separator per read: T >= n_reads, and T = 0 exactly for a batch without reads
-    if (n_reads > T || (T && !n_reads) || T > ctx->prm.max_batch_bases || T >= 0xFFFFFF00ULL) {
-        ctx->err = "load_slice_expect: T stream positions (bases + one separator per read, at most max_batch_bases) of n_reads <= T reads";
-        return FGPU_ERR_ARG;
-    }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    PackedBlock* b = nullptr;
-    if (T)
-        if (int rc = fgpu_packed_acquire(ctx, T, n_reads, 2, "load_slice_expect", &b)) return rc;
-    packed_describe(b, n_reads, out);
-    return FGPU_OK;
-}
-
-int fgpu_load_slice_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk) {
-    if (!ctx || !pk) return FGPU_ERR_ARG;
-    if (int rc = slice_open_for(ctx, "load_slice_batch_packed")) return rc;
-    if (ctx->slice_probe_owed) {
-        ctx->err = "load_slice_batch_packed: the previous batch of this mercy pass has not been probed (fgpu_load_slice_mercy_probe, after its fail "
-                   "plane has been ORed): its first-set times must be read before the next batch is marked";
-        return FGPU_ERR_STATE;
-    }
-    if (!pk->block_dev) {                        // a batch without reads has no block
-        if (pk->T || pk->nbytes || pk->n_reads) { ctx->err = "load_slice_batch_packed: a description without a block must be empty"; return FGPU_ERR_ARG; }
-        return FGPU_OK;
-    }
-    PackedBlock* b = nullptr;
-    for (PackedBlock* q : ctx->packed)
-        if (q->buf.p == pk->block_dev) b = q;
-    if (!b || (b->state != 1 && b->state != 2)) {
-        ctx->err = !b ? "load_slice_batch_packed: not a block of fgpu_load_slice_pack / fgpu_load_slice_expect"
-                      : b->state == 3 ? "load_slice_batch_packed: the block has been loaded already"
-                                      : "load_slice_batch_packed: the block belongs to an earlier pass";
-        return FGPU_ERR_STATE;
-    }
-    if (pk->T != b->T || pk->nbytes != fgpu_packed_bytes(b->n_words) || pk->n_reads != b->n_reads) {
-        ctx->err = "load_slice_batch_packed: T, nbytes or n_reads are not those the block was made with";
-        return FGPU_ERR_ARG;
-    }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    if (int rc = fgpu_stage_slice_load_packed(ctx, b)) return rc;
-    ctx->pass_batches++;
-    ctx->load_stats.reads_processed += b->n_reads;
-    return FGPU_OK;
-}
-
-int fgpu_load_slice_plane(fgpu_ctx* ctx, uint64_t batch, void** fail_dev, uint64_t* nbytes) {
-    if (!ctx || !fail_dev) return FGPU_ERR_ARG;
-    if (ctx->phase != 3) { ctx->err = "load_slice_plane outside load_slice_begin/load_slice_end"; return FGPU_ERR_STATE; }
-    if (batch >= ctx->resident_count) { ctx->err = "load_slice_plane: no such batch (empty batches keep no plane)"; return FGPU_ERR_ARG; }
-    const ResidentBatch& r = *ctx->resident[batch];
-    *fail_dev = r.fail.p;
-    if (nbytes) *nbytes = (r.n_words * 8 + 15) & ~15ULL;
-    return FGPU_OK;
-}
-
-int fgpu_load_slice_mercy_probe(fgpu_ctx* ctx) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 3 || !ctx->slice_mercy) { ctx->err = "load_slice_mercy_probe outside a pass opened by load_slice_mercy_begin"; return FGPU_ERR_STATE; }
-    if (!ctx->slice_probe_owed) return FGPU_OK;      // an empty batch, or nothing since the last probe
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    return fgpu_stage_slice_mercy_probe(ctx);
-}
-
-int fgpu_load_slice_mercy_planes(fgpu_ctx* ctx, uint64_t batch, void** miss_dev, uint64_t* nbytes) {
-    if (!ctx || !miss_dev) return FGPU_ERR_ARG;
-    if (ctx->phase != 3 || !ctx->slice_mercy) { ctx->err = "load_slice_mercy_planes outside a pass opened by load_slice_mercy_begin"; return FGPU_ERR_STATE; }
-    if (batch >= ctx->resident_count) { ctx->err = "load_slice_mercy_planes: no such batch (empty batches keep no planes)"; return FGPU_ERR_ARG; }
-    if (ctx->slice_probe_owed && batch == ctx->resident_count - 1) {
-        ctx->err = "load_slice_mercy_planes: this batch has not been probed yet (fgpu_load_slice_mercy_probe)";
-        return FGPU_ERR_STATE;
-    }
-    const ResidentBatch& r = *ctx->resident[batch];
-    *miss_dev = r.miss.p;
-    if (nbytes) *nbytes = 4 * (r.n_words + FGPU_PADW) * 8;      // four planes of the fail plane's padded stride, one block
-    return FGPU_OK;
-}
-
-int fgpu_diag_slice_mercy(fgpu_ctx* ctx, uint64_t out[6]) {
-    if (!ctx || !out) return FGPU_ERR_ARG;
-    for (int i = 0; i < 6; i++) out[i] = ctx->slice_mercy_diag[i];
-    return FGPU_OK;
-}
-
-int fgpu_load_slice_commit(fgpu_ctx* ctx) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 3) { ctx->err = "load_slice_commit outside load_slice_begin/load_slice_end"; return FGPU_ERR_STATE; }
-    if (ctx->slice_committed) { ctx->err = "load_slice_commit twice in one pass"; return FGPU_ERR_STATE; }
-    if (ctx->slice_probe_owed) { ctx->err = "load_slice_commit: the last batch of this mercy pass has not been probed (fgpu_load_slice_mercy_probe)"; return FGPU_ERR_STATE; }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    int rc = fgpu_stage_slice_commit(ctx);
-    if (rc) return rc;
-    ctx->slice_committed = true;
-    return FGPU_OK;
-}
-
-int fgpu_load_slice_end(fgpu_ctx* ctx, fgpu_load_stats* stats) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 3) { ctx->err = "load_slice_end without load_slice_begin"; return FGPU_ERR_STATE; }
-    if (!ctx->slice_committed) { ctx->err = "load_slice_end before load_slice_commit"; return FGPU_ERR_STATE; }
-    int rc = fgpu_slice_sweep(ctx);          // bits set since the last sweep join the slice of bloo1
-    if (!rc) rc = fgpu_slice_pair_end(ctx);
-    if (!rc) rc = pull_counters(ctx);
-    ctx->phase = 0;
-    if (rc) return rc;
-    ctx->load_stats.kmers = ctx->counters_host->kmers;
-    ctx->load_stats.to_bloo2 = ctx->counters_host->to_bloo2;
-    ctx->load_mark_hits = 0;
-    for (int i = 0; i < 6; i++) ctx->slice_mercy_diag[i] = ctx->slice_mercy ? ctx->counters_host->slice_mercy[i] : 0;
-    ctx->load_mark_pending = ctx->counters_host->mark_pending;
-    ctx->load_stats.unambiguous_reads = ctx->counters_host->segments;
-    if (stats) *stats = ctx->load_stats;
-    return FGPU_OK;
-}
-
-int fgpu_load_slice_state(fgpu_ctx* ctx, int* ready, uint64_t* working_bytes, uint64_t* n_batches) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ready) *ready = ctx->phase == 3 && !ctx->slice_committed ? 1 : 0;
-    if (working_bytes) *working_bytes = ctx->slice_first_bytes + ctx->slice_pair_bytes;
-    if (n_batches) *n_batches = ctx->phase == 3 ? ctx->resident_count : 0;
     return FGPU_OK;
 }
 
@@ -1087,7 +859,7 @@ static int journal_add(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads) {
     const uint64_t cb = 2 * (b->n_words + FGPU_PADW) * 8, bbytes = (b->n_words + FGPU_PADW) * 8, ob = ctx->record_stops ? (b->n_reads + 1) * 8 : 0;
     if (ctx->journal_bytes + cb + bbytes + ob > ctx->journal_budget) {
         // no room: everything walked so far is checked (and scanned again if need be), the rest of the scan is eager
-        int rc = pull_counters(ctx);
+        int rc = fgpu_pull_counters(ctx);
         if (rc) return rc;
         BatchBufs* const cur = ctx->cur;
         // the batch being packed has already been folded into the device's longest-read maximum (fgpu_stage_pack) and is not in the journal:
@@ -1236,7 +1008,7 @@ static int scan_replay_once(fgpu_ctx* ctx) {
         ctx->pool.push_back(b);
     }
     ctx->cur = &ctx->bb_default;
-    if (!rc) rc = pull_counters(ctx);     // (still in_replay: an overflow of the last walks is reported here, to scan_replay, not flagged for later)
+    if (!rc) rc = fgpu_pull_counters(ctx);     // (still in_replay: an overflow of the last walks is reported here, to scan_replay, not flagged for later)
     ctx->in_replay = false;
     ctx->scan_replays++;
     return rc;
@@ -1247,7 +1019,7 @@ int fgpu_scan_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (ctx->phase != 2) { ctx->err = "scan_batch outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
     if (!ctx->prepared.empty()) { ctx->err = "scan_batch while prepared batches are waiting: call fgpu_scan_walk_prepared first"; return FGPU_ERR_STATE; }
     if (ctx->hint_in_table) { ctx->err = "the junction table holds a preview (fgpu_scan_import_hint): import the real table before walking"; return FGPU_ERR_STATE; }
-    int rc = check_reads(ctx, reads);
+    int rc = fgpu_check_reads(ctx, reads);
     if (rc) return rc;
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     if (ctx->lazy_failed && (rc = scan_replay(ctx))) return rc;      // an earlier walk met a preview it could not repair: scan again, eagerly
@@ -1284,7 +1056,7 @@ int fgpu_scan_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
 int fgpu_scan_prepare(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 2) { ctx->err = "scan_prepare outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
-    int rc = check_reads(ctx, reads);
+    int rc = fgpu_check_reads(ctx, reads);
     if (rc) return rc;
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     BatchBufs* b;
@@ -1352,7 +1124,7 @@ int fgpu_scan_walk_prepared(fgpu_ctx* ctx) {
     for (size_t i = 0; i < ctx->prepared.size() && !rc; i++) {
         BatchBufs* b = ctx->prepared[i];
         if (i > 0) {   // feedback for the window controller and for the size of the junction table between batches
-            if ((rc = pull_counters(ctx))) break;                  // (the walk of batch i - 1 has finished; so have the planes of batch i)
+            if ((rc = fgpu_pull_counters(ctx))) break;                  // (the walk of batch i - 1 has finished; so have the planes of batch i)
             if (ctx->lazy_failed) { ctx->cur = &ctx->bb_default; return scan_replay(ctx); }
             if (!ctx->prm.walk_window_span) adapt_window(ctx);
             if ((rc = fgpu_scan_reserve(ctx, ctx->counters_host->n_junctions + ctx->scan_imported))) break;
@@ -1461,10 +1233,10 @@ int fgpu_scan_end(fgpu_ctx* ctx, fgpu_scan_stats* stats) {
                         "pure stage issue (second half) %.2f, walk issue %.2f\n", ctx->host_ms[0], ctx->host_ms[1], ctx->host_ms[2], ctx->host_ms[3], ctx->host_ms[4], ctx->host_ms[5]);
         for (double& v : ctx->host_ms) v = 0;
     }
-    int rc = pull_counters(ctx);
+    int rc = fgpu_pull_counters(ctx);
     if (!rc && ctx->lazy_failed) {                          // the last walks met a preview they could not repair: scan again before closing
         rc = scan_replay(ctx);
-        if (!rc) rc = pull_counters(ctx);
+        if (!rc) rc = fgpu_pull_counters(ctx);
     }
     while (!rc && !ctx->to_harvest.empty()) rc = fgpu_scan_harvest(ctx, ctx->to_harvest.front());   // every walk has finished
     if (!rc) rc = fgpu_long_pairs_close(ctx);              // the last batch of lists: its rounds' outcome, a first end left without a mate

@@ -247,11 +247,11 @@ struct fgpu_ctx {
     uint32_t* bloo2 = nullptr;
     uint32_t* first = nullptr;       // first-set time per Bloom bit, 4*tai bytes (allocated at load_begin)
     uint2* pair = nullptr;           // {bloo1 word, bloo2 word} interleaved: the working copy of both filters during a load pass
-    uint32_t* rec = nullptr;         // the same state as 256-byte records {bloo1 word, bloo2 word, ..., 32 first-set times} (load.hip, Filt<1>):
+    uint32_t* rec = nullptr;         // the same state as 256-byte records {bloo1 word, bloo2 word, ..., 32 first-set times} (load_common.h, Filt<1>):
     bool rec_layout = false;         // filters of 2^32 bits and more; `pair` and `first` are not used (nor allocated) then
     uint64_t bloom_bytes = 0;
     int phase = 0;                   // 0 idle, 1 loading, 2 scanning, 3 loading one slice of the filter bits (fgpu_load_slice_*)
-    // the filter-sliced pass: own bit positions [slice_lo, slice_lo + slice_n), its working state sized by the slice (load.hip, Slice)
+    // the filter-sliced pass: own bit positions [slice_lo, slice_lo + slice_n), its working state sized by the slice (load_common.h, Slice)
     uint64_t slice_lo = 0, slice_n = 0;
     uint32_t* slice_first = nullptr; // first-set time per OWN bit, 4 * slice_n bytes
     uint2* slice_pair = nullptr;     // {carry word, bloo2 word} per 32 own bits
@@ -509,6 +509,7 @@ static inline bool fgpu_overflow_absorbable(const fgpu_ctx* ctx) {
 // stage entry points implemented in the .hip files
 int fgpu_text_streams(fgpu_ctx* ctx);
 void fgpu_touch_load();
+void fgpu_touch_load_slices();
 void fgpu_touch_pack();
 void fgpu_touch_text();
 void fgpu_touch_scan_pure();
@@ -519,18 +520,22 @@ int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads);
 int fgpu_stage_pack_block(fgpu_ctx* ctx, const fgpu_reads* reads, PackedBlock** out);
 int fgpu_packed_acquire(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, int state, const char* who, PackedBlock** out);
 int fgpu_packed_digest(fgpu_ctx* ctx, const PackedBlock* b, bool verify);
-int fgpu_stage_slice_load_packed(fgpu_ctx* ctx, PackedBlock* b);
 int fgpu_host_batch_done(fgpu_ctx* ctx, const fgpu_reads* reads);
 int fgpu_stage_load(fgpu_ctx* ctx);
 int fgpu_load_sweep(fgpu_ctx* ctx);
 int fgpu_stage_fixup(fgpu_ctx* ctx, const uint32_t* prefix);
 int fgpu_stage_presence(fgpu_ctx* ctx);
-int fgpu_stage_slice_load(fgpu_ctx* ctx);
-int fgpu_stage_slice_commit(fgpu_ctx* ctx);
-int fgpu_stage_slice_mercy_probe(fgpu_ctx* ctx);
-int fgpu_slice_sweep(fgpu_ctx* ctx);
-int fgpu_slice_pair_begin(fgpu_ctx* ctx);
-int fgpu_slice_pair_end(fgpu_ctx* ctx);
+// what load.hip shares with the sliced pass (load_slices.hip): the epoch clock, and the next resident slot with the budget arithmetic
+int fgpu_epoch_before_batch(fgpu_ctx* ctx, uint64_t span);
+int fgpu_epoch_after_batch(fgpu_ctx* ctx, uint64_t span);
+enum { FGPU_TAKE_OK = 0, FGPU_TAKE_NO_BUDGET, FGPU_TAKE_NO_MEMORY };
+int fgpu_resident_take(fgpu_ctx* ctx, const uint64_t (&parts)[5], bool budgeted, ResidentBatch** out, uint64_t* total);
+// what the sliced pass' entry points share with api.hip
+int fgpu_pull_counters(fgpu_ctx* ctx);
+int fgpu_check_reads(fgpu_ctx* ctx, const fgpu_reads* r);
+void fgpu_load_pass_policy(fgpu_ctx* ctx);
+int fgpu_load_pass_counters(fgpu_ctx* ctx);
+int fgpu_load_pass_end(fgpu_ctx* ctx, fgpu_load_stats* stats);
 int fgpu_load_pair_begin(fgpu_ctx* ctx);
 int fgpu_load_pair_end(fgpu_ctx* ctx);
 void fgpu_resident_reset(fgpu_ctx* ctx, bool keep_going);
@@ -542,7 +547,7 @@ int fgpu_scan_build_cand(fgpu_ctx* ctx, BatchBufs* b);
 int fgpu_scan_import_probe(fgpu_ctx* ctx, const void* dev_entries, uint64_t n, uint64_t after_seq, uint32_t* dfilter, uint64_t dfilter_bits,
                            uint64_t* max_seq, uint64_t* n_newer, uint64_t digest[2]);
 int fgpu_stage_scan_debug_drop(fgpu_ctx* ctx);
-int fgpu_util_count_segments(fgpu_ctx* ctx, int minlen);
+int fgpu_util_count_segments(fgpu_ctx* ctx, const void* bad, uint64_t n_words, int minlen);
 int fgpu_util_popcount(fgpu_ctx* ctx, const void* dev, uint64_t nbytes, unsigned long long* dev_out);
 int fgpu_util_or(fgpu_ctx* ctx, void* dst, const void* src, uint64_t nbytes);
 int fgpu_util_probe_hash(fgpu_ctx* ctx, const uint64_t* d_kmers, uint64_t n, uint64_t* d_canon, uint64_t* d_hA, uint64_t* d_hB);

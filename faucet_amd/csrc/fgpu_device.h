@@ -144,3 +144,23 @@ __device__ __forceinline__ uint64_t fd_mix(uint64_t x) {
 }
 
 __device__ __forceinline__ int fd_lane() { return (int)(threadIdx.x & 63); }
+
+// What the lanes of a wave counted, added to a counter by lane 0 (a sum of zero costs no atomic)
+__device__ __forceinline__ void wave_add(unsigned long long* dst, unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (fd_lane() == 0 && v) atomicAdd(dst, v);
+}
+
+// one atomic per BLOCK of 256 threads: the waves of a grid-stride kernel retire together, and 16 K of them adding to one word is a queue of
+// ~10 ns same-address atomics at the tail of every launch (k_scan_pieces spent most of its time in it).  All threads must call.
+__device__ __forceinline__ void block_add(unsigned long long* dst, unsigned long long v) {
+    __shared__ unsigned long long part[4];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (fd_lane() == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long t = part[0] + part[1] + part[2] + part[3];
+        if (t) atomicAdd(dst, t);
+    }
+    __syncthreads();   // part[] is reused by the next call
+}

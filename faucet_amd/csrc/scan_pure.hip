@@ -23,24 +23,6 @@
 
 namespace {
 
-__device__ __forceinline__ void wave_add(unsigned long long* dst, unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if (fd_lane() == 0 && v) atomicAdd(dst, v);
-}
-
-// one atomic per BLOCK of 256 threads (see load.hip); every thread of the block must call
-__device__ __forceinline__ void block_add(unsigned long long* dst, unsigned long long v) {
-    __shared__ unsigned long long part[4];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if (fd_lane() == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long t = part[0] + part[1] + part[2] + part[3];
-        if (t) atomicAdd(dst, t);
-    }
-    __syncthreads();
-}
-
 // Is this batch, word for word, the load batch kept under the same index?  *same starts non-zero; any differing word clears it.
 __global__ void __launch_bounds__(256) k_scan_same(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ kept_codes, uint64_t n_code_words,
                                                    const uint64_t* __restrict__ bad, const uint64_t* __restrict__ kept_bad, uint64_t n_words,
@@ -570,7 +552,7 @@ int fgpu_stage_scan_pure(fgpu_ctx* ctx, uint64_t* n_pieces) {
     // the previous batch was measured and does not pay: the walk is slowed by memory contention, not by slots)
     const unsigned grid = fgpu_grid(bb.n_words * 64, 256);
     const unsigned wgrid = fgpu_grid(bb.n_words, 256);            // kernels with one thread per 64-position word
-    if ((rc = fgpu_util_count_segments(ctx, ctx->fd.k + 2 * ctx->fd.j + 1))) return rc;
+    if ((rc = fgpu_util_count_segments(ctx, ctx->cur->bad.p, ctx->cur->n_words, ctx->fd.k + 2 * ctx->fd.j + 1))) return rc;
     // the load pass' batch of the same index, if it was kept and has the same shape: compare the streams on the device
     // (of the index fgpu_scan_resident_base moved it to: a rank whose scan shard begins in the middle of the batches its sliced pass loaded)
     const uint64_t kept_index = ctx->scan_resident_base + ctx->scan_batch_index;

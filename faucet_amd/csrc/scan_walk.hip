@@ -1283,10 +1283,6 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;   // (lane 0 holds the sum)
 }
-__device__ __forceinline__ void wave_add(unsigned long long* total, unsigned long long v) {
-    v = wave_sum(v);
-    if (fd_lane() == 0 && v) atomicAdd(total, v);
-}
 // the reference's four scan statistics (ReadScanner's NbProcessed, NbSkipped, NbJCheckKmer, NbNoJuncs)
 __device__ __forceinline__ void walk_counters_flush(DevCounters* cnt, unsigned long long processed, unsigned long long skipped, unsigned long long jcheck,
                                                     unsigned long long no_juncs) {

@@ -10,7 +10,7 @@ OUT=faucet_amd/build_asan
 mkdir -p $OUT
 FLAGS="-O1 -g -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-result -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer"
 pids=()
-for s in api pack load scan_pure scan_walk scan_table scan_harvest diag text stage3 pairs group; do
+for s in api pack load load_slices scan_pure scan_walk scan_table scan_harvest diag text stage3 pairs group; do
   /opt/rocm/bin/hipcc $FLAGS -x hip -c faucet_amd/csrc/$s.hip -o $OUT/$s.o &
   pids+=($!)
 done

@@ -1,5 +1,5 @@
-"""Pass 1 alone on config 2's reads, with the kernels' times (GPU box; used by scripts/first_table_experiment.sh -- the measurement builds give wrong
-filters, so nothing is scanned)."""
+"""Pass 1 alone on config 2's reads, with the kernels' times (GPU box; nothing is scanned: it served the measurement builds of
+profiles/r03_first_table.txt, whose filters were wrong)."""
 import os
 import sys
 

@@ -1292,7 +1292,7 @@ def test_a_replay_applies_the_long_pair_loop_to_every_batch_once():
 
 @pytest.mark.parametrize("case", ["c1_k21", "ragged_k31", "mercy_k21", "twohash_k31_L150", "pe_repeats_k25"])
 def test_load_pass_with_256_byte_records_gives_the_reference_filter(case, tmp_path):
-    """FGPU_LOAD_LAYOUT=records (load.hip, Filt<1>; round 5, measured and not the default): the pass keeps {bloo1 word, bloo2 word, 32 first-set
+    """FGPU_LOAD_LAYOUT=records (load_common.h, Filt<1>; round 5, measured and not the default): the pass keeps {bloo1 word, bloo2 word, 32 first-set
     times} in one aligned 256-byte record per 32 filter bits instead of the interleaved pair + first[] -- same algorithm, other addresses; the
     reference's files come out, --mercy (times of every bit) and several batches with their sweeps included, and with -gpus 2 the fix-up
     protocol reads its times from the records"""

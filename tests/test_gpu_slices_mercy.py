@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from faucet_amd import _lib as L
-from faucet_amd import api, sharded
+from faucet_amd import api, sharded, synth
 from oracle import pyoracle as po
 from tests.golden_util import Case
 from tests.test_gpu_parity import _random_case, chunks
@@ -297,6 +297,54 @@ def test_mercy_fuzz_by_slices(seed, monkeypatch):
     ctxs, stats, diags = run_mercy_slices(k, tai, nh, chunks(bases, offs, n_batches), bounds)
     assert_slices_equal(ctxs, stats, bounds, tai, b1.bits(), b2.bits(), lst, len(offs) - 1)
     assert_counts(diags)
+    close_all(ctxs)
+
+
+# ---- 6b. segments on the 64-position words of `bad` ----------------------------------------------------------------------------------------
+WORD_EDGE_LENGTHS = [62, 63, 64, 126, 127, 128, 20, 21, 22, 85]
+
+
+@functools.lru_cache(maxsize=None)
+def word_boundary_case():
+    """reads of 62..128 and of k - 1, k, k + 1 bases, one after the other in the stream: the unambiguous runs start on every bit of a 64-position
+    word of `bad`, end a base short of k, at k and past it, and cross up to three words.  Returns the input, the oracle's --mercy load, the
+    stand-in's counts and (start, length) of every run of good stream positions."""
+    k, tai, nh = 21, 1 << 22, 3
+    g = synth.make_genome(40000, 313)
+    r = synth.make_reads(g, 3000, 128, 0.012, 314, n_rate=0.004)
+    bases, offs = po.reads_from_lines([r[i, :WORD_EDGE_LENGTHS[i % 10]].tobytes() for i in range(len(r))])
+    T = len(bases) + len(offs) - 1                           # the stream: every read's bases, then its separator
+    good = np.zeros(T, bool)
+    at = np.arange(len(bases)) + np.searchsorted(offs[1:].astype(np.int64), np.arange(len(bases)), side="right")
+    good[at] = np.isin(bases, np.frombuffer(b"ACGT", np.uint8))
+    edge = np.diff(np.concatenate(([0], good.astype(np.int8), [0])))
+    start = np.flatnonzero(edge == 1)
+    return k, tai, nh, bases, offs, T, mercy_oracle(bases, offs, k, tai, nh), standin_counts(bases, offs, k, tai, nh), start, np.flatnonzero(edge == -1) - start
+
+
+@pytest.mark.parametrize("how,n", [("plain", 1), ("plain", 3), ("slices", 1), ("slices", 2), ("slices", 3)])
+def test_mercy_segments_on_word_boundaries(how, n):
+    """the segment walker and the state machine that the plain and the sliced --mercy pass share, at the edges of the 64-position word: the
+    plain pass in n batches, the sliced one on n ranks, each against the oracle"""
+    k, tai, nh, bases, offs, T, (b1, b2, lst), counts, start, length = word_boundary_case()
+    # what the input is for, before the device sees it
+    assert T == 218_400
+    on_bit = np.bincount(start % 64, minlength=64)
+    assert on_bit.min() > 0 and (on_bit[0], on_bit[63]) == (123, 160)
+    assert [int((length == x).sum()) for x in (k - 1, k, k + 1)] == [296, 297, 291]
+    assert int((length >= 127).sum()) == 374                # a window of 64 positions lies inside the run: it crosses three words
+    assert counts == [70098, 43, 1799, 720, 349, 5543]
+    if how == "plain":
+        ctx = api.Context(k, tai, nh, mercy=True)
+        st = api.load_two_filters(api.Bloom(ctx, L.BLOO1), api.Bloom(ctx, L.BLOO2), chunks(bases, offs, n))
+        assert np.array_equal(ctx.bloom_download(L.BLOO1), b1.bits()) and np.array_equal(ctx.bloom_download(L.BLOO2), b2.bits())
+        assert (st["kmers"], st["to_bloo2"], st["unambiguous_reads"]) == (lst.kmers, lst.to_bloo2, lst.unambiguous_reads)
+        ctx.close()
+        return
+    bounds = equal_slices(tai, n)
+    ctxs, stats, diags = run_mercy_slices(k, tai, nh, chunks(bases, offs, 3), bounds)
+    assert_slices_equal(ctxs, stats, bounds, tai, b1.bits(), b2.bits(), lst, len(offs) - 1)
+    assert_counts(diags, counts)
     close_all(ctxs)
 
 
