@@ -8,6 +8,7 @@ hipcc cross-compiles for gfx950 without a GPU; the built .so travels to the GPU 
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -58,7 +59,7 @@ def build(force: bool = False, jobs: int = 6) -> str:
     if force or _newer(LIB, objs):
         _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs)
     main = os.path.join(HERE, "host", "faucet_main.cpp")
-    if os.path.exists(main) and (force or _newer(CLI, [main, LIB] + [os.path.join(HERE, "host", h) for h in ("junction_order.h", "shard_host.h", "batch_board.h", "text_source.h", "pair_loop.h")] + hdrs)):
+    if os.path.exists(main) and (force or _newer(CLI, [main, LIB] + glob.glob(os.path.join(HERE, "host", "*.h")) + hdrs)):
         _run(["g++", "-std=c++11", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), main, "-o", CLI,
               "-L", HERE, "-lfaucet_gpu", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + "/opt/rocm/lib", "-lpthread"])
     return LIB

@@ -24,7 +24,9 @@
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
+#include <atomic>
 #include <fstream>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <string>
@@ -33,10 +35,11 @@
 
 #include "faucet_gpu.h"
 #include "junction_order.h"
-#include "pair_loop.h"
+#include "scan_pass.h"
 #include "shard_host.h"
 #include "text_source.h"
 
+using faucet_host::ReadSource;
 using faucet_host::TextSource;
 using faucet_host::pinned_slot;
 using faucet_host::kTextPad;
@@ -56,7 +59,9 @@ struct Options {   // globals of src/Faucet.h:14-53
     int max_spacer_dist = 100;
     uint64_t batch_reads = 0;         // not a reference flag: > 0 = split records on the host, this many reads per device call
     uint64_t chunk_mb = 64;           // not a reference flag: file text handed to the device per call, records split there
-    uint64_t chunk_bytes = 0;         // = chunk_mb << 20, less for regular files that are smaller (main)
+    uint64_t chunk_bytes = 0;         // = chunk_mb << 20, less for regular files that are smaller (choose_chunk_bytes)
+    uint64_t tai = 0;                 // bloo1 / bloo2: bits and hash functions, from the flags above (size_filters)
+    int32_t n_hash = 0;
     int gpus = 1;                     // not a reference flag: read shards over this many GPUs, one host thread each (shard_host.h)
     std::string transport = "copy";   // not a reference flag: how the shards' bitmaps and tables travel: copy (device-to-device copies) | rccl
 };
@@ -139,53 +144,23 @@ int handle_arguments(int argc, char** argv, Options& o) {
     return 0;
 }
 
-// Record splitting exactly as the reference's loops do it (utils/Bloom.cpp:280-282,340; src/ReadScanner.cpp:306-308,349):
-//   while (getline(header)) { getline(sequence); ...; if (fastq) getline, getline; }
-// Works on non-seekable input (the reference is fed process substitutions, src/stream_data_from_urls_list.sh:12-15).
-class ReadSource {
-public:
-    ReadSource(const std::string& path, bool fastq) : in_(path.c_str()), fastq_(fastq) {}
-    bool is_open() const { return in_.is_open(); }
-    // next batch of at most max_reads sequence lines; false when the input is exhausted
-    bool next(uint64_t max_reads, std::vector<char>& bases, std::vector<uint64_t>& offsets) {
-        bases.clear();
-        offsets.assign(1, 0);
-        std::string line;
-        while (offsets.size() - 1 < max_reads && std::getline(in_, line)) {
-            line.clear();
-            std::getline(in_, line);
-            bases.insert(bases.end(), line.begin(), line.end());
-            offsets.push_back(bases.size());
-            if (fastq_) { std::getline(in_, line); std::getline(in_, line); }
-        }
-        return offsets.size() > 1;
-    }
-private:
-    std::ifstream in_;
-    bool fastq_;
-};
-
-// one interface over both ways of cutting the input into batches
+// one interface over both ways of cutting the input into batches: file text split on the device (TextSource), or -batch_reads records
+// split here (ReadSource) -- text_source.h
 class BatchSource {
 public:
     BatchSource(const Options& o, const std::string& path)
         : host_(o.batch_reads ? new ReadSource(path, o.fastq) : nullptr),
           text_(o.batch_reads ? nullptr : new TextSource(path, o.fastq, o.chunk_bytes)), batch_reads_(o.batch_reads) {}
     ~BatchSource() { delete host_; delete text_; }
+    BatchSource(const BatchSource&) = delete;
+    BatchSource& operator=(const BatchSource&) = delete;
     bool is_open() const { return host_ ? host_->is_open() : text_->is_open(); }
-    int next(fgpu_ctx* ctx, fgpu_reads* out) {
-        if (text_) return text_->next(ctx, out);
-        if (!host_->next(batch_reads_, bases_, offsets_)) return 0;
-        fgpu_reads r = {bases_.data(), offsets_.data(), offsets_.size() - 1, 0, 0, nullptr};
-        *out = r;
-        return 1;
-    }
+    // 1 = a batch, 0 = input exhausted, < 0 = -status of a failed fgpu_text_split
+    int next(fgpu_ctx* ctx, fgpu_reads* out) { return text_ ? text_->next(ctx, out) : host_->next(batch_reads_, out) ? 1 : 0; }
 private:
     ReadSource* host_;
     TextSource* text_;
     uint64_t batch_reads_;
-    std::vector<char> bases_;
-    std::vector<uint64_t> offsets_;
 };
 
 #define CHECK(call)                                                                   \
@@ -286,7 +261,7 @@ int write_junctions(const std::string& path, const uint64_t* keys, const fgpu_ju
     std::mutex m;
     std::condition_variable cv;
     size_t known = 0, next = 0;          // offset[0 .. known] are final; next chunk to hand out
-    bool failed = false;
+    std::atomic<bool> failed(false);     // (set under the mutex, read outside it as well)
     auto worker = [&]() {
         std::vector<char> buf;
         for (;;) {
@@ -474,12 +449,134 @@ int write_scan_outputs(const Options& o, fgpu_ctx* ctx, const fgpu_scan_stats& s
     return 0;
 }
 
-// ---- `-gpus N`: the same run with the reads sharded over N GPUs, one host thread per device (shard_host.h) -------------------------------
-// Same files, same log, same exit codes as the single-device run below; what differs is who does the passes: shard r = the r-th file-order
-// share of the records, on device r (with fewer devices than shards several shards share a device: what a one-GPU box can test).  Inputs
-// must be regular files (a shard is a byte range); -bloom_file restarts load the filter on every device.
-int main_sharded(const Options& o, const fgpu_params& prm, uint64_t tai, PhaseClock& clk) {
-    using namespace faucet_host;
+namespace {
+
+using faucet_host::ShardedRun;
+
+// The device side of a run: one context, or -- `-gpus N` -- read shards over N GPUs, one host thread per device (shard_host.h): shard r = the
+// r-th file-order share of the records, on device r (with fewer devices than shards several shards share a device: what a one-GPU box can
+// test).  Same files, same log, same exit codes either way; what differs is who does the two passes.
+// fgpu_create returns while a thread of the library is still creating the walk's streams and loading code objects: every way out of main
+// goes through fgpu_destroy (here, or in ~ShardedRun), which joins it, before the HIP runtime is torn down.  The one exception is
+// the _exit at the very end, after both passes -- the first scan call has joined the thread by then.
+struct Run {
+    fgpu_ctx* one = nullptr;
+    std::unique_ptr<ShardedRun> shards;
+    ~Run() { close(); }
+    void close() {
+        shards.reset();
+        if (one) { fgpu_destroy(one); one = nullptr; }
+    }
+    std::vector<fgpu_ctx*> contexts() const {
+        if (!shards) return std::vector<fgpu_ctx*>(1, one);
+        std::vector<fgpu_ctx*> all;
+        for (int r = 0; r < shards->n_ranks(); r++) all.push_back(shards->ctx(r));
+        return all;
+    }
+    fgpu_ctx* first() const { return shards ? shards->first_ctx() : one; }
+    fgpu_ctx* last() const { return shards ? shards->last_ctx() : one; }      // holds the run's junction map and pair filters after pass 2
+};
+
+// bloo2's bytes and the thread that writes them to <prefix>.bloom (Bloom::dump, utils/Bloom.cpp:571-578) beside pass 2: every way out of main
+// waits for the file to be complete (the destructor), and every SUCCESSFUL way out looks at how the write went (complete(): a short write
+// of --just_load_bloom's only output is not exit code 0)
+class BloomFile {
+public:
+    BloomFile(const std::string& prefix, uint64_t tai) : bytes((size_t)(tai / 8)), path_(prefix + ".bloom") {}
+    ~BloomFile() { if (writer_.joinable()) writer_.join(); }
+    std::vector<uint8_t> bytes;
+    // the bytes are in host memory; writing them out (64 MiB - 1 GiB) is waited for before the process ends
+    int start_writing() {
+        FILE* f = fopen(path_.c_str(), "wb");
+        if (!f) { fprintf(stderr, "cannot write %s\n", path_.c_str()); return 2; }
+        writer_ = std::thread([this, f] {
+            if (fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size()) failed_ = true;
+            if (fclose(f) != 0) failed_ = true;
+        });
+        return 0;
+    }
+    bool complete() {
+        if (writer_.joinable()) writer_.join();
+        if (failed_) fprintf(stderr, "cannot write %s\n", path_.c_str());
+        return !failed_;
+    }
+private:
+    const std::string path_;
+    std::thread writer_;
+    bool failed_ = false;      // (written by the writer, read behind its join)
+};
+
+// ---- filter sizing: getBloomFilterFromReads / getBloomFilterFromFile (src/Faucet.cpp:185-219).  0, or exit code 1
+int size_filters(Options& o) {
+    int32_t bits = 0;
+    if (o.from_bloom) {
+        if (o.two_hash) fgpu_size_two_hash(o.estimated_kmers, o.fp_rate, &bits, &o.tai, &o.n_hash);
+        else fgpu_size_optimal(o.estimated_kmers, o.fp_rate, &bits, &o.tai, &o.n_hash);
+        printf("Bits per kmer: %d \n", bits);                       // create_bloom_filter_2_hash / _optimal, utils/Bloom.cpp:204-247
+        if (o.two_hash) {
+            printf("Estimated items: %llu \n", (unsigned long long)o.estimated_kmers);
+            printf("Estimated bloom size: %llu .\n", (unsigned long long)(o.estimated_kmers * (uint64_t)bits));
+        }
+        printf("BF memory: %f MB\n", (float)((o.estimated_kmers * (uint64_t)bits) / 8ULL / 1024ULL) / 1024);
+        printf("Number of hash functions: %d \n", o.n_hash);
+        return 0;
+    }
+    int32_t iters = 0;
+    const double p1 = fgpu_solve_p1(o.estimated_kmers, o.singletons, o.fp_rate, &iters);
+    if (p1 < 0) {   // the reference prints a message and goes on with nonsense sizes; we refuse
+        fprintf(stderr, "Signs of f(lower_bound) and f(upper_bound) must be opposites: check -singletons (must be > 0)\n");
+        return 1;
+    }
+    printf("After %d iterations the root is: %g\n", iters, p1);
+    printf("p2 is %g p1 estimated as %g\n", (double)o.fp_rate, p1);
+    fgpu_size_optimal(o.estimated_kmers, (float)p1, &bits, &o.tai, &o.n_hash);
+    for (int i = 0; i < 2; i++) {   // printed once per filter, utils/Bloom.cpp:234-243
+        printf("Bits per kmer: %d \n", bits);
+        printf("BF memory: %f MB\n", (float)((o.estimated_kmers * (uint64_t)bits) / 8ULL / 1024ULL) / 1024);
+        printf("Number of hash functions: %d \n", o.n_hash);
+    }
+    return 0;
+}
+
+fgpu_params context_params(const Options& o) {
+    fgpu_params prm;
+    memset(&prm, 0, sizeof(prm));
+    prm.k = o.k;
+    prm.j = o.j;
+    prm.max_spacer_dist = o.max_spacer_dist;
+    prm.n_hash = o.n_hash;
+    prm.tai = o.tai;
+    // scanInputRead's lists feed the pair filters and the pair counts, all on the device (scan_pass.h); with --no_cleaning only the paired-end
+    // loop's two counts are left of them
+    if (!o.no_cleaning || o.paired_ends) prm.flags |= FGPU_FLAG_RECORD_STOPS;
+    prm.flags |= FGPU_FLAG_KEY_ORDER_FROM_START;   // real genomes have repeats: a few launches per window against a first batch walked by cluster
+    if (o.mercy) prm.flags |= FGPU_FLAG_MERCY;
+    return prm;
+}
+
+// the size of the larger of the inputs that are regular files; false if one of them is something else (a pipe)
+bool largest_input(const Options& o, uint64_t* largest) {
+    bool all_regular = true;
+    *largest = 0;
+    for (const std::string* f : {&o.read_load_file, &o.read_scan_file}) {
+        struct stat st;
+        if (f->empty()) continue;
+        if (stat(f->c_str(), &st) == 0 && S_ISREG(st.st_mode)) *largest = std::max<uint64_t>(*largest, (uint64_t)st.st_size);
+        else all_regular = false;
+    }
+    return all_regular;
+}
+
+// The text buffers are page-locked, and pinning costs time in proportion (2 x 80 MB: ~40 ms beside the context's creation, on the same
+// driver): input files that are smaller than a chunk -- the reference's own test case is 100 KB -- get buffers of their size.
+void choose_chunk_bytes(Options& o) {
+    o.chunk_bytes = o.chunk_mb << 20;
+    uint64_t largest = 0;
+    if (largest_input(o, &largest) && largest + (1u << 20) < o.chunk_bytes) o.chunk_bytes = ((largest >> 20) + 1) << 20;
+}
+
+// ---- the run's contexts.  0, or the exit code of a failure
+int open_shards(const Options& o, const fgpu_params& prm, bool verbose, Run* run) {
     if (o.batch_reads) { fprintf(stderr, "-batch_reads (records split on the host) cannot be combined with -gpus: the shards split their records on their devices\n"); return 1; }
     for (const std::string* f : {&o.read_load_file, &o.read_scan_file}) {      // (before any device is touched)
         struct stat st;
@@ -489,434 +586,247 @@ int main_sharded(const Options& o, const fgpu_params& prm, uint64_t tai, PhaseCl
     }
     const int ndev = fgpu_device_count();
     if (ndev < 1) { fprintf(stderr, "fgpu_create failed (%d): no gfx950 device\n", FGPU_ERR_HIP); return 2; }
-    ShardOptions so;
-    so.n_ranks = o.gpus;
-    so.transport = o.transport == "rccl" ? FGPU_TRANSPORT_RCCL : FGPU_TRANSPORT_COPY;
-    for (int r = 0; r < o.gpus; r++) so.devices.push_back(r % ndev);
     if (ndev < o.gpus) fprintf(stderr, "note: %d read shards on %d device%s: shards share devices\n", o.gpus, ndev, ndev == 1 ? "" : "s");
-    so.prm = prm;
-    so.fastq = o.fastq;
-    so.mercy = o.mercy;
-    so.paired_ends = o.paired_ends;
-    so.no_cleaning = o.no_cleaning;
-    so.verbose = clk.on;
     // every shard reads its share through buffers of its own: chunks no larger than a share needs
-    so.chunk_bytes = o.chunk_bytes;
-    {
-        struct stat st;
-        uint64_t largest = 0;
-        for (const std::string* f : {&o.read_load_file, &o.read_scan_file})
-            if (stat(f->c_str(), &st) == 0 && S_ISREG(st.st_mode)) largest = std::max<uint64_t>(largest, (uint64_t)st.st_size);
-        const uint64_t share = largest / (uint64_t)o.gpus + (4u << 20);
-        if (share < so.chunk_bytes) so.chunk_bytes = ((share >> 20) + 1) << 20;
-    }
-    ShardedRun run(so);
-    if (int rc = run.create()) { fprintf(stderr, "fgpu_create failed (%d): %s\n", rc, run.error().c_str()); return 2; }
-    clk.mark("arguments, sizing, contexts");
-    std::vector<uint8_t> bloom_bytes(tai / 8);
-    std::thread bloom_writer;
-    bool bloom_write_failed = false;
-    struct JoinWriter {
-        std::thread& t;
-        ~JoinWriter() { if (t.joinable()) t.join(); }
-    } join_writer{bloom_writer};
-    auto bloom_file_complete = [&]() -> bool {
-        if (bloom_writer.joinable()) bloom_writer.join();
-        if (bloom_write_failed) fprintf(stderr, "cannot write %s.bloom\n", o.file_prefix.c_str());
-        return !bloom_write_failed;
-    };
-    fgpu_ctx* ctx = run.first_ctx();      // (CHECK reports through it)
-    if (o.from_bloom) {                   // Bloom::load (utils/Bloom.cpp:580-587), the filter on every device
-        FILE* f = fopen(o.bloom_input_file.c_str(), "rb");
-        if (!f) { fprintf(stderr, "cannot open %s\n", o.bloom_input_file.c_str()); return 2; }
-        printf("loading bloom filter from file, nelem %llu \n", (unsigned long long)(tai / 8));
-        const size_t got = fread(bloom_bytes.data(), 1, bloom_bytes.size(), f);
-        fclose(f);
-        if (got != bloom_bytes.size())
-            fprintf(stderr, "note: %s holds %llu of the %llu bytes this run's filter has: the rest stays empty (as in the reference)\n",
-                    o.bloom_input_file.c_str(), (unsigned long long)got, (unsigned long long)(tai / 8));
-        for (int r = 0; r < run.n_ranks(); r++) {
-            ctx = run.ctx(r);
-            CHECK(fgpu_bloom_upload(ctx, FGPU_BLOO2, bloom_bytes.data(), bloom_bytes.size()));
-        }
-        printf("bloom loaded\n");
-    } else {
-        time_t start, stop;
-        time(&start);
-        printf("Weights before load: %f, %f \n", 0.0f, 0.0f);
-        ShardLoadResult lr;
-        if (int rc = run.load(o.read_load_file, &lr)) { fprintf(stderr, "load pass failed (%d): %s\n", rc, run.error().c_str()); return 2; }
-        clk.mark(lr.slices ? "pass 1 (shards, filter slices)" : lr.fixup ? "pass 1 (shards, fix-up protocol)" : "pass 1 (shards, presence protocol)");
-        fprintf(stdout, "\rreads consumed: %lld", (long long)lr.stats.reads_processed);
-        printf("\n");
-        printf("Weights after load: %f, %f \n", lr.w1, lr.w2);
-        printf("Reads processed: %llu\n", (unsigned long long)lr.stats.reads_processed);
-        printf("Unambiguous reads: %llu\n", (unsigned long long)lr.stats.unambiguous_reads);
-        time(&stop);
-        printf("Time to load: %f \n", difftime(stop, start));
-        ctx = run.first_ctx();
-        CHECK(fgpu_bloom_download(ctx, FGPU_BLOO2, bloom_bytes.data(), bloom_bytes.size()));
-        const std::string path = o.file_prefix + ".bloom";       // Bloom::dump, utils/Bloom.cpp:571-578
-        FILE* f = fopen(path.c_str(), "wb");
-        if (!f) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 2; }
-        bloom_writer = std::thread([f, &bloom_bytes, &bloom_write_failed] {
-            if (fwrite(bloom_bytes.data(), 1, bloom_bytes.size(), f) != bloom_bytes.size()) bloom_write_failed = true;
-            if (fclose(f) != 0) bloom_write_failed = true;
-        });
-        printf("bloom dumped \n");
-        clk.mark("bloom download (dump beside pass 2)");
-    }
-    PairFilter short_pf, long_pf;        // src/Faucet.cpp:266-283, as in the single-device run
-    {
-        const uint64_t E = o.estimated_kmers;
-        short_pf.create(o.high_cov ? E / 2 : o.mercy ? E / 10 : E / 20, 0.01f);
-        if (o.paired_ends) long_pf.create(o.high_cov ? E / 2 : o.mercy ? E / 5 : E / 10, 0.01f);
-    }
-    if (o.just_load) return bloom_file_complete() ? 0 : 2;
-    {
-        time_t start, stop;
-        time(&start);
-        float w2 = 0;
-        ctx = run.last_ctx();
-        CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO2, &w2));
-        printf("Weight before read scan: %f \n", w2);
-        run.set_pair_filters(o.no_cleaning ? 0 : short_pf.tai, short_pf.n_hash, o.paired_ends && !o.no_cleaning ? long_pf.tai : 0, long_pf.n_hash);
-        ShardScanResult sr;
-        if (int rc = run.scan(o.read_scan_file, &sr)) { fprintf(stderr, "junction scan failed (%d): %s\n", rc, run.error().c_str()); return 2; }
-        fprintf(stdout, "\rreads scanned: %lld", (long long)sr.stats.reads_processed);
-        if (!o.no_cleaning) CHECK(fgpu_scan_short_pairs_download(ctx, short_pf.bits.data(), short_pf.bits.size()));
-        if (o.paired_ends && !o.no_cleaning) {
-            uint64_t e = 0, ne = 0;      // (the counts are the sum over the shards, sr; the last shard's filter is the run's)
-            CHECK(fgpu_scan_long_pairs_download(ctx, long_pf.bits.data(), long_pf.bits.size(), &e, &ne));
-        }
-        time(&stop);
-        clk.mark("pass 2 (shards)");
-        if (int rc = write_scan_outputs(o, ctx, sr.stats, sr.empty_count, sr.not_empty_count, difftime(stop, start), short_pf, long_pf, clk)) return rc;
-    }
-    clk.mark("pair filter weights");
-    if (!o.no_cleaning)
-        fprintf(stderr, "The contig-graph stage is not part of this build: the load and scan outputs have been written; the reference\n"
-                        "continues from the same calls through integration/faucet_binding.cpp (INTEGRATION.md).\n");
-    if (!bloom_file_complete()) return 2;
-    const int code = o.no_cleaning ? 0 : 3;
-    if (!getenv("FGPU_CLI_TIDY")) {      // (as in the single-device run: the driver releases what the process held)
-        fflush(stdout);
-        fflush(stderr);
-        _exit(code);
-    }
-    return code;
+    uint64_t chunk_bytes = o.chunk_bytes, largest = 0;
+    largest_input(o, &largest);
+    const uint64_t share = largest / (uint64_t)o.gpus + (4u << 20);
+    if (share < chunk_bytes) chunk_bytes = ((share >> 20) + 1) << 20;
+    faucet_host::ShardOptions so = faucet_host::shard_options(o.gpus, o.transport == "rccl" ? FGPU_TRANSPORT_RCCL : FGPU_TRANSPORT_COPY, prm, o.fastq, o.mercy,
+                                                              o.paired_ends, o.no_cleaning, chunk_bytes);
+    so.verbose = verbose;
+    run->shards.reset(new ShardedRun(so));
+    if (int rc = run->shards->create()) { fprintf(stderr, "fgpu_create failed (%d): %s\n", rc, run->shards->error().c_str()); return 2; }
+    return 0;
 }
+
+int open_one_device(const Options& o, const fgpu_params& prm, Run* run) {
+    std::thread pin;   // the two text buffers, pinned beside the context's creation; joined before anything else can fail or read
+    if (!o.batch_reads && !o.from_junctions)
+        pin = std::thread([&o] { for (int i = 0; i < 2; i++) pinned_slot(i, kTextPad + o.chunk_bytes); });
+    const int rc = fgpu_create(&prm, &run->one);
+    if (pin.joinable()) pin.join();
+    if (rc != FGPU_OK) { fprintf(stderr, "fgpu_create failed (%d): %s\n", rc, fgpu_last_error(nullptr)); return 2; }
+    return 0;
+}
+
+// ---- -bloom_file (Bloom::load, utils/Bloom.cpp:580-587): the filter into every context
+int load_bloom_file(const Options& o, const Run& run, BloomFile& bloom) {
+    FILE* f = fopen(o.bloom_input_file.c_str(), "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", o.bloom_input_file.c_str()); return 2; }
+    printf("loading bloom filter from file, nelem %llu \n", (unsigned long long)(o.tai / 8));
+    const size_t got = fread(bloom.bytes.data(), 1, bloom.bytes.size(), f);
+    fclose(f);
+    // Bloom::load reads as many bytes as the filter it has just sized holds and does not look at fread's count: a longer file gives its
+    // head, a shorter one leaves the rest of the (zeroed) filter empty -- e.g. the .bloom of a run that loaded from reads (sized with p1)
+    // restarted with the sizes -fp implies.  Same here; a note on stderr is all that is added.
+    if (got != bloom.bytes.size())
+        fprintf(stderr, "note: %s holds %llu of the %llu bytes this run's filter has: the rest stays empty (as in the reference)\n",
+                o.bloom_input_file.c_str(), (unsigned long long)got, (unsigned long long)(o.tai / 8));
+    for (fgpu_ctx* ctx : run.contexts()) CHECK(fgpu_bloom_upload(ctx, FGPU_BLOO2, bloom.bytes.data(), bloom.bytes.size()));
+    printf("bloom loaded\n");
+    return 0;
+}
+
+// (both ways of pass 1 answer with a ShardLoadResult: the run's counters and the weights of bloo1 / bloo2)
+int load_one_device(fgpu_ctx* ctx, BatchSource& src, PhaseClock& clk, faucet_host::ShardLoadResult* out) {
+    CHECK(fgpu_load_begin(ctx, 0));
+    uint64_t consumed = 0;
+    fgpu_reads r;
+    for (int more; (more = src.next(ctx, &r)) != 0;) {
+        if (more < 0) { fprintf(stderr, "fgpu_text_split failed (%d): %s\n", -more, fgpu_last_error(ctx)); return 2; }
+        const auto t_batch = std::chrono::steady_clock::now();
+        CHECK(fgpu_load_batch(ctx, &r));
+        clk.batch_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_batch).count();
+        consumed += r.n_reads;
+        fprintf(stdout, "\rreads consumed: %lld", (long long)consumed);
+        fflush(stdout);
+    }
+    const auto t_end = std::chrono::steady_clock::now();
+    CHECK(fgpu_load_end(ctx, &out->stats));
+    if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_load_batch calls, %.2f ms in fgpu_load_end\n", clk.batch_ms,
+                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_end).count());
+    clk.mark("pass 1 (read + load)");
+    CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO1, &out->w1));
+    CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO2, &out->w2));
+    return 0;
+}
+
+int load_shards(const Options& o, ShardedRun& run, PhaseClock& clk, faucet_host::ShardLoadResult* out) {
+    if (int rc = run.load(o.read_load_file, out)) { fprintf(stderr, "load pass failed (%d): %s\n", rc, run.error().c_str()); return 2; }
+    clk.mark(out->slices ? "pass 1 (shards, filter slices)" : out->fixup ? "pass 1 (shards, fix-up protocol)" : "pass 1 (shards, presence protocol)");
+    fprintf(stdout, "\rreads consumed: %lld", (long long)out->stats.reads_processed);
+    return 0;
+}
+
+// ---- pass 1 (load_two_filters, utils/Bloom.cpp:267-350), and bloo2 on its way into <prefix>.bloom
+int load_from_reads(const Options& o, const Run& run, PhaseClock& clk, BloomFile& bloom) {
+    std::unique_ptr<BatchSource> src;      // (one device; the shards open their byte ranges themselves)
+    if (!run.shards) {
+        src.reset(new BatchSource(o, o.read_load_file));
+        if (!src->is_open()) { fprintf(stderr, "cannot open %s\n", o.read_load_file.c_str()); return 2; }   // the reference silently reads nothing
+    }
+    time_t start, stop;
+    time(&start);
+    printf("Weights before load: %f, %f \n", 0.0f, 0.0f);
+    faucet_host::ShardLoadResult lo;
+    if (int rc = run.shards ? load_shards(o, *run.shards, clk, &lo) : load_one_device(run.one, *src, clk, &lo)) return rc;
+    printf("\n");
+    printf("Weights after load: %f, %f \n", lo.w1, lo.w2);
+    printf("Reads processed: %llu\n", (unsigned long long)lo.stats.reads_processed);
+    printf("Unambiguous reads: %llu\n", (unsigned long long)lo.stats.unambiguous_reads);
+    time(&stop);
+    printf("Time to load: %f \n", difftime(stop, start));
+    fgpu_ctx* ctx = run.first();           // (every context holds the run's bloo2)
+    CHECK(fgpu_bloom_download(ctx, FGPU_BLOO2, bloom.bytes.data(), bloom.bytes.size()));
+    if (int rc = bloom.start_writing()) return rc;
+    printf("bloom dumped \n");
+    clk.mark("bloom download (dump beside pass 2)");
+    return 0;
+}
+
+// ---- pair filters (src/Faucet.cpp:266-283): created, and their sizes printed, before --just_load_bloom returns
+void create_pair_filters(const Options& o, PairFilter* short_pf, PairFilter* long_pf) {
+    const uint64_t E = o.estimated_kmers;
+    // mercy k-mers lead to more junctions: the reference doubles both filters (src/Faucet.cpp:268-271)
+    short_pf->create(o.high_cov ? E / 2 : o.mercy ? E / 10 : E / 20, 0.01f);
+    if (o.paired_ends) long_pf->create(o.high_cov ? E / 2 : o.mercy ? E / 5 : E / 10, 0.01f);
+}
+
+// ---- -junctions_file <prefix> (src/Faucet.cpp:104-109,289-293): the scan's three files are reloaded instead of being made.  What the
+// reference does next is its contig graph, which is not part of this build: the files are parsed and checked (sizes as the flags imply),
+// the lines the reference prints after reloading are printed, and the program stops where every run of this build stops (exit code 3).
+int reload_scan_files(const Options& o, PairFilter& short_pf, PairFilter& long_pf) {
+    JunctionTable junction_map;
+    printf("Reading from Junction file to build junction map.\n");
+    const long n_lines = read_junctions(o.junctions_prefix + ".junctions", o.k, junction_map);
+    if (n_lines < 0) { fprintf(stderr, "cannot read %s.junctions (missing, or not in the .junctions format for k = %d)\n", o.junctions_prefix.c_str(), o.k); return 2; }
+    if (int rc = load_pair_filter(short_pf, o.junctions_prefix + ".short_pair_filter")) return rc;
+    if (o.paired_ends)
+        if (int rc = load_pair_filter(long_pf, o.junctions_prefix + ".long_pair_filter")) return rc;
+    printf("Weight of short pair filter: %f\n", short_pf.weight());
+    if (o.paired_ends) printf("Weight of long pair filter: %f\n", long_pf.weight());
+    printf("Number of junctions: %llu\n", (unsigned long long)junction_map.size());
+    fprintf(stderr, "The contig-graph stage is not part of this build: -bloom_file / -junctions_file inputs have been read and checked; the\n"
+                    "reference continues from them.\n");
+    return 0;
+}
+
+// FGPU_CLI_TIMES: what the library counted during pass 2
+void tell_scan_diagnostics(const Options& o, fgpu_ctx* ctx) {
+    uint64_t waits = 0;
+    double wait_ms = 0;
+    if (fgpu_diag_host_waits(ctx, &waits, &wait_ms) == FGPU_OK)
+        fprintf(stderr, "[cli]   pass 2: the host waited for the device %llu times, %.2f ms in all\n", (unsigned long long)waits, wait_ms);
+    uint64_t d[6] = {0, 0, 0, 0, 0, 0};
+    if (o.paired_ends && !o.no_cleaning && fgpu_diag_long_pairs(ctx, d) == FGPU_OK)
+        fprintf(stderr, "[cli]   long pair filter on the device: %llu first-end k-mers checked, %llu paired by the filter as their batch found it, %llu inserted; "
+                        "%llu evaluation rounds over %llu batches (at most %llu in one)\n",
+                (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2], (unsigned long long)d[3], (unsigned long long)d[5], (unsigned long long)d[4]);
+    memset(d, 0, sizeof(d));
+    if (fgpu_diag_ovw(ctx, d) == FGPU_OK && (d[2] || d[3] || d[5]))
+        fprintf(stderr, "[cli]   large clusters, walked optimistically: %llu pieces, %llu rounds over %llu windows (%llu piece-rounds kept their log); "
+                        "%llu windows left to the key-ordered walk, %llu to the walk by cluster\n",
+                (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2], (unsigned long long)d[4], (unsigned long long)d[3],
+                (unsigned long long)d[5]);
+}
+
+// pass 2 on the one device: scan_pass.h over this program's batches; the progress line and the phase clock are this side's
+int scan_one_device(const Options& o, fgpu_ctx* ctx, PairFilter& short_pf, PairFilter& long_pf, PhaseClock& clk, faucet_host::ScanPassResult* res) {
+    BatchSource src(o, o.read_scan_file);
+    if (!src.is_open()) { fprintf(stderr, "cannot open %s\n", o.read_scan_file.c_str()); return 2; }
+    const faucet_host::PairTarget none = {nullptr, 0, 0};
+    const faucet_host::PairTarget short_target = {short_pf.bits.data(), short_pf.tai, short_pf.n_hash}, long_target = {long_pf.bits.data(), long_pf.tai, long_pf.n_hash};
+    uint64_t scanned = 0;
+    const auto t_pass = std::chrono::steady_clock::now();
+    auto t_fed = t_pass;
+    const int rc = faucet_host::scan_pass(ctx, o.k, o.no_cleaning ? none : short_target, o.no_cleaning || !o.paired_ends ? none : long_target, o.paired_ends,
+        [&](const faucet_host::EachBatch& each) -> int {
+            fgpu_reads r;
+            for (int more; (more = src.next(ctx, &r)) != 0;) {
+                if (more < 0) { res->failed = "fgpu_text_split"; return -more; }
+                const auto t_scan = std::chrono::steady_clock::now();
+                if (int brc = each(&r)) return brc;
+                clk.scan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_scan).count();
+                scanned += r.n_reads;
+                fprintf(stdout, "\rreads scanned: %lld", (long long)scanned);
+                fflush(stdout);
+            }
+            t_fed = std::chrono::steady_clock::now();
+            return FGPU_OK;
+        }, res);
+    if (rc != FGPU_OK) { fprintf(stderr, "%s failed (%d): %s\n", res->failed, rc, fgpu_last_error(ctx)); return 2; }
+    clk.take_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fed).count();
+    if (clk.on) {
+        fprintf(stderr, "[cli]   %.2f ms in fgpu_scan_batch calls, %.2f ms in fgpu_scan_end (the last walks, the last lists, the pair filters' last batches)\n",
+                clk.scan_ms, clk.take_ms);
+        tell_scan_diagnostics(o, ctx);
+    }
+    return 0;
+}
+
+// pass 2 over the read shards: the last shard ends with the run's junction map and pair filters, the counts are the sum over the shards
+int scan_shards(const Options& o, ShardedRun& run, PairFilter& short_pf, PairFilter& long_pf, faucet_host::ScanPassResult* res) {
+    fgpu_ctx* ctx = run.last_ctx();
+    run.set_pair_filters(o.no_cleaning ? 0 : short_pf.tai, short_pf.n_hash, o.paired_ends && !o.no_cleaning ? long_pf.tai : 0, long_pf.n_hash);
+    faucet_host::ShardScanResult sr;
+    if (int rc = run.scan(o.read_scan_file, &sr)) { fprintf(stderr, "junction scan failed (%d): %s\n", rc, run.error().c_str()); return 2; }
+    fprintf(stdout, "\rreads scanned: %lld", (long long)sr.stats.reads_processed);
+    if (!o.no_cleaning) CHECK(fgpu_scan_short_pairs_download(ctx, short_pf.bits.data(), short_pf.bits.size()));
+    if (o.paired_ends && !o.no_cleaning) {
+        uint64_t e = 0, ne = 0;      // (this shard's counts)
+        CHECK(fgpu_scan_long_pairs_download(ctx, long_pf.bits.data(), long_pf.bits.size(), &e, &ne));
+    }
+    res->stats = sr.stats;
+    res->empty_count = sr.empty_count;
+    res->not_empty_count = sr.not_empty_count;
+    return 0;
+}
+
+// ---- pass 2 (ReadScanner::scanReads, src/ReadScanner.cpp:284-359; printScanSummary :19-27) and the files it makes
+int scan_and_write(const Options& o, const Run& run, PairFilter& short_pf, PairFilter& long_pf, PhaseClock& clk) {
+    time_t start, stop;
+    time(&start);
+    float w2 = 0;
+    fgpu_ctx* ctx = run.last();
+    CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO2, &w2));
+    printf("Weight before read scan: %f \n", w2);
+    faucet_host::ScanPassResult res;
+    if (int rc = run.shards ? scan_shards(o, *run.shards, short_pf, long_pf, &res) : scan_one_device(o, ctx, short_pf, long_pf, clk, &res)) return rc;
+    time(&stop);
+    clk.mark(run.shards ? "pass 2 (shards)" : "pass 2 (read + scan)");
+    return write_scan_outputs(o, ctx, res.stats, res.empty_count, res.not_empty_count, difftime(stop, start), short_pf, long_pf, clk);
+}
+
+}  // namespace
 
 int main(int argc, char** argv) {
     PhaseClock clk;
     Options o;
     if (handle_arguments(argc, argv, o) == 1) return 1;
-    fgpu_ctx* ctx = nullptr;
     if (o.k < 1 || o.k > 31) { fprintf(stderr, "k must be in 1..31 on this build\n"); return 1; }
-
-    // ---- filter sizing: getBloomFilterFromReads / getBloomFilterFromFile (src/Faucet.cpp:185-219)
-    uint64_t tai = 0;
-    int32_t n_hash = 0, bits = 0;
-    if (o.from_bloom) {
-        if (o.two_hash) fgpu_size_two_hash(o.estimated_kmers, o.fp_rate, &bits, &tai, &n_hash);
-        else fgpu_size_optimal(o.estimated_kmers, o.fp_rate, &bits, &tai, &n_hash);
-        printf("Bits per kmer: %d \n", bits);                       // create_bloom_filter_2_hash / _optimal, utils/Bloom.cpp:204-247
-        if (o.two_hash) {
-            printf("Estimated items: %llu \n", (unsigned long long)o.estimated_kmers);
-            printf("Estimated bloom size: %llu .\n", (unsigned long long)(o.estimated_kmers * (uint64_t)bits));
-        }
-        printf("BF memory: %f MB\n", (float)((o.estimated_kmers * (uint64_t)bits) / 8ULL / 1024ULL) / 1024);
-        printf("Number of hash functions: %d \n", n_hash);
-    } else {
-        int32_t iters = 0;
-        double p1 = fgpu_solve_p1(o.estimated_kmers, o.singletons, o.fp_rate, &iters);
-        if (p1 < 0) {   // the reference prints a message and goes on with nonsense sizes; we refuse
-            fprintf(stderr, "Signs of f(lower_bound) and f(upper_bound) must be opposites: check -singletons (must be > 0)\n");
-            return 1;
-        }
-        printf("After %d iterations the root is: %g\n", iters, p1);
-        printf("p2 is %g p1 estimated as %g\n", (double)o.fp_rate, p1);
-        fgpu_size_optimal(o.estimated_kmers, (float)p1, &bits, &tai, &n_hash);
-        for (int i = 0; i < 2; i++) {   // printed once per filter, utils/Bloom.cpp:234-243
-            printf("Bits per kmer: %d \n", bits);
-            printf("BF memory: %f MB\n", (float)((o.estimated_kmers * (uint64_t)bits) / 8ULL / 1024ULL) / 1024);
-            printf("Number of hash functions: %d \n", n_hash);
-        }
-    }
-
-    fgpu_params prm;
-    memset(&prm, 0, sizeof(prm));
-    prm.k = o.k;
-    prm.j = o.j;
-    prm.max_spacer_dist = o.max_spacer_dist;
-    prm.n_hash = n_hash;
-    prm.tai = tai;
-    // scanInputRead's lists feed the pair filters and the pair counts, all on the device: the short filter's adds are order-free
-    // (fgpu_scan_short_pairs), the long filter's check-then-insert loop is iterated to the sequential result (fgpu_scan_long_pairs); with
-    // --no_cleaning only the paired-end loop's two counts are left of them
-    const bool record_lists = !o.no_cleaning || o.paired_ends;
-    const bool device_short_pairs = !o.no_cleaning;
-    if (record_lists) prm.flags |= FGPU_FLAG_RECORD_STOPS;
-    prm.flags |= FGPU_FLAG_KEY_ORDER_FROM_START;   // real genomes have repeats: a few launches per window against a first batch walked by cluster
-    if (o.mercy) prm.flags |= FGPU_FLAG_MERCY;
-    // The text buffers are page-locked, and pinning costs time in proportion (2 x 80 MB: ~40 ms beside the context's creation, on the same
-    // driver): input files that are smaller than a chunk -- the reference's own test case is 100 KB -- get buffers of their size.
-    o.chunk_bytes = o.chunk_mb << 20;
-    {
-        uint64_t largest = 0;
-        bool all_regular = true;
-        for (const std::string* f : {&o.read_load_file, &o.read_scan_file}) {
-            struct stat st;
-            if (f->empty()) continue;
-            if (stat(f->c_str(), &st) == 0 && S_ISREG(st.st_mode)) largest = std::max<uint64_t>(largest, (uint64_t)st.st_size);
-            else all_regular = false;
-        }
-        if (all_regular && largest + (1u << 20) < o.chunk_bytes) o.chunk_bytes = ((largest >> 20) + 1) << 20;
-    }
-    if (o.gpus > 1 && !o.from_junctions) return main_sharded(o, prm, tai, clk);
-    {
-        std::thread pin;   // (joined before anything else can fail or read)
-        if (!o.batch_reads && !o.from_junctions)
-            pin = std::thread([&o] { for (int i = 0; i < 2; i++) pinned_slot(i, kTextPad + o.chunk_bytes); });
-        int rc = fgpu_create(&prm, &ctx);
-        if (pin.joinable()) pin.join();
-        if (rc != FGPU_OK) { fprintf(stderr, "fgpu_create failed (%d): %s\n", rc, fgpu_last_error(nullptr)); return 2; }
-    }
-    // fgpu_create returns while a thread of the library is still creating the walk's streams and loading code objects: every way out of main
-    // goes through fgpu_destroy, which joins it, before the HIP runtime is torn down.  The one exception is the _exit at the very
-    // end, after both passes -- the first scan call has joined the thread by then.
-    struct CloseContext {
-        fgpu_ctx*& c;
-        ~CloseContext() { if (c) { fgpu_destroy(c); c = nullptr; } }
-    } close_context{ctx};
-    clk.mark("arguments, sizing, fgpu_create");
-    std::vector<uint8_t> bloom_bytes(tai / 8);
-    std::thread bloom_writer;
-    bool bloom_write_failed = false;
-    struct JoinWriter {      // every way out of main waits for the .bloom file to be complete
-        std::thread& t;
-        ~JoinWriter() { if (t.joinable()) t.join(); }
-    } join_writer{bloom_writer};
-    // ... and every SUCCESSFUL way out looks at how that write went (a short write of --just_load_bloom's only output is not exit code 0)
-    auto bloom_file_complete = [&]() -> bool {
-        if (bloom_writer.joinable()) bloom_writer.join();
-        if (bloom_write_failed) fprintf(stderr, "cannot write %s.bloom\n", o.file_prefix.c_str());
-        return !bloom_write_failed;
-    };
-
-    // ---- pass 1 (load_two_filters, utils/Bloom.cpp:267-350) or -bloom_file (Bloom::load, :580-587)
-    if (o.from_bloom) {
-        FILE* f = fopen(o.bloom_input_file.c_str(), "rb");
-        if (!f) { fprintf(stderr, "cannot open %s\n", o.bloom_input_file.c_str()); return 2; }
-        printf("loading bloom filter from file, nelem %llu \n", (unsigned long long)(tai / 8));
-        size_t got = fread(bloom_bytes.data(), 1, bloom_bytes.size(), f);
-        fclose(f);
-        // Bloom::load (utils/Bloom.cpp:580-587) reads as many bytes as the filter it has just sized holds and does not look at fread's
-        // count: a longer file gives its head, a shorter one leaves the rest of the (zeroed) filter empty -- e.g. the .bloom of a run that
-        // loaded from reads (sized with p1) restarted with the sizes -fp implies.  Same here; a note on stderr is all that is added.
-        if (got != bloom_bytes.size())
-            fprintf(stderr, "note: %s holds %llu of the %llu bytes this run's filter has: the rest stays empty (as in the reference)\n",
-                    o.bloom_input_file.c_str(), (unsigned long long)got, (unsigned long long)(tai / 8));
-        CHECK(fgpu_bloom_upload(ctx, FGPU_BLOO2, bloom_bytes.data(), bloom_bytes.size()));
-        printf("bloom loaded\n");
-    } else {
-        BatchSource src(o, o.read_load_file);
-        if (!src.is_open()) { fprintf(stderr, "cannot open %s\n", o.read_load_file.c_str()); return 2; }   // the reference silently reads nothing
-        time_t start, stop;
-        time(&start);
-        printf("Weights before load: %f, %f \n", 0.0f, 0.0f);
-        CHECK(fgpu_load_begin(ctx, 0));
-        uint64_t consumed = 0;
-        fgpu_reads r;
-        for (int more; (more = src.next(ctx, &r)) != 0;) {
-            if (more < 0) { fprintf(stderr, "fgpu_text_split failed (%d): %s\n", -more, fgpu_last_error(ctx)); return 2; }
-            const auto t_batch = std::chrono::steady_clock::now();
-            CHECK(fgpu_load_batch(ctx, &r));
-            clk.batch_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_batch).count();
-            consumed += r.n_reads;
-            fprintf(stdout, "\rreads consumed: %lld", (long long)consumed);
-            fflush(stdout);
-        }
-        fgpu_load_stats ls;
-        const auto t_end = std::chrono::steady_clock::now();
-        CHECK(fgpu_load_end(ctx, &ls));
-        if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_load_batch calls, %.2f ms in fgpu_load_end\n", clk.batch_ms,
-                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_end).count());
-        clk.mark("pass 1 (read + load)");
-        float w1 = 0, w2 = 0;
-        CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO1, &w1));
-        CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO2, &w2));
-        printf("\n");
-        printf("Weights after load: %f, %f \n", w1, w2);
-        printf("Reads processed: %llu\n", (unsigned long long)ls.reads_processed);
-        printf("Unambiguous reads: %llu\n", (unsigned long long)ls.unambiguous_reads);
-        time(&stop);
-        printf("Time to load: %f \n", difftime(stop, start));
-        CHECK(fgpu_bloom_download(ctx, FGPU_BLOO2, bloom_bytes.data(), bloom_bytes.size()));
-        const std::string path = o.file_prefix + ".bloom";       // Bloom::dump, utils/Bloom.cpp:571-578
-        FILE* f = fopen(path.c_str(), "wb");
-        if (!f) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 2; }
-        // the bytes are in host memory; writing them out (64 MiB - 1 GiB) runs beside pass 2 and is waited for before the process ends
-        bloom_writer = std::thread([f, &bloom_bytes, &bloom_write_failed] {
-            if (fwrite(bloom_bytes.data(), 1, bloom_bytes.size(), f) != bloom_bytes.size()) bloom_write_failed = true;
-            if (fclose(f) != 0) bloom_write_failed = true;
-        });
-        printf("bloom dumped \n");
-        clk.mark("bloom download (dump beside pass 2)");
-    }
-    // ---- pair filters (src/Faucet.cpp:266-283): created, and their sizes printed, before --just_load_bloom returns
+    if (int rc = size_filters(o)) return rc;
+    const fgpu_params prm = context_params(o);
+    choose_chunk_bytes(o);
+    const bool sharded = o.gpus > 1 && !o.from_junctions;
+    Run run;                    // (declared before the .bloom writer: the file is complete before the contexts go)
+    if (int rc = sharded ? open_shards(o, prm, clk.on, &run) : open_one_device(o, prm, &run)) return rc;
+    clk.mark(sharded ? "arguments, sizing, contexts" : "arguments, sizing, fgpu_create");
+    BloomFile bloom(o.file_prefix, o.tai);
+    if (int rc = o.from_bloom ? load_bloom_file(o, run, bloom) : load_from_reads(o, run, clk, bloom)) return rc;
     PairFilter short_pf, long_pf;
-    {
-        const uint64_t E = o.estimated_kmers;
-        // mercy k-mers lead to more junctions: the reference doubles both filters (src/Faucet.cpp:268-271)
-        short_pf.create(o.high_cov ? E / 2 : o.mercy ? E / 10 : E / 20, 0.01f);
-        if (o.paired_ends) long_pf.create(o.high_cov ? E / 2 : o.mercy ? E / 5 : E / 10, 0.01f);
-    }
-    if (o.just_load) return bloom_file_complete() ? 0 : 2;
-
-    // ---- -junctions_file <prefix> (src/Faucet.cpp:104-109,289-293): the scan's three files are reloaded instead of being made.  What the
-    // reference does next is its contig graph, which is not part of this build: the files are parsed and checked (sizes as the flags imply),
-    // the lines the reference prints after reloading are printed, and the program stops where every run of this build stops (exit code 3).
+    create_pair_filters(o, &short_pf, &long_pf);
+    if (o.just_load) return bloom.complete() ? 0 : 2;
     if (o.from_junctions) {
-        JunctionTable junction_map;
-        printf("Reading from Junction file to build junction map.\n");
-        const long n_lines = read_junctions(o.junctions_prefix + ".junctions", o.k, junction_map);
-        if (n_lines < 0) { fprintf(stderr, "cannot read %s.junctions (missing, or not in the .junctions format for k = %d)\n", o.junctions_prefix.c_str(), o.k); return 2; }
-        if (int rc = load_pair_filter(short_pf, o.junctions_prefix + ".short_pair_filter")) return rc;
-        if (o.paired_ends)
-            if (int rc = load_pair_filter(long_pf, o.junctions_prefix + ".long_pair_filter")) return rc;
-        printf("Weight of short pair filter: %f\n", short_pf.weight());
-        if (o.paired_ends) printf("Weight of long pair filter: %f\n", long_pf.weight());
-        printf("Number of junctions: %llu\n", (unsigned long long)junction_map.size());
-        fprintf(stderr, "The contig-graph stage is not part of this build: -bloom_file / -junctions_file inputs have been read and checked; the\n"
-                        "reference continues from them.\n");
-        return bloom_file_complete() ? 3 : 2;
+        if (int rc = reload_scan_files(o, short_pf, long_pf)) return rc;
+        return bloom.complete() ? 3 : 2;
     }
-
-    // ---- pass 2 (ReadScanner::scanReads, src/ReadScanner.cpp:284-359; printScanSummary :19-27)
-    {
-        time_t start, stop;
-        time(&start);
-        float w2 = 0;
-        CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO2, &w2));
-        printf("Weight before read scan: %f \n", w2);
-        uint64_t empty_count = 0, not_empty_count = 0;
-        fgpu_scan_stats ss;
-        // One scan of the file.  0 = done, 2 = fatal (-1: a status only library versions before the scan journal could return).
-        auto scan_once = [&]() -> int {
-            BatchSource src(o, o.read_scan_file);
-            if (!src.is_open()) { fprintf(stderr, "cannot open %s\n", o.read_scan_file.c_str()); return 2; }
-            auto failed = [&](const char* what, int rc) -> int {
-                const std::string msg = fgpu_last_error(ctx);
-                if (rc == FGPU_ERR_STATE && msg.find("lazy-flag") != std::string::npos) return -1;
-                fprintf(stderr, "%s failed (%d): %s\n", what, rc, msg.c_str());
-                return 2;
-            };
-            int rc = device_short_pairs ? fgpu_scan_short_pairs(ctx, short_pf.tai, short_pf.n_hash, 0) : FGPU_OK;
-            if (rc != FGPU_OK) return failed("fgpu_scan_short_pairs", rc);
-            // scanReads' paired-end loop (src/ReadScanner.cpp:317-343): on the device, from the same lists, in file order
-            bool host_long_pairs = false;
-            if (o.paired_ends) {
-                rc = o.no_cleaning ? fgpu_scan_long_pairs(ctx, 0, 0, FGPU_LONG_PAIRS_COUNT) : fgpu_scan_long_pairs(ctx, long_pf.tai, long_pf.n_hash, FGPU_LONG_PAIRS_FILTER);
-                if (rc == FGPU_ERR_NOMEM && !o.no_cleaning) {
-                    // the device cannot hold the filter's working state (4 bytes per filter bit; --high_cov sizes the filter at E / 2 x 9 bits,
-                    // src/Faucet.cpp:279-280): the loop runs HERE instead, over the lists the device hands out (pair_loop.h) -- the reference
-                    // has no such limit, so neither has the command line
-                    fprintf(stderr, "note: the long pair filter (%llu bits) does not fit the device's fixed-point form; the paired-end loop runs on the host\n",
-                            (unsigned long long)long_pf.tai);
-                    host_long_pairs = true;
-                    rc = fgpu_scan_long_pairs(ctx, 0, 0, FGPU_LONG_PAIRS_OFF);
-                    if (rc == FGPU_OK && device_short_pairs) rc = fgpu_scan_short_pairs(ctx, short_pf.tai, short_pf.n_hash, 1);   // (the lists come to the host)
-                }
-                if (rc != FGPU_OK) return failed("fgpu_scan_long_pairs", rc);
-            }
-            faucet_host::HostLongPairs hlp(long_pf.bits.data(), long_pf.tai, long_pf.n_hash, o.k, true);
-            std::vector<fgpu_stop> stops;
-            std::vector<uint64_t> batch_reads;
-            auto take_lists = [&](bool all) -> int {     // one batch's lists (after a batch call: the batch before it), or all that are left
-                for (;;) {
-                    uint64_t n_stops = 0;
-                    int64_t seq = -1;
-                    int trc = fgpu_scan_take_stops(ctx, stops.data(), stops.size(), &n_stops, &seq);
-                    if (trc == FGPU_ERR_CAPACITY && seq >= 0) { stops.resize((size_t)(n_stops + n_stops / 4 + 16)); continue; }
-                    if (trc != FGPU_OK) return failed("fgpu_scan_take_stops", trc);
-                    if (seq < 0) return 0;
-                    hlp.batch(stops.data(), n_stops, batch_reads[(size_t)seq]);
-                    if (!all) return 0;
-                }
-            };
-            rc = fgpu_scan_begin(ctx);
-            if (rc != FGPU_OK) return failed("fgpu_scan_begin", rc);
-            uint64_t scanned = 0;
-            fgpu_reads r;
-            for (int more; (more = src.next(ctx, &r)) != 0;) {
-                if (more < 0) return failed("fgpu_text_split", -more);
-                const auto t_scan = std::chrono::steady_clock::now();
-                if ((rc = fgpu_scan_batch(ctx, &r)) != FGPU_OK) return failed("fgpu_scan_batch", rc);
-                clk.scan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_scan).count();
-                if (host_long_pairs) {
-                    batch_reads.push_back(r.n_reads);
-                    if (batch_reads.size() > 1) { const int trc = take_lists(false); if (trc) return trc; }
-                }
-                scanned += r.n_reads;
-                fprintf(stdout, "\rreads scanned: %lld", (long long)scanned);
-                fflush(stdout);
-            }
-            const auto t_end = std::chrono::steady_clock::now();
-            if ((rc = fgpu_scan_end(ctx, &ss)) != FGPU_OK) return failed("fgpu_scan_end", rc);
-            clk.take_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_end).count();
-            if (device_short_pairs && (rc = fgpu_scan_short_pairs_download(ctx, short_pf.bits.data(), short_pf.bits.size())) != FGPU_OK)
-                return failed("fgpu_scan_short_pairs_download", rc);
-            if (host_long_pairs) {
-                const int trc = take_lists(true);
-                if (trc) return trc;
-                empty_count = hlp.empty_count;
-                not_empty_count = hlp.not_empty_count;
-            } else
-            if (o.paired_ends) {
-                rc = o.no_cleaning ? fgpu_scan_long_pairs_download(ctx, nullptr, 0, &empty_count, &not_empty_count)
-                                   : fgpu_scan_long_pairs_download(ctx, long_pf.bits.data(), long_pf.bits.size(), &empty_count, &not_empty_count);
-                if (rc != FGPU_OK) return failed("fgpu_scan_long_pairs_download", rc);
-            }
-            return 0;
-        };
-        // (a preview of the junction walk that the library cannot repair is absorbed inside the library: it keeps the scan's batches in HBM and
-        // scans them again by itself -- nothing is read twice here, which is what lets both inputs be pipes)
-        const int src_rc = scan_once();
-        if (src_rc == -1) { fprintf(stderr, "scan failed: %s\n", fgpu_last_error(ctx)); return 2; }
-        if (src_rc) return src_rc;
-        time(&stop);
-        if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_scan_batch calls, %.2f ms in fgpu_scan_end (the last walks, the last lists, the pair filters' last batches)\n",
-                            clk.scan_ms, clk.take_ms);
-        if (clk.on) {
-            uint64_t waits = 0;
-            double wait_ms = 0;
-            if (fgpu_diag_host_waits(ctx, &waits, &wait_ms) == FGPU_OK)
-                fprintf(stderr, "[cli]   pass 2: the host waited for the device %llu times, %.2f ms in all\n", (unsigned long long)waits, wait_ms);
-        }
-        if (clk.on && o.paired_ends && !o.no_cleaning) {
-            uint64_t d[6] = {0, 0, 0, 0, 0, 0};
-            if (fgpu_diag_long_pairs(ctx, d) == FGPU_OK)
-                fprintf(stderr, "[cli]   long pair filter on the device: %llu first-end k-mers checked, %llu paired by the filter as their batch found it, %llu inserted; "
-                                "%llu evaluation rounds over %llu batches (at most %llu in one)\n",
-                        (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2], (unsigned long long)d[3], (unsigned long long)d[5], (unsigned long long)d[4]);
-        }
-        if (clk.on) {
-            uint64_t d[6] = {0, 0, 0, 0, 0, 0};
-            if (fgpu_diag_ovw(ctx, d) == FGPU_OK && (d[2] || d[3] || d[5]))
-                fprintf(stderr, "[cli]   large clusters, walked optimistically: %llu pieces, %llu rounds over %llu windows (%llu piece-rounds kept their log); "
-                                "%llu windows left to the key-ordered walk, %llu to the walk by cluster\n",
-                        (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2], (unsigned long long)d[4], (unsigned long long)d[3],
-                        (unsigned long long)d[5]);
-        }
-        clk.mark("pass 2 (read + scan)");
-        if (int rc = write_scan_outputs(o, ctx, ss, empty_count, not_empty_count, difftime(stop, start), short_pf, long_pf, clk)) return rc;
-    }
+    if (int rc = scan_and_write(o, run, short_pf, long_pf, clk)) return rc;
     clk.mark("pair filter weights");
     if (!o.no_cleaning)
         fprintf(stderr, "The contig-graph stage is not part of this build: the load and scan outputs have been written; the reference\n"
                         "continues from the same calls through integration/faucet_binding.cpp (INTEGRATION.md).\n");
-    if (!bloom_file_complete()) return 2;                  // (_exit below skips destructors)
+    if (!bloom.complete()) return 2;                  // (_exit below skips destructors)
     const int code = o.no_cleaning ? 0 : 3;
     // Every output file is closed and both passes have ended with a synchronised device.  Returning several hundred HBM buffers one by
     // one, unpinning the text buffers and unloading the HIP runtime took 0.15 s of a 0.9 s run and changes nothing the caller can see:
@@ -926,8 +836,7 @@ int main(int argc, char** argv) {
         fflush(stderr);
         _exit(code);
     }
-    fgpu_destroy(ctx);
-    ctx = nullptr;
+    run.close();
     clk.mark("fgpu_destroy");
     return code;
 }

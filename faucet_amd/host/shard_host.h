@@ -62,6 +62,24 @@ struct ShardOptions {
     bool verbose = false;                 // FGPU_CLI_TIMES: per-rank stage times on stderr
 };
 
+// The options of a run of n_ranks read shards: rank r on device r % fgpu_device_count() (fewer devices than shards: they share).  The caller
+// has made sure there is a device (the hosts word that failure differently); the pair filters follow with ShardedRun::set_pair_filters.
+inline ShardOptions shard_options(int n_ranks, int transport, const fgpu_params& prm, bool fastq, bool mercy, bool paired_ends, bool no_cleaning,
+                                  uint64_t chunk_bytes) {
+    ShardOptions so;
+    so.n_ranks = n_ranks;
+    so.transport = transport;
+    const int ndev = std::max(fgpu_device_count(), 1);
+    for (int r = 0; r < n_ranks; r++) so.devices.push_back(r % ndev);
+    so.prm = prm;
+    so.fastq = fastq;
+    so.mercy = mercy;
+    so.paired_ends = paired_ends;
+    so.no_cleaning = no_cleaning;
+    so.chunk_bytes = chunk_bytes;
+    return so;
+}
+
 struct ShardLoadResult {
     fgpu_load_stats stats;                // summed over the shards = the sequential run's
     float w1 = 0, w2 = 0;                 // Bloom::weight of the run's bloo1 / bloo2
@@ -439,33 +457,14 @@ public:
                 // all the preview of their pure stage needs (fgpu_scan_import_hint); the hint never enters a result.
                 bool shown = n == 1;
                 const uint64_t quarter = (cuts[1] - cuts[0]) / 4;
-                auto show = [&]() -> int {
-                    uint64_t n_entries = 0;
-                    RANK_CHECK(fgpu_scan_table_entries(c, &n_entries));
-                    RANK_CHECK(fgpu_device_alloc(c, std::max<uint64_t>(n_entries, 1) * FGPU_TABLE_ENTRY_BYTES, &hint_buf));
-                    uint64_t got = 0;
-                    RANK_CHECK(fgpu_scan_export_table(c, hint_buf, std::max<uint64_t>(n_entries, 1) * FGPU_TABLE_ENTRY_BYTES, &got));
-                    for (int q = 1; q < n; q++) GROUP_CHECK(fgpu_group_send_async(group_, 0, q, hint_buf, got * FGPU_TABLE_ENTRY_BYTES));
-                    announce(&hint_, got, nullptr);
-                    shown = true;
-                    return FGPU_OK;
-                };
                 // Round 6: the rank above this one has nobody to pass it a table, so it is shown a second, later state of this one (after 7/10 of the
                 // shard): its planes and candidate planes are made against a table a few million keys short of the one it is handed, and its
                 // hop is the short one of every later rank (fgpu_scan_refresh_prepared).  Sent without waiting: the scan goes on beside the copy.
                 bool shown_late = n == 1 || !late_hints;
                 const uint64_t late_at = (cuts[1] - cuts[0]) / 10 * 7;
-                auto show_late = [&]() -> int {
-                    uint64_t n_entries = 0;
-                    RANK_CHECK(fgpu_scan_table_entries(c, &n_entries));
-                    RANK_CHECK(fgpu_device_alloc(c, std::max<uint64_t>(n_entries, 1) * FGPU_TABLE_ENTRY_BYTES, &late_buf));
-                    uint64_t got = 0;
-                    RANK_CHECK(fgpu_scan_export_table(c, late_buf, std::max<uint64_t>(n_entries, 1) * FGPU_TABLE_ENTRY_BYTES, &got));
-                    GROUP_CHECK(fgpu_group_send_async(group_, 0, 1, late_buf, got * FGPU_TABLE_ENTRY_BYTES));
-                    announce(&late_[1], got, nullptr);
-                    shown_late = true;
-                    return FGPU_OK;
-                };
+                // (both previews: show_table -- asynchronous sends, announced once they are queued)
+                auto show = [&]() -> int { shown = true; return show_table(&hint_buf, 1, n, &hint_); };
+                auto show_late = [&]() -> int { shown_late = true; return show_table(&late_buf, 1, 2, &late_[1]); };
                 RANK_TRY(for_each_batch(r, path, cuts, [&](const fgpu_reads* b) { return fgpu_scan_batch(c, b); },
                                         [&](uint64_t bytes_done) -> int {
                                             if (!shown && bytes_done >= quarter) { const int src = show(); if (src != FGPU_OK) return src; }
@@ -483,8 +482,7 @@ public:
                 auto take_hint = [&](bool wait, bool use) -> int {
                     uint64_t n_entries = 0;
                     if (!announced(&hint_, wait, &n_entries, nullptr)) return aborted_ ? FGPU_ERR_STATE : FGPU_OK;
-                    RANK_CHECK(fgpu_device_alloc(c, std::max<uint64_t>(n_entries, 1) * FGPU_TABLE_ENTRY_BYTES, &hint_buf));
-                    GROUP_CHECK(fgpu_group_recv(group_, r, 0, hint_buf, n_entries * FGPU_TABLE_ENTRY_BYTES));
+                    RANK_TRY(receive_table(r, 0, n_entries, &hint_buf));
                     if (use) RANK_CHECK(fgpu_scan_import_hint(c, hint_buf, n_entries));
                     have_hint = true;
                     return FGPU_OK;
@@ -501,8 +499,7 @@ public:
                     // keys that rank created (fgpu_scan_refresh_prepared, faucet_gpu.h)
                     uint64_t n_late = 0;
                     if (!announced(&late_[(size_t)r], true, &n_late, nullptr)) { err_[(size_t)r] = "the run was aborted while this rank waited for the fresher preview"; return FGPU_ERR_STATE; }
-                    RANK_CHECK(fgpu_device_alloc(c, std::max<uint64_t>(n_late, 1) * FGPU_TABLE_ENTRY_BYTES, &late_buf));
-                    GROUP_CHECK(fgpu_group_recv(group_, r, r - 1, late_buf, n_late * FGPU_TABLE_ENTRY_BYTES));
+                    RANK_TRY(receive_table(r, r - 1, n_late, &late_buf));
                     RANK_CHECK(fgpu_scan_import_hint(c, late_buf, n_late));
                     RANK_CHECK(fgpu_scan_refresh_prepared(c));
                 }
@@ -510,8 +507,7 @@ public:
                 uint64_t n_in = 0;
                 fgpu_scan_stats carried;
                 if (!announced(&chain_[(size_t)r], true, &n_in, &carried)) { err_[(size_t)r] = "the run was aborted while this rank waited for the junction table"; return FGPU_ERR_STATE; }
-                RANK_CHECK(fgpu_device_alloc(c, std::max<uint64_t>(n_in, 1) * FGPU_TABLE_ENTRY_BYTES, &table_in));
-                GROUP_CHECK(fgpu_group_recv(group_, r, r - 1, table_in, n_in * FGPU_TABLE_ENTRY_BYTES));
+                RANK_TRY(receive_table(r, r - 1, n_in, &table_in));
                 if (late_hints && r + 1 < n) {                       // pass it on before walking on it: the copy runs beside the walk
                     GROUP_CHECK(fgpu_group_send_async(group_, r, r + 1, table_in, n_in * FGPU_TABLE_ENTRY_BYTES));
                     announce(&late_[(size_t)r + 1], n_in, nullptr);
@@ -526,10 +522,8 @@ public:
             }
             if (o_.paired_ends) RANK_CHECK(fgpu_scan_long_pairs_download(c, nullptr, 0, &empty[(size_t)r], &not_empty[(size_t)r]));
             if (r < n - 1) {
-                uint64_t n_out = 0, got = 0;
-                RANK_CHECK(fgpu_scan_table_entries(c, &n_out));
-                RANK_CHECK(fgpu_device_alloc(c, std::max<uint64_t>(n_out, 1) * FGPU_TABLE_ENTRY_BYTES, &table_out));
-                RANK_CHECK(fgpu_scan_export_table(c, table_out, std::max<uint64_t>(n_out, 1) * FGPU_TABLE_ENTRY_BYTES, &got));
+                uint64_t got = 0;
+                RANK_TRY(export_table(r, &table_out, &got));
                 announce(&chain_[(size_t)r + 1], got, &st);
                 GROUP_CHECK(fgpu_group_send(group_, r, r + 1, table_out, got * FGPU_TABLE_ENTRY_BYTES));
                 RANK_TRY(move_pair_filters(r, short_pairs, long_filter, true));
@@ -617,6 +611,33 @@ private:
         *n = a->n;
         if (st) *st = a->stats;
         return true;
+    }
+
+    // the rank's junction table as it stands, exported into a buffer of its size: *buf (freed by the caller's Deferred), *got entries
+    int export_table(int r, void** buf, uint64_t* got) {
+        fgpu_ctx* c = ctx_[(size_t)r];
+        uint64_t n_entries = 0;
+        RANK_CHECK(fgpu_scan_table_entries(c, &n_entries));
+        const uint64_t bytes = std::max<uint64_t>(n_entries, 1) * FGPU_TABLE_ENTRY_BYTES;
+        RANK_CHECK(fgpu_device_alloc(c, bytes, buf));
+        RANK_CHECK(fgpu_scan_export_table(c, *buf, bytes, got));
+        return FGPU_OK;
+    }
+    // ... and a table of n_entries that rank `from` has announced, received into a buffer of its size
+    int receive_table(int r, int from, uint64_t n_entries, void** buf) {
+        fgpu_ctx* c = ctx_[(size_t)r];
+        RANK_CHECK(fgpu_device_alloc(c, std::max<uint64_t>(n_entries, 1) * FGPU_TABLE_ENTRY_BYTES, buf));
+        GROUP_CHECK(fgpu_group_recv(group_, r, from, *buf, n_entries * FGPU_TABLE_ENTRY_BYTES));
+        return FGPU_OK;
+    }
+    // the first rank shows ranks [to, to_end) its table as it stands -- sent without waiting: its scan goes on beside the copies -- and raises `a`
+    int show_table(void** buf, int to, int to_end, Announce* a) {
+        const int r = 0;
+        uint64_t got = 0;
+        RANK_TRY(export_table(r, buf, &got));
+        for (int q = to; q < to_end; q++) GROUP_CHECK(fgpu_group_send_async(group_, r, q, *buf, got * FGPU_TABLE_ENTRY_BYTES));
+        announce(a, got, nullptr);
+        return FGPU_OK;
     }
 
     // the two pair filters travel with the junction table: what rank r ends with is what rank r + 1 starts from (adds only; check-then-insert

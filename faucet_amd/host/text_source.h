@@ -5,6 +5,7 @@
 // page-locked buffers, read ahead by a thread of its own -- and the library applies that loop on the device; it carries the unconsumed tail
 // (an incomplete record) over to the next call.  Works on non-seekable input.  A source may be limited to a byte range [begin, end) of a
 // regular file: the range of one read shard (record_cuts below), read by the host thread that drives the shard's GPU.
+// ReadSource is that loop on the host, for callers that split their records themselves.
 #pragma once
 #include <errno.h>
 #include <fcntl.h>
@@ -19,6 +20,7 @@
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
+#include <fstream>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -246,6 +248,38 @@ private:
     std::thread reader_;
     std::mutex m_;
     std::condition_variable cv_;
+};
+
+// Record splitting on the HOST, exactly as the reference's loops do it (utils/Bloom.cpp:280-282,340; src/ReadScanner.cpp:306-308,349):
+//   while (getline(header)) { getline(sequence); ...; if (fastq) getline, getline; }
+// cut into batches of sequence lines: the command line's -batch_reads, and the binding (integration/faucet_binding.cpp), which reads its
+// input the way the program around it does.  Works on non-seekable input (the reference is fed process substitutions,
+// src/stream_data_from_urls_list.sh:12-15).
+class ReadSource {
+public:
+    ReadSource(const std::string& path, bool fastq) : in_(path.c_str()), fastq_(fastq) {}
+    bool is_open() const { return in_.is_open(); }
+    // next batch of at most max_reads sequence lines (host pointers, valid until the next call); false when the input is exhausted
+    bool next(uint64_t max_reads, fgpu_reads* out) {
+        bases_.clear();
+        offsets_.assign(1, 0);
+        std::string line;
+        while (offsets_.size() - 1 < max_reads && std::getline(in_, line)) {
+            line.clear();
+            std::getline(in_, line);
+            bases_.insert(bases_.end(), line.begin(), line.end());
+            offsets_.push_back(bases_.size());
+            if (fastq_) { std::getline(in_, line); std::getline(in_, line); }
+        }
+        const fgpu_reads r = {bases_.data(), offsets_.data(), offsets_.size() - 1, 0, 0, nullptr};
+        *out = r;
+        return offsets_.size() > 1;
+    }
+private:
+    std::ifstream in_;
+    bool fastq_;
+    std::vector<char> bases_;
+    std::vector<uint64_t> offsets_;
 };
 
 // ---- record-aligned cuts of a regular file into n file-order shards ---------------------------------------------------------------------------

@@ -13,7 +13,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <string>
 #include <vector>
 
@@ -23,7 +22,7 @@
 #include "../utils/Kmer.h"
 #include "../utils/JuncPairs.h"
 #include "faucet_gpu.h"
-#include "pair_loop.h"      // faucet_amd/host: scanReads' paired-end loop over the device's lists, where the device cannot hold the long pair filter's working state
+#include "scan_pass.h"      // faucet_amd/host: pass 2 on one device, with scanReads' paired-end loop on the host where the device cannot hold the long pair filter's working state
 #include "shard_host.h"     // faucet_amd/host: the two passes over several GPUs from this one process (one host thread per device)
 
 extern int j;               // src/Faucet.h:15
@@ -58,34 +57,14 @@ static void gpu_die(const char* what, int rc) {
 }
 #define GPU_CHECK(call) do { int rc__ = (call); if (rc__ != FGPU_OK) gpu_die(#call, rc__); } while (0)
 
-// The reference's record loop (utils/Bloom.cpp:280-282,340; src/ReadScanner.cpp:306-308,349), cut into batches of sequence lines.
-// `each` returns an fgpu status; the first failure ends the loop and is returned.
-template <class F>
-static int for_each_batch(const std::string& filename, bool fastq, F each) {
-    std::ifstream in(filename.c_str());
-    std::string line, bases;
-    std::vector<uint64_t> offs(1, 0);
-    auto flush = [&]() -> int {
-        fgpu_reads r;
-        memset(&r, 0, sizeof(r));
-        r.bases = bases.data();
-        r.offsets = offs.data();
-        r.n_reads = offs.size() - 1;
-        const int rc = each(&r);
-        bases.clear();
-        offs.assign(1, 0);
-        return rc;
-    };
-    while (getline(in, line)) {
-        line.clear();
-        getline(in, line);
-        bases += line;
-        offs.push_back(bases.size());
-        if (fastq) { getline(in, line); getline(in, line); }
-        if (offs.size() > 1000000)
-            if (int rc = flush()) return rc;
-    }
-    return offs.size() > 1 ? flush() : FGPU_OK;
+// The reference's record loop (utils/Bloom.cpp:280-282,340; src/ReadScanner.cpp:306-308,349) cut into batches of a million sequence lines
+// (host/text_source.h, ReadSource).  `each` returns an fgpu status; the first failure ends the loop and is returned.
+static int for_each_batch(const std::string& filename, bool fastq, const faucet_host::EachBatch& each) {
+    faucet_host::ReadSource src(filename, fastq);
+    fgpu_reads r;
+    while (src.next(1000000, &r))
+        if (int rc = each(&r)) return rc;
+    return FGPU_OK;
 }
 
 // replaces the call of load_two_filters in getBloomFilterFromReads() (src/Faucet.cpp:220); bloo1 / bloo2 are the two Bloom objects
@@ -101,19 +80,8 @@ void gpu_load_two_filters(Bloom* bloo1, Bloom* bloo2, std::string reads_filename
     p.flags = (mercy ? FGPU_FLAG_MERCY : 0) | ((g_want_pairs || g_paired_ends) ? (FGPU_FLAG_RECORD_STOPS | FGPU_FLAG_KEY_ORDER_FROM_START) : 0);
     if (g_gpus > 1) {
         // read shards: shard r = the r-th file-order share of the records, on device r (fewer devices than shards: they share), one host thread each
-        faucet_host::ShardOptions so;
-        const int ndev = fgpu_device_count();
-        if (ndev < 1) { fprintf(stderr, "fgpu_create failed: no gfx950 device\n"); exit(2); }
-        so.n_ranks = g_gpus;
-        so.transport = g_transport;
-        for (int r = 0; r < g_gpus; r++) so.devices.push_back(r % ndev);
-        so.prm = p;
-        so.fastq = fastq;
-        so.mercy = mercy;
-        so.paired_ends = g_paired_ends;
-        so.no_cleaning = !g_want_pairs;
-        so.chunk_bytes = 32u << 20;
-        g_run = new faucet_host::ShardedRun(so);
+        if (fgpu_device_count() < 1) { fprintf(stderr, "fgpu_create failed: no gfx950 device\n"); exit(2); }
+        g_run = new faucet_host::ShardedRun(faucet_host::shard_options(g_gpus, g_transport, p, fastq, mercy, g_paired_ends, !g_want_pairs, 32u << 20));
         int rc = g_run->create();
         if (rc != FGPU_OK) gpu_die("creating the read shards' contexts", rc);
         faucet_host::ShardLoadResult lr;
@@ -134,15 +102,6 @@ void gpu_load_two_filters(Bloom* bloo1, Bloom* bloo2, std::string reads_filename
     GPU_CHECK(fgpu_bloom_download(g_ctx, FGPU_BLOO1, bloo1->blooma, bloo1->tai / 8));
     GPU_CHECK(fgpu_bloom_download(g_ctx, FGPU_BLOO2, bloo2->blooma, bloo2->tai / 8));
     printf("Reads processed: %llu\nUnambiguous reads: %llu\n", (unsigned long long)st.reads_processed, (unsigned long long)st.unambiguous_reads);
-}
-
-// one pass over the scan file; FGPU_OK, or the status of the first call that failed
-static int gpu_scan_pass(const std::string& read_scan_file, bool fastq, fgpu_scan_stats* st) {
-    int rc = fgpu_scan_begin(g_ctx);
-    if (rc != FGPU_OK) return rc;
-    rc = for_each_batch(read_scan_file, fastq, [&](const fgpu_reads* r) { return fgpu_scan_batch(g_ctx, r); });
-    const int end_rc = fgpu_scan_end(g_ctx, st);      // always closes the pass, also after a failed batch
-    return rc != FGPU_OK ? rc : end_rc;
 }
 
 // the device's junction records into the reference's container: creation order -> the reference's unordered_map iteration (= dump) order
@@ -171,9 +130,6 @@ static void gpu_print_scan_summary(const fgpu_scan_stats& st) {
     printf("Reads without errors: %llu\n", (unsigned long long)st.reads_no_errors);
 }
 
-// replaces buildJunctionMapFromReads() (src/Faucet.cpp:240-246) for single-end input.  With cleaning on (short_pair_filter != NULL, the
-// Bloom made at src/Faucet.cpp:266-283) scan_forward's addPair calls (src/ReadScanner.cpp:208-225) happen on the device and the filter's
-// bytes come back at the end; gpu_configure(true, false) must have been called before pass 1 (FGPU_FLAG_RECORD_STOPS).
 // several GPUs: the same scan over the read shards; the last shard ends with the run's junction map, pair filters and counters
 static void gpu_scan_sharded(JunctionMap* junctionMap, const std::string& read_scan_file, Bloom* short_pair_filter, Bloom* long_pair_filter, bool paired) {
     g_run->set_pair_filters(short_pair_filter ? short_pair_filter->tai : 0, short_pair_filter ? short_pair_filter->getNumHash() : 0,
@@ -191,15 +147,27 @@ static void gpu_scan_sharded(JunctionMap* junctionMap, const std::string& read_s
     gpu_print_scan_summary(sr.stats);
 }
 
+// one device: host/scan_pass.h does the pass; a NULL Bloom is "no filter"
+static faucet_host::PairTarget pair_target(Bloom* b) {
+    const faucet_host::PairTarget t = {b ? (uint8_t*)b->blooma : NULL, b ? b->tai : 0, b ? b->getNumHash() : 0};
+    return t;
+}
+static void gpu_scan_one_device(JunctionMap* junctionMap, const std::string& read_scan_file, bool fastq, Bloom* short_pair_filter, Bloom* long_pair_filter, bool paired) {
+    faucet_host::ScanPassResult res;
+    const int rc = faucet_host::scan_pass(g_ctx, sizeKmer, pair_target(short_pair_filter), pair_target(long_pair_filter), paired,
+                                          [&](const faucet_host::EachBatch& each) { return for_each_batch(read_scan_file, fastq, each); }, &res);
+    if (rc != FGPU_OK) gpu_die(res.failed, rc);
+    gpu_fill_junction_map(junctionMap);
+    if (paired) printf("Empty count: %d, not empty count: %d\n", (int)res.empty_count, (int)res.not_empty_count);
+    gpu_print_scan_summary(res.stats);
+}
+
+// replaces buildJunctionMapFromReads() (src/Faucet.cpp:240-246) for single-end input.  With cleaning on (short_pair_filter != NULL, the
+// Bloom made at src/Faucet.cpp:266-283) scan_forward's addPair calls (src/ReadScanner.cpp:208-225) happen on the device and the filter's
+// bytes come back at the end; gpu_configure(true, false) must have been called before pass 1 (FGPU_FLAG_RECORD_STOPS).
 void gpu_scan(JunctionMap* junctionMap, std::string read_scan_file, bool fastq, Bloom* short_pair_filter = NULL) {
     if (g_run) return gpu_scan_sharded(junctionMap, read_scan_file, short_pair_filter, NULL, false);
-    fgpu_scan_stats st;
-    if (short_pair_filter) GPU_CHECK(fgpu_scan_short_pairs(g_ctx, short_pair_filter->tai, short_pair_filter->getNumHash(), 0));
-    const int rc = gpu_scan_pass(read_scan_file, fastq, &st);
-    if (rc != FGPU_OK) gpu_die("junction scan", rc);
-    if (short_pair_filter) GPU_CHECK(fgpu_scan_short_pairs_download(g_ctx, short_pair_filter->blooma, short_pair_filter->tai / 8));
-    gpu_fill_junction_map(junctionMap);
-    gpu_print_scan_summary(st);
+    gpu_scan_one_device(junctionMap, read_scan_file, fastq, short_pair_filter, NULL, false);
 }
 
 // ---- paired ends (--paired_ends; BASELINE config 3) -------------------------------------------------------------------------------------
@@ -212,70 +180,9 @@ void gpu_scan(JunctionMap* junctionMap, std::string read_scan_file, bool fastq, 
 // made at src/Faucet.cpp:268-281; short_pair_filter may be NULL (--no_cleaning: the reference then only counts empty / non-empty pairs).
 void gpu_scan_paired(JunctionMap* junctionMap, std::string read_scan_file, bool fastq, Bloom* short_pair_filter, Bloom* long_pair_filter,
                      bool no_cleaning) {
-    const bool filters = !no_cleaning && long_pair_filter;
-    if (g_run) return gpu_scan_sharded(junctionMap, read_scan_file, no_cleaning ? NULL : short_pair_filter, filters ? long_pair_filter : NULL, true);
-    if (short_pair_filter && !no_cleaning)
-        GPU_CHECK(fgpu_scan_short_pairs(g_ctx, short_pair_filter->tai, short_pair_filter->getNumHash(), 0));
-    bool host_loop = false;
-    if (filters) {
-        const int lrc = fgpu_scan_long_pairs(g_ctx, long_pair_filter->tai, long_pair_filter->getNumHash(), FGPU_LONG_PAIRS_FILTER);
-        if (lrc == FGPU_ERR_NOMEM) {
-            // The device form of the loop keeps 4 bytes of HBM per filter bit; a filter it cannot hold (--high_cov: E / 2 x 9 bits,
-            // src/Faucet.cpp:279-280) is filled HERE, by the reference's own loop (src/ReadScanner.cpp:317-343) over the lists the device hands out
-            // (fgpu_scan_take_stops; host/pair_loop.h), straight into long_pair_filter's bit array
-            fprintf(stderr, "note: the long pair filter does not fit the device's fixed-point form; the paired-end loop runs on the host\n");
-            host_loop = true;
-            GPU_CHECK(fgpu_scan_long_pairs(g_ctx, 0, 0, FGPU_LONG_PAIRS_OFF));
-            if (short_pair_filter) GPU_CHECK(fgpu_scan_short_pairs(g_ctx, short_pair_filter->tai, short_pair_filter->getNumHash(), 1));   // (lists to the host)
-        } else if (lrc != FGPU_OK) {
-            gpu_die("fgpu_scan_long_pairs", lrc);
-        }
-    } else {
-        GPU_CHECK(fgpu_scan_long_pairs(g_ctx, 0, 0, FGPU_LONG_PAIRS_COUNT));
-    }
-    fgpu_scan_stats st;
-    uint64_t empty_count = 0, not_empty_count = 0;
-    int rc;
-    if (host_loop) {
-        faucet_host::HostLongPairs hlp((uint8_t*)long_pair_filter->blooma, long_pair_filter->tai, long_pair_filter->getNumHash(), sizeKmer, true);
-        std::vector<fgpu_stop> stops;
-        std::vector<uint64_t> batch_reads;
-        auto take_lists = [&](bool all) -> int {
-            for (;;) {
-                uint64_t n_stops = 0;
-                int64_t seq = -1;
-                const int trc = fgpu_scan_take_stops(g_ctx, stops.data(), stops.size(), &n_stops, &seq);
-                if (trc == FGPU_ERR_CAPACITY && seq >= 0) { stops.resize((size_t)(n_stops + n_stops / 4 + 16)); continue; }
-                if (trc != FGPU_OK || seq < 0) return trc;
-                hlp.batch(stops.data(), n_stops, batch_reads[(size_t)seq]);
-                if (!all) return FGPU_OK;
-            }
-        };
-        rc = fgpu_scan_begin(g_ctx);
-        if (rc == FGPU_OK)
-            rc = for_each_batch(read_scan_file, fastq, [&](const fgpu_reads* r) -> int {
-                const int brc = fgpu_scan_batch(g_ctx, r);
-                if (brc != FGPU_OK) return brc;
-                batch_reads.push_back(r->n_reads);
-                return batch_reads.size() > 1 ? take_lists(false) : FGPU_OK;
-            });
-        const int end_rc = fgpu_scan_end(g_ctx, &st);
-        if (rc == FGPU_OK) rc = end_rc;
-        if (rc == FGPU_OK) rc = take_lists(true);
-        empty_count = hlp.empty_count;
-        not_empty_count = hlp.not_empty_count;
-    } else {
-        rc = gpu_scan_pass(read_scan_file, fastq, &st);
-    }
-    if (rc != FGPU_OK) gpu_die("paired-end junction scan", rc);
-    if (short_pair_filter && !no_cleaning)
-        GPU_CHECK(fgpu_scan_short_pairs_download(g_ctx, short_pair_filter->blooma, short_pair_filter->tai / 8));
-    if (!host_loop)
-        GPU_CHECK(fgpu_scan_long_pairs_download(g_ctx, filters ? long_pair_filter->blooma : NULL, filters ? long_pair_filter->tai / 8 : 0, &empty_count,
-                                                &not_empty_count));
-    gpu_fill_junction_map(junctionMap);
-    printf("Empty count: %d, not empty count: %d\n", (int)empty_count, (int)not_empty_count);
-    gpu_print_scan_summary(st);
+    if (no_cleaning) short_pair_filter = long_pair_filter = NULL;
+    if (g_run) return gpu_scan_sharded(junctionMap, read_scan_file, short_pair_filter, long_pair_filter, true);
+    gpu_scan_one_device(junctionMap, read_scan_file, fastq, short_pair_filter, long_pair_filter, true);
 }
 
 // ---- Stage 3: JunctionMap::findNeighbor for many (junction, extension) pairs in one device call ------------------------------------------

@@ -115,8 +115,8 @@ def test_junction_file_text_round_trips(name):
 
 
 def test_integration_binding_compiles_against_the_reference_headers():
-    """integration/faucet_binding.cpp -- the patch INTEGRATION.md shows a Faucet maintainer, status checks and the lazy-flag retry
-    included -- must be valid C++11 against the reference's own Bloom.h / JunctionMap.h / Junction.h (only where that tree is mounted)."""
+    """integration/faucet_binding.cpp -- the patch INTEGRATION.md shows a Faucet maintainer, status checks and the host headers it
+    calls (faucet_amd/host: scan_pass.h, shard_host.h) included -- must be valid C++11 against the reference's own Bloom.h / JunctionMap.h / Junction.h (only where that tree is mounted)."""
     import os
     import shutil
     import subprocess
