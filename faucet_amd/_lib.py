@@ -125,6 +125,7 @@ SIGNATURES = {
     "fgpu_scan_long_pairs": (C.c_int, [_vp, _u64, _i32, _i32]),
     "fgpu_scan_long_pairs_download": (C.c_int, [_vp, _vp, _u64, _P(_u64), _P(_u64)]),
     "fgpu_diag_long_pairs": (C.c_int, [_vp, _P(_u64)]),
+    "fgpu_diag_long_pairs_state": (C.c_int, [_vp, _P(_u64)]),
     "fgpu_diag_ovw": (C.c_int, [_vp, _P(_u64)]),
     "fgpu_diag_ovw_tables": (C.c_int, [_vp, _P(_u64), _P(_u64)]),
     "fgpu_scan_refresh_prepared": (C.c_int, [_vp]),

@@ -456,7 +456,9 @@ class Context:
 
     def scan_long_pairs(self, tai: int, n_hash: int, mode: int = 2):
         """keep the long pair filter (scanReads' paired-end loop, src/ReadScanner.cpp:317-343) on the device from the next scan on;
-        mode 0 = off, 1 = only the empty / not-empty pair counts (--no_cleaning), 2 = counts and filter"""
+        mode 0 = off, 1 = only the empty / not-empty pair counts (--no_cleaning), 2 = counts and filter (first-set times dense where their
+        4 bytes per bit fit, else per batch), 3 = counts and filter, first-set times always per batch (sparse); FGPU_LONG_PAIRS_STATE =
+        dense | sparse | auto overrides what mode 2 takes"""
         self._c(self.lib.fgpu_scan_long_pairs(self.h, int(tai), int(n_hash), int(mode)))
 
     def scan_long_pairs_download(self, tai: int = 0):
@@ -476,6 +478,13 @@ class Context:
         out = (C.c_uint64 * 6)()
         self._c(self.lib.fgpu_diag_long_pairs(self.h, out))
         return dict(zip(("items", "paired_by_carry", "inserts", "rounds", "max_rounds", "batches"), (int(v) for v in out)))
+
+    def diag_long_pairs_state(self):
+        """the form of the long pair filter's first-set times: form None / "dense" / "sparse", working bytes beyond the bits, the most table
+        slots a batch of the last scan had (sparse), the internal-error flag (sparse)"""
+        out = (C.c_uint64 * 4)()
+        self._c(self.lib.fgpu_diag_long_pairs_state(self.h, out))
+        return {"form": (None, "dense", "sparse")[int(out[0])], "working_bytes": int(out[1]), "table_slots_high": int(out[2]), "error": int(out[3])}
 
     def diag_ovw(self):
         """the optimistic walk of large clusters during the last scan: pieces walked, rounds run, windows settled, windows left to the key-ordered walk"""

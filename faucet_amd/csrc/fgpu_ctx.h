@@ -120,11 +120,14 @@ struct StopBatch {   // harvested stops of one scanned batch, waiting for fgpu_s
 
 // The long pair filter on the device (pairs.hip): scanReads' paired-end loop over the harvested lists
 struct LongPairs {
-    int mode = 0;                    // FGPU_LONG_PAIRS_OFF / _COUNT / _FILTER
+    int mode = 0;                    // FGPU_LONG_PAIRS_OFF / _COUNT / _FILTER (both forms of the filter: `sparse` says which)
+    bool sparse = false;             // the first-set times live in a per-batch table (`table`), not in `first`
     uint64_t tai = 0;
     int n_hash = 0;
     uint32_t* bits = nullptr;        // the filter, tai / 8 bytes
-    uint32_t* first = nullptr;       // first-set time per filter bit of the batch in hand, 4 * tai bytes (all "never" between batches)
+    uint32_t* first = nullptr;       // dense form: first-set time per filter bit of the batch in hand, 4 * tai bytes (all "never" between batches)
+    DevBuf table;                    // sparse form: the batch's table of {bit position, first-set time}, keys then times (pairs.hip)
+    uint64_t table_high = 0;         // most slots a batch's table had in this scan
     DevBuf canon, h0, h1, vread, rs, state, dev;   // per list element / per read scratch; dev: counters and flip counts
     DevBuf kept_set[2];              // a waiting first end's list (canonical forms, then the two hashes): two buffers used in turn
     int kept_cur = 0;

@@ -17,7 +17,10 @@
 // earlier one), so every round settles it and everything before it: the fixed point is unique and is the sequential run's, reached after at
 // most (longest chain of flips) + 1 rounds -- two or three on real lists.  Then the inserters' bits are ORed into the filter, which is the
 // carry of the next batch.  A first end whose mate opens the next batch waits in `kept`.
+#include <string.h>
+
 #include <algorithm>
+#include <string>
 
 #include "fgpu_ctx.h"
 
@@ -26,9 +29,79 @@ namespace {
 constexpr uint32_t LP_NEVER = 0xFFFFFFFFu;
 enum : uint8_t { LP_NONE = 0, LP_FINAL = 1, LP_INSERT = 2, LP_PAIRED = 3 };
 
+// Where the first-set times of the batch in hand live.  Two layouts, one interface (as the filter view of load_common.h): insert(h, t) --
+// round 0 posts time t for bit position h --, post(h, t) in a later round, withdraw(h), time(h), retire(h) at the commit.  The kernels are
+// templates on the view: which one a scan uses is decided once, on the host (fgpu_scan_long_pairs).
+//   TimesDense   first[]: one time per filter bit, 4 * tai bytes, all LP_NEVER between batches.
+//   TimesSparse  a per-batch open-addressing table keyed by bit position.  Only items that the carry does not pair ever insert, their pair
+//                (element, front of the mate's list) is the same in every round and the carry stands still during a batch: round 0 (k_lp_init)
+//                touches every bit position a later round can, at most n_hash per element.  So keys are inserted in k_lp_init ALONE (64-bit
+//                compare-and-swap on the key word; "empty" or "my key" means the slot is mine), no kernel deletes one, and every later look-up
+//                is a plain linear probe that ends at the key or at an empty slot and never races with an insertion; absent = LP_NEVER.
+//                `cap` slots, a power of two >= 2 * n_hash * elements (load <= 1/2): keys[cap] (64 bits: filters reach 2^37 bits), then
+//                times[cap].  Empty key = all ones = LP_NEVER: one memset of 0xFF clears a batch's table.  Every probe loop ends after `cap`
+//                steps at the latest; running out, or a key that k_lp_post misses, raises *err (reported by fgpu_long_pairs_close).
+struct TimesDense {
+    uint32_t* first;
+    __device__ __forceinline__ void insert(uint64_t h, uint32_t t) const { atomicMin(&first[h], t); }
+    __device__ __forceinline__ void post(uint64_t h, uint32_t t) const { atomicMin(&first[h], t); }
+    __device__ __forceinline__ void withdraw(uint64_t h) const { first[h] = LP_NEVER; }
+    __device__ __forceinline__ uint32_t time(uint64_t h) const { return first[h]; }
+    __device__ __forceinline__ void retire(uint64_t h) const { first[h] = LP_NEVER; }
+};
+
+constexpr uint64_t LP_EMPTY = ~0ULL;
+constexpr uint64_t LP_NO_SLOT = ~0ULL;
+constexpr uint64_t LP_TABLE_FLOOR = 64;   // slots of the smallest table: tiny batches collide and wrap
+
+struct TimesSparse {
+    unsigned long long* keys;
+    uint32_t* times;
+    uint64_t cap_mask;    // cap - 1
+    int shift;            // 64 - log2(cap)
+    uint32_t* err;
+    __device__ __forceinline__ uint64_t home(uint64_t h) const { return (h * 0x9E3779B97F4A7C15ULL) >> shift; }
+    // the slot of key h, LP_NO_SLOT if the table does not hold it (after k_lp_init: plain loads)
+    __device__ __forceinline__ uint64_t find(uint64_t h) const {
+        uint64_t s = home(h);
+        for (uint64_t n = 0; n <= cap_mask; n++) {
+            const uint64_t k = keys[s];
+            if (k == h) return s;
+            if (k == LP_EMPTY) return LP_NO_SLOT;
+            s = (s + 1) & cap_mask;
+        }
+        *err = 1u;        // a full table: the capacity rule was broken
+        return LP_NO_SLOT;
+    }
+    __device__ __forceinline__ void insert(uint64_t h, uint32_t t) const {
+        uint64_t s = home(h);
+        for (uint64_t n = 0; n <= cap_mask; n++) {
+            const unsigned long long k = atomicCAS(&keys[s], (unsigned long long)LP_EMPTY, (unsigned long long)h);
+            if (k == LP_EMPTY || k == h) { atomicMin(&times[s], t); return; }
+            s = (s + 1) & cap_mask;
+        }
+        *err = 1u;
+    }
+    __device__ __forceinline__ void post(uint64_t h, uint32_t t) const {
+        const uint64_t s = find(h);
+        if (s == LP_NO_SLOT) *err = 1u;      // round 0 posted to this bit: an internal error, never an insert
+        else atomicMin(&times[s], t);
+    }
+    __device__ __forceinline__ void withdraw(uint64_t h) const {   // (a bit of the carry was never posted: nothing to take back)
+        const uint64_t s = find(h);
+        if (s != LP_NO_SLOT) times[s] = LP_NEVER;
+    }
+    __device__ __forceinline__ uint32_t time(uint64_t h) const {
+        const uint64_t s = find(h);
+        return s == LP_NO_SLOT ? LP_NEVER : times[s];
+    }
+    __device__ __forceinline__ void retire(uint64_t) const {}      // the next batch wipes the table
+};
+
+template <class T>
 struct LpFilter {
     uint32_t* bits;       // the filter: tai / 8 bytes, bit p = bit (p & 31) of word p >> 5 (utils/Bloom.h:44-53 on little-endian words)
-    uint32_t* first;      // first-set time per filter bit of the batch in hand; LP_NEVER between batches
+    T times;              // first-set time per filter bit of the batch in hand; LP_NEVER between batches
     uint64_t mask;        // tai - 1
     int n_hash;
 };
@@ -87,7 +160,8 @@ __global__ void __launch_bounds__(256) k_lp_count(const uint32_t* __restrict__ r
     }
 }
 
-__device__ __forceinline__ bool lp_carry_bit(const LpFilter& F, uint64_t h) { return (F.bits[h >> 5] >> (h & 31)) & 1u; }
+template <class T>
+__device__ __forceinline__ bool lp_carry_bit(const LpFilter<T>& F, uint64_t h) { return (F.bits[h >> 5] >> (h & 31)) & 1u; }
 
 // the element's read pair: [b0, b1) = the second end's list.  false: the element is no item (second end, empty mate, waiting first end)
 __device__ __forceinline__ bool lp_item(const LpLists& L, uint32_t e, uint32_t& b0, uint32_t& b1) {
@@ -99,7 +173,8 @@ __device__ __forceinline__ bool lp_item(const LpLists& L, uint32_t e, uint32_t& 
 }
 
 // round 0: paired against the carried-in filter alone?  Otherwise assume "insert" and post the times of the missing bits.
-__global__ void __launch_bounds__(256) k_lp_init(LpLists L, LpFilter F, uint8_t* __restrict__ state, uint8_t* __restrict__ state_new,
+template <class T>
+__global__ void __launch_bounds__(256) k_lp_init(LpLists L, LpFilter<T> F, uint8_t* __restrict__ state, uint8_t* __restrict__ state_new,
                                                  unsigned long long* __restrict__ diag) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t b0, b1;
@@ -118,7 +193,7 @@ __global__ void __launch_bounds__(256) k_lp_init(LpLists L, LpFilter F, uint8_t*
             uint64_t hA, hB;
             lp_pair_hash(L, e, b0, hA, hB);
             for (int i = 0; i < F.n_hash; i++) {
-                if (!lp_carry_bit(F, hA)) atomicMin(&F.first[hA], e);
+                if (!lp_carry_bit(F, hA)) F.times.insert(hA, e);
                 hA = (hA + hB) & F.mask;
             }
         }
@@ -137,7 +212,8 @@ __global__ void __launch_bounds__(256) k_lp_init(LpLists L, LpFilter F, uint8_t*
 }
 
 // round r >= 1: does the item find a partner in (carry, inserts of earlier items as currently assumed)?
-__global__ void __launch_bounds__(256) k_lp_eval(LpLists L, LpFilter F, const uint8_t* __restrict__ state, uint8_t* __restrict__ state_new,
+template <class T>
+__global__ void __launch_bounds__(256) k_lp_eval(LpLists L, LpFilter<T> F, const uint8_t* __restrict__ state, uint8_t* __restrict__ state_new,
                                                  const uint32_t* __restrict__ flips_before, uint32_t* __restrict__ flips) {
     if (flips_before && *flips_before == 0) return;   // settled in an earlier round of this group of launches
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -151,7 +227,7 @@ __global__ void __launch_bounds__(256) k_lp_eval(LpLists L, LpFilter F, const ui
         lp_pair_hash(L, e, j, hA, hB);
         bool all = true;
         for (int i = 0; i < F.n_hash && all; i++) {
-            all = lp_carry_bit(F, hA) || F.first[hA] < e;
+            all = lp_carry_bit(F, hA) || F.times.time(hA) < e;
             hA = (hA + hB) & F.mask;
         }
         paired = all;
@@ -165,16 +241,18 @@ __global__ void __launch_bounds__(256) k_lp_eval(LpLists L, LpFilter F, const ui
 }
 
 // first[] is rebuilt for the new assumptions: the bits of every item that inserted under the old ones are taken back ...
-__global__ void __launch_bounds__(256) k_lp_withdraw(LpLists L, LpFilter F, const uint8_t* __restrict__ state, const uint32_t* __restrict__ flips) {
+template <class T>
+__global__ void __launch_bounds__(256) k_lp_withdraw(LpLists L, LpFilter<T> F, const uint8_t* __restrict__ state, const uint32_t* __restrict__ flips) {
     if (*flips == 0) return;
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= L.n_elems || state[e] != LP_INSERT) return;
     uint64_t hA, hB;
     lp_pair_hash(L, e, L.rs[L.vread[e] + 1], hA, hB);
-    for (int i = 0; i < F.n_hash; i++) { F.first[hA] = LP_NEVER; hA = (hA + hB) & F.mask; }
+    for (int i = 0; i < F.n_hash; i++) { F.times.withdraw(hA); hA = (hA + hB) & F.mask; }
 }
 // ... and those of every item that inserts under the new ones are posted; the new assumptions become the current ones
-__global__ void __launch_bounds__(256) k_lp_post(LpLists L, LpFilter F, uint8_t* __restrict__ state, const uint8_t* __restrict__ state_new,
+template <class T>
+__global__ void __launch_bounds__(256) k_lp_post(LpLists L, LpFilter<T> F, uint8_t* __restrict__ state, const uint8_t* __restrict__ state_new,
                                                  const uint32_t* __restrict__ flips) {
     if (*flips == 0) return;
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -185,13 +263,14 @@ __global__ void __launch_bounds__(256) k_lp_post(LpLists L, LpFilter F, uint8_t*
     uint64_t hA, hB;
     lp_pair_hash(L, e, L.rs[L.vread[e] + 1], hA, hB);
     for (int i = 0; i < F.n_hash; i++) {
-        if (!lp_carry_bit(F, hA)) atomicMin(&F.first[hA], e);
+        if (!lp_carry_bit(F, hA)) F.times.post(hA, e);
         hA = (hA + hB) & F.mask;
     }
 }
 
 // settled: the inserters' bits go into the filter (the carry of the next batch) and their times out of first[]
-__global__ void __launch_bounds__(256) k_lp_commit(LpLists L, LpFilter F, const uint8_t* __restrict__ state, unsigned long long* __restrict__ diag,
+template <class T>
+__global__ void __launch_bounds__(256) k_lp_commit(LpLists L, LpFilter<T> F, const uint8_t* __restrict__ state, unsigned long long* __restrict__ diag,
                                                    const uint32_t* __restrict__ last_flips) {
     if (last_flips && *last_flips != 0) return;      // the rounds issued ahead did not settle: the host issues more, then commits (lp_close)
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -201,7 +280,7 @@ __global__ void __launch_bounds__(256) k_lp_commit(LpLists L, LpFilter F, const 
         lp_pair_hash(L, e, L.rs[L.vread[e] + 1], hA, hB);
         for (int i = 0; i < F.n_hash; i++) {
             atomicOr(&F.bits[hA >> 5], 1u << (hA & 31));
-            F.first[hA] = LP_NEVER;
+            F.times.retire(hA);
             hA = (hA + hB) & F.mask;
         }
     }
@@ -216,14 +295,66 @@ __global__ void __launch_bounds__(256) k_lp_commit(LpLists L, LpFilter F, const 
 // group of four rounds and one per odd batch).  lp_close is that look: how many rounds the batch took, more rounds and the commit if kAhead did
 // not settle it (not seen so far: 4 at most on config 3's shape), and the list of a first end that waits for its mate.
 constexpr int kAhead = 8;
+// lp.dev: 64-bit words [0..2] diagnostics, [3] empty, [4] not empty, [5] the sparse form's internal-error flag; from word 8 on one 32-bit flip
+// flag per round issued ahead.  lp.flips_host: [0..kAhead) the flips, [kAhead] where a waiting first end's list begins, [kAhead + 1] the flag.
+constexpr int LP_DEV_ERR = 5;
 
-static int lp_rounds(fgpu_ctx* ctx, const LpLists& L, const LpFilter& F, uint8_t* state, uint8_t* state_new, uint32_t* d_flips, int n, unsigned blocks) {
+template <class T>
+static int lp_rounds(fgpu_ctx* ctx, const LpLists& L, const LpFilter<T>& F, uint8_t* state, uint8_t* state_new, uint32_t* d_flips, int n, unsigned blocks) {
     FGPU_HIP(hipMemsetAsync(d_flips, 0, 4 * n, ctx->stream));
     for (int g = 0; g < n; g++) {
-        FGPU_LAUNCH("long_pairs", k_lp_eval, blocks, 256, L, F, (const uint8_t*)state, state_new, g ? (const uint32_t*)(d_flips + g - 1) : (const uint32_t*)nullptr, d_flips + g);
-        FGPU_LAUNCH("long_pairs", k_lp_withdraw, blocks, 256, L, F, (const uint8_t*)state, (const uint32_t*)(d_flips + g));
-        FGPU_LAUNCH("long_pairs", k_lp_post, blocks, 256, L, F, state, (const uint8_t*)state_new, (const uint32_t*)(d_flips + g));
+        FGPU_LAUNCH("long_pairs", k_lp_eval<T>, blocks, 256, L, F, (const uint8_t*)state, state_new, g ? (const uint32_t*)(d_flips + g - 1) : (const uint32_t*)nullptr, d_flips + g);
+        FGPU_LAUNCH("long_pairs", k_lp_withdraw<T>, blocks, 256, L, F, (const uint8_t*)state, (const uint32_t*)(d_flips + g));
+        FGPU_LAUNCH("long_pairs", k_lp_post<T>, blocks, 256, L, F, state, (const uint8_t*)state_new, (const uint32_t*)(d_flips + g));
     }
+    return FGPU_OK;
+}
+
+static TimesDense lp_dense(const LongPairs& lp) { return TimesDense{lp.first}; }
+// the table of a batch of n_elems elements, in lp.table: keys, then times
+static uint64_t lp_table_slots(const LongPairs& lp, uint32_t n_elems) {
+    uint64_t cap = LP_TABLE_FLOOR;
+    while (cap < 2ULL * (uint64_t)lp.n_hash * n_elems) cap <<= 1;
+    return cap;
+}
+static TimesSparse lp_sparse(const LongPairs& lp, uint32_t n_elems) {
+    const uint64_t cap = lp_table_slots(lp, n_elems);
+    return TimesSparse{(unsigned long long*)lp.table.p, (uint32_t*)((unsigned long long*)lp.table.p + cap), cap - 1, 64 - __builtin_ctzll(cap),
+                       (uint32_t*)((unsigned long long*)lp.dev.p + LP_DEV_ERR)};
+}
+
+// round 0, kAhead rounds and the commit behind them
+template <class T>
+static int lp_issue(fgpu_ctx* ctx, const LpLists& L, const T& times, uint8_t* state, uint8_t* state_new, unsigned long long* d_diag, uint32_t* d_flips, unsigned blocks) {
+    const LongPairs& lp = ctx->lp;
+    const LpFilter<T> F = {lp.bits, times, lp.tai - 1, lp.n_hash};
+    FGPU_LAUNCH("long_pairs", k_lp_init<T>, blocks, 256, L, F, state, state_new, d_diag);
+    if (int rc = lp_rounds(ctx, L, F, state, state_new, d_flips, kAhead, blocks)) return rc;
+    FGPU_LAUNCH("long_pairs", k_lp_commit<T>, blocks, 256, L, F, (const uint8_t*)state, d_diag, (const uint32_t*)(d_flips + kAhead - 1));
+    return FGPU_OK;
+}
+
+// the rounds issued ahead did not settle the batch: the old way, a look per group, then the commit
+template <class T>
+static int lp_settle(fgpu_ctx* ctx, const LpLists& L, const T& times, uint8_t* state, uint8_t* state_new, unsigned long long* d_diag, uint32_t* d_flips, unsigned blocks,
+                     uint64_t* rounds) {
+    LongPairs& lp = ctx->lp;
+    const LpFilter<T> F = {lp.bits, times, lp.tai - 1, lp.n_hash};
+    constexpr int kGroup = 4;
+    for (;;) {
+        if (int rc = lp_rounds(ctx, L, F, state, state_new, d_flips, kGroup, blocks)) return rc;
+        FGPU_HIP(hipMemcpyAsync(lp.flips_host, d_flips, 4 * kGroup, hipMemcpyDeviceToHost, ctx->stream));
+        FGPU_HIP(hipMemcpyAsync(lp.flips_host + kAhead + 1, d_diag + LP_DEV_ERR, 4, hipMemcpyDeviceToHost, ctx->stream));
+        FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+        int u = kGroup;
+        for (int g = 0; g < kGroup; g++)
+            if (lp.flips_host[g] == 0) { u = g + 1; break; }
+        *rounds += (uint64_t)u;
+        if (lp.flips_host[u - 1] == 0) break;
+        if (lp.flips_host[kAhead + 1]) return FGPU_OK;      // (the caller reports it)
+        if (*rounds > (uint64_t)L.n_elems + kAhead + kGroup) { ctx->err = "long pair filter: the rounds did not settle (internal error)"; return FGPU_ERR_STATE; }
+    }
+    FGPU_LAUNCH("long_pairs", k_lp_commit<T>, blocks, 256, L, F, (const uint8_t*)state, d_diag, (const uint32_t*)nullptr);
     return FGPU_OK;
 }
 
@@ -238,7 +369,6 @@ int fgpu_long_pairs_close(fgpu_ctx* ctx) {
     if (lp.open_filter) {
         uint8_t *state = (uint8_t*)lp.state.p, *state_new = state + n_elems;
         const LpLists L = {canon, h0, h1, (uint32_t*)lp.vread.p, (uint32_t*)lp.rs.p, n_elems, n_vreads};
-        const LpFilter F = {lp.bits, lp.first, lp.tai ? lp.tai - 1 : 0, lp.n_hash};
         unsigned long long* d_diag = (unsigned long long*)lp.dev.p;
         uint32_t* d_flips = (uint32_t*)((unsigned long long*)lp.dev.p + 8);
         const unsigned blocks = fgpu_blocks(std::max<uint64_t>(n_elems, 1), 256);
@@ -246,20 +376,14 @@ int fgpu_long_pairs_close(fgpu_ctx* ctx) {
         for (int g = 0; g < kAhead; g++)
             if (lp.flips_host[g] == 0) { used = g + 1; break; }
         uint64_t rounds = (uint64_t)used;
-        if (lp.flips_host[kAhead - 1] != 0) {          // not settled by the rounds issued ahead: the old way, a look per group, then the commit
-            constexpr int kGroup = 4;
-            for (;;) {
-                if (int rc = lp_rounds(ctx, L, F, state, state_new, d_flips, kGroup, blocks)) return rc;
-                FGPU_HIP(hipMemcpyAsync(lp.flips_host, d_flips, 4 * kGroup, hipMemcpyDeviceToHost, ctx->stream));
-                FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-                int u = kGroup;
-                for (int g = 0; g < kGroup; g++)
-                    if (lp.flips_host[g] == 0) { u = g + 1; break; }
-                rounds += (uint64_t)u;
-                if (lp.flips_host[u - 1] == 0) break;
-                if (rounds > (uint64_t)n_elems + kAhead + kGroup) { ctx->err = "long pair filter: the rounds did not settle (internal error)"; return FGPU_ERR_STATE; }
-            }
-            FGPU_LAUNCH("long_pairs", k_lp_commit, blocks, 256, L, F, (const uint8_t*)state, d_diag, (const uint32_t*)nullptr);
+        if (lp.flips_host[kAhead - 1] != 0 && !(lp.sparse && lp.flips_host[kAhead + 1])) {     // not settled by the rounds issued ahead
+            const int rc = lp.sparse ? lp_settle(ctx, L, lp_sparse(lp, n_elems), state, state_new, d_diag, d_flips, blocks, &rounds)
+                                     : lp_settle(ctx, L, lp_dense(lp), state, state_new, d_diag, d_flips, blocks, &rounds);
+            if (rc) return rc;
+        }
+        if (lp.sparse && lp.flips_host[kAhead + 1]) {
+            ctx->err = "long pair filter: the per-batch table of first-set times missed a key or ran full (internal error)";
+            return FGPU_ERR_STATE;
         }
         lp.rounds += rounds;
         lp.max_rounds = std::max<uint64_t>(lp.max_rounds, rounds);
@@ -325,13 +449,23 @@ int fgpu_long_pairs_batch(fgpu_ctx* ctx, const fgpu_stop* d_stops, uint64_t n_st
     if (n_pairs) FGPU_LAUNCH("long_pairs", k_lp_count, fgpu_blocks(n_pairs, 256), 256, (const uint32_t*)rs, n_pairs, d_diag + 3);
     const LpLists L = {canon, h0, h1, vread, rs, n_elems, n_vreads};
     const bool filter = lp.mode == FGPU_LONG_PAIRS_FILTER && n_pairs;
-    if (filter) {
-        const LpFilter F = {lp.bits, lp.first, mask, lp.n_hash};
-        FGPU_LAUNCH("long_pairs", k_lp_init, blocks, 256, L, F, state, state_new, d_diag);
-        if ((rc = lp_rounds(ctx, L, F, state, state_new, d_flips, kAhead, blocks))) return rc;
-        FGPU_LAUNCH("long_pairs", k_lp_commit, blocks, 256, L, F, (const uint8_t*)state, d_diag, (const uint32_t*)(d_flips + kAhead - 1));
-        FGPU_HIP(hipMemcpyAsync(lp.flips_host, d_flips, 4 * kAhead, hipMemcpyDeviceToHost, ctx->stream));
+    if (filter && lp.sparse) {
+        // this batch's table: sized from what the host knows without a look at the device, cleared on the context's stream
+        const uint64_t cap = lp_table_slots(lp, n_elems);
+        if (fgpu_ensure_b(ctx, &lp.table, 12 * cap) != FGPU_OK) {
+            (void)hipGetLastError();
+            ctx->err = "long pair filter: no room for the table of first-set times (" + std::to_string(12 * cap) + " bytes) of a batch of " +
+                       std::to_string(n_elems) + " list elements";
+            return FGPU_ERR_NOMEM;
+        }
+        lp.table_high = std::max(lp.table_high, cap);
+        FGPU_HIP(hipMemsetAsync(lp.table.p, 0xFF, 12 * cap, ctx->stream));
+        if ((rc = lp_issue(ctx, L, lp_sparse(lp, n_elems), state, state_new, d_diag, d_flips, blocks))) return rc;
+        FGPU_HIP(hipMemcpyAsync(lp.flips_host + kAhead + 1, d_diag + LP_DEV_ERR, 4, hipMemcpyDeviceToHost, ctx->stream));
+    } else if (filter) {
+        if ((rc = lp_issue(ctx, L, lp_dense(lp), state, state_new, d_diag, d_flips, blocks))) return rc;
     }
+    if (filter) FGPU_HIP(hipMemcpyAsync(lp.flips_host, d_flips, 4 * kAhead, hipMemcpyDeviceToHost, ctx->stream));
     if (odd) FGPU_HIP(hipMemcpyAsync(lp.flips_host + kAhead, rs + (n_vreads - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
     if (!filter && !odd) {           // nothing to look at later
         lp.pending_first = false;
@@ -357,7 +491,8 @@ int fgpu_long_pairs_reset(fgpu_ctx* ctx) {
     FGPU_HIP(hipMemsetAsync(lp.dev.p, 0, 128, ctx->stream));
     lp.pending_first = false;
     lp.n_kept = 0;
-    lp.empty_host = lp.rounds = lp.max_rounds = lp.batches = 0;
+    lp.empty_host = lp.rounds = lp.max_rounds = lp.batches = lp.table_high = 0;
+    if (lp.flips_host) lp.flips_host[kAhead + 1] = 0;
     return FGPU_OK;
 }
 
@@ -376,25 +511,52 @@ int fgpu_scan_long_pairs(fgpu_ctx* ctx, uint64_t tai, int32_t n_hash, int32_t mo
     }
     lp.mode = FGPU_LONG_PAIRS_OFF;
     lp.tai = 0;
+    lp.sparse = false;
     if (mode == FGPU_LONG_PAIRS_OFF) return FGPU_OK;
-    if (mode != FGPU_LONG_PAIRS_COUNT && mode != FGPU_LONG_PAIRS_FILTER) { ctx->err = "fgpu_scan_long_pairs: mode must be FGPU_LONG_PAIRS_OFF / _COUNT / _FILTER"; return FGPU_ERR_ARG; }
+    if (mode != FGPU_LONG_PAIRS_COUNT && mode != FGPU_LONG_PAIRS_FILTER && mode != FGPU_LONG_PAIRS_FILTER_SPARSE) {
+        ctx->err = "fgpu_scan_long_pairs: mode must be FGPU_LONG_PAIRS_OFF / _COUNT / _FILTER / _FILTER_SPARSE";
+        return FGPU_ERR_ARG;
+    }
     if (!ctx->record_stops) { ctx->err = "fgpu_scan_long_pairs needs FGPU_FLAG_RECORD_STOPS"; return FGPU_ERR_STATE; }
-    if (mode == FGPU_LONG_PAIRS_FILTER) {
+    if (mode == FGPU_LONG_PAIRS_FILTER || mode == FGPU_LONG_PAIRS_FILTER_SPARSE) {
         if (!tai || (tai & (tai - 1)) || tai < 128 || n_hash < 1 || n_hash > 32) { ctx->err = "fgpu_scan_long_pairs: tai must be a power of two >= 128, n_hash 1..32"; return FGPU_ERR_ARG; }
-        // FGPU_DEBUG_LONG_PAIRS_NOMEM=1 (tests): as if the filter's working state -- 4 bytes per bit -- did not fit, so that the hosts' way on can be tested
+        // FGPU_LONG_PAIRS_STATE=dense|sparse|auto: the form of the first-set times that FGPU_LONG_PAIRS_FILTER takes (auto, the default: dense where
+        // its 4 bytes per bit fit, else sparse).  Read at every call: a process may switch between scans.
+        const char* form = getenv("FGPU_LONG_PAIRS_STATE");
+        const bool force_dense = form && !strcmp(form, "dense"), force_sparse = form && !strcmp(form, "sparse");
+        if (form && form[0] && !force_dense && !force_sparse && strcmp(form, "auto")) { ctx->err = "FGPU_LONG_PAIRS_STATE must be dense, sparse or auto"; return FGPU_ERR_ARG; }
+        // FGPU_DEBUG_LONG_PAIRS_NOMEM=1 (tests): as if nothing of the filter fit, so that the hosts' way on can be tested;
+        // FGPU_DEBUG_LONG_PAIRS_DENSE_NOMEM=1 (tests): as if only the dense first-set times did not
         static const bool dbg_nomem = getenv("FGPU_DEBUG_LONG_PAIRS_NOMEM") != nullptr;
+        const bool dbg_dense_nomem = getenv("FGPU_DEBUG_LONG_PAIRS_DENSE_NOMEM") != nullptr;
         hipError_t e = dbg_nomem ? hipErrorOutOfMemory : hipMalloc(&lp.bits, tai / 8);
-        if (e == hipSuccess) e = hipMalloc(&lp.first, tai * 4);
         if (e != hipSuccess) {
-            if (lp.bits) hipFree(lp.bits);
             lp.bits = nullptr;
             (void)hipGetLastError();
-            ctx->err = std::string("fgpu_scan_long_pairs: hipMalloc of the filter and its first-set times (4 bytes per bit) failed: ") + hipGetErrorString(e) +
+            ctx->err = std::string("fgpu_scan_long_pairs: hipMalloc of the filter's bits (") + std::to_string(tai / 8) + " bytes) failed: " + hipGetErrorString(e) +
                        " -- hosts run the loop themselves over fgpu_scan_take_stops' lists then (host/pair_loop.h)";
             return FGPU_ERR_NOMEM;
         }
+        bool sparse = mode == FGPU_LONG_PAIRS_FILTER_SPARSE || force_sparse;
+        if (!sparse) {
+            e = dbg_dense_nomem ? hipErrorOutOfMemory : hipMalloc(&lp.first, tai * 4);
+            if (e != hipSuccess) {
+                lp.first = nullptr;
+                (void)hipGetLastError();
+                if (force_dense) {
+                    (void)hipFree(lp.bits);
+                    lp.bits = nullptr;
+                    ctx->err = std::string("fgpu_scan_long_pairs: hipMalloc of the filter's first-set times (4 bytes per bit, FGPU_LONG_PAIRS_STATE=dense) failed: ") +
+                               hipGetErrorString(e) + " -- hosts run the loop themselves over fgpu_scan_take_stops' lists then (host/pair_loop.h)";
+                    return FGPU_ERR_NOMEM;
+                }
+                sparse = true;      // the bits stay; the times live per batch
+            }
+        }
+        lp.sparse = sparse;
         lp.tai = tai;
         lp.n_hash = n_hash;
+        mode = FGPU_LONG_PAIRS_FILTER;      // (one mode from here on: lp.sparse says which form)
     }
     int rc = fgpu_ensure(ctx, &lp.dev, 256);
     if (rc) return rc;
@@ -418,6 +580,25 @@ int fgpu_scan_long_pairs_download(fgpu_ctx* ctx, uint8_t* out, uint64_t n_bytes,
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
     if (empty_count) *empty_count = c[3] + lp.empty_host;
     if (not_empty_count) *not_empty_count = c[4];
+    return FGPU_OK;
+}
+
+int fgpu_diag_long_pairs_state(fgpu_ctx* ctx, uint64_t out[4]) {
+    if (!ctx || !out) return FGPU_ERR_ARG;
+    LongPairs& lp = ctx->lp;
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    if (lp.mode != FGPU_LONG_PAIRS_FILTER) return FGPU_OK;
+    out[0] = lp.sparse ? 2 : 1;
+    for (const DevBuf* b : {&lp.canon, &lp.h0, &lp.h1, &lp.vread, &lp.rs, &lp.state, &lp.dev, &lp.kept_set[0], &lp.kept_set[1]}) out[1] += b->p ? b->bytes : 0;
+    out[1] += lp.sparse ? (lp.table.p ? lp.table.bytes : 0) : lp.tai * 4;
+    out[2] = lp.table_high;
+    unsigned long long flag = 0;
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    if (lp.dev.p) {
+        FGPU_HIP(hipMemcpyAsync(&flag, (unsigned long long*)lp.dev.p + LP_DEV_ERR, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));   // (behind the batches queued on the context's stream)
+        FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    }
+    out[3] = flag;
     return FGPU_OK;
 }
 

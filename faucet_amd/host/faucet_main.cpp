@@ -718,11 +718,14 @@ void tell_scan_diagnostics(const Options& o, fgpu_ctx* ctx) {
     double wait_ms = 0;
     if (fgpu_diag_host_waits(ctx, &waits, &wait_ms) == FGPU_OK)
         fprintf(stderr, "[cli]   pass 2: the host waited for the device %llu times, %.2f ms in all\n", (unsigned long long)waits, wait_ms);
-    uint64_t d[6] = {0, 0, 0, 0, 0, 0};
-    if (o.paired_ends && !o.no_cleaning && fgpu_diag_long_pairs(ctx, d) == FGPU_OK)
+    uint64_t d[6] = {0, 0, 0, 0, 0, 0}, form[4] = {0, 0, 0, 0};
+    if (o.paired_ends && !o.no_cleaning && fgpu_diag_long_pairs(ctx, d) == FGPU_OK) {
+        if (fgpu_diag_long_pairs_state) (void)fgpu_diag_long_pairs_state(ctx, form);
         fprintf(stderr, "[cli]   long pair filter on the device: %llu first-end k-mers checked, %llu paired by the filter as their batch found it, %llu inserted; "
-                        "%llu evaluation rounds over %llu batches (at most %llu in one)\n",
-                (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2], (unsigned long long)d[3], (unsigned long long)d[5], (unsigned long long)d[4]);
+                        "%llu evaluation rounds over %llu batches (at most %llu in one); first-set times %s, at most %llu table slots in a batch\n",
+                (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2], (unsigned long long)d[3], (unsigned long long)d[5], (unsigned long long)d[4],
+                form[0] == 2 ? "sparse" : form[0] == 1 ? "dense" : "unknown", (unsigned long long)form[2]);
+    }
     memset(d, 0, sizeof(d));
     if (fgpu_diag_ovw(ctx, d) == FGPU_OK && (d[2] || d[3] || d[5]))
         fprintf(stderr, "[cli]   large clusters, walked optimistically: %llu pieces, %llu rounds over %llu windows (%llu piece-rounds kept their log); "

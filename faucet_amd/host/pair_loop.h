@@ -1,8 +1,9 @@
 // pair_loop.h — scanReads' paired-end loop on the HOST, over the lists the device hands out: the hosts' way on when the device cannot hold the
-// long pair filter's working state.
+// long pair filter's BITS.
 //
-// fgpu_scan_long_pairs keeps 4 bytes of HBM per filter bit (first-set times of its fixed point, csrc/pairs.hip); `--high_cov` sizes that filter
-// at estimated_kmers / 2 x 9 bits (src/Faucet.cpp:279-280), so a large enough run gets FGPU_ERR_NOMEM there -- where the reference has no
+// `--high_cov` sizes that filter at estimated_kmers / 2 x 9 bits (src/Faucet.cpp:279-280).  Where the 4 bytes per bit of fgpu_scan_long_pairs'
+// dense first-set times (csrc/pairs.hip) do not fit, the library keeps the times per batch instead (its sparse state: tai / 8 + O(batch) bytes)
+// and nothing here is needed; only a filter whose bits themselves do not fit the device gets FGPU_ERR_NOMEM -- where the reference has no
 // limit but host memory.  The hosts (faucet_main.cpp, integration/faucet_binding.cpp) then run the reference's own loop
 // (src/ReadScanner.cpp:304-351) over scanInputRead's lists as fgpu_scan_take_stops returns them, batch by batch, in file order:
 //     first end:  back1 = its list          second end:  both lists non-empty -> not_empty_count++, and with cleaning on, for every element of

@@ -5,24 +5,37 @@
 // and the pair counts brought back.  scanInputRead's per-read lists feed the pair filters and the pair counts on the device: the short filter's
 // adds are order-free (fgpu_scan_short_pairs); the long filter's check-then-insert loop (:317-343) is iterated to the sequential result
 // (fgpu_scan_long_pairs), and with --no_cleaning only that loop's two counts are left of it.  Where the device cannot hold the long filter's
-// working state (FGPU_ERR_NOMEM: 4 bytes of HBM per filter bit, and --high_cov sizes the filter at E / 2 x 9 bits, src/Faucet.cpp:279-280) the
-// loop runs HERE instead, over the lists the device hands out (pair_loop.h), straight into the caller's bytes -- the reference has no such
-// limit, so neither have the hosts.  Nothing asks the caller to read its input again: a preview of the junction walk that the library cannot
+// first-set times at 4 bytes per filter bit (--high_cov sizes the filter at E / 2 x 9 bits, src/Faucet.cpp:279-280) the library keeps them per
+// batch instead (its sparse state: a note on stderr says so); where not even the filter's BITS fit (FGPU_ERR_NOMEM) the loop runs HERE, over the
+// lists the device hands out (pair_loop.h), straight into the caller's bytes -- the reference has no such limit, so neither have the hosts.  Nothing asks the caller to read its input again: a preview of the junction walk that the library cannot
 // repair is absorbed inside the library, which scans its own copy of the batches again -- both inputs may be pipes.
 // What the hosts do with the junction map afterwards (write_scan_outputs there, gpu_fill_junction_map here) stays with them.
 // ShardedRun::scan (shard_host.h) is the same pass over several devices; it has no host loop yet.
+// fgpu_diag_long_pairs_state is referred to weakly: a library without it (the tests' CPU stand-in of the ABI) links unchanged and gets no note.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
 #include <functional>
 #include <vector>
 
 #include "faucet_gpu.h"
 #include "pair_loop.h"
 
+#pragma weak fgpu_diag_long_pairs_state
+
 namespace faucet_host {
+
+// after fgpu_scan_long_pairs has set a filter of `tai` bits up: says on stderr, once per run, when its first-set times are kept per batch
+inline void note_long_pairs_state(fgpu_ctx* ctx, uint64_t tai) {
+    static std::atomic<bool> said(false);
+    uint64_t st[4] = {0, 0, 0, 0};
+    if (!fgpu_diag_long_pairs_state || fgpu_diag_long_pairs_state(ctx, st) != FGPU_OK || st[0] != 2) return;
+    if (!said.exchange(true))
+        fprintf(stderr, "note: the long pair filter (%llu bits) keeps its first-set times per batch (sparse state)\n", (unsigned long long)tai);
+}
 
 // a pair filter the scan fills: the caller's tai / 8 bytes (src/Faucet.cpp:266-283).  bits == nullptr: no filter (--no_cleaning, or the
 // single-end scan of a caller without one)
@@ -58,13 +71,14 @@ inline int scan_pass(fgpu_ctx* ctx, int k, const PairTarget& short_pf, const Pai
     if (paired_ends) {
         rc = long_pf.bits ? fgpu_scan_long_pairs(ctx, long_pf.tai, long_pf.n_hash, FGPU_LONG_PAIRS_FILTER) : fgpu_scan_long_pairs(ctx, 0, 0, FGPU_LONG_PAIRS_COUNT);
         if (rc == FGPU_ERR_NOMEM && long_pf.bits) {
-            fprintf(stderr, "note: the long pair filter (%llu bits) does not fit the device's fixed-point form; the paired-end loop runs on the host\n",
+            fprintf(stderr, "note: the long pair filter (%llu bits) does not fit the device; the paired-end loop runs on the host\n",
                     (unsigned long long)long_pf.tai);
             out->host_loop = true;
             rc = fgpu_scan_long_pairs(ctx, 0, 0, FGPU_LONG_PAIRS_OFF);
             if (rc == FGPU_OK && short_pf.bits) SCAN_PASS_TRY(fgpu_scan_short_pairs, ctx, short_pf.tai, short_pf.n_hash, 1);   // (the lists come to the host)
         }
         if (rc != FGPU_OK) { out->failed = "fgpu_scan_long_pairs"; return rc; }
+        if (long_pf.bits && !out->host_loop) note_long_pairs_state(ctx, long_pf.tai);
     }
     HostLongPairs hlp(long_pf.bits, long_pf.tai, long_pf.n_hash, k, true);
     std::vector<fgpu_stop> stops;

@@ -47,6 +47,7 @@
 #pragma weak fgpu_load_slice_end
 #pragma weak fgpu_group_allgather
 #pragma weak fgpu_scan_resident_base
+#pragma weak fgpu_diag_long_pairs_state
 
 namespace faucet_host {
 
@@ -440,6 +441,11 @@ public:
             if (short_pairs) RANK_CHECK(fgpu_scan_short_pairs(c, o_.short_tai, o_.short_hashes, 0));
             if (o_.paired_ends)
                 RANK_CHECK(long_filter ? fgpu_scan_long_pairs(c, o_.long_tai, o_.long_hashes, FGPU_LONG_PAIRS_FILTER) : fgpu_scan_long_pairs(c, 0, 0, FGPU_LONG_PAIRS_COUNT));
+            if (long_filter) {      // (a note on stderr, once per run, when the first-set times are kept per batch: include/faucet_gpu.h)
+                uint64_t form[4] = {0, 0, 0, 0};
+                if (fgpu_diag_long_pairs_state && fgpu_diag_long_pairs_state(c, form) == FGPU_OK && form[0] == 2 && !sparse_said_.exchange(true))
+                    fprintf(stderr, "note: the long pair filter (%llu bits) keeps its first-set times per batch (sparse state)\n", (unsigned long long)o_.long_tai);
+            }
             if (!sliced_counts_.empty()) {
                 // after a sliced pass 1 this rank holds the batches of the whole stream: its own shard's begin behind those of the shards below
                 uint64_t below = 0;
@@ -716,6 +722,7 @@ private:
     std::mutex m_;
     std::condition_variable cv_;
     std::atomic<bool> aborted_{false};
+    std::atomic<bool> sparse_said_{false};     // the note about the long pair filter's sparse state is out
     Announce hint_;
     std::vector<Announce> chain_;
     std::vector<Announce> late_;      // the table a rank was handed, passed on to the rank above as a fresher preview

@@ -393,15 +393,24 @@ int fgpu_scan_short_pairs_download(fgpu_ctx* ctx, uint8_t* out, uint64_t n_bytes
  * After fgpu_scan_long_pairs(tai, n_hash, FGPU_LONG_PAIRS_FILTER) -- the filter create_bloom_filter_optimal would make, src/Faucet.cpp:268-281 --
  * every scan keeps that filter in HBM and applies the loop to each batch's lists as they are harvested, exactly: every list element gets
  * its file-order time, inserts post first-set times per filter bit, and the check / insert decisions are iterated to their fixed point,
- * which is the sequential run's (faucet_amd/csrc/pairs.hip; 4 bytes of HBM per filter bit beside the filter).  Reads 2p and 2p+1 of the
+ * which is the sequential run's (faucet_amd/csrc/pairs.hip).  Reads 2p and 2p+1 of the
  * SCAN (counted over all its batches, empty records included) are a pair; a first end at the end of a batch waits for the next batch.
  * FGPU_LONG_PAIRS_COUNT: only the reference's "Empty count / not empty count" (what --no_cleaning leaves of the loop); tai, n_hash unused.
  * fgpu_scan_long_pairs_download (after fgpu_scan_end): the tai / 8 bytes of the reference's .long_pair_filter (out may be NULL) and the two
  * counts.  Lists then leave the device only if fgpu_scan_short_pairs(..., lists_to_host != 0) asks for them.
+ * The first-set times have two forms.  DENSE: one per filter bit, 4 bytes of HBM per bit beside the filter's tai / 8.  SPARSE: a table per
+ * batch, keyed by bit position -- only the bits that round 0 of a batch posts can carry a time in that batch, at most n_hash per list
+ * element -- so the working state is tai / 8 + O(batch) bytes; a table that cannot be allocated is FGPU_ERR_NOMEM from the batch call.
+ * FGPU_LONG_PAIRS_FILTER chooses: dense where both allocations succeed, sparse where only the bits fit; FGPU_ERR_NOMEM is left for a filter
+ * whose bits themselves do not fit the device (hosts then run the loop themselves, host/pair_loop.h).  FGPU_LONG_PAIRS_FILTER_SPARSE: always
+ * sparse.  The environment variable FGPU_LONG_PAIRS_STATE = dense | sparse | auto (read at every call) overrides the choice of
+ * FGPU_LONG_PAIRS_FILTER: sparse makes it FGPU_LONG_PAIRS_FILTER_SPARSE, dense answers FGPU_ERR_NOMEM where the 4 bytes per bit do not fit.
+ * Both forms compute the same filter, counts and fgpu_diag_long_pairs figures.
  * Needs FGPU_FLAG_RECORD_STOPS; FGPU_LONG_PAIRS_OFF switches it off again.  Only between passes. */
 #define FGPU_LONG_PAIRS_OFF 0
 #define FGPU_LONG_PAIRS_COUNT 1
 #define FGPU_LONG_PAIRS_FILTER 2
+#define FGPU_LONG_PAIRS_FILTER_SPARSE 3
 int fgpu_scan_long_pairs(fgpu_ctx* ctx, uint64_t tai, int32_t n_hash, int32_t mode);
 int fgpu_scan_long_pairs_download(fgpu_ctx* ctx, uint8_t* out, uint64_t n_bytes, uint64_t* empty_count, uint64_t* not_empty_count);
 
@@ -629,6 +638,10 @@ int fgpu_diag_late_flags(fgpu_ctx* ctx, uint64_t out[3]);
  * paired against the filter as their batch found it, [2] addPair calls, [3] evaluation rounds over all batches, [4] most rounds one batch
  * needed, [5] batches */
 int fgpu_diag_long_pairs(fgpu_ctx* ctx, uint64_t out[6]);
+/* after fgpu_scan_long_pairs: the form of the filter's first-set times.  [0] 0 no filter on the device, 1 dense, 2 sparse, [1] bytes of working
+ * state the filter holds beyond its tai / 8 bytes of bits, [2] sparse: most slots a batch's table had in the last scan (a power of two),
+ * [3] sparse: the internal-error flag (a table that ran full or missed a key; fgpu_scan_end then answers FGPU_ERR_STATE) */
+int fgpu_diag_long_pairs_state(fgpu_ctx* ctx, uint64_t out[4]);
 /* after fgpu_scan_end: the optimistic walk of large clusters: [0] pieces it walked, [1] rounds it ran, [2] windows it settled,
  * [3] windows it left to the key-ordered walk (rounds that did not settle, full tables), [4] piece-rounds in which a piece kept its log (no
  * earlier piece had changed what it reads), [5] windows whose large clusters outgrew the tables of both walks (walked by cluster) */
