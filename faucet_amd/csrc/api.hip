@@ -449,6 +449,7 @@ void fgpu_destroy(fgpu_ctx* ctx) {
     for (BatchBufs* b : ctx->all_batches) {
         if (b->pure_done) hipEventDestroy(b->pure_done);
         if (b->walk_done) hipEventDestroy(b->walk_done);
+        for (hipEvent_t e : b->range_ev) if (e) hipEventDestroy(e);
         delete b;
     }
     delete ctx;
@@ -698,6 +699,19 @@ int fgpu_scan_begin(fgpu_ctx* ctx) {
     ctx->dbg_stall_us = getenv("FGPU_DEBUG_WALK_STALL_US") ? std::min(100000, std::max(0, atoi(getenv("FGPU_DEBUG_WALK_STALL_US")))) : 0;
     ctx->dbg_delta_check = getenv("FGPU_DEBUG_DELTA_CHECK") != nullptr;
     ctx->no_sparse_link = getenv("FGPU_NO_SPARSE_LINK") != nullptr;      // measurement aid: no candidate planes, every window of a prepared batch linked in full
+    // ranges of the pure stage's back half (scan_pure.hip): n >= 8 forces 2^n positions per range (tests), 0 one range per batch -- the schedule
+    // before there were ranges, also what FGPU_NO_OVERLAP=1 runs (the walk follows on the same stream); anything else: the default policy
+    ctx->scan_range_log2 = -1;
+    if (const char* e = getenv("FGPU_SCAN_RANGE_LOG2")) {
+        char* end = nullptr;
+        const long n = strtol(e, &end, 10);
+        if (end == e || *end || (n != 0 && (n < 8 || n > 40))) {      // (empty, not a number, 1..7, beyond 2^40: no silent meaning)
+            ctx->err = std::string("FGPU_SCAN_RANGE_LOG2=") + e + ": 0 (one range per batch) or 8..40 (ranges of 2^n positions)";
+            return FGPU_ERR_ARG;
+        }
+        ctx->scan_range_log2 = (int)n;
+    }
+    if (fgpu_walk_no_overlap()) ctx->scan_range_log2 = 0;
     // calibrated upwards window by window; a context that has scanned before starts a quarter below where that scan ended up
     const uint64_t start_span = std::max<uint64_t>(1ULL << 18, ctx->settled_span / 4);
     ctx->window_span = ctx->prm.walk_window_span ? std::min<uint64_t>(std::max<uint64_t>(ctx->prm.walk_window_span, 64), ctx->max_span)
@@ -784,6 +798,21 @@ static void adapt_window(fgpu_ctx* ctx) {
     ctx->adapt_overflows = ctx->counters_host->ko_overflows;
 }
 
+// a batch's buffers (empty) with its events, made once
+static BatchBufs* new_batch(fgpu_ctx* ctx) {
+    BatchBufs* b = new BatchBufs();
+    ctx->all_batches.push_back(b);
+    hipEventCreateWithFlags(&b->pure_done, hipEventDisableTiming);
+    hipEventCreateWithFlags(&b->walk_done, hipEventDisableTiming);
+    bool all = true;
+    for (hipEvent_t& e : b->range_ev) all = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess && all;
+    if (!all) {      // without every range event the batch's back half stays one range (scan_range_plan looks at slot 0)
+        for (hipEvent_t& e : b->range_ev) { if (e) hipEventDestroy(e); e = nullptr; }
+        (void)hipGetLastError();
+    }
+    return b;
+}
+
 static BatchBufs* acquire_batch(fgpu_ctx* ctx) {
     // FIFO over (at least) two BatchBufs, so that the one handed out was last walked two batches ago
     BatchBufs* b;
@@ -799,10 +828,7 @@ static BatchBufs* acquire_batch(fgpu_ctx* ctx) {
         b = ctx->pool[at];
         ctx->pool.erase(ctx->pool.begin() + at);
     } else {
-        b = new BatchBufs();
-        ctx->all_batches.push_back(b);
-        hipEventCreateWithFlags(&b->pure_done, hipEventDisableTiming);
-        hipEventCreateWithFlags(&b->walk_done, hipEventDisableTiming);
+        b = new_batch(ctx);
     }
     return b;
 }
@@ -814,7 +840,8 @@ static void note_walked(fgpu_ctx* ctx, BatchBufs* b) {
     ctx->to_harvest.push_back(b);
 }
 
-static int scan_pure_into(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads) {
+// one_range: the batch is prepared ahead of its turn -- nothing walks it beside its own pure stage, so its back half is not cut into ranges
+static int scan_pure_into(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads, bool one_range = false) {
     if (b->stops_pending) {   // the buffers still hold the visit planes of an earlier batch: bring its lists to the host first
         int hrc = fgpu_scan_harvest(ctx, b);
         if (hrc) return hrc;      // (FGPU_INTERNAL_REPLAY: that batch's walk went wrong; the caller replays and comes back)
@@ -832,7 +859,7 @@ static int scan_pure_into(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads) 
     ctx->host_ms[1] += fgpu_host_now() - t_b;
     if (!rc) rc = journal_add(ctx, b, reads);
     uint64_t n_pieces = 0;
-    if (!rc) rc = fgpu_stage_scan_pure(ctx, &n_pieces);   // ends with the batch's only synchronisation (piece count)
+    if (!rc) rc = fgpu_stage_scan_pure(ctx, &n_pieces, one_range);   // ends with the batch's only synchronisation (piece count)
     if (!rc) ctx->journal_max_read_len = std::max<uint64_t>(ctx->journal_max_read_len, ctx->counters_host->max_read_len);
     if (!rc) rc = check_errors(ctx);
     if (!rc) ctx->scan_stats.reads_processed += reads->n_reads;
@@ -995,7 +1022,7 @@ static int scan_replay_once(fgpu_ctx* ctx) {
             FGPU_HIP(hipMemcpyAsync(b->bad.p, j->bad.p, bbytes, hipMemcpyDeviceToDevice, ctx->stream));
         }
         uint64_t n_pieces = 0;
-        rc = fgpu_stage_scan_pure(ctx, &n_pieces);
+        rc = fgpu_stage_scan_pure(ctx, &n_pieces, true);      // (the replay: one range per batch)
         if (!rc) rc = check_errors(ctx);
         if (!rc && b->pure_done) FGPU_HIP(hipEventRecord(b->pure_done, ctx->stream));
         if (!rc) rc = fgpu_scan_reserve(ctx, ctx->counters_host->n_junctions + ctx->scan_imported);
@@ -1061,13 +1088,8 @@ int fgpu_scan_prepare(fgpu_ctx* ctx, const fgpu_reads* reads) {
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     BatchBufs* b;
     if (!ctx->pool.empty()) { b = ctx->pool.front(); ctx->pool.erase(ctx->pool.begin()); }
-    else {
-        b = new BatchBufs();
-        ctx->all_batches.push_back(b);
-        hipEventCreateWithFlags(&b->pure_done, hipEventDisableTiming);
-        hipEventCreateWithFlags(&b->walk_done, hipEventDisableTiming);
-    }
-    rc = scan_pure_into(ctx, b, reads);
+    else b = new_batch(ctx);
+    rc = scan_pure_into(ctx, b, reads, true);
     ctx->cur = &ctx->bb_default;
     if (rc == FGPU_INTERNAL_REPLAY) {   // (only after walks of this scan: prepare-only scans never get here)
         ctx->pool.insert(ctx->pool.begin(), b);

@@ -29,6 +29,11 @@
 #define FGPU_USUAL_SPAN (1ULL << 26)
 #define FGPU_MAX_SPAN (1ULL << 26)
 
+// events per batch for the ranges of the pure stage's back half (BatchBufs::range_ev)
+#define FGPU_RANGE_EVENTS 16
+// ... and the shortest range the default policy cuts off: a range costs three launches, an event and the thin end of its junction-test kernel
+#define FGPU_RANGE_MIN (1ULL << 20)
+
 // A growable device buffer (hipMalloc'd; freed with the context).
 struct DevBuf {
     void*    p = nullptr;
@@ -66,6 +71,14 @@ struct BatchBufs {
     uint64_t n_pieces = 0;         // valid pieces found by the pure scan stage
     uint64_t max_piece_span = 0;   // longest read (+64): how far a piece may reach past its scheduling window
     hipEvent_t pure_done = nullptr;   // main stream: planes of this batch are complete
+    // The pure stage's back half (snapshot look-up, need plane, junction tests) is issued by ranges of positions, an event behind each: a window
+    // of the walk waits for the range its pieces end in, not for the batch.  n_ranges <= 1: pure_done is all there is.
+    // Range r records range_ev[r % FGPU_RANGE_EVENTS]; a waiter issued after all of them waits for the slot's LAST record, a range at or beyond r.
+    hipEvent_t range_ev[FGPU_RANGE_EVENTS] = {};
+    uint64_t range_first = 0;      // positions of range 0 ...
+    uint64_t range_span = 0;       // ... and of every further range (multiples of 64)
+    uint64_t n_ranges = 0;
+    uint64_t ranges_waited = 0;    // walk stage: ranges its windows have waited for so far
     hipEvent_t walk_done = nullptr;   // walk stream: the walk has finished with this batch's buffers
     bool walk_pending = false;
     uint32_t planes_gen = 0;       // read shards: the preview (fgpu_scan_import_hint, counted from 1) the snapshot planes nF / nB speak of; 0 = an empty table
@@ -337,6 +350,7 @@ struct fgpu_ctx {
     int dbg_stall_us = 0;            // FGPU_DEBUG_WALK_STALL_US, FGPU_DEBUG_DELTA_CHECK: read once per scan (fgpu_scan_begin), not from the walk's inner calls
     bool dbg_delta_check = false;
     bool no_sparse_link = false;     // FGPU_NO_SPARSE_LINK, read once per scan
+    int scan_range_log2 = -1;        // FGPU_SCAN_RANGE_LOG2, read once per scan: >= 8 forces ranges of 2^n positions, 0 one range per batch; -1: the default policy
     DevBuf import_probe;             // device: [0] largest piece number among the entries of the last import, [1] entries newer than the preview, [2] [3] digest of the others
     uint64_t scan_grown = 0;         // times the junction table was rehashed into a larger one
 
@@ -542,14 +556,17 @@ int fgpu_load_pass_end(fgpu_ctx* ctx, fgpu_load_stats* stats);
 int fgpu_load_pair_begin(fgpu_ctx* ctx);
 int fgpu_load_pair_end(fgpu_ctx* ctx);
 void fgpu_resident_reset(fgpu_ctx* ctx, bool keep_going);
-int fgpu_stage_scan_pure(fgpu_ctx* ctx, uint64_t* n_pieces);
+int fgpu_stage_scan_pure(fgpu_ctx* ctx, uint64_t* n_pieces, bool one_range);      // one_range: the back half is not cut (prepared batches, the replay)
+bool fgpu_walk_no_overlap();                                                       // FGPU_NO_OVERLAP=1 (scan_walk.hip's knobs, read once per process)
 int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces);
-int fgpu_stage_scan_need(fgpu_ctx* ctx);
+int fgpu_stage_scan_need(fgpu_ctx* ctx);                                           // whole batch: the need plane cleared, the hash plane there
+int fgpu_stage_scan_need_lookup(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi);      // words [w_lo, w_hi): snapshot planes and hashes
+int fgpu_stage_scan_need_prewalk(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi);     // the pieces that start in those words: their need bits
 int fgpu_scan_refresh_planes(fgpu_ctx* ctx, BatchBufs* b);
 int fgpu_scan_build_cand(fgpu_ctx* ctx, BatchBufs* b);
 int fgpu_scan_import_probe(fgpu_ctx* ctx, const void* dev_entries, uint64_t n, uint64_t after_seq, uint32_t* dfilter, uint64_t dfilter_bits,
                            uint64_t* max_seq, uint64_t* n_newer, uint64_t digest[2]);
-int fgpu_stage_scan_debug_drop(fgpu_ctx* ctx);
+int fgpu_stage_scan_debug_drop(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi);
 int fgpu_util_count_segments(fgpu_ctx* ctx, const void* bad, uint64_t n_words, int minlen);
 int fgpu_util_popcount(fgpu_ctx* ctx, const void* dev, uint64_t nbytes, unsigned long long* dev_out);
 int fgpu_util_or(fgpu_ctx* ctx, void* dst, const void* src, uint64_t nbytes);

@@ -212,22 +212,22 @@ __global__ void __launch_bounds__(256) k_scan_piece_read(const uint2* __restrict
 // lanes of a wave idle while the others wait for their probes: instead a wave takes 256 positions at a time, gathers the
 // two work masks of each of the four words, and hands the set bits out densely, 64 items per round (rank -> word by
 // prefix counts, rank within the word -> bit by popcount bisection).  Results are rare non-zero bits: atomicOr into
-// zero-initialised planes.
+// zero-initialised planes.  Words [w_lo, w_hi) of the batch (a range of the stage's back half; pm is complete for the whole batch).
 __global__ void __launch_bounds__(256) k_scan_flags(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ pm,
-                                                    const uint64_t* __restrict__ need, uint64_t T, uint64_t n_words, FdParams fp, const uint32_t* __restrict__ bloom,
+                                                    const uint64_t* __restrict__ need, uint64_t T, uint64_t w_lo, uint64_t w_hi, FdParams fp, const uint32_t* __restrict__ bloom,
                                                     unsigned long long* ff, unsigned long long* fb, unsigned long long* cf0,
                                                     unsigned long long* cf1, unsigned long long* cb0, unsigned long long* cb1,
                                                     DevCounters* cnt) {
     const int lane = fd_lane();
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    const uint64_t n_chunks = (n_words + 3) / 4;
+    const uint64_t n_chunks = (w_hi - w_lo + 3) / 4;
     unsigned long long n_eval = 0, n_piece = 0;
     for (uint64_t chunk = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; chunk < n_chunks; chunk += n_waves) {
-        // lanes 0..3: forward work mask of word 4*chunk + lane; lanes 4..7: backward work mask of word 4*chunk + lane - 4
+        // lanes 0..3: forward work mask of word w_lo + 4*chunk + lane; lanes 4..7: backward work mask of word w_lo + 4*chunk + lane - 4
         uint64_t mine = 0;
         if (lane < 8) {
-            const uint64_t w = chunk * 4 + (lane & 3);
-            if (w < n_words) {
+            const uint64_t w = w_lo + chunk * 4 + (lane & 3);
+            if (w < w_hi) {
                 const uint64_t tmask = (w + 1) * 64 <= T ? ~0ULL : (T > w * 64 ? (1ULL << (T - w * 64)) - 1 : 0ULL);
                 const uint64_t pmw = pm[w] & tmask, nd = need[w] & tmask;
                 if (lane < 4) {
@@ -256,7 +256,7 @@ __global__ void __launch_bounds__(256) k_scan_flags(const uint64_t* __restrict__
             for (int c = 1; c < 8; c++)
                 if (t >= cum[c]) { q = c; mq = m[c]; before = cum[c]; }
             const int bit = select_bit(mq, t - before);
-            const uint64_t w = chunk * 4 + (q & 3);
+            const uint64_t w = w_lo + chunk * 4 + (q & 3);
             const uint64_t pos = w * 64 + bit;
             const uint64_t km = fd_kmer_at(codes, pos, fp.k);
             bool flag;
@@ -287,6 +287,7 @@ __global__ void __launch_bounds__(256) k_scan_flags(const uint64_t* __restrict__
 // come from a pool the wave shares: 64 words (one per lane) of forward / backward work masks in LDS with their prefix counts;
 // item t is found by bisection over the prefix counts.  The pool rolls on to the next 64 words as soon as it is empty, while
 // unfinished chains of the previous words are still running (they hold everything they need in registers).
+// The kernel takes words [w_lo, w_hi) of the batch: the pools start at w_lo and the last one ends at w_hi.
 struct FlagPool {
     unsigned long long mf[64], mb[64];
     int excl[64];
@@ -308,7 +309,7 @@ struct FlagChain {
 
 template <int S>
 __global__ void __launch_bounds__(256) k_scan_flags_sm(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ pm,
-                                                       const uint64_t* __restrict__ need, uint64_t T, uint64_t n_words, FdParams fp,
+                                                       const uint64_t* __restrict__ need, uint64_t T, uint64_t w_lo, uint64_t w_hi, FdParams fp,
                                                        const uint32_t* __restrict__ bloom, unsigned long long* ff, unsigned long long* fb,
                                                        unsigned long long* cf0, unsigned long long* cf1, unsigned long long* cb0,
                                                        unsigned long long* cb1, DevCounters* cnt) {
@@ -322,7 +323,7 @@ __global__ void __launch_bounds__(256) k_scan_flags_sm(const uint64_t* __restric
     const uint64_t lt_mask = (1ULL << lane) - 1;
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
     const uint64_t wv = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t n_groups = (n_words + 63) / 64;
+    const uint64_t n_groups = (w_hi - w_lo + 63) / 64;
     uint64_t grp = wv * n_groups / n_waves;
     const uint64_t grp_end = (wv + 1) * n_groups / n_waves;
     unsigned long long n_eval = 0, n_piece = 0;
@@ -340,9 +341,9 @@ __global__ void __launch_bounds__(256) k_scan_flags_sm(const uint64_t* __restric
         for (int q = 0; q < S; q++) { idle[q] = __ballot(!(ch[q].st & FC_ACTIVE)); any_idle |= idle[q]; }
         while (any_idle && (next < total || grp < grp_end)) {
             if (next == total) {   // the pool is empty: the next 64 words
-                const uint64_t w = grp * 64 + lane;
+                const uint64_t w = w_lo + grp * 64 + lane;
                 uint64_t f = 0, b = 0;
-                if (w < n_words) {
+                if (w < w_hi) {
                     const uint64_t tmask = (w + 1) * 64 <= T ? ~0ULL : (T > w * 64 ? (1ULL << (T - w * 64)) - 1 : 0ULL);
                     const uint64_t pmw = pm[w] & tmask, nd = need[w] & tmask;
                     f = nd & pmw & ((pmw >> 1) | (pm[w + 1] << 63));              // a window follows: facing forward
@@ -362,7 +363,7 @@ __global__ void __launch_bounds__(256) k_scan_flags_sm(const uint64_t* __restric
                 pools[wid].excl[lane] = incl - c;
                 total = __builtin_amdgcn_readlane(incl, 63);
                 next = 0;
-                pool_word0 = grp * 64;
+                pool_word0 = w_lo + grp * 64;
                 grp++;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
@@ -531,10 +532,96 @@ int fgpu_util_probe_stage3(fgpu_ctx* ctx, const uint64_t* d_kmers, uint64_t n, i
     return FGPU_OK;
 }
 
-int fgpu_stage_scan_pure(fgpu_ctx* ctx, uint64_t* n_pieces) {
+// testForJunction at the need positions of words [w_lo, w_hi) of the current batch
+static int scan_pure_flags(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi) {
+    BatchBufs& bb = *ctx->cur;
+    const uint64_t nw = w_hi - w_lo;
+    // twice the usual grid: shorter-lived blocks free wave slots more often, which lets the high-priority walk kernels of the
+    // previous batch in sooner (walk stage 86 -> 80 ms per step; beyond 16 K blocks the flags kernel itself slows down)
+    const unsigned flags_grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>(nw / 16, 1), 2 * FGPU_GRID_BLOCKS);
+    static const int sm_blocks = getenv("FGPU_FLAGS_SM_BLOCKS") ? atoi(getenv("FGPU_FLAGS_SM_BLOCKS")) : 4096;
+    if (ctx->fd.j <= 1 && sm_blocks > 0) {
+        const unsigned sm_grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>((nw + 255) / 256, 1), (uint64_t)sm_blocks);
+        static const int sm_slots = getenv("FGPU_FLAGS_SM_SLOTS") ? atoi(getenv("FGPU_FLAGS_SM_SLOTS")) : 1;
+#define FGPU_FLAGS_SM(SLOTS)                                                                                                        \
+    FGPU_LAUNCH("scan_flags", k_scan_flags_sm<SLOTS>, sm_grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,           \
+                (const uint64_t*)bb.need.p, bb.T, w_lo, w_hi, ctx->fd, (const uint32_t*)ctx->bloo2, (unsigned long long*)bb.ff.p,    \
+                (unsigned long long*)bb.fb.p, (unsigned long long*)bb.cf0.p, (unsigned long long*)bb.cf1.p,                         \
+                (unsigned long long*)bb.cb0.p, (unsigned long long*)bb.cb1.p, ctx->counters)
+        if (sm_slots <= 1) FGPU_FLAGS_SM(1);
+        else if (sm_slots == 2) FGPU_FLAGS_SM(2);
+        else if (sm_slots == 3) FGPU_FLAGS_SM(3);
+        else FGPU_FLAGS_SM(4);
+#undef FGPU_FLAGS_SM
+    } else
+        FGPU_LAUNCH("scan_flags", k_scan_flags, flags_grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,
+                    (const uint64_t*)bb.need.p, bb.T, w_lo, w_hi, ctx->fd, (const uint32_t*)ctx->bloo2, (unsigned long long*)bb.ff.p,
+                    (unsigned long long*)bb.fb.p, (unsigned long long*)bb.cf0.p, (unsigned long long*)bb.cf1.p,
+                    (unsigned long long*)bb.cb0.p, (unsigned long long*)bb.cb1.p, ctx->counters);
+    return FGPU_OK;
+}
+
+// How the current batch's back half is cut: positions of the first range and of every further one (multiples of 64; first >= T: one range).
+// A range costs launches and, worse, the thin end of a junction-test kernel (the more the smaller the kernel), and a window of the walk waits
+// for the range its pieces END in: what pays is few ranges that end where windows end.  By default two: the first ends behind the window
+// nearest to two thirds of the batch (plus the longest piece's reach, so that the window itself need not wait for the second range), the
+// second takes the rest.  Measured on config 2 (windows of 2^25 positions, four to a batch): DESIGN.md section 7.
+// One range: batches prepared ahead of their turn and the journal's replay (their walks do not run beside this stage), batches without range
+// events, batches of a single window or too short to cut, FGPU_SCAN_RANGE_LOG2=0.  FGPU_SCAN_RANGE_LOG2=n >= 8 (tests): ranges of 2^n positions.
+static void scan_range_plan(const fgpu_ctx* ctx, const BatchBufs& bb, bool one_range, uint64_t* first, uint64_t* further) {
+    const uint64_t whole = bb.n_words * 64;
+    *first = *further = whole;
+    if (one_range || !bb.range_ev[0] || ctx->scan_range_log2 == 0) return;
+    if (ctx->scan_range_log2 > 0) { *first = *further = 1ULL << ctx->scan_range_log2; return; }
+    const uint64_t span = ctx->window_span;      // (as of the previous batch's walk: the controller may move it before this batch's -- later waits, same results)
+    if (span >= bb.T || bb.T < 2 * FGPU_RANGE_MIN) return;
+    const uint64_t n_windows = (bb.T + span - 1) / span;
+    uint64_t m = (uint64_t)(2.0 * (double)bb.T / (3.0 * (double)span) + 0.5);
+    m = std::min<uint64_t>(std::max<uint64_t>(m, 1), n_windows - 1);
+    const uint64_t cut = (m * span + bb.max_piece_span + 63) & ~63ULL;
+    if (cut + FGPU_RANGE_MIN > bb.T) return;
+    *first = cut;
+    *further = whole - cut;
+}
+
+// The back half of the pure stage -- everything that reads the junction table, and the junction tests -- issued range by range in stream
+// order with an event behind each range, so that the walk of THIS batch can begin while the batch's later ranges are still made (DESIGN.md
+// section 4):
+//   look-up (snapshot planes nF / nB, hashes)   per position
+//   prewalk (need bits)                         per piece that starts in the range; reads nF / nB to the piece's end and marks need bits as far:
+//                                               the look-up runs ahead of the range by the longest piece
+//   flags                                       per need position of the range; the pieces that can mark one start in this range or before it
+// L(0+) P(0) F(0) event 0, L(1+) P(1) F(1) event 1, ...
+static int scan_pure_back(fgpu_ctx* ctx, bool one_range) {
+    BatchBufs& bb = *ctx->cur;
+    int rc;
+    uint64_t first, further;
+    scan_range_plan(ctx, bb, one_range, &first, &further);
+    const uint64_t first_words = std::max<uint64_t>(first / 64, 1), further_words = std::max<uint64_t>(further / 64, 1);
+    const uint64_t reach_words = (bb.max_piece_span + 63) / 64 + 1;
+    bb.range_first = first_words * 64;
+    bb.range_span = further_words * 64;
+    bb.n_ranges = bb.n_words <= first_words ? 1 : 1 + (bb.n_words - first_words + further_words - 1) / further_words;
+    uint64_t looked = 0;      // words whose look-up has been issued
+    for (uint64_t r = 0, lo = 0; lo < bb.n_words; r++) {
+        const uint64_t hi = std::min(bb.n_words, lo + (r ? further_words : first_words));
+        const uint64_t look_to = std::min(bb.n_words, hi + reach_words);
+        if (looked < look_to) {
+            if ((rc = fgpu_stage_scan_need_lookup(ctx, looked, look_to))) return rc;
+            looked = look_to;
+        }
+        if ((rc = fgpu_stage_scan_need_prewalk(ctx, lo, hi)) || (rc = scan_pure_flags(ctx, lo, hi)) || (rc = fgpu_stage_scan_debug_drop(ctx, lo, hi))) return rc;
+        if (bb.n_ranges > 1) FGPU_HIP(hipEventRecord(bb.range_ev[r % FGPU_RANGE_EVENTS], ctx->stream));
+        lo = hi;
+    }
+    return FGPU_OK;
+}
+
+int fgpu_stage_scan_pure(fgpu_ctx* ctx, uint64_t* n_pieces, bool one_range) {
     BatchBufs& bb = *ctx->cur;
     *n_pieces = 0;
     bb.n_pieces = 0;   // the buffers are recycled: an empty batch must not inherit the previous batch's pieces
+    bb.n_ranges = 0;   // ... nor its ranges
     if (bb.T == 0) return FGPU_OK;
     const uint64_t wb = (bb.n_words + FGPU_PADW) * 8;
     int rc;
@@ -600,32 +687,11 @@ int fgpu_stage_scan_pure(fgpu_ctx* ctx, uint64_t* n_pieces) {
             FGPU_LAUNCH("piece_read", k_scan_piece_read, fgpu_blocks(np, 256), 256, (const uint2*)bb.pieces.p, np, bb.d_offs, bb.n_reads,
                         (uint32_t*)bb.piece_read.p);
         }
+        // whole-batch clears first: the need plane (and the hash plane's room), the six flag / count planes -- then the back half by ranges
         if ((rc = fgpu_stage_scan_need(ctx))) return rc;
         DevBuf* outs[] = {&bb.ff, &bb.fb, &bb.cf0, &bb.cf1, &bb.cb0, &bb.cb1};
         for (DevBuf* o : outs) FGPU_HIP(hipMemsetAsync(o->p, 0, wb, ctx->stream));
-        // twice the usual grid: shorter-lived blocks free wave slots more often, which lets the high-priority walk kernels of the
-        // previous batch in sooner (walk stage 86 -> 80 ms per step; beyond 16 K blocks the flags kernel itself slows down)
-        const unsigned flags_grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>(bb.n_words / 16, 1), 2 * FGPU_GRID_BLOCKS);
-        static const int sm_blocks = getenv("FGPU_FLAGS_SM_BLOCKS") ? atoi(getenv("FGPU_FLAGS_SM_BLOCKS")) : 4096;
-        if (ctx->fd.j <= 1 && sm_blocks > 0) {
-            const unsigned sm_grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>((bb.n_words + 255) / 256, 1), (uint64_t)sm_blocks);
-            static const int sm_slots = getenv("FGPU_FLAGS_SM_SLOTS") ? atoi(getenv("FGPU_FLAGS_SM_SLOTS")) : 1;
-#define FGPU_FLAGS_SM(SLOTS)                                                                                                        \
-    FGPU_LAUNCH("scan_flags", k_scan_flags_sm<SLOTS>, sm_grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,           \
-                (const uint64_t*)bb.need.p, bb.T, bb.n_words, ctx->fd, (const uint32_t*)ctx->bloo2, (unsigned long long*)bb.ff.p,    \
-                (unsigned long long*)bb.fb.p, (unsigned long long*)bb.cf0.p, (unsigned long long*)bb.cf1.p,                         \
-                (unsigned long long*)bb.cb0.p, (unsigned long long*)bb.cb1.p, ctx->counters)
-            if (sm_slots <= 1) FGPU_FLAGS_SM(1);
-            else if (sm_slots == 2) FGPU_FLAGS_SM(2);
-            else if (sm_slots == 3) FGPU_FLAGS_SM(3);
-            else FGPU_FLAGS_SM(4);
-#undef FGPU_FLAGS_SM
-        } else
-        FGPU_LAUNCH("scan_flags", k_scan_flags, flags_grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,
-                    (const uint64_t*)bb.need.p, bb.T, bb.n_words, ctx->fd, (const uint32_t*)ctx->bloo2, (unsigned long long*)bb.ff.p,
-                    (unsigned long long*)bb.fb.p, (unsigned long long*)bb.cf0.p, (unsigned long long*)bb.cf1.p,
-                    (unsigned long long*)bb.cb0.p, (unsigned long long*)bb.cb1.p, ctx->counters);
-        if ((rc = fgpu_stage_scan_debug_drop(ctx))) return rc;
+        if ((rc = scan_pure_back(ctx, one_range))) return rc;
     }
     ctx->host_ms[4] += fgpu_host_now() - t_c;
     return FGPU_OK;

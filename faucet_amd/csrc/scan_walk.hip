@@ -2374,10 +2374,10 @@ __global__ void k_debug_stall(unsigned long long ticks) {
     while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
 }
 
-__global__ void __launch_bounds__(256) k_debug_need_drop(uint64_t n_words, uint64_t* __restrict__ ff, uint64_t* __restrict__ fb,
+__global__ void __launch_bounds__(256) k_debug_need_drop(uint64_t w_lo, uint64_t w_hi, uint64_t* __restrict__ ff, uint64_t* __restrict__ fb,
                                                          uint64_t* need, uint64_t* cf0, uint64_t* cf1, uint64_t* cb0, uint64_t* cb1, int mode,
                                                          const uint64_t* __restrict__ pm, const uint32_t* __restrict__ kh) {
-    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * blockDim.x) {
+    for (uint64_t w = w_lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < w_hi; w += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t drop = need[w] & ~(ff[w] | fb[w]) & fd_mix(w * 0x9E3779B97F4A7C15ULL + 12345);
         // mode 2: the evaluated positions of one k-mer in 16 (chosen by the k-mer's hash: all its occurrences alike) go whatever the answer
         // was, so that the walk meets tests that come out TRUE at k-mers nobody registered (fill_missing's late junction tests)
@@ -2407,10 +2407,11 @@ __global__ void __launch_bounds__(256) k_debug_need_drop(uint64_t n_words, uint6
 // New junctions created inside a scanned stretch (flagged, spacer, fake) start with distance 0, i.e. the walk goes on
 // scanning: they do not change which positions are visited.  The walk double-checks: before it scans a position whose need bit
 // is clear it evaluates that position's tests itself (fill_missing); it never silently uses a flag that was not computed.
-__global__ void __launch_bounds__(256) k_need_lookup(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ pm, uint64_t n_words,
+// (words [w_first, w_end) of the batch: a range of the pure stage's back half, or the words of a window whose planes the walk makes again)
+__global__ void __launch_bounds__(256) k_need_lookup(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ pm, uint64_t w_end,
                                                      FdParams fp, JTable jt, uint64_t* __restrict__ nF, uint64_t* __restrict__ nB,
                                                      uint32_t* __restrict__ kh, uint64_t w_first) {
-    const uint64_t total = n_words * 64;
+    const uint64_t total = w_end * 64;
     for (uint64_t p = w_first * 64 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (uint64_t)gridDim.x * blockDim.x) {
         bool inF = false, inB = false;
         if ((pm[p >> 6] >> (p & 63)) & 1ULL) {
@@ -2486,10 +2487,13 @@ __device__ __forceinline__ void need_mark(unsigned long long* need, uint64_t a, 
     }
 }
 
-__global__ void __launch_bounds__(256) k_need_prewalk(const uint64_t* __restrict__ codes, const uint2* __restrict__ pieces, uint64_t n_pieces,
-                                                      FdParams fp, JTable jt, const uint64_t* __restrict__ nF, const uint64_t* __restrict__ nB,
-                                                      unsigned long long* need, int tight) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pieces; i += (uint64_t)gridDim.x * blockDim.x) {
+// The pieces that START in words [w_lo, w_hi): their numbers come from two rank queries, as a window's do (make_window).  Such a piece reads
+// nF / nB up to its own end, at most max_piece_span positions beyond w_hi, and marks need bits as far.
+__global__ void __launch_bounds__(256) k_need_prewalk(const uint64_t* __restrict__ codes, const uint2* __restrict__ pieces, const uint32_t* __restrict__ prefix,
+                                                      uint64_t w_lo, uint64_t w_hi, FdParams fp, JTable jt, const uint64_t* __restrict__ nF,
+                                                      const uint64_t* __restrict__ nB, unsigned long long* need, int tight) {
+    const uint64_t i_first = prefix[w_lo], i_end = prefix[w_hi];      // (prefix[w] = piece starts in the words before w; it has an entry for w = n_words)
+    for (uint64_t i = i_first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < i_end; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint2 pc = pieces[i];
         const uint64_t p0 = pc.x;
         const uint32_t nwin = pc.y;
@@ -2653,23 +2657,39 @@ int fgpu_scan_reset(fgpu_ctx* ctx) {
     return FGPU_OK;
 }
 
-// Pure-stage helper (main stream): need plane of the current batch = superset of the positions the walk will scan.
+// Pure-stage helpers (main stream).  The need plane of a batch = a superset of the positions the walk will scan.  This one is the whole-batch
+// part, ahead of any range: the plane cleared (all ones for an eager scan) and room for the hash plane; the ranges fill both in (below).
 int fgpu_stage_scan_need(fgpu_ctx* ctx) {
     BatchBufs& bb = *ctx->cur;
     const uint64_t wb = (bb.n_words + FGPU_PADW) * 8;
     const bool eager = (ctx->prm.flags & FGPU_FLAG_EAGER_FLAGS) || ctx->eager_runtime || ctx->eager_scan;   // evaluate testForJunction everywhere
     FGPU_HIP(hipMemsetAsync(bb.need.p, eager ? 0xFF : 0, wb, ctx->stream));
     if (!bb.n_pieces) return FGPU_OK;
-    if (int rc = fgpu_ensure_b(ctx, &bb.kh, (bb.n_words + FGPU_PADW) * 64 * 4)) return rc;
+    return fgpu_ensure_b(ctx, &bb.kh, (bb.n_words + FGPU_PADW) * 64 * 4);
+}
 
-    static const int need_tight = getenv("FGPU_NEED_TIGHT") ? atoi(getenv("FGPU_NEED_TIGHT")) : 2;   // measurement aid, see k_need_prewalk
-    JTable jt = make_jt(ctx);
+// ... of words [w_lo, w_hi) of the batch: the snapshot planes nF / nB against the table as it stands, and the hash plane
+int fgpu_stage_scan_need_lookup(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi) {
+    BatchBufs& bb = *ctx->cur;
+    if (!bb.n_pieces || w_lo >= w_hi) return FGPU_OK;
     // also with eager flags: this kernel writes the hash plane the walk stage's kernels work from
-    FGPU_LAUNCH("need_lookup", k_need_lookup, fgpu_grid(bb.n_words * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,
-                bb.n_words, ctx->fd, jt, (uint64_t*)bb.nF.p, (uint64_t*)bb.nB.p, (uint32_t*)bb.kh.p, (uint64_t)0);
-    if (eager) return FGPU_OK;
-    FGPU_LAUNCH("need_prewalk", k_need_prewalk, fgpu_grid(bb.n_pieces, 256), 256, (const uint64_t*)bb.codes.p, (const uint2*)bb.pieces.p,
-                bb.n_pieces, ctx->fd, jt, (const uint64_t*)bb.nF.p, (const uint64_t*)bb.nB.p, (unsigned long long*)bb.need.p, need_tight);
+    FGPU_LAUNCH("need_lookup", k_need_lookup, fgpu_grid((w_hi - w_lo) * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,
+                w_hi, ctx->fd, make_jt(ctx), (uint64_t*)bb.nF.p, (uint64_t*)bb.nB.p, (uint32_t*)bb.kh.p, w_lo);
+    return FGPU_OK;
+}
+
+// ... the need bits of the pieces that start in words [w_lo, w_hi).  They read nF / nB up to max_piece_span positions beyond w_hi: the look-up of
+// the words behind has to have been issued.
+int fgpu_stage_scan_need_prewalk(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi) {
+    BatchBufs& bb = *ctx->cur;
+    const bool eager = (ctx->prm.flags & FGPU_FLAG_EAGER_FLAGS) || ctx->eager_runtime || ctx->eager_scan;
+    if (eager || !bb.n_pieces || w_lo >= w_hi) return FGPU_OK;
+    static const int need_tight = getenv("FGPU_NEED_TIGHT") ? atoi(getenv("FGPU_NEED_TIGHT")) : 2;   // measurement aid, see k_need_prewalk
+    // (the host knows the batch's pieces, not the range's: a piece and the gap behind it take k + 1 positions at the least)
+    const uint64_t most = std::min<uint64_t>(bb.n_pieces, (w_hi - w_lo) * 64 / (uint64_t)(ctx->fd.k + 1) + 2);
+    FGPU_LAUNCH("need_prewalk", k_need_prewalk, fgpu_grid(most, 256), 256, (const uint64_t*)bb.codes.p, (const uint2*)bb.pieces.p,
+                (const uint32_t*)bb.ps_prefix.p, w_lo, w_hi, ctx->fd, make_jt(ctx), (const uint64_t*)bb.nF.p, (const uint64_t*)bb.nB.p,
+                (unsigned long long*)bb.need.p, need_tight);
     return FGPU_OK;
 }
 
@@ -2709,13 +2729,13 @@ int fgpu_scan_build_cand(fgpu_ctx* ctx, BatchBufs* b) {
     return FGPU_OK;
 }
 
-int fgpu_stage_scan_debug_drop(fgpu_ctx* ctx) {
+int fgpu_stage_scan_debug_drop(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi) {
     static const int drop = getenv("FGPU_DEBUG_NEED_DROP") ? atoi(getenv("FGPU_DEBUG_NEED_DROP")) : 0;
     BatchBufs& bb = *ctx->cur;
-    if (!drop || !bb.n_pieces) return FGPU_OK;
+    if (!drop || !bb.n_pieces || w_lo >= w_hi) return FGPU_OK;
     // (mode 2 makes the walk meet junction tests that come out true, which may void a LAZY scan; the eager scan that follows has to stand)
     if (drop == 2 && ((ctx->prm.flags & FGPU_FLAG_EAGER_FLAGS) || ctx->eager_runtime || ctx->eager_scan)) return FGPU_OK;
-    FGPU_LAUNCH("debug_need_drop", k_debug_need_drop, fgpu_grid(bb.n_words, 256), 256, bb.n_words, (uint64_t*)bb.ff.p, (uint64_t*)bb.fb.p,
+    FGPU_LAUNCH("debug_need_drop", k_debug_need_drop, fgpu_grid(w_hi - w_lo, 256), 256, w_lo, w_hi, (uint64_t*)bb.ff.p, (uint64_t*)bb.fb.p,
                 (uint64_t*)bb.need.p, (uint64_t*)bb.cf0.p, (uint64_t*)bb.cf1.p, (uint64_t*)bb.cb0.p, (uint64_t*)bb.cb1.p, drop,
                 (const uint64_t*)bb.pm.p, (const uint32_t*)bb.kh.p);
     return FGPU_OK;
@@ -2745,6 +2765,7 @@ struct WalkKnobs {
     const bool dbg_span = getenv("FGPU_DEBUG_SPAN") != nullptr;         // every look of the window-size controller on stderr
 };
 static const WalkKnobs& walk_knobs() { static const WalkKnobs knobs; return knobs; }
+bool fgpu_walk_no_overlap() { return walk_knobs().no_overlap; }
 
 // what every window of a batch's walk works with
 struct WalkBatch {
@@ -2831,11 +2852,27 @@ static int walk_refresh_prepared(fgpu_ctx* ctx, BatchBufs& bb, const JTable& jt,
                             bb.seq, 0);
 }
 
-// The window's turn on the walk stream: its parity's arrays have been reset since the window before last used them, and the window table gets
-// its epoch -- entries carry the window's, everything older counts as empty (the table is wiped once every 255 windows).
+// What a window reads of the pure stage's planes lies below pos_end: it waits for the range that holds pos_end - 1, not for the batch.  The
+// ranges complete in order on the main stream and the windows move forward, so a range at or below the last one waited for needs no new wait.
+// (Every range event of the batch was recorded before this stage was issued.  Where the batch has more ranges than events the slot of range r
+// has been recorded again by later ranges, and the wait is for the last of them: later than need be, never earlier.)
+static int walk_wait_range(fgpu_ctx* ctx, const WalkBatch& wb, uint64_t pos_end) {
+    BatchBufs& bb = wb.bb;
+    if (bb.n_ranges <= 1) return FGPU_OK;      // (one range: the stage has waited for pure_done)
+    const uint64_t last = pos_end - 1;
+    const uint64_t r = last < bb.range_first ? 0 : std::min<uint64_t>(1 + (last - bb.range_first) / bb.range_span, bb.n_ranges - 1);
+    if (r < bb.ranges_waited) return FGPU_OK;
+    FGPU_HIP(hipStreamWaitEvent(wb.walk_stream, bb.range_ev[r % FGPU_RANGE_EVENTS], 0));
+    bb.ranges_waited = r + 1;
+    return FGPU_OK;
+}
+
+// The window's turn on the walk stream: the planes it reads are complete, its parity's arrays have been reset since the window before last used
+// them, and the window table gets its epoch -- entries carry the window's, everything older counts as empty (the table is wiped once every 255 windows).
 static int walk_window_begin(fgpu_ctx* ctx, const WalkBatch& wb, uint64_t lo, uint64_t hi, WalkWindow* w) {
     const int parity = (int)(ctx->scan_windows & 1);
     const uint64_t set = parity * (uint64_t)ctx->wmax;
+    if (int rc = walk_wait_range(ctx, wb, std::min<uint64_t>(wb.T, hi + wb.ext))) return rc;
     FGPU_HIP(hipStreamWaitEvent(wb.walk_stream, ctx->ev_uf_reset[parity], 0));
     if (++ctx->wt_epoch > 255) {
         FGPU_HIP(hipMemsetAsync(ctx->wkeys, 0, ctx->wcap * 8, wb.walk_stream));
@@ -3211,7 +3248,8 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
         ctx->err = "a read of " + std::to_string(ext) + " bases is longer than the junction creation stamps allow (2^19 windows)";
         return FGPU_ERR_CAPACITY;
     }
-    // the whole stage goes to the walk stream, behind the completion of this batch's pure stage; the optimistic rounds to a stream of their own
+    // the whole stage goes to the walk stream, every window behind the ranges of this batch's pure stage that it reads (a batch of one range: the
+    // stage behind the batch's pure stage); the optimistic rounds to a stream of their own
     hipStream_t walk_stream = kn.no_overlap ? ctx->stream : ctx->wstream;
     hipStream_t ovw_stream = (kn.ovw_beside && !kn.no_overlap && ctx->ostream) ? ctx->ostream : walk_stream;
     // the list this batch's created keys go to: the oldest of the ring (its readers -- the windows of the batches in between -- are
@@ -3219,7 +3257,8 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
     WalkBatch wb{bb, pl, make_jt(ctx), bb.T, ext, ctx->scan_piece_base, walk_stream, ovw_stream, false, &ctx->delta_ring[ctx->delta_next % FGPU_DELTA_RING]};
     const uint64_t T = wb.T;
     ctx->launch_stream = walk_stream;
-    if (bb.pure_done) FGPU_HIP(hipStreamWaitEvent(walk_stream, bb.pure_done, 0));
+    bb.ranges_waited = 0;
+    if (bb.n_ranges <= 1 && bb.pure_done) FGPU_HIP(hipStreamWaitEvent(walk_stream, bb.pure_done, 0));
     if (ctx->dbg_stall_us) FGPU_LAUNCH("debug_stall", k_debug_stall, 1, 1, (unsigned long long)ctx->dbg_stall_us * 100ULL);
     if (ctx->refresh_snapshot && (rc = walk_refresh_prepared(ctx, bb, wb.jt, walk_stream, &wb.cand_ok))) return rc;
     if (ctx->record_stops) {

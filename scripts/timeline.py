@@ -1,5 +1,6 @@
 """Timeline of one step from a rocprofv3 kernel trace (CSV): per HIP stream (queue) busy time, how much of it overlaps with the other streams, and
-the gaps of the whole device -- where pass 2's wall time goes beyond its kernels.
+the gaps of the whole device -- where pass 2's wall time goes beyond its kernels; and, per batch of pass 2, how the batch's walk lies against its
+own pure stage (first walk dispatch - end of the last junction-test dispatch: negative when the walk starts before the tests are done).
   python scripts/timeline.py <kernel_trace.csv> [step_index_from_the_end=1]"""
 import csv
 import re
@@ -55,6 +56,35 @@ for name, part in (("pass 1", step[:split + 1]), ("pass 2", step[split + 1:])):
         span = (max(r[1] for r in rs) - min(r[0] for r in rs)) / 1e6
         top = ", ".join(f"{n} {ms:.1f}" for n, ms in sorted(kt.items(), key=lambda kv: -kv[1])[:7])
         print(f"   stream {q}: {len(rs)} dispatches, busy {sum(r[1] - r[0] for r in rs) / 1e6:.2f} ms over a span of {span:.2f} ms (first at {(min(r[0] for r in rs) - a) / 1e6:.2f} ms) | {top}")
+    if name == "pass 2":
+        # batches: the main stream's k_scan_valid opens one; the walk stream clears two buffers (fill kernels) before a batch's first window
+        main = next((r[4] for r in part if r[2] == "k_scan_valid"), None)
+        walk = next((r[4] for r in part if r[2] == "k_walk_register"), None)
+        opens = [r[0] for r in part if r[2] == "k_scan_valid"]
+        flags = [r for r in part if r[2].startswith("k_scan_flags") and r[4] == main]
+        first_walks, armed = [], True
+        for r in part:
+            if r[4] != walk:
+                continue
+            if "fill" in r[2].lower():
+                armed = True
+            elif armed and r[2] == "k_walk_register":
+                first_walks.append(r)
+                armed = False
+        print(f"   batches (main stream {main}, walk stream {walk}): pure stage opens at, junction tests from .. to (dispatches), first walk dispatch at, gap = first walk - last test's end [ms]")
+        batch_flags = []
+        for i, t in enumerate(opens):
+            nxt = opens[i + 1] if i + 1 < len(opens) else None
+            batch_flags.append([r for r in flags if r[0] >= t and (nxt is None or r[0] < nxt)])
+        walked = [fl for fl in batch_flags if fl]      # (a batch without pieces has neither tests nor a walk)
+        if len(first_walks) != len(walked):             # (another clear on the walk stream -- the window table's wipe, stop planes -- shifts the pairing)
+            print(f"      WARNING: {len(first_walks)} first walk dispatches found for {len(walked)} batches with junction tests: the rows below are paired by index and may be shifted")
+        for i, fl in enumerate(walked):
+            fw = first_walks[i] if i < len(first_walks) else None
+            t_open = max(t for t in opens if t <= fl[0][0])
+            gap = f"{(fw[0] - max(r[1] for r in fl)) / 1e6:8.3f}" if fw else "       ?"
+            print(f"      batch {i:2d}: {(t_open - a) / 1e6:8.3f}  {(fl[0][0] - a) / 1e6:8.3f} .. {(max(r[1] for r in fl) - a) / 1e6:8.3f} ({len(fl):2d})  "
+                  f"{(fw[0] - a) / 1e6 if fw else -1:8.3f}  {gap}")
     if name == "pass 2" and len(sys.argv) > 3:
         for r in part:
             print(f"      {(r[0] - a) / 1e6:8.3f} {(r[1] - r[0]) / 1e6:7.3f} {r[4]:>4} {r[2]}")
