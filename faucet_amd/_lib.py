@@ -48,6 +48,19 @@ class LoadStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+EST_LEVELS, EST_SHIFT, EST_MIN_BITS, EST_MAX_BITS, EST_DEFAULT_BITS = 4, 4, 8, 34, 30
+
+
+class Estimate(C.Structure):
+    """fgpu_estimate: the counts of a sketch of the reads (pass 0) and what fgpu_estimate_solve makes of them"""
+    _fields_ = [("empty", C.c_uint64 * 4), ("once", C.c_uint64 * 4), ("kmers", C.c_uint64), ("r_bits", C.c_int32), ("level", C.c_int32),
+                ("f0", C.c_double), ("f1", C.c_double)]
+
+    def as_dict(self):
+        return {"empty": [int(x) for x in self.empty], "once": [int(x) for x in self.once], "kmers": int(self.kmers), "r_bits": int(self.r_bits),
+                "level": int(self.level), "f0": float(self.f0), "f1": float(self.f1)}
+
+
 class ScanStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("reads_processed", "unambiguous_reads", "reads_no_errors", "nb_jcheck_kmer", "nb_no_juncs",
                                           "nb_processed", "nb_skipped", "n_junctions", "kmers", "walk_windows", "walk_followers",
@@ -75,6 +88,10 @@ SIGNATURES = {
     "fgpu_bloom_tai": (_u64, [_u64]),
     "fgpu_size_optimal": (None, [_u64, _f32, _P(_i32), _P(_u64), _P(_i32)]),
     "fgpu_size_two_hash": (None, [_u64, _f32, _P(_i32), _P(_u64), _P(_i32)]),
+    "fgpu_estimate_begin": (C.c_int, [_vp, _i32]),
+    "fgpu_estimate_batch": (C.c_int, [_vp, _P(Reads)]),
+    "fgpu_estimate_end": (C.c_int, [_vp, _P(Estimate)]),
+    "fgpu_estimate_solve": (C.c_int, [_P(Estimate)]),
     "fgpu_load_begin": (C.c_int, [_vp, C.c_int]),
     "fgpu_load_batch": (C.c_int, [_vp, _P(Reads)]),
     "fgpu_load_end": (C.c_int, [_vp, _P(LoadStats)]),

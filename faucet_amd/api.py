@@ -50,6 +50,22 @@ def size_two_hash(estimated: int, fp: float):
     return b.value, t.value, h.value
 
 
+def estimate_solve(empty, once, r_bits: int):
+    """(level, F0, f1) from the counts of a sketch of 2^r_bits cells per level (fgpu_estimate_solve: host arithmetic, no device): empty[l] cells of
+    level l never hit, once[l] hit exactly once.  ValueError for r_bits outside 8..34 or counts no sketch gives; FaucetGpuError when even the
+    thinnest level is too full (raise r_bits)."""
+    e = L.Estimate()
+    e.empty[:] = [int(x) for x in empty]
+    e.once[:] = [int(x) for x in once]
+    e.r_bits = int(r_bits)
+    rc = L.load().fgpu_estimate_solve(C.byref(e))
+    if rc == L.ERR_CAPACITY:
+        raise FaucetGpuError(f"libfaucet_gpu error {rc}: the sketch is too full even at its thinnest level: raise r_bits")
+    if rc != L.OK:
+        raise ValueError("estimate_solve: r_bits must be in 8..34 and empty[l] + once[l] at most 2^r_bits")
+    return int(e.level), float(e.f0), float(e.f1)
+
+
 def load_filter_shape(estimated_kmers: int, singletons: int, fp: float = 0.04):
     """(tai, n_hash) of bloo1/bloo2 as getBloomFilterFromReads sizes them (src/Faucet.cpp:204-219)."""
     p1 = solve_p1(estimated_kmers, singletons, fp)
@@ -179,6 +195,24 @@ class Context:
 
     def _c(self, rc):
         _check(rc, self.h)
+
+    # pass 0: -estimated_kmers (F0) and -singletons (f1) from a sketch of the reads (faucet_gpu.h, fgpu_estimate_*)
+    def estimate_begin(self, r_bits: int = 0):
+        """a pass of its own over the reads: 2^r_bits cells per level, 2^r_bits bytes of device memory until estimate_end (0 = the default, 30)"""
+        self._c(self.lib.fgpu_estimate_begin(self.h, int(r_bits)))
+
+    def estimate_batch(self, batch: ReadBatch):
+        s = batch.c_struct()
+        self._c(self.lib.fgpu_estimate_batch(self.h, C.byref(s)))
+
+    def estimate_end(self) -> dict:
+        """{"empty": [4], "once": [4], "kmers", "r_bits", "level", "f0", "f1"}; the pass is over and its memory free whatever happens.  A sketch
+        too full to solve raises (raise r_bits) with the counts left in self.last_estimate."""
+        e = L.Estimate()
+        rc = self.lib.fgpu_estimate_end(self.h, C.byref(e))
+        self.last_estimate = e.as_dict() if rc in (L.OK, L.ERR_CAPACITY) else None
+        self._c(rc)
+        return self.last_estimate
 
     # pass 1
     def load_begin(self, keep_carry=False, shard_times=False, shard_planes=False):

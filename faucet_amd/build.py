@@ -18,7 +18,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfaucet_gpu.so")
 CLI = os.path.join(HERE, "faucet")
-HIP_SOURCES = ["api.hip", "pack.hip", "load.hip", "load_slices.hip", "scan_pure.hip", "scan_walk.hip", "scan_table.hip", "scan_harvest.hip", "diag.hip", "text.hip", "stage3.hip", "pairs.hip", "group.hip"]
+HIP_SOURCES = ["api.hip", "pack.hip", "load.hip", "load_slices.hip", "estimate.hip", "scan_pure.hip", "scan_walk.hip", "scan_table.hip", "scan_harvest.hip", "diag.hip", "text.hip", "stage3.hip", "pairs.hip", "group.hip"]
 CPP_SOURCES = ["sizing.cpp"]
 HEADERS = ["fgpu_ctx.h", "fgpu_device.h", "fgpu_flags.h", "load_common.h", "walk_tables.h", os.path.join(ROOT, "include", "faucet_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -299,6 +299,7 @@ int fgpu_create(const fgpu_params* p, fgpu_ctx** out) {
         fgpu_touch_pack();
         fgpu_touch_load();
         fgpu_touch_load_slices();
+        fgpu_touch_estimate();
         (void)fgpu_text_streams(ctx);
         (void)hipGetLastError();
     });
@@ -425,7 +426,7 @@ void fgpu_destroy(fgpu_ctx* ctx) {
     for (DevBuf* b : ctx->owned) if (b->p) hipFree(b->p);
     if (ctx->lp.flips_host) hipHostFree(ctx->lp.flips_host);
     if (ctx->lp.ev_open) hipEventDestroy(ctx->lp.ev_open);
-    void* ptrs[] = {ctx->lp.bits, ctx->lp.first, ctx->short_pf, ctx->bloo1, ctx->bloo2, ctx->first, ctx->pair, ctx->rec, ctx->slice_first, ctx->slice_pair, ctx->jkeys, ctx->jrecs, ctx->jstamps, ctx->jfilter, ctx->wkeys,
+    void* ptrs[] = {ctx->lp.bits, ctx->lp.first, ctx->short_pf, ctx->bloo1, ctx->bloo2, ctx->first, ctx->pair, ctx->rec, ctx->slice_first, ctx->slice_pair, ctx->est_planes, ctx->jkeys, ctx->jrecs, ctx->jstamps, ctx->jfilter, ctx->wkeys,
                     ctx->wbits, ctx->uf_parent, ctx->cl_count, ctx->cl_offset, ctx->cl_fill, ctx->cl_fail, ctx->ko_hk, ctx->ko_occ, ctx->ko_piece, ctx->cl_members, ctx->cl_roots, ctx->counters,
                     ctx->wdesc};
     for (void* p : ptrs) if (p) hipFree(p);

@@ -1,0 +1,160 @@
+// estimate.hip — pass 0: a sketch of the read set that gives -estimated_kmers (F0, distinct canonical k-mers) and -singletons (f1, those
+// seen exactly once), the two numbers every run sizes its filters from (src/Faucet.cpp:197-219) and the reference asks a separate tool for.
+//
+// A valid window (the occurrences of the loop at utils/Bloom.cpp:289: fd_window_ok on the packed stream) is hashed once, h = fd_mix(canon) --
+// a bijection, so no two k-mers share an h -- and lands in level min(clz64(h) / 4, 3), cell h & (m - 1), m = 2^r_bits cells per level:
+// levels >= l together hold the k-mers whose h has at least 4 l leading zeros, a 16^-l sample of the k-mer space.  A cell has two bits,
+// `seen` (hit at least once) and `twice` (hit at least twice, by the same or by different k-mers), both in one 32-bit word as the {bloo1,
+// bloo2} pair of load.hip keeps its two filters: 16 cells per word, `seen` in the low half, `twice` in the high half at the same place.
+// The planes a pass ends with are a function of the multiset of occurrences alone -- not of order, grid, batching or races -- so the counts
+// (cells without `seen`, cells with `seen` and not `twice`, per level) can be checked on the CPU to the last counter.  The arithmetic that
+// turns the counts into F0 and f1 is host code: fgpu_estimate_solve, sizing.cpp.
+#include <string>
+
+#include "fgpu_ctx.h"
+
+namespace {
+
+constexpr int EST_LEVELS = FGPU_EST_LEVELS, EST_SHIFT = FGPU_EST_SHIFT;
+
+// One occurrence per stream position, on the striding grid of the other per-position kernels.  An occurrence ORs `seen`; if the word it gets
+// back had `seen` already it was not the first and ORs `twice`.  The plain test in front spares the atomics of settled cells: a stale 0 only
+// costs a redundant atomic, a 1 is never stale because bits are never cleared (fd_bloom_set).  Whoever sees `seen` set -- by the load or by
+// the atomic's answer -- is not the cell's first occurrence, and exactly one atomic per hit cell is answered without `seen`: `twice` ends up
+// set iff the cell was hit at least twice.
+__global__ void __launch_bounds__(256) k_est_sketch(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ bad, uint64_t T, uint64_t n_words,
+                                                    int k, uint32_t* planes, int r_bits, unsigned long long* kmers) {
+    unsigned long long n_ok = 0;
+    const uint64_t total = n_words * 64, cell_mask = (1ULL << r_bits) - 1;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (uint64_t)gridDim.x * blockDim.x) {
+        if (!(p < T && fd_window_ok(bad, p, k))) continue;
+        n_ok++;
+        const uint64_t h = fd_mix(fd_canon(fd_kmer_at(codes, p, k), k));
+        const int lz = h ? __clzll((long long)h) : 64;
+        const uint64_t level = (uint64_t)min(lz / EST_SHIFT, EST_LEVELS - 1);
+        const uint64_t cell = h & cell_mask;
+        uint32_t* word = planes + ((level << (r_bits - 4)) + (cell >> 4));
+        const uint32_t seen = 1u << (cell & 15), twice = seen << 16;
+        uint32_t w = *word;
+        if (w & twice) continue;
+        if (!(w & seen)) {
+            w = atomicOr(word, seen);
+            if (!(w & seen)) continue;      // the cell's first occurrence
+        }
+        if (!(w & twice)) atomicOr(word, twice);
+    }
+    block_add(kmers, n_ok);
+}
+
+// empty[l] = cells of level l without `seen`, once[l] = cells with `seen` and not `twice`: the planes streamed 64 cells (16 bytes) per lane
+// and step, level by level; out = {empty[4], once[4]}
+__global__ void __launch_bounds__(256) k_est_count(const uint4* __restrict__ planes, int r_bits, unsigned long long* out) {
+    const uint64_t per_level = 1ULL << (r_bits - 6), stride = (uint64_t)gridDim.x * blockDim.x;
+    for (int l = 0; l < EST_LEVELS; l++) {
+        const uint4* lv = planes + (uint64_t)l * per_level;
+        unsigned long long n_empty = 0, n_once = 0;
+        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_level; i += stride) {
+            const uint4 v = lv[i];
+            n_empty += 64 - (__popc(v.x & 0xFFFFu) + __popc(v.y & 0xFFFFu) + __popc(v.z & 0xFFFFu) + __popc(v.w & 0xFFFFu));
+            n_once += __popc(v.x & ~(v.x >> 16) & 0xFFFFu) + __popc(v.y & ~(v.y >> 16) & 0xFFFFu) + __popc(v.z & ~(v.z >> 16) & 0xFFFFu) +
+                      __popc(v.w & ~(v.w >> 16) & 0xFFFFu);
+        }
+        block_add(&out[l], n_empty);
+        block_add(&out[EST_LEVELS + l], n_once);
+    }
+}
+
+}  // namespace
+
+// (see fgpu_touch_load)
+void fgpu_touch_estimate() {
+    hipFuncAttributes attr;
+    (void)hipFuncGetAttributes(&attr, (const void*)k_est_sketch);
+}
+
+static_assert(EST_LEVELS == 4 && EST_SHIFT == 4, "fgpu_estimate holds four levels of a 16^-l sample each");
+
+extern "C" {
+
+int fgpu_estimate_begin(fgpu_ctx* ctx, int32_t r_bits) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (r_bits == 0) r_bits = FGPU_EST_DEFAULT_BITS;
+    if (r_bits < FGPU_EST_MIN_BITS || r_bits > FGPU_EST_MAX_BITS) { ctx->err = "estimate_begin: r_bits must be 0 (the default, 30) or in 8..34"; return FGPU_ERR_ARG; }
+    if (ctx->phase != 0) { ctx->err = "estimate_begin while another pass is open"; return FGPU_ERR_STATE; }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    // 2 bits x 4 levels x 2^r_bits cells = 2^r_bits bytes, for the duration of the pass
+    const uint64_t bytes = 1ULL << r_bits;
+    hipError_t e = hipMalloc(&ctx->est_planes, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->est_planes = nullptr;
+        ctx->err = std::string("hipMalloc of the estimate planes (") + std::to_string(bytes) + " bytes) failed: " + hipGetErrorString(e) + ": lower r_bits";
+        return FGPU_ERR_NOMEM;
+    }
+    int rc = fgpu_ensure(ctx, &ctx->est_counts, (2 * EST_LEVELS + 1) * 8);
+    if (!rc && hipMemsetAsync(ctx->est_planes, 0, bytes, ctx->stream) != hipSuccess) { ctx->err = "estimate_begin: clearing the planes failed"; rc = FGPU_ERR_HIP; }
+    if (!rc && hipMemsetAsync(ctx->est_counts.p, 0, (2 * EST_LEVELS + 1) * 8, ctx->stream) != hipSuccess) { ctx->err = "estimate_begin: clearing the counts failed"; rc = FGPU_ERR_HIP; }
+    // (the packing kernels report a wrong fgpu_reads.total_bases through the context's error flags: read at the end of the pass)
+    if (!rc && hipMemsetAsync(&ctx->counters->error_flags, 0, 8, ctx->stream) != hipSuccess) { ctx->err = "estimate_begin: clearing the error flags failed"; rc = FGPU_ERR_HIP; }
+    if (rc) {
+        (void)hipFree(ctx->est_planes);
+        ctx->est_planes = nullptr;
+        return rc;
+    }
+    ctx->est_r_bits = r_bits;
+    ctx->phase = 4;
+    return FGPU_OK;
+}
+
+int fgpu_estimate_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 4) { ctx->err = "estimate_batch outside estimate_begin/estimate_end"; return FGPU_ERR_STATE; }
+    int rc = fgpu_check_reads(ctx, reads);
+    if (rc) return rc;
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    if ((rc = fgpu_stage_pack(ctx, reads))) return rc;
+    const BatchBufs& bb = *ctx->cur;
+    if (bb.T)
+        FGPU_LAUNCH("est_sketch", k_est_sketch, fgpu_grid(bb.n_words * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p, bb.T,
+                    bb.n_words, ctx->fd.k, ctx->est_planes, ctx->est_r_bits, (unsigned long long*)ctx->est_counts.p + 2 * EST_LEVELS);
+    return fgpu_host_batch_done(ctx, reads);
+}
+
+// the counts of the open pass into *out (host), behind everything the pass has queued
+static int estimate_counts(fgpu_ctx* ctx, fgpu_estimate* out) {
+    unsigned long long* d = (unsigned long long*)ctx->est_counts.p;
+    FGPU_LAUNCH("est_count", k_est_count, fgpu_grid(1ULL << (ctx->est_r_bits - 6), 256), 256, (const uint4*)ctx->est_planes, ctx->est_r_bits, d);
+    unsigned long long h[2 * EST_LEVELS + 1];
+    FGPU_HIP(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = fgpu_pull_counters(ctx)) return rc;      // waits for the stream; a batch's total_bases that did not match its offsets
+    for (int l = 0; l < EST_LEVELS; l++) {
+        out->empty[l] = h[l];
+        out->once[l] = h[EST_LEVELS + l];
+    }
+    out->kmers = h[2 * EST_LEVELS];
+    return FGPU_OK;
+}
+
+int fgpu_estimate_end(fgpu_ctx* ctx, fgpu_estimate* out) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 4) { ctx->err = "estimate_end without estimate_begin"; return FGPU_ERR_STATE; }
+    (void)hipSetDevice(ctx->prm.device);
+    fgpu_estimate e;
+    memset(&e, 0, sizeof(e));
+    e.r_bits = ctx->est_r_bits;
+    e.level = -1;
+    int rc = estimate_counts(ctx, &e);
+    // the pass is over either way, and its planes go back
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(ctx->est_planes);
+    ctx->est_planes = nullptr;
+    ctx->phase = 0;
+    if (rc) return rc;
+    rc = fgpu_estimate_solve(&e);
+    if (rc == FGPU_ERR_CAPACITY) ctx->err = "estimate_end: the sketch is too full even at its thinnest level (fewer than an eighth of its cells empty): raise r_bits";
+    else if (rc) ctx->err = "estimate_end: counts that no sketch gives (internal error)";
+    if (out) *out = e;
+    return rc;
+}
+
+}  // extern "C"

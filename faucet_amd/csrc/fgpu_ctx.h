@@ -266,7 +266,11 @@ struct fgpu_ctx {
     uint32_t* rec = nullptr;         // the same state as 256-byte records {bloo1 word, bloo2 word, ..., 32 first-set times} (load_common.h, Filt<1>):
     bool rec_layout = false;         // filters of 2^32 bits and more; `pair` and `first` are not used (nor allocated) then
     uint64_t bloom_bytes = 0;
-    int phase = 0;                   // 0 idle, 1 loading, 2 scanning, 3 loading one slice of the filter bits (fgpu_load_slice_*)
+    int phase = 0;                   // 0 idle, 1 loading, 2 scanning, 3 loading one slice of the filter bits (fgpu_load_slice_*), 4 estimating (fgpu_estimate_*)
+    // pass 0 (estimate.hip): the sketch's planes -- {seen, twice} of 16 cells per word, 2^(r_bits - 4) words per level -- held from _begin to _end
+    uint32_t* est_planes = nullptr;
+    int est_r_bits = 0;
+    DevBuf est_counts;               // empty[4], once[4], kmers
     // the filter-sliced pass: own bit positions [slice_lo, slice_lo + slice_n), its working state sized by the slice (load_common.h, Slice)
     uint64_t slice_lo = 0, slice_n = 0;
     uint32_t* slice_first = nullptr; // first-set time per OWN bit, 4 * slice_n bytes
@@ -527,6 +531,7 @@ static inline bool fgpu_overflow_absorbable(const fgpu_ctx* ctx) {
 int fgpu_text_streams(fgpu_ctx* ctx);
 void fgpu_touch_load();
 void fgpu_touch_load_slices();
+void fgpu_touch_estimate();
 void fgpu_touch_pack();
 void fgpu_touch_text();
 void fgpu_touch_scan_pure();

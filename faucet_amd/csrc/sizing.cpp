@@ -6,6 +6,8 @@
 //   create_bloom_filter_2_hash          utils/Bloom.cpp:206-226
 //   Bloom::Bloom(tai_bloom, k)          utils/Bloom.cpp:165-181   (hashSize = (int)log2(size)+1: a power of two doubles)
 //   set_number_of_hash_func             utils/Bloom.cpp:491-498   (values outside 1..10 keep the default 4)
+// fgpu_estimate_solve has no counterpart there: the reference is handed -estimated_kmers and -singletons; here they can come from a sketch of the
+// reads (estimate.hip), and the arithmetic that turns the sketch's counts into the two numbers is this file's.
 // The false-positive rate is a float in the reference (src/Faucet.h:14) and its logarithm is taken in float.
 #include <cmath>
 #include <cstdint>
@@ -86,6 +88,34 @@ void fgpu_size_two_hash(uint64_t estimated, float fp, int32_t* bits_per_item, ui
     if (bits_per_item) *bits_per_item = bits;
     if (tai) *tai = fgpu_bloom_tai(static_cast<uint64_t>(estimated * static_cast<uint64_t>(bits)));
     if (n_hash) *n_hash = 2;
+}
+
+// F0 and f1 from the counts of a sketch (faucet_gpu.h, pass 0): level l is usable while at least an eighth of its m cells is empty; the estimates
+// are summed over the levels from `level` on -- the lowest from which all are usable -- and scaled by the sample's 16^level.
+int fgpu_estimate_solve(fgpu_estimate* e) {
+    if (!e) return FGPU_ERR_ARG;
+    e->level = -1;
+    e->f0 = e->f1 = 0;
+    if (e->r_bits < FGPU_EST_MIN_BITS || e->r_bits > FGPU_EST_MAX_BITS) return FGPU_ERR_ARG;
+    const uint64_t m = 1ULL << e->r_bits;
+    for (int l = 0; l < FGPU_EST_LEVELS; l++)
+        if (e->empty[l] > m || e->once[l] > m - e->empty[l]) return FGPU_ERR_ARG;
+    auto usable = [&](int l) { return 8 * e->empty[l] >= m; };
+    int level = FGPU_EST_LEVELS - 1;
+    if (!usable(level)) return FGPU_ERR_CAPACITY;      // raise r_bits
+    while (level > 0 && usable(level - 1)) level--;
+    const double md = static_cast<double>(m);
+    double s0 = 0, s1 = 0;
+    for (int l = level; l < FGPU_EST_LEVELS; l++) {
+        const double empty = static_cast<double>(e->empty[l]);
+        s0 += md * std::log(md / empty);
+        s1 += md * static_cast<double>(e->once[l]) / empty;
+    }
+    const double scale = std::pow(2.0, FGPU_EST_SHIFT * level);
+    e->level = level;
+    e->f0 = scale * s0;
+    e->f1 = scale * s1;
+    return FGPU_OK;
 }
 
 }  // extern "C"

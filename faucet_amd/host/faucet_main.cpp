@@ -10,6 +10,8 @@
 // finds no gfx950 device the program fails (there is no CPU path).  What stays on the host is what SURVEY.md 8(b)
 // leaves there: the JunctionMap container that fixes the dump order, and the files.  Both pair filters are filled on the
 // device from scanInputRead's per-read lists (fgpu_scan_short_pairs, fgpu_scan_long_pairs) and come back as bytes.
+// Not in the reference: --estimate.  -estimated_kmers and -singletons, which the reference has its users find with a separate k-mer counter,
+// may then be left out; a pass 0 over -read_load_file sketches the reads on the device (fgpu_estimate_*) and fills in whichever is absent.
 #include <errno.h>
 #include <fcntl.h>
 #include <stdint.h>
@@ -20,6 +22,8 @@
 #include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
+
+#include <math.h>
 
 #include <algorithm>
 #include <chrono>
@@ -38,6 +42,12 @@
 #include "scan_pass.h"
 #include "shard_host.h"
 #include "text_source.h"
+
+// The estimate pass' entry points are referred to WEAKLY, as shard_host.h refers to the sliced pass': linked against an implementation of the ABI
+// without them they are null, and --estimate is refused before anything is read.
+#pragma weak fgpu_estimate_begin
+#pragma weak fgpu_estimate_batch
+#pragma weak fgpu_estimate_end
 
 using faucet_host::ReadSource;
 using faucet_host::TextSource;
@@ -64,6 +74,8 @@ struct Options {   // globals of src/Faucet.h:14-53
     int32_t n_hash = 0;
     int gpus = 1;                     // not a reference flag: read shards over this many GPUs, one host thread each (shard_host.h)
     std::string transport = "copy";   // not a reference flag: how the shards' bitmaps and tables travel: copy (device-to-device copies) | rccl
+    bool estimate = false;            // not a reference flag: --estimate, -estimated_kmers / -singletons may be left out and are then estimated (pass 0)
+    int estimate_bits = 0;            // not a reference flag: -estimate_bits r, 2^r cells per level of the sketch (0: the library's default, 30)
 };
 
 void argument_error() {   // src/Faucet.cpp:50-54
@@ -105,6 +117,8 @@ int handle_arguments(int argc, char** argv, Options& o) {
         else if (a == "-chunk_mb") { if (!val(v)) goto bad; o.chunk_mb = (uint64_t)atoll(v); if (!o.chunk_mb) o.chunk_mb = 1; }
         else if (a == "-gpus") { if (!val(v)) goto bad; o.gpus = atoi(v); if (o.gpus < 1 || o.gpus > 64) { fprintf(stderr, "-gpus must be in 1..64\n"); return 1; } }
         else if (a == "-transport") { if (!val(v)) goto bad; o.transport = v; if (o.transport != "copy" && o.transport != "rccl") { fprintf(stderr, "-transport must be copy or rccl\n"); return 1; } }
+        else if (a == "--estimate") o.estimate = true;
+        else if (a == "-estimate_bits") { if (!val(v)) goto bad; o.estimate_bits = atoi(v); if (o.estimate_bits < FGPU_EST_MIN_BITS || o.estimate_bits > FGPU_EST_MAX_BITS) { fprintf(stderr, "-estimate_bits must be in %d..%d\n", FGPU_EST_MIN_BITS, FGPU_EST_MAX_BITS); return 1; } }
         else if (a == "--help" || a == "-h") { argument_error(); return 1; }
         else { fprintf(stderr, "Cannot parse tag %s\n", argv[i]); argument_error(); return 1; }
         continue;
@@ -113,7 +127,8 @@ int handle_arguments(int argc, char** argv, Options& o) {
         argument_error();
         return 1;
     }
-    if (!(o.load_file_flag && o.scan_file_flag && o.k_val_flag && o.max_len_flag && o.est_kmers_flag && o.est_sing_flag && o.pref_flag)) {
+    // (--estimate: the two counts may be left out, pass 0 fills them in)
+    if (!(o.load_file_flag && o.scan_file_flag && o.k_val_flag && o.max_len_flag && (o.est_kmers_flag || o.estimate) && (o.est_sing_flag || o.estimate) && o.pref_flag)) {
         fprintf(stderr, "Some required argument is missing.\n");
         argument_error();
         return 1;
@@ -123,6 +138,11 @@ int handle_arguments(int argc, char** argv, Options& o) {
         argument_error();
         return 1;
     }
+    return 0;
+}
+
+// ... and the lines it prints once the arguments stand (src/Faucet.cpp:136-181): apart, so that --estimate can fill in the two counts in between
+void print_settings(const Options& o) {
     if (o.from_junctions) printf("Starting from after read scan based on bloom and junction files.\n");
     else if (o.from_bloom) printf("Starting from after bloom load based on bloom file.\n");
     else printf("Starting at the beginning: will load bloom and find junctions from the read set.\n");
@@ -141,7 +161,6 @@ int handle_arguments(int argc, char** argv, Options& o) {
     // src/Faucet.cpp:177-181 prints sizeof(Junction / ContigNode / Contig / int / long) of ITS build: the reference's values on x86-64 Linux,
     // so that what a caller greps or diffs in the log stays where it is
     printf("Size of junction: 14\nSize of contigNode: 48\nSize of contig: 104\nSize of int: 4\nSize of long: 8\n");
-    return 0;
 }
 
 // one interface over both ways of cutting the input into batches: file text split on the device (TextSource), or -batch_reads records
@@ -628,19 +647,84 @@ int load_bloom_file(const Options& o, const Run& run, BloomFile& bloom) {
     return 0;
 }
 
+// ---- the reading loop of every pass on one device: the batches of `src` in file order, each handed to `each` (a status); the time spent in
+// `each` is added to *each_ms, `progress` (or null) is the line rewritten on stdout.  FGPU_OK, or the status that ended it with *failed = who
+template <class Each>
+int feed_batches(fgpu_ctx* ctx, BatchSource& src, const char* progress, double* each_ms, const char** failed, const Each& each) {
+    uint64_t reads = 0;
+    fgpu_reads r;
+    for (int more; (more = src.next(ctx, &r)) != 0;) {
+        if (more < 0) { *failed = "fgpu_text_split"; return -more; }
+        const auto t_batch = std::chrono::steady_clock::now();
+        if (int rc = each(&r)) return rc;
+        *each_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_batch).count();
+        reads += r.n_reads;
+        if (progress) {
+            fprintf(stdout, "\r%s: %lld", progress, (long long)reads);
+            fflush(stdout);
+        }
+    }
+    return FGPU_OK;
+}
+
+// ---- pass 0 (--estimate): whichever of -estimated_kmers / -singletons the command line left out, from a sketch of -read_load_file on the first
+// device.  The sizes of the run's context follow from these numbers, so the pass has a placeholder context of its own (tai = 128, one hash
+// function: the pass reads neither), destroyed before the run's contexts are made.  0, or the exit code of a failure
+int estimate_missing(Options& o, PhaseClock& clk) {
+    // decided before any device call: the file is read once more by pass 1, and the library has to have the pass
+    struct stat st;
+    if (stat(o.read_load_file.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) {
+        fprintf(stderr, "--estimate: %s is not a regular file: pass 0 reads -read_load_file once more than the run does (give -estimated_kmers and -singletons for a pipe)\n",
+                o.read_load_file.c_str());
+        return 1;
+    }
+    if (!fgpu_estimate_begin || !fgpu_estimate_batch || !fgpu_estimate_end) {
+        fprintf(stderr, "--estimate: the library this program is linked against lacks the entry points of the estimate pass "
+                        "(fgpu_estimate_begin, fgpu_estimate_batch, fgpu_estimate_end)\n");
+        return 2;
+    }
+    fgpu_params prm;
+    memset(&prm, 0, sizeof(prm));
+    prm.k = o.k;
+    prm.j = 1;
+    prm.max_spacer_dist = 100;
+    prm.n_hash = 1;
+    prm.tai = 128;
+    Run placeholder;
+    if (int rc = open_one_device(o, prm, &placeholder)) return rc;
+    fgpu_ctx* ctx = placeholder.one;
+    clk.mark("arguments, placeholder context");
+    BatchSource src(o, o.read_load_file);
+    if (!src.is_open()) { fprintf(stderr, "cannot open %s\n", o.read_load_file.c_str()); return 2; }
+    CHECK(fgpu_estimate_begin(ctx, o.estimate_bits));
+    double batch_ms = 0;
+    const char* failed = "fgpu_estimate_batch";
+    if (int rc = feed_batches(ctx, src, nullptr, &batch_ms, &failed, [&](const fgpu_reads* r) { return fgpu_estimate_batch(ctx, r); })) {
+        fprintf(stderr, "%s failed (%d): %s\n", failed, rc, fgpu_last_error(ctx));
+        return 2;
+    }
+    fgpu_estimate est;
+    const int rc = fgpu_estimate_end(ctx, &est);
+    if (rc == FGPU_ERR_CAPACITY) { fprintf(stderr, "--estimate: the sketch of 2^%d cells per level is too full for these reads: raise -estimate_bits\n", (int)est.r_bits); return 2; }
+    if (rc != FGPU_OK) { fprintf(stderr, "fgpu_estimate_end failed (%d): %s\n", rc, fgpu_last_error(ctx)); return 2; }
+    if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_estimate_batch calls; %llu k-mers sketched, 2^%d cells per level, estimates from level %d on\n", batch_ms,
+                        (unsigned long long)est.kmers, (int)est.r_bits, (int)est.level);
+    clk.mark("pass 0 (read + estimate)");
+    const long long f0 = llround(est.f0), f1 = std::max(llround(est.f1), 1LL);
+    printf("Estimated distinct k-mers (F0): %lld\n", f0);
+    printf("Estimated singletons (f1): %lld\n", f1);
+    if (!o.est_kmers_flag) o.estimated_kmers = (uint64_t)f0;
+    if (!o.est_sing_flag) o.singletons = (uint64_t)f1;
+    return 0;
+}
+
 // (both ways of pass 1 answer with a ShardLoadResult: the run's counters and the weights of bloo1 / bloo2)
 int load_one_device(fgpu_ctx* ctx, BatchSource& src, PhaseClock& clk, faucet_host::ShardLoadResult* out) {
     CHECK(fgpu_load_begin(ctx, 0));
-    uint64_t consumed = 0;
-    fgpu_reads r;
-    for (int more; (more = src.next(ctx, &r)) != 0;) {
-        if (more < 0) { fprintf(stderr, "fgpu_text_split failed (%d): %s\n", -more, fgpu_last_error(ctx)); return 2; }
-        const auto t_batch = std::chrono::steady_clock::now();
-        CHECK(fgpu_load_batch(ctx, &r));
-        clk.batch_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_batch).count();
-        consumed += r.n_reads;
-        fprintf(stdout, "\rreads consumed: %lld", (long long)consumed);
-        fflush(stdout);
+    const char* failed = "fgpu_load_batch";
+    if (int rc = feed_batches(ctx, src, "reads consumed", &clk.batch_ms, &failed, [&](const fgpu_reads* r) { return fgpu_load_batch(ctx, r); })) {
+        fprintf(stderr, "%s failed (%d): %s\n", failed, rc, fgpu_last_error(ctx));
+        return 2;
     }
     const auto t_end = std::chrono::steady_clock::now();
     CHECK(fgpu_load_end(ctx, &out->stats));
@@ -740,21 +824,11 @@ int scan_one_device(const Options& o, fgpu_ctx* ctx, PairFilter& short_pf, PairF
     if (!src.is_open()) { fprintf(stderr, "cannot open %s\n", o.read_scan_file.c_str()); return 2; }
     const faucet_host::PairTarget none = {nullptr, 0, 0};
     const faucet_host::PairTarget short_target = {short_pf.bits.data(), short_pf.tai, short_pf.n_hash}, long_target = {long_pf.bits.data(), long_pf.tai, long_pf.n_hash};
-    uint64_t scanned = 0;
     const auto t_pass = std::chrono::steady_clock::now();
     auto t_fed = t_pass;
     const int rc = faucet_host::scan_pass(ctx, o.k, o.no_cleaning ? none : short_target, o.no_cleaning || !o.paired_ends ? none : long_target, o.paired_ends,
         [&](const faucet_host::EachBatch& each) -> int {
-            fgpu_reads r;
-            for (int more; (more = src.next(ctx, &r)) != 0;) {
-                if (more < 0) { res->failed = "fgpu_text_split"; return -more; }
-                const auto t_scan = std::chrono::steady_clock::now();
-                if (int brc = each(&r)) return brc;
-                clk.scan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_scan).count();
-                scanned += r.n_reads;
-                fprintf(stdout, "\rreads scanned: %lld", (long long)scanned);
-                fflush(stdout);
-            }
+            if (int frc = feed_batches(ctx, src, "reads scanned", &clk.scan_ms, &res->failed, each)) return frc;
             t_fed = std::chrono::steady_clock::now();
             return FGPU_OK;
         }, res);
@@ -807,6 +881,12 @@ int main(int argc, char** argv) {
     PhaseClock clk;
     Options o;
     if (handle_arguments(argc, argv, o) == 1) return 1;
+    if (o.estimate && !(o.est_kmers_flag && o.est_sing_flag)) {     // pass 0, ahead of everything the two numbers decide (and of the lines that print them)
+        if (o.k < 1 || o.k > 31) { fprintf(stderr, "k must be in 1..31 on this build\n"); return 1; }
+        choose_chunk_bytes(o);
+        if (int rc = estimate_missing(o, clk)) return rc;
+    }
+    print_settings(o);
     if (o.k < 1 || o.k > 31) { fprintf(stderr, "k must be in 1..31 on this build\n"); return 1; }
     if (int rc = size_filters(o)) return rc;
     const fgpu_params prm = context_params(o);

@@ -163,6 +163,47 @@ uint64_t fgpu_bloom_tai(uint64_t requested_bits);                               
 void     fgpu_size_optimal(uint64_t estimated, float fp, int32_t* bits_per_item, uint64_t* tai, int32_t* n_hash);
 void     fgpu_size_two_hash(uint64_t estimated, float fp, int32_t* bits_per_item, uint64_t* tai, int32_t* n_hash);
 
+/* ---- pass 0: the two numbers the sizing above starts from, counted on the device ------------------------
+ * Every run needs -estimated_kmers (F0: distinct canonical k-mers of the read set) and -singletons (f1: those seen exactly once); the reference
+ * sizes its filters from nothing else (src/Faucet.cpp:197-219) and leaves it to a separate k-mer counter to find them.  This pass sketches the
+ * reads instead.  Every valid window -- the occurrences of the loop at utils/Bloom.cpp:289, fgpu_load_stats.kmers of them -- is hashed once with
+ * a 64-bit bijection, h; it falls into level min(clz64(h) / FGPU_EST_SHIFT, FGPU_EST_LEVELS - 1) (clz64(0) = 64) and there into cell
+ * h & (m - 1) of m = 2^r_bits: levels >= l together hold a 16^-l sample of the k-mer space.  A cell knows whether it was hit at least once and
+ * whether at least twice (by the same or by different k-mers): 2 bits x 4 levels x m cells = 2^r_bits bytes of device memory between _begin
+ * and _end (r_bits 8..34; the default, 30, is 1 GiB).  What comes back per level: empty[l], the cells never hit, and once[l], the cells hit
+ * exactly once -- functions of the multiset of occurrences alone, whatever the batching.
+ * The solve (host arithmetic in doubles): level l is usable iff 8 * empty[l] >= m (a load of at most ln 8); level = the smallest l such that
+ * levels l..3 are all usable; with n distinct keys thrown into m cells a cell stays empty with probability e^-(n/m) and holds exactly one
+ * occurrence with probability (n/m) e^-(n/m) x (the singletons' share), hence
+ *     f0 = 16^level * sum over l >= level of m * ln(m / empty[l])          f1 = 16^level * sum over l >= level of m * once[l] / empty[l]
+ * At level 0 nothing is sampled: only the collision correction is left.  Level 3 not usable: FGPU_ERR_CAPACITY ("raise r_bits"), level = -1.
+ * The pass reads k, the device and max_batch_bases of the context, never tai or n_hash: a caller that does not know its sizes yet creates a
+ * context with tai = 128, n_hash = 1 for it, and destroys that context before it makes the real one (two contexts would hold their working
+ * buffers side by side). */
+#define FGPU_EST_LEVELS 4
+#define FGPU_EST_SHIFT 4
+#define FGPU_EST_MIN_BITS 8
+#define FGPU_EST_MAX_BITS 34
+#define FGPU_EST_DEFAULT_BITS 30
+typedef struct {
+    uint64_t empty[FGPU_EST_LEVELS];   /* cells of the level that no occurrence hit */
+    uint64_t once[FGPU_EST_LEVELS];    /* cells of the level that exactly one occurrence hit */
+    uint64_t kmers;                    /* occurrences sketched: fgpu_load_stats.kmers of a load of the same reads */
+    int32_t  r_bits;                   /* m = 2^r_bits cells per level */
+    int32_t  level;                    /* the level the estimates start from; -1: none */
+    double   f0, f1;
+} fgpu_estimate;
+/* r_bits = 0: the default.  A pass of its own: FGPU_ERR_STATE inside a load or scan pass (and their _begin inside this one); FGPU_ERR_ARG for
+ * other r_bits; FGPU_ERR_NOMEM when the planes cannot be had. */
+int fgpu_estimate_begin(fgpu_ctx* ctx, int32_t r_bits);
+/* One batch, in any order: host, device and fgpu_text_split batches alike (packed as fgpu_load_batch packs them). */
+int fgpu_estimate_batch(fgpu_ctx* ctx, const fgpu_reads* reads);
+/* Counts, solves, frees the planes and ends the pass whatever it returns; out may be NULL.  FGPU_ERR_CAPACITY leaves the counts filled in. */
+int fgpu_estimate_end(fgpu_ctx* ctx, fgpu_estimate* out);
+/* Host only, no device: level, f0, f1 from empty / once / r_bits.  FGPU_ERR_ARG: r_bits outside 8..34, or counts no sketch of m cells gives
+ * (empty[l] + once[l] > m). */
+int fgpu_estimate_solve(fgpu_estimate* e);
+
 /* ---- pass 1: Bloom load (replaces load_two_filters, utils/Bloom.cpp:267-350) ------------------- */
 /* Zero both filters (or keep bloo1's current content as the carried-in state when keep_carry != 0:
  * multi-GPU shards start from the prefix-OR of the lower ranks' k-mer presence bitmaps). */
