@@ -390,7 +390,24 @@ class Context:
             recs = np.zeros(cap, dtype=JUNC_DTYPE)
         got = C.c_uint64()
         self._c(self.lib.fgpu_scan_download_junctions(self.h, keys.ctypes.data, recs.ctypes.data, len(keys), C.byref(got)))
+        self._n_downloaded = int(got.value)
         return keys[: got.value], recs[: got.value]
+
+    def scan_dump_order(self, counts, buckets, n=None) -> np.ndarray:
+        """The reference's dump order of the first n junctions of the last junctions() call (default: all of them), computed on the device
+        from the caller's rehash schedule: counts[j] nodes are present when the container goes to buckets[j] buckets, first entry
+        (0, buckets of the empty container).  order[i] = index in creation order of the i-th junction dumped (faucet_gpu.h,
+        fgpu_scan_dump_order)."""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        buckets = np.ascontiguousarray(buckets, dtype=np.uint64)
+        if counts.ndim != 1 or counts.shape != buckets.shape:
+            raise ValueError("scan_dump_order: counts and buckets are two lists of the same length")
+        n = getattr(self, "_n_downloaded", 0) if n is None else int(n)
+        order = np.zeros(max(n, 1), dtype=np.uint32)
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        self._c(self.lib.fgpu_scan_dump_order(self.h, counts.ctypes.data_as(u64p), buckets.ctypes.data_as(u64p), len(counts), n,
+                                              order.ctypes.data_as(u32p)))
+        return order[:n]
 
     def table_entries(self) -> int:
         n = C.c_uint64()

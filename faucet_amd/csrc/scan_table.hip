@@ -272,7 +272,19 @@ int fgpu_scan_reserve(fgpu_ctx* ctx, uint64_t records) {
 // order_host[i] = index (in creation order) of the i-th junction of the reference's dump; d_keys: the junction keys in creation order on the device
 int fgpu_scan_dump_order_impl(fgpu_ctx* ctx, const uint64_t* d_keys, const uint64_t* counts, const uint64_t* buckets, uint64_t n_phases, uint64_t n,
                               uint32_t* order_host) {
+    // The whole schedule is checked here, on the host, before anything is allocated, set or launched: the first stretch reads list[t] for
+    // t < counts[0] from a list no stretch has written yet, later ones from what the stretch before sorted (counts[j] <= counts[j + 1] entries),
+    // and a bucket number is kept in 32 bits.
+    bool any = false;
+    for (uint64_t j = 0; j < n_phases; j++) {
+        const uint64_t c = counts[j], m = j + 1 < n_phases ? counts[j + 1] : n, B = buckets[j];
+        if (j == 0 && c != 0) { ctx->err = "fgpu_scan_dump_order: the schedule starts with the empty container (rehash_counts[0] = 0)"; return FGPU_ERR_ARG; }
+        if (c > m || m > n) { ctx->err = "fgpu_scan_dump_order: rehash counts must not descend and must not exceed n"; return FGPU_ERR_ARG; }
+        if (!B || B > 0xFFFFFFFFULL) { ctx->err = "fgpu_scan_dump_order: bucket counts must be in 1 .. 2^32 - 1"; return FGPU_ERR_ARG; }
+        any = any || m > 0;
+    }
     if (!n) return FGPU_OK;
+    if (!any) { ctx->err = "fgpu_scan_dump_order: empty schedule"; return FGPU_ERR_ARG; }
     uint64_t max_b = 1;
     for (uint64_t j = 0; j < n_phases; j++) max_b = std::max(max_b, buckets[j]);
     DevBuf list_a, list_b, bucket, first, key_a, key_b, tmp;
@@ -291,11 +303,9 @@ int fgpu_scan_dump_order_impl(fgpu_ctx* ctx, const uint64_t* d_keys, const uint6
     if ((rc = alloc(tmp, tmp_bytes + 16))) return rc;
     uint32_t* list = (uint32_t*)list_a.p;      // the list as the last stretch left it
     uint32_t* other = (uint32_t*)list_b.p;
-    bool any = false;
     for (uint64_t j = 0; j < n_phases; j++) {
         const uint64_t c = counts[j], m = j + 1 < n_phases ? counts[j + 1] : n, B = buckets[j];
         if (m == 0) continue;
-        if (c > m || m > n || !B) { ctx->err = "fgpu_scan_dump_order: rehash counts must ascend to n, bucket counts must not be zero"; return FGPU_ERR_ARG; }
         FGPU_HIP(hipMemsetAsync(first.p, 0xFF, B * 4, ctx->stream));
         hipLaunchKernelGGL(k_dump_first, dim3(fgpu_grid(m, 256)), dim3(256), 0, ctx->stream, d_keys, (const uint32_t*)list, c, m, B, (uint32_t*)bucket.p, (uint32_t*)first.p);
         hipLaunchKernelGGL(k_dump_key, dim3(fgpu_grid(m, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)list, c, m, (const uint32_t*)bucket.p, (const uint32_t*)first.p,
@@ -303,9 +313,7 @@ int fgpu_scan_dump_order_impl(fgpu_ctx* ctx, const uint64_t* d_keys, const uint6
         // (`other` holds the nodes in sequence order now; sorted into `list`)
         size_t tb = tmp_bytes;
         FGPU_HIP(rocprim::radix_sort_pairs(tmp.p, tb, (uint64_t*)key_a.p, (uint64_t*)key_b.p, other, list, m, 0, 64, ctx->stream));
-        any = true;
     }
-    if (!any) { ctx->err = "fgpu_scan_dump_order: empty schedule"; return FGPU_ERR_ARG; }
     FGPU_HIP(hipMemcpyAsync(order_host, list, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
     return FGPU_OK;

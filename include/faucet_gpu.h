@@ -479,7 +479,11 @@ int fgpu_scan_table_entries(fgpu_ctx* ctx, uint64_t* n_entries);
  * buckets (DumpOrder::schedule: asked of the library's own policy object): rehash_counts[j] nodes are present when the table goes to
  * rehash_buckets[j] buckets, first entry {0, buckets of the empty container}; the hash of a 64-bit key is the key (libstdc++).  order[i] =
  * index in creation order of the i-th junction dumped, for the first n keys (n <= the downloaded count; a prefix lets a host check the device
- * against its own container before trusting it).  Replaces a host-side replay that took 5.7 s for 2.95e7 junctions. */
+ * against its own container before trusting it).  Replaces a host-side replay that took 5.7 s for 2.95e7 junctions.
+ * Preconditions on the schedule, all checked on the host before anything runs on the device (FGPU_ERR_ARG otherwise): n_rehashes >= 1;
+ * rehash_counts[0] == 0; the counts do not descend (equal counts = several rehashes in a row) and none exceeds n; every bucket count is in
+ * 1 .. 2^32 - 1 (the device keeps a bucket number in 32 bits, and one 4-byte word per bucket of the largest count).  FGPU_ERR_STATE: inside
+ * an open pass, before any download, or n above the downloaded count.  n == 0 (after a download of at least one key) writes nothing. */
 int fgpu_scan_dump_order(fgpu_ctx* ctx, const uint64_t* rehash_counts, const uint64_t* rehash_buckets, uint64_t n_rehashes, uint64_t n, uint32_t* order);
 int fgpu_scan_export_table(fgpu_ctx* ctx, void* dev_buf, uint64_t buf_bytes, uint64_t* n_entries);
 int fgpu_scan_import_table(fgpu_ctx* ctx, const void* dev_buf, uint64_t n_entries, const fgpu_scan_stats* carried);
