@@ -92,6 +92,10 @@ SIGNATURES = {
     "fgpu_estimate_batch": (C.c_int, [_vp, _P(Reads)]),
     "fgpu_estimate_end": (C.c_int, [_vp, _P(Estimate)]),
     "fgpu_estimate_solve": (C.c_int, [_P(Estimate)]),
+    "fgpu_estimate_planes": (C.c_int, [_vp, _P(_vp), _P(_u64)]),
+    "fgpu_estimate_merge": (C.c_int, [_vp, _vp, _u64, _u64]),
+    "fgpu_estimate_download": (C.c_int, [_vp, _vp, _u64]),
+    "fgpu_estimate_kmers": (C.c_int, [_vp, _P(_u64)]),
     "fgpu_load_begin": (C.c_int, [_vp, C.c_int]),
     "fgpu_load_batch": (C.c_int, [_vp, _P(Reads)]),
     "fgpu_load_end": (C.c_int, [_vp, _P(LoadStats)]),
@@ -187,6 +191,7 @@ SIGNATURES = {
     "fgpu_group_or_allreduce": (C.c_int, [_vp, C.c_int, _vp, _u64]),
     "fgpu_group_exclusive_prefix_or": (C.c_int, [_vp, C.c_int, _vp, _vp, _u64]),
     "fgpu_group_allgather": (C.c_int, [_vp, C.c_int, _vp, _u64, _P(_u64)]),
+    "fgpu_group_estimate_end": (C.c_int, [_vp, C.c_int, _P(Estimate)]),
     "fgpu_group_send": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _u64]),
     "fgpu_group_send_async": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _u64]),
     "fgpu_group_flush": (C.c_int, [_vp, C.c_int]),

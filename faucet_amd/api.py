@@ -214,6 +214,30 @@ class Context:
         self._c(rc)
         return self.last_estimate
 
+    def estimate_planes_devptr(self):
+        """(device pointer, bytes) of the open pass' planes: 2^r_bits bytes, level l in the l-th quarter, 16 cells per 32-bit word"""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._c(self.lib.fgpu_estimate_planes(self.h, C.byref(p), C.byref(n)))
+        return p.value, int(n.value)
+
+    def estimate_merge(self, peer_dev_ptr, first_byte: int, nbytes: int):
+        """bytes [first_byte, first_byte + nbytes) of another sketch with the same r_bits, held at peer_dev_ptr on this device, merged into the same
+        bytes of this context's planes (saturating addition of the cells; whole 16-byte granules), on the context's stream"""
+        self._c(self.lib.fgpu_estimate_merge(self.h, peer_dev_ptr, int(first_byte), int(nbytes)))
+
+    def estimate_download(self) -> np.ndarray:
+        """the open pass' planes as they stand behind everything queued (uint32 words)"""
+        _, n = self.estimate_planes_devptr()
+        out = np.empty(n // 4, np.uint32)
+        self._c(self.lib.fgpu_estimate_download(self.h, out.ctypes.data, n))
+        return out
+
+    def estimate_kmers(self) -> int:
+        """the occurrences the open pass has sketched so far on this context"""
+        n = C.c_uint64()
+        self._c(self.lib.fgpu_estimate_kmers(self.h, C.byref(n)))
+        return int(n.value)
+
     # pass 1
     def load_begin(self, keep_carry=False, shard_times=False, shard_planes=False):
         self._c(self.lib.fgpu_load_begin(self.h, (L.LOAD_KEEP_CARRY if keep_carry else 0) | (L.LOAD_SHARD_TIMES if shard_times else 0) |
@@ -696,6 +720,15 @@ def group_allgather(group, rank: int, buf_dev_ptr, nbytes: int, bounds) -> int:
     rank holds all of them.  Returns the status (the caller reads fgpu_group_last_error)."""
     arr = (C.c_uint64 * len(bounds))(*[int(b) for b in bounds])
     return L.load().fgpu_group_allgather(group, rank, buf_dev_ptr, nbytes, arr)
+
+
+def group_estimate_end(group, rank: int):
+    """fgpu_group_estimate_end, called by every rank's thread in place of Context.estimate_end: (status, the dict estimate_end gives -- the same on
+    every rank, that of one sketch of all the ranks' reads; None unless the status is OK or ERR_CAPACITY).  The pass is over on every rank whatever
+    the status (the caller reads fgpu_group_last_error)."""
+    e = L.Estimate()
+    rc = L.load().fgpu_group_estimate_end(group, rank, C.byref(e))
+    return rc, (e.as_dict() if rc in (L.OK, L.ERR_CAPACITY) else None)
 
 
 def load_two_filters(bloo1: Bloom, bloo2: Bloom, batches) -> dict:

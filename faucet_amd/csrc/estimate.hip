@@ -8,7 +8,8 @@
 // bloo2} pair of load.hip keeps its two filters: 16 cells per word, `seen` in the low half, `twice` in the high half at the same place.
 // The planes a pass ends with are a function of the multiset of occurrences alone -- not of order, grid, batching or races -- so the counts
 // (cells without `seen`, cells with `seen` and not `twice`, per level) can be checked on the CPU to the last counter.  The arithmetic that
-// turns the counts into F0 and f1 is host code: fgpu_estimate_solve, sizing.cpp.
+// turns the counts into F0 and f1 is host code: fgpu_estimate_solve, sizing.cpp.  For the same reason the sketches of the shards of a read set merge
+// into the sketch of the whole (k_est_merge), which is how pass 0 runs over several GPUs: fgpu_group_estimate_end, group.hip.
 #include <string>
 
 #include "fgpu_ctx.h"
@@ -46,21 +47,38 @@ __global__ void __launch_bounds__(256) k_est_sketch(const uint64_t* __restrict__
     block_add(kmers, n_ok);
 }
 
-// empty[l] = cells of level l without `seen`, once[l] = cells with `seen` and not `twice`: the planes streamed 64 cells (16 bytes) per lane
-// and step, level by level; out = {empty[4], once[4]}
-__global__ void __launch_bounds__(256) k_est_count(const uint4* __restrict__ planes, int r_bits, unsigned long long* out) {
+// empty[l] = cells of level l without `seen`, once[l] = cells with `seen` and not `twice`, over the 16-byte granules [g0, g1) of the planes
+// (a granule is 64 cells of one level: level = granule >> (r_bits - 6), so a range may begin and end inside a level and cross several): the
+// planes streamed one granule per lane and step, level by level; out = {empty[4], once[4]}.  Counts add over disjoint ranges: the whole
+// range gives a sketch's counts, a rank's slice of a merged sketch its share of them (fgpu_group_estimate_end).
+__global__ void __launch_bounds__(256) k_est_count(const uint4* __restrict__ planes, int r_bits, uint64_t g0, uint64_t g1, unsigned long long* out) {
     const uint64_t per_level = 1ULL << (r_bits - 6), stride = (uint64_t)gridDim.x * blockDim.x;
     for (int l = 0; l < EST_LEVELS; l++) {
-        const uint4* lv = planes + (uint64_t)l * per_level;
+        const uint64_t lo = max(g0, (uint64_t)l * per_level), hi = min(g1, (uint64_t)(l + 1) * per_level);
+        if (lo >= hi) continue;           // (uniform over the grid: no level's block_add is entered by a part of a block)
         unsigned long long n_empty = 0, n_once = 0;
-        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_level; i += stride) {
-            const uint4 v = lv[i];
+        for (uint64_t i = lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += stride) {
+            const uint4 v = planes[i];
             n_empty += 64 - (__popc(v.x & 0xFFFFu) + __popc(v.y & 0xFFFFu) + __popc(v.z & 0xFFFFu) + __popc(v.w & 0xFFFFu));
             n_once += __popc(v.x & ~(v.x >> 16) & 0xFFFFu) + __popc(v.y & ~(v.y >> 16) & 0xFFFFu) + __popc(v.z & ~(v.z >> 16) & 0xFFFFu) +
                       __popc(v.w & ~(v.w >> 16) & 0xFFFFu);
         }
         block_add(&out[l], n_empty);
         block_add(&out[EST_LEVELS + l], n_once);
+    }
+}
+
+// A cell is a counter that saturates at 2 (`seen` alone: 1, `seen` and `twice`: 2 or more), and two sketches of the same r_bits merge by
+// saturating addition cell by cell: `seen` and `twice` are ORed, and a cell both sides have seen has been hit twice.  Associative and
+// commutative, so any order of merging the sketches of the shards of a read set gives the planes one sketch of all reads ends with.
+__device__ __forceinline__ uint32_t est_merge_word(uint32_t a, uint32_t b) { return a | b | ((a & b & 0xFFFFu) << 16); }
+
+// own[i] = merge(own[i], peer[i]) over n granules, one uint4 (64 cells) per lane and step.  Plain loads and stores: the stream orders the
+// kernel behind the copy that brought the peer's words and behind the sketch kernels of this context, and nobody else writes this range.
+__global__ void __launch_bounds__(256) k_est_merge(uint4* __restrict__ own, const uint4* __restrict__ peer, uint64_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint4 a = own[i], b = peer[i];
+        own[i] = make_uint4(est_merge_word(a.x, b.x), est_merge_word(a.y, b.y), est_merge_word(a.z, b.z), est_merge_word(a.w, b.w));
     }
 }
 
@@ -73,6 +91,33 @@ void fgpu_touch_estimate() {
 }
 
 static_assert(EST_LEVELS == 4 && EST_SHIFT == 4, "fgpu_estimate holds four levels of a 16^-l sample each");
+
+// ---- what fgpu_estimate_end shares with the collective end of the pass (fgpu_group_estimate_end, group.hip)
+// the counts of granules [g0, g1) of the open pass' planes and the pass' k-mers into h (host: empty[4], once[4], kmers), behind everything
+// the pass has queued; returns once the device has finished it all
+int fgpu_estimate_range_counts(fgpu_ctx* ctx, uint64_t g0, uint64_t g1, uint64_t h[2 * FGPU_EST_LEVELS + 1]) {
+    unsigned long long* d = (unsigned long long*)ctx->est_counts.p;
+    if (g1 > g0) FGPU_LAUNCH("est_count", k_est_count, fgpu_grid(g1 - g0, 256), 256, (const uint4*)ctx->est_planes, ctx->est_r_bits, g0, g1, d);
+    FGPU_HIP(hipMemcpyAsync(h, d, (2 * EST_LEVELS + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    return fgpu_pull_counters(ctx);      // waits for the stream; a batch's total_bases that did not match its offsets
+}
+
+// the pass is over, and its planes go back.  `later` (or null): the planes are not freed but handed to the caller, who frees them once
+// nothing can be reading them any more (a peer's copy out of them may still run: fgpu_group_estimate_end)
+void fgpu_estimate_close(fgpu_ctx* ctx, void** later) {
+    if (later) *later = ctx->est_planes;
+    else (void)hipFree(ctx->est_planes);
+    ctx->est_planes = nullptr;
+    ctx->phase = 0;
+}
+
+// level, f0, f1 from the counts, with the words fgpu_estimate_end leaves in the context for a status that is not FGPU_OK
+int fgpu_estimate_finish(fgpu_ctx* ctx, fgpu_estimate* e, const char* who) {
+    const int rc = fgpu_estimate_solve(e);
+    if (rc == FGPU_ERR_CAPACITY) ctx->err = std::string(who) + ": the sketch is too full even at its thinnest level (fewer than an eighth of its cells empty): raise r_bits";
+    else if (rc) ctx->err = std::string(who) + ": counts that no sketch gives (internal error)";
+    return rc;
+}
 
 extern "C" {
 
@@ -120,21 +165,6 @@ int fgpu_estimate_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     return fgpu_host_batch_done(ctx, reads);
 }
 
-// the counts of the open pass into *out (host), behind everything the pass has queued
-static int estimate_counts(fgpu_ctx* ctx, fgpu_estimate* out) {
-    unsigned long long* d = (unsigned long long*)ctx->est_counts.p;
-    FGPU_LAUNCH("est_count", k_est_count, fgpu_grid(1ULL << (ctx->est_r_bits - 6), 256), 256, (const uint4*)ctx->est_planes, ctx->est_r_bits, d);
-    unsigned long long h[2 * EST_LEVELS + 1];
-    FGPU_HIP(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = fgpu_pull_counters(ctx)) return rc;      // waits for the stream; a batch's total_bases that did not match its offsets
-    for (int l = 0; l < EST_LEVELS; l++) {
-        out->empty[l] = h[l];
-        out->once[l] = h[EST_LEVELS + l];
-    }
-    out->kmers = h[2 * EST_LEVELS];
-    return FGPU_OK;
-}
-
 int fgpu_estimate_end(fgpu_ctx* ctx, fgpu_estimate* out) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 4) { ctx->err = "estimate_end without estimate_begin"; return FGPU_ERR_STATE; }
@@ -143,18 +173,60 @@ int fgpu_estimate_end(fgpu_ctx* ctx, fgpu_estimate* out) {
     memset(&e, 0, sizeof(e));
     e.r_bits = ctx->est_r_bits;
     e.level = -1;
-    int rc = estimate_counts(ctx, &e);
+    uint64_t h[2 * EST_LEVELS + 1];
+    int rc = fgpu_estimate_range_counts(ctx, 0, 4ULL << (ctx->est_r_bits - 6), h);
     // the pass is over either way, and its planes go back
     if (rc) (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(ctx->est_planes);
-    ctx->est_planes = nullptr;
-    ctx->phase = 0;
+    fgpu_estimate_close(ctx, nullptr);
     if (rc) return rc;
-    rc = fgpu_estimate_solve(&e);
-    if (rc == FGPU_ERR_CAPACITY) ctx->err = "estimate_end: the sketch is too full even at its thinnest level (fewer than an eighth of its cells empty): raise r_bits";
-    else if (rc) ctx->err = "estimate_end: counts that no sketch gives (internal error)";
+    for (int l = 0; l < EST_LEVELS; l++) {
+        e.empty[l] = h[l];
+        e.once[l] = h[EST_LEVELS + l];
+    }
+    e.kmers = h[2 * EST_LEVELS];
+    rc = fgpu_estimate_finish(ctx, &e, "estimate_end");
     if (out) *out = e;
     return rc;
+}
+
+int fgpu_estimate_planes(fgpu_ctx* ctx, void** dev, uint64_t* nbytes) {
+    if (!ctx || !dev) return FGPU_ERR_ARG;
+    if (ctx->phase != 4) { ctx->err = "estimate_planes outside estimate_begin/estimate_end"; return FGPU_ERR_STATE; }
+    *dev = ctx->est_planes;
+    if (nbytes) *nbytes = 1ULL << ctx->est_r_bits;
+    return FGPU_OK;
+}
+
+int fgpu_estimate_merge(fgpu_ctx* ctx, const void* peer_dev, uint64_t first_byte, uint64_t nbytes) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 4) { ctx->err = "estimate_merge outside estimate_begin/estimate_end"; return FGPU_ERR_STATE; }
+    const uint64_t bytes = 1ULL << ctx->est_r_bits;
+    if (!peer_dev || ((uintptr_t)peer_dev & 15) || (first_byte & 15) || (nbytes & 15) || first_byte > bytes || nbytes > bytes - first_byte) {
+        ctx->err = "estimate_merge: a device pointer and a range of whole 16-byte granules inside the planes";
+        return FGPU_ERR_ARG;
+    }
+    if (!nbytes) return FGPU_OK;
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    FGPU_LAUNCH("est_merge", k_est_merge, fgpu_grid(nbytes / 16, 256), 256, (uint4*)((char*)ctx->est_planes + first_byte), (const uint4*)peer_dev, nbytes / 16);
+    return FGPU_OK;
+}
+
+int fgpu_estimate_kmers(fgpu_ctx* ctx, uint64_t* kmers) {
+    if (!ctx || !kmers) return FGPU_ERR_ARG;
+    if (ctx->phase != 4) { ctx->err = "estimate_kmers outside estimate_begin/estimate_end"; return FGPU_ERR_STATE; }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    FGPU_HIP(hipMemcpyAsync(kmers, (const unsigned long long*)ctx->est_counts.p + 2 * EST_LEVELS, 8, hipMemcpyDeviceToHost, ctx->stream));
+    return fgpu_pull_counters(ctx);      // waits for the stream
+}
+
+int fgpu_estimate_download(fgpu_ctx* ctx, void* host, uint64_t nbytes) {
+    if (!ctx || !host) return FGPU_ERR_ARG;
+    if (ctx->phase != 4) { ctx->err = "estimate_download outside estimate_begin/estimate_end"; return FGPU_ERR_STATE; }
+    if (nbytes != 1ULL << ctx->est_r_bits) { ctx->err = "estimate_download: the planes are 2^r_bits bytes"; return FGPU_ERR_ARG; }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    FGPU_HIP(hipMemcpyAsync(host, ctx->est_planes, nbytes, hipMemcpyDeviceToHost, ctx->stream));
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    return FGPU_OK;
 }
 
 }  // extern "C"

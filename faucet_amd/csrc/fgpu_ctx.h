@@ -572,6 +572,10 @@ int fgpu_scan_build_cand(fgpu_ctx* ctx, BatchBufs* b);
 int fgpu_scan_import_probe(fgpu_ctx* ctx, const void* dev_entries, uint64_t n, uint64_t after_seq, uint32_t* dfilter, uint64_t dfilter_bits,
                            uint64_t* max_seq, uint64_t* n_newer, uint64_t digest[2]);
 int fgpu_stage_scan_debug_drop(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi);
+// the end of the estimate pass, in the steps the collective end takes one by one (estimate.hip)
+int fgpu_estimate_range_counts(fgpu_ctx* ctx, uint64_t g0, uint64_t g1, uint64_t h[2 * FGPU_EST_LEVELS + 1]);
+void fgpu_estimate_close(fgpu_ctx* ctx, void** later);
+int fgpu_estimate_finish(fgpu_ctx* ctx, fgpu_estimate* e, const char* who);
 int fgpu_util_count_segments(fgpu_ctx* ctx, const void* bad, uint64_t n_words, int minlen);
 int fgpu_util_popcount(fgpu_ctx* ctx, const void* dev, uint64_t nbytes, unsigned long long* dev_out);
 int fgpu_util_or(fgpu_ctx* ctx, void* dst, const void* src, uint64_t nbytes);

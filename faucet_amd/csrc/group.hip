@@ -55,6 +55,10 @@ struct RankState {
     uint64_t scratch_bytes[2] = {0, 0};
     ncclComm_t comm = nullptr;
     std::string err;
+    // fgpu_group_estimate_end: what this rank tells the others through host memory -- the r_bits of its open pass (-1: none), then its counts
+    int est_r_bits = -1;
+    uint64_t est_counts[2 * FGPU_EST_LEVELS + 1] = {};
+    std::vector<void*> est_graveyard;     // planes of a collective end that failed: a peer's copy may still read them (freed by fgpu_group_destroy)
 };
 
 }  // namespace
@@ -303,6 +307,10 @@ void fgpu_group_destroy(fgpu_group* g) {
         for (hipEvent_t e : r.events) (void)hipEventDestroy(e);
         for (void* p : r.scratch) if (p) (void)hipFree(p);
         for (Msg* msg : r.outstanding) note(msg);
+    }
+    for (RankState& r : g->ranks) {          // behind the loop above: EVERY rank's stream has been waited for
+        if (r.device >= 0 && !r.est_graveyard.empty()) (void)hipSetDevice(r.device);
+        for (void* p : r.est_graveyard) (void)hipFree(p);
     }
     for (Channel& c : g->chan)
         for (Msg* msg : c.q) note(msg);
@@ -618,6 +626,128 @@ int fgpu_group_selftest(fgpu_group* g, int rank, uint64_t nbytes, int* ok) {
     GHIP(hipStreamSynchronize(st));
     *ok = memcmp(src.data(), back.data(), (size_t)nbytes) == 0 ? 1 : 0;
     return FGPU_OK;
+}
+
+// ---- the collective end of pass 0 (faucet_gpu.h) ----------------------------------------------------------------------
+// Bytes of staging per peer and step: one chunk per peer, 128 MiB in all at the most
+static uint64_t estimate_chunk(int n) {
+    uint64_t chunk = ((128ULL << 20) / (uint64_t)(n - 1)) & ~15ULL;
+    if (const char* e = getenv("FGPU_ESTIMATE_MERGE_CHUNK")) {
+        const uint64_t v = strtoull(e, nullptr, 10) & ~15ULL;
+        if (v >= 16 && v < chunk) chunk = v;
+    }
+    return chunk;
+}
+
+int fgpu_group_estimate_end(fgpu_group* g, int rank, fgpu_estimate* out) {
+    if (bad_rank(g, rank)) return FGPU_ERR_ARG;
+    RankState& r = g->ranks[(size_t)rank];
+    fgpu_ctx* ctx = r.ctx;
+    // (nothing of this call has been exchanged where it is refused before or at the agreement: an open pass is closed and its planes freed at once)
+    auto refuse = [&](int rc) {
+        if (ctx && ctx->phase == 4) {
+            (void)hipSetDevice(r.device);
+            (void)hipStreamSynchronize(ctx->stream);
+            fgpu_estimate_close(ctx, nullptr);
+        }
+        return rc;
+    };
+    if (int rc = check_rank(g, rank)) return refuse(rc);
+    if (g->n == 1) {
+        const int rc = fgpu_estimate_end(ctx, out);
+        return rc == FGPU_OK ? rc : gfail(g, rank, rc, ctx->err);
+    }
+    const int n = g->n;
+    // 1  the ranks agree.  Between two barriers: no rank is back with the r_bits of its next pass while another still reads those of this one
+    const int mine_bits = ctx->phase == 4 ? ctx->est_r_bits : -1;
+    {
+        std::lock_guard<std::mutex> lk(g->m);
+        r.est_r_bits = mine_bits;
+    }
+    int agreed = fgpu_group_barrier(g, rank);
+    const char* why = nullptr;
+    if (agreed == FGPU_OK) {
+        {
+            std::lock_guard<std::mutex> lk(g->m);
+            for (const RankState& q : g->ranks)
+                if (q.est_r_bits < 0) { agreed = FGPU_ERR_STATE; why = "group_estimate_end: a rank of the group is not in an estimate pass (fgpu_estimate_begin)"; }
+            for (const RankState& q : g->ranks)
+                if (agreed == FGPU_OK && q.est_r_bits != mine_bits) { agreed = FGPU_ERR_ARG; why = "group_estimate_end: the ranks' sketches differ in r_bits"; }
+        }
+        if (int rc = fgpu_group_barrier(g, rank)) { agreed = rc; why = nullptr; }
+    }
+    if (agreed != FGPU_OK) return refuse(why ? gfail(g, rank, agreed, why) : agreed);
+    // from here on a peer may be reading this rank's planes: a failure leaves them to fgpu_group_destroy and wakes the others
+    auto fail = [&](int rc, const std::string& what) {      // (what: empty where the call that failed has left its words with the rank)
+        void* planes = nullptr;
+        fgpu_estimate_close(ctx, &planes);
+        {
+            std::lock_guard<std::mutex> lk(g->m);
+            if (planes) r.est_graveyard.push_back(planes);
+            if (!what.empty()) r.err = what;
+        }
+        fgpu_group_abort(g);
+        return rc;
+    };
+    if (hipSetDevice(r.device) != hipSuccess) return fail(FGPU_ERR_HIP, "group_estimate_end: hipSetDevice failed");
+    // 2  range q of every rank's planes to rank q, merged there chunk by chunk
+    const uint64_t nbytes = 1ULL << mine_bits, chunk = estimate_chunk(n);
+    std::vector<uint64_t> lo, hi;
+    slices(nbytes, n, lo, hi);
+    const uint64_t mine = hi[(size_t)rank] - lo[(size_t)rank], step = std::min(chunk, lo[1] - lo[0]);      // (slice 0 is the longest)
+    char* planes = (char*)ctx->est_planes;
+    char* stage = nullptr;
+    if (mine) {
+        void* stage_v = nullptr;
+        if (int rc = scratch(g, rank, 0, std::min(step, mine) * (uint64_t)(n - 1), &stage_v)) return fail(rc, "");
+        stage = (char*)stage_v;
+    }
+    const uint64_t stride = std::min(step, mine);          // bytes between two peers' chunks in the staging buffer
+    std::vector<Xfer> sends, recvs;
+    for (uint64_t at = 0; at < lo[1] - lo[0]; at += step) {
+        sends.clear();
+        recvs.clear();
+        const uint64_t take_now = at < mine ? std::min(step, mine - at) : 0;
+        int i = 0;
+        for (int q = 0; q < n; q++) {
+            if (q == rank) continue;
+            const uint64_t len_q = hi[(size_t)q] - lo[(size_t)q];
+            if (at < len_q) sends.push_back(Xfer{q, planes + lo[(size_t)q] + at, std::min(step, len_q - at)});
+            if (take_now) recvs.push_back(Xfer{q, stage + (uint64_t)i * stride, take_now});
+            i++;
+        }
+        if (int rc = exchange(g, rank, sends, recvs)) return fail(rc, "");
+        // ... on the context's stream, behind the copies that have just been queued there; the next step's copies follow the merges
+        for (int s = 0; take_now && s < n - 1; s++)
+            if (int rc = fgpu_estimate_merge(ctx, stage + (uint64_t)s * stride, lo[(size_t)rank] + at, take_now)) return fail(rc, ctx->err);
+    }
+    // 3  the counts of the own range; the call waits for this rank's device: every copy INTO this rank has finished when it returns
+    uint64_t h[2 * FGPU_EST_LEVELS + 1];
+    if (int rc = fgpu_estimate_range_counts(ctx, lo[(size_t)rank] / 16, hi[(size_t)rank] / 16, h)) return fail(rc, ctx->err);
+    {
+        std::lock_guard<std::mutex> lk(g->m);
+        memcpy(r.est_counts, h, sizeof(h));
+    }
+    // every rank has waited for its device behind this barrier: nobody reads anybody's planes any more, and all counts stand
+    if (int rc = fgpu_group_barrier(g, rank)) return fail(rc, "");
+    fgpu_estimate_close(ctx, nullptr);
+    fgpu_estimate e;
+    memset(&e, 0, sizeof(e));
+    e.r_bits = mine_bits;
+    e.level = -1;
+    {
+        std::lock_guard<std::mutex> lk(g->m);
+        for (const RankState& q : g->ranks) {
+            for (int l = 0; l < FGPU_EST_LEVELS; l++) {
+                e.empty[l] += q.est_counts[l];
+                e.once[l] += q.est_counts[FGPU_EST_LEVELS + l];
+            }
+            e.kmers += q.est_counts[2 * FGPU_EST_LEVELS];
+        }
+    }
+    const int rc = fgpu_estimate_finish(ctx, &e, "group_estimate_end");
+    if (out) *out = e;
+    return rc == FGPU_OK ? rc : gfail(g, rank, rc, ctx->err);
 }
 
 // ---- device memory for the host's exchange buffers ---------------------------------------------------------------------------------------

@@ -11,7 +11,8 @@
 // leaves there: the JunctionMap container that fixes the dump order, and the files.  Both pair filters are filled on the
 // device from scanInputRead's per-read lists (fgpu_scan_short_pairs, fgpu_scan_long_pairs) and come back as bytes.
 // Not in the reference: --estimate.  -estimated_kmers and -singletons, which the reference has its users find with a separate k-mer counter,
-// may then be left out; a pass 0 over -read_load_file sketches the reads on the device (fgpu_estimate_*) and fills in whichever is absent.
+// may then be left out; a pass 0 over -read_load_file sketches the reads on the device (fgpu_estimate_*) and fills in whichever is absent;
+// with -gpus N every rank sketches its read shard and the sketches are merged (ShardedRun::estimate).
 #include <errno.h>
 #include <fcntl.h>
 #include <stdint.h>
@@ -594,6 +595,17 @@ void choose_chunk_bytes(Options& o) {
     if (largest_input(o, &largest) && largest + (1u << 20) < o.chunk_bytes) o.chunk_bytes = ((largest >> 20) + 1) << 20;
 }
 
+// the options of the run's read shards (and of pass 0's, which runs on the same devices over the same transport)
+faucet_host::ShardOptions shard_options_of(const Options& o, const fgpu_params& prm) {
+    // every shard reads its share through buffers of its own: chunks no larger than a share needs
+    uint64_t chunk_bytes = o.chunk_bytes, largest = 0;
+    largest_input(o, &largest);
+    const uint64_t share = largest / (uint64_t)o.gpus + (4u << 20);
+    if (share < chunk_bytes) chunk_bytes = ((share >> 20) + 1) << 20;
+    return faucet_host::shard_options(o.gpus, o.transport == "rccl" ? FGPU_TRANSPORT_RCCL : FGPU_TRANSPORT_COPY, prm, o.fastq, o.mercy, o.paired_ends,
+                                      o.no_cleaning, chunk_bytes);
+}
+
 // ---- the run's contexts.  0, or the exit code of a failure
 int open_shards(const Options& o, const fgpu_params& prm, bool verbose, Run* run) {
     if (o.batch_reads) { fprintf(stderr, "-batch_reads (records split on the host) cannot be combined with -gpus: the shards split their records on their devices\n"); return 1; }
@@ -606,13 +618,7 @@ int open_shards(const Options& o, const fgpu_params& prm, bool verbose, Run* run
     const int ndev = fgpu_device_count();
     if (ndev < 1) { fprintf(stderr, "fgpu_create failed (%d): no gfx950 device\n", FGPU_ERR_HIP); return 2; }
     if (ndev < o.gpus) fprintf(stderr, "note: %d read shards on %d device%s: shards share devices\n", o.gpus, ndev, ndev == 1 ? "" : "s");
-    // every shard reads its share through buffers of its own: chunks no larger than a share needs
-    uint64_t chunk_bytes = o.chunk_bytes, largest = 0;
-    largest_input(o, &largest);
-    const uint64_t share = largest / (uint64_t)o.gpus + (4u << 20);
-    if (share < chunk_bytes) chunk_bytes = ((share >> 20) + 1) << 20;
-    faucet_host::ShardOptions so = faucet_host::shard_options(o.gpus, o.transport == "rccl" ? FGPU_TRANSPORT_RCCL : FGPU_TRANSPORT_COPY, prm, o.fastq, o.mercy,
-                                                              o.paired_ends, o.no_cleaning, chunk_bytes);
+    faucet_host::ShardOptions so = shard_options_of(o, prm);
     so.verbose = verbose;
     run->shards.reset(new ShardedRun(so));
     if (int rc = run->shards->create()) { fprintf(stderr, "fgpu_create failed (%d): %s\n", rc, run->shards->error().c_str()); return 2; }
@@ -667,9 +673,55 @@ int feed_batches(fgpu_ctx* ctx, BatchSource& src, const char* progress, double* 
     return FGPU_OK;
 }
 
-// ---- pass 0 (--estimate): whichever of -estimated_kmers / -singletons the command line left out, from a sketch of -read_load_file on the first
-// device.  The sizes of the run's context follow from these numbers, so the pass has a placeholder context of its own (tai = 128, one hash
-// function: the pass reads neither), destroyed before the run's contexts are made.  0, or the exit code of a failure
+// ---- pass 0 (--estimate): whichever of -estimated_kmers / -singletons the command line left out, from a sketch of -read_load_file.  The sizes
+// of the run's contexts follow from these numbers, so the pass has placeholder contexts of its own (tai = 128, one hash function: the pass
+// reads neither), destroyed before the run's contexts are made.  With -gpus N every rank sketches its read shard and the sketches are merged
+// (ShardedRun::estimate): the same counts, hence the same two lines and the same run, as from the first device alone -- which is what
+// FAUCET_ESTIMATE_SHARDS=0 (A/B timing, tests), a library without fgpu_group_estimate_end and -batch_reads (refused by open_shards, behind
+// pass 0) still get.  0, or the exit code of a failure
+int estimate_one_device(const Options& o, const fgpu_params& prm, PhaseClock& clk, fgpu_estimate* est) {
+    Run placeholder;
+    if (int rc = open_one_device(o, prm, &placeholder)) return rc;
+    fgpu_ctx* ctx = placeholder.one;
+    clk.mark("arguments, placeholder context");
+    BatchSource src(o, o.read_load_file);
+    if (!src.is_open()) { fprintf(stderr, "cannot open %s\n", o.read_load_file.c_str()); return 2; }
+    CHECK(fgpu_estimate_begin(ctx, o.estimate_bits));
+    double batch_ms = 0;
+    const char* failed = "fgpu_estimate_batch";
+    if (int rc = feed_batches(ctx, src, nullptr, &batch_ms, &failed, [&](const fgpu_reads* r) { return fgpu_estimate_batch(ctx, r); })) {
+        fprintf(stderr, "%s failed (%d): %s\n", failed, rc, fgpu_last_error(ctx));
+        return 2;
+    }
+    const int rc = fgpu_estimate_end(ctx, est);
+    if (rc == FGPU_ERR_CAPACITY) { fprintf(stderr, "--estimate: the sketch of 2^%d cells per level is too full for these reads: raise -estimate_bits\n", (int)est->r_bits); return 2; }
+    if (rc != FGPU_OK) { fprintf(stderr, "fgpu_estimate_end failed (%d): %s\n", rc, fgpu_last_error(ctx)); return 2; }
+    if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_estimate_batch calls; %llu k-mers sketched, 2^%d cells per level, estimates from level %d on\n", batch_ms,
+                        (unsigned long long)est->kmers, (int)est->r_bits, (int)est->level);
+    clk.mark("pass 0 (read + estimate)");
+    return 0;
+}
+
+int estimate_shards(const Options& o, const fgpu_params& prm, PhaseClock& clk, fgpu_estimate* est) {
+    if (fgpu_device_count() < 1) { fprintf(stderr, "fgpu_create failed (%d): no gfx950 device\n", FGPU_ERR_HIP); return 2; }
+    faucet_host::ShardOptions so = shard_options_of(o, prm);
+    so.verbose = clk.on;
+    ShardedRun placeholder(so);
+    if (int rc = placeholder.create()) { fprintf(stderr, "fgpu_create failed (%d): %s\n", rc, placeholder.error().c_str()); return 2; }
+    clk.mark("arguments, placeholder contexts");
+    std::vector<uint64_t> kmers;
+    const int rc = placeholder.estimate(o.read_load_file, o.estimate_bits, est, &kmers);
+    if (rc == FGPU_ERR_CAPACITY) { fprintf(stderr, "--estimate: the sketch of 2^%d cells per level is too full for these reads: raise -estimate_bits\n", (int)est->r_bits); return 2; }
+    if (rc != FGPU_OK) { fprintf(stderr, "estimate pass failed (%d): %s\n", rc, placeholder.error().c_str()); return 2; }
+    if (clk.on) {
+        for (size_t r = 0; r < kmers.size(); r++) fprintf(stderr, "[cli]   rank %d: %llu k-mers sketched\n", (int)r, (unsigned long long)kmers[r]);
+        fprintf(stderr, "[cli]   %llu k-mers sketched over %d read shards, 2^%d cells per level, estimates from level %d on\n", (unsigned long long)est->kmers, o.gpus,
+                (int)est->r_bits, (int)est->level);
+    }
+    clk.mark("pass 0 (shards)");      // (the placeholder contexts go as the one-device pass' does: behind the mark)
+    return 0;
+}
+
 int estimate_missing(Options& o, PhaseClock& clk) {
     // decided before any device call: the file is read once more by pass 1, and the library has to have the pass
     struct stat st;
@@ -690,26 +742,11 @@ int estimate_missing(Options& o, PhaseClock& clk) {
     prm.max_spacer_dist = 100;
     prm.n_hash = 1;
     prm.tai = 128;
-    Run placeholder;
-    if (int rc = open_one_device(o, prm, &placeholder)) return rc;
-    fgpu_ctx* ctx = placeholder.one;
-    clk.mark("arguments, placeholder context");
-    BatchSource src(o, o.read_load_file);
-    if (!src.is_open()) { fprintf(stderr, "cannot open %s\n", o.read_load_file.c_str()); return 2; }
-    CHECK(fgpu_estimate_begin(ctx, o.estimate_bits));
-    double batch_ms = 0;
-    const char* failed = "fgpu_estimate_batch";
-    if (int rc = feed_batches(ctx, src, nullptr, &batch_ms, &failed, [&](const fgpu_reads* r) { return fgpu_estimate_batch(ctx, r); })) {
-        fprintf(stderr, "%s failed (%d): %s\n", failed, rc, fgpu_last_error(ctx));
-        return 2;
-    }
+    const char* by_shards_env = getenv("FAUCET_ESTIMATE_SHARDS");
+    const bool by_shards = o.gpus > 1 && !o.from_junctions && !o.batch_reads && ShardedRun::estimate_linked() && !(by_shards_env && by_shards_env[0] == '0');
     fgpu_estimate est;
-    const int rc = fgpu_estimate_end(ctx, &est);
-    if (rc == FGPU_ERR_CAPACITY) { fprintf(stderr, "--estimate: the sketch of 2^%d cells per level is too full for these reads: raise -estimate_bits\n", (int)est.r_bits); return 2; }
-    if (rc != FGPU_OK) { fprintf(stderr, "fgpu_estimate_end failed (%d): %s\n", rc, fgpu_last_error(ctx)); return 2; }
-    if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_estimate_batch calls; %llu k-mers sketched, 2^%d cells per level, estimates from level %d on\n", batch_ms,
-                        (unsigned long long)est.kmers, (int)est.r_bits, (int)est.level);
-    clk.mark("pass 0 (read + estimate)");
+    memset(&est, 0, sizeof(est));
+    if (int rc = by_shards ? estimate_shards(o, prm, clk, &est) : estimate_one_device(o, prm, clk, &est)) return rc;
     const long long f0 = llround(est.f0), f1 = std::max(llround(est.f1), 1LL);
     printf("Estimated distinct k-mers (F0): %lld\n", f0);
     printf("Estimated singletons (f1): %lld\n", f1);

@@ -8,6 +8,8 @@
 // one PROCESS per GPU over torch.distributed; DESIGN.md section 5 says why each step is exact.
 //
 //   shard r = the r-th file-order share of the records (text_source.h, record_cuts), read and driven by thread r on device r
+//   pass 0   (ShardedRun::estimate, for a caller that does not know -estimated_kmers / -singletons yet) every rank sketches its shard
+//            (fgpu_estimate_begin / _batch), the sketches are merged by slices of the planes and counted (fgpu_group_estimate_end)
 //   pass 1   fix-up protocol (a shard that stays in HBM, at most 4 hash functions): every rank loads its shard alone
 //            (FGPU_LOAD_SHARD_TIMES) -> exclusive prefix-OR of the shards' bloo1 over ranks -> fgpu_load_fixup against that prefix on
 //            ranks > 0 -> OR-allreduce of bloo2;  presence protocol (otherwise, and with --mercy): presence bitmap of the shard ->
@@ -48,6 +50,11 @@
 #pragma weak fgpu_group_allgather
 #pragma weak fgpu_scan_resident_base
 #pragma weak fgpu_diag_long_pairs_state
+// ... and so are those of pass 0 over read shards (ShardedRun::estimate)
+#pragma weak fgpu_estimate_begin
+#pragma weak fgpu_estimate_batch
+#pragma weak fgpu_estimate_kmers
+#pragma weak fgpu_group_estimate_end
 
 namespace faucet_host {
 
@@ -160,6 +167,49 @@ public:
             if (ctx_[r]) { fgpu_destroy(ctx_[r]); ctx_[r] = nullptr; }
             for (int i = 0; i < 2; i++) if (bufs_[r].p[i]) { fgpu_host_free(bufs_[r].p[i]); bufs_[r].p[i] = nullptr; }
         }
+    }
+
+    // ---- pass 0 (not in the reference: include/faucet_gpu.h, fgpu_estimate_*): every rank sketches its shard of `path` with 2^r_bits cells per
+    // level (0: the library's default) and the ranks merge their sketches; *out is what ONE sketch of the whole file gives, to the last counter.
+    // FGPU_ERR_CAPACITY (the sketch is too full: raise r_bits) leaves the counts in *out.  kmers_by_rank (or null): the occurrences per shard.
+    static bool estimate_linked() { return fgpu_estimate_begin && fgpu_estimate_batch && fgpu_estimate_kmers && fgpu_group_estimate_end; }
+    int estimate(const std::string& path, int r_bits, fgpu_estimate* out, std::vector<uint64_t>* kmers_by_rank = nullptr) {
+        if (!estimate_linked()) {
+            error_ = "the library this program is linked against lacks the entry points of the estimate pass over read shards "
+                     "(fgpu_estimate_begin, fgpu_estimate_batch, fgpu_estimate_kmers, fgpu_group_estimate_end)";
+            return FGPU_ERR_STATE;
+        }
+        std::vector<uint64_t> cuts;
+        const double t_cuts = now_ms();
+        if (!record_cuts(path, o_.fastq ? 4 : 2, o_.paired_ends ? 2 : 1, o_.n_ranks, &cuts)) {
+            error_ = "cannot cut " + path + " into read shards: with several GPUs the input must be a regular file";
+            return FGPU_ERR_ARG;
+        }
+        if (o_.verbose) fprintf(stderr, "[cli]   pass 0: record cuts of %s found in %.1f ms (kept for the passes that follow)\n", path.c_str(), now_ms() - t_cuts);
+        std::vector<fgpu_estimate> est((size_t)o_.n_ranks);
+        std::vector<uint64_t> kmers((size_t)o_.n_ranks, 0);
+        std::vector<int> status((size_t)o_.n_ranks, FGPU_OK);
+        int rc = run_ranks([&](int r) -> int {
+            fgpu_ctx* c = ctx_[(size_t)r];
+            const double t0 = now_ms();
+            RANK_CHECK(fgpu_estimate_begin(c, r_bits));
+            // (a rank that fails before the collective end aborts the group through run_ranks: the others' end returns, and fgpu_destroy
+            // gives this rank's planes back behind fgpu_group_destroy)
+            RANK_TRY(for_each_batch(r, path, cuts, [&](const fgpu_reads* b) { return fgpu_estimate_batch(c, b); }, nullptr));
+            RANK_CHECK(fgpu_estimate_kmers(c, &kmers[(size_t)r]));
+            const double t1 = now_ms();
+            memset(&est[(size_t)r], 0, sizeof(fgpu_estimate));
+            const int rc_end = fgpu_group_estimate_end(group_, r, &est[(size_t)r]);
+            status[(size_t)r] = rc_end;
+            if (rc_end != FGPU_OK && rc_end != FGPU_ERR_CAPACITY) { err_[(size_t)r] = std::string("fgpu_group_estimate_end failed: ") + fgpu_group_last_error(group_, r); return rc_end; }
+            tell(r, "pass 0: sketch of the shard %.1f ms, merge by slices + count %.1f ms", t1 - t0, now_ms() - t1);
+            return FGPU_OK;             // (too full a sketch is every rank's answer, not a rank's failure: the group stays usable)
+        });
+        if (rc != FGPU_OK) return rc;
+        *out = est[0];
+        if (kmers_by_rank) *kmers_by_rank = kmers;
+        if (status[0] == FGPU_ERR_CAPACITY) error_ = "the sketch is too full even at its thinnest level: raise r_bits";
+        return status[0];
     }
 
     // ---- pass 1 (load_two_filters, utils/Bloom.cpp:267-350): afterwards every rank holds the run's bloo2, the last rank its bloo1

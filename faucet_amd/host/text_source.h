@@ -298,6 +298,20 @@ inline bool record_cuts(const std::string& path, int lines_per_record, int group
     cuts->assign((size_t)n + 1, size);
     (*cuts)[0] = 0;
     if (n == 1 || size == 0) { close(fd); return true; }
+    // Finding the cuts counts every newline of the file, and every pass over the shards asks for them (pass 0, 1 and 2 of one run: three times
+    // the same file as a rule): the last answer is kept, for the same file (device, inode, size, modification time) cut the same way.
+    struct Kept { dev_t dev; ino_t ino; uint64_t size; struct timespec mtime; int lines_per_record, group, n; std::vector<uint64_t> cuts; };
+    static std::mutex kept_m;
+    static Kept kept = {0, 0, 0, {0, 0}, 0, 0, 0, std::vector<uint64_t>()};
+    {
+        std::lock_guard<std::mutex> lk(kept_m);
+        if (kept.n == n && kept.dev == st.st_dev && kept.ino == st.st_ino && kept.size == size && kept.mtime.tv_sec == st.st_mtim.tv_sec &&
+            kept.mtime.tv_nsec == st.st_mtim.tv_nsec && kept.lines_per_record == lines_per_record && kept.group == group) {
+            *cuts = kept.cuts;
+            close(fd);
+            return true;
+        }
+    }
     const char* map = mapped_file(fd, st);
     std::vector<char> whole;
     if (!map) {                                   // FGPU_CLI_NO_MMAP: read it
@@ -351,6 +365,10 @@ inline bool record_cuts(const std::string& path, int lines_per_record, int group
         (*cuts)[(size_t)r] = pos;
     }
     for (int r = 1; r <= n; r++) (*cuts)[(size_t)r] = std::max((*cuts)[(size_t)r], (*cuts)[(size_t)r - 1]);   // (monotone: a long record may swallow a nominal cut)
+    {
+        std::lock_guard<std::mutex> lk(kept_m);
+        kept = Kept{st.st_dev, st.st_ino, size, st.st_mtim, lines_per_record, group, n, *cuts};
+    }
     return true;
 }
 

@@ -203,6 +203,25 @@ int fgpu_estimate_end(fgpu_ctx* ctx, fgpu_estimate* out);
 /* Host only, no device: level, f0, f1 from empty / once / r_bits.  FGPU_ERR_ARG: r_bits outside 8..34, or counts no sketch of m cells gives
  * (empty[l] + once[l] > m). */
 int fgpu_estimate_solve(fgpu_estimate* e);
+/* The sketches of the shards of a read set merge into the sketch of all of it.  A cell is a counter that saturates at 2 -- `seen` alone: 1,
+ * `seen` and `twice`: 2 or more -- and merging is saturating addition, cell by cell; on the 32-bit words of the planes (16 cells: `seen` in
+ * the low half, `twice` in the high half at the same place)
+ *     out = a | b | ((a & b & 0xFFFF) << 16)
+ * which is associative and commutative: whatever the order, the merged planes are those one pass over all reads ends with, to the last bit.
+ * The planes are 2^r_bits bytes, level l in bytes [l * 2^(r_bits - 2), (l + 1) * 2^(r_bits - 2)), cell c of a level in bit c & 15 (`seen`) and
+ * 16 + (c & 15) (`twice`) of its word c >> 4.
+ * _planes: the device pointer and size of the open pass' planes, as fgpu_bloom_devptr gives the filters'; nbytes may be NULL.
+ * _merge: peer_dev holds bytes [first_byte, first_byte + nbytes) of another sketch with the same r_bits (on this context's device); they are
+ * merged into the same bytes of this context's planes, on the context's stream, behind whatever it has queued.  first_byte, nbytes and
+ * peer_dev are multiples of 16; nbytes = 0 does nothing.  FGPU_ERR_ARG: a null or misaligned pointer, a misaligned range, a range past the planes.
+ * _download: the planes to the host (nbytes = 2^r_bits), behind everything queued; waits.  For tests and diagnosis.
+ * _kmers: the occurrences the open pass has sketched so far (fgpu_estimate.kmers of this context alone: a rank's share under
+ * fgpu_group_estimate_end, which returns the sum); waits for what is queued.
+ * All four: FGPU_ERR_STATE outside estimate_begin / estimate_end. */
+int fgpu_estimate_planes(fgpu_ctx* ctx, void** dev, uint64_t* nbytes);
+int fgpu_estimate_merge(fgpu_ctx* ctx, const void* peer_dev, uint64_t first_byte, uint64_t nbytes);
+int fgpu_estimate_download(fgpu_ctx* ctx, void* host, uint64_t nbytes);
+int fgpu_estimate_kmers(fgpu_ctx* ctx, uint64_t* kmers);
 
 /* ---- pass 1: Bloom load (replaces load_two_filters, utils/Bloom.cpp:267-350) ------------------- */
 /* Zero both filters (or keep bloo1's current content as the carried-in state when keep_carry != 0:
@@ -573,6 +592,22 @@ int fgpu_group_probe(fgpu_group* g, int rank, int src, int* waiting, uint64_t* n
 /* the transport moves nbytes from a buffer of this rank to another buffer of this rank (RCCL: a send to itself and its receive in one group)
  * and the result is compared on the host: *ok = 1 iff every byte arrived.  What a box with one device can show of the RCCL transport. */
 int fgpu_group_selftest(fgpu_group* g, int rank, uint64_t nbytes, int* ok);
+/* The collective end of pass 0: every rank has sketched its shard of the reads on its own context (fgpu_estimate_begin / _batch with the same
+ * r_bits) and its thread calls this in place of fgpu_estimate_end.  Every rank returns the same fgpu_estimate, that of ONE sketch of all the
+ * reads, to the last counter:
+ *   1  the ranks agree: a rank that is not in an estimate pass gives EVERY rank FGPU_ERR_STATE, ranks with different r_bits FGPU_ERR_ARG;
+ *   2  the planes are cut into N ranges of 16-byte granules, as fgpu_group_or_allreduce slices a bitmap (uneven and empty ranges allowed);
+ *      rank q collects range q of every other rank -- the reduce-scatter half of that call, through the group's own sends and receives --
+ *      into a staging buffer, chunk by chunk, and merges each chunk into its planes (fgpu_estimate_merge).  The staging buffer holds one
+ *      chunk per peer and never more than 128 MiB in all, whatever r_bits and N; FGPU_ESTIMATE_MERGE_CHUNK = bytes per peer and step (read
+ *      at every call, rounded down to 16, the same for all ranks of the process) overrides the chunk size, for tests;
+ *   3  rank q counts its merged range; empty[], once[] and kmers are summed over the ranks on the host (counts add over disjoint ranges of
+ *      cells: no rank ever holds the whole merged sketch), and every rank runs fgpu_estimate_solve on the sums.
+ * The pass ends on every rank whatever the status: planes given back, the context idle.  A rank's planes are freed only once every rank has
+ * waited for its device -- a peer's copy out of them has been queued, not finished, when the send returns -- and, after a failure, only by
+ * fgpu_group_destroy.  FGPU_ERR_CAPACITY comes back on every rank with the counts filled in, as from fgpu_estimate_end.  A failure of one rank
+ * inside steps 2 and 3 aborts the group (fgpu_group_abort): the others return FGPU_ERR_STATE.  A group of one rank: fgpu_estimate_end. */
+int fgpu_group_estimate_end(fgpu_group* g, int rank, fgpu_estimate* out);
 
 /* ---- probes for tests (pure, no state change) ------------------------------------------------- */
 /* For each of n k-mers (2-bit encoded, utils/Kmer.cpp:82-88,410-425): canonical form and
