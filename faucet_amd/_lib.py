@@ -96,8 +96,12 @@ SIGNATURES = {
     "fgpu_estimate_merge": (C.c_int, [_vp, _vp, _u64, _u64]),
     "fgpu_estimate_download": (C.c_int, [_vp, _vp, _u64]),
     "fgpu_estimate_kmers": (C.c_int, [_vp, _P(_u64)]),
+    "fgpu_estimate_keep": (C.c_int, [_vp, _u64]),
+    "fgpu_estimate_keep_state": (C.c_int, [_vp, _P(C.c_int), _P(_u64), _P(_u64)]),
+    "fgpu_estimate_take_kept": (C.c_int, [_vp, _P(Packed), _u64, _P(_u64)]),
     "fgpu_load_begin": (C.c_int, [_vp, C.c_int]),
     "fgpu_load_batch": (C.c_int, [_vp, _P(Reads)]),
+    "fgpu_load_batch_packed": (C.c_int, [_vp, _P(Packed)]),
     "fgpu_load_end": (C.c_int, [_vp, _P(LoadStats)]),
     "fgpu_presence_batch": (C.c_int, [_vp, _P(Reads)]),
     "fgpu_load_fixup": (C.c_int, [_vp, _vp, _P(LoadStats)]),

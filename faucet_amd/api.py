@@ -238,6 +238,32 @@ class Context:
         self._c(self.lib.fgpu_estimate_kmers(self.h, C.byref(n)))
         return int(n.value)
 
+    # ... that keeps what it packs: one reading of the stream serves pass 0 and pass 1 (faucet_gpu.h, fgpu_estimate_keep)
+    def estimate_keep(self, budget: int):
+        """between estimate_begin and the first batch: every non-empty batch is packed into a block of its own and held, charged to `budget`
+        bytes at 4 bits per stream position; a batch that does not fit ends the keeping, never the pass"""
+        self._c(self.lib.fgpu_estimate_keep(self.h, int(budget)))
+
+    def estimate_keep_state(self):
+        """(is every non-empty batch so far held?, blocks held, bytes they are charged); does not wait for the device"""
+        keeping, n, b = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        self._c(self.lib.fgpu_estimate_keep_state(self.h, C.byref(keeping), C.byref(n), C.byref(b)))
+        return bool(keeping.value), int(n.value), int(b.value)
+
+    def estimate_take_kept(self) -> list:
+        """after estimate_end: the blocks in batch order (L.Packed).  They are the caller's now: load_batch_packed hands one on to a context,
+        fgpu_device_free of any context on the device releases it; they outlive this context"""
+        n = C.c_uint64(0)
+        self.lib.fgpu_estimate_keep_state(self.h, None, C.byref(n), None)
+        out = (L.Packed * max(1, int(n.value)))()
+        self._c(self.lib.fgpu_estimate_take_kept(self.h, out, int(n.value), C.byref(n)))
+        blocks = []
+        for i in range(int(n.value)):      # copies: the array is not kept alive by its elements' users
+            pk = L.Packed()
+            C.memmove(C.byref(pk), C.byref(out[i]), C.sizeof(L.Packed))
+            blocks.append(pk)
+        return blocks
+
     # pass 1
     def load_begin(self, keep_carry=False, shard_times=False, shard_planes=False):
         self._c(self.lib.fgpu_load_begin(self.h, (L.LOAD_KEEP_CARRY if keep_carry else 0) | (L.LOAD_SHARD_TIMES if shard_times else 0) |
@@ -328,6 +354,10 @@ class Context:
     def load_batch(self, batch: ReadBatch):
         s = batch.c_struct()
         self._c(self.lib.fgpu_load_batch(self.h, C.byref(s)))
+
+    def load_batch_packed(self, pk: "L.Packed"):
+        """one batch of the plain pass from a packed block (estimate_take_kept): what load_batch does behind its packing; the context adopts the block"""
+        self._c(self.lib.fgpu_load_batch_packed(self.h, C.byref(pk)))
 
     def presence_batch(self, batch: ReadBatch):
         s = batch.c_struct()

@@ -422,6 +422,9 @@ void fgpu_destroy(fgpu_ctx* ctx) {
     if (ctx->ev_text_done) hipEventDestroy(ctx->ev_text_done);
     if (ctx->wstream) hipStreamSynchronize(ctx->wstream);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
+    fgpu_estimate_drop_kept(ctx);                 // blocks of pass 0 that nobody took, blocks a load pass adopted
+    fgpu_adopted_release(ctx, &ctx->adopted);
+    fgpu_adopted_release(ctx, &ctx->adopted_done);
     for (PendingEvent& pe : ctx->pending_events) { hipEventDestroy(pe.a); hipEventDestroy(pe.b); }
     for (DevBuf* b : ctx->owned) if (b->p) hipFree(b->p);
     if (ctx->lp.flips_host) hipHostFree(ctx->lp.flips_host);
@@ -535,10 +538,53 @@ int fgpu_load_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (rc) return rc;
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     if ((rc = fgpu_stage_pack(ctx, reads))) return rc;
-    if ((rc = fgpu_stage_load(ctx))) return rc;
+    const BatchBufs& bb = *ctx->cur;
+    if ((rc = fgpu_stage_load(ctx, bb.codes.p, bb.bad.p, bb.T, bb.n_words))) return rc;
+    if (bb.T && (rc = fgpu_resident_keep(ctx))) return rc;
     if (ctx->cur->T) ctx->pass_batches++;
     ctx->load_stats.reads_processed += reads->n_reads;
     return fgpu_host_batch_done(ctx, reads);   // (the host buffers were free again when the copy had run: fgpu_stage_pack)
+}
+
+// One batch of the plain pass from a packed block of another pass or context (fgpu_estimate_take_kept): the block's planes in place of the
+// batch in hand's, the block adopted as the resident batch's codes / bad.  A block's content is checked against its trailer like one that
+// came from a peer (error flag 64 at the pass' next synchronising call).
+int fgpu_load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk) {
+    if (!ctx || !pk) return FGPU_ERR_ARG;
+    if (ctx->phase != 1) { ctx->err = "load_batch_packed outside load_begin/load_end"; return FGPU_ERR_STATE; }
+    if (ctx->shard_times || ctx->shard_planes) {
+        ctx->err = "load_batch_packed in the pass of a read shard (FGPU_LOAD_SHARD_TIMES / FGPU_LOAD_SHARD_PLANES): the fix-up reads the batches' own copies";
+        return FGPU_ERR_STATE;
+    }
+    if (!pk->block_dev) {                        // a batch without reads has no block
+        if (pk->T || pk->nbytes || pk->n_reads) { ctx->err = "load_batch_packed: a description without a block must be empty"; return FGPU_ERR_ARG; }
+        return FGPU_OK;
+    }
+    PackedBlock b;
+    b.buf.p = pk->block_dev;
+    b.buf.bytes = pk->nbytes;
+    b.T = pk->T;
+    b.n_words = (pk->T + 63) / 64;
+    b.n_reads = pk->n_reads;
+    if (!pk->T || pk->T > ctx->prm.max_batch_bases || pk->T >= 0xFFFFFF00ULL || pk->n_reads > pk->T || !pk->n_reads || pk->nbytes != fgpu_packed_bytes(b.n_words)) {
+        ctx->err = "load_batch_packed: a block of nbytes = 24 * (ceil(T / 64) + 8) + 16 for T stream positions (at most max_batch_bases) of 1 <= n_reads <= T reads";
+        return FGPU_ERR_ARG;
+    }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    int rc = fgpu_packed_digest(ctx, &b, true);
+    if (rc) return rc;
+    const uint64_t* words = (const uint64_t*)b.buf.p;
+    if ((rc = fgpu_stage_load(ctx, words, words + 2 * (b.n_words + FGPU_PADW), b.T, b.n_words))) {
+        (void)hipStreamSynchronize(ctx->stream);   // the caller still owns the block and may free it: nothing queued reads it any more
+        return rc;
+    }
+    if ((rc = fgpu_resident_adopt(ctx, b))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    ctx->pass_batches++;
+    ctx->load_stats.reads_processed += b.n_reads;
+    return FGPU_OK;
 }
 
 int fgpu_presence_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
@@ -555,7 +601,9 @@ int fgpu_presence_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
 int fgpu_load_end(fgpu_ctx* ctx, fgpu_load_stats* stats) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 1) { ctx->err = "load_end without load_begin"; return FGPU_ERR_STATE; }
-    return fgpu_load_pass_end(ctx, stats);
+    const int rc = fgpu_load_pass_end(ctx, stats);
+    fgpu_adopted_release(ctx, &ctx->adopted_done);   // blocks of batches the pass did not keep resident (fgpu_load_batch_packed)
+    return rc;
 }
 
 int fgpu_load_fixup_state(fgpu_ctx* ctx, int* ready, uint64_t* resident_budget_bytes) {

@@ -111,6 +111,17 @@ void fgpu_estimate_close(fgpu_ctx* ctx, void** later) {
     ctx->phase = 0;
 }
 
+// Every block the pass holds goes back (the sketch kernels that read them may still be queued: the stream is waited for first)
+void fgpu_estimate_drop_kept(fgpu_ctx* ctx) {
+    if (!ctx->est_kept.empty()) {
+        (void)hipSetDevice(ctx->prm.device);
+        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+        for (PackedBlock& b : ctx->est_kept) (void)hipFree(b.buf.p);
+        ctx->est_kept.clear();
+    }
+    ctx->est_keep_bytes = 0;
+}
+
 // level, f0, f1 from the counts, with the words fgpu_estimate_end leaves in the context for a status that is not FGPU_OK
 int fgpu_estimate_finish(fgpu_ctx* ctx, fgpu_estimate* e, const char* who) {
     const int rc = fgpu_estimate_solve(e);
@@ -127,6 +138,9 @@ int fgpu_estimate_begin(fgpu_ctx* ctx, int32_t r_bits) {
     if (r_bits < FGPU_EST_MIN_BITS || r_bits > FGPU_EST_MAX_BITS) { ctx->err = "estimate_begin: r_bits must be 0 (the default, 30) or in 8..34"; return FGPU_ERR_ARG; }
     if (ctx->phase != 0) { ctx->err = "estimate_begin while another pass is open"; return FGPU_ERR_STATE; }
     FGPU_HIP(hipSetDevice(ctx->prm.device));
+    fgpu_estimate_drop_kept(ctx);        // blocks of an earlier pass that nobody took
+    ctx->est_keep_asked = ctx->est_keeping = false;
+    ctx->est_batches = 0;
     // 2 bits x 4 levels x 2^r_bits cells = 2^r_bits bytes, for the duration of the pass
     const uint64_t bytes = 1ULL << r_bits;
     hipError_t e = hipMalloc(&ctx->est_planes, bytes);
@@ -157,12 +171,88 @@ int fgpu_estimate_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     int rc = fgpu_check_reads(ctx, reads);
     if (rc) return rc;
     FGPU_HIP(hipSetDevice(ctx->prm.device));
-    if ((rc = fgpu_stage_pack(ctx, reads))) return rc;
-    const BatchBufs& bb = *ctx->cur;
-    if (bb.T)
-        FGPU_LAUNCH("est_sketch", k_est_sketch, fgpu_grid(bb.n_words * 64, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p, bb.T,
-                    bb.n_words, ctx->fd.k, ctx->est_planes, ctx->est_r_bits, (unsigned long long*)ctx->est_counts.p + 2 * EST_LEVELS);
+    ctx->est_batches++;
+    const uint64_t *codes, *bad;
+    uint64_t T, n_words;
+    PackedBlock blk;
+    if (ctx->est_keeping && reads->n_reads) {
+        bool no_memory;
+        if ((rc = fgpu_stage_pack_keep(ctx, reads, ctx->est_keep_budget - ctx->est_keep_bytes, &blk, &no_memory))) return rc;
+        if (!blk.buf.p) {   // the batch is not kept, so nothing is: the pass goes on as one that was never asked to keep
+            ctx->est_keep_stop_need = 4 * (blk.n_words + FGPU_PADW) * 8;
+            ctx->est_keep_stop_used = ctx->est_keep_bytes;
+            ctx->est_keep_stop_blocks = ctx->est_kept.size();
+            ctx->est_keep_stop_nomem = no_memory;
+            ctx->est_keeping = false;
+            fgpu_estimate_drop_kept(ctx);
+        }
+    } else if ((rc = fgpu_stage_pack(ctx, reads))) {
+        return rc;
+    }
+    if (blk.buf.p) {
+        codes = (const uint64_t*)blk.buf.p;
+        bad = codes + 2 * (blk.n_words + FGPU_PADW);
+        T = blk.T;
+        n_words = blk.n_words;
+        ctx->est_kept.push_back(blk);
+        ctx->est_keep_bytes += 4 * (blk.n_words + FGPU_PADW) * 8;
+    } else {
+        const BatchBufs& bb = *ctx->cur;
+        codes = (const uint64_t*)bb.codes.p;
+        bad = (const uint64_t*)bb.bad.p;
+        T = bb.T;
+        n_words = bb.n_words;
+    }
+    if (T)
+        FGPU_LAUNCH("est_sketch", k_est_sketch, fgpu_grid(n_words * 64, 256), 256, codes, bad, T, n_words, ctx->fd.k, ctx->est_planes, ctx->est_r_bits,
+                    (unsigned long long*)ctx->est_counts.p + 2 * EST_LEVELS);
     return fgpu_host_batch_done(ctx, reads);
+}
+
+int fgpu_estimate_keep(fgpu_ctx* ctx, uint64_t budget_bytes) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 4) { ctx->err = "estimate_keep outside estimate_begin/estimate_end"; return FGPU_ERR_STATE; }
+    if (ctx->est_batches) { ctx->err = "estimate_keep after the pass' first batch: a pass keeps all of its batches or none"; return FGPU_ERR_STATE; }
+    ctx->est_keep_asked = ctx->est_keeping = true;
+    ctx->est_keep_budget = budget_bytes;
+    ctx->est_keep_bytes = 0;
+    return FGPU_OK;
+}
+
+int fgpu_estimate_keep_state(fgpu_ctx* ctx, int* keeping, uint64_t* n_blocks, uint64_t* bytes) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (keeping) *keeping = ctx->est_keeping ? 1 : 0;
+    if (n_blocks) *n_blocks = ctx->est_kept.size();
+    if (bytes) *bytes = ctx->est_keep_bytes;
+    return FGPU_OK;
+}
+
+int fgpu_estimate_take_kept(fgpu_ctx* ctx, fgpu_packed* out, uint64_t cap, uint64_t* n_out) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase == 4) { ctx->err = "estimate_take_kept inside the pass: its blocks are handed out after estimate_end"; return FGPU_ERR_STATE; }
+    if (n_out) *n_out = ctx->est_kept.size();
+    if (ctx->est_keep_asked && !ctx->est_keeping) {
+        ctx->err = "estimate_take_kept: the pass stopped keeping at a batch that needed " + std::to_string(ctx->est_keep_stop_need) + " bytes with " +
+                   std::to_string(ctx->est_keep_stop_used) + " bytes held in " + std::to_string(ctx->est_keep_stop_blocks) + " blocks" +
+                   (ctx->est_keep_stop_nomem ? ": the device had no memory for its block (budget " : ": beyond the budget of ") +
+                   std::to_string(ctx->est_keep_budget) + (ctx->est_keep_stop_nomem ? " bytes)" : " bytes");
+        return FGPU_ERR_NOMEM;
+    }
+    if (ctx->est_kept.size() > cap || (!out && !ctx->est_kept.empty())) {
+        ctx->err = "estimate_take_kept: room for " + std::to_string(out ? cap : 0) + " blocks, the pass kept " + std::to_string(ctx->est_kept.size());
+        return FGPU_ERR_ARG;
+    }
+    for (size_t i = 0; i < ctx->est_kept.size(); i++) {
+        const PackedBlock& b = ctx->est_kept[i];
+        out[i].block_dev = b.buf.p;
+        out[i].nbytes = fgpu_packed_bytes(b.n_words);
+        out[i].T = b.T;
+        out[i].n_reads = b.n_reads;
+    }
+    ctx->est_kept.clear();
+    ctx->est_keep_bytes = 0;
+    ctx->est_keep_asked = ctx->est_keeping = false;
+    return FGPU_OK;
 }
 
 int fgpu_estimate_end(fgpu_ctx* ctx, fgpu_estimate* out) {

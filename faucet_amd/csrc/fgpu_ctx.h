@@ -271,6 +271,14 @@ struct fgpu_ctx {
     uint32_t* est_planes = nullptr;
     int est_r_bits = 0;
     DevBuf est_counts;               // empty[4], once[4], kmers
+    // fgpu_estimate_keep: the pass packs every non-empty batch into a block of its own and holds it (plain device allocations, not `owned`:
+    // fgpu_estimate_take_kept hands them to the caller).  est_keep_asked stays set once the pass has stopped keeping (budget, or no memory)
+    bool est_keep_asked = false, est_keeping = false;
+    uint64_t est_keep_budget = 0, est_keep_bytes = 0;   // 4 bits per stream position of the kept blocks: what a plain load keeps of a batch
+    uint64_t est_keep_stop_need = 0, est_keep_stop_used = 0, est_keep_stop_blocks = 0;   // the batch that ended the keeping: what it needed, what was held
+    bool est_keep_stop_nomem = false;                   // ... because the device had no memory for its block (else: beyond the budget)
+    uint64_t est_batches = 0;        // batches of the open pass so far (fgpu_estimate_keep comes before the first)
+    std::vector<PackedBlock> est_kept;   // in batch order
     // the filter-sliced pass: own bit positions [slice_lo, slice_lo + slice_n), its working state sized by the slice (load_common.h, Slice)
     uint64_t slice_lo = 0, slice_n = 0;
     uint32_t* slice_first = nullptr; // first-set time per OWN bit, 4 * slice_n bytes
@@ -289,6 +297,9 @@ struct fgpu_ctx {
     uint64_t scan_resident_base = 0; // fgpu_scan_resident_base: the scan's first batch within the resident batches (0 again at the next load pass)
     std::vector<PackedBlock*> packed;      // packed blocks of the current sliced pass (and free ones of earlier passes)
     DevBuf packed_digest;            // one word: the digest of the block being loaded, before it is compared with the block's trailer
+    // blocks adopted by fgpu_load_batch_packed (plain device allocations): those that are resident batches' codes / bad, held until the
+    // resident batches are forgotten, and those of batches that were not kept, released at the end of their pass
+    std::vector<void*> adopted, adopted_done;
 
     // pass 2 state: junction table (open addressing on the canonical k-mer)
     uint64_t jcap = 0;               // slots (power of two)
@@ -543,7 +554,13 @@ int fgpu_stage_pack_block(fgpu_ctx* ctx, const fgpu_reads* reads, PackedBlock** 
 int fgpu_packed_acquire(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, int state, const char* who, PackedBlock** out);
 int fgpu_packed_digest(fgpu_ctx* ctx, const PackedBlock* b, bool verify);
 int fgpu_host_batch_done(fgpu_ctx* ctx, const fgpu_reads* reads);
-int fgpu_stage_load(fgpu_ctx* ctx);
+// one batch of the plain pass from a packed stream (the batch in hand's planes, or a block's): everything but keeping it resident
+int fgpu_stage_load(fgpu_ctx* ctx, const void* codes, const void* bad, uint64_t T, uint64_t n_words);
+int fgpu_resident_keep(fgpu_ctx* ctx);                       // ... the batch in hand: copies of codes, bad, sure
+int fgpu_resident_adopt(fgpu_ctx* ctx, const PackedBlock& b);   // ... a block: it becomes the resident batch's codes / bad (fgpu_load_batch_packed)
+void fgpu_adopted_release(fgpu_ctx* ctx, std::vector<void*>* blocks);
+int fgpu_stage_pack_keep(fgpu_ctx* ctx, const fgpu_reads* reads, uint64_t budget_left, PackedBlock* out, bool* no_memory);
+void fgpu_estimate_drop_kept(fgpu_ctx* ctx);
 int fgpu_load_sweep(fgpu_ctx* ctx);
 int fgpu_stage_fixup(fgpu_ctx* ctx, const uint32_t* prefix);
 int fgpu_stage_presence(fgpu_ctx* ctx);

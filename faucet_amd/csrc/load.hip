@@ -530,6 +530,7 @@ void fgpu_touch_load() {
 
 // Forget the kept batches (their buffers are recycled by the next load pass).  keep_going: a new load pass starts.
 void fgpu_resident_reset(fgpu_ctx* ctx, bool keep_going) {
+    fgpu_adopted_release(ctx, &ctx->adopted);      // blocks that were resident batches' codes / bad (fgpu_load_batch_packed)
     ctx->resident_count = 0;
     ctx->resident_bytes = 0;
     ctx->resident_open = keep_going && ctx->resident_budget > 0;
@@ -551,9 +552,18 @@ int fgpu_resident_take(fgpu_ctx* ctx, const uint64_t (&parts)[5], bool budgeted,
     return FGPU_TAKE_OK;
 }
 
+// Adopted blocks go back once nothing queued can be reading them
+void fgpu_adopted_release(fgpu_ctx* ctx, std::vector<void*>* blocks) {
+    if (blocks->empty()) return;
+    (void)hipSetDevice(ctx->prm.device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    for (void* p : *blocks) (void)hipFree(p);
+    blocks->clear();
+}
+
 // Keep the batch's stream and its routed-to-bloo2 plane for the scan pass (data stays in HBM between the passes
 // instead of being recomputed by probing); stops silently once the budget is used: the scan then probes as usual.
-static int fgpu_resident_keep(fgpu_ctx* ctx) {
+int fgpu_resident_keep(fgpu_ctx* ctx) {
     if (!ctx->resident_open) return FGPU_OK;
     BatchBufs& bb = *ctx->cur;
     const uint64_t pb = (bb.n_words + FGPU_PADW) * 8;
@@ -575,6 +585,37 @@ static int fgpu_resident_keep(fgpu_ctx* ctx) {
     if (parts[3]) FGPU_HIP(hipMemcpyAsync(r->fail.p, bb.fail.p, parts[3], hipMemcpyDeviceToDevice, ctx->stream));
     ctx->resident_count++;
     ctx->resident_bytes += kept;
+    return FGPU_OK;
+}
+
+// The same for a batch that was loaded from a packed block the context has adopted (fgpu_load_batch_packed): the block IS the resident batch's
+// codes / bad, only `sure` is kept beside it; charged as a plain batch is (4 bits per stream position).  Beyond the budget, or without memory
+// for the plane, the batch is not kept -- the later ones then are not either, as above -- and its block goes back at the end of the pass.
+int fgpu_resident_adopt(fgpu_ctx* ctx, const PackedBlock& b) {
+    const uint64_t pb = (b.n_words + FGPU_PADW) * 8;
+    const uint64_t parts[5] = {0, 0, pb, 0, 0};
+    ResidentBatch* r = nullptr;
+    uint64_t kept;
+    if (ctx->resident_open && ctx->resident_bytes + 4 * pb <= ctx->resident_budget) {
+        if (fgpu_resident_take(ctx, parts, false, &r, &kept)) {
+            (void)hipGetLastError();
+            r = nullptr;
+        }
+    }
+    if (!r) {
+        ctx->resident_open = false;
+        ctx->adopted_done.push_back(b.buf.p);
+        return FGPU_OK;
+    }
+    FGPU_HIP(hipMemcpyAsync(r->sure.p, ctx->cur->sure.p, pb, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->adopted.push_back(b.buf.p);
+    r->T = b.T;
+    r->n_words = b.n_words;
+    r->tb = ctx->cur_tb;
+    r->packed_codes = b.buf.p;
+    r->packed_bad = (uint64_t*)b.buf.p + 2 * (b.n_words + FGPU_PADW);
+    ctx->resident_count++;
+    ctx->resident_bytes += 4 * pb;
     return FGPU_OK;
 }
 
@@ -609,28 +650,30 @@ int fgpu_epoch_after_batch(fgpu_ctx* ctx, uint64_t span) {
 }
 
 // One batch of the plain pass in the layout of f: mark, resolve, --mercy's runs, the carry by re-hashing
+// (codes, bad: the stream's planes of T positions -- the batch in hand's, or a packed block's; pending, sure, fail: the batch in hand's)
 template <int REC>
-static int load_batch(fgpu_ctx* ctx, const Filt<REC>& f, uint32_t tb, bool keep_fail) {
+static int load_batch(fgpu_ctx* ctx, const Filt<REC>& f, uint32_t tb, bool keep_fail, const uint64_t* codes, const uint64_t* bad, uint64_t T,
+                      uint64_t n_words) {
     BatchBufs& bb = *ctx->cur;
-    const uint64_t plane_stride = bb.n_words + FGPU_PADW;
-    const unsigned grid = fgpu_grid(bb.n_words * 64, 256);
+    const uint64_t plane_stride = n_words + FGPU_PADW;
+    const unsigned grid = fgpu_grid(n_words * 64, 256);
     static const int resolve_sm = getenv("FGPU_RESOLVE_SM") ? atoi(getenv("FGPU_RESOLVE_SM")) : 4096;
-    FGPU_LAUNCH("load_mark", k_load_mark<REC>, grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p, bb.T, bb.n_words, ctx->fd, f,
+    FGPU_LAUNCH("load_mark", k_load_mark<REC>, grid, 256, codes, bad, T, n_words, ctx->fd, f,
                 tb, (uint64_t*)bb.pending.p, plane_stride, (uint64_t*)bb.sure.p, ctx->counters);
     if (ctx->fd.n_hash <= MISS_PLANES && resolve_sm && !keep_fail) {
-        const unsigned rgrid = (unsigned)std::min<uint64_t>((bb.n_words + 255) / 256, (uint64_t)std::max(resolve_sm, 64));
-        FGPU_LAUNCH("load_resolve", k_load_resolve_sm<REC>, rgrid, 256, (const uint64_t*)bb.codes.p, bb.n_words, ctx->fd, f, tb,
+        const unsigned rgrid = (unsigned)std::min<uint64_t>((n_words + 255) / 256, (uint64_t)std::max(resolve_sm, 64));
+        FGPU_LAUNCH("load_resolve", k_load_resolve_sm<REC>, rgrid, 256, codes, n_words, ctx->fd, f, tb,
                     (const uint64_t*)bb.pending.p, plane_stride, (unsigned long long*)bb.sure.p, ctx->counters);
     } else {
-        FGPU_LAUNCH("load_resolve", k_load_resolve<REC>, grid, 256, (const uint64_t*)bb.codes.p, bb.T, bb.n_words, ctx->fd, f, tb,
+        FGPU_LAUNCH("load_resolve", k_load_resolve<REC>, grid, 256, codes, T, n_words, ctx->fd, f, tb,
                     (const uint64_t*)bb.pending.p, plane_stride, (uint64_t*)bb.sure.p, ctx->counters,
                     keep_fail ? (uint64_t*)bb.fail.p : (uint64_t*)nullptr);
     }
     if (ctx->prm.flags & FGPU_FLAG_MERCY)
-        FGPU_LAUNCH("load_mercy", k_load_mercy<REC>, fgpu_grid(bb.n_words, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p,
-                    bb.n_words, ctx->fd, f, tb, (const uint64_t*)bb.sure.p);
+        FGPU_LAUNCH("load_mercy", k_load_mercy<REC>, fgpu_grid(n_words, 256), 256, codes, bad,
+                    n_words, ctx->fd, f, tb, (const uint64_t*)bb.sure.p);
     if (ctx->carry_by_set)
-        FGPU_LAUNCH("carry_update", k_carry_set<REC>, grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p, bb.T, bb.n_words,
+        FGPU_LAUNCH("carry_update", k_carry_set<REC>, grid, 256, codes, bad, T, n_words,
                     ctx->fd, f, (const uint64_t*)bb.sure.p);
     return FGPU_OK;
 }
@@ -642,21 +685,21 @@ static int with_layout(fgpu_ctx* ctx, Fn&& fn) {
     return fn(Filt<0>{(uint32_t*)ctx->pair, ctx->first});
 }
 
-int fgpu_stage_load(fgpu_ctx* ctx) {
+int fgpu_stage_load(fgpu_ctx* ctx, const void* codes, const void* bad, uint64_t T, uint64_t n_words) {
     BatchBufs& bb = *ctx->cur;
-    if (bb.T == 0) return FGPU_OK;
-    const uint64_t plane_stride = bb.n_words + FGPU_PADW;   // plane 0: pending; planes 1..MISS_PLANES: bit i missing from the carry
+    if (T == 0) return FGPU_OK;
+    const uint64_t plane_stride = n_words + FGPU_PADW;   // plane 0: pending; planes 1..MISS_PLANES: bit i missing from the carry
     int rc = fgpu_ensure_b(ctx, &bb.pending, (MISS_PLANES + 1) * plane_stride * 8);
     if (rc) return rc;
-    if ((rc = fgpu_ensure_b(ctx, &bb.sure, (bb.n_words + FGPU_PADW) * 8))) return rc;
-    if ((rc = fgpu_util_count_segments(ctx, bb.bad.p, bb.n_words, ctx->fd.k))) return rc;
+    if ((rc = fgpu_ensure_b(ctx, &bb.sure, plane_stride * 8))) return rc;
+    if ((rc = fgpu_util_count_segments(ctx, bad, n_words, ctx->fd.k))) return rc;
     // Times are positions within the current EPOCH = the batches since the last sweep of first[] (k_carry_from_first).  A bit
     // that is still 0 in the carry has first[bit] == never or a time of this epoch, so the carry does not have to be brought up
     // to date after every batch: "set before t" = in the carry or first[bit] < t holds with any carry that is a subset of
     // bloo1 as of the epoch's start.  A lagging carry only sends more occurrences through the resolve kernel, and once the carry
     // holds a few coverages of the genome nearly every k-mer that will ever be in it already is: sweeps are made when an epoch
     // has grown to sweep_num/sweep_den of what the carry already covers (after batches 0, 1, 3, 7 ... of equal batches).
-    const uint64_t span = bb.n_words * 64;
+    const uint64_t span = n_words * 64;
     if ((rc = fgpu_epoch_before_batch(ctx, span))) return rc;
     if (ctx->shard_times && ctx->pass_positions + span >= 0xFFFFFFF0ULL) {
         ctx->err = "FGPU_LOAD_SHARD_TIMES: the pass exceeds 2^32 stream positions (FGPU_LOAD_SHARD_PLANES has no such limit)";
@@ -669,10 +712,9 @@ int fgpu_stage_load(fgpu_ctx* ctx) {
     if (keep_fail && (rc = fgpu_ensure_b(ctx, &bb.fail, MISS_PLANES * plane_stride * 8))) return rc;
     ctx->cur_tb = tb;
     ctx->pass_positions += span;
-    if ((rc = with_layout(ctx, [&](auto f) { return load_batch(ctx, f, tb, keep_fail); }))) return rc;
+    if ((rc = with_layout(ctx, [&](auto f) { return load_batch(ctx, f, tb, keep_fail, (const uint64_t*)codes, (const uint64_t*)bad, T, n_words); }))) return rc;
     // carry := carry | bits set during this batch -- or later: the carry may lag behind (see fgpu_load_sweep)
-    if ((rc = fgpu_epoch_after_batch(ctx, span))) return rc;
-    return fgpu_resident_keep(ctx);
+    return fgpu_epoch_after_batch(ctx, span);
 }
 
 // interleave the carried-in bloo1 with an empty bloo2 at the start of a load pass, split them again at its end

@@ -327,12 +327,10 @@ static int pack_run(fgpu_ctx* ctx, const PackSrc& src, uint64_t n, uint64_t n_wo
     return FGPU_OK;
 }
 
-int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads) {
+// the batch whose source is known into the planes of the batch in hand
+static int pack_into_cur(fgpu_ctx* ctx, const PackSrc& src, uint64_t n) {
     BatchBufs& bb = *ctx->cur;
-    const uint64_t n = reads->n_reads;
-    PackSrc src;
-    int rc = pack_source(ctx, reads, &src);
-    if (rc) return rc;
+    int rc;
     const uint64_t T = src.total + n;
     bb.T = T;
     bb.n_words = (T + 63) / 64;
@@ -348,6 +346,13 @@ int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if ((rc = fgpu_ensure_b(ctx, &bb.codes, (2 * (bb.n_words + FGPU_PADW)) * 8))) return rc;
     if ((rc = fgpu_ensure_b(ctx, &bb.bad, (bb.n_words + FGPU_PADW) * 8))) return rc;
     return pack_run(ctx, src, n, bb.n_words, bb.codes.p, bb.bad.p, &bb.readflag);
+}
+
+int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads) {
+    PackSrc src;
+    int rc = pack_source(ctx, reads, &src);
+    if (rc) return rc;
+    return pack_into_cur(ctx, src, reads->n_reads);
 }
 
 // ---- packed blocks of a sliced pass (fgpu_load_slice_pack / _expect / _batch_packed) -------------------------------------------------------
@@ -448,5 +453,42 @@ int fgpu_stage_pack_block(fgpu_ctx* ctx, const fgpu_reads* reads, PackedBlock** 
         return rc;
     }
     *out = b;
+    return FGPU_OK;
+}
+
+// fgpu_estimate_batch of a pass that keeps (fgpu_estimate_keep): a batch with reads packed straight into a block of its own -- a plain device
+// allocation of exactly the block's size, the layout, padding, trailer and digest of fgpu_stage_pack_block -- which the caller holds from then
+// on (out->buf.p).  A block that would take more than budget_left (4 bits per stream position: what a plain load keeps of a batch), or for
+// which the device has no memory (*no_memory), is not made: the batch goes into the planes of the batch in hand as fgpu_stage_pack puts it
+// there, out->buf.p = nullptr, and out->T / n_words still say what it would have been.
+int fgpu_stage_pack_keep(fgpu_ctx* ctx, const fgpu_reads* reads, uint64_t budget_left, PackedBlock* out, bool* no_memory) {
+    const uint64_t n = reads->n_reads;
+    *out = PackedBlock();
+    *no_memory = false;
+    PackSrc src;
+    int rc = pack_source(ctx, reads, &src);
+    if (rc) return rc;
+    out->T = src.total + n;
+    out->n_words = (out->T + 63) / 64;
+    out->n_reads = n;
+    if (4 * (out->n_words + FGPU_PADW) * 8 > budget_left) return pack_into_cur(ctx, src, n);
+    const uint64_t bytes = fgpu_packed_bytes(out->n_words);
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *no_memory = true;
+        return pack_into_cur(ctx, src, n);
+    }
+    out->buf.p = p;
+    out->buf.bytes = bytes;
+    out->state = 1;
+    uint64_t* words = (uint64_t*)p;
+    if ((rc = pack_run(ctx, src, n, out->n_words, words, words + 2 * (out->n_words + FGPU_PADW), &ctx->cur->readflag)) ||
+        (rc = fgpu_packed_digest(ctx, out, false))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(p);
+        out->buf = DevBuf();
+        return rc;
+    }
     return FGPU_OK;
 }

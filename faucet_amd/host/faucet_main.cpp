@@ -12,7 +12,8 @@
 // device from scanInputRead's per-read lists (fgpu_scan_short_pairs, fgpu_scan_long_pairs) and come back as bytes.
 // Not in the reference: --estimate.  -estimated_kmers and -singletons, which the reference has its users find with a separate k-mer counter,
 // may then be left out; a pass 0 over -read_load_file sketches the reads on the device (fgpu_estimate_*) and fills in whichever is absent;
-// with -gpus N every rank sketches its read shard and the sketches are merged (ShardedRun::estimate).
+// with -gpus N every rank sketches its read shard and the sketches are merged (ShardedRun::estimate).  Where -read_load_file can be read only
+// once (a pipe) pass 0 keeps the batches it packs on the device and pass 1 loads from them (fgpu_estimate_keep, fgpu_load_batch_packed).
 #include <errno.h>
 #include <fcntl.h>
 #include <stdint.h>
@@ -49,6 +50,11 @@
 #pragma weak fgpu_estimate_begin
 #pragma weak fgpu_estimate_batch
 #pragma weak fgpu_estimate_end
+// ... and so are the four that let pass 0 keep its packed reads for pass 1: without them --estimate needs a -read_load_file it can read twice
+#pragma weak fgpu_estimate_keep
+#pragma weak fgpu_estimate_keep_state
+#pragma weak fgpu_estimate_take_kept
+#pragma weak fgpu_load_batch_packed
 
 using faucet_host::ReadSource;
 using faucet_host::TextSource;
@@ -679,7 +685,26 @@ int feed_batches(fgpu_ctx* ctx, BatchSource& src, const char* progress, double* 
 // (ShardedRun::estimate): the same counts, hence the same two lines and the same run, as from the first device alone -- which is what
 // FAUCET_ESTIMATE_SHARDS=0 (A/B timing, tests), a library without fgpu_group_estimate_end and -batch_reads (refused by open_shards, behind
 // pass 0) still get.  0, or the exit code of a failure
-int estimate_one_device(const Options& o, const fgpu_params& prm, PhaseClock& clk, fgpu_estimate* est) {
+// The packed reads pass 0 kept for pass 1 (fgpu_estimate_take_kept): device blocks that belong to this program until a context adopts them
+// (fgpu_load_batch_packed).  What is left when a run ends early goes back through whichever context is at hand.
+struct KeptReads {
+    bool asked = false;               // pass 0 is to keep its batches ...
+    bool must = false;                // ... and the run cannot go on without them: -read_load_file cannot be read again
+    bool have = false;                // it did, and `blocks` are all of -read_load_file
+    uint64_t budget = 0, bytes = 0;   // the budget the pass had, what its blocks are charged
+    std::vector<fgpu_packed> blocks;
+    size_t next = 0;                  // blocks before this one have been adopted
+    void release(fgpu_ctx* ctx) {
+        for (; ctx && next < blocks.size(); next++) (void)fgpu_device_free(ctx, blocks[next].block_dev);
+        blocks.clear();
+        next = 0;
+        have = false;
+    }
+};
+
+const int kStoppedKeeping = 1000;     // estimate_one_device's batch callback: not a status of the library
+
+int estimate_one_device(const Options& o, const fgpu_params& prm, PhaseClock& clk, fgpu_estimate* est, KeptReads* kept) {
     Run placeholder;
     if (int rc = open_one_device(o, prm, &placeholder)) return rc;
     fgpu_ctx* ctx = placeholder.one;
@@ -687,18 +712,53 @@ int estimate_one_device(const Options& o, const fgpu_params& prm, PhaseClock& cl
     BatchSource src(o, o.read_load_file);
     if (!src.is_open()) { fprintf(stderr, "cannot open %s\n", o.read_load_file.c_str()); return 2; }
     CHECK(fgpu_estimate_begin(ctx, o.estimate_bits));
+    bool keeping = false;
+    if (kept->asked) {      // what a context sets aside for resident batches: what pass 0 keeps, the run's context can hold
+        CHECK(fgpu_load_fixup_state(ctx, nullptr, &kept->budget));
+        if (const char* cap = getenv("FAUCET_ESTIMATE_KEEP_BYTES")) kept->budget = std::min<uint64_t>(kept->budget, strtoull(cap, nullptr, 10));   // (tests)
+        CHECK(fgpu_estimate_keep(ctx, kept->budget));
+        keeping = true;
+    }
     double batch_ms = 0;
     const char* failed = "fgpu_estimate_batch";
-    if (int rc = feed_batches(ctx, src, nullptr, &batch_ms, &failed, [&](const fgpu_reads* r) { return fgpu_estimate_batch(ctx, r); })) {
-        fprintf(stderr, "%s failed (%d): %s\n", failed, rc, fgpu_last_error(ctx));
+    const int frc = feed_batches(ctx, src, nullptr, &batch_ms, &failed, [&](const fgpu_reads* r) -> int {
+        if (int rc = fgpu_estimate_batch(ctx, r)) return rc;
+        if (!keeping) return FGPU_OK;
+        int still = 0;
+        uint64_t bytes = 0;
+        if (int rc = fgpu_estimate_keep_state(ctx, &still, nullptr, &bytes)) { failed = "fgpu_estimate_keep_state"; return rc; }
+        if (still) { kept->bytes = bytes; return FGPU_OK; }
+        keeping = false;
+        if (kept->must) return kStoppedKeeping;
+        fprintf(stderr, "note: --estimate: pass 0 stopped keeping its packed reads (%llu bytes kept, budget %llu bytes): pass 1 reads %s again\n",
+                (unsigned long long)kept->bytes, (unsigned long long)kept->budget, o.read_load_file.c_str());
+        return FGPU_OK;
+    });
+    if (frc == kStoppedKeeping) {      // (the source and the placeholder go on the way out: a writer at the other end of a pipe is not left waiting)
+        fprintf(stderr, "--estimate: the packed reads of %s do not fit the device memory set aside for them (%llu bytes kept, budget %llu bytes) and a pipe "
+                        "cannot be read again for pass 1: give -estimated_kmers and -singletons\n",
+                o.read_load_file.c_str(), (unsigned long long)kept->bytes, (unsigned long long)kept->budget);
+        return 2;
+    }
+    if (frc) {
+        fprintf(stderr, "%s failed (%d): %s\n", failed, frc, fgpu_last_error(ctx));
         return 2;
     }
     const int rc = fgpu_estimate_end(ctx, est);
     if (rc == FGPU_ERR_CAPACITY) { fprintf(stderr, "--estimate: the sketch of 2^%d cells per level is too full for these reads: raise -estimate_bits\n", (int)est->r_bits); return 2; }
     if (rc != FGPU_OK) { fprintf(stderr, "fgpu_estimate_end failed (%d): %s\n", rc, fgpu_last_error(ctx)); return 2; }
+    if (keeping) {
+        uint64_t n = 0;
+        CHECK(fgpu_estimate_keep_state(ctx, nullptr, &n, &kept->bytes));
+        kept->blocks.resize((size_t)n);
+        CHECK(fgpu_estimate_take_kept(ctx, kept->blocks.data(), n, &n));
+        kept->have = true;
+    }
     if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_estimate_batch calls; %llu k-mers sketched, 2^%d cells per level, estimates from level %d on\n", batch_ms,
                         (unsigned long long)est->kmers, (int)est->r_bits, (int)est->level);
-    clk.mark("pass 0 (read + estimate)");
+    if (clk.on && kept->have) fprintf(stderr, "[cli]   %llu bytes of packed reads kept in %llu blocks (budget %llu bytes)\n", (unsigned long long)kept->bytes,
+                                      (unsigned long long)kept->blocks.size(), (unsigned long long)kept->budget);
+    clk.mark(kept->have ? "pass 0 (read + estimate, reads kept)" : "pass 0 (read + estimate)");
     return 0;
 }
 
@@ -722,14 +782,25 @@ int estimate_shards(const Options& o, const fgpu_params& prm, PhaseClock& clk, f
     return 0;
 }
 
-int estimate_missing(Options& o, PhaseClock& clk) {
-    // decided before any device call: the file is read once more by pass 1, and the library has to have the pass
+int estimate_missing(Options& o, PhaseClock& clk, KeptReads* kept) {
+    // decided before any device call: the file is read once more by pass 1 -- unless pass 0 can keep what it packs --, and the library has to have the pass
     struct stat st;
-    if (stat(o.read_load_file.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) {
+    const bool can_keep = fgpu_estimate_keep && fgpu_estimate_keep_state && fgpu_estimate_take_kept && fgpu_load_batch_packed;
+    const bool found = stat(o.read_load_file.c_str(), &st) == 0, regular = found && S_ISREG(st.st_mode);
+    if (!found || (!regular && !can_keep)) {
         fprintf(stderr, "--estimate: %s is not a regular file: pass 0 reads -read_load_file once more than the run does (give -estimated_kmers and -singletons for a pipe)\n",
                 o.read_load_file.c_str());
         return 1;
     }
+    if (!regular && o.gpus > 1 && !o.from_bloom) {      // open_shards would say so with pass 0 behind it and the pipe consumed
+        fprintf(stderr, "%s is not a regular file: with -gpus the read shards are byte ranges of their input (pipes need -gpus 1)\n", o.read_load_file.c_str());
+        return 2;
+    }
+    // Pass 1 from what pass 0 packed: where the input cannot be read twice, and on request (FAUCET_ESTIMATE_KEEP=1: measurements) for files.
+    // One device only; with -bloom_file no pass 1 follows and a pipe is simply sketched once.
+    const char* keep_env = getenv("FAUCET_ESTIMATE_KEEP");
+    kept->must = !regular && !o.from_bloom;
+    kept->asked = can_keep && !o.from_bloom && o.gpus == 1 && (!regular || (keep_env && keep_env[0] == '1'));
     if (!fgpu_estimate_begin || !fgpu_estimate_batch || !fgpu_estimate_end) {
         fprintf(stderr, "--estimate: the library this program is linked against lacks the entry points of the estimate pass "
                         "(fgpu_estimate_begin, fgpu_estimate_batch, fgpu_estimate_end)\n");
@@ -743,10 +814,10 @@ int estimate_missing(Options& o, PhaseClock& clk) {
     prm.n_hash = 1;
     prm.tai = 128;
     const char* by_shards_env = getenv("FAUCET_ESTIMATE_SHARDS");
-    const bool by_shards = o.gpus > 1 && !o.from_junctions && !o.batch_reads && ShardedRun::estimate_linked() && !(by_shards_env && by_shards_env[0] == '0');
+    const bool by_shards = o.gpus > 1 && regular && !o.from_junctions && !o.batch_reads && ShardedRun::estimate_linked() && !(by_shards_env && by_shards_env[0] == '0');
     fgpu_estimate est;
     memset(&est, 0, sizeof(est));
-    if (int rc = by_shards ? estimate_shards(o, prm, clk, &est) : estimate_one_device(o, prm, clk, &est)) return rc;
+    if (int rc = by_shards ? estimate_shards(o, prm, clk, &est) : estimate_one_device(o, prm, clk, &est, kept)) return rc;
     const long long f0 = llround(est.f0), f1 = std::max(llround(est.f1), 1LL);
     printf("Estimated distinct k-mers (F0): %lld\n", f0);
     printf("Estimated singletons (f1): %lld\n", f1);
@@ -773,6 +844,29 @@ int load_one_device(fgpu_ctx* ctx, BatchSource& src, PhaseClock& clk, faucet_hos
     return 0;
 }
 
+// ... from the blocks pass 0 kept: the same pass, a block where load_one_device has a batch of the file.  Blocks the context has not adopted
+// when the pass fails are still the caller's (KeptReads::release)
+int load_kept(fgpu_ctx* ctx, KeptReads& kept, PhaseClock& clk, faucet_host::ShardLoadResult* out) {
+    CHECK(fgpu_load_begin(ctx, 0));
+    uint64_t reads = 0;
+    for (; kept.next < kept.blocks.size(); kept.next++) {
+        const auto t_batch = std::chrono::steady_clock::now();
+        CHECK(fgpu_load_batch_packed(ctx, &kept.blocks[kept.next]));
+        clk.batch_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_batch).count();
+        reads += kept.blocks[kept.next].n_reads;
+        fprintf(stdout, "\rreads consumed: %lld", (long long)reads);
+        fflush(stdout);
+    }
+    const auto t_end = std::chrono::steady_clock::now();
+    CHECK(fgpu_load_end(ctx, &out->stats));
+    if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_load_batch_packed calls, %.2f ms in fgpu_load_end\n", clk.batch_ms,
+                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_end).count());
+    clk.mark("pass 1 (load from kept reads)");
+    CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO1, &out->w1));
+    CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO2, &out->w2));
+    return 0;
+}
+
 int load_shards(const Options& o, ShardedRun& run, PhaseClock& clk, faucet_host::ShardLoadResult* out) {
     if (int rc = run.load(o.read_load_file, out)) { fprintf(stderr, "load pass failed (%d): %s\n", rc, run.error().c_str()); return 2; }
     clk.mark(out->slices ? "pass 1 (shards, filter slices)" : out->fixup ? "pass 1 (shards, fix-up protocol)" : "pass 1 (shards, presence protocol)");
@@ -781,9 +875,9 @@ int load_shards(const Options& o, ShardedRun& run, PhaseClock& clk, faucet_host:
 }
 
 // ---- pass 1 (load_two_filters, utils/Bloom.cpp:267-350), and bloo2 on its way into <prefix>.bloom
-int load_from_reads(const Options& o, const Run& run, PhaseClock& clk, BloomFile& bloom) {
-    std::unique_ptr<BatchSource> src;      // (one device; the shards open their byte ranges themselves)
-    if (!run.shards) {
+int load_from_reads(const Options& o, const Run& run, PhaseClock& clk, BloomFile& bloom, KeptReads& kept) {
+    std::unique_ptr<BatchSource> src;      // (one device; the shards open their byte ranges themselves; kept reads need no source)
+    if (!run.shards && !kept.have) {
         src.reset(new BatchSource(o, o.read_load_file));
         if (!src->is_open()) { fprintf(stderr, "cannot open %s\n", o.read_load_file.c_str()); return 2; }   // the reference silently reads nothing
     }
@@ -791,7 +885,7 @@ int load_from_reads(const Options& o, const Run& run, PhaseClock& clk, BloomFile
     time(&start);
     printf("Weights before load: %f, %f \n", 0.0f, 0.0f);
     faucet_host::ShardLoadResult lo;
-    if (int rc = run.shards ? load_shards(o, *run.shards, clk, &lo) : load_one_device(run.one, *src, clk, &lo)) return rc;
+    if (int rc = run.shards ? load_shards(o, *run.shards, clk, &lo) : kept.have ? load_kept(run.one, kept, clk, &lo) : load_one_device(run.one, *src, clk, &lo)) return rc;
     printf("\n");
     printf("Weights after load: %f, %f \n", lo.w1, lo.w2);
     printf("Reads processed: %llu\n", (unsigned long long)lo.stats.reads_processed);
@@ -917,11 +1011,12 @@ int scan_and_write(const Options& o, const Run& run, PairFilter& short_pf, PairF
 int main(int argc, char** argv) {
     PhaseClock clk;
     Options o;
+    KeptReads kept;
     if (handle_arguments(argc, argv, o) == 1) return 1;
     if (o.estimate && !(o.est_kmers_flag && o.est_sing_flag)) {     // pass 0, ahead of everything the two numbers decide (and of the lines that print them)
         if (o.k < 1 || o.k > 31) { fprintf(stderr, "k must be in 1..31 on this build\n"); return 1; }
         choose_chunk_bytes(o);
-        if (int rc = estimate_missing(o, clk)) return rc;
+        if (int rc = estimate_missing(o, clk, &kept)) return rc;
     }
     print_settings(o);
     if (o.k < 1 || o.k > 31) { fprintf(stderr, "k must be in 1..31 on this build\n"); return 1; }
@@ -933,7 +1028,10 @@ int main(int argc, char** argv) {
     if (int rc = sharded ? open_shards(o, prm, clk.on, &run) : open_one_device(o, prm, &run)) return rc;
     clk.mark(sharded ? "arguments, sizing, contexts" : "arguments, sizing, fgpu_create");
     BloomFile bloom(o.file_prefix, o.tai);
-    if (int rc = o.from_bloom ? load_bloom_file(o, run, bloom) : load_from_reads(o, run, clk, bloom)) return rc;
+    if (int rc = o.from_bloom ? load_bloom_file(o, run, bloom) : load_from_reads(o, run, clk, bloom, kept)) {
+        kept.release(run.first());
+        return rc;
+    }
     PairFilter short_pf, long_pf;
     create_pair_filters(o, &short_pf, &long_pf);
     if (o.just_load) return bloom.complete() ? 0 : 2;

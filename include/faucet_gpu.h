@@ -365,6 +365,46 @@ int fgpu_load_slice_expect(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, fgpu_pac
  * mercy pass' "probe owed"; the batch is the pass' next one (fgpu_load_slice_plane counts it), reads_processed grows by n_reads. */
 int fgpu_load_slice_batch_packed(fgpu_ctx* ctx, const fgpu_packed* b);
 
+/* ---- pass 0 keeps what it packs, the plain pass loads from it: one reading of the stream serves both -----------------------------------------
+ * Pass 0 reads, splits and packs the whole stream only to sketch it, and pass 1 then does all of that again -- which a stream that can be
+ * read once (a pipe) does not allow at all.  A pass that KEEPS packs every non-empty batch straight into a packed block of its own -- the
+ * layout, padding, trailer and digest of fgpu_load_slice_pack, 3 bits per stream position -- and sketches it there: no second copy.  The
+ * blocks are plain device allocations that belong to whoever holds them: the pass, then the caller that takes them, then the context that
+ * loads them.  They outlive the context that made them, so the placeholder context of pass 0 (tai = 128) can be destroyed before the run's
+ * context is made:
+ *
+ *     fgpu_estimate_begin(c0, r_bits);  fgpu_estimate_keep(c0, budget);  fgpu_estimate_batch(c0, b) ...;  fgpu_estimate_end(c0, &e);
+ *     fgpu_estimate_take_kept(c0, blocks, cap, &n);  fgpu_destroy(c0);
+ *     fgpu_create(sized from e, &c1);  fgpu_load_begin(c1, 0);  fgpu_load_batch_packed(c1, &blocks[i]) ...;  fgpu_load_end(c1, &stats);
+ *
+ * _keep: between fgpu_estimate_begin and the pass' first batch (FGPU_ERR_STATE otherwise).  A block is charged to budget_bytes as 4 bits per
+ * position, 4 * (ceil(T / 64) + 8) * 8 bytes: what a plain load keeps of a batch (codes, bad, sure), so that whatever pass 0 keeps a context
+ * with the same budget (fgpu_load_fixup_state) can keep resident.  A batch that does not fit the budget, or for which the device has no
+ * memory, does not fail the pass: every block kept so far is released, the pass stops keeping and goes on sketching as one without _keep.
+ * The sketch is the same to the last counter either way.
+ * _keep_state: *keeping = 1 while every non-empty batch so far is held; *n_blocks, *bytes: the blocks held and what they are charged.  All
+ * three may be NULL.  Host state: does not wait for the device.  Valid inside the pass and after its end, until the blocks are taken.
+ * _take_kept: after fgpu_estimate_end (whether FGPU_OK or FGPU_ERR_CAPACITY; FGPU_ERR_STATE inside a pass): the blocks in batch order, one per
+ * non-empty batch, with T, n_reads and nbytes.  Ownership passes to the caller: fgpu_load_batch_packed hands a block on, fgpu_device_free of
+ * any context on the same device releases it.  *n_out (may be NULL) = the number of blocks, also when cap is too small (FGPU_ERR_ARG, nothing
+ * taken).  FGPU_ERR_NOMEM, with a message naming the numbers, if the pass stopped keeping.  Blocks that are never taken are released by the
+ * next fgpu_estimate_begin or by fgpu_destroy, with the stream waited for first. */
+int fgpu_estimate_keep(fgpu_ctx* ctx, uint64_t budget_bytes);
+int fgpu_estimate_keep_state(fgpu_ctx* ctx, int* keeping, uint64_t* n_blocks, uint64_t* bytes);
+int fgpu_estimate_take_kept(fgpu_ctx* ctx, fgpu_packed* out, uint64_t cap, uint64_t* n_out);
+/* One batch of the PLAIN pass from a packed block: fgpu_load_batch of the same reads behind its packing -- segment count, epochs, both
+ * layouts, --mercy, the carry -- with reads_processed growing by n_reads and unambiguous_reads, kmers, to_bloo2 as for those reads.  In a
+ * pass opened by fgpu_load_begin(ctx, 0) or with FGPU_LOAD_KEEP_CARRY; may be mixed with fgpu_load_batch.  On FGPU_OK the context ADOPTS the
+ * block (on an error the caller still owns it): it becomes the resident batch's codes / bad, with only the `sure` plane allocated beside it,
+ * until the next load pass begins or the context is destroyed.  Beyond the resident budget, or with FGPU_FLAG_NO_RESIDENT, the batch is
+ * loaded all the same, the pass stops keeping batches as after an fgpu_load_batch that did not fit, and the block is released no later than
+ * fgpu_load_end.  The block's digest and T are recomputed and compared with its trailer as for a block from fgpu_load_slice_expect: a mismatch
+ * is FGPU_ERR_ARG at the pass' next synchronising call, fgpu_load_end at the latest.  A description with a NULL block must be all zeros and
+ * does nothing.  FGPU_ERR_STATE: outside a plain pass (a sliced pass included), or in the pass of a read shard (FGPU_LOAD_SHARD_TIMES /
+ * FGPU_LOAD_SHARD_PLANES).  FGPU_ERR_ARG: null arguments; nbytes != 24 * (ceil(T / 64) + 8) + 16, T beyond max_batch_bases, n_reads > T or
+ * no reads. */
+int fgpu_load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* b);
+
 /* filters: raw bit arrays, tai/8 bytes, exactly the .bloom file body (utils/Bloom.cpp:571-587) */
 int fgpu_bloom_download(fgpu_ctx* ctx, int which, uint8_t* host_out, uint64_t nbytes);
 /* The same copy, started now and finished by fgpu_bloom_download_wait: it runs on its own copy stream behind the work
