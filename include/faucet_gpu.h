@@ -349,7 +349,20 @@ int fgpu_diag_slice_mercy(fgpu_ctx* ctx, uint64_t out[6]);
  * FGPU_ERR_STATE: outside a sliced pass or after its commit; _batch_packed of a block that is not of this pass' _pack / _expect, or has been
  * loaded already, or while a mercy pass owes its latest batch the probe.  FGPU_ERR_ARG: null arguments; _expect with n_reads > T, T > 0 without
  * reads or T beyond max_batch_bases; a description whose T / nbytes / n_reads are not the block's.  FGPU_ERR_NOMEM: the batch does not fit the
- * resident budget (fgpu_load_fixup_state; the message names the numbers) or the device has no memory for it. */
+ * resident budget (fgpu_load_fixup_state; the message names the numbers) or the device has no memory for it.
+ *
+ * THE FORMAT (restated in plain Python by tests/pack_ref.py, which the tests hold the packing kernels to byte for byte).  Words are 64 bits,
+ * little-endian; W = n_words + 8.
+ *   stream     Read i starts at position S_i = (bytes of the reads before it) + i and is followed by ONE separator position; T = bytes + reads.
+ *   tokens     A read is cut into its maximal runs of good bytes -- upper-case A C G T, nothing else -- and of other bytes.  The runs are laid
+ *              out in REVERSE run order, the bytes inside a run in their own order: ascending stream position is the order in which the
+ *              reference works through a read's pieces (getUnambiguousReads hands them out last first).
+ *   codes      words 0 .. 2W-1.  Position p: word p / 32, bits 62 - 2 * (p % 32) and the one above (the first position of a word in its two most
+ *              significant bits).  A good byte c has code (c >> 1) & 3 (A0 C1 T2 G3); every other position, the tail and the padding have 0.
+ *   bad plane  words 2W .. 3W-1.  Position p: bit p % 64 of word p / 64.  1 for separators, for bytes that are not good, for every position
+ *              from T to the end of word n_words - 1, and for all 64 bits of the 8 padding words.
+ *   trailer    word 3W: the digest = sum mod 2^64 over i = 0 .. 3W-1 of mix(word[i] ^ ((i + 1) * 0x9E3779B97F4A7C15)), with mix the finaliser of
+ *              splitmix64: x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31.  Word 3W+1: T. */
 typedef struct {
     void*    block_dev;   /* the block on the context's device; NULL for a batch without reads (nbytes = T = 0) */
     uint64_t nbytes;      /* 24 * (ceil(T / 64) + 8) + 16 */
