@@ -28,7 +28,7 @@ class Params(C.Structure):
                 ("max_batch_bases", C.c_uint64), ("stream", C.c_void_p), ("walk_window_span", C.c_uint64)]
 
 
-LOAD_KEEP_CARRY, LOAD_SHARD_TIMES, LOAD_SHARD_PLANES = 1, 2, 4
+LOAD_KEEP_CARRY, LOAD_SHARD_TIMES, LOAD_SHARD_PLANES, LOAD_KEEP_READS = 1, 2, 4, 8
 
 
 class Reads(C.Structure):
@@ -39,6 +39,11 @@ class Reads(C.Structure):
 class Packed(C.Structure):
     """fgpu_packed: one packed batch of a sliced pass as a device block"""
     _fields_ = [("block_dev", C.c_void_p), ("nbytes", C.c_uint64), ("T", C.c_uint64), ("n_reads", C.c_uint64)]
+
+
+class KeptReads(C.Structure):
+    """fgpu_kept_reads: the read offsets of one packed batch (device), its read count, the longest read of its pass"""
+    _fields_ = [("offsets_dev", C.c_void_p), ("n_reads", C.c_uint64), ("max_read_len", C.c_uint64)]
 
 
 class LoadStats(C.Structure):
@@ -99,6 +104,11 @@ SIGNATURES = {
     "fgpu_estimate_keep": (C.c_int, [_vp, _u64]),
     "fgpu_estimate_keep_state": (C.c_int, [_vp, _P(C.c_int), _P(_u64), _P(_u64)]),
     "fgpu_estimate_take_kept": (C.c_int, [_vp, _P(Packed), _u64, _P(_u64)]),
+    "fgpu_estimate_keep_reads": (C.c_int, [_vp]),
+    "fgpu_estimate_take_kept_reads": (C.c_int, [_vp, _P(KeptReads), _u64, _P(_u64)]),
+    "fgpu_load_batch_packed_reads": (C.c_int, [_vp, _P(Packed), _P(KeptReads)]),
+    "fgpu_scan_kept_state": (C.c_int, [_vp, _P(C.c_int), _P(_u64), _P(_u64), _P(_u64)]),
+    "fgpu_scan_batch_kept": (C.c_int, [_vp, _u64, _P(_u64)]),
     "fgpu_load_begin": (C.c_int, [_vp, C.c_int]),
     "fgpu_load_batch": (C.c_int, [_vp, _P(Reads)]),
     "fgpu_load_batch_packed": (C.c_int, [_vp, _P(Packed)]),

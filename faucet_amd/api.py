@@ -264,10 +264,32 @@ class Context:
             blocks.append(pk)
         return blocks
 
+    def estimate_keep_reads(self):
+        """after estimate_keep, before the first batch: the pass also keeps every batch's read offsets beside its block (charged to the budget)"""
+        self._c(self.lib.fgpu_estimate_keep_reads(self.h))
+
+    def estimate_take_kept_reads(self) -> list:
+        """after estimate_take_kept: the kept blocks' reads in block order (L.KeptReads); the caller's, like the blocks, until
+        load_batch_packed_reads hands them on"""
+        n = C.c_uint64(0)
+        rc = self.lib.fgpu_estimate_take_kept_reads(self.h, None, 0, C.byref(n))
+        if rc == L.OK or not n.value:
+            self._c(rc)
+            return []
+        out = (L.KeptReads * int(n.value))()
+        self._c(self.lib.fgpu_estimate_take_kept_reads(self.h, out, int(n.value), C.byref(n)))
+        reads = []
+        for i in range(int(n.value)):
+            kr = L.KeptReads()
+            C.memmove(C.byref(kr), C.byref(out[i]), C.sizeof(L.KeptReads))
+            reads.append(kr)
+        return reads
+
     # pass 1
-    def load_begin(self, keep_carry=False, shard_times=False, shard_planes=False):
+    def load_begin(self, keep_carry=False, shard_times=False, shard_planes=False, keep_reads=False):
+        """keep_reads: every resident batch also keeps its read offsets, for a scan of the kept batches (scan_batch_kept)"""
         self._c(self.lib.fgpu_load_begin(self.h, (L.LOAD_KEEP_CARRY if keep_carry else 0) | (L.LOAD_SHARD_TIMES if shard_times else 0) |
-                                         (L.LOAD_SHARD_PLANES if shard_planes else 0)))
+                                         (L.LOAD_SHARD_PLANES if shard_planes else 0) | (L.LOAD_KEEP_READS if keep_reads else 0)))
 
     def load_fixup(self, prefix_dev_ptr) -> dict:
         """multi-GPU: re-evaluate what this shard's own pass kept out of bloo2 against the OR of the lower ranks' bloo1"""
@@ -359,6 +381,10 @@ class Context:
         """one batch of the plain pass from a packed block (estimate_take_kept): what load_batch does behind its packing; the context adopts the block"""
         self._c(self.lib.fgpu_load_batch_packed(self.h, C.byref(pk)))
 
+    def load_batch_packed_reads(self, pk: "L.Packed", kr: "L.KeptReads"):
+        """load_batch_packed in a pass begun with keep_reads, plus the adoption of the block's read offsets (estimate_take_kept_reads)"""
+        self._c(self.lib.fgpu_load_batch_packed_reads(self.h, C.byref(pk), C.byref(kr)))
+
     def presence_batch(self, batch: ReadBatch):
         s = batch.c_struct()
         self._c(self.lib.fgpu_presence_batch(self.h, C.byref(s)))
@@ -417,6 +443,18 @@ class Context:
     def scan_batch(self, batch: ReadBatch):
         s = batch.c_struct()
         self._c(self.lib.fgpu_scan_batch(self.h, C.byref(s)))
+
+    def scan_kept_state(self) -> dict:
+        """after a load pass: did it keep every non-empty batch with its reads (load_begin(keep_reads=True))?  Host state, never waits"""
+        c, nb, nr, by = C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._c(self.lib.fgpu_scan_kept_state(self.h, C.byref(c), C.byref(nb), C.byref(nr), C.byref(by)))
+        return {"complete": bool(c.value), "n_batches": int(nb.value), "n_reads": int(nr.value), "bytes": int(by.value)}
+
+    def scan_batch_kept(self, i: int) -> int:
+        """scan_batch of the reads kept batch i was loaded from, without their text; returns the batch's number of reads"""
+        n = C.c_uint64(0)
+        self._c(self.lib.fgpu_scan_batch_kept(self.h, int(i), C.byref(n)))
+        return int(n.value)
 
     def scan_prepare(self, batch: ReadBatch):
         s = batch.c_struct()

@@ -184,6 +184,8 @@ static bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 static void journal_recycle(fgpu_ctx* ctx);
 static int journal_add(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads);
 static int scan_replay(fgpu_ctx* ctx);
+static int load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk, const fgpu_kept_reads* kr);
+static int scan_batch_from(fgpu_ctx* ctx, const fgpu_reads* reads, const ResidentBatch* kept);
 
 // ---- pass 1: what the plain pass' entry points (below) and the sliced pass' (load_slices.hip) share -----------------------------------------
 int fgpu_check_reads(fgpu_ctx* ctx, const fgpu_reads* r) {
@@ -234,6 +236,8 @@ int fgpu_load_pass_end(fgpu_ctx* ctx, fgpu_load_stats* stats) {
     ctx->load_mark_pending = ctx->counters_host->mark_pending;
     ctx->load_stats.unambiguous_reads = ctx->counters_host->segments;
     if (stats) *stats = ctx->load_stats;
+    // FGPU_LOAD_KEEP_READS: the longest read the pass packed (blocks brought theirs: fgpu_resident_adopt) -- a scan of the kept batches packs nothing
+    if (ctx->keep_reads) ctx->kept_max_read_len = std::max<uint64_t>(ctx->kept_max_read_len, ctx->counters_host->max_read_len);
     ctx->fixup_ready = (ctx->shard_times || ctx->shard_planes) && ctx->pass_empty_carry &&
                        ctx->resident_count == ctx->pass_batches && !(ctx->prm.flags & FGPU_FLAG_MERCY);
     return FGPU_OK;
@@ -468,6 +472,10 @@ int fgpu_synchronize(fgpu_ctx* ctx) {
 int fgpu_load_begin(fgpu_ctx* ctx, int keep_carry) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 0) { ctx->err = "load_begin while another pass is open"; return FGPU_ERR_STATE; }
+    if ((keep_carry & FGPU_LOAD_KEEP_READS) && (keep_carry & (FGPU_LOAD_SHARD_TIMES | FGPU_LOAD_SHARD_PLANES))) {
+        ctx->err = "load_begin: FGPU_LOAD_KEEP_READS in the pass of a read shard (FGPU_LOAD_SHARD_TIMES / FGPU_LOAD_SHARD_PLANES): read shards keep batches of their own";
+        return FGPU_ERR_STATE;
+    }
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     if (int rc = fgpu_bloom_download_wait(ctx)) return rc;   // a download still in flight reads the filters this pass rewrites
     // Where the pass keeps its state (load_common.h, Filt): the interleaved pair + first[], or -- FGPU_LOAD_LAYOUT=records: measured in round 5, a
@@ -518,10 +526,12 @@ int fgpu_load_begin(fgpu_ctx* ctx, int keep_carry) {
     ctx->scan_resident_base = 0;
     ctx->pass_positions = ctx->pass_batches = 0;
     ctx->pass_empty_carry = !(keep_carry & FGPU_LOAD_KEEP_CARRY);
+    const bool keep_reads = (keep_carry & FGPU_LOAD_KEEP_READS) != 0;
     keep_carry &= FGPU_LOAD_KEEP_CARRY;
     fgpu_load_pass_policy(ctx);
     if (!ctx->rec_layout) FGPU_HIP(hipMemsetAsync(ctx->first, 0xFF, ctx->prm.tai * 4, ctx->stream));   // (records: k_rec_init, fgpu_load_pair_begin)
     fgpu_resident_reset(ctx, true);
+    ctx->keep_reads = keep_reads;
     if (!keep_carry) FGPU_HIP(hipMemsetAsync(ctx->bloo1, 0, ctx->bloom_bytes, ctx->stream));
     FGPU_HIP(hipMemsetAsync(ctx->bloo2, 0, ctx->bloom_bytes, ctx->stream));
     int rc = fgpu_load_pair_begin(ctx);
@@ -549,7 +559,21 @@ int fgpu_load_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
 // One batch of the plain pass from a packed block of another pass or context (fgpu_estimate_take_kept): the block's planes in place of the
 // batch in hand's, the block adopted as the resident batch's codes / bad.  A block's content is checked against its trailer like one that
 // came from a peer (error flag 64 at the pass' next synchronising call).
-int fgpu_load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk) {
+int fgpu_load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk) { return load_batch_packed(ctx, pk, nullptr); }
+
+// ... with the batch's read offsets, adopted beside the block for a scan of the kept batch (FGPU_LOAD_KEEP_READS, fgpu_scan_batch_kept)
+int fgpu_load_batch_packed_reads(fgpu_ctx* ctx, const fgpu_packed* pk, const fgpu_kept_reads* kr) {
+    if (!ctx || !pk || !kr) return FGPU_ERR_ARG;
+    if (ctx->phase == 1 && !ctx->keep_reads) { ctx->err = "load_batch_packed_reads in a pass opened without FGPU_LOAD_KEEP_READS"; return FGPU_ERR_STATE; }
+    if (kr->n_reads != pk->n_reads || (pk->block_dev != nullptr) != (kr->offsets_dev != nullptr)) {
+        ctx->err = "load_batch_packed_reads: the reads described are not the block's (n_reads differ, or offsets without a block)";
+        return FGPU_ERR_ARG;
+    }
+    return load_batch_packed(ctx, pk, pk->block_dev ? kr : nullptr);
+}
+
+}  // extern "C"
+static int load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk, const fgpu_kept_reads* kr) {
     if (!ctx || !pk) return FGPU_ERR_ARG;
     if (ctx->phase != 1) { ctx->err = "load_batch_packed outside load_begin/load_end"; return FGPU_ERR_STATE; }
     if (ctx->shard_times || ctx->shard_planes) {
@@ -578,7 +602,7 @@ int fgpu_load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk) {
         (void)hipStreamSynchronize(ctx->stream);   // the caller still owns the block and may free it: nothing queued reads it any more
         return rc;
     }
-    if ((rc = fgpu_resident_adopt(ctx, b))) {
+    if ((rc = fgpu_resident_adopt(ctx, b, kr))) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
@@ -586,6 +610,7 @@ int fgpu_load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk) {
     ctx->load_stats.reads_processed += b.n_reads;
     return FGPU_OK;
 }
+extern "C" {
 
 int fgpu_presence_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (!ctx) return FGPU_ERR_ARG;
@@ -890,7 +915,27 @@ static void note_walked(fgpu_ctx* ctx, BatchBufs* b) {
 }
 
 // one_range: the batch is prepared ahead of its turn -- nothing walks it beside its own pure stage, so its back half is not cut into ranges
-static int scan_pure_into(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads, bool one_range = false) {
+// The batch's stream comes into `b` from the text (reads: packed) or from a batch the load pass kept (kept: its planes copied, nothing packed
+// or compared -- fgpu_scan_batch_kept); everything behind that is common.
+static int scan_take_kept(fgpu_ctx* ctx, BatchBufs* b, const ResidentBatch* kept) {
+    b->T = kept->T; b->n_words = kept->n_words; b->n_reads = kept->n_reads;
+    b->d_offs = (const uint64_t*)kept->offs_p();
+    const uint64_t cb = 2 * (b->n_words + FGPU_PADW) * 8, bbytes = (b->n_words + FGPU_PADW) * 8;
+    int rc;
+    if ((rc = fgpu_ensure_b(ctx, &b->codes, cb)) || (rc = fgpu_ensure_b(ctx, &b->bad, bbytes))) return rc;
+    FGPU_HIP(hipMemcpyAsync(b->codes.p, kept->codes_p(), cb, hipMemcpyDeviceToDevice, ctx->stream));
+    FGPU_HIP(hipMemcpyAsync(b->bad.p, kept->bad_p(), bbytes, hipMemcpyDeviceToDevice, ctx->stream));
+    // the longest read bounds how far a piece reaches (max_piece_span): the text path's packing refills the counter, here the load pass' value
+    // seeds it, host copy and device copy (as the replay does from journal_max_read_len), before the first pure stage that needs it
+    if (ctx->counters_host->max_read_len < ctx->kept_max_read_len) {
+        ctx->kept_seed = ctx->kept_max_read_len;
+        ctx->counters_host->max_read_len = ctx->kept_seed;
+        FGPU_HIP(hipMemcpyAsync(&ctx->counters->max_read_len, &ctx->kept_seed, 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return FGPU_OK;
+}
+
+static int scan_pure_into(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads, bool one_range = false, const ResidentBatch* kept = nullptr) {
     if (b->stops_pending) {   // the buffers still hold the visit planes of an earlier batch: bring its lists to the host first
         int hrc = fgpu_scan_harvest(ctx, b);
         if (hrc) return hrc;      // (FGPU_INTERNAL_REPLAY: that batch's walk went wrong; the caller replays and comes back)
@@ -904,16 +949,18 @@ static int scan_pure_into(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads, 
     }
     const double t_b = fgpu_host_now();
     ctx->host_ms[0] += t_b - t_a;
-    int rc = fgpu_stage_pack(ctx, reads);
+    int rc = kept ? scan_take_kept(ctx, b, kept) : fgpu_stage_pack(ctx, reads);
     ctx->host_ms[1] += fgpu_host_now() - t_b;
     if (!rc) rc = journal_add(ctx, b, reads);
     uint64_t n_pieces = 0;
+    ctx->scan_take_kept = kept;
     if (!rc) rc = fgpu_stage_scan_pure(ctx, &n_pieces, one_range);   // ends with the batch's only synchronisation (piece count)
+    ctx->scan_take_kept = nullptr;
     if (!rc) ctx->journal_max_read_len = std::max<uint64_t>(ctx->journal_max_read_len, ctx->counters_host->max_read_len);
     if (!rc) rc = check_errors(ctx);
-    if (!rc) ctx->scan_stats.reads_processed += reads->n_reads;
+    if (!rc) ctx->scan_stats.reads_processed += b->n_reads;
     if (!rc && b->pure_done) FGPU_HIP(hipEventRecord(b->pure_done, ctx->stream));
-    if (!rc) rc = fgpu_host_batch_done(ctx, reads);
+    if (!rc && reads) rc = fgpu_host_batch_done(ctx, reads);
     return rc;
 }
 
@@ -1090,6 +1137,39 @@ static int scan_replay_once(fgpu_ctx* ctx) {
     return rc;
 }
 
+// every non-empty batch of the last load pass is resident with its read offsets (fgpu_scan_kept_state)
+static bool kept_complete(const fgpu_ctx* ctx) {
+    if (!ctx->keep_reads || ctx->phase == 1 || ctx->phase == 3 || ctx->resident_count != ctx->pass_batches) return false;
+    for (uint64_t i = 0; i < ctx->resident_count; i++)
+        if (!ctx->resident[i]->n_reads) return false;      // (a block adopted without its offsets: fgpu_load_batch_packed in such a pass)
+    return true;
+}
+
+int fgpu_scan_kept_state(fgpu_ctx* ctx, int* complete, uint64_t* n_batches, uint64_t* n_reads, uint64_t* bytes) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (complete) *complete = kept_complete(ctx) ? 1 : 0;
+    if (n_batches) *n_batches = ctx->resident_count;
+    if (n_reads) *n_reads = ctx->kept_reads_total;
+    if (bytes) *bytes = ctx->resident_bytes;
+    return FGPU_OK;
+}
+
+int fgpu_scan_batch_kept(fgpu_ctx* ctx, uint64_t i, uint64_t* n_reads_out) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 2) { ctx->err = "scan_batch_kept outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
+    if (!ctx->prepared.empty()) { ctx->err = "scan_batch_kept while prepared batches are waiting: call fgpu_scan_walk_prepared first"; return FGPU_ERR_STATE; }
+    if (ctx->hint_in_table) { ctx->err = "the junction table holds a preview (fgpu_scan_import_hint): import the real table before walking"; return FGPU_ERR_STATE; }
+    if (!kept_complete(ctx)) {
+        ctx->err = "scan_batch_kept: the last load pass did not keep every batch with its reads (FGPU_LOAD_KEEP_READS, all batches inside the resident budget of " +
+                   std::to_string(ctx->resident_budget) + " bytes; " + std::to_string(ctx->resident_count) + " of " + std::to_string(ctx->pass_batches) + " batches are resident)";
+        return FGPU_ERR_STATE;
+    }
+    if (i >= ctx->resident_count) { ctx->err = "scan_batch_kept: no such batch (empty batches keep nothing)"; return FGPU_ERR_ARG; }
+    const ResidentBatch* kept = ctx->resident[i];
+    if (n_reads_out) *n_reads_out = kept->n_reads;
+    return scan_batch_from(ctx, nullptr, kept);
+}
+
 int fgpu_scan_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 2) { ctx->err = "scan_batch outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
@@ -1097,16 +1177,23 @@ int fgpu_scan_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (ctx->hint_in_table) { ctx->err = "the junction table holds a preview (fgpu_scan_import_hint): import the real table before walking"; return FGPU_ERR_STATE; }
     int rc = fgpu_check_reads(ctx, reads);
     if (rc) return rc;
+    return scan_batch_from(ctx, reads, nullptr);
+}
+
+}  // extern "C"
+// pure stage + ordered walk of one batch, from its text (reads) or from a kept batch
+static int scan_batch_from(fgpu_ctx* ctx, const fgpu_reads* reads, const ResidentBatch* kept) {
+    int rc;
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     if (ctx->lazy_failed && (rc = scan_replay(ctx))) return rc;      // an earlier walk met a preview it could not repair: scan again, eagerly
     BatchBufs* b = acquire_batch(ctx);
-    rc = scan_pure_into(ctx, b, reads);          // main stream; overlaps the previous batch's walk on the walk stream
+    rc = scan_pure_into(ctx, b, reads, false, kept);          // main stream; overlaps the previous batch's walk on the walk stream
     if (rc == FGPU_INTERNAL_REPLAY) {            // noticed while the buffers' previous lists were fetched: replay, then this batch from the start
         ctx->cur = &ctx->bb_default;
         ctx->pool.insert(ctx->pool.begin(), b);
         if ((rc = scan_replay(ctx))) return rc;
         b = acquire_batch(ctx);
-        rc = scan_pure_into(ctx, b, reads);
+        rc = scan_pure_into(ctx, b, reads, false, kept);
     }
     if (!rc && ctx->lazy_failed) {
         // noticed at this batch's own synchronisation: the batch is in the journal (prepared lazily); the replay scans it with the others
@@ -1128,6 +1215,7 @@ int fgpu_scan_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     ctx->pool.push_back(b);
     return rc;
 }
+extern "C" {
 
 int fgpu_scan_prepare(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (!ctx) return FGPU_ERR_ARG;

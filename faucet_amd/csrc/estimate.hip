@@ -119,6 +119,14 @@ void fgpu_estimate_drop_kept(fgpu_ctx* ctx) {
         for (PackedBlock& b : ctx->est_kept) (void)hipFree(b.buf.p);
         ctx->est_kept.clear();
     }
+    if (!ctx->est_kept_reads.empty() || !ctx->est_taken_reads.empty()) {      // the offsets kept beside them (fgpu_estimate_keep_reads), taken or not
+        (void)hipSetDevice(ctx->prm.device);
+        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+        for (fgpu_kept_reads& r : ctx->est_kept_reads) (void)hipFree(r.offsets_dev);
+        for (fgpu_kept_reads& r : ctx->est_taken_reads) (void)hipFree(r.offsets_dev);
+        ctx->est_kept_reads.clear();
+        ctx->est_taken_reads.clear();
+    }
     ctx->est_keep_bytes = 0;
 }
 
@@ -140,6 +148,7 @@ int fgpu_estimate_begin(fgpu_ctx* ctx, int32_t r_bits) {
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     fgpu_estimate_drop_kept(ctx);        // blocks of an earlier pass that nobody took
     ctx->est_keep_asked = ctx->est_keeping = false;
+    ctx->est_keep_reads = false;
     ctx->est_batches = 0;
     // 2 bits x 4 levels x 2^r_bits cells = 2^r_bits bytes, for the duration of the pass
     const uint64_t bytes = 1ULL << r_bits;
@@ -177,9 +186,22 @@ int fgpu_estimate_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     PackedBlock blk;
     if (ctx->est_keeping && reads->n_reads) {
         bool no_memory;
-        if ((rc = fgpu_stage_pack_keep(ctx, reads, ctx->est_keep_budget - ctx->est_keep_bytes, &blk, &no_memory))) return rc;
+        // fgpu_estimate_keep_reads: the batch's (n_reads + 1) offsets are charged with its block, and kept in an allocation of their own
+        const uint64_t ob = ctx->est_keep_reads ? (reads->n_reads + 1) * 8 : 0, left = ctx->est_keep_budget - ctx->est_keep_bytes;
+        void* offs = nullptr;
+        if (ob && ob <= left && hipMalloc(&offs, ob) != hipSuccess) { (void)hipGetLastError(); offs = nullptr; }
+        if ((rc = fgpu_stage_pack_keep(ctx, reads, ob && !offs ? 0 : left - ob, &blk, &no_memory))) { if (offs) (void)hipFree(offs); return rc; }
+        if (ob && !offs && !blk.buf.p) no_memory = ob <= left;
+        if (offs && blk.buf.p) {
+            FGPU_HIP(hipMemcpyAsync(offs, ctx->cur->d_offs, ob, hipMemcpyDeviceToDevice, ctx->stream));
+            fgpu_kept_reads kr = {offs, reads->n_reads, 0};
+            ctx->est_kept_reads.push_back(kr);
+            ctx->est_keep_bytes += ob;
+        } else if (offs) {
+            (void)hipFree(offs);
+        }
         if (!blk.buf.p) {   // the batch is not kept, so nothing is: the pass goes on as one that was never asked to keep
-            ctx->est_keep_stop_need = 4 * (blk.n_words + FGPU_PADW) * 8;
+            ctx->est_keep_stop_need = 4 * (blk.n_words + FGPU_PADW) * 8 + ob;
             ctx->est_keep_stop_used = ctx->est_keep_bytes;
             ctx->est_keep_stop_blocks = ctx->est_kept.size();
             ctx->est_keep_stop_nomem = no_memory;
@@ -219,6 +241,41 @@ int fgpu_estimate_keep(fgpu_ctx* ctx, uint64_t budget_bytes) {
     return FGPU_OK;
 }
 
+int fgpu_estimate_keep_reads(fgpu_ctx* ctx) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 4 || !ctx->est_keep_asked) { ctx->err = "estimate_keep_reads comes after estimate_keep, inside its pass"; return FGPU_ERR_STATE; }
+    if (ctx->est_batches) { ctx->err = "estimate_keep_reads after the pass' first batch: a pass keeps all of its batches' reads or none"; return FGPU_ERR_STATE; }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    FGPU_HIP(hipMemsetAsync(&ctx->counters->max_read_len, 0, 8, ctx->stream));      // the longest read of THIS pass (k_pack_fix: a running maximum)
+    ctx->est_keep_reads = true;
+    return FGPU_OK;
+}
+
+int fgpu_estimate_take_kept_reads(fgpu_ctx* ctx, fgpu_kept_reads* out, uint64_t cap, uint64_t* n_out) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase == 4 || !ctx->est_kept.empty() || !ctx->est_kept_reads.empty()) {
+        ctx->err = "estimate_take_kept_reads comes after estimate_end and estimate_take_kept of the same pass";
+        return FGPU_ERR_STATE;
+    }
+    if (n_out) *n_out = ctx->est_taken_reads.size();
+    if (!ctx->est_keep_reads) { ctx->err = "estimate_take_kept_reads: the pass did not keep its reads (fgpu_estimate_keep_reads)"; return FGPU_ERR_STATE; }
+    if (ctx->est_taken_reads.size() > cap || (!out && !ctx->est_taken_reads.empty())) {
+        ctx->err = "estimate_take_kept_reads: room for " + std::to_string(out ? cap : 0) + " entries, the pass kept " + std::to_string(ctx->est_taken_reads.size());
+        return FGPU_ERR_ARG;
+    }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    unsigned long long longest = 0;      // (fgpu_estimate_end has waited for the pass' last kernels)
+    FGPU_HIP(hipMemcpyAsync(&longest, &ctx->counters->max_read_len, 8, hipMemcpyDeviceToHost, ctx->stream));
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    for (size_t i = 0; i < ctx->est_taken_reads.size(); i++) {
+        out[i] = ctx->est_taken_reads[i];
+        out[i].max_read_len = longest;
+    }
+    ctx->est_taken_reads.clear();
+    ctx->est_keep_reads = false;
+    return FGPU_OK;
+}
+
 int fgpu_estimate_keep_state(fgpu_ctx* ctx, int* keeping, uint64_t* n_blocks, uint64_t* bytes) {
     if (!ctx) return FGPU_ERR_ARG;
     if (keeping) *keeping = ctx->est_keeping ? 1 : 0;
@@ -250,6 +307,7 @@ int fgpu_estimate_take_kept(fgpu_ctx* ctx, fgpu_packed* out, uint64_t cap, uint6
         out[i].n_reads = b.n_reads;
     }
     ctx->est_kept.clear();
+    ctx->est_taken_reads.swap(ctx->est_kept_reads);      // (the blocks are the caller's: their offsets wait for fgpu_estimate_take_kept_reads)
     ctx->est_keep_bytes = 0;
     ctx->est_keep_asked = ctx->est_keeping = false;
     return FGPU_OK;

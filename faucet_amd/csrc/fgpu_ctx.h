@@ -97,6 +97,12 @@ struct ResidentBatch {
     void *packed_codes = nullptr, *packed_bad = nullptr;
     const void* codes_p() const { return packed_codes ? packed_codes : codes.p; }
     const void* bad_p() const { return packed_bad ? packed_bad : bad.p; }
+    // FGPU_LOAD_KEEP_READS: the (n_reads + 1) read offsets of the batch, for a scan without the text (fgpu_scan_batch_kept) -- a copy, or
+    // the allocation that came with an adopted block (fgpu_load_batch_packed_reads; released with the block); n_reads = 0: not kept
+    DevBuf offs;
+    void* packed_offs = nullptr;
+    uint64_t n_reads = 0;
+    const void* offs_p() const { return packed_offs ? packed_offs : offs.p; }
 };
 
 // A packed batch of a sliced pass as ONE device buffer (fgpu_packed): codes plane (2 x stride words), bad plane (stride words), stride =
@@ -279,6 +285,9 @@ struct fgpu_ctx {
     bool est_keep_stop_nomem = false;                   // ... because the device had no memory for its block (else: beyond the budget)
     uint64_t est_batches = 0;        // batches of the open pass so far (fgpu_estimate_keep comes before the first)
     std::vector<PackedBlock> est_kept;   // in batch order
+    // fgpu_estimate_keep_reads: every kept block's read offsets beside it (plain device allocations, handed out by fgpu_estimate_take_kept_reads)
+    bool est_keep_reads = false;
+    std::vector<fgpu_kept_reads> est_kept_reads, est_taken_reads;   // of the blocks held / of the blocks taken, until they are taken too
     // the filter-sliced pass: own bit positions [slice_lo, slice_lo + slice_n), its working state sized by the slice (load_common.h, Slice)
     uint64_t slice_lo = 0, slice_n = 0;
     uint32_t* slice_first = nullptr; // first-set time per OWN bit, 4 * slice_n bytes
@@ -293,6 +302,11 @@ struct fgpu_ctx {
     uint64_t resident_count = 0;     // entries of `resident` that hold the current load pass
     uint64_t resident_bytes = 0, resident_budget = 0;
     bool resident_open = false;      // the current load pass is still keeping its batches
+    // FGPU_LOAD_KEEP_READS (cleared with the resident batches, fgpu_resident_reset): the pass keeps its batches' read offsets; reads kept so far;
+    // the longest read of the pass (DevCounters::max_read_len at fgpu_load_end, or what came with adopted blocks): seeds a kept scan's max_piece_span
+    bool keep_reads = false;
+    uint64_t kept_reads_total = 0, kept_max_read_len = 0, kept_seed = 0;
+    const ResidentBatch* scan_take_kept = nullptr;   // fgpu_scan_batch_kept: the pure stage in hand takes this batch's sure plane without comparing
     uint64_t scan_batch_index = 0;   // scan batch i pairs with resident[scan_resident_base + i]
     uint64_t scan_resident_base = 0; // fgpu_scan_resident_base: the scan's first batch within the resident batches (0 again at the next load pass)
     std::vector<PackedBlock*> packed;      // packed blocks of the current sliced pass (and free ones of earlier passes)
@@ -557,7 +571,7 @@ int fgpu_host_batch_done(fgpu_ctx* ctx, const fgpu_reads* reads);
 // one batch of the plain pass from a packed stream (the batch in hand's planes, or a block's): everything but keeping it resident
 int fgpu_stage_load(fgpu_ctx* ctx, const void* codes, const void* bad, uint64_t T, uint64_t n_words);
 int fgpu_resident_keep(fgpu_ctx* ctx);                       // ... the batch in hand: copies of codes, bad, sure
-int fgpu_resident_adopt(fgpu_ctx* ctx, const PackedBlock& b);   // ... a block: it becomes the resident batch's codes / bad (fgpu_load_batch_packed)
+int fgpu_resident_adopt(fgpu_ctx* ctx, const PackedBlock& b, const fgpu_kept_reads* reads = nullptr);   // ... a block: it becomes the resident batch's codes / bad (fgpu_load_batch_packed)
 void fgpu_adopted_release(fgpu_ctx* ctx, std::vector<void*>* blocks);
 int fgpu_stage_pack_keep(fgpu_ctx* ctx, const fgpu_reads* reads, uint64_t budget_left, PackedBlock* out, bool* no_memory);
 void fgpu_estimate_drop_kept(fgpu_ctx* ctx);

@@ -534,6 +534,8 @@ void fgpu_resident_reset(fgpu_ctx* ctx, bool keep_going) {
     ctx->resident_count = 0;
     ctx->resident_bytes = 0;
     ctx->resident_open = keep_going && ctx->resident_budget > 0;
+    ctx->keep_reads = false;                       // (fgpu_load_begin sets it again for a pass with FGPU_LOAD_KEEP_READS)
+    ctx->kept_reads_total = ctx->kept_max_read_len = 0;
 }
 
 // The next resident slot, its buffers sized: parts = bytes of {codes, bad, sure, fail, miss} to keep (0: not kept).  The budget arithmetic of
@@ -547,7 +549,8 @@ int fgpu_resident_take(fgpu_ctx* ctx, const uint64_t (&parts)[5], bool budgeted,
     DevBuf* const bufs[5] = {&r.codes, &r.bad, &r.sure, &r.fail, &r.miss};
     for (int i = 0; i < 5; i++)
         if (parts[i] && fgpu_ensure_b(ctx, bufs[i], parts[i])) return FGPU_TAKE_NO_MEMORY;
-    r.packed_codes = r.packed_bad = nullptr;
+    r.packed_codes = r.packed_bad = r.packed_offs = nullptr;
+    r.n_reads = 0;
     *out = &r;
     return FGPU_TAKE_OK;
 }
@@ -571,10 +574,20 @@ int fgpu_resident_keep(fgpu_ctx* ctx) {
     const uint64_t parts[5] = {2 * pb, pb, pb, ctx->shard_planes ? MISS_PLANES * pb : 0, 0};
     ResidentBatch* r;
     uint64_t kept;
-    if (int why = fgpu_resident_take(ctx, parts, true, &r, &kept)) {
+    // FGPU_LOAD_KEEP_READS: the batch's read offsets beside its planes, charged with them -- a batch that fits only without them is not kept
+    const uint64_t ob = ctx->keep_reads ? (bb.n_reads + 1) * 8 : 0;
+    int why = ob && ctx->resident_bytes + parts[0] + parts[1] + parts[2] + parts[3] + ob > ctx->resident_budget ? (int)FGPU_TAKE_NO_BUDGET : fgpu_resident_take(ctx, parts, true, &r, &kept);
+    if (!why && ob && fgpu_ensure_b(ctx, &r->offs, ob)) why = FGPU_TAKE_NO_MEMORY;
+    if (why) {
         if (why == FGPU_TAKE_NO_MEMORY) (void)hipGetLastError();   // out of memory: do without
         ctx->resident_open = false;   // batches pair by index: once one is missing, later ones would not line up
         return FGPU_OK;
+    }
+    if (ob) {      // (the offsets are the caller's, or a staging set's: valid while this call queues its work)
+        FGPU_HIP(hipMemcpyAsync(r->offs.p, bb.d_offs, ob, hipMemcpyDeviceToDevice, ctx->stream));
+        r->n_reads = bb.n_reads;
+        ctx->kept_reads_total += bb.n_reads;
+        kept += ob;
     }
     r->T = bb.T;
     r->n_words = bb.n_words;
@@ -591,12 +604,14 @@ int fgpu_resident_keep(fgpu_ctx* ctx) {
 // The same for a batch that was loaded from a packed block the context has adopted (fgpu_load_batch_packed): the block IS the resident batch's
 // codes / bad, only `sure` is kept beside it; charged as a plain batch is (4 bits per stream position).  Beyond the budget, or without memory
 // for the plane, the batch is not kept -- the later ones then are not either, as above -- and its block goes back at the end of the pass.
-int fgpu_resident_adopt(fgpu_ctx* ctx, const PackedBlock& b) {
+int fgpu_resident_adopt(fgpu_ctx* ctx, const PackedBlock& b, const fgpu_kept_reads* reads) {
     const uint64_t pb = (b.n_words + FGPU_PADW) * 8;
     const uint64_t parts[5] = {0, 0, pb, 0, 0};
     ResidentBatch* r = nullptr;
     uint64_t kept;
-    if (ctx->resident_open && ctx->resident_bytes + 4 * pb <= ctx->resident_budget) {
+    const uint64_t ob = reads ? (reads->n_reads + 1) * 8 : 0;      // fgpu_load_batch_packed_reads: the offsets are adopted (and charged) with the block
+    if (reads) ctx->kept_max_read_len = std::max<uint64_t>(ctx->kept_max_read_len, reads->max_read_len);
+    if (ctx->resident_open && ctx->resident_bytes + 4 * pb + ob <= ctx->resident_budget) {
         if (fgpu_resident_take(ctx, parts, false, &r, &kept)) {
             (void)hipGetLastError();
             r = nullptr;
@@ -605,17 +620,24 @@ int fgpu_resident_adopt(fgpu_ctx* ctx, const PackedBlock& b) {
     if (!r) {
         ctx->resident_open = false;
         ctx->adopted_done.push_back(b.buf.p);
+        if (reads) ctx->adopted_done.push_back(reads->offsets_dev);
         return FGPU_OK;
     }
     FGPU_HIP(hipMemcpyAsync(r->sure.p, ctx->cur->sure.p, pb, hipMemcpyDeviceToDevice, ctx->stream));
     ctx->adopted.push_back(b.buf.p);
+    if (reads) {
+        ctx->adopted.push_back(reads->offsets_dev);
+        r->packed_offs = reads->offsets_dev;
+        r->n_reads = reads->n_reads;
+        ctx->kept_reads_total += reads->n_reads;
+    }
     r->T = b.T;
     r->n_words = b.n_words;
     r->tb = ctx->cur_tb;
     r->packed_codes = b.buf.p;
     r->packed_bad = (uint64_t*)b.buf.p + 2 * (b.n_words + FGPU_PADW);
     ctx->resident_count++;
-    ctx->resident_bytes += 4 * pb;
+    ctx->resident_bytes += 4 * pb + ob;
     return FGPU_OK;
 }
 

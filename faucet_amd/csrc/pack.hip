@@ -471,6 +471,7 @@ int fgpu_stage_pack_keep(fgpu_ctx* ctx, const fgpu_reads* reads, uint64_t budget
     out->T = src.total + n;
     out->n_words = (out->T + 63) / 64;
     out->n_reads = n;
+    ctx->cur->d_offs = src.d_offs;      // (fgpu_estimate_keep_reads copies them, inside the call that packs)
     if (4 * (out->n_words + FGPU_PADW) * 8 > budget_left) return pack_into_cur(ctx, src, n);
     const uint64_t bytes = fgpu_packed_bytes(out->n_words);
     void* p = nullptr;

@@ -646,12 +646,16 @@ int fgpu_stage_scan_pure(fgpu_ctx* ctx, uint64_t* n_pieces, bool one_range) {
     const ResidentBatch* kept = kept_index < ctx->resident_count ? ctx->resident[kept_index] : nullptr;
     ctx->scan_batch_index++;
     if (kept && (kept->T != bb.T || kept->n_words != bb.n_words)) kept = nullptr;
+    // fgpu_scan_batch_kept: the stream in hand IS that kept batch's (whatever its index): its sure plane is taken without the comparison
+    const bool taken = ctx->scan_take_kept != nullptr;
+    if (taken) kept = ctx->scan_take_kept;
     if (kept) {
         if ((rc = fgpu_ensure_b(ctx, &bb.same, 64))) return rc;
         FGPU_HIP(hipMemsetAsync(bb.same.p, 0x01, 4, ctx->stream));
         const uint64_t ncw = 2 * bb.n_words;   // 32 bases per code word
-        FGPU_LAUNCH("scan_same", k_scan_same, fgpu_grid(ncw, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)kept->codes_p(), ncw,
-                    (const uint64_t*)bb.bad.p, (const uint64_t*)kept->bad_p(), bb.n_words, (uint32_t*)bb.same.p);
+        if (!taken)
+            FGPU_LAUNCH("scan_same", k_scan_same, fgpu_grid(ncw, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)kept->codes_p(), ncw,
+                        (const uint64_t*)bb.bad.p, (const uint64_t*)kept->bad_p(), bb.n_words, (uint32_t*)bb.same.p);
     }
     FGPU_LAUNCH("scan_valid", k_scan_valid, grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p, bb.T, bb.n_words, ctx->fd,
                 (const uint32_t*)ctx->bloo2, kept ? (const uint64_t*)kept->sure.p : (const uint64_t*)nullptr,

@@ -14,6 +14,9 @@
 // may then be left out; a pass 0 over -read_load_file sketches the reads on the device (fgpu_estimate_*) and fills in whichever is absent;
 // with -gpus N every rank sketches its read shard and the sketches are merged (ShardedRun::estimate).  Where -read_load_file can be read only
 // once (a pipe) pass 0 keeps the batches it packs on the device and pass 1 loads from them (fgpu_estimate_keep, fgpu_load_batch_packed).
+// Not in the reference either: --scan_kept.  Pass 1 keeps, beside the packed batches it keeps anyway, their read offsets (FGPU_LOAD_KEEP_READS),
+// and pass 2 scans those batches (fgpu_scan_batch_kept) instead of reading, splitting and packing the input a second time: -read_scan_file may
+// be left out, and one reading of the input -- with --estimate on a pipe: of a stream -- serves the whole run.  One device only.
 #include <errno.h>
 #include <fcntl.h>
 #include <stdint.h>
@@ -55,6 +58,11 @@
 #pragma weak fgpu_estimate_keep_state
 #pragma weak fgpu_estimate_take_kept
 #pragma weak fgpu_load_batch_packed
+// ... and the three through which pass 0's blocks carry their reads, for --scan_kept behind --estimate on a pipe (scan_pass.h refers to the two of
+// the kept scan itself)
+#pragma weak fgpu_estimate_keep_reads
+#pragma weak fgpu_estimate_take_kept_reads
+#pragma weak fgpu_load_batch_packed_reads
 
 using faucet_host::ReadSource;
 using faucet_host::TextSource;
@@ -83,6 +91,7 @@ struct Options {   // globals of src/Faucet.h:14-53
     std::string transport = "copy";   // not a reference flag: how the shards' bitmaps and tables travel: copy (device-to-device copies) | rccl
     bool estimate = false;            // not a reference flag: --estimate, -estimated_kmers / -singletons may be left out and are then estimated (pass 0)
     int estimate_bits = 0;            // not a reference flag: -estimate_bits r, 2^r cells per level of the sketch (0: the library's default, 30)
+    bool scan_kept = false;           // not a reference flag: --scan_kept, pass 2 scans the batches pass 1 kept; -read_scan_file may be left out
 };
 
 void argument_error() {   // src/Faucet.cpp:50-54
@@ -91,6 +100,8 @@ void argument_error() {   // src/Faucet.cpp:50-54
                     "-estimated_kmers <num_kmers> -singletons <num_kmers> -file_prefix <prefix>");
     fprintf(stderr, "\nOptional arguments: --fastq --mercy --high_cov -max_spacer_dist <dist> -fp rate <rate> -j <int> --two_hash "
                     "-bloom_file <filename> -junctions_file <filename> --paired_ends --no_cleaning\n");
+    fprintf(stderr, "Of this build: -gpus <n> -transport copy|rccl -batch_reads <n> -chunk_mb <n> --estimate -estimate_bits <r> "
+                    "--scan_kept (pass 2 scans the reads pass 1 kept on the device: -read_scan_file may be left out)\n");
 }
 
 // src/Faucet.cpp:57-182 (with the missing `return 0` supplied and a bounds check on flag values)
@@ -125,6 +136,7 @@ int handle_arguments(int argc, char** argv, Options& o) {
         else if (a == "-gpus") { if (!val(v)) goto bad; o.gpus = atoi(v); if (o.gpus < 1 || o.gpus > 64) { fprintf(stderr, "-gpus must be in 1..64\n"); return 1; } }
         else if (a == "-transport") { if (!val(v)) goto bad; o.transport = v; if (o.transport != "copy" && o.transport != "rccl") { fprintf(stderr, "-transport must be copy or rccl\n"); return 1; } }
         else if (a == "--estimate") o.estimate = true;
+        else if (a == "--scan_kept") o.scan_kept = true;
         else if (a == "-estimate_bits") { if (!val(v)) goto bad; o.estimate_bits = atoi(v); if (o.estimate_bits < FGPU_EST_MIN_BITS || o.estimate_bits > FGPU_EST_MAX_BITS) { fprintf(stderr, "-estimate_bits must be in %d..%d\n", FGPU_EST_MIN_BITS, FGPU_EST_MAX_BITS); return 1; } }
         else if (a == "--help" || a == "-h") { argument_error(); return 1; }
         else { fprintf(stderr, "Cannot parse tag %s\n", argv[i]); argument_error(); return 1; }
@@ -134,8 +146,8 @@ int handle_arguments(int argc, char** argv, Options& o) {
         argument_error();
         return 1;
     }
-    // (--estimate: the two counts may be left out, pass 0 fills them in)
-    if (!(o.load_file_flag && o.scan_file_flag && o.k_val_flag && o.max_len_flag && (o.est_kmers_flag || o.estimate) && (o.est_sing_flag || o.estimate) && o.pref_flag)) {
+    // (--estimate: the two counts may be left out, pass 0 fills them in; --scan_kept: the scan file may be, pass 2 reads no file)
+    if (!(o.load_file_flag && (o.scan_file_flag || o.scan_kept) && o.k_val_flag && o.max_len_flag && (o.est_kmers_flag || o.estimate) && (o.est_sing_flag || o.estimate) && o.pref_flag)) {
         fprintf(stderr, "Some required argument is missing.\n");
         argument_error();
         return 1;
@@ -156,7 +168,7 @@ void print_settings(const Options& o) {
     if (o.just_load) printf("Only loading bloom, dumping and termination.\n");
     printf(o.node_graph ? "Using node graph.\n" : "Using contig graph.\n");          // src/Faucet.cpp:146-149 (a switch of the stage this build stops before)
     printf("Read load file name: %s\n", o.read_load_file.c_str());
-    printf("Read scan file name: %s\n", o.read_scan_file.c_str());
+    printf("Read scan file name: %s\n", (o.scan_file_flag ? o.read_scan_file : o.read_load_file).c_str());      // (--scan_kept without one: the reads of the load file)
     printf("k: %d \n", o.k);
     printf("Maximal read length: %d\n", o.read_length);
     printf("Estimated number of distinct kmers, for sizing bloom filter: %llu.\n", (unsigned long long)o.estimated_kmers);
@@ -693,10 +705,16 @@ struct KeptReads {
     bool have = false;                // it did, and `blocks` are all of -read_load_file
     uint64_t budget = 0, bytes = 0;   // the budget the pass had, what its blocks are charged
     std::vector<fgpu_packed> blocks;
+    bool with_reads = false;          // --scan_kept: every block came with its read offsets (fgpu_estimate_keep_reads), adopted with it
+    std::vector<fgpu_kept_reads> reads;
     size_t next = 0;                  // blocks before this one have been adopted
     void release(fgpu_ctx* ctx) {
-        for (; ctx && next < blocks.size(); next++) (void)fgpu_device_free(ctx, blocks[next].block_dev);
+        for (; ctx && next < blocks.size(); next++) {
+            (void)fgpu_device_free(ctx, blocks[next].block_dev);
+            if (next < reads.size()) (void)fgpu_device_free(ctx, reads[next].offsets_dev);
+        }
         blocks.clear();
+        reads.clear();
         next = 0;
         have = false;
     }
@@ -717,6 +735,7 @@ int estimate_one_device(const Options& o, const fgpu_params& prm, PhaseClock& cl
         CHECK(fgpu_load_fixup_state(ctx, nullptr, &kept->budget));
         if (const char* cap = getenv("FAUCET_ESTIMATE_KEEP_BYTES")) kept->budget = std::min<uint64_t>(kept->budget, strtoull(cap, nullptr, 10));   // (tests)
         CHECK(fgpu_estimate_keep(ctx, kept->budget));
+        if (kept->with_reads) CHECK(fgpu_estimate_keep_reads(ctx));
         keeping = true;
     }
     double batch_ms = 0;
@@ -753,6 +772,10 @@ int estimate_one_device(const Options& o, const fgpu_params& prm, PhaseClock& cl
         kept->blocks.resize((size_t)n);
         CHECK(fgpu_estimate_take_kept(ctx, kept->blocks.data(), n, &n));
         kept->have = true;
+        if (kept->with_reads) {
+            kept->reads.resize((size_t)n);
+            CHECK(fgpu_estimate_take_kept_reads(ctx, kept->reads.data(), n, &n));
+        }
     }
     if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_estimate_batch calls; %llu k-mers sketched, 2^%d cells per level, estimates from level %d on\n", batch_ms,
                         (unsigned long long)est->kmers, (int)est->r_bits, (int)est->level);
@@ -801,6 +824,7 @@ int estimate_missing(Options& o, PhaseClock& clk, KeptReads* kept) {
     const char* keep_env = getenv("FAUCET_ESTIMATE_KEEP");
     kept->must = !regular && !o.from_bloom;
     kept->asked = can_keep && !o.from_bloom && o.gpus == 1 && (!regular || (keep_env && keep_env[0] == '1'));
+    kept->with_reads = kept->asked && o.scan_kept;      // (main has seen to it that the library has the entry points)
     if (!fgpu_estimate_begin || !fgpu_estimate_batch || !fgpu_estimate_end) {
         fprintf(stderr, "--estimate: the library this program is linked against lacks the entry points of the estimate pass "
                         "(fgpu_estimate_begin, fgpu_estimate_batch, fgpu_estimate_end)\n");
@@ -827,8 +851,8 @@ int estimate_missing(Options& o, PhaseClock& clk, KeptReads* kept) {
 }
 
 // (both ways of pass 1 answer with a ShardLoadResult: the run's counters and the weights of bloo1 / bloo2)
-int load_one_device(fgpu_ctx* ctx, BatchSource& src, PhaseClock& clk, faucet_host::ShardLoadResult* out) {
-    CHECK(fgpu_load_begin(ctx, 0));
+int load_one_device(fgpu_ctx* ctx, BatchSource& src, PhaseClock& clk, faucet_host::ShardLoadResult* out, bool keep_reads) {
+    CHECK(fgpu_load_begin(ctx, keep_reads ? FGPU_LOAD_KEEP_READS : 0));
     const char* failed = "fgpu_load_batch";
     if (int rc = feed_batches(ctx, src, "reads consumed", &clk.batch_ms, &failed, [&](const fgpu_reads* r) { return fgpu_load_batch(ctx, r); })) {
         fprintf(stderr, "%s failed (%d): %s\n", failed, rc, fgpu_last_error(ctx));
@@ -838,7 +862,7 @@ int load_one_device(fgpu_ctx* ctx, BatchSource& src, PhaseClock& clk, faucet_hos
     CHECK(fgpu_load_end(ctx, &out->stats));
     if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_load_batch calls, %.2f ms in fgpu_load_end\n", clk.batch_ms,
                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_end).count());
-    clk.mark("pass 1 (read + load)");
+    clk.mark(keep_reads ? "pass 1 (read + load, reads kept)" : "pass 1 (read + load)");
     CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO1, &out->w1));
     CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO2, &out->w2));
     return 0;
@@ -847,11 +871,12 @@ int load_one_device(fgpu_ctx* ctx, BatchSource& src, PhaseClock& clk, faucet_hos
 // ... from the blocks pass 0 kept: the same pass, a block where load_one_device has a batch of the file.  Blocks the context has not adopted
 // when the pass fails are still the caller's (KeptReads::release)
 int load_kept(fgpu_ctx* ctx, KeptReads& kept, PhaseClock& clk, faucet_host::ShardLoadResult* out) {
-    CHECK(fgpu_load_begin(ctx, 0));
+    CHECK(fgpu_load_begin(ctx, kept.with_reads ? FGPU_LOAD_KEEP_READS : 0));
     uint64_t reads = 0;
     for (; kept.next < kept.blocks.size(); kept.next++) {
         const auto t_batch = std::chrono::steady_clock::now();
-        CHECK(fgpu_load_batch_packed(ctx, &kept.blocks[kept.next]));
+        if (kept.with_reads) CHECK(fgpu_load_batch_packed_reads(ctx, &kept.blocks[kept.next], &kept.reads[kept.next]));
+        else CHECK(fgpu_load_batch_packed(ctx, &kept.blocks[kept.next]));
         clk.batch_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_batch).count();
         reads += kept.blocks[kept.next].n_reads;
         fprintf(stdout, "\rreads consumed: %lld", (long long)reads);
@@ -861,7 +886,7 @@ int load_kept(fgpu_ctx* ctx, KeptReads& kept, PhaseClock& clk, faucet_host::Shar
     CHECK(fgpu_load_end(ctx, &out->stats));
     if (clk.on) fprintf(stderr, "[cli]   %.2f ms in fgpu_load_batch_packed calls, %.2f ms in fgpu_load_end\n", clk.batch_ms,
                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_end).count());
-    clk.mark("pass 1 (load from kept reads)");
+    clk.mark(kept.with_reads ? "pass 1 (load from kept reads, reads kept)" : "pass 1 (load from kept reads)");
     CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO1, &out->w1));
     CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO2, &out->w2));
     return 0;
@@ -885,7 +910,7 @@ int load_from_reads(const Options& o, const Run& run, PhaseClock& clk, BloomFile
     time(&start);
     printf("Weights before load: %f, %f \n", 0.0f, 0.0f);
     faucet_host::ShardLoadResult lo;
-    if (int rc = run.shards ? load_shards(o, *run.shards, clk, &lo) : kept.have ? load_kept(run.one, kept, clk, &lo) : load_one_device(run.one, *src, clk, &lo)) return rc;
+    if (int rc = run.shards ? load_shards(o, *run.shards, clk, &lo) : kept.have ? load_kept(run.one, kept, clk, &lo) : load_one_device(run.one, *src, clk, &lo, o.scan_kept)) return rc;
     printf("\n");
     printf("Weights after load: %f, %f \n", lo.w1, lo.w2);
     printf("Reads processed: %llu\n", (unsigned long long)lo.stats.reads_processed);
@@ -973,6 +998,59 @@ int scan_one_device(const Options& o, fgpu_ctx* ctx, PairFilter& short_pf, PairF
     return 0;
 }
 
+// ... over the batches pass 1 kept (--scan_kept): no file is opened, a batch is fgpu_scan_batch_kept(i)
+int scan_kept_one_device(const Options& o, fgpu_ctx* ctx, uint64_t n_batches, PairFilter& short_pf, PairFilter& long_pf, PhaseClock& clk, faucet_host::ScanPassResult* res) {
+    const faucet_host::PairTarget none = {nullptr, 0, 0};
+    const faucet_host::PairTarget short_target = {short_pf.bits.data(), short_pf.tai, short_pf.n_hash}, long_target = {long_pf.bits.data(), long_pf.tai, long_pf.n_hash};
+    const auto t_pass = std::chrono::steady_clock::now();
+    auto t_fed = t_pass;
+    const int rc = faucet_host::scan_pass_kept(ctx, o.k, o.no_cleaning ? none : short_target, o.no_cleaning || !o.paired_ends ? none : long_target, o.paired_ends,
+        n_batches, [&](uint64_t reads) {
+            fprintf(stdout, "\rreads scanned: %lld", (long long)reads);
+            fflush(stdout);
+            t_fed = std::chrono::steady_clock::now();
+        }, res);
+    if (rc != FGPU_OK) { fprintf(stderr, "%s failed (%d): %s\n", res->failed, rc, fgpu_last_error(ctx)); return 2; }
+    clk.scan_ms += std::chrono::duration<double, std::milli>(t_fed - t_pass).count();
+    clk.take_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fed).count();
+    if (clk.on) {
+        fprintf(stderr, "[cli]   %.2f ms in fgpu_scan_batch_kept calls (%llu kept batches), %.2f ms in fgpu_scan_end (the last walks, the last lists, the pair filters' last batches)\n",
+                clk.scan_ms, (unsigned long long)n_batches, clk.take_ms);
+        tell_scan_diagnostics(o, ctx);
+    }
+    return 0;
+}
+
+// --scan_kept, after pass 1: did it keep every batch with its reads?  *from_kept: pass 2 scans them.  If not, pass 2 can still read
+// -read_scan_file where one was given and the input is a file that can be read again (one note); otherwise the run ends here, exit code 2,
+// with <prefix>.bloom written -- the restart that exists.  FAUCET_DEBUG_SCAN_KEPT_BUDGET=<bytes> (tests): "the device keeps this many bytes"
+int decide_scan_kept(const Options& o, fgpu_ctx* ctx, BloomFile& bloom, const PhaseClock& clk, bool* from_kept, uint64_t* n_batches) {
+    int complete = 0;
+    uint64_t bytes = 0, budget = 0;
+    CHECK(fgpu_scan_kept_state(ctx, &complete, n_batches, nullptr, &bytes));
+    CHECK(fgpu_load_fixup_state(ctx, nullptr, &budget));
+    if (const char* e = getenv("FAUCET_DEBUG_SCAN_KEPT_BUDGET")) {
+        budget = std::min<uint64_t>(budget, strtoull(e, nullptr, 10));
+        if (bytes > budget) { complete = 0; bytes = 0; }      // (as if the first batch had not fitted)
+    }
+    *from_kept = complete != 0;
+    if (clk.on) fprintf(stderr, "[cli]   %llu bytes kept on the device in %llu batches (budget %llu bytes)%s\n", (unsigned long long)bytes, (unsigned long long)*n_batches,
+                        (unsigned long long)budget, complete ? "" : ": not all of pass 1");
+    if (complete) return 0;
+    struct stat st;
+    const bool regular = stat(o.read_load_file.c_str(), &st) == 0 && S_ISREG(st.st_mode);
+    if (o.scan_file_flag && regular) {
+        fprintf(stderr, "note: --scan_kept: pass 1 could not keep all of its reads on the device (%llu bytes kept, budget %llu bytes): pass 2 reads %s\n",
+                (unsigned long long)bytes, (unsigned long long)budget, o.read_scan_file.c_str());
+        return 0;
+    }
+    fprintf(stderr, "--scan_kept: pass 1 could not keep all of its reads on the device (%llu bytes kept, budget %llu bytes) and there is no input pass 2 could "
+                    "read instead.  %s.bloom has been written: -bloom_file %s.bloom -read_scan_file <the reads> finishes the job\n",
+            (unsigned long long)bytes, (unsigned long long)budget, o.file_prefix.c_str(), o.file_prefix.c_str());
+    (void)bloom.complete();
+    return 2;
+}
+
 // pass 2 over the read shards: the last shard ends with the run's junction map and pair filters, the counts are the sum over the shards
 int scan_shards(const Options& o, ShardedRun& run, PairFilter& short_pf, PairFilter& long_pf, faucet_host::ScanPassResult* res) {
     fgpu_ctx* ctx = run.last_ctx();
@@ -992,7 +1070,7 @@ int scan_shards(const Options& o, ShardedRun& run, PairFilter& short_pf, PairFil
 }
 
 // ---- pass 2 (ReadScanner::scanReads, src/ReadScanner.cpp:284-359; printScanSummary :19-27) and the files it makes
-int scan_and_write(const Options& o, const Run& run, PairFilter& short_pf, PairFilter& long_pf, PhaseClock& clk) {
+int scan_and_write(const Options& o, const Run& run, PairFilter& short_pf, PairFilter& long_pf, PhaseClock& clk, bool from_kept, uint64_t kept_batches) {
     time_t start, stop;
     time(&start);
     float w2 = 0;
@@ -1000,9 +1078,10 @@ int scan_and_write(const Options& o, const Run& run, PairFilter& short_pf, PairF
     CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO2, &w2));
     printf("Weight before read scan: %f \n", w2);
     faucet_host::ScanPassResult res;
-    if (int rc = run.shards ? scan_shards(o, *run.shards, short_pf, long_pf, &res) : scan_one_device(o, ctx, short_pf, long_pf, clk, &res)) return rc;
+    if (int rc = run.shards ? scan_shards(o, *run.shards, short_pf, long_pf, &res) : from_kept ? scan_kept_one_device(o, ctx, kept_batches, short_pf, long_pf, clk, &res)
+                                                                                               : scan_one_device(o, ctx, short_pf, long_pf, clk, &res)) return rc;
     time(&stop);
-    clk.mark(run.shards ? "pass 2 (shards)" : "pass 2 (read + scan)");
+    clk.mark(run.shards ? "pass 2 (shards)" : from_kept ? "pass 2 (scan of kept reads)" : "pass 2 (read + scan)");
     return write_scan_outputs(o, ctx, res.stats, res.empty_count, res.not_empty_count, difftime(stop, start), short_pf, long_pf, clk);
 }
 
@@ -1013,6 +1092,15 @@ int main(int argc, char** argv) {
     Options o;
     KeptReads kept;
     if (handle_arguments(argc, argv, o) == 1) return 1;
+    if (o.scan_kept) {      // refused before any input is opened and before anything is printed or written
+        if (o.gpus > 1) { fprintf(stderr, "--scan_kept needs -gpus 1: read shards and filter slices keep batches of their own\n"); return 2; }
+        if (o.from_bloom) { fprintf(stderr, "--scan_kept cannot be combined with -bloom_file: without pass 1 no reads are kept (give -read_scan_file and leave --scan_kept out)\n"); return 2; }
+        if (!faucet_host::scan_kept_linked() || !fgpu_estimate_keep_reads || !fgpu_estimate_take_kept_reads || !fgpu_load_batch_packed_reads) {
+            fprintf(stderr, "--scan_kept: the library this program is linked against lacks the entry points of the scan of kept reads "
+                            "(fgpu_scan_kept_state, fgpu_scan_batch_kept, fgpu_estimate_keep_reads, fgpu_estimate_take_kept_reads, fgpu_load_batch_packed_reads)\n");
+            return 2;
+        }
+    }
     if (o.estimate && !(o.est_kmers_flag && o.est_sing_flag)) {     // pass 0, ahead of everything the two numbers decide (and of the lines that print them)
         if (o.k < 1 || o.k > 31) { fprintf(stderr, "k must be in 1..31 on this build\n"); return 1; }
         choose_chunk_bytes(o);
@@ -1032,6 +1120,10 @@ int main(int argc, char** argv) {
         kept.release(run.first());
         return rc;
     }
+    bool from_kept = false;
+    uint64_t kept_batches = 0;
+    if (o.scan_kept && !o.just_load)
+        if (int rc = decide_scan_kept(o, run.one, bloom, clk, &from_kept, &kept_batches)) return rc;
     PairFilter short_pf, long_pf;
     create_pair_filters(o, &short_pf, &long_pf);
     if (o.just_load) return bloom.complete() ? 0 : 2;
@@ -1039,7 +1131,7 @@ int main(int argc, char** argv) {
         if (int rc = reload_scan_files(o, short_pf, long_pf)) return rc;
         return bloom.complete() ? 3 : 2;
     }
-    if (int rc = scan_and_write(o, run, short_pf, long_pf, clk)) return rc;
+    if (int rc = scan_and_write(o, run, short_pf, long_pf, clk, from_kept, kept_batches)) return rc;
     clk.mark("pair filter weights");
     if (!o.no_cleaning)
         fprintf(stderr, "The contig-graph stage is not part of this build: the load and scan outputs have been written; the reference\n"

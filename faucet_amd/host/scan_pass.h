@@ -11,6 +11,7 @@
 // repair is absorbed inside the library, which scans its own copy of the batches again -- both inputs may be pipes.
 // What the hosts do with the junction map afterwards (write_scan_outputs there, gpu_fill_junction_map here) stays with them.
 // ShardedRun::scan (shard_host.h) is the same pass over several devices; it has no host loop yet.
+// scan_pass_kept is the same pass over the batches pass 1 kept on the device (FGPU_LOAD_KEEP_READS): no scan file is read at all.
 // fgpu_diag_long_pairs_state is referred to weakly: a library without it (the tests' CPU stand-in of the ABI) links unchanged and gets no note.
 #pragma once
 #include <stdint.h>
@@ -25,6 +26,9 @@
 #include "pair_loop.h"
 
 #pragma weak fgpu_diag_long_pairs_state
+// ... and so are the two entry points of the scan over the batches pass 1 kept (scan_pass_kept): null against a library without them
+#pragma weak fgpu_scan_kept_state
+#pragma weak fgpu_scan_batch_kept
 
 namespace faucet_host {
 
@@ -58,10 +62,16 @@ typedef std::function<int(const fgpu_reads*)> EachBatch;      // an fgpu status;
 // itself (it cannot split its text, say) names what failed in ScanPassResult::failed
 typedef std::function<int(const EachBatch& each)> BatchFeed;
 
+// The same one level up: a batch is something that scans itself (one call of the library, named by `call` when it fails) and says how many
+// reads it had -- a batch of text through fgpu_scan_batch, or a batch pass 1 kept through fgpu_scan_batch_kept.
+typedef std::function<int(uint64_t* n_reads)> ScanItem;
+typedef std::function<int(const ScanItem& item)> EachItem;
+typedef std::function<int(const EachItem& each)> ItemFeed;
+
 // FGPU_OK, or the status of the first call that failed (out->failed names it; fgpu_last_error(ctx) has its text).  Once fgpu_scan_begin has
 // succeeded the pass is closed with fgpu_scan_end whatever happens in between.
-inline int scan_pass(fgpu_ctx* ctx, int k, const PairTarget& short_pf, const PairTarget& long_pf, bool paired_ends, const BatchFeed& feed,
-                     ScanPassResult* out) {
+inline int scan_pass_items(fgpu_ctx* ctx, int k, const PairTarget& short_pf, const PairTarget& long_pf, bool paired_ends, const ItemFeed& feed,
+                           const char* call, ScanPassResult* out) {
     int rc = FGPU_OK;
 #define SCAN_PASS_TRY(call, ...)                                                         \
     do {                                                                                 \
@@ -96,11 +106,12 @@ inline int scan_pass(fgpu_ctx* ctx, int k, const PairTarget& short_pf, const Pai
         }
     };
     SCAN_PASS_TRY(fgpu_scan_begin, ctx);
-    rc = feed([&](const fgpu_reads* r) -> int {
-        const int brc = fgpu_scan_batch(ctx, r);
-        if (brc != FGPU_OK) { out->failed = "fgpu_scan_batch"; return brc; }
+    rc = feed([&](const ScanItem& item) -> int {
+        uint64_t n_reads = 0;
+        const int brc = item(&n_reads);
+        if (brc != FGPU_OK) { out->failed = call; return brc; }
         if (!out->host_loop) return FGPU_OK;
-        batch_reads.push_back(r->n_reads);
+        batch_reads.push_back(n_reads);
         return batch_reads.size() > 1 ? take_lists(false) : FGPU_OK;
     });
     const int end_rc = fgpu_scan_end(ctx, &out->stats);
@@ -116,6 +127,44 @@ inline int scan_pass(fgpu_ctx* ctx, int k, const PairTarget& short_pf, const Pai
     }
 #undef SCAN_PASS_TRY
     return FGPU_OK;
+}
+
+// the batches of the scan file as text: each is scanned by fgpu_scan_batch
+inline int scan_pass(fgpu_ctx* ctx, int k, const PairTarget& short_pf, const PairTarget& long_pf, bool paired_ends, const BatchFeed& feed,
+                     ScanPassResult* out) {
+    return scan_pass_items(ctx, k, short_pf, long_pf, paired_ends, [&](const EachItem& each) -> int {
+        return feed([&](const fgpu_reads* r) -> int {
+            return each([&](uint64_t* n_reads) -> int {
+                *n_reads = r->n_reads;
+                return fgpu_scan_batch(ctx, r);
+            });
+        });
+    }, "fgpu_scan_batch", out);
+}
+
+// can this library scan the batches pass 1 kept (both entry points are there)?
+inline bool scan_kept_linked() { return fgpu_scan_kept_state && fgpu_scan_batch_kept; }
+
+// Pass 2 over the n_batches batches a load pass opened with FGPU_LOAD_KEEP_READS kept (fgpu_scan_kept_state says how many, and that they are
+// complete): no input is read.  `progress` (or null) hears the reads scanned so far after every batch.
+inline int scan_pass_kept(fgpu_ctx* ctx, int k, const PairTarget& short_pf, const PairTarget& long_pf, bool paired_ends, uint64_t n_batches,
+                          const std::function<void(uint64_t reads)>& progress, ScanPassResult* out) {
+    if (!scan_kept_linked()) { out->failed = "fgpu_scan_batch_kept (not in this library)"; return FGPU_ERR_STATE; }
+    return scan_pass_items(ctx, k, short_pf, long_pf, paired_ends, [&](const EachItem& each) -> int {
+        uint64_t reads = 0;
+        for (uint64_t i = 0; i < n_batches; i++) {
+            uint64_t n = 0;
+            const int rc = each([&](uint64_t* n_reads) -> int {
+                const int brc = fgpu_scan_batch_kept(ctx, i, &n);
+                *n_reads = n;
+                return brc;
+            });
+            if (rc != FGPU_OK) return rc;
+            reads += n;
+            if (progress) progress(reads);
+        }
+        return FGPU_OK;
+    }, "fgpu_scan_batch_kept", out);
 }
 
 }  // namespace faucet_host

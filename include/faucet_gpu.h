@@ -235,6 +235,11 @@ int fgpu_load_begin(fgpu_ctx* ctx, int keep_carry);
                                     * occurrence's bits were NOT set before it within the shard (n_hash <= 4 planes of one bit per position, kept in HBM
                                     * with the batch), and the fix-up asks the lower shards' bits for exactly those.  The resolve kernel then looks at every
                                     * missing bit instead of stopping at the first that fails (+10 % on the pass). */
+#define FGPU_LOAD_KEEP_READS   8   /* the plain pass (with or without FGPU_LOAD_KEEP_CARRY; FGPU_ERR_STATE together with the two shard flags) keeps, beside
+                                    * every resident batch's codes, bad and sure planes, what a scan of the batch needs without its text: the
+                                    * (n_reads + 1) read offsets, charged to the resident budget, the read count, and the longest read of the pass.
+                                    * fgpu_scan_batch_kept then scans the batches with no second reading of the input.  Filters, stats and sure
+                                    * planes are bit for bit those of a pass without the flag; a batch that does not fit ends the keeping as always. */
 /* Consume one batch, in file order.  Exact: occurrence t goes to bloo2 iff all its bits were set
  * by occurrences < t, t following the reference's processing order. */
 int fgpu_load_batch(fgpu_ctx* ctx, const fgpu_reads* reads);
@@ -418,6 +423,32 @@ int fgpu_estimate_take_kept(fgpu_ctx* ctx, fgpu_packed* out, uint64_t cap, uint6
  * no reads. */
 int fgpu_load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* b);
 
+/* ---- pass 0's blocks carry their reads: the offsets a scan of a block needs (fgpu_scan_batch_kept) ------------------------------------------
+ * A packed block holds the stream, not where its reads begin (a separator and an N are both a bad position), and its format is fixed.  A
+ * keeping pass 0 can keep every batch's (n_reads + 1) read offsets beside its block, as a plain device allocation of its own:
+ *
+ *     fgpu_estimate_keep(c0, budget);  fgpu_estimate_keep_reads(c0);  fgpu_estimate_batch(c0, b) ...;  fgpu_estimate_end(c0, &e);
+ *     fgpu_estimate_take_kept(c0, blocks, cap, &n);  fgpu_estimate_take_kept_reads(c0, reads, cap, &n);  fgpu_destroy(c0);
+ *     fgpu_load_begin(c1, FGPU_LOAD_KEEP_READS);  fgpu_load_batch_packed_reads(c1, &blocks[i], &reads[i]) ...;  fgpu_load_end(c1, &stats);
+ *
+ * _keep_reads: after fgpu_estimate_keep, before the pass' first batch (FGPU_ERR_STATE otherwise).  A batch is then charged (n_reads + 1) * 8
+ * bytes more; a batch whose offsets cannot be had ends the keeping like one whose block cannot.
+ * _take_kept_reads: after fgpu_estimate_take_kept of the same pass (FGPU_ERR_STATE before it, or in a pass that did not keep reads), in block
+ * order; max_read_len is the longest read of the PASS in every entry.  Ownership passes to the caller as with the blocks: fgpu_device_free
+ * releases an entry's offsets, fgpu_load_batch_packed_reads hands them on; what is never taken goes with the next fgpu_estimate_begin or
+ * fgpu_destroy.  *n_out (may be NULL) = the number of entries, also when cap is too small (FGPU_ERR_ARG, nothing taken).
+ * fgpu_load_batch_packed_reads: fgpu_load_batch_packed, in a pass opened with FGPU_LOAD_KEEP_READS (FGPU_ERR_STATE otherwise), plus the
+ * adoption of the offsets: on FGPU_OK both allocations are the context's, released with the block; on an error both are still the caller's.
+ * FGPU_ERR_ARG: null arguments, reads->n_reads != b->n_reads, no offsets beside a block. */
+typedef struct fgpu_kept_reads {
+    void*    offsets_dev;      /* (n_reads + 1) x uint64: fgpu_reads.offsets of the batch, on the device */
+    uint64_t n_reads;
+    uint64_t max_read_len;
+} fgpu_kept_reads;
+int fgpu_estimate_keep_reads(fgpu_ctx* ctx);
+int fgpu_estimate_take_kept_reads(fgpu_ctx* ctx, fgpu_kept_reads* out, uint64_t cap, uint64_t* n_out);
+int fgpu_load_batch_packed_reads(fgpu_ctx* ctx, const fgpu_packed* b, const fgpu_kept_reads* reads);
+
 /* filters: raw bit arrays, tai/8 bytes, exactly the .bloom file body (utils/Bloom.cpp:571-587) */
 int fgpu_bloom_download(fgpu_ctx* ctx, int which, uint8_t* host_out, uint64_t nbytes);
 /* The same copy, started now and finished by fgpu_bloom_download_wait: it runs on its own copy stream behind the work
@@ -470,6 +501,22 @@ int fgpu_scan_resident_base(fgpu_ctx* ctx, uint64_t first_batch);
 int fgpu_scan_begin(fgpu_ctx* ctx);
 /* Pure stage + ordered walk for one batch, in file order. */
 int fgpu_scan_batch(fgpu_ctx* ctx, const fgpu_reads* reads);
+/* ---- the scan of the batches pass 1 kept: one reading of the input serves both passes --------------------------------------------------------
+ * After a load pass opened with FGPU_LOAD_KEEP_READS every resident batch holds what a scan needs (packed stream, sure plane, read offsets).
+ * _scan_kept_state: host state only, never waits; valid from fgpu_load_end until the next load pass begins (plain or sliced; fgpu_bloom_upload
+ * of bloo2 forgets the batches as well).  *complete = 1 iff the last load pass had the flag and EVERY non-empty batch stayed resident with
+ * its offsets; *n_batches, *n_reads, *bytes: the resident batches, their reads, the budget they are charged.  All four may be NULL.
+ * _scan_batch_kept: between fgpu_scan_begin and fgpu_scan_end, kept batch i (empty batches keep nothing: i counts the non-empty batches, as
+ * for fgpu_scan_resident_base).  In every observable result -- junction records and their creation order, fgpu_scan_stats, stop lists, both
+ * pair filters, pair counts, reads_processed -- it equals fgpu_scan_batch on the reads batch i was loaded from; nothing is packed or
+ * compared, the sure plane is reused unconditionally (valid_reused grows as for a batch that compared equal).  The batch's planes are COPIED
+ * into the scan's buffers (3 bits per position, device to device); the journal, the replay after a voided lazy scan or an outgrown junction
+ * table, and the harvest of stop lists work as for fgpu_scan_batch, and text batches may be mixed in.  *n_reads_out (may be NULL) = the
+ * batch's reads.  The batches live until the next load pass: a later scan of the same context may scan them again.
+ * fgpu_scan_batch's preconditions apply (no prepared batches waiting, no preview in the table).  FGPU_ERR_STATE: outside a scan, or the
+ * state is not complete; FGPU_ERR_ARG: i >= n_batches. */
+int fgpu_scan_kept_state(fgpu_ctx* ctx, int* complete, uint64_t* n_batches, uint64_t* n_reads, uint64_t* bytes);
+int fgpu_scan_batch_kept(fgpu_ctx* ctx, uint64_t i, uint64_t* n_reads_out);
 /* The same in two steps, so that read shards can do the pure part concurrently and only the
  * ordered walk is serial: scan_prepare runs the pure stage and keeps its bit planes resident
  * (about 1.6 bytes of HBM per base); scan_walk_prepared walks every prepared batch in the order
