@@ -542,12 +542,17 @@ class Context:
         """the largest chunk text_split will be handed: its buffers are sized for it once instead of growing with the first chunks"""
         self._c(self.lib.fgpu_text_reserve(self.h, int(max_chunk_bytes)))
 
-    def text_split(self, text: bytes, fastq: bool, final_chunk: bool):
+    def text_split(self, text, fastq: bool, final_chunk: bool, text_on_device: bool = False, nbytes: int = None):
         """Record splitting of raw FASTA/FASTQ text on the device (the reference's getline loops).  Returns (ReadBatch that
-        points into the device copy of the text and is valid until the next text_split, bytes consumed)."""
-        buf = np.frombuffer(text, dtype=np.uint8) if len(text) else np.zeros(1, np.uint8)
+        points into the device copy of the text and is valid until the next text_split, bytes consumed).
+        text_on_device: `text` is the address of `nbytes` bytes of text in device memory, written in the order of the context's stream (or
+        complete); the batch then points into the caller's text, which has to stay as long as the batch is used."""
         out, used = L.Reads(), C.c_uint64(0)
-        self._c(self.lib.fgpu_text_split(self.h, buf.ctypes.data, len(text), 0, int(fastq), int(final_chunk), C.byref(out), C.byref(used)))
+        if text_on_device:
+            self._c(self.lib.fgpu_text_split(self.h, int(text), int(nbytes), 1, int(fastq), int(final_chunk), C.byref(out), C.byref(used)))
+        else:
+            buf = np.frombuffer(text, dtype=np.uint8) if len(text) else np.zeros(1, np.uint8)
+            self._c(self.lib.fgpu_text_split(self.h, buf.ctypes.data, len(text), 0, int(fastq), int(final_chunk), C.byref(out), C.byref(used)))
         rb = ReadBatch(out.bases or 0, out.offsets or 0, n_reads=int(out.n_reads), on_device=True, starts=out.starts)
         return rb, int(used.value)
 

@@ -52,8 +52,10 @@ __global__ void __launch_bounds__(256) k_text_newlines(const unsigned char* __re
     }
 }
 
-// defaults for records whose header / read line is not terminated inside the text (only possible in the final chunk):
-// an absent read is empty, an unterminated one runs to the end of the text
+// defaults for records whose header / read line is not terminated inside the text (only possible in the final chunk): an unterminated read
+// runs to the end of the text, and a read that is absent behind a header that ended with its newline is empty.  (Absent behind a header that
+// ended with the TEXT, the read is that header line: the reference has one string for both, the failed getline leaves it alone --
+// k_text_lengths' `header_is_read`.)
 __global__ void __launch_bounds__(256) k_text_defaults(uint64_t* __restrict__ starts, uint64_t* __restrict__ ends, uint64_t n_rec, uint64_t n) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += (uint64_t)gridDim.x * blockDim.x) {
         starts[i] = n;
@@ -81,10 +83,19 @@ __global__ void __launch_bounds__(256) k_text_records(const uint64_t* __restrict
     }
 }
 
-__global__ void __launch_bounds__(256) k_text_lengths(const uint64_t* __restrict__ starts, const uint64_t* __restrict__ ends, uint64_t n_rec,
-                                                      uint64_t* __restrict__ len) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n_rec; i += (uint64_t)gridDim.x * blockDim.x)
-        len[i] = i < n_rec ? ends[i] - starts[i] : 0;   // one extra 0 so that the exclusive scan also yields the total
+// `header_is_read` (final chunk only): the text's last line is a header without its newline, which the reference goes on to process as that
+// record's read -- from behind the last newline (where record n_rec - 2 ends; 0 if there is none) to the end of the text
+__global__ void __launch_bounds__(256) k_text_lengths(uint64_t* __restrict__ starts, const uint64_t* ends, uint64_t n_rec, uint64_t* len,
+                                                      const uint64_t* __restrict__ rec_end, uint64_t n, int header_is_read) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n_rec; i += (uint64_t)gridDim.x * blockDim.x) {
+        if (header_is_read && i == n_rec - 1) {
+            const uint64_t s = n_rec >= 2 ? rec_end[n_rec - 2] : 0;
+            starts[i] = s;
+            len[i] = n - s;
+        } else {
+            len[i] = i < n_rec ? ends[i] - starts[i] : 0;   // one extra 0 so that the exclusive scan also yields the total
+        }
+    }
 }
 
 }  // namespace
@@ -194,6 +205,7 @@ extern "C" int fgpu_text_split(fgpu_ctx* ctx, const char* text, uint64_t nbytes,
     // lines as getline counts them: every '\n' ends one; at the end of the file a non-empty unterminated tail is one more
     const uint64_t n_lines = n_newlines + ((final_chunk && last_byte != '\n') ? 1 : 0);
     const uint64_t n_rec = final_chunk ? (n_lines + P - 1) / P : n_newlines / P;
+    const int header_is_read = (final_chunk && last_byte != '\n' && n_newlines % P == 0) ? 1 : 0;   // the file's last line: an unterminated header
     if (n_rec == 0) return FGPU_OK;   // not even one complete record: the caller reads more
     if (n_rec >= 0xFFFFFFFFULL) { ctx->err = "more than 2^32 records in one chunk of text"; return FGPU_ERR_CAPACITY; }
     if ((rc = fgpu_ensure(ctx, &ts.rec, (4 * std::max<uint64_t>(n_rec, n_rec * cap / nbytes + 16) + 4) * 8))) return rc;   // (records of a chunk of the reserved size, at this chunk's density)
@@ -205,7 +217,8 @@ extern "C" int fgpu_text_split(fgpu_ctx* ctx, const char* text, uint64_t nbytes,
     FGPU_HIP(hipMemsetAsync(rec_end, 0, n_rec * 8, st));
     FGPU_LAUNCH("text_records", k_text_records, fgpu_grid(n_words, 256), 256, (const uint64_t*)nl, (const uint32_t*)rank, n_words, P, n_rec,
                 starts, ends, rec_end);
-    FGPU_LAUNCH("text_lengths", k_text_lengths, fgpu_grid(n_rec + 1, 256), 256, (const uint64_t*)starts, (const uint64_t*)ends, n_rec, ends);
+    FGPU_LAUNCH("text_lengths", k_text_lengths, fgpu_grid(n_rec + 1, 256), 256, starts, (const uint64_t*)ends, n_rec, ends, (const uint64_t*)rec_end, nbytes,
+                header_is_read);
     size_t need = tmp_bytes;
     FGPU_HIP(rocprim::exclusive_scan(ts.tmp.p, need, ends, offsets, (uint64_t)0, n_rec + 1, rocprim::plus<uint64_t>(), st));
     uint64_t used = nbytes, total = 0;

@@ -262,11 +262,11 @@ public:
     // next batch of at most max_reads sequence lines (host pointers, valid until the next call); false when the input is exhausted
     bool next(uint64_t max_reads, fgpu_reads* out) {
         bases_.clear();
+        bases_.reserve(64);               // (a batch of nothing but empty reads still hands out a pointer: the library refuses a batch with reads and no bases)
         offsets_.assign(1, 0);
         std::string line;
         while (offsets_.size() - 1 < max_reads && std::getline(in_, line)) {
-            line.clear();
-            std::getline(in_, line);
+            std::getline(in_, line);      // (one string, as in the reference: behind a header that ended with the file this call fails and leaves the header in it)
             bases_.insert(bases_.end(), line.begin(), line.end());
             offsets_.push_back(bases_.size());
             if (fastq_) { std::getline(in_, line); std::getline(in_, line); }

@@ -473,8 +473,11 @@ int fgpu_bitmap_or(fgpu_ctx* ctx, void* dst_dev, const void* src_dev, uint64_t n
  * context, ready for fgpu_load_batch / fgpu_scan_batch / fgpu_presence_batch.
  * final_chunk == 0: only records whose 2 (FASTA) or 4 (FASTQ) lines all end inside the text are taken; *consumed = bytes
  * they occupy -- the caller prepends the rest to the next chunk.  final_chunk != 0: the text ends the file; a last line
- * without a newline, a missing sequence line (empty read) and missing FASTQ tail lines are handled as getline handles
- * them; *consumed = nbytes.  A carriage return before the newline stays part of the line, as it does in the reference. */
+ * without a newline, a missing sequence line and missing FASTQ tail lines are handled as getline handles them, called
+ * with ONE string as the reference calls it: behind a header that ends with its newline a missing sequence line is an
+ * empty read; behind a header that ends with the text (no newline) the failed call leaves the string alone, and the read
+ * is that header line.  *consumed = nbytes.  A carriage return before the newline stays part of the line, as it does in
+ * the reference. */
 /* Page-locked host memory for the text handed to fgpu_text_split (or for read batches): copies to the device then run at
  * link speed and asynchronously.  NULL when it cannot be had; plain malloc'ed memory works too, only slower. */
 void* fgpu_host_alloc(uint64_t bytes);

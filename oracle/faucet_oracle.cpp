@@ -520,7 +520,7 @@ int fo_reads_from_file(const char* path, int fastq, fo_reads* out) {
     std::string line, all;
     std::vector<uint64_t> offs{0};
     while (std::getline(in, line)) {                /* header (any line) */
-        std::getline(in, line);                     /* sequence; empty if the stream just ended */
+        std::getline(in, line);                     /* sequence; a failed call leaves the line: "" behind a header's newline, the header itself behind one cut off by the end of the file */
         all += line;
         offs.push_back(all.size());
         if (fastq) { std::getline(in, line); std::getline(in, line); }

@@ -118,19 +118,22 @@ int fgpu_text_split(fgpu_ctx* c, const char* text, uint64_t nbytes, int text_on_
     uint64_t pos = 0, used = 0;
     for (;;) {
         // the record's lines: [begin, end) without the newline; a line that ends with the text (no newline) only counts in the final chunk
-        uint64_t p = pos, seq_b = 0, seq_e = 0, have = 0;
-        bool complete = true;
+        uint64_t p = pos, seq_b = 0, seq_e = 0, have = 0, head_b = pos;
+        bool complete = true, head_open = false;
         for (uint64_t l = 0; l < lines_per_record; l++) {
-            if (p >= nbytes) {                      // getline fails: the header's failure ends the loop, later ones leave the line empty
+            if (p >= nbytes) {                      // getline fails: the header's failure ends the loop
                 if (l == 0) { complete = false; break; }
                 if (!final_chunk) { complete = false; break; }
-                if (l == 1) seq_b = seq_e = nbytes;
+                // the read's: behind a header that ended with its newline the string was erased; behind one that ended with the file the stream
+                // is at its end, the call fails before it touches the string, and the header line stays in it as the read
+                if (l == 1) { seq_b = head_open ? head_b : nbytes; seq_e = nbytes; }
                 have++;
                 continue;
             }
             const char* nl = (const char*)memchr(c->text.data() + p, '\n', nbytes - p);
             if (!nl && !final_chunk) { complete = false; break; }
             const uint64_t e = nl ? (uint64_t)(nl - c->text.data()) : nbytes;
+            if (l == 0) head_open = !nl;
             if (l == 1) { seq_b = p; seq_e = e; }
             p = nl ? e + 1 : nbytes;
             have++;
@@ -150,6 +153,9 @@ int fgpu_text_split(fgpu_ctx* c, const char* text, uint64_t nbytes, int text_on_
     out->on_device = 1;                         // what the product returns; the stub's "device" is host memory
     return FGPU_OK;
 }
+
+// what the product refuses (fgpu_check_reads): reads without bases or offsets, even if every read is empty
+static bool null_batch(const fgpu_reads* r) { return r->n_reads && (!r->bases || !r->offsets); }
 
 // a batch as the contiguous (bases, offsets) pair the oracle takes
 static void flatten(fgpu_ctx* c, const fgpu_reads* r, const char** bases, const uint64_t** offs) {
@@ -177,6 +183,7 @@ int fgpu_load_begin(fgpu_ctx* c, int flags) {
 
 int fgpu_load_batch(fgpu_ctx* c, const fgpu_reads* r) {
     if (!c || !r) return FGPU_ERR_ARG;
+    if (null_batch(r)) return fail(c, FGPU_ERR_ARG, "null read batch");
     if (c->phase != 1) return fail(c, FGPU_ERR_STATE, "load_batch outside load_begin/load_end");
     const char* bases;
     const uint64_t* offs;
@@ -332,6 +339,7 @@ static int stub_scan_flat(fgpu_ctx* c, const char* bases, const uint64_t* offs, 
 
 int fgpu_scan_batch(fgpu_ctx* c, const fgpu_reads* r) {
     if (!c || !r) return FGPU_ERR_ARG;
+    if (null_batch(r)) return fail(c, FGPU_ERR_ARG, "null read batch");
     if (c->phase != 2) return fail(c, FGPU_ERR_STATE, "scan_batch outside scan_begin/scan_end");
     const char* bases;
     const uint64_t* offs;
@@ -342,6 +350,7 @@ int fgpu_scan_batch(fgpu_ctx* c, const fgpu_reads* r) {
 // the pure stage has no counterpart in the oracle: a prepared batch is kept as it is and scanned when its turn comes
 int fgpu_scan_prepare(fgpu_ctx* c, const fgpu_reads* r) {
     if (!c || !r) return FGPU_ERR_ARG;
+    if (null_batch(r)) return fail(c, FGPU_ERR_ARG, "null read batch");
     if (c->phase != 2) return fail(c, FGPU_ERR_STATE, "scan_prepare outside scan_begin/scan_end");
     const char* bases;
     const uint64_t* offs;
@@ -460,6 +469,7 @@ int fgpu_stage3_find_neighbors(fgpu_ctx* c, const uint64_t*, const int8_t*, uint
 // "Device" memory is host memory here, a stream is the calling thread: every call has finished when it returns.
 int fgpu_presence_batch(fgpu_ctx* c, const fgpu_reads* r) {
     if (!c || !r) return FGPU_ERR_ARG;
+    if (null_batch(r)) return fail(c, FGPU_ERR_ARG, "null read batch");
     if (c->phase != 0) return fail(c, FGPU_ERR_STATE, "presence_batch while a pass is open");
     const char* bases;
     const uint64_t* offs;

@@ -5,6 +5,7 @@ import pytest
 from faucet_amd import _lib as L
 from faucet_amd import api, synth
 from oracle import pyoracle as po
+from tests import getline_ref
 from tests.golden_util import CASES, Case, kat
 
 pytestmark = pytest.mark.gpu
@@ -989,21 +990,6 @@ def test_config4_sized_filters_index_past_32_bits(log_tai, nh):
     ctx.close()
 
 
-def _getline_records(text: bytes, fastq: bool):
-    """the reference's reading loop (utils/Bloom.cpp:280-282,340) in Python: the sequence line of every record"""
-    lines = text.split(b"\n")
-    if lines and lines[-1] == b"":
-        lines.pop()                     # a final newline does not start another line
-    reads, i = [], 0
-    while i < len(lines):
-        i += 1                          # header (whatever it contains)
-        reads.append(lines[i] if i < len(lines) else b"")
-        i += 1
-        if fastq:
-            i += 2
-    return reads
-
-
 def _load_split(ctx, text, fastq, chunk):
     """stream `text` through fgpu_text_split in chunks of `chunk` bytes, carrying the unconsumed tail, into a load pass"""
     ctx.load_begin()
@@ -1052,13 +1038,13 @@ def test_device_record_splitting_edge_cases_follow_getline(fastq):
         return (b"@r%d\n" % i + s + b"\n+\n" + b"I" * len(s) + b"\n") if fastq else (b">r%d\n" % i + s + b"\n")
     full = b"".join(record(i, s) for i, s in enumerate(seqs))
     texts = [full, full[:-1],                       # no final newline
-             full + (b"@last\n" if fastq else b">last\n"),        # header without a sequence line: an empty read
-             full + (b"@last" if fastq else b">last"),            # ... unterminated
+             full + b"GATTACATTGCA\n",                   # header (any line: here one with k-mers of its own) without a sequence line: an empty read
+             full + b"GATTACATTGCA",                     # ... unterminated: the reference's one string still holds it when the sequence's getline fails -- the read
              full + (b"@x\nACGTACGTAC" if fastq else b">x\nACGTACGTAC"),   # unterminated sequence line / missing FASTQ tail
              full + (b"@x\nACGTACGTAC\n+" if fastq else b">x\nACGTACGTAC\n>y"),
-             b"\n\n" + full, b"", b"\n", b"ACGT"]
+             b"\n\n" + full, b"", b"\n", b"ACGT", b"ACGTTGCATT"]       # (a single line without a newline: header and read at once)
     for text in texts:
-        want = _getline_records(text, fastq)
+        want = getline_ref.reads(text, fastq)      # (tests/getline_ref.py: the reading loop as a stream simulation, pinned to the compiled reference)
         for chunk in (1 << 20, 7, 23):
             ctx = api.Context(k, 1 << 12, 2)
             st, n_reads = _load_split(ctx, text, fastq, chunk)
