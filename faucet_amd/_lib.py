@@ -109,6 +109,12 @@ SIGNATURES = {
     "fgpu_load_batch_packed_reads": (C.c_int, [_vp, _P(Packed), _P(KeptReads)]),
     "fgpu_scan_kept_state": (C.c_int, [_vp, _P(C.c_int), _P(_u64), _P(_u64), _P(_u64)]),
     "fgpu_scan_batch_kept": (C.c_int, [_vp, _u64, _P(_u64)]),
+    "fgpu_scan_kept_range": (C.c_int, [_vp, _u64, _u64, _u64, _P(C.c_int)]),
+    "fgpu_scan_prepare_kept": (C.c_int, [_vp, _u64, _P(_u64)]),
+    "fgpu_load_slice_keep_reads": (C.c_int, [_vp]),
+    "fgpu_load_slice_packed_reads": (C.c_int, [_vp, _P(Packed), _P(KeptReads)]),
+    "fgpu_load_slice_expect_reads": (C.c_int, [_vp, _P(Packed), _P(KeptReads)]),
+    "fgpu_load_slice_adopt_reads": (C.c_int, [_vp, _P(Packed), _P(KeptReads)]),
     "fgpu_load_begin": (C.c_int, [_vp, C.c_int]),
     "fgpu_load_batch": (C.c_int, [_vp, _P(Reads)]),
     "fgpu_load_batch_packed": (C.c_int, [_vp, _P(Packed)]),

@@ -369,6 +369,27 @@ class Context:
         """mark + resolve of a packed batch against the slice: what load_slice_batch does behind its packing"""
         self._c(self.lib.fgpu_load_slice_batch_packed(self.h, C.byref(pk)))
 
+    # ... a sliced pass that keeps reads: the offsets of the packed batches travel beside the blocks (faucet_gpu.h)
+    def load_slice_keep_reads(self):
+        """inside a sliced pass, before its first batch: load_slice_pack also keeps every batch's read offsets beside its block"""
+        self._c(self.lib.fgpu_load_slice_keep_reads(self.h))
+
+    def load_slice_packed_reads(self, pk: "L.Packed") -> "L.KeptReads":
+        """the read offsets of a block this context packed (device pointer, n_reads, the longest read it packed: known once the pass has ended)"""
+        kr = L.KeptReads()
+        self._c(self.lib.fgpu_load_slice_packed_reads(self.h, C.byref(pk), C.byref(kr)))
+        return kr
+
+    def load_slice_expect_reads(self, pk: "L.Packed") -> "L.KeptReads":
+        """an empty (n_reads + 1) x 8-byte allocation beside a block from load_slice_expect: the caller fills it, then load_slice_adopt_reads"""
+        kr = L.KeptReads()
+        self._c(self.lib.fgpu_load_slice_expect_reads(self.h, C.byref(pk), C.byref(kr)))
+        return kr
+
+    def load_slice_adopt_reads(self, pk: "L.Packed", kr: "L.KeptReads"):
+        """the filled allocation becomes the resident batch's offsets; checked on the device against the block (reported by the next synchronising call)"""
+        self._c(self.lib.fgpu_load_slice_adopt_reads(self.h, C.byref(pk), C.byref(kr)))
+
     def scan_resident_base(self, first_batch: int):
         """between the passes: batch i of the next scan pairs with the load pass' resident batch first_batch + i"""
         self._c(self.lib.fgpu_scan_resident_base(self.h, first_batch))
@@ -454,6 +475,18 @@ class Context:
         """scan_batch of the reads kept batch i was loaded from, without their text; returns the batch's number of reads"""
         n = C.c_uint64(0)
         self._c(self.lib.fgpu_scan_batch_kept(self.h, int(i), C.byref(n)))
+        return int(n.value)
+
+    def scan_kept_range(self, lo: int, hi: int, max_read_len: int = 0) -> bool:
+        """between the passes: are the kept batches [lo, hi) all resident with their read offsets?  Waits; max_read_len = the pass' longest read over all ranks"""
+        c = C.c_int(0)
+        self._c(self.lib.fgpu_scan_kept_range(self.h, int(lo), int(hi), int(max_read_len), C.byref(c)))
+        return bool(c.value)
+
+    def scan_prepare_kept(self, i: int) -> int:
+        """scan_prepare of the reads kept batch i was loaded from, without their text; returns the batch's number of reads"""
+        n = C.c_uint64(0)
+        self._c(self.lib.fgpu_scan_prepare_kept(self.h, int(i), C.byref(n)))
         return int(n.value)
 
     def scan_prepare(self, batch: ReadBatch):

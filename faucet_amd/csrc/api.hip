@@ -161,6 +161,7 @@ int fgpu_pull_counters(fgpu_ctx* ctx) {
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->cstream));
     FGPU_HIP(hipMemcpyAsync(ctx->counters_host, ctx->counters, sizeof(DevCounters), hipMemcpyDeviceToHost, ctx->stream));
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    if (int rc = fgpu_offs_check_report(ctx)) return rc;      // read offsets adopted from a peer that are not their block's (fgpu_load_slice_adopt_reads)
     // A late junction test that came out true at an unregistered k-mer leaves the lazy scan standing only because k_delta_collect has looked
     // for that k-mer on the window's other pieces.  Every walk and every sweep issued so far has completed here, so each
     // noted position must have been passed over by its window's sweep -- [2] == [0]; if one was not, the scan is treated as void and scanned
@@ -465,7 +466,8 @@ void fgpu_destroy(fgpu_ctx* ctx) {
 
 int fgpu_synchronize(fgpu_ctx* ctx) {
     if (!ctx) return FGPU_ERR_ARG;
-    return sync_all(ctx);
+    if (int rc = sync_all(ctx)) return rc;
+    return fgpu_offs_check_report(ctx);
 }
 
 // ---- pass 1 --------------------------------------------------------------------------------------------------
@@ -739,6 +741,7 @@ int fgpu_scan_begin(fgpu_ctx* ctx) {
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     int rc = fgpu_bg_join(ctx);      // the walk's streams and events (made beside pass 1, fgpu_create)
     if (rc) return rc;
+    if ((rc = fgpu_offs_check_report(ctx))) return rc;
     if ((rc = fgpu_scan_alloc(ctx))) return rc;
     if ((rc = fgpu_scan_reset(ctx))) return rc;
     ctx->fixup_ready = false;   // the load pass' counters go with this reset
@@ -1154,18 +1157,47 @@ int fgpu_scan_kept_state(fgpu_ctx* ctx, int* complete, uint64_t* n_batches, uint
     return FGPU_OK;
 }
 
+// kept batch i of the last load pass for a scan call `who`: after a plain pass every batch has to be there (fgpu_scan_kept_state); after a
+// sliced pass that keeps reads a rank holds offsets for the batches it packed or adopted them for, and is asked batch by batch
+static int kept_batch_at(fgpu_ctx* ctx, const char* who, uint64_t i, const ResidentBatch** out) {
+    const std::string w(who);
+    if (ctx->kept_sliced ? !ctx->keep_reads : !kept_complete(ctx)) {
+        ctx->err = w + ": the last load pass did not keep every batch with its reads (FGPU_LOAD_KEEP_READS, all batches inside the resident budget of " +
+                   std::to_string(ctx->resident_budget) + " bytes; " + std::to_string(ctx->resident_count) + " of " + std::to_string(ctx->pass_batches) + " batches are resident)";
+        return FGPU_ERR_STATE;
+    }
+    if (i >= ctx->resident_count) { ctx->err = w + ": no such batch (empty batches keep nothing)"; return FGPU_ERR_ARG; }
+    if (!ctx->resident[i]->n_reads) {
+        ctx->err = w + ": batch " + std::to_string(i) + " is resident without its read offsets (packed by another rank: fgpu_load_slice_adopt_reads brings them)";
+        return FGPU_ERR_STATE;
+    }
+    *out = ctx->resident[i];
+    return FGPU_OK;
+}
+
+int fgpu_scan_kept_range(fgpu_ctx* ctx, uint64_t lo, uint64_t hi, uint64_t max_read_len, int* complete) {
+    if (!ctx || !complete) return FGPU_ERR_ARG;
+    *complete = 0;
+    if (ctx->phase != 0) { ctx->err = "scan_kept_range while a pass is open: between the load pass and fgpu_scan_begin"; return FGPU_ERR_STATE; }
+    if (lo > hi) { ctx->err = "scan_kept_range: batches [lo, hi) with lo <= hi"; return FGPU_ERR_ARG; }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    if (ctx->stream) FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    if (int rc = fgpu_offs_check_report(ctx)) return rc;
+    if (!ctx->keep_reads || hi > ctx->resident_count || (!ctx->kept_sliced && !kept_complete(ctx))) return FGPU_OK;
+    for (uint64_t i = lo; i < hi; i++)
+        if (!ctx->resident[i]->n_reads) return FGPU_OK;
+    ctx->kept_max_read_len = std::max<uint64_t>(ctx->kept_max_read_len, max_read_len);      // the longest read of the PASS, over all ranks
+    *complete = 1;
+    return FGPU_OK;
+}
+
 int fgpu_scan_batch_kept(fgpu_ctx* ctx, uint64_t i, uint64_t* n_reads_out) {
     if (!ctx) return FGPU_ERR_ARG;
     if (ctx->phase != 2) { ctx->err = "scan_batch_kept outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
     if (!ctx->prepared.empty()) { ctx->err = "scan_batch_kept while prepared batches are waiting: call fgpu_scan_walk_prepared first"; return FGPU_ERR_STATE; }
     if (ctx->hint_in_table) { ctx->err = "the junction table holds a preview (fgpu_scan_import_hint): import the real table before walking"; return FGPU_ERR_STATE; }
-    if (!kept_complete(ctx)) {
-        ctx->err = "scan_batch_kept: the last load pass did not keep every batch with its reads (FGPU_LOAD_KEEP_READS, all batches inside the resident budget of " +
-                   std::to_string(ctx->resident_budget) + " bytes; " + std::to_string(ctx->resident_count) + " of " + std::to_string(ctx->pass_batches) + " batches are resident)";
-        return FGPU_ERR_STATE;
-    }
-    if (i >= ctx->resident_count) { ctx->err = "scan_batch_kept: no such batch (empty batches keep nothing)"; return FGPU_ERR_ARG; }
-    const ResidentBatch* kept = ctx->resident[i];
+    const ResidentBatch* kept = nullptr;
+    if (int rc = kept_batch_at(ctx, "scan_batch_kept", i, &kept)) return rc;
     if (n_reads_out) *n_reads_out = kept->n_reads;
     return scan_batch_from(ctx, nullptr, kept);
 }
@@ -1217,27 +1249,41 @@ static int scan_batch_from(fgpu_ctx* ctx, const fgpu_reads* reads, const Residen
 }
 extern "C" {
 
-int fgpu_scan_prepare(fgpu_ctx* ctx, const fgpu_reads* reads) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 2) { ctx->err = "scan_prepare outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
-    int rc = fgpu_check_reads(ctx, reads);
-    if (rc) return rc;
+// the pure stage of one batch ahead of its walk, from its text (reads) or from a kept batch: the batch joins the prepared ones
+static int scan_prepare_from(fgpu_ctx* ctx, const fgpu_reads* reads, const ResidentBatch* kept) {
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     BatchBufs* b;
     if (!ctx->pool.empty()) { b = ctx->pool.front(); ctx->pool.erase(ctx->pool.begin()); }
     else b = new_batch(ctx);
-    rc = scan_pure_into(ctx, b, reads, true);
+    int rc = scan_pure_into(ctx, b, reads, true, kept);
     ctx->cur = &ctx->bb_default;
     if (rc == FGPU_INTERNAL_REPLAY) {   // (only after walks of this scan: prepare-only scans never get here)
         ctx->pool.insert(ctx->pool.begin(), b);
         if ((rc = scan_replay(ctx))) return rc;
-        return fgpu_scan_prepare(ctx, reads);
+        return scan_prepare_from(ctx, reads, kept);
     }
     if (rc) { ctx->pool.push_back(b); return rc; }
     b->planes_gen = ctx->hint_in_table ? ctx->hint_gen : 0;      // what this batch's snapshot planes speak of
     b->cand_gen = 0;
     ctx->prepared.push_back(b);
     return FGPU_OK;
+}
+
+int fgpu_scan_prepare(fgpu_ctx* ctx, const fgpu_reads* reads) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 2) { ctx->err = "scan_prepare outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
+    int rc = fgpu_check_reads(ctx, reads);
+    if (rc) return rc;
+    return scan_prepare_from(ctx, reads, nullptr);
+}
+
+int fgpu_scan_prepare_kept(fgpu_ctx* ctx, uint64_t i, uint64_t* n_reads_out) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (ctx->phase != 2) { ctx->err = "scan_prepare_kept outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
+    const ResidentBatch* kept = nullptr;
+    if (int rc = kept_batch_at(ctx, "scan_prepare_kept", i, &kept)) return rc;
+    if (n_reads_out) *n_reads_out = kept->n_reads;
+    return scan_prepare_from(ctx, nullptr, kept);
 }
 
 // Read shards: a FRESHER preview has taken the place of the one the batches were prepared against (fgpu_scan_import_hint again: the table the

@@ -112,6 +112,10 @@ struct PackedBlock {
     DevBuf buf;
     uint64_t T = 0, n_words = 0, n_reads = 0;
     int state = 0;               // 0 free, 1 packed here, 2 expected from elsewhere (its digest is checked when it is loaded), 3 loaded
+    // a sliced pass that keeps reads (fgpu_load_slice_keep_reads): the batch's (n_reads + 1) read offsets beside the block, never inside it
+    DevBuf offs;
+    int offs_state = 0;          // 0 none, 1 copied by fgpu_load_slice_pack, 2 made empty for a peer to fill (fgpu_load_slice_expect_reads), 3 adopted
+    uint64_t resident_index = ~0ULL;   // the resident batch the block became (fgpu_load_slice_batch_packed)
 };
 static inline uint64_t fgpu_packed_bytes(uint64_t n_words) { return 3 * (n_words + FGPU_PADW) * 8 + 16; }
 
@@ -225,6 +229,11 @@ struct DevCounters {
     unsigned long long slice_mercy[6];
 };
 
+// what k_offs_check leaves for the host (load_slices.hip): [0] non-zero iff offsets adopted since the last look failed their check, [1] the lowest such batch
+struct OffsCheck {
+    unsigned long long failed, batch;
+};
+
 // (three sets since round 6: with two, the split of chunk c + 1 could only begin when batch c - 1 had finished, and the batch cut out of it was queued
 // with at most a fraction of batch c left to run.  Measured through the command line on config 4's 22 GB: pass 1 1.73 -> 1.75 s, pass 2 1.53 -> 1.43 s,
 // both inside the box's run-to-run spread: the passes are bound by the device's own work, not by the hand-over -- kept because it costs 150 MB)
@@ -306,6 +315,11 @@ struct fgpu_ctx {
     // the longest read of the pass (DevCounters::max_read_len at fgpu_load_end, or what came with adopted blocks): seeds a kept scan's max_piece_span
     bool keep_reads = false;
     uint64_t kept_reads_total = 0, kept_max_read_len = 0, kept_seed = 0;
+    // fgpu_load_slice_keep_reads: the pass that keeps the reads is a sliced one -- a rank holds offsets for the batches it packed and for those whose
+    // offsets it adopted, and a kept scan asks per batch (fgpu_scan_kept_range), not for all of them
+    bool kept_sliced = false;
+    DevBuf offs_check;               // OffsCheck on the device
+    std::vector<uint64_t> offs_unchecked;   // resident batches whose adopted offsets the host has not seen the check of yet
     const ResidentBatch* scan_take_kept = nullptr;   // fgpu_scan_batch_kept: the pure stage in hand takes this batch's sure plane without comparing
     uint64_t scan_batch_index = 0;   // scan batch i pairs with resident[scan_resident_base + i]
     uint64_t scan_resident_base = 0; // fgpu_scan_resident_base: the scan's first batch within the resident batches (0 again at the next load pass)
@@ -565,7 +579,9 @@ void fgpu_touch_scan_table();
 void fgpu_touch_scan_harvest();
 int fgpu_stage_pack(fgpu_ctx* ctx, const fgpu_reads* reads);
 int fgpu_stage_pack_block(fgpu_ctx* ctx, const fgpu_reads* reads, PackedBlock** out);
-int fgpu_packed_acquire(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, int state, const char* who, PackedBlock** out);
+int fgpu_packed_acquire(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, int state, const char* who, PackedBlock** out, uint64_t beside = 0);
+int fgpu_offs_keep(fgpu_ctx* ctx, void* dst, const uint64_t* src, uint64_t n);   // (pack.hip)
+int fgpu_offs_check_report(fgpu_ctx* ctx);                   // the checks of adopted offsets queued so far (load_slices.hip): waits; FGPU_ERR_ARG names the batch
 int fgpu_packed_digest(fgpu_ctx* ctx, const PackedBlock* b, bool verify);
 int fgpu_host_batch_done(fgpu_ctx* ctx, const fgpu_reads* reads);
 // one batch of the plain pass from a packed stream (the batch in hand's planes, or a block's): everything but keeping it resident

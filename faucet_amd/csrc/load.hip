@@ -536,6 +536,8 @@ void fgpu_resident_reset(fgpu_ctx* ctx, bool keep_going) {
     ctx->resident_open = keep_going && ctx->resident_budget > 0;
     ctx->keep_reads = false;                       // (fgpu_load_begin sets it again for a pass with FGPU_LOAD_KEEP_READS)
     ctx->kept_reads_total = ctx->kept_max_read_len = 0;
+    ctx->kept_sliced = false;                      // (fgpu_load_slice_keep_reads)
+    ctx->offs_unchecked.clear();
 }
 
 // The next resident slot, its buffers sized: parts = bytes of {codes, bad, sure, fail, miss} to keep (0: not kept).  The budget arithmetic of

@@ -184,6 +184,31 @@ __global__ void __launch_bounds__(256) k_slice_mercy_commit(const uint64_t* __re
     block_add(&cnt->slice_mercy[5], c.kmers);
 }
 
+// Read offsets that came from another rank, against the block they are said to belong to, before any scan uses them: sends and receives pair
+// up by order, and offsets in the wrong slot would be silently wrong stop lists.  By the format (faucet_gpu.h) read i occupies stream positions
+// offs[i] + i .. offs[i + 1] + i - 1 and the separator behind it, position offs[i + 1] + i, is a bad position; offs[0] = 0, the offsets do not
+// descend, offs[n] + n = T.  One lane per read; every position is compared with T before the bad plane is read, so garbage reads nothing out
+// of bounds (the plane holds ceil(T / 64) + FGPU_PADW words).  A violation: out->failed, and the lowest such batch.
+__global__ void __launch_bounds__(256) k_offs_check(const uint64_t* __restrict__ offs, uint64_t n, uint64_t T, const uint64_t* __restrict__ bad,
+                                                    uint64_t batch, OffsCheck* out) {
+    bool wrong = false;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t a = offs[i], b = offs[i + 1];
+        if (i == 0 && a != 0) wrong = true;
+        if (b < a || b >= T) {             // (b < T: then b + i < 2 T cannot wrap, and n <= T)
+            wrong = true;
+        } else {
+            const uint64_t sep = b + i;    // the separator behind read i
+            if (sep >= T || !((bad[sep >> 6] >> (sep & 63)) & 1ULL)) wrong = true;
+            if (i == n - 1 && sep + 1 != T) wrong = true;
+        }
+    }
+    if (__ballot(wrong) && fd_lane() == 0) {
+        atomicOr(&out->failed, 1ULL);
+        atomicMin(&out->batch, (unsigned long long)batch);
+    }
+}
+
 }  // namespace
 
 // (see fgpu_touch_load)
@@ -246,9 +271,13 @@ static int fgpu_stage_slice_load(fgpu_ctx* ctx) {
     const uint64_t parts[5] = {2 * pb, pb, pb, pb, ctx->slice_mercy ? MERCY_NT * pb : 0};
     ResidentBatch* r;
     uint64_t kept;
-    switch (fgpu_resident_take(ctx, parts, true, &r, &kept)) {
+    // a pass that keeps its reads: the batch's offsets beside its planes, charged with them
+    const uint64_t ob = ctx->keep_reads ? (bb.n_reads + 1) * 8 : 0;
+    const bool no_room = ob && ctx->resident_bytes + parts[0] + parts[1] + parts[2] + parts[3] + parts[4] + ob > ctx->resident_budget;
+    switch (no_room ? (int)FGPU_TAKE_NO_BUDGET : fgpu_resident_take(ctx, parts, true, &r, &kept)) {
     case FGPU_TAKE_NO_BUDGET:
-        ctx->err = "load_slice_batch: the batch does not fit the budget for resident batches (" + std::to_string(ctx->resident_budget) +
+        ctx->err = "load_slice_batch: the batch" + (ob ? " and its " + std::to_string(ob) + " bytes of read offsets do" : std::string(" does")) +
+                   " not fit the budget for resident batches (" + std::to_string(ctx->resident_budget) +
                    " bytes, " + std::to_string(ctx->resident_bytes) + " in use; FGPU_FLAG_NO_RESIDENT sets it to 0): a sliced pass keeps every batch" +
                    (ctx->slice_mercy ? ", under --mercy with four miss planes (9 bits per stream position)" : "");
         return FGPU_ERR_NOMEM;
@@ -259,6 +288,13 @@ static int fgpu_stage_slice_load(fgpu_ctx* ctx) {
     if (int rc = slice_mark_resolve(ctx, bb.codes.p, bb.bad.p, bb.T, bb.n_words, *r)) return rc;
     FGPU_HIP(hipMemcpyAsync(r->codes.p, bb.codes.p, parts[0], hipMemcpyDeviceToDevice, ctx->stream));
     FGPU_HIP(hipMemcpyAsync(r->bad.p, bb.bad.p, pb, hipMemcpyDeviceToDevice, ctx->stream));
+    if (ob) {
+        if (int rc = fgpu_ensure_b(ctx, &r->offs, ob)) return rc;
+        if (int rc = fgpu_offs_keep(ctx, r->offs.p, bb.d_offs, bb.n_reads + 1)) return rc;
+        r->n_reads = bb.n_reads;
+        ctx->kept_reads_total += bb.n_reads;
+        kept += ob;
+    }
     ctx->resident_count++;
     ctx->resident_bytes += kept;
     return FGPU_OK;
@@ -283,6 +319,12 @@ static int fgpu_stage_slice_load_packed(fgpu_ctx* ctx, PackedBlock* b) {
     r->packed_bad = words + 2 * plane_stride;
     if ((rc = slice_mark_resolve(ctx, r->packed_codes, r->packed_bad, b->T, b->n_words, *r))) return rc;
     b->state = 3;
+    b->resident_index = ctx->resident_count;
+    if (b->offs_state == 1) {      // packed here by a pass that keeps its reads: the offsets go with the batch (a peer's come later, fgpu_load_slice_adopt_reads)
+        r->packed_offs = b->offs.p;
+        r->n_reads = b->n_reads;
+        ctx->kept_reads_total += b->n_reads;
+    }
     ctx->resident_count++;
     return FGPU_OK;
 }
@@ -494,6 +536,134 @@ int fgpu_load_slice_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk) {
     ctx->load_stats.reads_processed += b->n_reads;
     return FGPU_OK;
 }
+
+// ---- a sliced pass that keeps reads: the offsets of its packed batches, beside the blocks (faucet_gpu.h) ----------------------------------------
+int fgpu_load_slice_keep_reads(fgpu_ctx* ctx) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (int rc = slice_check(ctx, "load_slice_keep_reads", SLICE_LOADING)) return rc;
+    bool any = ctx->pass_batches != 0 || ctx->resident_count != 0;
+    for (const PackedBlock* b : ctx->packed) any = any || b->state != 0;
+    if (any) { ctx->err = "load_slice_keep_reads after the pass' first batch or block: a pass keeps the reads of all the batches it packs or of none"; return FGPU_ERR_STATE; }
+    ctx->keep_reads = ctx->kept_sliced = true;
+    return FGPU_OK;
+}
+
+// the block of the latest sliced pass a description speaks of, with the resident batch it became (null: not loaded yet)
+static int kept_block_of(fgpu_ctx* ctx, const char* who, const fgpu_packed* pk, PackedBlock** out, ResidentBatch** res) {
+    const std::string w(who);
+    if (ctx->phase != 0 && ctx->phase != 3) { ctx->err = w + " inside a pass that is not a sliced load pass"; return FGPU_ERR_STATE; }
+    if (!ctx->kept_sliced) { ctx->err = w + ": the latest load pass was not a sliced pass that keeps its reads (fgpu_load_slice_keep_reads)"; return FGPU_ERR_STATE; }
+    PackedBlock* b = nullptr;
+    if (pk->block_dev)
+        for (PackedBlock* q : ctx->packed)
+            if (q->buf.p == pk->block_dev && q->state != 0) b = q;
+    if (!b) { ctx->err = w + ": not a block of this pass' fgpu_load_slice_pack / fgpu_load_slice_expect"; return FGPU_ERR_STATE; }
+    if (pk->T != b->T || pk->nbytes != fgpu_packed_bytes(b->n_words) || pk->n_reads != b->n_reads) {
+        ctx->err = w + ": T, nbytes or n_reads are not those the block was made with";
+        return FGPU_ERR_ARG;
+    }
+    *out = b;
+    *res = nullptr;
+    if (b->state == 3 && b->resident_index < ctx->resident_count && ctx->resident[b->resident_index]->packed_codes == b->buf.p) *res = ctx->resident[b->resident_index];
+    return FGPU_OK;
+}
+
+int fgpu_load_slice_packed_reads(fgpu_ctx* ctx, const fgpu_packed* pk, fgpu_kept_reads* out) {
+    if (!ctx || !pk || !out) return FGPU_ERR_ARG;
+    PackedBlock* b;
+    ResidentBatch* r;
+    if (!pk->block_dev && !pk->T && !pk->n_reads) { *out = fgpu_kept_reads{nullptr, 0, 0}; return FGPU_OK; }      // a batch without reads has neither
+    if (int rc = kept_block_of(ctx, "load_slice_packed_reads", pk, &b, &r)) return rc;
+    if (b->offs_state != 1 && b->offs_state != 3) { ctx->err = "load_slice_packed_reads: the block has no read offsets (it was not packed here, and none have been adopted)"; return FGPU_ERR_STATE; }
+    out->offsets_dev = b->offs.p;
+    out->n_reads = b->n_reads;
+    out->max_read_len = ctx->kept_max_read_len;
+    return FGPU_OK;
+}
+
+int fgpu_load_slice_expect_reads(fgpu_ctx* ctx, const fgpu_packed* pk, fgpu_kept_reads* out) {
+    if (!ctx || !pk || !out) return FGPU_ERR_ARG;
+    PackedBlock* b;
+    ResidentBatch* r;
+    if (!pk->block_dev && !pk->T && !pk->n_reads) { *out = fgpu_kept_reads{nullptr, 0, 0}; return FGPU_OK; }      // a batch without reads has neither
+    if (int rc = kept_block_of(ctx, "load_slice_expect_reads", pk, &b, &r)) return rc;
+    if (b->offs_state == 1 || b->offs_state == 3) { ctx->err = "load_slice_expect_reads: the block has its read offsets already"; return FGPU_ERR_STATE; }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    const uint64_t ob = (b->n_reads + 1) * 8;
+    if (b->offs_state == 0) {
+        if (ctx->resident_bytes + ob > ctx->resident_budget) {
+            ctx->err = "load_slice_expect_reads: the " + std::to_string(ob) + " bytes of read offsets of a batch of " + std::to_string(b->n_reads) +
+                       " reads do not fit the budget for resident batches (" + std::to_string(ctx->resident_budget) + " bytes, " + std::to_string(ctx->resident_bytes) + " in use)";
+            return FGPU_ERR_NOMEM;
+        }
+        if (int rc = fgpu_ensure(ctx, &b->offs, ob)) {
+            ctx->err = "load_slice_expect_reads: no device memory for the read offsets (budget " + std::to_string(ctx->resident_budget) + " bytes): " + ctx->err;
+            return rc;
+        }
+        ctx->resident_bytes += ob;
+        b->offs_state = 2;
+    }
+    out->offsets_dev = b->offs.p;
+    out->n_reads = b->n_reads;
+    out->max_read_len = 0;
+    return FGPU_OK;
+}
+
+int fgpu_load_slice_adopt_reads(fgpu_ctx* ctx, const fgpu_packed* pk, const fgpu_kept_reads* kr) {
+    if (!ctx || !pk || !kr) return FGPU_ERR_ARG;
+    PackedBlock* b;
+    ResidentBatch* r;
+    if (!pk->block_dev && !pk->T && !pk->n_reads && !kr->offsets_dev) return FGPU_OK;
+    if (int rc = kept_block_of(ctx, "load_slice_adopt_reads", pk, &b, &r)) return rc;
+    if (b->offs_state != 2) { ctx->err = "load_slice_adopt_reads: no allocation of fgpu_load_slice_expect_reads waits beside this block"; return FGPU_ERR_STATE; }
+    if (!r) { ctx->err = "load_slice_adopt_reads: the block has not been loaded yet (fgpu_load_slice_batch_packed): its bad plane is what the offsets are checked against"; return FGPU_ERR_STATE; }
+    if (kr->offsets_dev != b->offs.p || kr->n_reads != b->n_reads) { ctx->err = "load_slice_adopt_reads: not the allocation fgpu_load_slice_expect_reads made for this block"; return FGPU_ERR_ARG; }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    if (!ctx->offs_check.p) {
+        if (int rc = fgpu_ensure(ctx, &ctx->offs_check, sizeof(OffsCheck))) return rc;
+        FGPU_HIP(hipMemsetAsync(ctx->offs_check.p, 0, 8, ctx->stream));
+        FGPU_HIP(hipMemsetAsync((char*)ctx->offs_check.p + 8, 0xFF, 8, ctx->stream));
+    }
+    FGPU_LAUNCH("offs_check", k_offs_check, fgpu_grid(b->n_reads, 256), 256, (const uint64_t*)b->offs.p, b->n_reads, b->T, (const uint64_t*)r->bad_p(),
+                b->resident_index, (OffsCheck*)ctx->offs_check.p);
+    ctx->offs_unchecked.push_back(b->resident_index);
+    b->offs_state = 3;
+    r->packed_offs = b->offs.p;
+    r->n_reads = b->n_reads;
+    ctx->kept_reads_total += b->n_reads;
+    ctx->kept_max_read_len = std::max<uint64_t>(ctx->kept_max_read_len, kr->max_read_len);
+    return FGPU_OK;
+}
+
+}  // extern "C"
+
+// The checks of the offsets adopted since the last look: waits for the context's stream.  A failure takes the offsets of every batch adopted
+// since then away again (only the lowest failing batch is known by name) and leaves the context usable.
+int fgpu_offs_check_report(fgpu_ctx* ctx) {
+    if (ctx->offs_unchecked.empty()) return FGPU_OK;
+    OffsCheck oc = {0, 0};
+    FGPU_HIP(hipMemcpyAsync(&oc, ctx->offs_check.p, sizeof(oc), hipMemcpyDeviceToHost, ctx->stream));
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    std::vector<uint64_t> unchecked;
+    unchecked.swap(ctx->offs_unchecked);
+    if (!oc.failed) return FGPU_OK;
+    FGPU_HIP(hipMemsetAsync(ctx->offs_check.p, 0, 8, ctx->stream));
+    FGPU_HIP(hipMemsetAsync((char*)ctx->offs_check.p + 8, 0xFF, 8, ctx->stream));
+    for (uint64_t i : unchecked) {
+        if (i >= ctx->resident_count || !ctx->resident[i]->n_reads) continue;
+        ResidentBatch& r = *ctx->resident[i];
+        ctx->kept_reads_total -= r.n_reads;
+        r.n_reads = 0;
+        r.packed_offs = nullptr;
+        for (PackedBlock* b : ctx->packed)
+            if (b->resident_index == i && b->offs_state == 3) b->offs_state = 2;      // (the allocation stays, charged: it may be filled and adopted again)
+    }
+    ctx->err = "fgpu_load_slice_adopt_reads: the read offsets adopted for batch " + std::to_string(oc.batch) + " are not those of its block (offsets[0] = 0, "
+               "ascending, offsets[n] + n = T, a separator behind every read in the block's bad plane): another batch's offsets, or damaged on their way";
+    return FGPU_ERR_ARG;
+}
+
+extern "C" {
 
 int fgpu_load_slice_plane(fgpu_ctx* ctx, uint64_t batch, void** fail_dev, uint64_t* nbytes) {
     if (!ctx || !fail_dev) return FGPU_ERR_ARG;

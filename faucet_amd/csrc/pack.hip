@@ -375,6 +375,13 @@ __global__ void __launch_bounds__(256) k_packed_digest(const uint64_t* __restric
     if ((threadIdx.x & 63) == 0 && acc) atomicAdd(sum, (unsigned long long)acc);
 }
 
+// the read offsets kept beside a block or a resident batch of a sliced pass: the batch's own, counted from 0 (fgpu_reads.offsets[0] need not be 0,
+// and offsets that travel to another rank are checked against "offsets[0] = 0", k_offs_check)
+__global__ void __launch_bounds__(256) k_offs_rebase(uint64_t* __restrict__ dst, const uint64_t* __restrict__ src, uint64_t n) {
+    const uint64_t off0 = src[0];
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) dst[i] = src[i] - off0;
+}
+
 // a block packed here: its trailer's length (the digest has been summed into trailer[0])
 __global__ void k_packed_seal(unsigned long long* trailer, uint64_t T) { trailer[1] = T; }
 
@@ -388,12 +395,13 @@ __global__ void k_packed_verify(const unsigned long long* __restrict__ trailer, 
 
 // A block for a batch of T stream positions out of the pass' pool (its buffer recycled from an earlier pass where there is one), counted
 // against the resident budget NOW with everything the loaded batch will keep beside it (fail, sure, under --mercy four miss planes).
-int fgpu_packed_acquire(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, int state, const char* who, PackedBlock** out) {
+// `beside`: bytes kept beside the block and charged with it (the read offsets of a pass that keeps its reads).
+int fgpu_packed_acquire(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, int state, const char* who, PackedBlock** out, uint64_t beside) {
     const uint64_t n_words = (T + 63) / 64, pb = (n_words + FGPU_PADW) * 8;
-    const uint64_t need = 5 * pb + (ctx->slice_mercy ? 4 * pb : 0);
+    const uint64_t need = 5 * pb + (ctx->slice_mercy ? 4 * pb : 0) + beside;
     if (!ctx->resident_open || ctx->resident_bytes + need > ctx->resident_budget) {
         ctx->err = std::string(who) + ": a batch of " + std::to_string(T) + " stream positions needs " + std::to_string(need) +
-                   " bytes of the budget for resident batches (" + std::to_string(ctx->resident_budget) + " bytes, " + std::to_string(ctx->resident_bytes) +
+                   " bytes" + (beside ? " (" + std::to_string(beside) + " of them for its read offsets)" : std::string()) + " of the budget for resident batches (" + std::to_string(ctx->resident_budget) + " bytes, " + std::to_string(ctx->resident_bytes) +
                    " in use; FGPU_FLAG_NO_RESIDENT sets it to 0): a sliced pass keeps every batch" +
                    (ctx->slice_mercy ? ", under --mercy with four miss planes (9 bits per stream position)" : "");
         return FGPU_ERR_NOMEM;
@@ -414,6 +422,8 @@ int fgpu_packed_acquire(fgpu_ctx* ctx, uint64_t T, uint64_t n_reads, int state, 
     b->n_words = n_words;
     b->n_reads = n_reads;
     b->state = state;
+    b->offs_state = 0;
+    b->resident_index = ~0ULL;
     ctx->resident_bytes += need;
     *out = b;
     return FGPU_OK;
@@ -435,6 +445,12 @@ int fgpu_packed_digest(fgpu_ctx* ctx, const PackedBlock* b, bool verify) {
     return FGPU_OK;
 }
 
+// n offsets of a batch, device to device and counted from 0, into what a sliced pass keeps of it
+int fgpu_offs_keep(fgpu_ctx* ctx, void* dst, const uint64_t* src, uint64_t n) {
+    FGPU_LAUNCH("offs_rebase", k_offs_rebase, fgpu_grid(n, 256), 256, (uint64_t*)dst, src, n);
+    return FGPU_OK;
+}
+
 // fgpu_load_slice_pack: the batch packed straight into a block of the pass; *out = nullptr for a batch without reads.  Nothing of the batch
 // in hand (ctx->cur) is touched: a mercy pass may still owe its latest batch the probe.
 int fgpu_stage_pack_block(fgpu_ctx* ctx, const fgpu_reads* reads, PackedBlock** out) {
@@ -445,12 +461,18 @@ int fgpu_stage_pack_block(fgpu_ctx* ctx, const fgpu_reads* reads, PackedBlock** 
     int rc = pack_source(ctx, reads, &src);
     if (rc) return rc;
     PackedBlock* b = nullptr;
-    if ((rc = fgpu_packed_acquire(ctx, src.total + n, n, 1, "load_slice_pack", &b))) return rc;
+    // a pass that keeps its reads (fgpu_load_slice_keep_reads): the (n + 1) offsets beside the block, charged with it
+    const uint64_t ob = ctx->keep_reads ? (n + 1) * 8 : 0;
+    if ((rc = fgpu_packed_acquire(ctx, src.total + n, n, 1, "load_slice_pack", &b, ob))) return rc;
     uint64_t* words = (uint64_t*)b->buf.p;
     if ((rc = pack_run(ctx, src, n, b->n_words, words, words + 2 * (b->n_words + FGPU_PADW), &ctx->cur->readflag)) ||
-        (rc = fgpu_packed_digest(ctx, b, false))) {
+        (rc = fgpu_packed_digest(ctx, b, false)) || (ob && (rc = fgpu_ensure(ctx, &b->offs, ob)))) {
         b->state = 0;
         return rc;
+    }
+    if (ob) {      // (the offsets are the caller's, or a staging set's: valid while this call queues its work)
+        if ((rc = fgpu_offs_keep(ctx, b->offs.p, src.d_offs, n + 1))) { b->state = 0; return rc; }
+        b->offs_state = 1;
     }
     *out = b;
     return FGPU_OK;

@@ -6,6 +6,11 @@
 // learns what to expect from whom, and how many batches a shard has once its owner has CLOSED it.  Every rank therefore sees the same list,
 // which is what lets them make the same sequence of collective calls.
 //
+// The stream's batches come onto the board in one of two ways, and StreamCursor walks either in the stream's order:
+//   by shards  (a regular file)  rank r posts the batches of its own file-order share; global order = shard 0's batches, shard 1's, ...
+//   by turns   (a pipe)          the ranks take turns at ONE reader: chunk g is posted by rank g mod N as its batch g / N; global order = g
+// "Global batch g is (owner, j) on the board" is all the consumers need to know.
+//
 // Nothing here knows about devices: the standard library only, so it can be tested alone (tests/host/batch_board_check.cpp).
 #pragma once
 #include <stdint.h>
@@ -87,6 +92,38 @@ private:
     std::condition_variable cv_;
     std::vector<Shard> shards_;
     bool aborted_ = false;
+};
+
+// The board's batches in the order of the stream, one consumer's view (every consumer has a cursor of its own)
+class StreamCursor {
+public:
+    StreamCursor(BatchBoard* board, bool by_turns) : board_(board), by_turns_(by_turns) {}
+    // Blocks like BatchBoard::wait.  BATCH: the stream's next batch is batch *j of *owner; CLOSED: the stream has ended; ABORTED.
+    BatchBoard::Wait next(int* owner, uint64_t* j, BoardBatch* out) {
+        const int n = board_->n_shards();
+        if (n <= 0) return BatchBoard::CLOSED;
+        if (by_turns_) {      // chunk g belongs to rank g mod n: the first turn that finds its owner closed is the end of the stream
+            *owner = (int)(g_ % (uint64_t)n);
+            *j = g_ / (uint64_t)n;
+            const BatchBoard::Wait w = board_->wait(*owner, *j, out);
+            if (w == BatchBoard::BATCH) g_++;
+            return w;
+        }
+        while (shard_ < n) {
+            const BatchBoard::Wait w = board_->wait(shard_, j_, out);
+            if (w == BatchBoard::CLOSED) { shard_++; j_ = 0; continue; }
+            if (w == BatchBoard::BATCH) { *owner = shard_; *j = j_++; g_++; }
+            return w;
+        }
+        return BatchBoard::CLOSED;
+    }
+    uint64_t taken() const { return g_; }      // batches handed out so far = the global number of the next one
+
+private:
+    BatchBoard* board_;
+    bool by_turns_;
+    uint64_t g_ = 0, j_ = 0;
+    int shard_ = 0;
 };
 
 }  // namespace faucet_host

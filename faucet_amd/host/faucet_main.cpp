@@ -618,20 +618,35 @@ faucet_host::ShardOptions shard_options_of(const Options& o, const fgpu_params& 
     // every shard reads its share through buffers of its own: chunks no larger than a share needs
     uint64_t chunk_bytes = o.chunk_bytes, largest = 0;
     largest_input(o, &largest);
+    const bool all_regular = largest_input(o, &largest);
     const uint64_t share = largest / (uint64_t)o.gpus + (4u << 20);
-    if (share < chunk_bytes) chunk_bytes = ((share >> 20) + 1) << 20;
-    return faucet_host::shard_options(o.gpus, o.transport == "rccl" ? FGPU_TRANSPORT_RCCL : FGPU_TRANSPORT_COPY, prm, o.fastq, o.mercy, o.paired_ends,
-                                      o.no_cleaning, chunk_bytes);
+    if (all_regular && share < chunk_bytes) chunk_bytes = ((share >> 20) + 1) << 20;      // (a pipe's size is not known: the chunks -chunk_mb asks for)
+    faucet_host::ShardOptions so = faucet_host::shard_options(o.gpus, o.transport == "rccl" ? FGPU_TRANSPORT_RCCL : FGPU_TRANSPORT_COPY, prm, o.fastq, o.mercy,
+                                                              o.paired_ends, o.no_cleaning, chunk_bytes);
+    so.scan_kept = o.scan_kept && ShardedRun::slices_asked();
+    return so;
 }
 
 // ---- the run's contexts.  0, or the exit code of a failure
 int open_shards(const Options& o, const fgpu_params& prm, bool verbose, Run* run) {
     if (o.batch_reads) { fprintf(stderr, "-batch_reads (records split on the host) cannot be combined with -gpus: the shards split their records on their devices\n"); return 1; }
+    const bool slices = ShardedRun::slices_asked();
     for (const std::string* f : {&o.read_load_file, &o.read_scan_file}) {      // (before any device is touched)
         struct stat st;
         if (o.from_bloom && f == &o.read_load_file) continue;
+        // --scan_kept under filter slices: -read_load_file is read once and may be a pipe; a scan file, where one was given, is only looked
+        // at if pass 2 has to fall back to it
+        if (slices && o.scan_kept && f == &o.read_scan_file) continue;
         if (stat(f->c_str(), &st) != 0) { fprintf(stderr, "cannot open %s\n", f->c_str()); return 2; }
-        if (!S_ISREG(st.st_mode)) { fprintf(stderr, "%s is not a regular file: with -gpus the read shards are byte ranges of their input (pipes need -gpus 1)\n", f->c_str()); return 2; }
+        if (slices && o.scan_kept && f == &o.read_load_file) continue;
+        if (!S_ISREG(st.st_mode)) {
+            if (slices)
+                fprintf(stderr, "%s is not a regular file: under FAUCET_SHARD_PROTOCOL=slices a pipe can be the run's only input with --scan_kept (pass 2 then scans "
+                                "the reads pass 1 kept); without it there is no second stream to shard\n", f->c_str());
+            else
+                fprintf(stderr, "%s is not a regular file: with -gpus the read shards are byte ranges of their input (pipes need -gpus 1)\n", f->c_str());
+            return 2;
+        }
     }
     const int ndev = fgpu_device_count();
     if (ndev < 1) { fprintf(stderr, "fgpu_create failed (%d): no gfx950 device\n", FGPU_ERR_HIP); return 2; }
@@ -894,7 +909,7 @@ int load_kept(fgpu_ctx* ctx, KeptReads& kept, PhaseClock& clk, faucet_host::Shar
 
 int load_shards(const Options& o, ShardedRun& run, PhaseClock& clk, faucet_host::ShardLoadResult* out) {
     if (int rc = run.load(o.read_load_file, out)) { fprintf(stderr, "load pass failed (%d): %s\n", rc, run.error().c_str()); return 2; }
-    clk.mark(out->slices ? "pass 1 (shards, filter slices)" : out->fixup ? "pass 1 (shards, fix-up protocol)" : "pass 1 (shards, presence protocol)");
+    clk.mark(out->slices && run.reads_kept() ? "pass 1 (shards, filter slices, reads kept)" : out->slices ? "pass 1 (shards, filter slices)" : out->fixup ? "pass 1 (shards, fix-up protocol)" : "pass 1 (shards, presence protocol)");
     fprintf(stdout, "\rreads consumed: %lld", (long long)out->stats.reads_processed);
     return 0;
 }
@@ -1051,12 +1066,32 @@ int decide_scan_kept(const Options& o, fgpu_ctx* ctx, BloomFile& bloom, const Ph
     return 2;
 }
 
+// --scan_kept over filter slices, after pass 1: does every rank hold the reads of its range?  As decide_scan_kept: if not, a regular file that
+// came with a -read_scan_file is scanned from the text (one note); otherwise the run ends here, exit code 2, with <prefix>.bloom written
+int decide_scan_kept_shards(const Options& o, ShardedRun& run, BloomFile& bloom, bool* from_kept) {
+    *from_kept = run.reads_kept();
+    if (*from_kept) return 0;
+    struct stat st;
+    const bool regular = stat(o.read_load_file.c_str(), &st) == 0 && S_ISREG(st.st_mode);
+    const bool scan_regular = o.scan_file_flag && stat(o.read_scan_file.c_str(), &st) == 0 && S_ISREG(st.st_mode);
+    if (regular && scan_regular) {
+        fprintf(stderr, "note: --scan_kept: the ranks could not keep all of their reads on the device (%llu bytes kept, budget %llu bytes): pass 2 reads %s\n",
+                (unsigned long long)run.kept_bytes(), (unsigned long long)run.kept_budget(), o.read_scan_file.c_str());
+        return 0;
+    }
+    fprintf(stderr, "--scan_kept: the ranks could not keep all of their reads on the device (%llu bytes kept, budget %llu bytes) and there is no input pass 2 could "
+                    "read instead.  %s.bloom has been written: -bloom_file %s.bloom -read_scan_file <the reads> finishes the job\n",
+            (unsigned long long)run.kept_bytes(), (unsigned long long)run.kept_budget(), o.file_prefix.c_str(), o.file_prefix.c_str());
+    (void)bloom.complete();
+    return 2;
+}
+
 // pass 2 over the read shards: the last shard ends with the run's junction map and pair filters, the counts are the sum over the shards
-int scan_shards(const Options& o, ShardedRun& run, PairFilter& short_pf, PairFilter& long_pf, faucet_host::ScanPassResult* res) {
+int scan_shards(const Options& o, ShardedRun& run, PairFilter& short_pf, PairFilter& long_pf, faucet_host::ScanPassResult* res, bool from_kept) {
     fgpu_ctx* ctx = run.last_ctx();
     run.set_pair_filters(o.no_cleaning ? 0 : short_pf.tai, short_pf.n_hash, o.paired_ends && !o.no_cleaning ? long_pf.tai : 0, long_pf.n_hash);
     faucet_host::ShardScanResult sr;
-    if (int rc = run.scan(o.read_scan_file, &sr)) { fprintf(stderr, "junction scan failed (%d): %s\n", rc, run.error().c_str()); return 2; }
+    if (int rc = run.scan(o.read_scan_file, &sr, from_kept)) { fprintf(stderr, "junction scan failed (%d): %s\n", rc, run.error().c_str()); return 2; }
     fprintf(stdout, "\rreads scanned: %lld", (long long)sr.stats.reads_processed);
     if (!o.no_cleaning) CHECK(fgpu_scan_short_pairs_download(ctx, short_pf.bits.data(), short_pf.bits.size()));
     if (o.paired_ends && !o.no_cleaning) {
@@ -1078,10 +1113,10 @@ int scan_and_write(const Options& o, const Run& run, PairFilter& short_pf, PairF
     CHECK(fgpu_bloom_weight(ctx, FGPU_BLOO2, &w2));
     printf("Weight before read scan: %f \n", w2);
     faucet_host::ScanPassResult res;
-    if (int rc = run.shards ? scan_shards(o, *run.shards, short_pf, long_pf, &res) : from_kept ? scan_kept_one_device(o, ctx, kept_batches, short_pf, long_pf, clk, &res)
+    if (int rc = run.shards ? scan_shards(o, *run.shards, short_pf, long_pf, &res, from_kept) : from_kept ? scan_kept_one_device(o, ctx, kept_batches, short_pf, long_pf, clk, &res)
                                                                                                : scan_one_device(o, ctx, short_pf, long_pf, clk, &res)) return rc;
     time(&stop);
-    clk.mark(run.shards ? "pass 2 (shards)" : from_kept ? "pass 2 (scan of kept reads)" : "pass 2 (read + scan)");
+    clk.mark(run.shards && from_kept ? "pass 2 (shards, scan of kept reads)" : run.shards ? "pass 2 (shards)" : from_kept ? "pass 2 (scan of kept reads)" : "pass 2 (read + scan)");
     return write_scan_outputs(o, ctx, res.stats, res.empty_count, res.not_empty_count, difftime(stop, start), short_pf, long_pf, clk);
 }
 
@@ -1093,8 +1128,19 @@ int main(int argc, char** argv) {
     KeptReads kept;
     if (handle_arguments(argc, argv, o) == 1) return 1;
     if (o.scan_kept) {      // refused before any input is opened and before anything is printed or written
-        if (o.gpus > 1) { fprintf(stderr, "--scan_kept needs -gpus 1: read shards and filter slices keep batches of their own\n"); return 2; }
+        const bool slices = o.gpus > 1 && ShardedRun::slices_asked();      // (filter slices: every rank ends pass 1 holding the whole stream)
+        if (o.gpus > 1 && !slices) { fprintf(stderr, "--scan_kept needs -gpus 1: read shards and filter slices keep batches of their own\n"); return 2; }
+        if (slices && o.batch_reads) {
+            fprintf(stderr, "--scan_kept with -gpus %d cannot be combined with -batch_reads: the ranks split their records on their devices (leave -batch_reads out)\n", o.gpus);
+            return 2;
+        }
         if (o.from_bloom) { fprintf(stderr, "--scan_kept cannot be combined with -bloom_file: without pass 1 no reads are kept (give -read_scan_file and leave --scan_kept out)\n"); return 2; }
+        if (slices && !ShardedRun::scan_kept_linked()) {
+            fprintf(stderr, "--scan_kept with -gpus %d: the library this program is linked against lacks the entry points of the sliced pass that keeps its reads "
+                            "(fgpu_load_slice_keep_reads, fgpu_load_slice_packed_reads, fgpu_load_slice_expect_reads, fgpu_load_slice_adopt_reads, "
+                            "fgpu_scan_kept_range, fgpu_scan_batch_kept, fgpu_scan_prepare_kept): run with -gpus 1, or give -read_scan_file and leave --scan_kept out\n", o.gpus);
+            return 2;
+        }
         if (!faucet_host::scan_kept_linked() || !fgpu_estimate_keep_reads || !fgpu_estimate_take_kept_reads || !fgpu_load_batch_packed_reads) {
             fprintf(stderr, "--scan_kept: the library this program is linked against lacks the entry points of the scan of kept reads "
                             "(fgpu_scan_kept_state, fgpu_scan_batch_kept, fgpu_estimate_keep_reads, fgpu_estimate_take_kept_reads, fgpu_load_batch_packed_reads)\n");
@@ -1123,7 +1169,7 @@ int main(int argc, char** argv) {
     bool from_kept = false;
     uint64_t kept_batches = 0;
     if (o.scan_kept && !o.just_load)
-        if (int rc = decide_scan_kept(o, run.one, bloom, clk, &from_kept, &kept_batches)) return rc;
+        if (int rc = run.shards ? decide_scan_kept_shards(o, *run.shards, bloom, &from_kept) : decide_scan_kept(o, run.one, bloom, clk, &from_kept, &kept_batches)) return rc;
     PairFilter short_pf, long_pf;
     create_pair_filters(o, &short_pf, &long_pf);
     if (o.just_load) return bloom.complete() ? 0 : 2;

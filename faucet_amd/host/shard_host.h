@@ -17,14 +17,21 @@
 //            (FAUCET_SHARD_PROTOCOL=slices, opt-in): every rank packs its own shard's batches and sends the packed blocks to the others, all
 //            load the whole stream into their slice of the bit positions -> OR-allreduce of the batches' fail (miss) planes -> commit ->
 //            all-gather of both filters by the slices' byte ranges (load_slices below)
+//            With ShardOptions::scan_kept the sliced pass also keeps the reads (fgpu_load_slice_keep_reads) and pass 2 scans the kept batches: the
+//            input is read ONCE, and may then be a pipe -- the ranks take turns at one reader (text_source.h, TurnSource), pass 2's shards
+//            are ranges of the stream's batches (kept_ranges.h), and the read offsets of a batch packed by another rank than its scanner
+//            travel between the passes
 //   pass 2   rank 0 streams its shard and shows the others its junction table after a quarter of it (the preview their pure stage uses);
 //            ranks > 0 run the pure stage of their shard meanwhile (fgpu_scan_prepare), then take the table, the counters and the two
 //            pair filters from the rank below, walk, and hand all four on.  The last rank holds the run's junction map and pair filters.
 #pragma once
 #include <string.h>
 
+#include <sys/stat.h>
+
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <condition_variable>
 #include <string>
@@ -33,6 +40,7 @@
 
 #include "batch_board.h"
 #include "faucet_gpu.h"
+#include "kept_ranges.h"
 #include "text_source.h"
 
 // The sliced pass' entry points are referred to WEAKLY: a library that defines them (libfaucet_gpu.so) resolves them as usual; linked against
@@ -50,6 +58,14 @@
 #pragma weak fgpu_group_allgather
 #pragma weak fgpu_scan_resident_base
 #pragma weak fgpu_diag_long_pairs_state
+// ... those of the sliced pass that keeps its reads and of the scan of kept batches (ShardOptions::scan_kept)
+#pragma weak fgpu_load_slice_keep_reads
+#pragma weak fgpu_load_slice_packed_reads
+#pragma weak fgpu_load_slice_expect_reads
+#pragma weak fgpu_load_slice_adopt_reads
+#pragma weak fgpu_scan_kept_range
+#pragma weak fgpu_scan_batch_kept
+#pragma weak fgpu_scan_prepare_kept
 // ... and so are those of pass 0 over read shards (ShardedRun::estimate)
 #pragma weak fgpu_estimate_begin
 #pragma weak fgpu_estimate_batch
@@ -68,6 +84,7 @@ struct ShardOptions {
     uint64_t short_tai = 0, long_tai = 0; // pair filters (0: none), create_bloom_filter_optimal's sizes (src/Faucet.cpp:266-283)
     int short_hashes = 0, long_hashes = 0;
     bool verbose = false;                 // FGPU_CLI_TIMES: per-rank stage times on stderr
+    bool scan_kept = false;               // filter slices only: pass 1 keeps the reads, pass 2 scans them -- the input is read once (a pipe included)
 };
 
 // The options of a run of n_ranks read shards: rank r on device r % fgpu_device_count() (fewer devices than shards: they share).  The caller
@@ -93,6 +110,8 @@ struct ShardLoadResult {
     float w1 = 0, w2 = 0;                 // Bloom::weight of the run's bloo1 / bloo2
     bool fixup = false;
     bool slices = false;                  // the pass ran by filter slices (FAUCET_SHARD_PROTOCOL=slices)
+    bool reads_kept = false;              // ... and kept the reads: every rank holds the offsets of the batches it scans (ShardedRun::scan, from_kept)
+    uint64_t kept_bytes = 0, kept_budget = 0;   // what a rank keeps resident for that (planes of every batch, offsets of its own range), and may
 };
 
 struct ShardScanResult {
@@ -213,8 +232,29 @@ public:
     }
 
     // ---- pass 1 (load_two_filters, utils/Bloom.cpp:267-350): afterwards every rank holds the run's bloo2, the last rank its bloo1
+    // the entry points ShardOptions::scan_kept needs beside those of the sliced pass
+    static bool scan_kept_linked() {
+        return fgpu_load_slice_keep_reads && fgpu_load_slice_packed_reads && fgpu_load_slice_expect_reads && fgpu_load_slice_adopt_reads &&
+               fgpu_scan_kept_range && fgpu_scan_batch_kept && fgpu_scan_prepare_kept;
+    }
+    static bool slices_asked() {
+        const char* e = getenv("FAUCET_SHARD_PROTOCOL");
+        return e && !strcmp(e, "slices");
+    }
+
     int load(const std::string& path, ShardLoadResult* out) {
         std::vector<uint64_t> cuts;
+        struct stat st_in;
+        if (o_.scan_kept && slices_asked() && stat(path.c_str(), &st_in) == 0 && !S_ISREG(st_in.st_mode)) {
+            // one stream that can be read once: no byte ranges, the ranks take turns at it (load_slices)
+            uint64_t b = ~0ULL;
+            for (int r = 0; r < o_.n_ranks; r++) {
+                uint64_t rb = 0;
+                if (fgpu_load_fixup_state(ctx_[(size_t)r], nullptr, &rb) != FGPU_OK) rb = 0;
+                b = std::min(b, rb);
+            }
+            return load_slices(path, cuts, b, out);
+        }
         if (!record_cuts(path, o_.fastq ? 4 : 2, o_.paired_ends ? 2 : 1, o_.n_ranks, &cuts)) {
             error_ = "cannot cut " + path + " into read shards: with several GPUs the input must be a regular file";
             return FGPU_ERR_ARG;
@@ -322,20 +362,30 @@ public:
     // order, so that all ranks load the same batches and make the same sequence of collectives.
     int load_slices(const std::string& path, const std::vector<uint64_t>& cuts, uint64_t budget, ShardLoadResult* out) {
         const int n = o_.n_ranks;
+        const bool by_turns = cuts.empty();                  // a pipe: no byte ranges, one reader the ranks take turns at
         if (!slices_linked()) {
             error_ = "FAUCET_SHARD_PROTOCOL=slices: the library this program is linked against lacks the entry points of the sliced pass "
                      "(fgpu_load_slice_*, fgpu_group_allgather, fgpu_scan_resident_base)";
             return FGPU_ERR_STATE;
         }
+        if (o_.scan_kept && !scan_kept_linked()) {
+            error_ = "FAUCET_SHARD_PROTOCOL=slices with kept reads: the library this program is linked against lacks the entry points "
+                     "(fgpu_load_slice_keep_reads, fgpu_load_slice_packed_reads, fgpu_load_slice_expect_reads, fgpu_load_slice_adopt_reads, "
+                     "fgpu_scan_kept_range, fgpu_scan_batch_kept, fgpu_scan_prepare_kept)";
+            return FGPU_ERR_STATE;
+        }
         if (const char* e = getenv("FAUCET_DEBUG_SLICES_BUDGET")) budget = strtoull(e, nullptr, 10);      // tests: "the ranks keep this many bytes resident"
         // every rank keeps every batch: 5 bits per stream position (codes, bad, fail, sure), 9 with the four miss planes of --mercy; a stream
-        // position per input byte is the upper bound (headers and quality lines only lower it)
-        const uint64_t input = cuts.back(), bits = o_.mercy ? 9 : 5, need = input / 8 * bits + (input % 8 * bits + 7) / 8;
-        if (need > budget) {
-            error_ = "FAUCET_SHARD_PROTOCOL=slices: every rank keeps the whole input resident in its packed form: " + std::to_string(input) +
-                     " bytes of input x " + (o_.mercy ? "9/8 (--mercy)" : "5/8") + " = " + std::to_string(need) + " bytes, the ranks' smallest budget for resident batches is " +
-                     std::to_string(budget) + " bytes";
-            return FGPU_ERR_NOMEM;
+        // position per input byte is the upper bound (headers and quality lines only lower it).  (A pipe's size is not known: there the
+        // batches are counted as they come, SliceKept::add.)
+        if (!by_turns) {
+            const uint64_t input = cuts.back(), bits = o_.mercy ? 9 : 5, need = input / 8 * bits + (input % 8 * bits + 7) / 8;
+            if (need > budget) {
+                error_ = "FAUCET_SHARD_PROTOCOL=slices: every rank keeps the whole input resident in its packed form: " + std::to_string(input) +
+                         " bytes of input x " + (o_.mercy ? "9/8 (--mercy)" : "5/8") + " = " + std::to_string(need) + " bytes, the ranks' smallest budget for resident batches is " +
+                         std::to_string(budget) + " bytes";
+                return FGPU_ERR_NOMEM;
+            }
         }
         // slice bounds: tai bits over n ranks in units of 512 bits (64 bytes), the last ones short or empty
         const uint64_t nbytes = o_.prm.tai / 8;
@@ -346,14 +396,33 @@ public:
             for (int q = 0; q <= n; q++) bounds[(size_t)q] = std::min<uint64_t>((uint64_t)q * step, nbytes);
         }
         BatchBoard board(n);
+        std::unique_ptr<TextSource> stream;
+        std::unique_ptr<TurnSource> turns;
+        if (by_turns) {
+            stream.reset(new TextSource(path, o_.fastq, o_.chunk_bytes, 0, ~0ULL, bufs_[0].p));
+            if (!stream->is_open()) { error_ = "cannot open " + path; return FGPU_ERR_ARG; }
+            turns.reset(new TurnSource(stream.get(), n));
+        }
+        SliceShared sh;
+        sh.board = &board;
+        sh.turns = turns.get();
+        sh.budget = budget;
+        sh.longest.assign((size_t)n, 0);
         std::vector<fgpu_load_stats> st((size_t)n);
         std::vector<uint64_t> counts((size_t)n, 0);
         float w1 = 0, w2 = 0;
+        kept_ready_ = false;
+        kept_bounds_.clear();
         int rc = run_ranks([&](int r) -> int {
-            const int rc_rank = slice_rank(r, path, cuts, bounds, &board, &st[(size_t)r], r == 0 ? &counts : nullptr, &w1, &w2);
-            if (rc_rank != FGPU_OK) board.abort();           // (ranks that wait for a batch of this one wake up and fail)
+            const int rc_rank = slice_rank(r, path, cuts, bounds, &sh, &st[(size_t)r], r == 0 ? &counts : nullptr, &w1, &w2);
+            if (rc_rank != FGPU_OK) {                        // (ranks that wait for a batch or a turn of this one wake up and fail)
+                board.abort();
+                if (turns) turns->abort();
+            }
             return rc_rank;
         });
+        turns.reset();
+        stream.reset();
         if (rc != FGPU_OK) return rc;
         sliced_counts_ = counts;
         out->stats = st[0];                                  // the stats of a sliced pass are the whole run's on every rank: one rank's, not a sum
@@ -361,6 +430,12 @@ public:
         out->w2 = w2;
         out->fixup = false;
         out->slices = true;
+        out->reads_kept = kept_ready_;
+        out->kept_bytes = kept_bytes_ = sh.kept_bytes;
+        out->kept_budget = kept_budget_ = budget;
+        if (o_.verbose && o_.scan_kept && by_turns)
+            fprintf(stderr, "[cli]   pass 1: the read offsets of %llu of %llu batches changed ranks between the passes\n", (unsigned long long)sh.moved.load(),
+                    (unsigned long long)kept_T_.size());
         return FGPU_OK;
     }
 
@@ -371,20 +446,34 @@ private:
                fgpu_group_allgather && fgpu_scan_resident_base;
     }
 
+    // what the ranks of one sliced pass share beside the board
+    struct SliceShared {
+        BatchBoard* board = nullptr;
+        TurnSource* turns = nullptr;           // a pipe: the one reader (null: every rank reads its own byte range)
+        uint64_t budget = 0;                   // bytes a rank may keep resident
+        uint64_t kept_bytes = 0;               // (rank 0's count: what a rank keeps, see slice_rank step 5)
+        std::vector<uint64_t> longest;         // per rank: the longest read it packed
+        std::atomic<uint64_t> moved{0};        // batches whose offsets changed ranks
+    };
+
     // one rank of load_slices
-    int slice_rank(int r, const std::string& path, const std::vector<uint64_t>& cuts, const std::vector<uint64_t>& bounds, BatchBoard* board,
+    int slice_rank(int r, const std::string& path, const std::vector<uint64_t>& cuts, const std::vector<uint64_t>& bounds, SliceShared* sh,
                    fgpu_load_stats* stats, std::vector<uint64_t>* counts, float* w1, float* w2) {
         fgpu_ctx* c = ctx_[(size_t)r];
+        BatchBoard* board = sh->board;
         const int n = o_.n_ranks;
+        const bool by_turns = sh->turns != nullptr;
         const double t0 = now_ms();
         // 1  open the pass on the own slice
         RANK_CHECK(o_.mercy ? fgpu_load_slice_mercy_begin(c, bounds[(size_t)r] * 8, bounds[(size_t)r + 1] * 8)
                             : fgpu_load_slice_begin(c, bounds[(size_t)r] * 8, bounds[(size_t)r + 1] * 8));
-        // 2  publish: pack the own shard's batches, post them, send them.  Nothing here waits for another rank.  Under --mercy the sends wait
+        if (o_.scan_kept) RANK_CHECK(fgpu_load_slice_keep_reads(c));
+        // 2  publish: pack the own batches, post them, send them.  Nothing here waits for another rank's CONSUMPTION (with one reader a rank
+        //    waits for its turn to read, which the ranks before it give up as soon as their chunk is split).  Under --mercy the sends wait
         //    for the batch's turn in step 3: there every batch is followed by collectives, and point-to-point calls pair up per (source,
         //    destination) in the order they are made -- a block sent now would meet the receive of an earlier batch's plane.
         std::vector<fgpu_packed> own;
-        RANK_TRY(for_each_batch(r, path, cuts, [&](const fgpu_reads* b) -> int {
+        auto publish = [&](const fgpu_reads* b) -> int {
             fgpu_packed pk;
             const int rc = fgpu_load_slice_pack(c, b, &pk);
             if (rc != FGPU_OK) return rc;
@@ -397,45 +486,77 @@ private:
                 for (int q = 0; q < n; q++)
                     if (q != r) GROUP_CHECK(fgpu_group_send_async(group_, r, q, pk.block_dev, pk.nbytes));
             return FGPU_OK;
-        }, nullptr));
+        };
+        if (by_turns) {
+            fgpu_reads b;
+            uint64_t g = 0;
+            for (int more; (more = sh->turns->next(r, c, &b, &g)) != 0;) {
+                if (more == TurnSource::ABORTED) { err_[(size_t)r] = "the run was aborted while this rank waited for its turn at the input"; return FGPU_ERR_STATE; }
+                if (more < 0) { err_[(size_t)r] = std::string("fgpu_text_split failed: ") + fgpu_last_error(c); return -more; }
+                const int rc = publish(&b);
+                if (rc != FGPU_OK) { if (err_[(size_t)r].empty()) err_[(size_t)r] = std::string("a batch call failed: ") + fgpu_last_error(c); return rc; }
+                if (aborted_) { err_[(size_t)r] = "the run was aborted (another rank failed)"; return FGPU_ERR_STATE; }
+            }
+        } else {
+            RANK_TRY(for_each_batch(r, path, cuts, publish, nullptr));
+        }
         board->close(r);
         const double t1 = now_ms();
-        // 3  consume in file order: shard 0's batches, shard 1's, ...; a peer's batch is received into a block of its size
+        // 3  consume in the stream's order (batch_board.h, StreamCursor); a peer's batch is received into a block of its size
         double t_exchange = 0;
         uint64_t loaded = 0;                                  // non-empty batches so far = the index of the next one's planes
-        for (int s = 0; s < n; s++) {
-            uint64_t in_shard = 0;
-            for (uint64_t j = 0;; j++) {
-                BoardBatch bb;
-                const BatchBoard::Wait w = board->wait(s, j, &bb);
-                if (w == BatchBoard::ABORTED) { err_[(size_t)r] = "the run was aborted while this rank waited for a batch of shard " + std::to_string(s); return FGPU_ERR_STATE; }
-                if (w == BatchBoard::CLOSED) break;
-                fgpu_packed pk;
-                if (s == r) {
-                    pk = own[(size_t)j];
-                    if (o_.mercy && pk.block_dev)
-                        for (int q = 0; q < n; q++)
-                            if (q != r) GROUP_CHECK(fgpu_group_send_async(group_, r, q, pk.block_dev, pk.nbytes));
-                } else {
-                    RANK_CHECK(fgpu_load_slice_expect(c, bb.T, bb.n_reads, &pk));
-                    if (pk.block_dev) GROUP_CHECK(fgpu_group_recv(group_, r, s, pk.block_dev, pk.nbytes));
-                }
-                RANK_CHECK(fgpu_load_slice_batch_packed(c, &pk));
-                if (!pk.block_dev) continue;
-                if (o_.mercy) {                               // the lockstep of a mercy pass: the batch's fail plane over all ranks, then its probe
-                    const double tx = now_ms();
-                    void* plane = nullptr;
-                    uint64_t pb = 0;
-                    RANK_CHECK(fgpu_load_slice_plane(c, loaded, &plane, &pb));
-                    GROUP_CHECK(fgpu_group_or_allreduce(group_, r, plane, pb));
-                    RANK_CHECK(fgpu_load_slice_mercy_probe(c));
-                    t_exchange += now_ms() - tx;
-                }
-                loaded++;
-                in_shard++;
+        std::vector<uint64_t> in_shard((size_t)n, 0);
+        std::vector<fgpu_packed> blocks;                      // the non-empty batches in the stream's order ...
+        std::vector<int> owner_of;                            // ... who packed each ...
+        std::vector<uint64_t> Ts, reads_of;                   // ... its stream positions and reads
+        uint64_t planes_bytes = 0;
+        StreamCursor cursor(board, by_turns);
+        for (;;) {
+            BoardBatch bb;
+            int s = 0;
+            uint64_t j = 0;
+            const BatchBoard::Wait w = cursor.next(&s, &j, &bb);
+            if (w == BatchBoard::ABORTED) { err_[(size_t)r] = "the run was aborted while this rank waited for a batch of shard " + std::to_string(s); return FGPU_ERR_STATE; }
+            if (w == BatchBoard::CLOSED) break;
+            fgpu_packed pk;
+            if (s == r) {
+                pk = own[(size_t)j];
+                if (o_.mercy && pk.block_dev)
+                    for (int q = 0; q < n; q++)
+                        if (q != r) GROUP_CHECK(fgpu_group_send_async(group_, r, q, pk.block_dev, pk.nbytes));
+            } else {
+                RANK_CHECK(fgpu_load_slice_expect(c, bb.T, bb.n_reads, &pk));
+                if (pk.block_dev) GROUP_CHECK(fgpu_group_recv(group_, r, s, pk.block_dev, pk.nbytes));
             }
-            if (counts) (*counts)[(size_t)s] = in_shard;
+            RANK_CHECK(fgpu_load_slice_batch_packed(c, &pk));
+            if (!pk.block_dev) continue;
+            if (o_.mercy) {                               // the lockstep of a mercy pass: the batch's fail plane over all ranks, then its probe
+                const double tx = now_ms();
+                void* plane = nullptr;
+                uint64_t pb = 0;
+                RANK_CHECK(fgpu_load_slice_plane(c, loaded, &plane, &pb));
+                GROUP_CHECK(fgpu_group_or_allreduce(group_, r, plane, pb));
+                RANK_CHECK(fgpu_load_slice_mercy_probe(c));
+                t_exchange += now_ms() - tx;
+            }
+            loaded++;
+            in_shard[(size_t)s]++;
+            if (o_.scan_kept) {
+                blocks.push_back(pk);
+                owner_of.push_back(s);
+                Ts.push_back(bb.T);
+                reads_of.push_back(bb.n_reads);
+                // a stream of unknown size is counted as it comes: the same sum on every rank, so all of them stop at the same batch
+                planes_bytes += (o_.mercy ? 9 : 5) * ((bb.T + 63) / 64 + 8) * 8;
+                if (by_turns && planes_bytes > sh->budget) {
+                    err_[(size_t)r] = "FAUCET_SHARD_PROTOCOL=slices: the stream does not fit the ranks' budget for resident batches: " + std::to_string(planes_bytes) +
+                                      " bytes kept after " + std::to_string(loaded) + " batches, budget " + std::to_string(sh->budget) +
+                                      " bytes; a pipe cannot be read again (fewer reads per run, or a file and the read-shard protocols)";
+                    return FGPU_ERR_NOMEM;
+                }
+            }
         }
+        if (counts) *counts = in_shard;
         const double t2 = now_ms();
         // 4  the planes over all ranks (the same batches on every rank: the same sequence of collectives), commit, the filters by slices
         for (uint64_t i = 0; i < loaded; i++) {
@@ -461,21 +582,113 @@ private:
         } else {
             RANK_CHECK(fgpu_synchronize(c));
         }
+        const double t5 = now_ms();
         tell(r, "pass 1 (filter slices): pack + publish %.1f ms, load %.1f ms, exchange of the planes %.1f ms, commit %.1f ms, gather of the filters %.1f ms",
-             t1 - t0, t2 - t1 - t_exchange, t_exchange + (t3 - t2), t4 - t3, now_ms() - t4);
+             t1 - t0, t2 - t1 - t_exchange, t_exchange + (t3 - t2), t4 - t3, t5 - t4);
+        if (!o_.scan_kept) return FGPU_OK;
+        // 5  pass 2's shards over the kept batches.  A file: rank r scans the batches it packed -- no offsets move.  A pipe: contiguous ranges of
+        //    the stream's batches balanced by stream positions (kept_ranges.h), and every batch whose owner is not its scanner has its offsets
+        //    sent from owner to scanner, point to point, in ascending g per (source, destination) pair.  The same arithmetic on every rank.
+        std::vector<uint64_t> range((size_t)n + 1, 0);
+        if (by_turns) {
+            range = kept_scan_ranges(Ts, reads_of, n, o_.paired_ends ? 2 : 1);
+        } else {
+            for (int q = 0; q < n; q++) range[(size_t)q + 1] = range[(size_t)q] + in_shard[(size_t)q];
+        }
+        std::vector<int> scanner_of(blocks.size(), 0);
+        for (int q = 0; q < n; q++)
+            for (uint64_t g = range[(size_t)q]; g < range[(size_t)q + 1]; g++) scanner_of[(size_t)g] = q;
+        // the longest read this rank packed (the library knows it since the pass has ended): every rank needs the pass-wide one
+        for (size_t g = 0; g < blocks.size(); g++)
+            if (owner_of[g] == r) {
+                fgpu_kept_reads mine;
+                RANK_CHECK(fgpu_load_slice_packed_reads(c, &blocks[g], &mine));
+                sh->longest[(size_t)r] = mine.max_read_len;
+                break;
+            }
+        if (!vote(true)) { err_[(size_t)r] = "the run was aborted (another rank failed)"; return FGPU_ERR_STATE; }      // the barrier between the passes
+        uint64_t longest = 0;
+        for (uint64_t l : sh->longest) longest = std::max(longest, l);
+        uint64_t offs_bytes = 0, moved_in = 0;
+        for (size_t g = 0; g < blocks.size(); g++)
+            if (owner_of[g] == r && scanner_of[g] != r) {
+                fgpu_kept_reads mine;
+                RANK_CHECK(fgpu_load_slice_packed_reads(c, &blocks[g], &mine));
+                GROUP_CHECK(fgpu_group_send_async(group_, r, scanner_of[g], mine.offsets_dev, (mine.n_reads + 1) * 8));
+            }
+        for (size_t g = 0; g < blocks.size(); g++) {
+            if (scanner_of[g] != r) continue;
+            offs_bytes += (reads_of[g] + 1) * 8;
+            if (owner_of[g] == r) continue;
+            fgpu_kept_reads theirs;
+            RANK_CHECK(fgpu_load_slice_expect_reads(c, &blocks[g], &theirs));
+            GROUP_CHECK(fgpu_group_recv(group_, r, owner_of[g], theirs.offsets_dev, (theirs.n_reads + 1) * 8));
+            theirs.max_read_len = longest;
+            RANK_CHECK(fgpu_load_slice_adopt_reads(c, &blocks[g], &theirs));      // (checked on the device against the block: reported below)
+            moved_in++;
+        }
+        GROUP_CHECK(fgpu_group_flush(group_, r));
+        int complete = 0;
+        RANK_CHECK(fgpu_scan_kept_range(c, range[(size_t)r], range[(size_t)r + 1], longest, &complete));
+        // what this rank keeps resident against what it may (tests lower the budget: FAUCET_DEBUG_SLICES_BUDGET)
+        uint64_t may = sh->budget;
+        if (const char* e = getenv("FAUCET_DEBUG_SCAN_KEPT_BUDGET")) may = std::min<uint64_t>(may, strtoull(e, nullptr, 10));      // (the one-device run's knob)
+        const bool fits = planes_bytes + offs_bytes <= may;
+        sh->moved += moved_in;
+        if (r == 0) sh->kept_bytes = planes_bytes + offs_bytes;
+        const bool all = vote(complete != 0 && fits);
+        if (aborted_) { err_[(size_t)r] = "the run was aborted (another rank failed)"; return FGPU_ERR_STATE; }
+        if (r == 0) {
+            kept_ready_ = all;
+            kept_bounds_ = range;
+            kept_T_ = Ts;
+        }
+        tell(r, "pass 1 (filter slices): reads kept for batches %llu to %llu of %llu, the offsets of %llu of them from other ranks, %.1f ms%s",
+             (unsigned long long)range[(size_t)r], (unsigned long long)range[(size_t)r + 1], (unsigned long long)blocks.size(), (unsigned long long)moved_in, now_ms() - t5,
+             all ? "" : ": NOT every rank holds its range");
         return FGPU_OK;
     }
 
 public:
 
     // ---- pass 2 (ReadScanner::scanReads, src/ReadScanner.cpp:284-359): afterwards the last rank holds the junction map and the pair filters
-    int scan(const std::string& path, ShardScanResult* out) {
+    // from_kept (after a sliced pass 1 that kept the reads, ShardLoadResult::reads_kept): no input is opened; rank r scans the kept batches of its
+    // range -- fgpu_scan_batch_kept on the first rank, fgpu_scan_prepare_kept on the ranks above -- and the progress that times the two
+    // previews is counted in stream positions instead of bytes.  The hand-over of tables, counters, hints and pair filters is the same.
+    bool reads_kept() const { return kept_ready_; }
+    uint64_t kept_bytes() const { return kept_bytes_; }      // what a rank keeps resident for it, and what it may
+    uint64_t kept_budget() const { return kept_budget_; }
+    int scan(const std::string& path, ShardScanResult* out, bool from_kept = false) {
         std::vector<uint64_t> cuts;
-        if (!record_cuts(path, o_.fastq ? 4 : 2, o_.paired_ends ? 2 : 1, o_.n_ranks, &cuts)) {
+        if (from_kept && !(kept_ready_ && kept_bounds_.size() == (size_t)o_.n_ranks + 1 && scan_kept_linked())) {
+            error_ = "the scan of kept reads needs a sliced pass 1 that kept them on every rank";
+            return FGPU_ERR_STATE;
+        }
+        if (!from_kept && !record_cuts(path, o_.fastq ? 4 : 2, o_.paired_ends ? 2 : 1, o_.n_ranks, &cuts)) {
             error_ = "cannot cut " + path + " into read shards: with several GPUs the input must be a regular file";
             return FGPU_ERR_ARG;
         }
         const int n = o_.n_ranks;
+        // the batches of rank r, in the stream's order, each handed to `each`; after(units of the shard handed out so far) runs behind each:
+        // bytes of text, or -- kept batches -- stream positions
+        auto shard_total = [&](int r) -> uint64_t {
+            if (!from_kept) return cuts[(size_t)r + 1] - cuts[(size_t)r];
+            uint64_t t = 0;
+            for (uint64_t g = kept_bounds_[(size_t)r]; g < kept_bounds_[(size_t)r + 1]; g++) t += kept_T_[(size_t)g];
+            return t;
+        };
+        auto each_batch = [&](int r, const std::function<int(const fgpu_reads*, uint64_t)>& each, const std::function<int(uint64_t)>& after) -> int {
+            if (!from_kept) return for_each_batch(r, path, cuts, [&](const fgpu_reads* b) { return each(b, 0); }, after);
+            uint64_t done = 0;
+            for (uint64_t g = kept_bounds_[(size_t)r]; g < kept_bounds_[(size_t)r + 1]; g++) {
+                const int rc = each(nullptr, g);
+                if (rc != FGPU_OK) { if (err_[(size_t)r].empty()) err_[(size_t)r] = std::string("a kept batch call failed: ") + fgpu_last_error(ctx_[(size_t)r]); return rc; }
+                done += kept_T_[(size_t)g];
+                if (after) { const int rc2 = after(done); if (rc2 != FGPU_OK) return rc2; }
+                if (aborted_) { err_[(size_t)r] = "the run was aborted (another rank failed)"; return FGPU_ERR_STATE; }
+            }
+            return FGPU_OK;
+        };
         const bool short_pairs = !o_.no_cleaning && o_.short_tai, long_filter = o_.paired_ends && !o_.no_cleaning && o_.long_tai;
         hint_ = Announce();
         chain_.assign((size_t)n, Announce());
@@ -496,7 +709,7 @@ public:
                 if (fgpu_diag_long_pairs_state && fgpu_diag_long_pairs_state(c, form) == FGPU_OK && form[0] == 2 && !sparse_said_.exchange(true))
                     fprintf(stderr, "note: the long pair filter (%llu bits) keeps its first-set times per batch (sparse state)\n", (unsigned long long)o_.long_tai);
             }
-            if (!sliced_counts_.empty()) {
+            if (!sliced_counts_.empty() && !from_kept) {
                 // after a sliced pass 1 this rank holds the batches of the whole stream: its own shard's begin behind those of the shards below
                 uint64_t below = 0;
                 for (int q = 0; q < r; q++) below += sliced_counts_[(size_t)q];
@@ -512,16 +725,16 @@ public:
                 // Once a quarter of it is walked the others are shown its table -- an earlier state of the very table they will be handed, which is
                 // all the preview of their pure stage needs (fgpu_scan_import_hint); the hint never enters a result.
                 bool shown = n == 1;
-                const uint64_t quarter = (cuts[1] - cuts[0]) / 4;
+                const uint64_t quarter = shard_total(0) / 4;
                 // Round 6: the rank above this one has nobody to pass it a table, so it is shown a second, later state of this one (after 7/10 of the
                 // shard): its planes and candidate planes are made against a table a few million keys short of the one it is handed, and its
                 // hop is the short one of every later rank (fgpu_scan_refresh_prepared).  Sent without waiting: the scan goes on beside the copy.
                 bool shown_late = n == 1 || !late_hints;
-                const uint64_t late_at = (cuts[1] - cuts[0]) / 10 * 7;
+                const uint64_t late_at = shard_total(0) / 10 * 7;
                 // (both previews: show_table -- asynchronous sends, announced once they are queued)
                 auto show = [&]() -> int { shown = true; return show_table(&hint_buf, 1, n, &hint_); };
                 auto show_late = [&]() -> int { shown_late = true; return show_table(&late_buf, 1, 2, &late_[1]); };
-                RANK_TRY(for_each_batch(r, path, cuts, [&](const fgpu_reads* b) { return fgpu_scan_batch(c, b); },
+                RANK_TRY(each_batch(r, [&](const fgpu_reads* b, uint64_t g) { return b ? fgpu_scan_batch(c, b) : fgpu_scan_batch_kept(c, g, nullptr); },
                                         [&](uint64_t bytes_done) -> int {
                                             if (!shown && bytes_done >= quarter) { const int src = show(); if (src != FGPU_OK) return src; }
                                             if (shown && !shown_late && bytes_done >= late_at) return show_late();
@@ -530,7 +743,8 @@ public:
                 if (!shown) RANK_TRY(show());                 // (a shard without batches still owes the others their preview)
                 if (!shown_late) RANK_TRY(show_late());
                 RANK_CHECK(fgpu_scan_end(c, &st));
-                tell(r, "pass 2: first shard streamed in %.1f ms; valid_reused %llu", now_ms() - t0, (unsigned long long)st.valid_reused);
+                tell(r, "%s: first shard streamed in %.1f ms; valid_reused %llu", from_kept ? "pass 2 (scan of kept reads)" : "pass 2", now_ms() - t0,
+                     (unsigned long long)st.valid_reused);
             } else {
                 // pure stage while the lower shards walk.  It does not wait for the preview: batches prepared before it arrives see an empty table
                 // (every junction test evaluated), the others the preview.
@@ -543,9 +757,9 @@ public:
                     have_hint = true;
                     return FGPU_OK;
                 };
-                RANK_TRY(for_each_batch(r, path, cuts, [&](const fgpu_reads* b) -> int {
+                RANK_TRY(each_batch(r, [&](const fgpu_reads* b, uint64_t g) -> int {
                     if (!have_hint) { const int rc = take_hint(false, true); if (rc != FGPU_OK) return rc; }
-                    return fgpu_scan_prepare(c, b);
+                    return b ? fgpu_scan_prepare(c, b) : fgpu_scan_prepare_kept(c, g, nullptr);
                 }, nullptr));
                 if (!have_hint) RANK_TRY(take_hint(true, false));   // the send is received even when it came too late to be of use
                 if (late_hints && r >= 1) {
@@ -573,8 +787,8 @@ public:
                 RANK_CHECK(fgpu_scan_import_table(c, table_in, n_in, &carried));   // (takes the place of the preview)
                 RANK_CHECK(fgpu_scan_walk_prepared(c));
                 RANK_CHECK(fgpu_scan_end(c, &st));
-                tell(r, "pass 2: pure stage %.1f ms, waited %.1f ms for the table, import + walk %.1f ms; valid_reused %llu", t1 - t0, t2 - t1, now_ms() - t2,
-                     (unsigned long long)st.valid_reused);
+                tell(r, "%s: pure stage %.1f ms, waited %.1f ms for the table, import + walk %.1f ms; valid_reused %llu",
+                     from_kept ? "pass 2 (scan of kept reads)" : "pass 2", t1 - t0, t2 - t1, now_ms() - t2, (unsigned long long)st.valid_reused);
             }
             if (o_.paired_ends) RANK_CHECK(fgpu_scan_long_pairs_download(c, nullptr, 0, &empty[(size_t)r], &not_empty[(size_t)r]));
             if (r < n - 1) {
@@ -777,6 +991,11 @@ private:
     std::vector<Announce> chain_;
     std::vector<Announce> late_;      // the table a rank was handed, passed on to the rank above as a fresher preview
     std::vector<std::vector<void*>> graveyard_{64};
+    // after a sliced pass 1 that kept the reads: every rank holds the offsets of its range; the ranges of pass 2 over the stream's non-empty
+    // batches (n + 1 bounds), and the batches' stream positions
+    bool kept_ready_ = false;
+    uint64_t kept_bytes_ = 0, kept_budget_ = 0;
+    std::vector<uint64_t> kept_bounds_, kept_T_;
     std::vector<uint64_t> sliced_counts_;   // after a sliced pass 1: non-empty batches per read shard (pass 2 finds its own among the resident ones)
     int vote_count_ = 0;
     bool vote_all_ = true, vote_result_ = false;

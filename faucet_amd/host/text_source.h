@@ -250,6 +250,51 @@ private:
     std::condition_variable cv_;
 };
 
+// ONE TextSource read by the threads of N ranks in turns (shard_host.h: a pipe under filter slices): chunk g of the stream, cut at record
+// boundaries as always, is read and split by rank g mod N on its own context.  Reading is serial -- a rank holds the turn from the moment its
+// chunk may be read until fgpu_text_split has returned -- and everything a rank does with its batch afterwards runs beside the next rank's read.
+// abort() wakes every waiter.
+class TurnSource {
+public:
+    TurnSource(TextSource* src, int n_ranks) : src_(src), n_((uint64_t)(n_ranks > 0 ? n_ranks : 1)) {}
+    TurnSource(const TurnSource&) = delete;
+    TurnSource& operator=(const TurnSource&) = delete;
+    enum { ABORTED = -1000 };      // (not a status of the library)
+    // rank's next chunk: 1 = a batch (*g: its number in the stream; device pointers of `ctx`, valid until this rank's next call), 0 = the stream
+    // has ended, ABORTED, or < 0 = -status of a failed fgpu_text_split (which ends the stream for everybody)
+    int next(int rank, fgpu_ctx* ctx, fgpu_reads* out, uint64_t* g) {
+        {
+            std::unique_lock<std::mutex> lk(m_);
+            cv_.wait(lk, [&] { return aborted_ || done_ || turn_ % n_ == (uint64_t)rank; });
+            if (aborted_) return ABORTED;
+            if (done_) return failed_ ? ABORTED : 0;
+        }
+        const int more = src_->next(ctx, out);      // (the turn is this rank's: nobody else is inside)
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            if (more == 1) *g = turn_++;
+            else { done_ = true; failed_ = more < 0; }
+        }
+        cv_.notify_all();
+        return more;
+    }
+    void abort() {
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            aborted_ = true;
+        }
+        cv_.notify_all();
+    }
+
+private:
+    TextSource* src_;
+    const uint64_t n_;
+    uint64_t turn_ = 0;
+    bool done_ = false, failed_ = false, aborted_ = false;
+    std::mutex m_;
+    std::condition_variable cv_;
+};
+
 // Record splitting on the HOST, exactly as the reference's loops do it (utils/Bloom.cpp:280-282,340; src/ReadScanner.cpp:306-308,349):
 //   while (getline(header)) { getline(sequence); ...; if (fastq) getline, getline; }
 // cut into batches of sequence lines: the command line's -batch_reads, and the binding (integration/faucet_binding.cpp), which reads its

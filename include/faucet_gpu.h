@@ -449,6 +449,44 @@ int fgpu_estimate_keep_reads(fgpu_ctx* ctx);
 int fgpu_estimate_take_kept_reads(fgpu_ctx* ctx, fgpu_kept_reads* out, uint64_t cap, uint64_t* n_out);
 int fgpu_load_batch_packed_reads(fgpu_ctx* ctx, const fgpu_packed* b, const fgpu_kept_reads* reads);
 
+/* ---- a SLICED pass that keeps reads: every rank ends pass 1 holding the whole stream, and a rank can scan any batch it has the offsets of ------
+ * After a sliced pass every rank holds every batch in packed form with its `sure` plane; what a scan without the text lacks is the
+ * (n_reads + 1) read offsets, which only the rank that packed a batch has seen.  The block format is fixed (tests/pack_ref.py), so the offsets
+ * travel SEPARATELY from the block, as a plain array of n_reads + 1 uint64:
+ *
+ *     fgpu_load_slice_begin / _mercy_begin(lo, hi);  fgpu_load_slice_keep_reads();                 every rank
+ *     owner:   fgpu_load_slice_pack(reads, &p)                                                     keeps the offsets beside the block
+ *     others:  fgpu_load_slice_expect(T, n, &q) ... fgpu_load_slice_batch_packed(&q)               as without keeping
+ *     ... commit, fgpu_load_slice_end on every rank ...
+ *     owner:   fgpu_load_slice_packed_reads(&p, &src)                                              device pointer, n_reads, longest read it packed
+ *     scanner: fgpu_load_slice_expect_reads(&q, &dst);  fill dst.offsets_dev from src.offsets_dev  (fgpu_group_recv, fgpu_device_copy)
+ *              dst.max_read_len = the maximum over the ranks;  fgpu_load_slice_adopt_reads(&q, &dst)
+ *     fgpu_scan_kept_range(lo, hi, max over the ranks, &complete);  fgpu_scan_begin;  fgpu_scan_batch_kept(i) / fgpu_scan_prepare_kept(i) ...
+ *
+ * _keep_reads: inside a sliced pass, plain or mercy, before its first batch or block (FGPU_ERR_STATE otherwise).  fgpu_load_slice_pack then
+ * also copies the batch's offsets, device to device inside that call and counted from 0, into an allocation beside the block; (n_reads + 1) * 8 bytes more are
+ * charged to the resident budget with the block, and a block or offsets that do not fit are FGPU_ERR_NOMEM with the numbers in the message
+ * (fgpu_load_slice_batch keeps its batch's offsets the same way).  Filters, planes, `sure` and stats are bit for bit those of a sliced pass
+ * without it.  A batch a rank packed itself is resident WITH its offsets once fgpu_load_slice_batch_packed has loaded it.
+ * _packed_reads: the offsets of a block this rank packed (or has adopted offsets for): the context's own memory, valid until the next load
+ * pass; max_read_len = the longest read THIS rank packed, known once the pass has ended (0 inside it).
+ * _expect_reads: an empty (n_reads + 1) * 8-byte allocation beside a block from fgpu_load_slice_expect, charged to the budget (FGPU_ERR_NOMEM
+ * names the numbers); the caller fills all of it.  Called again before the adoption it hands out the same allocation.
+ * _adopt_reads: the filled allocation becomes the offsets of the resident batch the block was loaded as (FGPU_ERR_STATE before
+ * fgpu_load_slice_batch_packed); reads->max_read_len joins the pass' longest read.  The offsets are CHECKED ON THE DEVICE against the block
+ * before any scan uses them -- offsets[0] = 0; ascending; offsets[n] + n = T; for every read the stream position of the separator behind it,
+ * offsets[i + 1] + i, is a bad position of the block -- with every position compared with T before the plane is read.  (The offsets a rank
+ * hands out start at 0 whatever fgpu_reads.offsets[0] was.)  A violation is reported as FGPU_ERR_ARG, naming the batch, by the next
+ * synchronising call (fgpu_synchronize, fgpu_scan_kept_range, fgpu_scan_begin, the end of a pass), as a digest mismatch is; the offsets
+ * adopted since the last such call are then dropped again (their allocations stay and may be filled and adopted once more).
+ * The last three work inside the sliced pass and after its end, until the next load pass begins.  A description without a block (a batch
+ * without reads) has no offsets: FGPU_OK, nothing done.  FGPU_ERR_STATE: the latest load pass was not a sliced pass that keeps reads, or
+ * the description is not of a block of it; FGPU_ERR_ARG: null arguments, T / nbytes / n_reads that are not the block's, another allocation. */
+int fgpu_load_slice_keep_reads(fgpu_ctx* ctx);
+int fgpu_load_slice_packed_reads(fgpu_ctx* ctx, const fgpu_packed* b, fgpu_kept_reads* out);
+int fgpu_load_slice_expect_reads(fgpu_ctx* ctx, const fgpu_packed* b, fgpu_kept_reads* out);
+int fgpu_load_slice_adopt_reads(fgpu_ctx* ctx, const fgpu_packed* b, const fgpu_kept_reads* reads);
+
 /* filters: raw bit arrays, tai/8 bytes, exactly the .bloom file body (utils/Bloom.cpp:571-587) */
 int fgpu_bloom_download(fgpu_ctx* ctx, int which, uint8_t* host_out, uint64_t nbytes);
 /* The same copy, started now and finished by fgpu_bloom_download_wait: it runs on its own copy stream behind the work
@@ -499,7 +537,8 @@ int fgpu_text_split(fgpu_ctx* ctx, const char* text, uint64_t nbytes, int text_o
  * `sure` planes (fgpu_scan_stats.valid_reused).  After a sliced pass a rank holds the batches of the WHOLE stream while its scan shard begins in
  * the middle of them; without this call the scan compares against the wrong batches -- safely (the streams are compared word for word before
  * anything is reused), but the reuse is lost.  Empty batches are not counted (they keep nothing).  0 again at the next load pass.
- * FGPU_ERR_STATE while a pass is open. */
+ * It shifts the batches of fgpu_scan_batch / fgpu_scan_prepare only: the index of fgpu_scan_batch_kept / fgpu_scan_prepare_kept is always the
+ * global one among the pass' non-empty batches.  FGPU_ERR_STATE while a pass is open. */
 int fgpu_scan_resident_base(fgpu_ctx* ctx, uint64_t first_batch);
 int fgpu_scan_begin(fgpu_ctx* ctx);
 /* Pure stage + ordered walk for one batch, in file order. */
@@ -517,9 +556,21 @@ int fgpu_scan_batch(fgpu_ctx* ctx, const fgpu_reads* reads);
  * table, and the harvest of stop lists work as for fgpu_scan_batch, and text batches may be mixed in.  *n_reads_out (may be NULL) = the
  * batch's reads.  The batches live until the next load pass: a later scan of the same context may scan them again.
  * fgpu_scan_batch's preconditions apply (no prepared batches waiting, no preview in the table).  FGPU_ERR_STATE: outside a scan, or the
- * state is not complete; FGPU_ERR_ARG: i >= n_batches. */
+ * state is not complete; FGPU_ERR_ARG: i >= n_batches.
+ * After a SLICED pass that keeps reads (fgpu_load_slice_keep_reads) a rank holds every batch but only some batches' offsets: _scan_batch_kept(i)
+ * works for every resident batch that has them -- i is the global index among the pass' non-empty batches, whatever fgpu_scan_resident_base
+ * says -- and answers FGPU_ERR_STATE for a batch without.  _scan_kept_state stays as above (complete = EVERY batch).
+ * _scan_kept_range: between the load pass and fgpu_scan_begin; *complete = 1 iff batches [lo, hi) are all resident with their offsets (after a
+ * plain pass: iff the state is complete and hi <= n_batches).  It WAITS for the context's stream and reports offsets that failed their check
+ * (FGPU_ERR_ARG, fgpu_load_slice_adopt_reads).  max_read_len: the longest read of the pass over ALL ranks -- a scan of kept batches bounds how
+ * far a piece reaches by it, and under slices a rank has packed only its own batches -- or 0 after a plain pass.
+ * _scan_prepare_kept: the two-step form, fgpu_scan_prepare (below) of the reads batch i was loaded from: ranks above the first run their pure
+ * stage from kept batches, take the hint / the table as always, and walk with fgpu_scan_walk_prepared; fgpu_scan_refresh_prepared works on
+ * batches prepared this way.  Errors as _scan_batch_kept, without its preconditions on prepared batches and previews. */
 int fgpu_scan_kept_state(fgpu_ctx* ctx, int* complete, uint64_t* n_batches, uint64_t* n_reads, uint64_t* bytes);
 int fgpu_scan_batch_kept(fgpu_ctx* ctx, uint64_t i, uint64_t* n_reads_out);
+int fgpu_scan_kept_range(fgpu_ctx* ctx, uint64_t lo, uint64_t hi, uint64_t max_read_len, int* complete);
+int fgpu_scan_prepare_kept(fgpu_ctx* ctx, uint64_t i, uint64_t* n_reads_out);
 /* The same in two steps, so that read shards can do the pure part concurrently and only the
  * ordered walk is serial: scan_prepare runs the pure stage and keeps its bit planes resident
  * (about 1.6 bytes of HBM per base); scan_walk_prepared walks every prepared batch in the order
