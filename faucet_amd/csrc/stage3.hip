@@ -11,6 +11,9 @@
 // The control flow is the one of faucet_amd/stage3.py (findNeighbor in lock-step over fgpu_probe_valid_extension, one device call per step,
 // bookkeeping in numpy), which is pinned on the reference's own findNeighbor (tests/golden/stage3_neighbors_*.jsonl.gz); this kernel is
 // checked against both.  No filter bit and no map entry is looked at on the host.
+//
+// abort = 1 wherever the reference trips an assert instead of returning: dist <= maxDist after the first k-mers (:318), a valid extension
+// at every step up to maxDist (:338-339), and a valid extension at a junction met before maxDist (:355, :370).  Past maxDist it has none.
 #include <hip/hip_runtime.h>
 
 #include "fgpu_ctx.h"
@@ -86,7 +89,7 @@ __global__ void __launch_bounds__(256) k_s3_find_neighbors(const uint64_t* __res
             done = true;
         }
         const int maxd = done ? 0 : s3_dist(packed, idx);
-        int dist = 1, ln = 0, lastnuc = 0, retidx = 4, phase = 0;
+        int dist = 1, ln = 0, lastnuc = 0, retidx = 4, phase = 0;       // phase 0: up to maxDist, 1: past it, 3: at a junction met before it (2, "finished" in stage3.py, is a break here)
         auto forward = [&](int nuc) {                        // DoubleKmer::forward (utils/DoubleKmer.cpp:17-23)
             km = ((km << 2) | (uint64_t)nuc) & fp.kmask;
             rc = (rc >> 2) | ((uint64_t)(nuc ^ 2) << (2 * k - 2));
@@ -143,6 +146,11 @@ __global__ void __launch_bounds__(256) k_s3_find_neighbors(const uint64_t* __res
             if (phase == 1 && dist >= maxd + 2 * max_read_length) { res = sink; break; }   // :376, ran past every possible overlap
             const int ext = s3_valid_extension(km, fp, bloom);
             probes++;
+            if (phase == 3) {                               // "this should be a spacer": assert(getValidJExtension(doubleKmer) >= 0), then the junction
+                if (ext < 0) res.abort = 1;
+                else finish(km, 1, retidx, dist, ln);
+                break;
+            }
             if (ext < 0) {
                 if (phase == 0) res.abort = 1;              // assert(validExtension != -1 / -2)
                 else res = sink;                            // off the real sequence: the sink stands
@@ -159,7 +167,7 @@ __global__ void __launch_bounds__(256) k_s3_find_neighbors(const uint64_t* __res
             bool isj = s3_find(tkeys, tdist, mask, km, other);
             if (phase == 0) {
                 if (dist == maxd) continue;                 // break of the first loop: handled at the top of the next round
-                if (isj) { finish(km, 1, retidx, dist, ln); break; }
+                if (isj) { phase = 3; continue; }           // a junction before maxDist: one more probe at the top of the next round (:355)
             } else if (isj) {                               // past maxDist: overlap test (:391-404)
                 if (s3_dist(other, lastnuc) + maxd - dist >= 0) finish(km, 1, lastnuc, dist, ln);
                 else res = sink;
@@ -172,7 +180,7 @@ __global__ void __launch_bounds__(256) k_s3_find_neighbors(const uint64_t* __res
             isj = s3_find(tkeys, tdist, mask, km, other);
             if (phase == 0) {
                 if (dist == maxd) continue;
-                if (isj) { finish(km, 1, 4, dist, ln); break; }
+                if (isj) { phase = 3; continue; }           // the same on the forward-facing k-mer (:370)
             } else if (isj) {
                 if (s3_dist(other, 4) + maxd - dist >= 0) finish(km, 1, 4, dist, ln);
                 else res = sink;

@@ -8,8 +8,11 @@ chain of dependent filter probes; different calls are independent.  Here all wal
 4 x (contains + jcheck) probes of each), the host does what the reference does between two probes -- advance the DoubleKmer, look
 the junction map up, keep the distance and contig-length bookkeeping.  No filter bit is tested on the host.
 
-Restated from the reference's control flow (not its text); checked against the reference's own findNeighbor on golden maps
-(oracle/_ref/ref_kat neighbors -> tests/golden/stage3_neighbors_*.jsonl.gz, tests/test_gpu_parity.py).
+Restated from the reference's control flow (not its text), its asserts included: a call in which the reference would trip one (:318,
+:338-339, and :355 / :370 -- a junction met before maxDist must itself have exactly one valid extension) comes back with abort = 1.
+Checked against the reference's own findNeighbor on the golden maps, on fresh runs at even and small k and on seeded variants of both
+with thinned maps, damaged filters and shifted distances (oracle/_ref/ref_kat neighbors -> tests/golden/stage3_neighbors_*.jsonl.gz,
+tests/stage3_variants.py, tests/test_stage3_walker.py).
 """
 from __future__ import annotations
 
@@ -47,7 +50,8 @@ class NeighborWalker:
 
     def find_neighbors(self, start_kmers, indices):
         """findNeighbor(junctionMap[start], start, index) for every pair; returns a structured array (kmer, node, rindex, dist, len,
-        abort) in input order.  `abort` marks the calls in which the reference trips one of its asserts."""
+        abort) in input order.  `abort` marks the calls in which the reference trips one of its asserts: dist <= maxDist after the first
+        k-mers, a valid extension at every step up to maxDist, and a valid extension at a junction met before maxDist."""
         k = self.k
         n = len(start_kmers)
         km = np.asarray(start_kmers, dtype=np.uint64).copy()
@@ -69,6 +73,20 @@ class NeighborWalker:
             out["kmer"][m], out["node"][m], out["rindex"][m], out["dist"][m], out["len"][m] = kmer, node, rindex, d, length
             done[m] = True
             phase[m] = 2
+
+        def early_junction(w, rindex):
+            """a junction before maxDist (:354-357, :368-372) "should be a spacer": the reference asserts that it has exactly one valid
+            extension before it returns it -- one more probe of the walks in `w`, which end here either way"""
+            if len(w) == 0:
+                return
+            ext = self.ctx.probe_valid_extension(km[w]).astype(np.int64)
+            self.steps += 1
+            self.probes += len(w)
+            ok, bad = w[ext >= 0], w[ext < 0]
+            finish(ok, km[ok], 1, rindex[ext >= 0], dist[ok], ln[ok])
+            out["abort"][bad] = 1                                                # assert(getValidJExtension(doubleKmer) >= 0)
+            done[bad] = True
+            phase[bad] = 2
 
         # ---- the first one or two k-mers (:251-302)
         back = idx == 4
@@ -138,7 +156,7 @@ class NeighborWalker:
             a = phase[act] == 0
             stop = a & (dist[act] == maxd[act])                                  # break: handled at the top of the next round
             hit = a & ~stop & isj
-            finish(act[hit], km[act[hit]], 1, retidx[act[hit]], dist[act[hit]], ln[act[hit]])
+            early_junction(act[hit], retidx[act[hit]])
             hb = ~a & isj                                                        # past maxDist: overlap test (:391-404)
             if hb.any():
                 w = act[hb]
@@ -157,7 +175,7 @@ class NeighborWalker:
             a = phase[act] == 0
             stop = a & (dist[act] == maxd[act])
             hit = a & ~stop & isj
-            finish(act[hit], km[act[hit]], 1, 4, dist[act[hit]], ln[act[hit]])
+            early_junction(act[hit], np.full(int(hit.sum()), 4, dtype=np.int64))
             hb = ~a & isj
             if hb.any():
                 w = act[hb]

@@ -791,8 +791,10 @@ int fgpu_probe_bloom_junction(fgpu_ctx* ctx, const uint64_t* kmers_host, uint64_
  * Result per walk = the reference's return value: the BaseNode* it would build -- `node` 1: a junction was reached (`kmer` its key, `rindex`
  * the index it was entered through, 4 = backward), 0: a sink (`rindex` as the reference sets it) -- with the distance and the contig
  * length the reference reports through its pointer arguments.  `abort` 1 marks the calls in which the reference trips one of its asserts
- * (dist <= maxDist, validExtension >= 0) instead of returning; 2 = startKmer is not in the map or index is not 0..4.
- * n_probes (may be NULL): getValidJExtension evaluations made, each up to 4 x (Bloom::oldContains + JChecker::jcheck).
+ * (dist <= maxDist after the first k-mers; validExtension >= 0 at every step up to maxDist; getValidJExtension >= 0 at a junction met
+ * before maxDist, :355 and :370) instead of returning; 2 = startKmer is not in the map or index is not 0..4.
+ * n_probes (may be NULL): getValidJExtension evaluations made (the one of an early junction's assert included), each up to 4 x
+ * (Bloom::oldContains + JChecker::jcheck).
  * contigs_out (may be NULL): BfSearchResult::contig of every walk, the sequence getContig (utils/JunctionMap.cpp:133-227) appends to its
  * contig string: walk w's string is `len` bases in contigs_out[w * contig_stride_words ..], 2 bits per base in the reference's code
  * (A 0, C 1, T 2, G 3), 32 bases per word, the first base in the lowest bits; contig_stride_words >= fgpu_stage3_contig_words(k,
