@@ -622,6 +622,7 @@ class Context:
         return self._probe_stage3(self.lib.fgpu_probe_bloom_junction, kmers)
 
     def diag_walk_probe(self):
+        """four zeros: the out-of-order walk these counted is retired (the entry point stays for the ABI)"""
         out = (C.c_uint64 * 4)()
         self._c(self.lib.fgpu_diag_walk_probe(self.h, out))
         return [int(v) for v in out]

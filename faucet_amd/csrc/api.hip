@@ -435,7 +435,7 @@ void fgpu_destroy(fgpu_ctx* ctx) {
     if (ctx->lp.flips_host) hipHostFree(ctx->lp.flips_host);
     if (ctx->lp.ev_open) hipEventDestroy(ctx->lp.ev_open);
     void* ptrs[] = {ctx->lp.bits, ctx->lp.first, ctx->short_pf, ctx->bloo1, ctx->bloo2, ctx->first, ctx->pair, ctx->rec, ctx->slice_first, ctx->slice_pair, ctx->est_planes, ctx->jkeys, ctx->jrecs, ctx->jstamps, ctx->jfilter, ctx->wkeys,
-                    ctx->wbits, ctx->uf_parent, ctx->cl_count, ctx->cl_offset, ctx->cl_fill, ctx->cl_fail, ctx->ko_hk, ctx->ko_occ, ctx->ko_piece, ctx->cl_members, ctx->cl_roots, ctx->counters,
+                    ctx->wbits, ctx->uf_parent, ctx->cl_count, ctx->cl_offset, ctx->cl_fill, ctx->cl_weight, ctx->ko_hk, ctx->ko_occ, ctx->ko_piece, ctx->cl_members, ctx->cl_roots, ctx->counters,
                     ctx->wdesc};
     for (void* p : ptrs) if (p) hipFree(p);
     stop_queue_recycle(ctx);
@@ -1319,13 +1319,8 @@ int fgpu_scan_walk_prepared(fgpu_ctx* ctx) {
     int rc = FGPU_OK;
     if (ctx->lazy_failed) return scan_replay(ctx);      // (walks the prepared batches as well)
     // The batches were prepared before their turn: their snapshot planes speak of a table that has since been replaced (the preview by the real
-    // table) and walked on, so they are made again by the walk stream right before every batch's walk.  FGPU_PREPARED_REFRESH=overlap
-    // (round 5, measured, not the default): batch i + 1's on the main stream WHILE batch i is walked, what batch i creates meanwhile reaching
-    // batch i + 1 through the created-key lists as in a streaming scan -- exact (the sharded tests pass with it), and no faster: the 23 ms of
-    // plane-making leave the chain, 11 ms of contention and 10 ms of registering three batches' created keys per window enter it (first hop of
-    // config 4 on 8 shards 66.2 against 65.4 ms, profiles/r05_hop_refresh_ab.txt).
-    static const bool serial_refresh = !(getenv("FGPU_PREPARED_REFRESH") && getenv("FGPU_PREPARED_REFRESH")[0] == 'o');
-    if (!serial_refresh && !ctx->prepared.empty()) rc = fgpu_scan_refresh_planes(ctx, ctx->prepared[0]);
+    // table) and walked on, so they are made again by the walk stream right before every batch's walk (refresh_snapshot; making batch i + 1's
+    // beside batch i's walk instead was measured and is no faster: DESIGN.md section 10, profiles/r05_hop_refresh_ab.txt).
     for (size_t i = 0; i < ctx->prepared.size() && !rc; i++) {
         BatchBufs* b = ctx->prepared[i];
         if (i > 0) {   // feedback for the window controller and for the size of the junction table between batches
@@ -1334,9 +1329,8 @@ int fgpu_scan_walk_prepared(fgpu_ctx* ctx) {
             if (!ctx->prm.walk_window_span) adapt_window(ctx);
             if ((rc = fgpu_scan_reserve(ctx, ctx->counters_host->n_junctions + ctx->scan_imported))) break;
         }
-        if (!serial_refresh && i + 1 < ctx->prepared.size() && (rc = fgpu_scan_refresh_planes(ctx, ctx->prepared[i + 1]))) break;
         ctx->cur = b;
-        ctx->refresh_snapshot = serial_refresh;
+        ctx->refresh_snapshot = true;
         rc = fgpu_stage_scan_walk(ctx, b->n_pieces);
         ctx->refresh_snapshot = false;
         ctx->walked_pieces += b->n_pieces;
@@ -1525,10 +1519,9 @@ int fgpu_scan_import_table(fgpu_ctx* ctx, const void* dev_buf, uint64_t n_entrie
         const uint64_t surplus = all ? n_entries - ctx->hint_n : 0;
         if (all && surplus <= (1ULL << 23)) {
             uint64_t bits = 1ULL << 20;      // (room for what this shard's own batches will add: they join the filter as they are walked)
-            // (32 bits of filter per new key, swept in round 6 on config 4's hop, FGPU_DELTA_FILTER_MULT = 8 / 16 / 32 / 64: the merge 16.4 / 14.4 / 13.0 / 13.9 ms, the
+            // (32 bits of filter per new key, swept in round 6 on config 4's hop, 8 / 16 / 32 / 64 bits per key: the merge 16.4 / 14.4 / 13.0 / 13.9 ms, the
             // link by the candidate plane -- which takes the filter's hits -- 11.6 / 9.7 / 8.7 / 8.2 ms, the hop 71.1 / 67.6 / 64.8 / 66.0 ms: false hits cost more than cache misses)
-            static const uint64_t mult = getenv("FGPU_DELTA_FILTER_MULT") ? (uint64_t)std::max(2, atoi(getenv("FGPU_DELTA_FILTER_MULT"))) : 32;
-            while (bits < mult * surplus) bits <<= 1;
+            while (bits < 32 * surplus) bits <<= 1;
             if ((rc = fgpu_ensure(ctx, &ctx->delta_filter, bits / 8))) return rc;
             FGPU_HIP(hipMemsetAsync(ctx->delta_filter.p, 0, bits / 8, ctx->stream));
             uint64_t max_seq = 0, newer = 0, digest[2] = {0, 0};
@@ -1652,14 +1645,9 @@ int fgpu_diag_late_flags(fgpu_ctx* ctx, uint64_t out[3]) {   // after fgpu_scan_
     return FGPU_OK;
 }
 
-int fgpu_diag_walk_probe(fgpu_ctx* ctx, uint64_t out[4]) {   // after fgpu_scan_end: probed pieces by outcome (k_walk_par)
+int fgpu_diag_walk_probe(fgpu_ctx* ctx, uint64_t out[4]) {   // kept for the ABI: the out-of-order walk it counted is retired, see the header
     if (!ctx || !out) return FGPU_ERR_ARG;
-    for (int i = 0; i < 4; i++) out[i] = ctx->counters_host->par_probe[i];
-    if (getenv("FGPU_KO_TIMING_PRINT")) {
-        fprintf(stderr, "[fgpu] k_walk_ko ticks (10 ns):");
-        for (int i = 0; i < 8; i++) fprintf(stderr, " %llu", ctx->counters_host->ko_time[i]);
-        fprintf(stderr, "\n");
-    }
+    for (int i = 0; i < 4; i++) out[i] = 0;
     return FGPU_OK;
 }
 

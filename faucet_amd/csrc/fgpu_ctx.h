@@ -212,16 +212,14 @@ struct DevCounters {
     unsigned long long followers_seen;  // `followers` as of the last window counted in walked_pieces: the two the controller divides come from one moment
     unsigned long long mark_hits;       // pass 1: occurrences k_load_mark itself routed to bloo2 (all bits already in the carry)
     unsigned long long mark_pending;    // pass 1: occurrences left to k_load_resolve
-    unsigned long long walk_parallel;   // pieces of large clusters walked out of order (k_walk_par)
-    unsigned long long par_probe[4];    // probed pieces by outcome: order-free, would create, would raise a distance, untested positions
-    unsigned long long ko_time[8];      // -DFGPU_KO_TIMING: ticks (10 ns) of k_walk_ko by part, see scripts/pe_profile.py
-    // late junction tests (scan_walk.hip, fill_missing): a test the walk ran itself came out TRUE at a k-mer the window's clusters were
-    // built without.  [0] entries noted by the walk, [1] of those, the ones k_delta_collect found elsewhere in their window (error bit 4);
-    // entries: stream position, number of the window
+    unsigned long long walk_parallel;   // pieces of large clusters walked by the large-cluster walks (k_walk_ko, k_ovw_commit)
     unsigned long long ko_overflows;    // windows whose large clusters did not fit the key-ordered / optimistic walks' tables
     unsigned long long ovw_kept;        // optimistic walk: piece-rounds in which a piece kept its log (no earlier piece had changed what it reads)
     unsigned long long ovw[4];          // optimistic walk of large clusters: pieces walked, rounds run, windows settled, windows left to the key-ordered walk
     unsigned long long ovw_fill;        // ... the most event-table entries a round of any window has held (k_ovw_commit counts them): the host grows the tables on it
+    // late junction tests (scan_walk.hip, fill_missing): a test the walk ran itself came out TRUE at a k-mer the window's clusters were
+    // built without.  [0] entries noted by the walk, [1] of those, the ones k_delta_collect found elsewhere in their window (error bit 4);
+    // entries: stream position, number of the window
     unsigned long long late_n[3];       // ([2] noted positions the check has passed over: every one of [0], once)
     unsigned long long late[2 * FGPU_LATE_CAP];
     // sliced pass under --mercy (fgpu_diag_slice_mercy): positions this rank probed; high->low tests answered "junction", runs opened,
@@ -366,9 +364,7 @@ struct fgpu_ctx {
     uint32_t walk_ko = 64;             // clusters of at least this many pieces are walked in k-mer order instead of piece order (0 = never); FGPU_WALK_KO
     uint32_t walk_ko_weight = 0;     // ... or whose pieces hold at least this many lk positions between them (0: rule off), see ko_cluster
     bool walk_ko_always = false;       // FGPU_WALK_KO_ALWAYS: from a scan's first window on (tests), not from the first large cluster seen
-    uint32_t* cl_fail = nullptr;       // per root: the cluster cannot be walked out of order (k_walk_par), two sets like cl_count
-    uint32_t walk_heavy = 0;           // clusters of at least this many pieces are tried out of order; 0 = never, the default: measured, it
-                                       // does not pay; FGPU_WALK_HEAVY sets it
+    uint32_t* cl_weight = nullptr;     // per root: the lk positions of the cluster's pieces (k_walk_cluster's sums, see ko_cluster), two sets like cl_count
     uint32_t* cl_members = nullptr;
     uint32_t* cl_roots = nullptr;      // per window: [0] leaders listed, [1] handed out, from word 16 on the list of the clusters' leaders (k_walk_dyn)
     void* wdesc = nullptr;           // device WinDesc of the window in flight

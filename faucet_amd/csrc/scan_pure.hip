@@ -542,17 +542,10 @@ static int scan_pure_flags(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi) {
     static const int sm_blocks = getenv("FGPU_FLAGS_SM_BLOCKS") ? atoi(getenv("FGPU_FLAGS_SM_BLOCKS")) : 4096;
     if (ctx->fd.j <= 1 && sm_blocks > 0) {
         const unsigned sm_grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>((nw + 255) / 256, 1), (uint64_t)sm_blocks);
-        static const int sm_slots = getenv("FGPU_FLAGS_SM_SLOTS") ? atoi(getenv("FGPU_FLAGS_SM_SLOTS")) : 1;
-#define FGPU_FLAGS_SM(SLOTS)                                                                                                        \
-    FGPU_LAUNCH("scan_flags", k_scan_flags_sm<SLOTS>, sm_grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,           \
-                (const uint64_t*)bb.need.p, bb.T, w_lo, w_hi, ctx->fd, (const uint32_t*)ctx->bloo2, (unsigned long long*)bb.ff.p,    \
-                (unsigned long long*)bb.fb.p, (unsigned long long*)bb.cf0.p, (unsigned long long*)bb.cf1.p,                         \
-                (unsigned long long*)bb.cb0.p, (unsigned long long*)bb.cb1.p, ctx->counters)
-        if (sm_slots <= 1) FGPU_FLAGS_SM(1);
-        else if (sm_slots == 2) FGPU_FLAGS_SM(2);
-        else if (sm_slots == 3) FGPU_FLAGS_SM(3);
-        else FGPU_FLAGS_SM(4);
-#undef FGPU_FLAGS_SM
+        FGPU_LAUNCH("scan_flags", k_scan_flags_sm<1>, sm_grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,
+                    (const uint64_t*)bb.need.p, bb.T, w_lo, w_hi, ctx->fd, (const uint32_t*)ctx->bloo2, (unsigned long long*)bb.ff.p,
+                    (unsigned long long*)bb.fb.p, (unsigned long long*)bb.cf0.p, (unsigned long long*)bb.cf1.p,
+                    (unsigned long long*)bb.cb0.p, (unsigned long long*)bb.cb1.p, ctx->counters);
     } else
         FGPU_LAUNCH("scan_flags", k_scan_flags, flags_grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.pm.p,
                     (const uint64_t*)bb.need.p, bb.T, w_lo, w_hi, ctx->fd, (const uint32_t*)ctx->bloo2, (unsigned long long*)bb.ff.p,

@@ -19,10 +19,10 @@
 //   D  k_walk_dyn      one thread per cluster replays its pieces IN ORDER against the live table; clusters are
 //                      disjoint in the keys they touch, so they run concurrently without changing any result
 //                      (the waves of a fixed grid draw the clusters from the window's list of leaders)
-//   D' k_walk_ko       clusters of 64 pieces and more (repeats at high coverage), once a scan has shown one: one piece per wave, the
-//                      ACCESSES ordered per junction k-mer by turn counters (k_ko_prepare, k_ko_rank), so the pieces of a cluster
-//                      overlap; k_walk_dyn leaves those clusters alone.  (k_walk_par, off: the out-of-order walk of clusters whose
-//                      pieces change nothing another piece reads -- exact, measured, does not pay.)
+//   D' k_ovw_round,    clusters of 64 pieces and more (repeats at high coverage), once a scan has shown one; k_walk_dyn leaves those clusters
+//      k_ovw_commit,   alone.  The optimistic walk takes them first: all pieces at once, read-only, round after round until their logs settle,
+//      k_walk_ko       then the logs are applied.  The key-ordered walk takes what that leaves: one piece per wave, the ACCESSES ordered per
+//                      junction k-mer by turn counters (k_ko_prepare, k_ko_rank), so the pieces of a cluster overlap.
 //   E  k_delta_collect the keys the window created go to the batch's list; k_walk_reset_uf (side stream) resets the union-find arrays
 //                      and the window table's presence filter of this parity (the table itself needs no cleaning: epoch-tagged entries)
 // Windows run one after another on the stream, so a later window sees everything earlier ones wrote.
@@ -469,7 +469,6 @@ struct KoHold {   // a k-mer whose turn this piece holds: entry, rank of its fir
 };
 struct KoState {
     KoTables kt;
-    DevCounters* cnt;       // (timing build)
     uint32_t base;          // first occurrence number of this piece
     uint32_t done;          // every lk position below `done` has been accounted for (passed or held)
     uint32_t mid;           // the position add_fake_junction would use
@@ -493,30 +492,19 @@ struct WalkCtx {
     bool created_now;   // set by junction_get
     KoState ko;         // WALK_KO: the piece's turn bookkeeping (by value: through a pointer it lived in scratch memory)
     uint32_t win_seq;   // number of the window being walked (late junction tests are noted with it)
-    int fail;           // WALK_PROBE: why this piece cannot be walked out of order (see k_walk_par): 1 would create, 2 would raise a distance, 3 untested positions
-    int dbg;            // FGPU_DEBUG_WALK bits (timing experiments only; results are wrong when non-zero)
+    int fail;           // the optimistic walk (ovw_walk_piece): 1 a table is full, 4 a late junction test came out true
 };
 // a walk's context at the start of a kernel: what the kernel was given, the accumulators at zero (wc.ko is the key-ordered walk's to set)
 __device__ __forceinline__ void walk_ctx_init(WalkCtx& wc, const Planes& pl, const FdParams& fp, const JTable& jt, DevCounters* cnt, const uint32_t* bloom,
-                                              uint32_t win_seq, int dbg) {
+                                              uint32_t win_seq) {
     wc.pl = pl; wc.fp = fp; wc.jt = jt; wc.cnt = cnt; wc.bloom = bloom; wc.win_seq = win_seq;
     wc.nb_processed = wc.nb_skipped = wc.nb_jcheck = wc.nb_no_juncs = wc.n_created = wc.n_filled = 0;
-    wc.created_now = false; wc.fail = 0; wc.dbg = dbg;
+    wc.created_now = false; wc.fail = 0;
 }
 
 // How a piece is walked.  WALK_SEQ: in its cluster's order by the cluster's one thread, reading and writing the junction table (the
-// reference's semantics as they stand).  WALK_PROBE / WALK_COMMIT: the two halves of the out-of-order walk of a large cluster, one thread
-// per piece (k_walk_par): PROBE walks read-only and notes whether the piece would change anything a later piece's path can depend on,
-// COMMIT walks the same path again and applies what is left -- coverage counts and link flags, both order-free -- with atomics.
-enum { WALK_SEQ = 0, WALK_PROBE = 1, WALK_COMMIT = 2, WALK_KO = 3, WALK_OVW = 4 };
-#ifdef FGPU_KO_TIMING
-#define KO_T0() const unsigned long long ko_t0__ = wall_clock64()
-#define KO_T1(cnt, i) atomicAdd(&(cnt)->ko_time[i], wall_clock64() - ko_t0__)
-#else
-#define KO_T0() do {} while (0)
-#define KO_T1(cnt, i) do {} while (0)
-#endif
-
+// reference's semantics as they stand).  WALK_KO, WALK_OVW: the large-cluster walks, see k_walk_ko and k_ovw_round.
+enum { WALK_SEQ = 0, WALK_KO = 1, WALK_OVW = 2 };
 
 // plane word for windows [64c, 64c+64) of the piece
 __device__ __forceinline__ uint64_t pv_word(const PieceView& v, uint64_t r0, uint64_t r1, const uint64_t* plane, uint32_t c) {
@@ -637,7 +625,6 @@ __device__ __noinline__ uint4 live_bits_impl(const uint64_t* __restrict__ codes,
 }
 
 __device__ __forceinline__ void created_bits(const WalkCtx& wc, const PieceView& v, uint32_t c, uint64_t& mF, uint64_t& mB) {
-    if (wc.dbg & 1) { mF = mB = 0; return; }
     const uint32_t base = c * 64;
     // (junctions are never removed during a scan: where the snapshot already has both facings there is nothing the live table could add --
     // inside a repeat at high coverage that is nearly every position, and the look-ups of a piece were a quarter of its walk)
@@ -682,7 +669,7 @@ __device__ __forceinline__ uint32_t pv_popc(const PieceView& v, uint64_t r0, uin
 
 // NbJCheckKmer increments of the half-steps t in [t0, t1): backward-facing half-steps are 2q, forward-facing 2q+1
 __device__ __forceinline__ uint32_t jcheck_sum(const WalkCtx& wc, const PieceView& v, int t0, int t1) {
-    if (t1 <= t0 || (wc.dbg & 4)) return 0;
+    if (t1 <= t0) return 0;
     const uint32_t bq0 = (uint32_t)((t0 + 1) >> 1), bq1 = (uint32_t)((t1 + 1) >> 1);
     const uint32_t fq0 = (uint32_t)(t0 >> 1), fq1 = (uint32_t)(t1 >> 1);
     return pv_popc(v, v.c0B0, v.c0B1, wc.pl.cb0, bq0, bq1) + 2 * pv_popc(v, v.c1B0, v.c1B1, wc.pl.cb1, bq0, bq1) +
@@ -711,7 +698,6 @@ __device__ __forceinline__ bool fill_missing(WalkCtx& wc, PieceView& v, int t0, 
     uint32_t qa = (uint32_t)(t0 >> 1), qb = (uint32_t)((t1 - 1) >> 1) + 1;
     if (qb > v.nwin) qb = v.nwin;
     if (pv_popc(v, v.nd0, v.nd1, wc.pl.need, qa, qb) == qb - qa) return false;   // the usual case: the preview covered the stretch
-    if (MODE == WALK_PROBE || MODE == WALK_COMMIT) { wc.fail = 3; return false; }   // left to the cluster's ordered walk
     bool any = false;
     while (qa < qb) {
         const uint32_t c = qa >> 6;
@@ -822,14 +808,11 @@ __device__ __forceinline__ bool junction_get(WalkCtx& wc, uint64_t key, uint64_t
     uint64_t slot;
     uint32_t present;
     if (MODE == WALK_KO && known_slot != ~0ULL) {   // the key-ordered walk has just found this junction in the map: no second probe
-        KO_T0();
         out.addr = (uint64_t*)(wc.jt.recs + (known_slot * 2 + orient) * 16);
         out.lo = ld_agent(&out.addr[0]);
         out.hi = ld_agent(&out.addr[1]);
         wc.created_now = false;
-        if (out.lo == 0xFFFFFFFFFFFFFFF1ULL) return false;
-        KO_T1(wc.cnt, 3);
-        return true;
+        return out.lo != 0xFFFFFFFFFFFFFFF1ULL;
     }
     // the key word and the record of the home slot are requested together: at the table's low load factor the key is
     // almost always in its home slot, so an event costs one memory round trip instead of two
@@ -865,39 +848,6 @@ __device__ __forceinline__ bool junction_get(WalkCtx& wc, uint64_t key, uint64_t
 }
 
 
-// the record of an EXISTING junction, read-only (WALK_PROBE / WALK_COMMIT); false = the key is not in the map (a walk would create it)
-__device__ __forceinline__ bool junction_find(const WalkCtx& wc, uint64_t key, RecRegs& out) {
-    const uint64_t rc = fd_revcomp(key, wc.fp.k);
-    const uint64_t canon = key < rc ? key : rc;
-    const int orient = key == canon ? 0 : 1;
-    uint64_t slot;
-    uint32_t present;
-    if (!jt_find_live(wc.jt, canon, slot, present) || !((present >> orient) & 1u)) return false;
-    out.addr = (uint64_t*)(wc.jt.recs + (slot * 2 + orient) * 16);
-    out.lo = out.addr[0];
-    out.hi = out.addr[1];
-    return true;
-}
-__device__ __forceinline__ bool rr_raises(const RecRegs& r, int idx, int length) { return rr_get(r, idx) < ((uint32_t)length & 0xFF); }
-// Junction::addCoverage / the link flags on a record other threads update at the same time (WALK_COMMIT): saturating +1 on one byte,
-// OR of one bit; `seen` is this thread's earlier plain read of the record and only saves atomics that cannot change anything
-__device__ __forceinline__ void rec_add_cov_atomic(const RecRegs& seen, int nuc) {
-    if (rr_get(seen, 5 + nuc) == 255) return;
-    unsigned long long* w = (unsigned long long*)(seen.addr + (nuc < 3 ? 0 : 1));
-    const int sh = nuc < 3 ? 8 * (5 + nuc) : 0;
-    unsigned long long old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (((old >> sh) & 0xFF) != 255) {
-        const unsigned long long was = atomicCAS(w, old, old + (1ULL << sh));
-        if (was == old) break;
-        old = was;
-    }
-}
-__device__ __forceinline__ void rec_link_atomic(const RecRegs& seen, int idx) {
-    if ((rr_get(seen, 9) >> idx) & 1u) return;
-    atomicOr((unsigned long long*)(seen.addr + 1), 1ULL << (8 + idx));
-}
-
-
 // -DFGPU_KO_TRACE: one piece in 16 also leaves a time stamp at every step of every position it deals with (kt.trace + 2^23 words on:
 // 1024 words per stamped piece: [0] piece << 16 | stamps, then {code << 56 | q << 40 | ticks since the piece's start}; scripts/ko_trace.py)
 #ifdef FGPU_KO_TRACE
@@ -926,15 +876,6 @@ __device__ __noinline__ unsigned long long ko_wait(const uint32_t* turn, uint32_
     if (ld_agent(turn) == r) return 0;            // (only what is spent AFTER a first look that found the turn elsewhere counts as waiting)
     const unsigned long long t_in = wall_clock64();
 #endif
-#ifdef FGPU_KO_TIMING
-    const unsigned long long tw = wall_clock64();
-    if (ld_agent(turn) != r) {
-        while (ld_agent(turn) != r) __builtin_amdgcn_s_sleep(1);
-        atomicAdd(&cnt->par_probe[1], wall_clock64() - tw);
-        atomicAdd(&cnt->par_probe[3], 1ULL);
-    }
-    return 0;
-#endif
     while (ld_agent(turn) != r) {
         __builtin_amdgcn_s_sleep(1);
         if ((++spins & 4095u) == 0) {   // a turn that never comes is a bug, not a state to wait in: say so once and let every piece run out
@@ -951,20 +892,15 @@ __device__ __noinline__ unsigned long long ko_wait(const uint32_t* turn, uint32_
     return 0;
 #endif
 }
-__device__ __forceinline__ DevCounters* ko_cnt(const KoState& ko) { return ko.cnt; }
 // the k-mer's turn goes to its next occurrence; whatever this piece stored is visible before the counter moves
 __device__ __forceinline__ void ko_give(const KoState& ko, KoHold& h) {
     // records and stamps are stored with agent-scope (write-through, sc1) stores and key words / planes change by device-scope atomics, so the
     // release is: wait until every one of them has been acknowledged (gfx950 counts stores and atomics in vmcnt), then move the counter.  A
     // workgroup-scope fence alone emits NO wait on this target (the turn store followed the record stores with nothing in between: ADVICE r2);
     // an agent-scope release fence would add a write-back of the whole L2 (buffer_wbl2), which nothing here needs: no plain store is shared.
-    {
-        KO_T0();
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // compiler barrier: no store may sink below the counter's
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __hip_atomic_store(&ko.kt.hk_turn[h.e], h.r + h.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        KO_T1(ko_cnt(ko), 1);
-    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // compiler barrier: no store may sink below the counter's
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __hip_atomic_store(&ko.kt.hk_turn[h.e], h.r + h.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     h.n = 0;
 }
 // the cursor leaves its position without having visited it
@@ -977,13 +913,12 @@ __device__ __forceinline__ void ko_leave_cursor(KoState& ko, bool have_last) {
 __device__ __forceinline__ void ko_account(WalkCtx& wc, uint32_t q, bool as_cursor, bool have_last) {
     KoState& ko = wc.ko;
     ko_leave_cursor(ko, have_last);
-    KO_T0();
     KO_STAMP(ko, 1, q);
     const uint32_t node = ko.base + ko_ordinal(ko, q);
     const uint32_t e = ko.kt.occ_entry[node], r = ko.kt.occ_rank[node];
     if (as_cursor) ko.cur_q = q;
-    if (e == 0xFFFFFFF0u) return;                   // (keeps the loads in front of the clock)
-    KO_T1(wc.cnt, 0);
+    if (e == 0xFFFFFFF0u) return;                   // (no entry has this number: the retired timing build's guard, kept because k_walk_ko's instruction
+                                                    // stream comes out reordered without it and the one behind jt_find_live in walk_piece -- 5827 -> 5789 instructions)
     if (ko.last.n && e == ko.last.e) { ko.last.n++; if (as_cursor) ko.cur_in = 1; return; }     // this piece holds the k-mer already
     if (ko.fake.n && e == ko.fake.e) { ko.fake.n++; if (as_cursor) ko.cur_in = 2; return; }
     ko.wait_acc += ko_wait(&ko.kt.hk_turn[e], r, wc.cnt);
@@ -1123,12 +1058,8 @@ __device__ __forceinline__ void walk_piece(WalkCtx& wc, uint64_t p0, uint32_t nw
                 const uint64_t canon = kmq < rcq ? kmq : rcq;
                 uint64_t slot = 0;      // (was compared uninitialised when the k-mer is not in the table: undefined behaviour that one
                 uint32_t present = 0;   // build of round 3 did not survive -- "a k-mer's turn never came" at full size)
-                {
-                    KO_T0();
-                    in_map = jt_find_live(wc.jt, canon, slot, present) && ((present >> ((fwd ? kmq : rcq) == canon ? 0 : 1)) & 1u);
-                    if (slot == 0xFFFFFFFFFFFFFFF0ULL) return;
-                    KO_T1(wc.cnt, 2);
-                }
+                in_map = jt_find_live(wc.jt, canon, slot, present) && ((present >> ((fwd ? kmq : rcq) == canon ? 0 : 1)) & 1u);
+                if (slot == 0xFFFFFFFFFFFFFFF0ULL) return;   // (no slot has this number: see ko_account)
                 KO_STAMP(wc.ko, 3, q);
                 ko_slot = in_map ? slot : ~0ULL;
                 if (potential && !in_map) {                 // registered, but not in the map (yet): not an event; look again from here
@@ -1140,7 +1071,6 @@ __device__ __forceinline__ void walk_piece(WalkCtx& wc, uint64_t p0, uint32_t nw
             if (fill_missing<MODE>(wc, v, t, (in_map || by_spacer) ? tn : tn + 1)) continue;
             break;
         }
-        if ((MODE == WALK_PROBE || MODE == WALK_COMMIT) && wc.fail) return;
         if (tn > tmax) {   // ran off the end of the piece
             wc.nb_processed += (unsigned long long)(tmax - t + 1);
             wc.nb_jcheck += jcheck_sum(wc, v, t, tmax + 1);
@@ -1156,54 +1086,31 @@ __device__ __forceinline__ void walk_piece(WalkCtx& wc, uint64_t p0, uint32_t nw
         RecRegs cur;
         const int ext_fwd = fwd ? real : 4;          // getExtensionIndex(FORWARD)
         const int ext_bwd = fwd ? 4 : real;          // getExtensionIndex(BACKWARD)
-        if (MODE == WALK_SEQ || MODE == WALK_KO) {
-            if (!junction_get<MODE>(wc, key, (piece_seq << STAMP_SHIFT) | (uint64_t)tn, p0 + q, cur, ko_slot)) return;
-            if (wc.pl.sF) atomicOr(&(fwd ? wc.pl.sF : wc.pl.sB)[(p0 + q) >> 6], 1ULL << ((p0 + q) & 63));   // result.push_back, :140
-            if (MODE == WALK_SEQ && wc.created_now) {   // the new key may recur further along this piece (tandem repeats)
-                created_bits(wc, v, 0, v.xF0, v.xB0);
-                if (nwin > 64) created_bits(wc, v, 1, v.xF1, v.xB1);
-            }
-            const bool same = have_last && cur.addr == last.addr;   // the same junction twice in a row: one register copy
-            if (same) cur = last;
-            last_pos = tn;
-            rr_add_cov(cur, real);
-            if (have_last) {                             // directLinkJunctions, JunctionMap.cpp:551-561
-                const int d = tn - last_t;
-                if (same) {
-                    rr_update(cur, last_ext_fwd, d);
-                    rr_link(cur, last_ext_fwd);
-                } else {
-                    rr_update(last, last_ext_fwd, d);
-                    rr_link(last, last_ext_fwd);
-                    rr_store_m<MODE>(last);
-                }
-                rr_update(cur, ext_bwd, d);
-                rr_link(cur, ext_bwd);
+        if (!junction_get<MODE>(wc, key, (piece_seq << STAMP_SHIFT) | (uint64_t)tn, p0 + q, cur, ko_slot)) return;
+        if (wc.pl.sF) atomicOr(&(fwd ? wc.pl.sF : wc.pl.sB)[(p0 + q) >> 6], 1ULL << ((p0 + q) & 63));   // result.push_back, :140
+        if (MODE == WALK_SEQ && wc.created_now) {   // the new key may recur further along this piece (tandem repeats)
+            created_bits(wc, v, 0, v.xF0, v.xB0);
+            if (nwin > 64) created_bits(wc, v, 1, v.xF1, v.xB1);
+        }
+        const bool same = have_last && cur.addr == last.addr;   // the same junction twice in a row: one register copy
+        if (same) cur = last;
+        last_pos = tn;
+        rr_add_cov(cur, real);
+        if (have_last) {                             // directLinkJunctions, JunctionMap.cpp:551-561
+            const int d = tn - last_t;
+            if (same) {
+                rr_update(cur, last_ext_fwd, d);
+                rr_link(cur, last_ext_fwd);
             } else {
-                have_last = true;
-                rr_update(cur, ext_bwd, tn - 2 * j);
+                rr_update(last, last_ext_fwd, d);
+                rr_link(last, last_ext_fwd);
+                rr_store_m<MODE>(last);
             }
+            rr_update(cur, ext_bwd, d);
+            rr_link(cur, ext_bwd);
         } else {
-            // Out of order: the junction must exist already, and no distance may be raised (a later piece's skips read them) -- then the
-            // only things this visit changes are a coverage count and two link flags, which no walk reads.
-            if (!junction_find(wc, key, cur)) { wc.fail = 1; return; }
-            if (MODE == WALK_COMMIT) {
-                if (wc.pl.sF) atomicOr(&(fwd ? wc.pl.sF : wc.pl.sB)[(p0 + q) >> 6], 1ULL << ((p0 + q) & 63));
-                rec_add_cov_atomic(cur, real);
-            }
-            last_pos = tn;
-            if (have_last) {
-                const int d = tn - last_t;
-                if (MODE == WALK_PROBE) {
-                    if (rr_raises(last, last_ext_fwd, d) || rr_raises(cur, ext_bwd, d)) { wc.fail = 2; return; }
-                } else {
-                    rec_link_atomic(last, last_ext_fwd);
-                    rec_link_atomic(cur, ext_bwd);
-                }
-            } else {
-                have_last = true;
-                if (MODE == WALK_PROBE && rr_raises(cur, ext_bwd, tn - 2 * j)) { wc.fail = 2; return; }
-            }
+            have_last = true;
+            rr_update(cur, ext_bwd, tn - 2 * j);
         }
         last = cur;
         last_t = tn;
@@ -1230,31 +1137,18 @@ __device__ __forceinline__ void walk_piece(WalkCtx& wc, uint64_t p0, uint32_t nw
         int real = pv_base(v, wc.pl.codes, p0 + m + k);
         RecRegs rec;
         const int tm = 2 * m + 1;
-        if (MODE == WALK_SEQ || MODE == WALK_KO) {
-            if (MODE == WALK_KO) {   // the middle k-mer's turn was kept when the cursor passed it (ko.fake), or is taken now
-                ko_leave_cursor(wc.ko, false);
-                ko_pass(wc, (uint32_t)m + 1, false);
-            }
-            if (!junction_get<MODE>(wc, key, (piece_seq << STAMP_SHIFT) | STAMP_FAKE, p0 + (uint64_t)m, rec)) return;
-            rr_add_cov(rec, real);
-            rr_update(rec, 4, tm - 2 * j);
-            rr_update(rec, real, (2 * (int)nwin - 1 - tm) - 2 * j);
-            rr_store_m<MODE>(rec);
-        } else {
-            if (!junction_find(wc, key, rec)) { wc.fail = 1; return; }
-            if (MODE == WALK_PROBE) {
-                if (rr_raises(rec, 4, tm - 2 * j) || rr_raises(rec, real, (2 * (int)nwin - 1 - tm) - 2 * j)) wc.fail = 2;
-            } else {
-                rec_add_cov_atomic(rec, real);
-            }
+        if (MODE == WALK_KO) {   // the middle k-mer's turn was kept when the cursor passed it (ko.fake), or is taken now
+            ko_leave_cursor(wc.ko, false);
+            ko_pass(wc, (uint32_t)m + 1, false);
         }
+        if (!junction_get<MODE>(wc, key, (piece_seq << STAMP_SHIFT) | STAMP_FAKE, p0 + (uint64_t)m, rec)) return;
+        rr_add_cov(rec, real);
+        rr_update(rec, 4, tm - 2 * j);
+        rr_update(rec, real, (2 * (int)nwin - 1 - tm) - 2 * j);
+        rr_store_m<MODE>(rec);
     } else {            // ReadScanner.cpp:202-206
-        if (MODE == WALK_SEQ || MODE == WALK_KO) {
-            rr_update(last, last_ext_fwd, (2 * (int)nwin - 1 - last_t) - 2 * j);
-            rr_store_m<MODE>(last);
-        } else if (MODE == WALK_PROBE && rr_raises(last, last_ext_fwd, (2 * (int)nwin - 1 - last_t) - 2 * j)) {
-            wc.fail = 2;
-        }
+        rr_update(last, last_ext_fwd, (2 * (int)nwin - 1 - last_t) - 2 * j);
+        rr_store_m<MODE>(last);
     }
 }
 
@@ -1302,11 +1196,11 @@ __device__ __forceinline__ void walk_counters_flush(DevCounters* cnt, unsigned l
 __global__ void __launch_bounds__(64) k_walk_dyn(Planes pl, FdParams fp, JTable jt, const uint32_t* __restrict__ root_list, uint32_t* roots_state,
                                                  const uint32_t* __restrict__ count, const uint32_t* __restrict__ head,
                                                  const uint32_t* __restrict__ next, uint32_t* pool, const WinDesc* __restrict__ wdp,
-                                                 uint64_t piece_seq_base, const uint32_t* __restrict__ bloom, DevCounters* cnt, int dbg,
-                                                 const uint32_t* __restrict__ par_fail, uint32_t heavy, const uint32_t* __restrict__ ko_bad,
+                                                 uint64_t piece_seq_base, const uint32_t* __restrict__ bloom, DevCounters* cnt,
+                                                 const uint32_t* __restrict__ weight, const uint32_t* __restrict__ ko_bad,
                                                  const uint32_t* __restrict__ ko_state, uint32_t ko_heavy, uint32_t win_seq, uint32_t ko_heavy_w) {
     WalkCtx wc;
-    walk_ctx_init(wc, pl, fp, jt, cnt, bloom, win_seq, dbg);
+    walk_ctx_init(wc, pl, fp, jt, cnt, bloom, win_seq);
     const WinDesc wd = *wdp;
     const uint32_t first_piece = wd.first_piece;
     if (ko_heavy && blockIdx.x == 0 && threadIdx.x == 0 && (ko_state[1] & 1u)) atomicAdd(&cnt->ko_overflows, 1ULL);
@@ -1332,13 +1226,12 @@ __global__ void __launch_bounds__(64) k_walk_dyn(Planes pl, FdParams fp, JTable 
                 else {
                     const uint32_t i = root_list[mine];
                     const uint32_t my_count = count[i];
-                    // a large cluster that the out-of-order / key-ordered / optimistic walks take is left alone here
-                    const bool elsewhere = (heavy && my_count + 1 >= heavy && !par_fail[i]) ||
-                                           (ko_usable && ko_cluster(my_count, par_fail[i], ko_heavy, ko_heavy_w) && !ko_bad[i]);
+                    // a large cluster that the key-ordered / optimistic walks take is left alone here
+                    const bool elsewhere = ko_usable && ko_cluster(my_count, weight[i], ko_heavy, ko_heavy_w) && !ko_bad[i];
                     if (!elsewhere) {
                         leader = i;
                         at = 0;
-                        nm = (dbg & 2) ? 0 : my_count;
+                        nm = my_count;
                         mem = local_mem;
                         if (nm) {
                             n_follow += nm;
@@ -1366,49 +1259,6 @@ __global__ void __launch_bounds__(64) k_walk_dyn(Planes pl, FdParams fp, JTable 
     walk_counters_flush(cnt, wc.nb_processed, wc.nb_skipped, wc.nb_jcheck, wc.nb_no_juncs);
     wave_add(&cnt->n_junctions, wc.n_created);
     wave_add(&cnt->flags_filled, wc.n_filled);
-}
-
-// The out-of-order walk of large clusters.  A cluster is the set of pieces of a window that share a junction k-mer; its one thread walks
-// them in file order because a piece may create junctions and raise distances that later pieces' skips depend on.  Where a repeat of the
-// genome is covered a thousand times the cluster holds hundreds of pieces per window, each with a junction at every position, and that one
-// thread decides how long the window takes (a 6 Mb genome with twenty copies of a 400-base repeat: 29 ms per window, 1.9 s of a 2 s scan).
-// But in such a cluster nearly every piece changes nothing another piece can see: its junctions exist and their distances -- maxima over
-// all earlier reads -- are not raised.  What is left of scan_forward then is a coverage count and two link flags per visit
-// (Junction::addCoverage saturating at 255, linked[] = true: JunctionMap.cpp:551-561), and those commute.  So, for clusters of at least
-// `heavy` pieces, one thread per PIECE:
-//   PROBE  (before k_walk_dyn)  walk read-only; par_fail[root] is set if any piece of the cluster would create a junction, raise a distance,
-//          or needs junction tests the preview left out.  If nobody sets it, no distance and no key of the cluster changes during this
-//          window, so every piece reads exactly what it would read in file order: the paths found here are the sequential paths.
-//   k_walk_dyn walks the clusters that failed (and all small ones) in order, as before.
-//   COMMIT (after k_walk_dyn)   the pieces of the clusters that passed walk the same path again and apply coverage and links with atomics,
-//          mark their visits for scanInputRead's lists and add their counters.
-// Keys are exclusive to a cluster (that is what makes it a cluster), so the three kernels never touch each other's records.
-template <int MODE>
-__global__ void __launch_bounds__(64) k_walk_par(Planes pl, FdParams fp, JTable jt, const uint32_t* __restrict__ root, const uint32_t* __restrict__ count,
-                                                 uint32_t* par_fail, const WinDesc* __restrict__ wdp, const uint32_t* __restrict__ bloom, DevCounters* cnt,
-                                                 uint32_t heavy) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    WalkCtx wc;
-    walk_ctx_init(wc, pl, fp, jt, cnt, bloom, 0, 0);
-    const WinDesc wd = *wdp;
-    unsigned long long walked = 0;
-    if (i < wd.n) {
-        const uint32_t r = root[i];
-        if (count[r] + 1 >= heavy && (MODE == WALK_PROBE || !par_fail[r])) {
-            const uint2 pc = pl.pieces[wd.first_piece + i];
-            walk_piece<MODE>(wc, pc.x, pc.y, 0);
-            if (MODE == WALK_PROBE) {
-                if (wc.fail) par_fail[r] = 1u;
-                atomicAdd(&cnt->par_probe[wc.fail], 1ULL);
-            } else {
-                walked = 1;
-            }
-        }
-    }
-    if (MODE == WALK_COMMIT) {
-        walk_counters_flush(cnt, wc.nb_processed, wc.nb_skipped, wc.nb_jcheck, wc.nb_no_juncs);
-        wave_add(&cnt->walk_parallel, walked);
-    }
 }
 
 // (tables of the optimistic walk, k_ovw_round further down: k_ko_prepare lists its pieces, k_walk_ko looks at its outcome)
@@ -1549,16 +1399,10 @@ __global__ void __launch_bounds__(64) k_walk_ko(Planes pl, FdParams fp, JTable j
     if (ovw_done && !ovw_state[3]) return;
     WalkCtx wc;
     KoState& ko = wc.ko;
-    walk_ctx_init(wc, pl, fp, jt, cnt, bloom, 0, 0);
+    walk_ctx_init(wc, pl, fp, jt, cnt, bloom, 0);
     ko.kt = kt;
-    ko.cnt = cnt;
     unsigned long long walked = 0;
     if (kt.state[3] == 0) return;                                      // no large cluster in this window (the usual case)
-#ifdef FGPU_KO_ONE_XCD
-    // experiment: only the waves that landed on XCD 0 take tickets (the grid is eight times as large), so that every hand-over stays
-    // inside one XCD; the accesses keep their agent scope, only their latency is looked at
-    if ((__builtin_amdgcn_s_getreg(6164) & 15) != 0) return;           // hwreg(HW_REG_XCC_ID, 0, 4)
-#endif
     // Pieces per ticket.  KO_TICKET (a multiple of 64) where the pieces of large clusters are few among the window's pieces -- a
     // same-address atomic per 64 pieces cost 0.2 ms per window -- so that a ticket holds about one of them.  Where they are dense (a small
     // genome at high coverage: EVERY piece of the reference's own 1 000-read example is in one cluster) a ticket of 64 would put 64
@@ -1619,9 +1463,6 @@ __global__ void __launch_bounds__(64) k_walk_ko(Planes pl, FdParams fp, JTable j
                         if (slot < 4096) ko.stamp_base = kt.trace + (1ULL << 23) + slot * 1024;
                     }
 #endif
-#ifdef FGPU_KO_TIMING
-                    const unsigned long long tp = wall_clock64();
-#endif
                     walk_piece<WALK_KO>(wc, pc.x, pc.y, piece_seq_base + wd.first_piece + li);
                     ko_finish(wc, pc.y);
                     walked++;
@@ -1639,10 +1480,6 @@ __global__ void __launch_bounds__(64) k_walk_ko(Planes pl, FdParams fp, JTable j
                     if (ko.stamp_base) ko.stamp_base[0] = ((piece_seq_base + wd.first_piece + li) << 16) | (ko.stamp_n < 1020 ? ko.stamp_n : 1020);
 #else
                     (void)n_lk;
-#endif
-#ifdef FGPU_KO_TIMING
-                    atomicAdd(&cnt->par_probe[0], wall_clock64() - tp);
-                    atomicAdd(&cnt->par_probe[2], 1ULL);
 #endif
                 }
             }
@@ -2126,7 +1963,7 @@ __global__ void __launch_bounds__(64) k_ovw_round(Planes pl, FdParams fp, JTable
             }
         }
         WalkCtx wc;
-        walk_ctx_init(wc, pl, fp, jt, cnt, bloom, 0, 0);
+        walk_ctx_init(wc, pl, fp, jt, cnt, bloom, 0);
         OvwWalk ow;
         ow.prev = ot.prev; ow.cur = ot.cur;
         ow.have_prev = round > 0;
@@ -2347,13 +2184,13 @@ __global__ void __launch_bounds__(256) k_delta_collect(unsigned long long* __res
 
 // union-find and list entries of a window's pieces back to "every piece its own cluster": the arrays exist twice and consecutive
 // windows alternate, so this runs on the side stream while the NEXT window is already being looked up and linked
-__global__ void __launch_bounds__(256) k_walk_reset_uf(uint32_t* parent, uint32_t* count, uint32_t* head, uint32_t* par_fail, uint32_t n, uint4* wbits,
+__global__ void __launch_bounds__(256) k_walk_reset_uf(uint32_t* parent, uint32_t* count, uint32_t* head, uint32_t* weight, uint32_t n, uint4* wbits,
                                                        uint32_t wbits_vec) {
     for (uint32_t a = blockIdx.x * blockDim.x + threadIdx.x; a < n; a += gridDim.x * blockDim.x) {
         parent[a] = a;
         count[a] = 0;
         head[a] = U_INF;
-        par_fail[a] = 0;
+        weight[a] = 0;
     }
     // ... and the window table's presence filter of this parity (a memset on the walk stream took 47 us per window when the
     // pure stage of the next batch ran beside it: 3.6 ms per step on the critical queue)
@@ -2585,7 +2422,6 @@ void fgpu_touch_scan_walk() {
 int fgpu_scan_alloc(fgpu_ctx* ctx) {
     if (ctx->jkeys) return FGPU_OK;
     ctx->jcap = ctx->prm.junction_capacity;
-    if (const char* e = getenv("FGPU_WBITS_LOG2")) ctx->wbits_log2 = std::min(28, std::max(16, atoi(e)));   // measurement aid
     // the key-ordered walk's tables (KoTables): 2^20 k-mers and 2^22 occurrences of large clusters per window, else the window is walked by cluster
     if (const char* e = getenv("FGPU_WALK_KO")) ctx->walk_ko = (uint32_t)std::max(0, atoi(e));
     ctx->walk_ko_always = getenv("FGPU_WALK_KO_ALWAYS") != nullptr || (ctx->prm.flags & FGPU_FLAG_KEY_ORDER_FROM_START) != 0;
@@ -2599,7 +2435,6 @@ int fgpu_scan_alloc(fgpu_ctx* ctx) {
     // (round 4: four times round 3's sizes -- the optimistic walk lets windows of repeat-rich data grow to 10^5 pieces of large clusters and more)
     ctx->ko_hk_cap = 1u << 22;
     ctx->ko_occ_cap = 1u << 24;
-    if (const char* e = getenv("FGPU_WALK_HEAVY")) ctx->walk_heavy = (uint32_t)std::max(0, atoi(e));   // clusters of at least this many pieces are tried out of order; 0 = never
     // Scheduling windows span at most max_span positions (+ one piece length).  Worst case every position is a candidate with a distinct
     // k-mer, so the window table holds 4x that -- 32 bytes per position of the bound: 2 GiB at 2^26, 8 GiB at the 2^28 that filters of 2^32
     // bits and more ask for (fgpu_create).  The larger bounds are a matter of speed, never of results, so they give way to the memory there
@@ -2621,7 +2456,7 @@ int fgpu_scan_alloc(fgpu_ctx* ctx) {
             {(void**)&ctx->wbits, 2 * (1ULL << ctx->wbits_log2) / 8},                  // two filters: consecutive windows alternate
             {(void**)&ctx->uf_parent, 2ULL * ctx->wmax * 4},                            // two sets each: consecutive windows alternate (k_walk_reset_uf)
             {(void**)&ctx->cl_count, 2ULL * ctx->wmax * 4}, {(void**)&ctx->cl_offset, 2ULL * ctx->wmax * 4}, {(void**)&ctx->cl_fill, (uint64_t)ctx->wmax * 4},
-            {(void**)&ctx->cl_fail, 2ULL * ctx->wmax * 4}, {(void**)&ctx->ko_hk, (uint64_t)ctx->ko_hk_cap * 4 * 3},
+            {(void**)&ctx->cl_weight, 2ULL * ctx->wmax * 4}, {(void**)&ctx->ko_hk, (uint64_t)ctx->ko_hk_cap * 4 * 3},
             {(void**)&ctx->ko_occ, (uint64_t)ctx->ko_occ_cap * (4 * 3 + 8)}, {(void**)&ctx->ko_piece, (uint64_t)ctx->wmax * 4 * 2 + 64},
             {(void**)&ctx->cl_members, (uint64_t)ctx->wmax * 4 * 2}, {(void**)&ctx->cl_roots, (uint64_t)ctx->wmax * 4 + 64}};
         hipError_t err = hipSuccess;
@@ -2650,7 +2485,7 @@ int fgpu_scan_reset(fgpu_ctx* ctx) {
     FGPU_LAUNCH("iota", k_iota_u32, 64, 256, ctx->uf_parent + ctx->wmax, (uint64_t)ctx->wmax);
     FGPU_HIP(hipMemsetAsync(ctx->cl_count, 0, 2 * ctx->wmax * 4, ctx->stream));
     FGPU_HIP(hipMemsetAsync(ctx->cl_offset, 0xFF, 2 * ctx->wmax * 4, ctx->stream));
-    FGPU_HIP(hipMemsetAsync(ctx->cl_fail, 0, 2 * ctx->wmax * 4, ctx->stream));
+    FGPU_HIP(hipMemsetAsync(ctx->cl_weight, 0, 2 * ctx->wmax * 4, ctx->stream));
     FGPU_HIP(hipMemsetAsync(ctx->ko_hk, 0xFF, (size_t)ctx->ko_hk_cap * 4 * 2, ctx->stream));        // keys free, lists empty,
     FGPU_HIP(hipMemsetAsync(ctx->ko_hk + 2 * (size_t)ctx->ko_hk_cap, 0, (size_t)ctx->ko_hk_cap * 4, ctx->stream));   // turns at zero,
     FGPU_HIP(hipMemsetAsync(ctx->ko_piece, 0, (size_t)ctx->wmax * 4 * 2 + 64, ctx->stream));        // flags and per-piece arrays clean
@@ -2693,9 +2528,8 @@ int fgpu_stage_scan_need_prewalk(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi) {
     return FGPU_OK;
 }
 
-// Read shards, FGPU_PREPARED_REFRESH=overlap (fgpu_scan_walk_prepared; measured in round 5, not the default): the snapshot planes of a batch that
-// was prepared before its turn, made again on the MAIN stream against the table as it stands, so that batch i + 1's are made while batch i is
-// walked.  The batch's walk waits for pure_done, recorded here.
+// Read shards (fgpu_scan_refresh_prepared, off the chain): the snapshot planes of a batch that was prepared before its turn, made again on the
+// MAIN stream against the table as it stands (a fresher preview).  The batch's walk waits for pure_done, recorded here.
 int fgpu_scan_refresh_planes(fgpu_ctx* ctx, BatchBufs* b) {
     if (!b->n_pieces || !b->T) return FGPU_OK;
     JTable jt = make_jt(ctx);
@@ -2743,22 +2577,17 @@ int fgpu_stage_scan_debug_drop(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi) {
 
 // ---- the walk stage on the host -------------------------------------------------------------------------------------------------------------
 // The stage's measurement aids and test switches, read from the environment once per process.  (The knobs that size tables or pick the
-// large-cluster walks -- FGPU_WALK_KO*, FGPU_OVW_ROUNDS, FGPU_OVW_EV_LOG2, FGPU_WALK_HEAVY, FGPU_WBITS_LOG2 -- live in the context: fgpu_scan_alloc.)
+// large-cluster walks -- FGPU_WALK_KO*, FGPU_OVW_ROUNDS, FGPU_OVW_EV_LOG2 -- live in the context: fgpu_scan_alloc.)
 static int env_int(const char* name, int absent) { const char* e = getenv(name); return e ? atoi(e) : absent; }
 static bool env_is_one(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
 struct WalkKnobs {
-    const int dbg_walk = env_int("FGPU_DEBUG_WALK", 0);                // bits for timing experiments only; results are wrong when non-zero
-    const bool serial_clean = env_is_one("FGPU_SERIAL_CLEAN");          // the walk stream waits for each window's union-find reset (measurement aid)
     const bool no_overlap = env_is_one("FGPU_NO_OVERLAP");              // the whole stage on the main stream, nothing beside the pure stage (measurement aid)
-    const bool no_whole_batch = getenv("FGPU_NO_WHOLE_BATCH") != nullptr;   // a prepared batch with a candidate plane is cut into windows like any other
     const unsigned cluster_grid = (unsigned)std::max(1, env_int("FGPU_CLUSTER_GRID", 256));              // the most blocks k_walk_cluster gets
     const uint64_t refresh_div = (uint64_t)std::max(1, env_int("FGPU_REFRESH_DIV", 4));                  // a window's planes are made again when the delta exceeds its positions / this
     const unsigned delta_per_block = (unsigned)std::max(1, env_int("FGPU_DELTA_PER_BLOCK", 1024));       // created keys per block of k_walk_register's delta part
     const int ko_avg = getenv("FGPU_WALK_KO_AVG") ? std::min(255, std::max(0, env_int("FGPU_WALK_KO_AVG", 0))) : -1;   // lk positions per piece that make "repeat pieces" (-1: large_cluster_rule decides)
     const int ko_avg_min = getenv("FGPU_WALK_KO_AVG_MIN") ? std::min(255, std::max(1, env_int("FGPU_WALK_KO_AVG_MIN", 0))) : -1;   // the bar in all for clusters of repeat pieces (-1: likewise)
-    const uint32_t ko_ticket = (uint32_t)std::max(64, env_int("FGPU_KO_TICKET", 64) / 64 * 64);          // pieces per ticket of k_walk_ko at the most, a multiple of 64
     const int ovw_followers = env_int("FGPU_OVW_FOLLOWERS", 0);         // 1: the optimistic walk's pieces count as queueing ones for the window-size controller
-    const bool ovw_beside = !env_is_one("FGPU_OVW_SERIAL");             // FGPU_OVW_SERIAL=1: the optimistic rounds behind k_walk_dyn on one stream instead of beside it
     // waves of k_walk_dyn (the walk alone on config 2 / config 4's per-GPU shape, ms per step: 1024 waves 19.6 / 16.6; 2048 20.5 / 17.7; 4096 23.3 / 18.8;
     // one lane per leading piece -- retired -- 19.3 / 22.9)
     const unsigned walk_dyn_grid = (unsigned)std::max(1, env_int("FGPU_WALK_DYN_GRID", 1024));
@@ -2773,7 +2602,7 @@ struct WalkBatch {
     Planes pl;
     JTable jt;
     uint64_t T, ext, seq_base;    // positions of the batch; how far a piece may reach beyond its window; global number of the batch's first piece
-    hipStream_t walk_stream, ovw_stream;   // the stage's stream; the optimistic rounds' (the walk stream itself: they run behind k_walk_dyn)
+    hipStream_t walk_stream, ovw_stream;   // the stage's stream; the optimistic rounds' (beside k_walk_dyn; FGPU_NO_OVERLAP: the stage's own)
     bool cand_ok;                 // the batch's candidate plane covers every position its first window's link pass can find (see k_walk_link_sparse)
     DeltaList* created;           // the list this batch's created keys go to
 };
@@ -2783,7 +2612,7 @@ struct WalkWindow {
     uint64_t lo, hi, pos_end;     // pos_end: how far its pieces reach at the most
     int parity;                   // which of the two sets of union-find / list arrays and presence filters it uses (consecutive windows alternate)
     uint64_t max_pieces;          // bound of its pieces: the grids are sized for THIS window
-    uint32_t *uf_parent, *cl_count, *cl_offset, *cl_fail;   // the parity's set: union-find, followers per root, list heads, k_walk_par's flags / the weights
+    uint32_t *uf_parent, *cl_count, *cl_offset, *cl_weight;   // the parity's set: union-find, followers per root, list heads, lk positions per cluster (k_walk_cluster's sums)
     WTable wt;
     uint32_t *roots_state, *root_list;   // the clusters' leaders: [0] listed, [1] handed out; the list
 };
@@ -2792,7 +2621,6 @@ struct WalkWindow {
 struct LargeClusterRule {
     uint32_t ko_heavy;     // clusters of at least this many pieces go to the large-cluster walks (0: none do)
     uint32_t ko_heavy_w;   // the rule by weight, packed (see ko_cluster; 0: off)
-    uint32_t heavy;        // the out-of-order walk's bar (k_walk_par; 0: off)
     int ovw_rounds;        // rounds of the optimistic walk per window
     bool ovw_on;           // ... and whether this window issues them
 };
@@ -2881,7 +2709,7 @@ static int walk_window_begin(fgpu_ctx* ctx, const WalkBatch& wb, uint64_t lo, ui
     // grids sized for THIS window (a window of w positions holds at most w/(k+1)+2 piece starts): small windows -- high
     // coverage data -- must not pay for the launch of the thousands of empty blocks the largest window would need
     const uint64_t max_pieces = std::min<uint64_t>((hi - lo) / (uint64_t)(ctx->fd.k + 1) + 2, ctx->wmax);
-    *w = WalkWindow{lo, hi, std::min<uint64_t>(wb.T, hi + wb.ext), parity, max_pieces, ctx->uf_parent + set, ctx->cl_count + set, ctx->cl_offset + set, ctx->cl_fail + set,
+    *w = WalkWindow{lo, hi, std::min<uint64_t>(wb.T, hi + wb.ext), parity, max_pieces, ctx->uf_parent + set, ctx->cl_count + set, ctx->cl_offset + set, ctx->cl_weight + set,
                     make_wt(ctx, ctx->wt_epoch, parity),     // (its presence filter was zeroed by the reset kernel of the window before last)
                     ctx->cl_roots, ctx->cl_roots + 16};
     return FGPU_OK;
@@ -2964,10 +2792,9 @@ static LargeClusterRule large_cluster_rule(fgpu_ctx* ctx, const WalkKnobs& kn) {
     // The key-ordered walk costs four small launches per window whether or not the window holds a large cluster, so it is switched on by
     // what the scan has shown so far: the largest cluster among the windows whose counters the host has seen.  Data without such clusters
     // never pays; data with them walks its first batch by cluster.  FGPU_WALK_KO_ALWAYS=1: from the first window (tests).
-    r.ko_heavy = (kn.dbg_walk || !ctx->walk_ko || !(ctx->walk_ko_always || seen.max_cluster >= ctx->walk_ko)) ? 0u : ctx->walk_ko;
+    r.ko_heavy = (!ctx->walk_ko || !(ctx->walk_ko_always || seen.max_cluster >= ctx->walk_ko)) ? 0u : ctx->walk_ko;
     // ... and, for callers that expect repeats, the clusters whose pieces hold many lk positions between them (ko_cluster): the weights
-    // are summed by k_walk_cluster into cl_fail, which the out-of-order walk (k_walk_par, the other way of taking clusters out of k_walk_dyn)
-    // does not use then
+    // are summed by k_walk_cluster into cl_weight.
     // The rule by weight has two bars: lk positions of a cluster in all (ko_total), and -- for clusters of "repeat pieces", pieces that hold
     // many of them -- positions per piece and a lower bar in all.  Ordinary pieces hold 2-5, some 8 and more; pieces inside a repeat at high
     // coverage 40 and more.  Once a scan HAS shown repeats (2 % of the pieces walked so far went to the large-cluster walks) the second bar
@@ -2981,7 +2808,6 @@ static LargeClusterRule large_cluster_rule(fgpu_ctx* ctx, const WalkKnobs& kn) {
     const uint32_t ko_avg = kn.ko_avg >= 0 ? (uint32_t)kn.ko_avg : repeats_seen ? 8u : 12u;
     const uint32_t ko_total_rep = kn.ko_avg_min > 0 ? (uint32_t)kn.ko_avg_min : repeats_seen ? 16u : std::min<uint32_t>(255u, 3 * ko_total / 8);
     r.ko_heavy_w = (r.ko_heavy && ko_total) ? (ko_total | (ko_avg << 16) | (ko_total_rep << 24)) : 0u;
-    r.heavy = (kn.dbg_walk || r.ko_heavy) ? 0u : ctx->walk_heavy;   // (one way of taking large clusters out of k_walk_dyn at a time)
     // The optimistic walk (k_ovw_round) takes the large clusters first; the key-ordered walk runs behind it for what it leaves.  Its
     // rounds are launches whether or not the window holds such a cluster, so -- like the key-ordered walk itself -- it is switched on by
     // what the scan has shown: pieces of large clusters among the pieces walked so far (callers that expect repeats: from the first window).
@@ -3074,7 +2900,7 @@ static int walk_large_first(fgpu_ctx* ctx, const WalkKnobs& kn, const WalkBatch&
         if (rule.ovw_on) FGPU_LAUNCH("walk_ko_prepare", k_ovw_reset, 64, 256, ot.state, ovw_filt, 3 * filt_words, ot.longp, (uint32_t)w.max_pieces,
                                      (uint32_t*)ctx->ovw_marks.p, 3u << OVW_MARK_LOG2);
         FGPU_LAUNCH("walk_ko_prepare", k_ko_prepare, fgpu_blocks(w.max_pieces, 256), 256, wb.pl, (const uint32_t*)ctx->cl_fill, (const uint32_t*)w.cl_count,
-                    (const WinDesc*)ctx->wdesc, kt, rule.ko_heavy, (uint32_t)w.parity, (const uint32_t*)w.cl_fail, rule.ko_heavy_w, ot);
+                    (const WinDesc*)ctx->wdesc, kt, rule.ko_heavy, (uint32_t)w.parity, (const uint32_t*)w.cl_weight, rule.ko_heavy_w, ot);
     }
     if (!rule.ovw_on) return FGPU_OK;
     if (wb.ovw_stream != wb.walk_stream) {
@@ -3122,39 +2948,30 @@ static int walk_large_first(fgpu_ctx* ctx, const WalkKnobs& kn, const WalkBatch&
     return FGPU_OK;
 }
 
-// Step D: the walks.  k_walk_dyn takes every cluster nobody else does; behind it (and behind the optimistic walk, whose settled logs are in the
-// map by then) the key-ordered walk takes what the optimistic walk left; k_walk_par's two halves bracket them where the out-of-order walk is on.
+// Steps D and D': the walks.  k_walk_dyn takes every cluster nobody else does; behind it (and behind the optimistic walk, whose settled logs are in
+// the map by then) the key-ordered walk takes what the optimistic walk left.
 static int walk_clusters(fgpu_ctx* ctx, const WalkKnobs& kn, const WalkBatch& wb, const WalkWindow& w, const LargeClusterRule& rule, const KoTables& kt,
                          const OvwTables& ot) {
     const unsigned walk_grid_w = fgpu_blocks(w.max_pieces, 64);
-#ifdef FGPU_KO_ONE_XCD
-    const unsigned ko_grid = 4096;
-#else
     const unsigned ko_grid = 512;
-#endif
-    if (rule.heavy)
-        FGPU_LAUNCH("walk_probe", k_walk_par<WALK_PROBE>, walk_grid_w, 64, wb.pl, ctx->fd, wb.jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)w.cl_count, w.cl_fail,
-                    (const WinDesc*)ctx->wdesc, (const uint32_t*)ctx->bloo2, ctx->counters, rule.heavy);
+    const uint32_t ko_ticket = 64;      // pieces per ticket of k_walk_ko at the most, a multiple of 64
     FGPU_LAUNCH("walk", k_walk_dyn, std::min(walk_grid_w, kn.walk_dyn_grid), 64, wb.pl, ctx->fd, wb.jt, (const uint32_t*)w.root_list, w.roots_state,
                 (const uint32_t*)w.cl_count, (const uint32_t*)w.cl_offset, (const uint32_t*)ctx->cl_members, ctx->cl_members + ctx->wmax, (const WinDesc*)ctx->wdesc,
-                wb.seq_base, (const uint32_t*)ctx->bloo2, ctx->counters, kn.dbg_walk, (const uint32_t*)w.cl_fail, rule.heavy, (const uint32_t*)kt.bad,
+                wb.seq_base, (const uint32_t*)ctx->bloo2, ctx->counters, (const uint32_t*)w.cl_weight, (const uint32_t*)kt.bad,
                 (const uint32_t*)kt.state, rule.ko_heavy, (uint32_t)ctx->scan_windows, rule.ko_heavy_w);
     if (rule.ovw_on && wb.ovw_stream != wb.walk_stream) FGPU_HIP(hipStreamWaitEvent(wb.walk_stream, ctx->ev_settled, 0));   // the settled logs are in the map
     if (rule.ko_heavy) {     // (ranks of the occurrences per k-mer: only the key-ordered walk needs them, and only for what the optimistic walk left)
         FGPU_LAUNCH("walk_ko_prepare", k_ko_rank, 256, 256, kt, (const uint32_t*)ot.state, rule.ovw_rounds);
         FGPU_LAUNCH("walk_ko", k_walk_ko, ko_grid, 64, wb.pl, ctx->fd, wb.jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)w.cl_count, (const WinDesc*)ctx->wdesc,
-                    wb.seq_base, (const uint32_t*)ctx->bloo2, ctx->counters, kt, rule.ko_heavy, kn.ko_ticket, (const uint32_t*)w.cl_fail, rule.ko_heavy_w,
+                    wb.seq_base, (const uint32_t*)ctx->bloo2, ctx->counters, kt, rule.ko_heavy, ko_ticket, (const uint32_t*)w.cl_weight, rule.ko_heavy_w,
                     (const uint32_t*)ot.state, (const uint32_t*)ot.longp, rule.ovw_rounds);
     }
-    if (rule.heavy)
-        FGPU_LAUNCH("walk_commit", k_walk_par<WALK_COMMIT>, walk_grid_w, 64, wb.pl, ctx->fd, wb.jt, (const uint32_t*)ctx->cl_fill, (const uint32_t*)w.cl_count, w.cl_fail,
-                    (const WinDesc*)ctx->wdesc, (const uint32_t*)ctx->bloo2, ctx->counters, rule.heavy);
     return FGPU_OK;
 }
 
 // Step E: the keys this window created join the batch's list (and leave the plane): the next window's delta.  The window's set of arrays is
 // reset on the side stream while the next window (the other set) is looked up and linked.
-static int walk_collect_and_reset(fgpu_ctx* ctx, const WalkKnobs& kn, const WalkBatch& wb, const WalkWindow& w) {
+static int walk_collect_and_reset(fgpu_ctx* ctx, const WalkBatch& wb, const WalkWindow& w) {
     const BatchBufs& bb = wb.bb;
     const uint64_t w_first = w.lo >> 6, w_last = std::min<uint64_t>(bb.n_words, (w.pos_end + 63) / 64);
     FGPU_LAUNCH("walk_delta", k_delta_collect, (unsigned)std::min<uint64_t>(fgpu_blocks(w_last - w_first, 256), 256), 256, (unsigned long long*)bb.cr.p,
@@ -3163,11 +2980,10 @@ static int walk_collect_and_reset(fgpu_ctx* ctx, const WalkKnobs& kn, const Walk
     FGPU_HIP(hipEventRecord(ctx->ev_walked, wb.walk_stream));
     FGPU_HIP(hipStreamWaitEvent(ctx->cstream, ctx->ev_walked, 0));
     ctx->launch_stream = ctx->cstream;
-    FGPU_LAUNCH("walk_clean", k_walk_reset_uf, std::min(256u, fgpu_blocks(w.max_pieces, 256)), 256, w.uf_parent, w.cl_count, w.cl_offset, w.cl_fail, (uint32_t)w.max_pieces,
+    FGPU_LAUNCH("walk_clean", k_walk_reset_uf, std::min(256u, fgpu_blocks(w.max_pieces, 256)), 256, w.uf_parent, w.cl_count, w.cl_offset, w.cl_weight, (uint32_t)w.max_pieces,
                 (uint4*)w.wt.bits, (uint32_t)((1u << ctx->wbits_log2) / 128));
     ctx->launch_stream = wb.walk_stream;
     FGPU_HIP(hipEventRecord(ctx->ev_uf_reset[w.parity], ctx->cstream));
-    if (kn.serial_clean) FGPU_HIP(hipStreamWaitEvent(wb.walk_stream, ctx->ev_uf_reset[w.parity], 0));
     return FGPU_OK;
 }
 
@@ -3251,7 +3067,7 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
     // the whole stage goes to the walk stream, every window behind the ranges of this batch's pure stage that it reads (a batch of one range: the
     // stage behind the batch's pure stage); the optimistic rounds to a stream of their own
     hipStream_t walk_stream = kn.no_overlap ? ctx->stream : ctx->wstream;
-    hipStream_t ovw_stream = (kn.ovw_beside && !kn.no_overlap && ctx->ostream) ? ctx->ostream : walk_stream;
+    hipStream_t ovw_stream = (!kn.no_overlap && ctx->ostream) ? ctx->ostream : walk_stream;
     // the list this batch's created keys go to: the oldest of the ring (its readers -- the windows of the batches in between -- are
     // behind us on this stream)
     WalkBatch wb{bb, pl, make_jt(ctx), bb.T, ext, ctx->scan_piece_base, walk_stream, ovw_stream, false, &ctx->delta_ring[ctx->delta_next % FGPU_DELTA_RING]};
@@ -3284,8 +3100,8 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
     // window is linked by the plane (the later ones register what the earlier ones created and are linked in full), and the walk itself is no
     // slower on the whole batch (hop of config 4 on 8 shards, 23 windows -> 14: k_walk_dyn 22.3 -> 22.6 ms, the link passes 12.7 -> 8.7, the hop
     // 69.1 -> 64.9 ms: profiles/r06_hop_sparse_link.txt).  The controller's own span is left as it is (it goes on voting from the counters; once it
-    // asks for less than half a batch this rule no longer applies).  FGPU_NO_WHOLE_BATCH=1: off (measurement aid).
-    const bool whole_batch = wb.cand_ok && !kn.no_whole_batch && !ctx->prm.walk_window_span && ctx->calib_left <= 0 && span * 2 >= T && span < T && T <= ctx->max_span &&
+    // asks for less than half a batch this rule no longer applies).
+    const bool whole_batch = wb.cand_ok && !ctx->prm.walk_window_span && ctx->calib_left <= 0 && span * 2 >= T && span < T && T <= ctx->max_span &&
                              bb.n_pieces <= ctx->wmax;
     for (uint64_t lo = 0, step = 0; lo < T; lo += step) {
         step = whole_batch ? T : span_now;
@@ -3297,9 +3113,9 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
         const LargeClusterRule rule = large_cluster_rule(ctx, kn);
         // clusters -> member lists: cl_count = followers per root, cl_offset = list heads, cl_fill = flat roots, cl_members = [next links | pool]
         FGPU_LAUNCH("walk_cluster", k_walk_cluster, std::min(kn.cluster_grid, fgpu_blocks(w.max_pieces, 256)), 256, (const uint32_t*)w.uf_parent, w.cl_count, w.cl_offset,
-                    ctx->cl_fill, ctx->cl_members, pl, lo, w.hi, (WinDesc*)ctx->wdesc, ctx->counters, w.cl_fail, rule.ko_heavy_w, w.root_list, w.roots_state);
+                    ctx->cl_fill, ctx->cl_members, pl, lo, w.hi, (WinDesc*)ctx->wdesc, ctx->counters, w.cl_weight, rule.ko_heavy_w, w.root_list, w.roots_state);
         if ((rc = walk_large_tables(ctx, wb, rule, kt, ot)) || (rc = walk_large_first(ctx, kn, wb, w, rule, kt, ot)) || (rc = walk_clusters(ctx, kn, wb, w, rule, kt, ot)) ||
-            (rc = walk_collect_and_reset(ctx, kn, wb, w)))
+            (rc = walk_collect_and_reset(ctx, wb, w)))
             return rc;
         ctx->scan_windows++;
         if ((rc = walk_span_look(ctx, kn, walk_stream, &span_now))) return rc;

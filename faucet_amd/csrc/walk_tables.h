@@ -161,11 +161,7 @@ __global__ void __launch_bounds__(256) k_iota_u32(uint32_t* p, uint64_t n) {
 }
 
 // ---- the tables of a context, as the kernels take them -------------------------------------------
-static inline uint64_t jfilter_bits(fgpu_ctx* ctx) {
-    static const int lg = getenv("FGPU_JFILTER_LOG2") ? atoi(getenv("FGPU_JFILTER_LOG2")) : 0;   // measurement aid
-    const uint64_t full = ctx->jcap * 2;
-    return lg >= 10 && (1ULL << lg) < full ? 1ULL << lg : full;
-}
+static inline uint64_t jfilter_bits(fgpu_ctx* ctx) { return ctx->jcap * 2; }
 static inline JTable make_jt(fgpu_ctx* ctx) { return JTable{ctx->jkeys, ctx->jrecs, ctx->jstamps, ctx->jcap - 1, ctx->jfilter, jfilter_bits(ctx) - 1}; }
 static inline WTable make_wt(fgpu_ctx* ctx, uint64_t epoch, int parity) {
     return WTable{ctx->wkeys, ctx->wbits + parity * ((1ULL << ctx->wbits_log2) / 32), ctx->wcap - 1, epoch << 56, (uint32_t)(32 - ctx->wbits_log2)};

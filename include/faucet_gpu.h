@@ -123,7 +123,8 @@ typedef struct {
     uint64_t valid_reused;       /* getValidReads answers taken from the load pass' resident planes (no filter probe) */
     uint64_t flags_filled;       /* windows whose testForJunction the walk evaluated itself because the preview had left them out */
     uint64_t walk_parallel;      /* pieces of large clusters walked apart from their cluster's thread: in the order of their junction k-mers'
-                                  * turns (k_walk_ko, the default for clusters of 64 pieces and more) or out of order (FGPU_WALK_HEAVY) */
+                                  * turns (k_walk_ko, the default for clusters of 64 pieces and more) or all at once, round after round until
+                                  * their logs settle (k_ovw_round / k_ovw_commit, the optimistic walk) */
 } fgpu_scan_stats;
 
 /* One element of the list ReadScanner::scanInputRead returns for a read (src/ReadScanner.cpp:260-282): the real-extension
@@ -857,8 +858,8 @@ int fgpu_diag_pair_placements(fgpu_ctx* ctx, int k, uint64_t n_items, double* it
 int fgpu_diag_binned_probes(fgpu_ctx* ctx, uint64_t table_bytes, uint64_t n_probes, uint64_t slice_bytes, int iters, double* direct_per_s,
                             double* binned_per_s, double* bin_ms, double* probe_ms);
 /* How often the library has scanned a pass's batches again by itself (lazy junction tests, see fgpu_scan_batch) since the context was made. */
-/* after fgpu_scan_end: pieces of large clusters probed for the out-of-order walk, by outcome: [0] order-free, [1] would create a junction,
- * [2] would raise a distance, [3] crosses positions whose junction tests the preview left out */
+/* Kept for the ABI: the out-of-order walk of large clusters whose probed pieces this counted by outcome is retired (measured: it did not pay);
+ * out[0..3] = 0. */
 int fgpu_diag_walk_probe(fgpu_ctx* ctx, uint64_t out[4]);
 int fgpu_diag_scan_replays(fgpu_ctx* ctx, uint64_t* replays);
 /* How often the host thread has waited for the device (hipStreamSynchronize / hipEventSynchronize inside the library) since the current or last pass

@@ -31,6 +31,5 @@ for rep in range(2):
     sc = api.ReadScanner(ctx)
     st = sc.scanReads(batches)
 print({k: st[k] for k in st})
-print('probe outcomes [order-free, create, raise, untested]:', ctx.diag_walk_probe())
 for name, (calls, ms) in sorted(ctx.kernel_times().items(), key=lambda kv: -kv[1][1])[:14]:
     print(f"{name:24s} {ms:9.2f} ms {calls}")
