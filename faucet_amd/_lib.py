@@ -180,6 +180,8 @@ SIGNATURES = {
     "fgpu_stage3_set_junctions": (C.c_int, [_vp, _vp, _vp, _u64]),
     "fgpu_stage3_find_neighbors": (C.c_int, [_vp, _vp, _vp, _u64, _i32, _vp, _P(_u64), _vp, _u64]),
     "fgpu_stage3_contig_words": (_u64, [_i32, _i32]),
+    "fgpu_stage3_contigs": (C.c_int, [_vp, _vp, _vp, _u64, _i32, _vp, _P(_u64), _P(_u64)]),
+    "fgpu_stage3_contigs_take": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),
     "fgpu_kernel_times": (C.c_int, [_vp, _P(KernelTime), C.c_int]),
     "fgpu_kernel_times_reset": (C.c_int, [_vp]),
     "fgpu_profile_enable": (C.c_int, [_vp, C.c_int]),

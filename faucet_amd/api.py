@@ -118,6 +118,8 @@ STOP_DTYPE = np.dtype([("ext", "<u8"), ("read", "<u4"), ("info", "<u4")])
 JUNC_DTYPE = np.dtype([("cov", np.uint8, 4), ("dist", np.uint8, 5), ("linked", np.uint8, 5)])
 NEIGHBOR_DTYPE = np.dtype([("kmer", "<u8"), ("dist", "<i4"), ("len", "<i4"), ("node", "i1"), ("rindex", "i1"), ("abort", "i1"), ("reserved", "i1"),
                            ("reserved2", "<i4")])   # fgpu_neighbor
+CONTIG_DTYPE = np.dtype([("end_kmer", "<u8"), ("text_word", "<u8"), ("seg_first", "<u8"), ("cov_first", "<u8"), ("len", "<u4"), ("n_seg", "<u4"),
+                         ("n_cov", "<u4"), ("ind1", "i1"), ("ind2", "i1"), ("end_node", "i1"), ("status", "i1")])   # fgpu_contig
 
 
 class _PinnedMemory:
@@ -720,6 +722,35 @@ class Context:
         codes = (text.reshape(n, stride)[:, :, None] >> (2 * np.arange(32, dtype=np.uint64))[None, None, :]) & np.uint64(3)
         chars = np.frombuffer(b"ACTG", dtype=np.uint8)[codes.reshape(n, stride * 32).astype(np.int64)]
         return out, int(probes.value), [chars[i, :int(out["len"][i])].tobytes().decode() for i in range(n)]
+
+    def stage3_contigs(self, start_kmers, indices, max_read_length: int, raw: bool = False):
+        """JunctionMap::getContig for every (start k-mer, start index) pair, whole chains on the device against the map of
+        stage3_set_junctions as it stands.  Returns (CONTIG_DTYPE array, strings, distances, coverages, kills, probes): per chain the contig
+        string, the distance and coverage lists as uint8 arrays and kmers_to_destroy as a uint64 array (all empty for a status other than 0),
+        and the number of getValidJExtension evaluations of the call.  raw=True: (CONTIG_DTYPE array, text words, segment k-mers, segment
+        distances, coverages, probes), the arrays as the library lays them out."""
+        start_kmers = np.ascontiguousarray(start_kmers, dtype=np.uint64)
+        indices = np.ascontiguousarray(indices, dtype=np.int8)
+        assert len(start_kmers) == len(indices)
+        n = len(start_kmers)
+        out = np.zeros(n, dtype=CONTIG_DTYPE)
+        totals = (C.c_uint64 * 3)()
+        probes = C.c_uint64(0)
+        self._c(self.lib.fgpu_stage3_contigs(self.h, start_kmers.ctypes.data, indices.ctypes.data, n, int(max_read_length), out.ctypes.data, totals, C.byref(probes)))
+        text, kmers = np.zeros(totals[0], dtype=np.uint64), np.zeros(totals[1], dtype=np.uint64)
+        dist, cov = np.zeros(totals[1], dtype=np.uint8), np.zeros(totals[2], dtype=np.uint8)
+        self._c(self.lib.fgpu_stage3_contigs_take(self.h, text.ctypes.data, len(text), kmers.ctypes.data, dist.ctypes.data, len(dist), cov.ctypes.data, len(cov)))
+        if raw:
+            return out, text, kmers, dist, cov, int(probes.value)
+        chars = np.frombuffer(b"ACTG", dtype=np.uint8)[((text[:, None] >> (2 * np.arange(32, dtype=np.uint64))[None, :]) & np.uint64(3)).astype(np.int64)].reshape(-1)
+        strings, dists, covs, kills = [], [], [], []
+        for c in out:
+            t, s, v, ns = int(c["text_word"]), int(c["seg_first"]), int(c["cov_first"]), int(c["n_seg"])
+            strings.append(chars[32 * t:32 * t + int(c["len"])].tobytes().decode())
+            dists.append(dist[s:s + ns])
+            covs.append(cov[v:v + int(c["n_cov"])])
+            kills.append(kmers[s:s + max(ns - 1, 0)])
+        return out, strings, dists, covs, kills, int(probes.value)
 
     def kernel_times(self) -> dict:
         arr = (L.KernelTime * 64)()

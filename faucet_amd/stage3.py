@@ -13,10 +13,47 @@ Restated from the reference's control flow (not its text), its asserts included:
 Checked against the reference's own findNeighbor on the golden maps, on fresh runs at even and small k and on seeded variants of both
 with thinned maps, damaged filters and shifted distances (oracle/_ref/ref_kat neighbors -> tests/golden/stage3_neighbors_*.jsonl.gz,
 tests/stage3_variants.py, tests/test_stage3_walker.py).
+
+`NeighborWalker.contigs` chains such calls into JunctionMap::getContig (:133-221) for many starts, one round of findNeighbor calls per chain
+segment, with the bookkeeping on the host: what a caller had to do before fgpu_stage3_contigs (api.Context.stage3_contigs) did the whole
+chain on the device.  It stays as the second implementation and as the baseline scripts/stage3_contig_times.py times.  `branching_starts`
+and `linear_starts` list the getContig calls of the reference's two graph-build loops on a map that does not change.
 """
 from __future__ import annotations
 
 import numpy as np
+
+NT = "ACTG"                                     # the reference's 2-bit code: A 0, C 1, T 2, G 3
+
+
+def _kmer_string(x: int, k: int) -> str:
+    return "".join(NT[(x >> (2 * i)) & 3] for i in range(k - 1, -1, -1))
+
+
+def branching_starts(keys, recs, k: int):
+    """(k-mers, indices) of the getContig calls buildBranchingPaths (utils/JunctionMap.cpp:36-50) makes on a map that does not change: every
+    covered index 0..4 of every junction with more than one path out, in map order -- the first base's extension of a homopolymer k-mer
+    left out (:43-47; coverage 4 is the sum of what is left)."""
+    cov = np.array(recs["cov"], dtype=np.int64)
+    keys = np.asarray(keys, dtype=np.uint64)
+    complex_ = (cov > 0).sum(axis=1) > 1
+    for r in np.nonzero(complex_)[0]:
+        s = _kmer_string(int(keys[r]), k)
+        if len(set(s)) == 1:
+            cov[r, NT.index(s[0])] = 0
+    c5 = np.concatenate([cov, cov.sum(axis=1, keepdims=True)], axis=1)
+    rows, idx = np.nonzero((c5 > 0) & complex_[:, None])
+    return keys[rows], idx.astype(np.int8)
+
+
+def linear_starts(keys, recs):
+    """(k-mers, indices) of the getContig calls buildLinearRegions (:105-118) makes: the covered extension, then 4, of every junction with
+    exactly one path out, in map order"""
+    cov = np.asarray(recs["cov"], dtype=np.int64)
+    keys = np.asarray(keys, dtype=np.uint64)
+    rows = np.nonzero((cov > 0).sum(axis=1) == 1)[0]
+    idx = np.stack([(cov[rows] > 0).argmax(axis=1), np.full(len(rows), 4)], axis=1)
+    return np.repeat(keys[rows], 2), idx.reshape(-1).astype(np.int8)
 
 
 class NeighborWalker:
@@ -26,9 +63,14 @@ class NeighborWalker:
         order = np.argsort(np.asarray(keys, dtype=np.uint64), kind="stable")
         self.keys = np.asarray(keys, dtype=np.uint64)[order]
         self.dist = np.asarray(recs["dist"], dtype=np.int64)[order]
+        try:
+            self.cov = np.asarray(recs["cov"], dtype=np.int64)[order]           # (only contigs() reads the coverages)
+        except (KeyError, ValueError):
+            self.cov = None
         self.mask = np.uint64((1 << (2 * k)) - 1)
         self.steps = 0          # device calls made by the last find_neighbors
         self.probes = 0         # k-mers handed to getValidJExtension in them
+        self.rounds = 0         # rounds of findNeighbor calls made by the last contigs
 
     # ---- the reference's k-mer helpers on arrays (utils/Kmer.cpp:238-252,410-425; utils/DoubleKmer.cpp) ----
     def _revcomp(self, x):
@@ -48,10 +90,11 @@ class NeighborWalker:
         i = np.minimum(i, len(self.keys) - 1)
         return self.keys[i] == km, i
 
-    def find_neighbors(self, start_kmers, indices):
+    def find_neighbors(self, start_kmers, indices, contigs: bool = False):
         """findNeighbor(junctionMap[start], start, index) for every pair; returns a structured array (kmer, node, rindex, dist, len,
         abort) in input order.  `abort` marks the calls in which the reference trips one of its asserts: dist <= maxDist after the first
-        k-mers, a valid extension at every step up to maxDist, and a valid extension at a junction met before maxDist."""
+        k-mers, a valid extension at every step up to maxDist, and a valid extension at a junction met before maxDist.
+        contigs=True: (that array, the list of BfSearchResult::contig strings)."""
         k = self.k
         n = len(start_kmers)
         km = np.asarray(start_kmers, dtype=np.uint64).copy()
@@ -110,6 +153,10 @@ class NeighborWalker:
         isj, _ = self._is_junction(km)
         m2 = m & isj
         finish(m2, km[m2], 1, 4, 2, ln[m2])
+        text = None
+        if contigs:                                                              # :254-256, :272-276: the reversed k-mer, or the first base and the k-mer behind it
+            first = np.asarray(start_kmers, dtype=np.uint64) >> np.uint64(2 * k - 2)
+            text = [([] if b else [int(f)]) + [(int(x) >> (2 * i)) & 3 for i in range(k - 1, -1, -1)] for b, f, x in zip(back, first, km)]
         m = ~done & (dist > maxd)                                                # the reference's assert(dist <= maxDist)
         out["abort"][m] = 1
         done[m] = True
@@ -148,6 +195,9 @@ class NeighborWalker:
             nk, nr = self._forward(km[act], rc[act], ext)
             km[act], rc[act] = nk, nr
             ln[act] += 1
+            if contigs:
+                for w, e in zip(act, ext):
+                    text[w].append(int(e))
             # backward-facing half-step
             dist[act] += 1
             km[act], rc[act] = rc[act].copy(), km[act].copy()
@@ -184,4 +234,66 @@ class NeighborWalker:
                 finish(w[ok], km[w[ok]], 1, 4, dist[w[ok]], ln[w[ok]])
                 out[w[~ok]] = sink[w[~ok]]
                 phase[w[~ok]] = 2
+        if contigs:
+            return out, ["".join(NT[c] for c in t[:int(ln_)]) for t, ln_ in zip(text, out["len"])]
         return out
+
+    def contigs(self, start_kmers, indices, find=None):
+        """getContig(junctionMap[start], start, index) (utils/JunctionMap.cpp:133-221) for every pair, all chains in lock-step: one `find`
+        call per round answers the next findNeighbor of every chain under way.  find(kmers, indices) -> (results, contig strings);
+        default: this walker's find_neighbors.  Returns a list of dicts in input order: status (0 the reference returns, 1 it trips an
+        assert, 2 no such junction or index, 3 it never returns: the chain came back to a (junction, index) that is not its start),
+        ind1, ind2, end_kmer, end_node, string, distances, coverages, kills -- the last five empty unless status is 0."""
+        k = self.k
+        find = find or (lambda km, ix: self.find_neighbors(km, ix, contigs=True))
+        start_kmers = np.asarray(start_kmers, dtype=np.uint64)
+        indices = np.asarray(indices, dtype=np.int64)
+        cov5 = np.concatenate([self.cov, self.cov.sum(axis=1, keepdims=True)], axis=1)
+
+        def row_of(x):
+            i = min(int(np.searchsorted(self.keys, np.uint64(x))), len(self.keys) - 1)
+            return i if len(self.keys) and int(self.keys[i]) == int(x) else -1
+
+        chains, act = [], []
+        for i, (x, ix) in enumerate(zip(start_kmers, indices)):
+            x, ix = int(x), int(ix)
+            r = row_of(x) if 0 <= ix <= 4 else -1
+            c = dict(status=0 if r >= 0 else 2, ind1=0, ind2=0, end_kmer=0, end_node=0, string="", distances=[], coverages=[], kills=[])
+            if r >= 0:
+                c.update(ind1=ix, coverages=[int(cov5[r, ix]) & 0xFF], at=(x, ix), seen=set(),
+                         string=_kmer_string(int(self._revcomp(np.array([x], dtype=np.uint64))[0]) if ix == 4 else x, k))    # :148-151
+                act.append(i)
+            chains.append(c)
+        self.rounds = 0
+        while act:
+            res, strings = find(np.array([chains[i]["at"][0] for i in act], dtype=np.uint64), np.array([chains[i]["at"][1] for i in act], dtype=np.int8))
+            self.rounds += 1
+            nxt = []
+            for i, r, text in zip(act, res, strings):
+                c = chains[i]
+                if r["abort"]:
+                    c["status"] = 1
+                    continue
+                if int(r["len"]) > k:                                             # :160-162
+                    c["string"] += text[k:]
+                c["distances"].append(int(r["dist"]) & 0xFF)                      # :163
+                c["end_kmer"], c["end_node"], c["ind2"] = int(r["kmer"]), int(r["node"]), int(r["rindex"]) if r["node"] else 4
+                if not r["node"]:
+                    continue
+                row = row_of(int(r["kmer"]))
+                c["coverages"].append(int(cov5[row, int(r["rindex"])]) & 0xFF)    # :169
+                if (self.cov[row] > 0).sum() != 1 or int(r["kmer"]) == int(start_kmers[i]):   # :171-191
+                    continue
+                c["kills"].append(int(r["kmer"]))
+                c["at"] = (int(r["kmer"]), 4 if r["rindex"] < 4 else int((self.cov[row] > 0).argmax()))   # getOppositeIndex
+                if c["at"] in c["seen"]:
+                    c["status"] = 3
+                    continue
+                c["seen"].add(c["at"])
+                nxt.append(i)
+            act = nxt
+        for c in chains:
+            c.pop("at", None), c.pop("seen", None)
+            if c["status"]:
+                c.update(ind1=0, ind2=0, end_kmer=0, end_node=0, string="", distances=[], coverages=[], kills=[])
+        return chains

@@ -816,6 +816,44 @@ int fgpu_stage3_find_neighbors(fgpu_ctx* ctx, const uint64_t* start_kmers_host, 
                                uint64_t contig_stride_words);
 uint64_t fgpu_stage3_contig_words(int32_t k, int32_t max_read_length);
 
+/* ---- Stage 3's contigs: whole getContig chains -------------------------------------
+ * JunctionMap::getContig(junctionMap[start], start, index) (utils/JunctionMap.cpp:133-221) for n starts at once, against bloo2 and the map of
+ * fgpu_stage3_set_junctions as they stand (here the four coverages of a record are read as well): findNeighbor after findNeighbor through
+ * every junction with one path out (Junction::numPathsOut() == 1; on at getOppositeIndex(result.index): 4 after a forward entry, the covered
+ * extension after a backward one) until a complex junction, a sink, or the start k-mer again.  The map is static within the call -- the
+ * reference kills the junctions of a chain only behind its loop (:210-216) -- so every chain is a function of (map, filter, start) alone,
+ * and which answers a graph build may still use after the kills of earlier ones is the caller's business.
+ * Cost: one call walks every directed segment it can need once -- the n first calls, and up to two per junction with one path out --
+ * whatever n is, and keeps nothing for the next call: hand over all starts of a stage in one call.
+ * Per chain: the string (print_kmer(start), its reverse complement for index 4, then result.contig.substr(k) of every segment longer than
+ * k), distances (one byte per findNeighbor call), coverages (getCoverage(startIndex), then nextJunc.getCoverage(result.index) of every
+ * call that ended at a junction; getCoverage(4) is the sum of the four; each a byte) and the k-mer every call ended at: seg_kmers of all
+ * segments but the last ARE kmers_to_destroy.  The string starts at a word of its own, 2 bits per base in fgpu_stage3_find_neighbors' code,
+ * 32 bases per word, first base lowest, the bits behind `len` zero.
+ * status 0: the reference returns; 1: a call of the chain trips one of the reference's asserts (fgpu_neighbor.abort == 1); 2: the start is
+ * not in the map, or the index is not 0..4; 3: the chain runs into a cycle that does not hold the start k-mer -- the reference's
+ * while(!done) never returns (found in a number of hops proportional to the chain's own tail and cycle).  With a status other than 0,
+ * len, n_seg and n_cov are 0 and nothing of the chain is stored.
+ * fgpu_stage3_contigs keeps the arrays on the device and says how long they are (totals: text words, segments, coverages; all 0 for
+ * n == 0); fgpu_stage3_contigs_take copies them out and frees them.  An array with fewer entries than the totals is FGPU_ERR_ARG: nothing
+ * is copied, and the results are still there.  Results that were not taken are dropped by the next fgpu_stage3_contigs. */
+typedef struct {
+    uint64_t end_kmer;    /* BfSearchResult::kmer of the chain's last findNeighbor call */
+    uint64_t text_word;   /* first word of this contig's string in the text array */
+    uint64_t seg_first;   /* first entry of this chain in the per-segment arrays */
+    uint64_t cov_first;   /* first entry of this chain in the coverage array */
+    uint32_t len;         /* bases of contigString */
+    uint32_t n_seg;       /* findNeighbor calls made = distances.size() */
+    uint32_t n_cov;       /* coverages.size() */
+    int8_t   ind1, ind2;  /* setIndices(startIndex, result.index or 4), :201-208 */
+    int8_t   end_node;    /* the last result's isNode */
+    int8_t   status;
+} fgpu_contig;
+int fgpu_stage3_contigs(fgpu_ctx* ctx, const uint64_t* start_kmers_host, const int8_t* indices_host, uint64_t n, int32_t max_read_length,
+                        fgpu_contig* out, uint64_t totals[3], uint64_t* n_probes);
+int fgpu_stage3_contigs_take(fgpu_ctx* ctx, uint64_t* text, uint64_t text_words, uint64_t* seg_kmers, uint8_t* seg_dist, uint64_t n_seg,
+                             uint8_t* cov, uint64_t n_cov);
+
 /* ---- profiling --------------------------------------------------------------------------------- */
 typedef struct {
     char     name[48];
