@@ -10,7 +10,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libfaucet_gpu.so")
 
-OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_CAPACITY, ERR_NOMEM = range(6)
+OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_CAPACITY, ERR_NOMEM, ERR_INTERNAL = range(7)
 BLOO1, BLOO2 = 0, 1
 FLAG_PROFILE = 1
 FLAG_EAGER_FLAGS = 2
@@ -73,6 +73,14 @@ class ScanStats(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+BUILD_ROUNDS_KEPT = 32
+
+
+class BuildInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("rounds", C.c_uint32), ("stop_call", C.c_uint64), ("calls_possible", C.c_uint64), ("rewalked", C.c_uint64),
+                ("probes", C.c_uint64), ("table_hits", C.c_uint64), ("regrown", C.c_uint64), ("rewalked_by_round", C.c_uint64 * BUILD_ROUNDS_KEPT)]
 
 
 class KernelTime(C.Structure):
@@ -182,6 +190,8 @@ SIGNATURES = {
     "fgpu_stage3_contig_words": (_u64, [_i32, _i32]),
     "fgpu_stage3_contigs": (C.c_int, [_vp, _vp, _vp, _u64, _i32, _vp, _P(_u64), _P(_u64)]),
     "fgpu_stage3_contigs_take": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),
+    "fgpu_stage3_build": (C.c_int, [_vp, _i32, _P(_u64), _P(BuildInfo)]),
+    "fgpu_stage3_build_take": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),
     "fgpu_kernel_times": (C.c_int, [_vp, _P(KernelTime), C.c_int]),
     "fgpu_kernel_times_reset": (C.c_int, [_vp]),
     "fgpu_profile_enable": (C.c_int, [_vp, C.c_int]),

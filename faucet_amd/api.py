@@ -121,6 +121,10 @@ NEIGHBOR_DTYPE = np.dtype([("kmer", "<u8"), ("dist", "<i4"), ("len", "<i4"), ("n
 CONTIG_DTYPE = np.dtype([("end_kmer", "<u8"), ("text_word", "<u8"), ("seg_first", "<u8"), ("cov_first", "<u8"), ("len", "<u4"), ("n_seg", "<u4"),
                          ("n_cov", "<u4"), ("ind1", "i1"), ("ind2", "i1"), ("end_node", "i1"), ("status", "i1")])   # fgpu_contig
 
+BUILD_DTYPE = np.dtype([("start_kmer", "<u8"), ("far_kmer", "<u8"), ("time", "<u4"), ("phase", "u1"), ("far_is_junction", "u1"), ("far_is_start", "u1"),
+                        ("reserved", "u1")])   # fgpu_build_call
+BUILD_BRANCHING, BUILD_LINEAR_FORWARD, BUILD_LINEAR_BACKWARD = range(3)
+
 
 class _PinnedMemory:
     """The owner of one fgpu_host_alloc block: the ONLY place that frees it, and only when the last reference is gone -- the HostBuffer
@@ -751,6 +755,35 @@ class Context:
             covs.append(cov[v:v + int(c["n_cov"])])
             kills.append(kmers[s:s + max(ns - 1, 0)])
         return out, strings, dists, covs, kills, int(probes.value)
+
+    def stage3_build(self, max_read_length: int, raw: bool = False):
+        """JunctionMap::buildContigGraph's contig list (utils/JunctionMap.cpp:11-129) in one call: every getContig call of buildBranchingPaths and
+        buildLinearRegions that the reference makes, each on the map of stage3_set_junctions as it stands at that moment, in the reference's
+        order.  Returns (CONTIG_DTYPE array, BUILD_DTYPE array, strings, distances, coverages, kills, info): one entry per call that is made,
+        the lists as stage3_contigs gives them, and info = dict(status, stop_call, calls_possible, rounds, rewalked, rewalked_by_round, probes, table_hits, regrown)
+        -- status 0: the build ran to its end; 1 / 3: the call with number stop_call, which is not output, trips an assert / never returns.
+        raw=True: (CONTIG_DTYPE array, BUILD_DTYPE array, text words, segment k-mers, segment distances, coverages, info)."""
+        totals = (C.c_uint64 * 4)()
+        bi = L.BuildInfo()
+        self._c(self.lib.fgpu_stage3_build(self.h, int(max_read_length), totals, C.byref(bi)))
+        out, calls = np.zeros(totals[0], dtype=CONTIG_DTYPE), np.zeros(totals[0], dtype=BUILD_DTYPE)
+        text, kmers = np.zeros(totals[1], dtype=np.uint64), np.zeros(totals[2], dtype=np.uint64)
+        dist, cov = np.zeros(totals[2], dtype=np.uint8), np.zeros(totals[3], dtype=np.uint8)
+        self._c(self.lib.fgpu_stage3_build_take(self.h, out.ctypes.data, calls.ctypes.data, len(out), text.ctypes.data, len(text), kmers.ctypes.data,
+                                                dist.ctypes.data, len(dist), cov.ctypes.data, len(cov)))
+        info = dict(status=int(bi.status), stop_call=int(bi.stop_call), calls_possible=int(bi.calls_possible), rounds=int(bi.rounds), rewalked=int(bi.rewalked),
+                    rewalked_by_round=[int(v) for v in bi.rewalked_by_round[:min(int(bi.rounds), L.BUILD_ROUNDS_KEPT)]], probes=int(bi.probes), table_hits=int(bi.table_hits), regrown=int(bi.regrown))
+        if raw:
+            return out, calls, text, kmers, dist, cov, info
+        chars = np.frombuffer(b"ACTG", dtype=np.uint8)[((text[:, None] >> (2 * np.arange(32, dtype=np.uint64))[None, :]) & np.uint64(3)).astype(np.int64)].reshape(-1)
+        strings, dists, covs, kills = [], [], [], []
+        for c in out:
+            t, s, v, ns = int(c["text_word"]), int(c["seg_first"]), int(c["cov_first"]), int(c["n_seg"])
+            strings.append(chars[32 * t:32 * t + int(c["len"])].tobytes().decode())
+            dists.append(dist[s:s + ns])
+            covs.append(cov[v:v + int(c["n_cov"])])
+            kills.append(kmers[s:s + max(ns - 1, 0)])
+        return out, calls, strings, dists, covs, kills, info
 
     def kernel_times(self) -> dict:
         arr = (L.KernelTime * 64)()

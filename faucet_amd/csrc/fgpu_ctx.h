@@ -460,6 +460,8 @@ struct fgpu_ctx {
     DevBuf s3_cov;                        // ... -> four coverages, and the junction's row in s3_in (the caller's keys and records, kept)
     void* s3c_out = nullptr;              // fgpu_stage3_contigs' arrays until fgpu_stage3_contigs_take: text, segment k-mers, distances, coverages
     uint64_t s3c_totals[3] = {0, 0, 0};   // their entries: text words, segments, coverages
+    void* s3b_out = nullptr;              // fgpu_stage3_build's results until fgpu_stage3_build_take: contigs, calls, then the same four arrays
+    uint64_t s3b_totals[4] = {0, 0, 0, 0};   // calls, text words, segments, coverages
     uint64_t s3_mask = 0, s3_count = 0;
     bool s3_ready = false;
     DevBuf dl_entries, dl_stamps, dl_stamps_sorted, dl_idx, dl_idx_sorted, dl_keys, dl_recs, dl_tmp;   // junction download scratch

@@ -18,6 +18,10 @@ tests/stage3_variants.py, tests/test_stage3_walker.py).
 segment, with the bookkeeping on the host: what a caller had to do before fgpu_stage3_contigs (api.Context.stage3_contigs) did the whole
 chain on the device.  It stays as the second implementation and as the baseline scripts/stage3_contig_times.py times.  `branching_starts`
 and `linear_starts` list the getContig calls of the reference's two graph-build loops on a map that does not change.
+
+`build_serial` is JunctionMap::buildContigGraph's loop (:11-129) itself, one getContig at a time through Context.stage3_contigs with the map set
+again after every call that kills: the second implementation of fgpu_stage3_build (api.Context.stage3_build) and the baseline
+scripts/stage3_build_times.py times.
 """
 from __future__ import annotations
 
@@ -56,6 +60,75 @@ def linear_starts(keys, recs):
     return np.repeat(keys[rows], 2), idx.reshape(-1).astype(np.int8)
 
 
+def build_serial(ctx, keys, recs, k: int, max_read_length: int, limit=None):
+    """buildContigGraph's contig list, literally: buildBranchingPaths (:34-82), destroyComplexJunctions (:90-102), buildLinearRegions
+    (:104-129), every getContig one device call on the map as it stands -- ctx.stage3_set_junctions again, without the junctions that
+    are gone, after every call that kills.  Returns (calls, status, sets): one dict per call made (phase 0 branching / 1 linear forward /
+    2 linear backward, start, ind1, ind2, end_kmer, end_node, string, distances, coverages, kills, far_kmer, far_is_junction, far_is_start);
+    status 0, or 1 / 3 where the reference would not return from the next call; the number of times the map was set.
+    limit: stop (status None) after that many calls."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    recs = np.ascontiguousarray(recs)
+    cov = np.array(recs["cov"], dtype=np.int64)
+    paths = (cov > 0).sum(axis=1)
+    row_of = {int(x): r for r, x in enumerate(keys)}
+    alive = np.ones(len(keys), dtype=bool)
+    claimed, calls, state = set(), [], dict(stale=True, sets=0)
+    code = {c: i for i, c in enumerate(NT)}
+
+    def get_contig(r, i, own, phase):
+        if state["stale"]:
+            ctx.stage3_set_junctions(keys[alive], recs[alive])
+            state.update(stale=False, sets=state["sets"] + 1)
+        out, strings, dists, covs, kills, _ = ctx.stage3_contigs(keys[r:r + 1], [i], max_read_length)
+        if int(out["status"][0]):
+            return int(out["status"][0])
+        c = dict(phase=phase, start=int(keys[r]), ind1=int(out["ind1"][0]), ind2=int(out["ind2"][0]), end_kmer=int(out["end_kmer"][0]),
+                 end_node=int(out["end_node"][0]), string=strings[0], distances=dists[0].tolist(), coverages=covs[0].tolist(), kills=[int(x) for x in kills[0]])
+        c["coverages"][0] = int(own[i] if i < 4 else own.sum()) & 0xFF                    # :148 reads the caller's copy of the junction (:43-47)
+        for x in c["kills"]:                                                               # :210-216
+            if x != c["start"]:
+                alive[row_of[x]] = False
+                state["stale"] = True
+        far = 0                                                                            # Contig::getSideKmer(2), src/Contig.cpp:235-239: the last
+        for ch in (c["string"][-k:] if c["ind2"] == 4 else reversed(c["string"][-k:])):   # k-mer, reverse-complemented unless ind2 is 4
+            far = (far << 2) | (code[ch] if c["ind2"] == 4 else code[ch] ^ 2)
+        is_j = far in row_of and bool(alive[row_of[far]])                                  # :56
+        c.update(far_kmer=far, far_is_junction=int(is_j), far_is_start=int(is_j and far == c["start"]))
+        calls.append(c)
+        return 0
+
+    for r in np.nonzero(paths > 1)[0]:
+        own = cov[r].copy()
+        s = _kmer_string(int(keys[r]), k)
+        if len(set(s)) == 1:
+            own[NT.index(s[0])] = 0
+        for i in range(5):
+            if (own[i] if i < 4 else own.sum()) > 0 and (r, i) not in claimed:             # :50
+                if limit is not None and len(calls) >= limit:
+                    return calls, None, state["sets"]
+                status = get_contig(r, i, own, 0)
+                if status:
+                    return calls, status, state["sets"]
+                c = calls[-1]
+                claimed.add((r, c["ind1"]))                                                # setEnds, src/Contig.cpp:123-133
+                if c["far_is_junction"]:
+                    claimed.add((row_of[c["far_kmer"]], c["ind2"]))
+    if (paths > 1).any():
+        alive[paths > 1] = False
+        state["stale"] = True
+    for r in np.nonzero(paths == 1)[0]:
+        if not alive[r]:
+            continue
+        for phase, i in ((1, int(np.nonzero(cov[r] > 0)[0][-1])), (2, 4)):                 # :111-118
+            if limit is not None and len(calls) >= limit:
+                return calls, None, state["sets"]
+            status = get_contig(r, i, cov[r], phase)
+            if status:
+                return calls, status, state["sets"]
+    return calls, 0, state["sets"]
+
+
 class NeighborWalker:
     def __init__(self, ctx, keys, recs, k: int, max_read_length: int):
         """keys / recs: the junction map (oriented k-mers; records with 'dist'), e.g. from Context.junctions() or a parsed .junctions"""
@@ -71,6 +144,9 @@ class NeighborWalker:
         self.steps = 0          # device calls made by the last find_neighbors
         self.probes = 0         # k-mers handed to getValidJExtension in them
         self.rounds = 0         # rounds of findNeighbor calls made by the last contigs
+        self.order = order      # sorted position -> row in the caller's arrays
+        self.met = None         # after find_neighbors(alive=...): per walk, the rows of the junctions its look-ups hit, visible or not
+        self._alive = self._hits = None
 
     # ---- the reference's k-mer helpers on arrays (utils/Kmer.cpp:238-252,410-425; utils/DoubleKmer.cpp) ----
     def _revcomp(self, x):
@@ -85,12 +161,37 @@ class NeighborWalker:
         nuc = nuc.astype(np.uint64)
         return ((km << np.uint64(2)) | nuc) & self.mask, (rc >> np.uint64(2)) | ((nuc ^ np.uint64(2)) << np.uint64(2 * self.k - 2))
 
-    def _is_junction(self, km):
+    def _is_junction(self, km, who=None):
         i = np.searchsorted(self.keys, km)
         i = np.minimum(i, len(self.keys) - 1)
-        return self.keys[i] == km, i
+        hit = self.keys[i] == km
+        if self._alive is not None:                     # a junction that is gone is not found; the walk that asked still depends on it
+            if who is not None:
+                self._hits.append((np.asarray(who)[hit], i[hit]))
+            hit = hit & self._alive[i]
+        return hit, i
 
-    def find_neighbors(self, start_kmers, indices, contigs: bool = False):
+    def find_neighbors(self, start_kmers, indices, contigs: bool = False, alive=None):
+        """(see _find_neighbors)  alive: a mask over the map's junctions, in the order of the keys handed to the constructor -- the walks see
+        only the junctions it marks, as findNeighbor does on a map from which the others were erased (killJunction); afterwards `met` lists,
+        per walk, the rows of every junction of the whole map that one of its look-ups hit: the answer stands for every mask that agrees
+        with this one on them.  Default: the whole map, unchanged."""
+        if alive is None:
+            self.met = None
+            return self._find_neighbors(start_kmers, indices, contigs)
+        self._alive, self._hits = np.asarray(alive, dtype=bool)[self.order], []
+        try:
+            out = self._find_neighbors(start_kmers, indices, contigs)
+            met = [[] for _ in range(len(start_kmers))]
+            for who, rows in self._hits:
+                for w, r in zip(who.tolist(), self.order[rows].tolist()):
+                    met[w].append(r)
+            self.met = [sorted(set(m)) for m in met]
+        finally:
+            self._alive = self._hits = None
+        return out
+
+    def _find_neighbors(self, start_kmers, indices, contigs: bool = False):
         """findNeighbor(junctionMap[start], start, index) for every pair; returns a structured array (kmer, node, rindex, dist, len,
         abort) in input order.  `abort` marks the calls in which the reference trips one of its asserts: dist <= maxDist after the first
         k-mers, a valid extension at every step up to maxDist, and a valid extension at a junction met before maxDist.
@@ -100,7 +201,8 @@ class NeighborWalker:
         km = np.asarray(start_kmers, dtype=np.uint64).copy()
         idx = np.asarray(indices, dtype=np.int64)
         rc = self._revcomp(km)
-        found, where = self._is_junction(km)
+        everyone = np.arange(n)
+        found, where = self._is_junction(km, everyone)
         assert found.all(), "every start k-mer must be a junction of the map"
         maxd = self.dist[where, idx]
         out = np.zeros(n, dtype=[("kmer", np.uint64), ("node", np.int8), ("rindex", np.int8), ("dist", np.int32), ("len", np.int32), ("abort", np.int8)])
@@ -135,7 +237,7 @@ class NeighborWalker:
         back = idx == 4
         km[back], rc[back] = rc[back].copy(), km[back].copy()                    # doubleKmer.reverse()
         ln[back] = k
-        isj, _ = self._is_junction(km)
+        isj, _ = self._is_junction(km, everyone)
         m = back & isj
         finish(m, km[m], 1, 4, 1, ln[m])
         fw = ~back
@@ -143,14 +245,14 @@ class NeighborWalker:
         nk, nr = self._forward(km[fw], rc[fw], idx[fw])
         km[fw], rc[fw] = nk, nr
         ln[fw] = 1 + k
-        isj, _ = self._is_junction(rc)
+        isj, _ = self._is_junction(rc, everyone)
         m = fw & isj
         finish(m, rc[m], 1, lastnuc[m], 1, ln[m])
         m = fw & ~done & (maxd == 1)
         finish(m, rc[m], 0, lastnuc[m], 1, ln[m])
         m = fw & ~done
         dist[m] = 2
-        isj, _ = self._is_junction(km)
+        isj, _ = self._is_junction(km, everyone)
         m2 = m & isj
         finish(m2, km[m2], 1, 4, 2, ln[m2])
         text = None
@@ -167,7 +269,7 @@ class NeighborWalker:
             # ---- leaving the first loop (:343-366): a junction exactly where expected, else this is (probably) a sink
             m = (phase == 0) & (dist >= maxd)
             if m.any():
-                isj, _ = self._is_junction(km)
+                isj, _ = self._is_junction(km, everyone)
                 j = m & isj
                 finish(j, km[j], 1, retidx[j], dist[j], ln[j])
                 s = m & ~isj
@@ -202,7 +304,7 @@ class NeighborWalker:
             dist[act] += 1
             km[act], rc[act] = rc[act].copy(), km[act].copy()
             retidx[act] = lastnuc[act]
-            isj, wj = self._is_junction(km[act])
+            isj, wj = self._is_junction(km[act], act)
             a = phase[act] == 0
             stop = a & (dist[act] == maxd[act])                                  # break: handled at the top of the next round
             hit = a & ~stop & isj
@@ -221,7 +323,7 @@ class NeighborWalker:
             dist[act] += 1
             km[act], rc[act] = rc[act].copy(), km[act].copy()
             retidx[act] = 4
-            isj, wj = self._is_junction(km[act])
+            isj, wj = self._is_junction(km[act], act)
             a = phase[act] == 0
             stop = a & (dist[act] == maxd[act])
             hit = a & ~stop & isj

@@ -35,7 +35,8 @@ enum {
     FGPU_ERR_HIP = 2,       /* HIP runtime error or no device; see fgpu_last_error() */
     FGPU_ERR_STATE = 3,     /* call out of sequence (e.g. load_batch before load_begin) */
     FGPU_ERR_CAPACITY = 4,  /* batch larger than max_batch_bases, junction table full, ... */
-    FGPU_ERR_NOMEM = 5
+    FGPU_ERR_NOMEM = 5,
+    FGPU_ERR_INTERNAL = 6   /* a bound that holds by construction did not (fgpu_stage3_build's round guard) */
 };
 
 enum { FGPU_BLOO1 = 0, FGPU_BLOO2 = 1 };
@@ -822,7 +823,7 @@ uint64_t fgpu_stage3_contig_words(int32_t k, int32_t max_read_length);
  * every junction with one path out (Junction::numPathsOut() == 1; on at getOppositeIndex(result.index): 4 after a forward entry, the covered
  * extension after a backward one) until a complex junction, a sink, or the start k-mer again.  The map is static within the call -- the
  * reference kills the junctions of a chain only behind its loop (:210-216) -- so every chain is a function of (map, filter, start) alone,
- * and which answers a graph build may still use after the kills of earlier ones is the caller's business.
+ * and which answers a graph build may still use after the kills of earlier ones is not this call's business: fgpu_stage3_build below.
  * Cost: one call walks every directed segment it can need once -- the n first calls, and up to two per junction with one path out --
  * whatever n is, and keeps nothing for the next call: hand over all starts of a stage in one call.
  * Per chain: the string (print_kmer(start), its reverse complement for index 4, then result.contig.substr(k) of every segment longer than
@@ -836,7 +837,8 @@ uint64_t fgpu_stage3_contig_words(int32_t k, int32_t max_read_length);
  * len, n_seg and n_cov are 0 and nothing of the chain is stored.
  * fgpu_stage3_contigs keeps the arrays on the device and says how long they are (totals: text words, segments, coverages; all 0 for
  * n == 0); fgpu_stage3_contigs_take copies them out and frees them.  An array with fewer entries than the totals is FGPU_ERR_ARG: nothing
- * is copied, and the results are still there.  Results that were not taken are dropped by the next fgpu_stage3_contigs. */
+ * is copied, and the results are still there.  Results that were not taken are dropped by the next fgpu_stage3_contigs or
+ * fgpu_stage3_build. */
 typedef struct {
     uint64_t end_kmer;    /* BfSearchResult::kmer of the chain's last findNeighbor call */
     uint64_t text_word;   /* first word of this contig's string in the text array */
@@ -853,6 +855,52 @@ int fgpu_stage3_contigs(fgpu_ctx* ctx, const uint64_t* start_kmers_host, const i
                         fgpu_contig* out, uint64_t totals[3], uint64_t* n_probes);
 int fgpu_stage3_contigs_take(fgpu_ctx* ctx, uint64_t* text, uint64_t text_words, uint64_t* seg_kmers, uint8_t* seg_dist, uint64_t n_seg,
                              uint8_t* cov, uint64_t n_cov);
+
+/* ---- Stage 3's graph build: the order-dependent contig list ----------------------
+ * Every getContig call JunctionMap::buildContigGraph (utils/JunctionMap.cpp:11-129) makes, each on the map as it stands at that moment, in the
+ * reference's order, in one call: buildBranchingPaths' map-order loop (:34-82: every covered index 0..4 of every junction with more than one
+ * path out that has no contig yet, :50; the homopolymer rule :43-47 on the start's own copy), destroyComplexJunctions (:90-102), and
+ * buildLinearRegions' loop (:104-129: of every junction still there, the call on its covered extension and then the one on 4), with every
+ * getContig erasing the inner junctions of its chain behind itself (:210-216) and Contig::setEnds (src/Contig.cpp:123-133) taking contigs[]
+ * of the start node and, where isJunction(Contig::getSideKmer(2)) holds on the map behind the call's own kills (:54-74;
+ * src/Contig.cpp:229-241), of the far node.  Map order is the order of the keys handed to fgpu_stage3_set_junctions.  The graph itself
+ * (ContigGraph, concatenate :120) stays with the caller: the two chains of a linear region come back as two calls, forward then backward.
+ * Per call that is made: an fgpu_contig as fgpu_stage3_contigs fills it (status 0; the shared arrays in fgpu_stage3_contigs_take's
+ * layout) and an fgpu_build_call beside it.  Calls that are skipped -- the start is gone, or its (node, index) has a contig -- are not
+ * output.
+ * The build ends at the first call that is made on which the reference does not return (fgpu_build_info.status 1: it trips an assert; 3:
+ * while(!done) never ends; 0: the build ran to its end); the calls before it are output, stop_call is their number.
+ * fgpu_stage3_build keeps the results on the device and gives totals (calls made, text words, segments, coverages);
+ * fgpu_stage3_build_take copies them out and frees them.  An array with fewer entries than the totals is FGPU_ERR_ARG: nothing is copied and
+ * the results are still there.  Results that were not taken are dropped by the next fgpu_stage3_build or fgpu_stage3_contigs.
+ * The call is a fixed point over rounds; more than calls + 1 rounds is FGPU_ERR_INTERNAL. */
+#define FGPU_BUILD_BRANCHING       0
+#define FGPU_BUILD_LINEAR_FORWARD  1
+#define FGPU_BUILD_LINEAR_BACKWARD 2
+#define FGPU_BUILD_ROUNDS_KEPT     32
+typedef struct {
+    uint64_t start_kmer;
+    uint64_t far_kmer;         /* Contig::getSideKmer(2) */
+    uint32_t time;             /* the call's place among all calls the reference could make (skipped ones and destroyComplexJunctions count) */
+    uint8_t  phase;            /* FGPU_BUILD_* */
+    uint8_t  far_is_junction;  /* isJunction(far_kmer), :56 */
+    uint8_t  far_is_start;     /* ... and far_kmer == kmer, :58 */
+    uint8_t  reserved;
+} fgpu_build_call;
+typedef struct {
+    int32_t  status;
+    uint32_t rounds;           /* rounds of the fixed point, the last one (in which nothing changed) included */
+    uint64_t stop_call;        /* calls output = the number of the call the build stopped at, if it did */
+    uint64_t calls_possible;   /* time slots: calls the reference could make, and one for destroyComplexJunctions */
+    uint64_t rewalked;         /* getContig evaluations over all rounds (round 0 evaluates every call) */
+    uint64_t probes;           /* getValidJExtension evaluations in them */
+    uint64_t table_hits;       /* junction-map hits the evaluations recorded (what each answer depends on), all rounds */
+    uint64_t regrown;          /* times a round outgrew the room for them and was run again with twice as much */
+    uint64_t rewalked_by_round[FGPU_BUILD_ROUNDS_KEPT];   /* ... of the first rounds */
+} fgpu_build_info;
+int fgpu_stage3_build(fgpu_ctx* ctx, int32_t max_read_length, uint64_t totals[4], fgpu_build_info* info);
+int fgpu_stage3_build_take(fgpu_ctx* ctx, fgpu_contig* contigs, fgpu_build_call* calls, uint64_t n_calls, uint64_t* text, uint64_t text_words,
+                           uint64_t* seg_kmers, uint8_t* seg_dist, uint64_t n_seg, uint8_t* cov, uint64_t n_cov);
 
 /* ---- profiling --------------------------------------------------------------------------------- */
 typedef struct {
