@@ -78,6 +78,17 @@ class ScanStats(C.Structure):
 BUILD_ROUNDS_KEPT = 32
 
 
+class RawInfo(C.Structure):
+    """fgpu_raw_info: what the raw contigs file holds"""
+    _fields_ = [(n, C.c_uint64) for n in ("records", "bubble_records", "node_contigs", "isolated_kept", "isolated_dropped", "nodes")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+PLAN_OK, PLAN_UNSET, PLAN_INPUT, PLAN_SHORT = range(4)
+
+
 class BuildInfo(C.Structure):
     _fields_ = [("status", C.c_int32), ("rounds", C.c_uint32), ("stop_call", C.c_uint64), ("calls_possible", C.c_uint64), ("rewalked", C.c_uint64),
                 ("probes", C.c_uint64), ("table_hits", C.c_uint64), ("regrown", C.c_uint64), ("rewalked_by_round", C.c_uint64 * BUILD_ROUNDS_KEPT)]
@@ -192,6 +203,10 @@ SIGNATURES = {
     "fgpu_stage3_contigs_take": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),
     "fgpu_stage3_build": (C.c_int, [_vp, _i32, _P(_u64), _P(BuildInfo)]),
     "fgpu_stage3_build_take": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),
+    "fgpu_raw_plan": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _i32, _i32, _vp, _u64, _P(_u64), _P(RawInfo)]),
+    "fgpu_stage3_fasta": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_u64)]),
+    "fgpu_stage3_fasta_take": (C.c_int, [_vp, _vp, _u64]),
+    "fgpu_stage3_raw_contigs": (C.c_int, [_vp, _i32, _P(_u64), _P(RawInfo)]),
     "fgpu_kernel_times": (C.c_int, [_vp, _P(KernelTime), C.c_int]),
     "fgpu_kernel_times_reset": (C.c_int, [_vp]),
     "fgpu_profile_enable": (C.c_int, [_vp, C.c_int]),

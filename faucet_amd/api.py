@@ -124,6 +124,8 @@ CONTIG_DTYPE = np.dtype([("end_kmer", "<u8"), ("text_word", "<u8"), ("seg_first"
 BUILD_DTYPE = np.dtype([("start_kmer", "<u8"), ("far_kmer", "<u8"), ("time", "<u4"), ("phase", "u1"), ("far_is_junction", "u1"), ("far_is_start", "u1"),
                         ("reserved", "u1")])   # fgpu_build_call
 BUILD_BRANCHING, BUILD_LINEAR_FORWARD, BUILD_LINEAR_BACKWARD = range(3)
+FASTA_SEQ_DTYPE = np.dtype([("text_word", "<u8", (2,)), ("len", "<u4", (2,)), ("flip", "u1", (2,)), ("pieces", "u1"), ("reserved", "u1"),
+                            ("number", "<u4")])   # fgpu_fasta_seq
 
 
 class _PinnedMemory:
@@ -756,16 +758,22 @@ class Context:
             kills.append(kmers[s:s + max(ns - 1, 0)])
         return out, strings, dists, covs, kills, int(probes.value)
 
-    def stage3_build(self, max_read_length: int, raw: bool = False):
+    def stage3_build(self, max_read_length: int, raw: bool = False, take: bool = True):
         """JunctionMap::buildContigGraph's contig list (utils/JunctionMap.cpp:11-129) in one call: every getContig call of buildBranchingPaths and
         buildLinearRegions that the reference makes, each on the map of stage3_set_junctions as it stands at that moment, in the reference's
         order.  Returns (CONTIG_DTYPE array, BUILD_DTYPE array, strings, distances, coverages, kills, info): one entry per call that is made,
         the lists as stage3_contigs gives them, and info = dict(status, stop_call, calls_possible, rounds, rewalked, rewalked_by_round, probes, table_hits, regrown)
         -- status 0: the build ran to its end; 1 / 3: the call with number stop_call, which is not output, trips an assert / never returns.
-        raw=True: (CONTIG_DTYPE array, BUILD_DTYPE array, text words, segment k-mers, segment distances, coverages, info)."""
+        raw=True: (CONTIG_DTYPE array, BUILD_DTYPE array, text words, segment k-mers, segment distances, coverages, info).
+        take=False: the results stay on the device (for stage3_raw_contigs, or a later fgpu_stage3_build_take); returns info alone, with the
+        four totals under "totals"."""
         totals = (C.c_uint64 * 4)()
         bi = L.BuildInfo()
         self._c(self.lib.fgpu_stage3_build(self.h, int(max_read_length), totals, C.byref(bi)))
+        if not take:
+            return dict(status=int(bi.status), stop_call=int(bi.stop_call), calls_possible=int(bi.calls_possible), rounds=int(bi.rounds), rewalked=int(bi.rewalked),
+                        rewalked_by_round=[int(v) for v in bi.rewalked_by_round[:min(int(bi.rounds), L.BUILD_ROUNDS_KEPT)]], probes=int(bi.probes),
+                        table_hits=int(bi.table_hits), regrown=int(bi.regrown), totals=[int(v) for v in totals])
         out, calls = np.zeros(totals[0], dtype=CONTIG_DTYPE), np.zeros(totals[0], dtype=BUILD_DTYPE)
         text, kmers = np.zeros(totals[1], dtype=np.uint64), np.zeros(totals[2], dtype=np.uint64)
         dist, cov = np.zeros(totals[2], dtype=np.uint8), np.zeros(totals[3], dtype=np.uint8)
@@ -784,6 +792,32 @@ class Context:
             covs.append(cov[v:v + int(c["n_cov"])])
             kills.append(kmers[s:s + max(ns - 1, 0)])
         return out, calls, strings, dists, covs, kills, info
+
+    def stage3_fasta_take(self, nbytes: int) -> bytes:
+        out = np.zeros(max(int(nbytes), 1), dtype=np.uint8)
+        self._c(self.lib.fgpu_stage3_fasta_take(self.h, out.ctypes.data, int(nbytes)))
+        return out[:int(nbytes)].tobytes()
+
+    def stage3_fasta(self, seqs, text=None) -> bytes:
+        """FASTA_SEQ_DTYPE records joined, oriented and printed on the device (fgpu_stage3_fasta): every record ">Contig<number>\n", then the
+        one piece or the first piece without its last k bases and the second, as canon_contig leaves it, and "\n".  text: 2-bit words (A 0,
+        C 1, T 2, G 3, 32 bases per word, first base lowest) the pieces index; None: the text of the last stage3_build(take=False)."""
+        seqs = np.ascontiguousarray(seqs, dtype=FASTA_SEQ_DTYPE)
+        if text is not None:
+            text = np.ascontiguousarray(text, dtype=np.uint64)
+        nbytes = C.c_uint64(0)
+        self._c(self.lib.fgpu_stage3_fasta(self.h, seqs.ctypes.data, len(seqs), None if text is None else text.ctypes.data, 0 if text is None else len(text),
+                                           C.byref(nbytes)))
+        return self.stage3_fasta_take(nbytes.value)
+
+    def stage3_raw_contigs(self, read_length: int):
+        """the reference's <prefix>.raw_contigs.fasta (ContigGraph::printContigs on the graph of buildContigGraph, src/Faucet.cpp:314) of the build
+        stage3_build(max_read_length, take=False) left on the device: (the file's bytes, info = dict(records, bubble_records, node_contigs,
+        isolated_kept, isolated_dropped, nodes)).  The build stays where it is."""
+        nbytes = C.c_uint64(0)
+        ri = L.RawInfo()
+        self._c(self.lib.fgpu_stage3_raw_contigs(self.h, int(read_length), C.byref(nbytes), C.byref(ri)))
+        return self.stage3_fasta_take(nbytes.value), ri.as_dict()
 
     def kernel_times(self) -> dict:
         arr = (L.KernelTime * 64)()

@@ -462,6 +462,10 @@ struct fgpu_ctx {
     uint64_t s3c_totals[3] = {0, 0, 0};   // their entries: text words, segments, coverages
     void* s3b_out = nullptr;              // fgpu_stage3_build's results until fgpu_stage3_build_take: contigs, calls, then the same four arrays
     uint64_t s3b_totals[4] = {0, 0, 0, 0};   // calls, text words, segments, coverages
+    bool s3b_have = false;                // a build has finished and has not been taken (s3b_out is null for an empty map's)
+    int32_t s3b_status = 0;               // ... its fgpu_build_info.status
+    void* s3f_out = nullptr;              // fgpu_stage3_fasta's bytes until fgpu_stage3_fasta_take (stage3_emit.hip)
+    uint64_t s3f_bytes = 0;
     uint64_t s3_mask = 0, s3_count = 0;
     bool s3_ready = false;
     DevBuf dl_entries, dl_stamps, dl_stamps_sorted, dl_idx, dl_idx_sorted, dl_keys, dl_recs, dl_tmp;   // junction download scratch
@@ -532,6 +536,8 @@ static inline hipError_t fgpu_sync_event_at(fgpu_ctx* ctx, hipEvent_t ev, const 
 #define fgpu_sync_event(ctx, ev) fgpu_sync_event_at(ctx, ev, __FILE__, __LINE__)
 
 int fgpu_ensure(fgpu_ctx* ctx, DevBuf* b, uint64_t bytes);
+// the untaken results of fgpu_stage3_build where they lie on the device (stage3.hip; any pointer may be null): 0 if there is no such build
+int fgpu_s3b_view(fgpu_ctx* ctx, const fgpu_contig** contigs, const fgpu_build_call** calls, const uint64_t** text);
 int fgpu_ensure_b(fgpu_ctx* ctx, DevBuf* b, uint64_t bytes);   // a buffer whose size follows the batch: grown for the largest batch announced (ensure_scale)
 int fgpu_bg_join(fgpu_ctx* ctx);
 int fgpu_prof_begin(fgpu_ctx* ctx, const char* name);

@@ -1014,6 +1014,7 @@ namespace {
 void s3b_drop(fgpu_ctx* ctx) {                             // results nobody took
     if (ctx->s3b_out) { (void)hipFree(ctx->s3b_out); ctx->s3b_out = nullptr; }
     for (int i = 0; i < 4; i++) ctx->s3b_totals[i] = 0;
+    ctx->s3b_have = false;
 }
 struct S3bLayout { uint64_t contigs, calls, text, kmers, dist, cov, bytes; };
 S3bLayout s3b_layout(const uint64_t tot[4]) {
@@ -1025,6 +1026,16 @@ S3bLayout s3b_layout(const uint64_t tot[4]) {
     return l;
 }
 }  // namespace
+
+int fgpu_s3b_view(fgpu_ctx* ctx, const fgpu_contig** contigs, const fgpu_build_call** calls, const uint64_t** text) {
+    if (!ctx->s3b_have) return 0;
+    const S3bLayout lay = s3b_layout(ctx->s3b_totals);
+    const char* res = (const char*)ctx->s3b_out;          // (null only where every total is 0)
+    if (contigs) *contigs = (const fgpu_contig*)(res + lay.contigs);
+    if (calls) *calls = (const fgpu_build_call*)(res + lay.calls);
+    if (text) *text = (const uint64_t*)(res + lay.text);
+    return 1;
+}
 
 extern "C" int fgpu_stage3_build(fgpu_ctx* ctx, int32_t max_read_length, uint64_t totals[4], fgpu_build_info* info) {
     if (!ctx || !totals || max_read_length < 1) return FGPU_ERR_ARG;
@@ -1043,7 +1054,11 @@ extern "C" int fgpu_stage3_build(fgpu_ctx* ctx, int32_t max_read_length, uint64_
     fgpu_build_info inf;
     memset(&inf, 0, sizeof(inf));
     if (info) *info = inf;
-    if (!nj) return FGPU_OK;
+    if (!nj) {
+        ctx->s3b_have = true;
+        ctx->s3b_status = 0;
+        return FGPU_OK;
+    }
     const int k = ctx->prm.k;
     const uint64_t stride = fgpu_stage3_contig_words(k, max_read_length);
     const uint64_t* d_keys = (const uint64_t*)((const char*)ctx->s3_in.p + 64);
@@ -1182,6 +1197,8 @@ extern "C" int fgpu_stage3_build(fgpu_ctx* ctx, int32_t max_read_length, uint64_
     inf.stop_call = tot[0];
     inf.calls_possible = n_calls;
     for (int i = 0; i < 4; i++) totals[i] = ctx->s3b_totals[i] = tot[i];
+    ctx->s3b_have = true;
+    ctx->s3b_status = inf.status;
     if (info) *info = inf;
     return FGPU_OK;
 }
@@ -1195,7 +1212,7 @@ extern "C" int fgpu_stage3_build_take(fgpu_ctx* ctx, fgpu_contig* contigs, fgpu_
         ctx->err = "fgpu_stage3_build_take: an array is smaller than the totals fgpu_stage3_build gave";
         return FGPU_ERR_ARG;
     }
-    if (!ctx->s3b_out) return FGPU_OK;
+    if (!ctx->s3b_out) { ctx->s3b_have = false; return FGPU_OK; }
     FGPU_HIP(hipSetDevice(ctx->prm.device));
     const S3bLayout lay = s3b_layout(tot);
     const char* res = (const char*)ctx->s3b_out;

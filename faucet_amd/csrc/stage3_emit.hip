@@ -1,0 +1,349 @@
+// stage3_emit.hip — Stage 3's first product on the device: the contigs of a build, joined, oriented and printed as FASTA where they lie
+// (fgpu_stage3_fasta, fgpu_stage3_fasta_take, fgpu_stage3_raw_contigs; include/faucet_gpu.h).
+//
+// What the reference does per record, ContigGraph::printContigs (src/ContigGraph.cpp:1532-1645):
+//   ContigJuncList::concatenate's sequence          utils/ContigJuncList.cpp:121   first.substr(0, len - k) + second
+//   ContigJuncList::reverse / revcomp_string        utils/ContigJuncList.cpp:98-103, utils/Kmer.cpp:353-359
+//   canon_contig                                    utils/Kmer.cpp:345-351         a comparison of strings of LETTERS: A < C < G < T
+// Which records, and in which order, is the host's business (raw_plan.cpp).  Four kernels, integer and bitwise only:
+//   k_emit_sizes   per record: words of its joined 2-bit string, bytes of its text (">Contig<n>\n" + bases + "\n"); rocPRIM scans them
+//   k_emit_join    one lane per WORD of the joined strings: 32 bases cut out of one or two pieces at any base offset by funnel shifts, a
+//                  reverse complement 32 bases at a time (bit reversal, pair swap, XOR 1010...: the complement of a code is code ^ 2)
+//   k_emit_canon   one wave per record: the first position where the string and its reverse complement differ, 32 x 64 bases per step, found
+//                  with a ballot; the ranks of the two letters there decide.  A palindrome never differs and stays.
+//   k_emit_ascii   one block per 4 KiB of OUTPUT, one lane per 16 bytes, whatever the records' lengths: the block looks up its first
+//                  record once, keeps the byte offsets of the records its tile can touch in LDS, a lane inside a sequence expands 16 codes
+//                  and stores 16 bytes at once, a lane on a header or a record's edge goes byte by byte.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <rocprim/rocprim.hpp>
+#include <string>
+#include <vector>
+
+#include "fgpu_ctx.h"
+
+namespace {
+
+static_assert(sizeof(fgpu_fasta_seq) == 32 && sizeof(fgpu_raw_info) == 48, "the records as api.py and _lib.py lay them out");
+
+constexpr uint32_t EMIT_TILE = 4096;             // bytes of output per block of k_emit_ascii: 256 lanes x 16 bytes
+constexpr uint32_t EMIT_TILE_RECORDS = 512;      // offsets kept per tile: a record has at least 11 bytes (">Contig1\n", a base, "\n"), so a tile touches at most 374
+constexpr uint64_t EMIT_ODD = 0x5555555555555555ULL, EMIT_COMPLEMENT = 0xAAAAAAAAAAAAAAAAULL;
+
+__device__ __forceinline__ uint32_t emit_joined_len(const fgpu_fasta_seq& s, int k) { return s.pieces == 2 ? s.len[0] - (uint32_t)k + s.len[1] : s.len[0]; }
+__device__ __forceinline__ uint32_t emit_digits(uint32_t v) {
+    uint32_t d = 1;
+    for (uint32_t p = 10; d < 10 && v >= p; p *= 10) d++;      // (p overflows only behind d == 10, where the loop has ended)
+    return d;
+}
+
+// bases a .. a + 31 of a 2-bit string of `len` bases, base a in the lowest bits; -31 <= a < len.  Fields outside 0 .. len - 1 hold no
+// information (the callers mask them); no word behind the string's last one is read.
+__device__ __forceinline__ uint64_t emit_window(const uint64_t* __restrict__ w, uint32_t len, int64_t a) {
+    const uint32_t words = (len + 31) >> 5;
+    if (a < 0) return w[0] << (2 * (uint32_t)(-a));
+    const uint32_t at = (uint32_t)(a >> 5), sh = 2 * ((uint32_t)a & 31);
+    const uint64_t lo = at < words ? w[at] : 0;
+    if (!sh) return lo;
+    const uint64_t hi = at + 1 < words ? w[at + 1] : 0;
+    return (lo >> sh) | (hi << (64 - sh));
+}
+// the reverse complement of 32 bases: the fields in reverse order, each code ^ 2
+__device__ __forceinline__ uint64_t emit_revcomp(uint64_t x) {
+    const uint64_t r = __brevll(x);
+    return (((r >> 1) & EMIT_ODD) | ((r & EMIT_ODD) << 1)) ^ EMIT_COMPLEMENT;
+}
+// bases pos .. pos + 31 of the string as it is read (flip: reverse-complemented), pos < len
+__device__ __forceinline__ uint64_t emit_oriented(const uint64_t* __restrict__ w, uint32_t len, bool flip, uint32_t pos) {
+    return flip ? emit_revcomp(emit_window(w, len, (int64_t)len - 32 - (int64_t)pos)) : emit_window(w, len, (int64_t)pos);
+}
+__device__ __forceinline__ uint64_t emit_low_fields(uint32_t n) { return n >= 32 ? ~0ULL : ((1ULL << (2 * n)) - 1); }
+
+// the last entry e of off[0 .. n] (ascending, off[0] = 0) with off[e] <= x, for x < off[n]
+__device__ __forceinline__ uint64_t emit_find(const uint64_t* __restrict__ off, uint64_t n, uint64_t x) {
+    uint64_t lo = 0, hi = n;                       // off[lo] <= x < off[hi]
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (off[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256) k_emit_sizes(const fgpu_fasta_seq* __restrict__ seqs, uint64_t n, int k, uint64_t* __restrict__ words, uint64_t* __restrict__ bytes) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { words[n] = 0; bytes[n] = 0; return; }      // (the scans' last entry: the totals)
+    const fgpu_fasta_seq s = seqs[i];
+    const uint32_t len = emit_joined_len(s, k);
+    words[i] = (len + 31) >> 5;
+    bytes[i] = 8ULL + emit_digits(s.number) + len + 1;
+}
+
+__global__ void __launch_bounds__(256) k_emit_join(const fgpu_fasta_seq* __restrict__ seqs, uint64_t n, int k, const uint64_t* __restrict__ text,
+                                                   const uint64_t* __restrict__ word0, uint64_t n_words, uint64_t* __restrict__ joined) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n_words) return;
+    const uint64_t i = emit_find(word0, n, g);
+    const fgpu_fasta_seq s = seqs[i];
+    const uint32_t len = emit_joined_len(s, k), pos = (uint32_t)(g - word0[i]) * 32;
+    const int last = s.pieces == 2 ? 1 : 0;
+    const uint32_t cut = s.pieces == 2 ? s.len[0] - (uint32_t)k : 0;       // bases the first piece gives
+    const uint64_t* tail = text + s.text_word[last];
+    uint64_t w;
+    if (pos >= cut) {
+        w = emit_oriented(tail, s.len[last], s.flip[last] != 0, pos - cut);
+    } else {
+        w = emit_oriented(text + s.text_word[0], s.len[0], s.flip[0] != 0, pos);
+        if (pos + 32 > cut) {                                              // the seam falls into this word
+            const uint32_t n1 = cut - pos;
+            w = (w & emit_low_fields(n1)) | (emit_oriented(tail, s.len[1], s.flip[1] != 0, 0) << (2 * n1));
+        }
+    }
+    joined[g] = w & emit_low_fields(len - pos);
+}
+
+__global__ void __launch_bounds__(256) k_emit_canon(const fgpu_fasta_seq* __restrict__ seqs, uint64_t n, int k, const uint64_t* __restrict__ word0,
+                                                    const uint64_t* __restrict__ joined, uint8_t* __restrict__ flipped) {
+    const uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // one wave per record (uniform within the wave)
+    if (i >= n) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t len = emit_joined_len(seqs[i], k), words = (len + 31) >> 5;
+    const uint64_t* w = joined + word0[i];
+    for (uint32_t j0 = 0; j0 < words; j0 += 64) {
+        const uint32_t j = j0 + lane;
+        uint64_t own = 0, other = 0;
+        if (j < words) {
+            const uint64_t valid = emit_low_fields(len - 32 * j);
+            own = w[j] & valid;
+            other = emit_oriented(w, len, true, 32 * j) & valid;
+        }
+        const uint64_t differ = own ^ other;
+        const unsigned long long who = __ballot(differ != 0);
+        if (who) {                                                         // (wave-uniform: every lane leaves together)
+            if (lane == (uint32_t)(__ffsll((long long)who) - 1)) {
+                const uint32_t f = (uint32_t)(__ffsll((long long)differ) - 1) >> 1;
+                const uint32_t a = (uint32_t)(own >> (2 * f)) & 3, b = (uint32_t)(other >> (2 * f)) & 3;
+                flipped[i] = ((a ^ (a >> 1)) > (b ^ (b >> 1))) ? 1 : 0;    // codes A 0, C 1, T 2, G 3 -> ranks of the letters 0, 1, 3, 2
+            }
+            return;
+        }
+    }
+    if (lane == 0) flipped[i] = 0;                                         // its own reverse complement
+}
+
+struct EmitRecord {                              // what k_emit_ascii knows of the record a byte lies in
+    uint64_t first;                              // its first byte
+    const uint64_t* w;
+    uint32_t len, number, digits;
+    bool flip;
+};
+__device__ __forceinline__ EmitRecord emit_record(const fgpu_fasta_seq* __restrict__ seqs, uint64_t i, int k, const uint64_t* __restrict__ word0,
+                                                  const uint64_t* __restrict__ joined, const uint8_t* __restrict__ flipped, uint64_t first) {
+    const fgpu_fasta_seq s = seqs[i];
+    EmitRecord r;
+    r.first = first;
+    r.w = joined + word0[i];
+    r.len = emit_joined_len(s, k);
+    r.number = s.number;
+    r.digits = emit_digits(s.number);
+    r.flip = flipped[i] != 0;
+    return r;
+}
+__device__ __forceinline__ uint32_t emit_letter(uint32_t code) { return (0x47544341u >> (8 * code)) & 0xFFu; }       // "ACTG"
+__device__ __forceinline__ uint32_t emit_byte(const EmitRecord& r, uint32_t at) {      // byte `at` of the record's text
+    if (at < 7) return (uint32_t)">Contig"[at];
+    if (at < 7 + r.digits) {
+        uint32_t v = r.number;
+        for (uint32_t d = 7 + r.digits - 1 - at; d; d--) v /= 10;
+        return '0' + v % 10;
+    }
+    const uint32_t base = at - (8 + r.digits);
+    if (at == 7 + r.digits || base >= r.len) return '\n';
+    return emit_letter((uint32_t)emit_oriented(r.w, r.len, r.flip, base) & 3);
+}
+
+__global__ void __launch_bounds__(256) k_emit_ascii(const fgpu_fasta_seq* __restrict__ seqs, uint64_t n, int k, const uint64_t* __restrict__ word0,
+                                                    const uint64_t* __restrict__ byte0, uint64_t n_bytes, const uint64_t* __restrict__ joined,
+                                                    const uint8_t* __restrict__ flipped, uint4* __restrict__ out) {
+    __shared__ uint64_t first_of[EMIT_TILE_RECORDS];
+    __shared__ uint64_t tile_first;
+    const uint64_t tile = (uint64_t)blockIdx.x * EMIT_TILE;               // (< n_bytes by the grid)
+    if (threadIdx.x == 0) tile_first = emit_find(byte0, n, tile);
+    __syncthreads();
+    const uint64_t i0 = tile_first;
+    for (uint32_t t = threadIdx.x; t < EMIT_TILE_RECORDS; t += 256) first_of[t] = i0 + t <= n ? byte0[i0 + t] : ~0ULL;
+    __syncthreads();
+    const uint64_t at = tile + 16ULL * threadIdx.x;
+    if (at >= n_bytes) return;
+    uint32_t lo = 0, hi = EMIT_TILE_RECORDS;                               // first_of[lo] <= at < first_of[hi] (hi = the array's end: no record starts there)
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first_of[mid] <= at) lo = mid; else hi = mid;
+    }
+    EmitRecord r = emit_record(seqs, i0 + lo, k, word0, joined, flipped, first_of[lo]);
+    uint32_t v[4] = {0, 0, 0, 0};
+    const uint64_t in = at - r.first, bases = 8 + r.digits;
+    if (in >= bases && in + 16 <= bases + r.len) {                         // sixteen bases of one sequence
+        const uint32_t c = (uint32_t)emit_oriented(r.w, r.len, r.flip, (uint32_t)(in - bases));
+#pragma unroll
+        for (int b = 0; b < 16; b++) v[b >> 2] |= emit_letter((c >> (2 * b)) & 3) << (8 * (b & 3));
+    } else {
+        for (uint32_t b = 0; b < 16 && at + b < n_bytes; b++) {            // (behind the last byte: zeros, in the buffer's own padding)
+            while (lo + 1 < EMIT_TILE_RECORDS && first_of[lo + 1] <= at + b) {
+                lo++;
+                r = emit_record(seqs, i0 + lo, k, word0, joined, flipped, first_of[lo]);
+            }
+            v[b >> 2] |= emit_byte(r, (uint32_t)(at + b - r.first)) << (8 * (b & 3));
+        }
+    }
+    out[at >> 4] = make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+struct EmitScratch {                             // device memory of one call, gone when it returns
+    void* p = nullptr;
+    ~EmitScratch() { if (p) (void)hipFree(p); }
+};
+inline uint64_t emit_take(uint64_t& at, uint64_t bytes) {
+    const uint64_t here = at;
+    at += (bytes + 15) & ~15ULL;
+    return here;
+}
+int emit_alloc(fgpu_ctx* ctx, void** p, uint64_t bytes, const char* what) {
+    const hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+    if (e != hipSuccess) {
+        *p = nullptr;
+        ctx->err = std::string("fgpu_stage3_fasta: hipMalloc of ") + std::to_string(bytes) + " bytes (" + what + ") failed: " + hipGetErrorString(e);
+        return FGPU_ERR_NOMEM;
+    }
+    return FGPU_OK;
+}
+void emit_drop(fgpu_ctx* ctx) {                  // a file nobody took
+    if (ctx->s3f_out) { (void)hipFree(ctx->s3f_out); ctx->s3f_out = nullptr; }
+    ctx->s3f_bytes = 0;
+}
+
+}  // namespace
+
+extern "C" int fgpu_stage3_fasta(fgpu_ctx* ctx, const fgpu_fasta_seq* seqs_host, uint64_t n, const uint64_t* text_host, uint64_t text_words, uint64_t* bytes) {
+    if (!ctx || !bytes || (n && !seqs_host) || (text_host == nullptr && text_words != 0)) return FGPU_ERR_ARG;
+    if (ctx->phase != 0) { ctx->err = "fgpu_stage3_fasta while a pass is open"; return FGPU_ERR_STATE; }
+    *bytes = 0;
+    const int k = ctx->prm.k;
+    const uint64_t* d_text = nullptr;
+    if (!text_host && n) {
+        if (!fgpu_s3b_view(ctx, nullptr, nullptr, &d_text)) { ctx->err = "fgpu_stage3_fasta without a text: no fgpu_stage3_build whose results are still on the device"; return FGPU_ERR_STATE; }
+        text_words = ctx->s3b_totals[1];
+    }
+    for (uint64_t i = 0; i < n; i++) {           // every word the kernels will read lies in the text
+        const fgpu_fasta_seq& s = seqs_host[i];
+        bool ok = s.pieces == 1 || s.pieces == 2;
+        for (int p = 0; ok && p < s.pieces; p++)
+            ok = s.len[p] >= 1 && s.len[p] < (1u << 30) && s.text_word[p] <= text_words && ((uint64_t)s.len[p] + 31) / 32 <= text_words - s.text_word[p];
+        if (ok && s.pieces == 2) ok = s.len[0] >= (uint32_t)k;
+        if (!ok) {
+            ctx->err = "fgpu_stage3_fasta: record " + std::to_string(i) + " has a piece outside the text, of no bases or of 2^30 and more, a first piece shorter than k, or pieces other than 1 or 2";
+            return FGPU_ERR_ARG;
+        }
+    }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    emit_drop(ctx);
+    if (!n) return FGPU_OK;
+    int rc;
+    size_t scan_bytes = 0;
+    FGPU_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), ctx->stream));
+    EmitScratch work;
+    uint64_t at = 0;
+    const uint64_t o_seqs = emit_take(at, n * sizeof(fgpu_fasta_seq)), o_cnt = emit_take(at, 2 * (n + 1) * 8), o_off = emit_take(at, 2 * (n + 1) * 8),
+                   o_scan = emit_take(at, scan_bytes), o_flip = emit_take(at, n), o_text = emit_take(at, text_host ? text_words * 8 : 0);
+    if ((rc = emit_alloc(ctx, &work.p, at, "the records"))) return rc;
+    char* wb = (char*)work.p;
+    fgpu_fasta_seq* d_seqs = (fgpu_fasta_seq*)(wb + o_seqs);
+    uint64_t *d_words = (uint64_t*)(wb + o_cnt), *d_bytes = d_words + (n + 1), *d_word0 = (uint64_t*)(wb + o_off), *d_byte0 = d_word0 + (n + 1);
+    uint8_t* d_flip = (uint8_t*)(wb + o_flip);
+    FGPU_HIP(hipMemcpyAsync(d_seqs, seqs_host, n * sizeof(fgpu_fasta_seq), hipMemcpyHostToDevice, ctx->stream));
+    if (text_host) {
+        FGPU_HIP(hipMemcpyAsync(wb + o_text, text_host, text_words * 8, hipMemcpyHostToDevice, ctx->stream));
+        d_text = (const uint64_t*)(wb + o_text);
+    }
+    FGPU_LAUNCH("s3f_sizes", k_emit_sizes, fgpu_blocks(n + 1, 256), 256, (const fgpu_fasta_seq*)d_seqs, n, k, d_words, d_bytes);
+    FGPU_HIP(rocprim::exclusive_scan(wb + o_scan, scan_bytes, d_words, d_word0, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), ctx->stream));
+    FGPU_HIP(rocprim::exclusive_scan(wb + o_scan, scan_bytes, d_bytes, d_byte0, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), ctx->stream));
+    uint64_t n_words = 0, n_bytes = 0;
+    FGPU_HIP(hipMemcpyAsync(&n_words, d_word0 + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    FGPU_HIP(hipMemcpyAsync(&n_bytes, d_byte0 + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    EmitScratch joined;
+    if ((rc = emit_alloc(ctx, &joined.p, n_words * 8, "the joined strings"))) return rc;
+    void* out = nullptr;
+    if ((rc = emit_alloc(ctx, &out, (n_bytes + 15) & ~15ULL, "the file"))) return rc;      // (whole 16-byte stores)
+    ctx->s3f_out = out;                          // (freed with the context from here on)
+    FGPU_LAUNCH("s3f_join", k_emit_join, fgpu_blocks(n_words, 256), 256, (const fgpu_fasta_seq*)d_seqs, n, k, d_text, (const uint64_t*)d_word0, n_words, (uint64_t*)joined.p);
+    FGPU_LAUNCH("s3f_canon", k_emit_canon, fgpu_blocks(n, 4), 256, (const fgpu_fasta_seq*)d_seqs, n, k, (const uint64_t*)d_word0, (const uint64_t*)joined.p, d_flip);
+    FGPU_LAUNCH("s3f_ascii", k_emit_ascii, fgpu_blocks(n_bytes, EMIT_TILE), 256, (const fgpu_fasta_seq*)d_seqs, n, k, (const uint64_t*)d_word0, (const uint64_t*)d_byte0, n_bytes,
+                (const uint64_t*)joined.p, (const uint8_t*)d_flip, (uint4*)out);
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    *bytes = ctx->s3f_bytes = n_bytes;
+    return FGPU_OK;
+}
+
+extern "C" int fgpu_stage3_fasta_take(fgpu_ctx* ctx, char* out, uint64_t bytes) {
+    if (!ctx) return FGPU_ERR_ARG;
+    if (bytes < ctx->s3f_bytes || (ctx->s3f_bytes && !out)) {
+        ctx->err = "fgpu_stage3_fasta_take: the buffer is smaller than the bytes fgpu_stage3_fasta gave";
+        return FGPU_ERR_ARG;
+    }
+    if (!ctx->s3f_out) return FGPU_OK;
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    if (ctx->s3f_bytes) FGPU_HIP(hipMemcpyAsync(out, ctx->s3f_out, ctx->s3f_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    emit_drop(ctx);
+    return FGPU_OK;
+}
+
+extern "C" int fgpu_stage3_raw_contigs(fgpu_ctx* ctx, int32_t read_length, uint64_t* bytes, fgpu_raw_info* info) {
+    if (!ctx || !bytes) return FGPU_ERR_ARG;
+    *bytes = 0;
+    if (info) memset(info, 0, sizeof(*info));
+    const fgpu_contig* d_contigs = nullptr;
+    const fgpu_build_call* d_calls = nullptr;
+    if (!fgpu_s3b_view(ctx, &d_contigs, &d_calls, nullptr)) {
+        ctx->err = "fgpu_stage3_raw_contigs: no fgpu_stage3_build whose results are still on the device (not run, or taken)";
+        return FGPU_ERR_ARG;
+    }
+    if (ctx->s3b_status != 0) {
+        ctx->err = "fgpu_stage3_raw_contigs: the build stopped with status " + std::to_string(ctx->s3b_status) + " at call " + std::to_string(ctx->s3b_totals[0]) +
+                   ": the reference does not return from JunctionMap::buildContigGraph on this map";
+        return FGPU_ERR_ARG;
+    }
+    if (ctx->phase != 0) { ctx->err = "fgpu_stage3_raw_contigs while a pass is open"; return FGPU_ERR_STATE; }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    const uint64_t n_calls = ctx->s3b_totals[0], nj = ctx->s3_count;
+    std::vector<fgpu_contig> contigs(n_calls);
+    std::vector<fgpu_build_call> calls(n_calls);
+    std::vector<uint64_t> keys(nj);
+    std::vector<fgpu_junction> recs(nj);
+    if (n_calls) {
+        FGPU_HIP(hipMemcpyAsync(contigs.data(), d_contigs, n_calls * sizeof(fgpu_contig), hipMemcpyDeviceToHost, ctx->stream));
+        FGPU_HIP(hipMemcpyAsync(calls.data(), d_calls, n_calls * sizeof(fgpu_build_call), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (nj) {                                    // the map as fgpu_stage3_set_junctions was handed it, in its order
+        const uint64_t* d_keys = (const uint64_t*)((const char*)ctx->s3_in.p + 64);
+        FGPU_HIP(hipMemcpyAsync(keys.data(), d_keys, nj * 8, hipMemcpyDeviceToHost, ctx->stream));
+        FGPU_HIP(hipMemcpyAsync(recs.data(), d_keys + nj, nj * sizeof(fgpu_junction), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    std::vector<fgpu_fasta_seq> seqs(n_calls);
+    uint64_t n = 0;
+    fgpu_raw_info inf;
+    memset(&inf, 0, sizeof(inf));
+    const int st = fgpu_raw_plan(keys.data(), recs.data(), nj, contigs.data(), calls.data(), n_calls, ctx->prm.k, read_length, seqs.data(), n_calls, &n, &inf);
+    if (st != FGPU_PLAN_OK) {
+        ctx->err = st == FGPU_PLAN_UNSET ? "fgpu_stage3_raw_contigs: on this graph ContigGraph::printContigs reads a contig pointer that was never set (undefined in the reference)"
+                                         : "fgpu_stage3_raw_contigs: the build's records are not a finished build of the map (fgpu_raw_plan status " + std::to_string(st) + ")";
+        return FGPU_ERR_STATE;
+    }
+    if (int rc = fgpu_stage3_fasta(ctx, seqs.data(), n, nullptr, 0, bytes)) return rc;
+    if (info) *info = inf;
+    return FGPU_OK;
+}

@@ -63,6 +63,11 @@
 #pragma weak fgpu_estimate_keep_reads
 #pragma weak fgpu_estimate_take_kept_reads
 #pragma weak fgpu_load_batch_packed_reads
+// ... and the four of --raw_contigs (Stage 3's graph build and the FASTA of its contigs): without them the flag is refused before anything is read
+#pragma weak fgpu_stage3_set_junctions
+#pragma weak fgpu_stage3_build
+#pragma weak fgpu_stage3_raw_contigs
+#pragma weak fgpu_stage3_fasta_take
 
 using faucet_host::ReadSource;
 using faucet_host::TextSource;
@@ -92,6 +97,7 @@ struct Options {   // globals of src/Faucet.h:14-53
     bool estimate = false;            // not a reference flag: --estimate, -estimated_kmers / -singletons may be left out and are then estimated (pass 0)
     int estimate_bits = 0;            // not a reference flag: -estimate_bits r, 2^r cells per level of the sketch (0: the library's default, 30)
     bool scan_kept = false;           // not a reference flag: --scan_kept, pass 2 scans the batches pass 1 kept; -read_scan_file may be left out
+    bool raw_contigs = false;         // not a reference flag: --raw_contigs, <prefix>.raw_contigs.fasta (the file src/Faucet.cpp:314 would write) behind the scan outputs
 };
 
 void argument_error() {   // src/Faucet.cpp:50-54
@@ -101,7 +107,8 @@ void argument_error() {   // src/Faucet.cpp:50-54
     fprintf(stderr, "\nOptional arguments: --fastq --mercy --high_cov -max_spacer_dist <dist> -fp rate <rate> -j <int> --two_hash "
                     "-bloom_file <filename> -junctions_file <filename> --paired_ends --no_cleaning\n");
     fprintf(stderr, "Of this build: -gpus <n> -transport copy|rccl -batch_reads <n> -chunk_mb <n> --estimate -estimate_bits <r> "
-                    "--scan_kept (pass 2 scans the reads pass 1 kept on the device: -read_scan_file may be left out)\n");
+                    "--scan_kept (pass 2 scans the reads pass 1 kept on the device: -read_scan_file may be left out) "
+                    "--raw_contigs (writes <prefix>.raw_contigs.fasta, the contigs of the graph build before any cleaning)\n");
 }
 
 // src/Faucet.cpp:57-182 (with the missing `return 0` supplied and a bounds check on flag values)
@@ -137,6 +144,7 @@ int handle_arguments(int argc, char** argv, Options& o) {
         else if (a == "-transport") { if (!val(v)) goto bad; o.transport = v; if (o.transport != "copy" && o.transport != "rccl") { fprintf(stderr, "-transport must be copy or rccl\n"); return 1; } }
         else if (a == "--estimate") o.estimate = true;
         else if (a == "--scan_kept") o.scan_kept = true;
+        else if (a == "--raw_contigs") o.raw_contigs = true;
         else if (a == "-estimate_bits") { if (!val(v)) goto bad; o.estimate_bits = atoi(v); if (o.estimate_bits < FGPU_EST_MIN_BITS || o.estimate_bits > FGPU_EST_MAX_BITS) { fprintf(stderr, "-estimate_bits must be in %d..%d\n", FGPU_EST_MIN_BITS, FGPU_EST_MAX_BITS); return 1; } }
         else if (a == "--help" || a == "-h") { argument_error(); return 1; }
         else { fprintf(stderr, "Cannot parse tag %s\n", argv[i]); argument_error(); return 1; }
@@ -399,6 +407,38 @@ struct PhaseClock {
     }
 };
 
+// --raw_contigs: ContigGraph::printContigs on the graph JunctionMap::buildContigGraph returns (src/Faucet.cpp:305-314, the printContigs line
+// commented out there), on the device that holds the map and bloo2.  The reference builds the graph on the map the scan left, iterated in
+// its container's order -- the order `.junctions` is written in; set_junctions gets the records in that order.  0, or the exit code.
+int write_raw_contigs(const Options& o, fgpu_ctx* ctx, const uint64_t* keys, const fgpu_junction* recs, const std::vector<uint32_t>& order, PhaseClock& clk) {
+    std::vector<uint64_t> map_keys(order.size() ? order.size() : 1);
+    std::vector<fgpu_junction> map_recs(order.size() ? order.size() : 1);
+    for (size_t i = 0; i < order.size(); i++) { map_keys[i] = keys[order[i]]; map_recs[i] = recs[order[i]]; }
+    CHECK(fgpu_stage3_set_junctions(ctx, map_keys.data(), map_recs.data(), order.size()));
+    uint64_t totals[4] = {0, 0, 0, 0};
+    fgpu_build_info bi;
+    CHECK(fgpu_stage3_build(ctx, o.read_length, totals, &bi));
+    clk.mark("  raw contigs: graph build");
+    if (bi.status != 0) {      // the reference itself does not return from buildContigGraph on this map: no file
+        fprintf(stderr, "--raw_contigs: getContig call %llu of JunctionMap::buildContigGraph %s: the reference does not get as far as printing on this map, no %s.raw_contigs.fasta is written\n",
+                (unsigned long long)bi.stop_call, bi.status == 1 ? "trips an assert of the reference" : "never returns in the reference", o.file_prefix.c_str());
+        return 2;
+    }
+    uint64_t bytes = 0;
+    fgpu_raw_info ri;
+    CHECK(fgpu_stage3_raw_contigs(ctx, o.read_length, &bytes, &ri));
+    std::vector<char> text(bytes ? bytes : 1);
+    CHECK(fgpu_stage3_fasta_take(ctx, text.data(), bytes));
+    const std::string path = o.file_prefix + ".raw_contigs.fasta";
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f || fwrite(text.data(), 1, bytes, f) != bytes || fclose(f) != 0) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 2; }
+    printf("Raw contigs: %llu records (%llu bubble, %llu off nodes, %llu isolated; %llu isolated below the read length left out) from %llu nodes, %llu bytes\n",
+           (unsigned long long)ri.records, (unsigned long long)ri.bubble_records, (unsigned long long)ri.node_contigs, (unsigned long long)ri.isolated_kept,
+           (unsigned long long)ri.isolated_dropped, (unsigned long long)ri.nodes, (unsigned long long)bytes);
+    clk.mark("  raw contigs: plan, emission, file");
+    return 0;
+}
+
 // What both kinds of run -- one device, or read shards over several -- do once the scan has ended: the lines ReadScanner::scanReads and
 // printScanSummary print (src/ReadScanner.cpp:19-27,352-358), the junction map (held by `ctx`: the only context, or the last shard's) into
 // <prefix>.junctions in the reference's dump order, and the pair filter files (src/Faucet.cpp:296-300).  0, or the exit code of a failure.
@@ -484,6 +524,7 @@ int write_scan_outputs(const Options& o, fgpu_ctx* ctx, const fgpu_scan_stats& s
     printf("Weight of short pair filter: %f\n", short_pf.weight());
     if (o.paired_ends) printf("Weight of long pair filter: %f\n", long_pf.weight());
     printf("Number of junctions: %llu\n", (unsigned long long)order.size());
+    if (o.raw_contigs) return write_raw_contigs(o, ctx, keys.data(), recs.data(), order, clk);
     return 0;
 }
 
@@ -1146,6 +1187,14 @@ int main(int argc, char** argv) {
                             "(fgpu_scan_kept_state, fgpu_scan_batch_kept, fgpu_estimate_keep_reads, fgpu_estimate_take_kept_reads, fgpu_load_batch_packed_reads)\n");
             return 2;
         }
+    }
+    if (o.raw_contigs) {    // refused before any input is opened and before anything is printed or written
+        if (!fgpu_stage3_set_junctions || !fgpu_stage3_build || !fgpu_stage3_raw_contigs || !fgpu_stage3_fasta_take) {
+            fprintf(stderr, "--raw_contigs: the library this program is linked against lacks the entry points of the graph build and its contigs "
+                            "(fgpu_stage3_set_junctions, fgpu_stage3_build, fgpu_stage3_raw_contigs, fgpu_stage3_fasta_take)\n");
+            return 2;
+        }
+        if (o.just_load || o.from_junctions) { fprintf(stderr, "--raw_contigs needs the junction scan of this run: leave out --just_load_bloom and -junctions_file\n"); return 2; }
     }
     if (o.estimate && !(o.est_kmers_flag && o.est_sing_flag)) {     // pass 0, ahead of everything the two numbers decide (and of the lines that print them)
         if (o.k < 1 || o.k > 31) { fprintf(stderr, "k must be in 1..31 on this build\n"); return 1; }

@@ -902,6 +902,75 @@ int fgpu_stage3_build(fgpu_ctx* ctx, int32_t max_read_length, uint64_t totals[4]
 int fgpu_stage3_build_take(fgpu_ctx* ctx, fgpu_contig* contigs, fgpu_build_call* calls, uint64_t n_calls, uint64_t* text, uint64_t text_words,
                            uint64_t* seg_kmers, uint8_t* seg_dist, uint64_t n_seg, uint8_t* cov, uint64_t n_cov);
 
+/* ---- Stage 3's first product: the build's contigs as FASTA ------------------------
+ * ContigGraph::printContigs (src/ContigGraph.cpp:1532-1645) on the graph JunctionMap::buildContigGraph returns: the file the reference
+ * names <prefix>.raw_contigs.fasta (src/Faucet.cpp:314).  Three layers, each callable alone.
+ *
+ * fgpu_raw_plan -- host only, no device, no text: WHAT is printed, and in which order.  From the map (keys and records in map order) and a
+ * finished build's fgpu_contig / fgpu_build_call arrays it makes the reference's graph -- nodeMap, a real std::unordered_map<uint64_t, ...>
+ * that takes the reference's inserts in the reference's order (ContigGraph::createContigNode, src/ContigGraph.cpp:1656: the start of every
+ * complex junction the branching loop visits, utils/JunctionMap.cpp:42, and the far junction of a call whose far_is_junction holds and whose
+ * far_is_start does not, :66; an insert of a key that is there changes nothing), every node a copy of its junction's four coverages (the
+ * homopolymer rule :43-47 zeroes one of a node visited as a start), Contig::setEnds (src/Contig.cpp:123-133) filling contigs[ind1] of the
+ * start node and contigs[ind2] of the far node (far_is_start: both of the start node), and isolated_contigs, one per linear region in call
+ * order (utils/JunctionMap.cpp:120) -- and then walks it as the two printing passes do:
+ *   printAndMarkBubbleContigs (:1543-1580), over nodeMap in the container's order: a node with exactly two covered extensions whose two
+ *     contigs have the same other-end node, and have one (isBubbleNode :490-503, allSame :153-162) and whose contigs[4] is shorter than 250
+ *     bases prints getNewConcatenatedContig(contigs[4], contigs[i], node) (:1509-1530) for every unmarked contigs[i], i = 0..3, while
+ *     contigs[4] is unmarked, and marks contigs[i]; contigs[4] is marked behind the node.  contigs[4] is reversed if Contig::getSide(node)
+ *     is 1 (node1_p is tested first, src/Contig.cpp:243-253), contigs[i] if it is 2.
+ *   printUnmarkedUnitigs (:1605-1645), over nodeMap again: every unmarked contigs[0..4], marked as printed; then every isolated contig
+ *     of at least read_length bases, backward->concatenate(forward, 1, 1): the backward chain reversed, then the forward one.
+ * One fgpu_fasta_seq per record, in file order: one or two pieces of the text (first word, bases, flip = reverse-complemented); the
+ * second piece is appended behind the first WITHOUT ITS LAST k BASES (ContigJuncList::concatenate, utils/ContigJuncList.cpp:107-123).
+ * `number` is the n of ">Contig<n>", counting from 1 through both passes.  The 250 test and the read_length test read the len fields only.
+ * The canonical orientation (canon_contig) is not decided here.
+ * Returns FGPU_PLAN_OK; FGPU_PLAN_UNSET: the reference would read a contig pointer nobody set (a bubble test on a node with a covered
+ * extension or a back that has no contig; the reference's behaviour is undefined there) -- nothing is guessed; FGPU_PLAN_INPUT: the arrays
+ * are not a finished build of this map (a start that is not a key of the map, a linear forward call without its backward one, a branching
+ * call behind a linear one, an index outside 0..4, a contig shorter than k); FGPU_PLAN_SHORT: more than cap records (*n_out says how many;
+ * n_calls always suffices).  With FGPU_PLAN_OK and FGPU_PLAN_SHORT `info` is filled.
+ *
+ * fgpu_stage3_fasta -- the device: join, orient and print n records.  text_host == NULL: the pieces index the text of the last
+ * fgpu_stage3_build whose results are still on the device (FGPU_ERR_STATE if there is none); the build's results are neither freed nor
+ * changed.  text_host != NULL: text_words words of 2-bit text (fgpu_stage3_contigs_take's layout and code) are uploaded first.  A piece
+ * that reaches past the text, a piece of no bases, a first piece of two that is shorter than k, or `pieces` other than 1 or 2 is
+ * FGPU_ERR_ARG.  Every record is ">Contig<number>\n<sequence>\n", the sequence or its reverse complement, whichever is not greater AS A
+ * STRING OF LETTERS (canon_contig, utils/Kmer.cpp:345-351: A < C < G < T, not the order of the 2-bit codes; a reverse-complement
+ * palindrome stays as it is).  The bytes stay on the device, *bytes says how many (0 for n == 0); fgpu_stage3_fasta_take copies them out
+ * and frees them.  A buffer shorter than that is FGPU_ERR_ARG: nothing is copied, and the results are still there.  Results that were not
+ * taken are dropped by the next fgpu_stage3_fasta or fgpu_stage3_raw_contigs.
+ *
+ * fgpu_stage3_raw_contigs -- both, on a finished build that has not been taken and whose status is 0 (otherwise FGPU_ERR_ARG and a message:
+ * with status 1 or 3 the reference itself does not get as far as printing).  Only the two record arrays of the build come to the host;
+ * fgpu_raw_plan's status other than FGPU_PLAN_OK is FGPU_ERR_STATE with a message.  Afterwards fgpu_stage3_build_take still returns the
+ * build, unchanged, and fgpu_stage3_fasta_take the file. */
+#define FGPU_PLAN_OK    0
+#define FGPU_PLAN_UNSET 1
+#define FGPU_PLAN_INPUT 2
+#define FGPU_PLAN_SHORT 3
+typedef struct {
+    uint64_t text_word[2];   /* first word of each piece's string in the text */
+    uint32_t len[2];         /* bases of each piece */
+    uint8_t  flip[2];        /* 1: the piece is reverse-complemented before it is joined */
+    uint8_t  pieces;         /* 1 or 2 */
+    uint8_t  reserved;
+    uint32_t number;         /* >Contig<number> */
+} fgpu_fasta_seq;
+typedef struct {
+    uint64_t records;           /* records of the file */
+    uint64_t bubble_records;    /* ... printed by printAndMarkBubbleContigs (two pieces each) */
+    uint64_t node_contigs;      /* ... printed by printUnmarkedUnitigs off a node */
+    uint64_t isolated_kept;     /* ... isolated contigs of at least read_length bases */
+    uint64_t isolated_dropped;  /* isolated contigs below read_length: not printed */
+    uint64_t nodes;             /* entries of nodeMap */
+} fgpu_raw_info;
+int fgpu_raw_plan(const uint64_t* keys, const fgpu_junction* recs, uint64_t n_junctions, const fgpu_contig* contigs, const fgpu_build_call* calls,
+                  uint64_t n_calls, int32_t k, int32_t read_length, fgpu_fasta_seq* out, uint64_t cap, uint64_t* n_out, fgpu_raw_info* info);
+int fgpu_stage3_fasta(fgpu_ctx* ctx, const fgpu_fasta_seq* seqs_host, uint64_t n, const uint64_t* text_host, uint64_t text_words, uint64_t* bytes);
+int fgpu_stage3_fasta_take(fgpu_ctx* ctx, char* out, uint64_t bytes);
+int fgpu_stage3_raw_contigs(fgpu_ctx* ctx, int32_t read_length, uint64_t* bytes, fgpu_raw_info* info);
+
 /* ---- profiling --------------------------------------------------------------------------------- */
 typedef struct {
     char     name[48];
