@@ -207,6 +207,8 @@ SIGNATURES = {
     "fgpu_stage3_fasta": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_u64)]),
     "fgpu_stage3_fasta_take": (C.c_int, [_vp, _vp, _u64]),
     "fgpu_stage3_raw_contigs": (C.c_int, [_vp, _i32, _P(_u64), _P(RawInfo)]),
+    "fgpu_stage3_join": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _P(_u64)]),
+    "fgpu_stage3_join_take": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64]),
     "fgpu_kernel_times": (C.c_int, [_vp, _P(KernelTime), C.c_int]),
     "fgpu_kernel_times_reset": (C.c_int, [_vp]),
     "fgpu_profile_enable": (C.c_int, [_vp, C.c_int]),

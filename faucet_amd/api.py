@@ -126,6 +126,9 @@ BUILD_DTYPE = np.dtype([("start_kmer", "<u8"), ("far_kmer", "<u8"), ("time", "<u
 BUILD_BRANCHING, BUILD_LINEAR_FORWARD, BUILD_LINEAR_BACKWARD = range(3)
 FASTA_SEQ_DTYPE = np.dtype([("text_word", "<u8", (2,)), ("len", "<u4", (2,)), ("flip", "u1", (2,)), ("pieces", "u1"), ("reserved", "u1"),
                             ("number", "<u4")])   # fgpu_fasta_seq
+JOIN_PIECE_DTYPE = np.dtype([("call", "<u4"), ("flip", "<u4")])   # fgpu_join_piece
+JOINED_DTYPE = np.dtype([("text_word", "<u8"), ("dist_first", "<u8"), ("cov_first", "<u8"), ("cov_sum", "<u8"), ("len", "<u4"), ("n_dist", "<u4"),
+                         ("n_cov", "<u4"), ("reserved", "<u4")])   # fgpu_joined
 
 
 class _PinnedMemory:
@@ -818,6 +821,38 @@ class Context:
         ri = L.RawInfo()
         self._c(self.lib.fgpu_stage3_raw_contigs(self.h, int(read_length), C.byref(nbytes), C.byref(ri)))
         return self.stage3_fasta_take(nbytes.value), ri.as_dict()
+
+    def stage3_join(self, lists, contigs=None, text=None, dist=None, cov=None, raw: bool = False):
+        """Contigs that are joins of contigs (fgpu_stage3_join): ContigJuncList::concatenate, applied left to right over every list of
+        (contig, flip) pieces -- a flipped piece is read as ContigJuncList::reverse leaves it; consecutive pieces overlap by k bases; the last
+        coverage of the left side and the first of the right become their minimum.  contigs=None: the pieces index the calls of the last
+        stage3_build(take=False), whose arrays are read where they lie on the device; otherwise a CONTIG_DTYPE array with the text words,
+        distances and coverages it indexes (stage3_contigs(raw=True)'s layout).  Returns (JOINED_DTYPE array, strings, distances, coverages,
+        average coverages): per list the joined string, the two lists as uint8 arrays, and cov_sum / n_cov as a float64, which is
+        ContigJuncList::getAvgCoverage.  raw=True: (JOINED_DTYPE array, text words, distances, coverages), as the library lays them out."""
+        lists = [list(pl) for pl in lists]
+        first = np.zeros(len(lists) + 1, dtype=np.uint64)
+        first[1:] = np.cumsum([len(pl) for pl in lists], dtype=np.uint64)
+        pieces = np.zeros(int(first[-1]), dtype=JOIN_PIECE_DTYPE)
+        flat = [pc for pl in lists for pc in pl]
+        pieces["call"], pieces["flip"] = [c for c, _ in flat], [int(f) for _, f in flat]
+        args = [None, 0, None, 0, None, 0, None, 0]
+        if contigs is not None:
+            contigs = np.ascontiguousarray(contigs, dtype=CONTIG_DTYPE)
+            text, dist, cov = np.ascontiguousarray(text, dtype=np.uint64), np.ascontiguousarray(dist, dtype=np.uint8), np.ascontiguousarray(cov, dtype=np.uint8)
+            args = [x for a in (contigs, text, dist, cov) for x in (a.ctypes.data, len(a))]
+        out = np.zeros(len(lists), dtype=JOINED_DTYPE)
+        totals = (C.c_uint64 * 3)()
+        self._c(self.lib.fgpu_stage3_join(self.h, first.ctypes.data, len(lists), pieces.ctypes.data, len(pieces), *args, out.ctypes.data, totals))
+        jtext, jdist, jcov = np.zeros(totals[0], dtype=np.uint64), np.zeros(totals[1], dtype=np.uint8), np.zeros(totals[2], dtype=np.uint8)
+        self._c(self.lib.fgpu_stage3_join_take(self.h, jtext.ctypes.data, len(jtext), jdist.ctypes.data, len(jdist), jcov.ctypes.data, len(jcov)))
+        if raw:
+            return out, jtext, jdist, jcov
+        chars = np.frombuffer(b"ACTG", dtype=np.uint8)[((jtext[:, None] >> (2 * np.arange(32, dtype=np.uint64))[None, :]) & np.uint64(3)).astype(np.int64)].reshape(-1)
+        strings = [chars[32 * int(j["text_word"]):32 * int(j["text_word"]) + int(j["len"])].tobytes().decode() for j in out]
+        dists = [jdist[int(j["dist_first"]):int(j["dist_first"]) + int(j["n_dist"])] for j in out]
+        covs = [jcov[int(j["cov_first"]):int(j["cov_first"]) + int(j["n_cov"])] for j in out]
+        return out, strings, dists, covs, out["cov_sum"].astype(np.float64) / out["n_cov"].astype(np.float64)
 
     def kernel_times(self) -> dict:
         arr = (L.KernelTime * 64)()

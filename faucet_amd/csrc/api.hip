@@ -436,7 +436,7 @@ void fgpu_destroy(fgpu_ctx* ctx) {
     if (ctx->lp.ev_open) hipEventDestroy(ctx->lp.ev_open);
     void* ptrs[] = {ctx->lp.bits, ctx->lp.first, ctx->short_pf, ctx->bloo1, ctx->bloo2, ctx->first, ctx->pair, ctx->rec, ctx->slice_first, ctx->slice_pair, ctx->est_planes, ctx->jkeys, ctx->jrecs, ctx->jstamps, ctx->jfilter, ctx->wkeys,
                     ctx->wbits, ctx->uf_parent, ctx->cl_count, ctx->cl_offset, ctx->cl_fill, ctx->cl_weight, ctx->ko_hk, ctx->ko_occ, ctx->ko_piece, ctx->cl_members, ctx->cl_roots, ctx->counters,
-                    ctx->wdesc, ctx->s3c_out, ctx->s3b_out, ctx->s3f_out};
+                    ctx->wdesc, ctx->s3c_out, ctx->s3b_out, ctx->s3f_out, ctx->s3j_out};
     for (void* p : ptrs) if (p) hipFree(p);
     stop_queue_recycle(ctx);
     for (StopBatch& f : ctx->stop_pool) hipHostFree(f.data);

@@ -466,6 +466,8 @@ struct fgpu_ctx {
     int32_t s3b_status = 0;               // ... its fgpu_build_info.status
     void* s3f_out = nullptr;              // fgpu_stage3_fasta's bytes until fgpu_stage3_fasta_take (stage3_emit.hip)
     uint64_t s3f_bytes = 0;
+    void* s3j_out = nullptr;              // fgpu_stage3_join's arrays until fgpu_stage3_join_take (stage3_join.hip): joined text, distances, coverages
+    uint64_t s3j_totals[3] = {0, 0, 0};   // their entries: text words, distances, coverages
     uint64_t s3_mask = 0, s3_count = 0;
     bool s3_ready = false;
     DevBuf dl_entries, dl_stamps, dl_stamps_sorted, dl_idx, dl_idx_sorted, dl_keys, dl_recs, dl_tmp;   // junction download scratch
@@ -538,6 +540,8 @@ static inline hipError_t fgpu_sync_event_at(fgpu_ctx* ctx, hipEvent_t ev, const 
 int fgpu_ensure(fgpu_ctx* ctx, DevBuf* b, uint64_t bytes);
 // the untaken results of fgpu_stage3_build where they lie on the device (stage3.hip; any pointer may be null): 0 if there is no such build
 int fgpu_s3b_view(fgpu_ctx* ctx, const fgpu_contig** contigs, const fgpu_build_call** calls, const uint64_t** text);
+// ... its per-segment distances and its coverages (the arrays fgpu_contig.seg_first / cov_first index)
+int fgpu_s3b_lists(fgpu_ctx* ctx, const uint8_t** seg_dist, const uint8_t** cov);
 int fgpu_ensure_b(fgpu_ctx* ctx, DevBuf* b, uint64_t bytes);   // a buffer whose size follows the batch: grown for the largest batch announced (ensure_scale)
 int fgpu_bg_join(fgpu_ctx* ctx);
 int fgpu_prof_begin(fgpu_ctx* ctx, const char* name);

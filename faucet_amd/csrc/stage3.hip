@@ -1037,6 +1037,15 @@ int fgpu_s3b_view(fgpu_ctx* ctx, const fgpu_contig** contigs, const fgpu_build_c
     return 1;
 }
 
+int fgpu_s3b_lists(fgpu_ctx* ctx, const uint8_t** seg_dist, const uint8_t** cov) {
+    if (!ctx->s3b_have) return 0;
+    const S3bLayout lay = s3b_layout(ctx->s3b_totals);
+    const char* res = (const char*)ctx->s3b_out;
+    if (seg_dist) *seg_dist = (const uint8_t*)(res + lay.dist);
+    if (cov) *cov = (const uint8_t*)(res + lay.cov);
+    return 1;
+}
+
 extern "C" int fgpu_stage3_build(fgpu_ctx* ctx, int32_t max_read_length, uint64_t totals[4], fgpu_build_info* info) {
     if (!ctx || !totals || max_read_length < 1) return FGPU_ERR_ARG;
     if (ctx->phase != 0) { ctx->err = "fgpu_stage3_build while a pass is open"; return FGPU_ERR_STATE; }

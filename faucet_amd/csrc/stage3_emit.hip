@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "fgpu_ctx.h"
+#include "stage3_bits.h"
 
 namespace {
 
@@ -29,45 +30,12 @@ static_assert(sizeof(fgpu_fasta_seq) == 32 && sizeof(fgpu_raw_info) == 48, "the 
 
 constexpr uint32_t EMIT_TILE = 4096;             // bytes of output per block of k_emit_ascii: 256 lanes x 16 bytes
 constexpr uint32_t EMIT_TILE_RECORDS = 512;      // offsets kept per tile: a record has at least 11 bytes (">Contig1\n", a base, "\n"), so a tile touches at most 374
-constexpr uint64_t EMIT_ODD = 0x5555555555555555ULL, EMIT_COMPLEMENT = 0xAAAAAAAAAAAAAAAAULL;
 
 __device__ __forceinline__ uint32_t emit_joined_len(const fgpu_fasta_seq& s, int k) { return s.pieces == 2 ? s.len[0] - (uint32_t)k + s.len[1] : s.len[0]; }
 __device__ __forceinline__ uint32_t emit_digits(uint32_t v) {
     uint32_t d = 1;
     for (uint32_t p = 10; d < 10 && v >= p; p *= 10) d++;      // (p overflows only behind d == 10, where the loop has ended)
     return d;
-}
-
-// bases a .. a + 31 of a 2-bit string of `len` bases, base a in the lowest bits; -31 <= a < len.  Fields outside 0 .. len - 1 hold no
-// information (the callers mask them); no word behind the string's last one is read.
-__device__ __forceinline__ uint64_t emit_window(const uint64_t* __restrict__ w, uint32_t len, int64_t a) {
-    const uint32_t words = (len + 31) >> 5;
-    if (a < 0) return w[0] << (2 * (uint32_t)(-a));
-    const uint32_t at = (uint32_t)(a >> 5), sh = 2 * ((uint32_t)a & 31);
-    const uint64_t lo = at < words ? w[at] : 0;
-    if (!sh) return lo;
-    const uint64_t hi = at + 1 < words ? w[at + 1] : 0;
-    return (lo >> sh) | (hi << (64 - sh));
-}
-// the reverse complement of 32 bases: the fields in reverse order, each code ^ 2
-__device__ __forceinline__ uint64_t emit_revcomp(uint64_t x) {
-    const uint64_t r = __brevll(x);
-    return (((r >> 1) & EMIT_ODD) | ((r & EMIT_ODD) << 1)) ^ EMIT_COMPLEMENT;
-}
-// bases pos .. pos + 31 of the string as it is read (flip: reverse-complemented), pos < len
-__device__ __forceinline__ uint64_t emit_oriented(const uint64_t* __restrict__ w, uint32_t len, bool flip, uint32_t pos) {
-    return flip ? emit_revcomp(emit_window(w, len, (int64_t)len - 32 - (int64_t)pos)) : emit_window(w, len, (int64_t)pos);
-}
-__device__ __forceinline__ uint64_t emit_low_fields(uint32_t n) { return n >= 32 ? ~0ULL : ((1ULL << (2 * n)) - 1); }
-
-// the last entry e of off[0 .. n] (ascending, off[0] = 0) with off[e] <= x, for x < off[n]
-__device__ __forceinline__ uint64_t emit_find(const uint64_t* __restrict__ off, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;                       // off[lo] <= x < off[hi]
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 __global__ void __launch_bounds__(256) k_emit_sizes(const fgpu_fasta_seq* __restrict__ seqs, uint64_t n, int k, uint64_t* __restrict__ words, uint64_t* __restrict__ bytes) {

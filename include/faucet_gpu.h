@@ -971,6 +971,53 @@ int fgpu_stage3_fasta(fgpu_ctx* ctx, const fgpu_fasta_seq* seqs_host, uint64_t n
 int fgpu_stage3_fasta_take(fgpu_ctx* ctx, char* out, uint64_t bytes);
 int fgpu_stage3_raw_contigs(fgpu_ctx* ctx, int32_t read_length, uint64_t* bytes, fgpu_raw_info* info);
 
+/* ---- Stage 3's contigs joined: ContigJuncList::concatenate over piece lists, on the device ----
+ * What ContigGraph's cleaning steps make of the build's contigs are JOINS of them: Contig::concatenate (src/Contig.cpp:83-109) reverses either
+ * side where it has to (ContigJuncList::reverse, utils/ContigJuncList.cpp:98-103: both lists reversed, the sequence reverse-complemented) and
+ * calls ContigJuncList::concatenate (utils/ContigJuncList.cpp:107-123), again and again as collapseNode (src/ContigGraph.cpp:709-736) takes
+ * node after node out.  A contig of the cleaned graph is therefore an ordered list of PIECES (a contig of the build, flip), consecutive
+ * pieces overlapping by k bases, and its three members are functions of that list alone:
+ *   seq        every piece but the last gives its first len - k bases as it is read (flip: reverse-complemented) -- which may be none --,
+ *              the last piece all of them (:121)
+ *   distances  the pieces' lists one behind the other, a flipped piece's reversed (:119-120)
+ *   coverages  ... likewise, but the last entry of the left side and the first of the right become ONE entry, the smaller of the two (:109-117).
+ *              Applied left to right an output entry is the minimum over a run of the concatenated oriented inputs: of length 1 inside a
+ *              piece, 2 at a join, and longer where middle pieces hold a single coverage entry (that entry is the left side's last AND,
+ *              one call on, the result's last again).  n_cov = the sum of the pieces' n_cov minus (pieces - 1).
+ *   cov_sum    the sum of the joined coverages: cov_sum / (double) n_cov IS ContigJuncList::getAvgCoverage (:166-176) -- every partial sum of
+ *              at most 2^53 / 255 bytes is exact in double -- which chimera removal, bulge collapsing and disentangling read.
+ * fgpu_stage3_join: n lists as a CSR -- list i is pieces[list_first[i] .. list_first[i + 1]), list_first[0] = 0, list_first[n] = n_pieces, no
+ * list empty.  contigs_host == NULL: `call` indexes the calls of the last fgpu_stage3_build whose results are still on the device
+ * (FGPU_ERR_STATE if there is none), and its text, distances and coverages are read where they lie; only its fgpu_contig records come to the
+ * host, to be checked.  The build is neither freed nor changed.  The other five array arguments must then be NULL / 0.  contigs_host !=
+ * NULL: n_contigs records and the three arrays they index, in fgpu_stage3_contigs_take's layout, are uploaded first (end_kmer, ind1, ind2,
+ * end_node, status are not read).  FGPU_ERR_ARG, with a message, totals 0, nothing launched and earlier results untouched (out[] may hold the lists checked so far): a CSR that is not one; a `call` that is no record; a
+ * flip other than 0 / 1; a piece that reaches past one of the arrays, has no bases or 2^30 and more, or has no coverage entry; a piece
+ * other than a list's last that is shorter than k; a joined string of 2^32 bases and more.
+ * Per list an fgpu_joined in out[i]; the joined strings (each from a word of its own, first base lowest, the bits behind `len` zero: what
+ * fgpu_stage3_fasta's kernels print from), distances and coverages stay on the device, totals says how long they are (text words,
+ * distances, coverages; all 0 for n == 0).  fgpu_stage3_join_take copies them out and frees them; an array with fewer entries than the
+ * totals is FGPU_ERR_ARG: nothing is copied, and the results are still there.  Results that were not taken are dropped by the next
+ * fgpu_stage3_join. */
+typedef struct {
+    uint32_t call;        /* the piece: record `call` of the contigs */
+    uint32_t flip;        /* 1: read reversed (ContigJuncList::reverse) */
+} fgpu_join_piece;
+typedef struct {
+    uint64_t text_word;   /* first word of the joined string in the joined text */
+    uint64_t dist_first;  /* first entry in the joined distances */
+    uint64_t cov_first;   /* first entry in the joined coverages */
+    uint64_t cov_sum;     /* sum of the joined coverages */
+    uint32_t len;         /* bases */
+    uint32_t n_dist;
+    uint32_t n_cov;
+    uint32_t reserved;
+} fgpu_joined;
+int fgpu_stage3_join(fgpu_ctx* ctx, const uint64_t* list_first, uint64_t n, const fgpu_join_piece* pieces, uint64_t n_pieces,
+                     const fgpu_contig* contigs_host, uint64_t n_contigs, const uint64_t* text_host, uint64_t text_words,
+                     const uint8_t* dist_host, uint64_t n_dist, const uint8_t* cov_host, uint64_t n_cov, fgpu_joined* out, uint64_t totals[3]);
+int fgpu_stage3_join_take(fgpu_ctx* ctx, uint64_t* text, uint64_t text_words, uint8_t* dist, uint64_t n_dist, uint8_t* cov, uint64_t n_cov);
+
 /* ---- profiling --------------------------------------------------------------------------------- */
 typedef struct {
     char     name[48];
