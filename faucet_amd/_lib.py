@@ -89,6 +89,25 @@ class RawInfo(C.Structure):
 PLAN_OK, PLAN_UNSET, PLAN_INPUT, PLAN_SHORT = range(4)
 
 
+class TipsInfo(C.Structure):
+    """fgpu_tips_info: what ContigGraph::deleteTipsAndClean did, and what the file printed behind it holds"""
+    _fields_ = [("nodes_before", C.c_uint64), ("tips", C.c_uint64), ("back_tips", C.c_uint64), ("collapsed", C.c_uint64 * 2), ("degenerate", C.c_uint64 * 2),
+                ("validated", C.c_uint32), ("changed", C.c_uint32), ("print", RawInfo)]
+
+    def as_dict(self):
+        return dict(nodes_before=int(self.nodes_before), tips=int(self.tips), back_tips=int(self.back_tips), collapsed=[int(v) for v in self.collapsed],
+                    degenerate=[int(v) for v in self.degenerate], validated=int(self.validated), changed=int(self.changed), print=self.print.as_dict())
+
+
+class TipsOut(C.Structure):
+    """fgpu_tips_out: the arrays fgpu_tips_plan and fgpu_stage3_graph_take fill, their room, and how much was needed"""
+    _fields_ = [("nodes", C.c_void_p), ("nodes_cap", C.c_uint64), ("n_nodes", C.c_uint64),
+                ("contigs", C.c_void_p), ("list_first", C.c_void_p), ("contigs_cap", C.c_uint64), ("n_contigs", C.c_uint64),
+                ("pieces", C.c_void_p), ("pieces_cap", C.c_uint64), ("n_pieces", C.c_uint64),
+                ("print_first", C.c_void_p), ("print_number", C.c_void_p), ("print_cap", C.c_uint64), ("n_print", C.c_uint64),
+                ("print_pieces", C.c_void_p), ("print_pieces_cap", C.c_uint64), ("n_print_pieces", C.c_uint64)]
+
+
 class BuildInfo(C.Structure):
     _fields_ = [("status", C.c_int32), ("rounds", C.c_uint32), ("stop_call", C.c_uint64), ("calls_possible", C.c_uint64), ("rewalked", C.c_uint64),
                 ("probes", C.c_uint64), ("table_hits", C.c_uint64), ("regrown", C.c_uint64), ("rewalked_by_round", C.c_uint64 * BUILD_ROUNDS_KEPT)]
@@ -209,6 +228,10 @@ SIGNATURES = {
     "fgpu_stage3_raw_contigs": (C.c_int, [_vp, _i32, _P(_u64), _P(RawInfo)]),
     "fgpu_stage3_join": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _P(_u64)]),
     "fgpu_stage3_join_take": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64]),
+    "fgpu_tips_plan": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _i32, _i32, _P(TipsOut), _P(TipsInfo)]),
+    "fgpu_stage3_fasta_joined": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _P(_u64)]),
+    "fgpu_stage3_detip": (C.c_int, [_vp, _i32, _P(_u64), _P(TipsInfo)]),
+    "fgpu_stage3_graph_take": (C.c_int, [_vp, _P(TipsOut)]),
     "fgpu_kernel_times": (C.c_int, [_vp, _P(KernelTime), C.c_int]),
     "fgpu_kernel_times_reset": (C.c_int, [_vp]),
     "fgpu_profile_enable": (C.c_int, [_vp, C.c_int]),

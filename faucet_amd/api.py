@@ -127,6 +127,9 @@ BUILD_BRANCHING, BUILD_LINEAR_FORWARD, BUILD_LINEAR_BACKWARD = range(3)
 FASTA_SEQ_DTYPE = np.dtype([("text_word", "<u8", (2,)), ("len", "<u4", (2,)), ("flip", "u1", (2,)), ("pieces", "u1"), ("reserved", "u1"),
                             ("number", "<u4")])   # fgpu_fasta_seq
 JOIN_PIECE_DTYPE = np.dtype([("call", "<u4"), ("flip", "<u4")])   # fgpu_join_piece
+TIPS_NODE_DTYPE = np.dtype([("key", "<u8"), ("cov", np.uint8, 4), ("slot", "<i4", (5,))])   # fgpu_tips_node
+TIPS_CONTIG_DTYPE = np.dtype([("node1", "<u8"), ("node2", "<u8"), ("len", "<u4"), ("has1", "u1"), ("has2", "u1"), ("ind1", "u1"), ("ind2", "u1"),
+                              ("isolated", "u1"), ("reserved", "u1", (7,))])   # fgpu_tips_contig
 JOINED_DTYPE = np.dtype([("text_word", "<u8"), ("dist_first", "<u8"), ("cov_first", "<u8"), ("cov_sum", "<u8"), ("len", "<u4"), ("n_dist", "<u4"),
                          ("n_cov", "<u4"), ("reserved", "<u4")])   # fgpu_joined
 
@@ -854,6 +857,44 @@ class Context:
         covs = [jcov[int(j["cov_first"]):int(j["cov_first"]) + int(j["n_cov"])] for j in out]
         return out, strings, dists, covs, out["cov_sum"].astype(np.float64) / out["n_cov"].astype(np.float64)
 
+    def stage3_fasta_joined(self, joined, numbers, text=None) -> bytes:
+        """JOINED_DTYPE records oriented and printed on the device (fgpu_stage3_fasta_joined): record i is ">Contig<numbers[i]>\n", its len bases
+        from word text_word of the text as canon_contig leaves them, and "\n".  text: the joined 2-bit words (stage3_join(raw=True)'s); None: the
+        joined text the last fgpu_stage3_join left on the device, read where it lies."""
+        joined = np.ascontiguousarray(joined, dtype=JOINED_DTYPE)
+        numbers = np.ascontiguousarray(numbers, dtype=np.uint32)
+        if len(numbers) != len(joined):
+            raise ValueError("one number per record")
+        if text is not None:
+            text = np.ascontiguousarray(text, dtype=np.uint64)
+        nbytes = C.c_uint64(0)
+        self._c(self.lib.fgpu_stage3_fasta_joined(self.h, joined.ctypes.data, numbers.ctypes.data, len(joined), None if text is None else text.ctypes.data,
+                                                  0 if text is None else len(text), C.byref(nbytes)))
+        return self.stage3_fasta_take(nbytes.value)
+
+    def stage3_graph_take(self) -> dict:
+        """the graph the last stage3_detip left (fgpu_stage3_graph_take): dict(nodes TIPS_NODE_DTYPE in map order, contigs TIPS_CONTIG_DTYPE,
+        lists = per contig its [(call, flip)] over the calls of the build: valid input to stage3_join)"""
+        out = L.TipsOut()
+        first = np.zeros(1, dtype=np.uint64)
+        out.list_first = first.ctypes.data
+        rc = self.lib.fgpu_stage3_graph_take(self.h, C.byref(out))          # (no room: how much is needed)
+        if rc == 0:                                                          # an empty graph: taken
+            return dict(nodes=np.zeros(0, dtype=TIPS_NODE_DTYPE), contigs=np.zeros(0, dtype=TIPS_CONTIG_DTYPE), lists=[])
+        if rc != L.ERR_ARG:
+            self._c(rc)
+        return _tips_graph(out, lambda: self._c(self.lib.fgpu_stage3_graph_take(self.h, C.byref(out))))
+
+    def stage3_detip(self, read_length: int):
+        """ContigGraph::deleteTipsAndClean (src/ContigGraph.cpp:168-175) and printContigs behind it, on the build stage3_build(max_read_length,
+        take=False) left on the device (fgpu_stage3_detip): (the file's bytes, info = dict(nodes_before, tips, back_tips, collapsed, degenerate,
+        validated, changed, print = stage3_raw_contigs' info of this file)).  The build stays where it is; stage3_graph_take() gives the graph
+        left.  Join results and a file that were not taken before the call are dropped."""
+        nbytes = C.c_uint64(0)
+        ti = L.TipsInfo()
+        self._c(self.lib.fgpu_stage3_detip(self.h, int(read_length), C.byref(nbytes), C.byref(ti)))
+        return self.stage3_fasta_take(nbytes.value), ti.as_dict()
+
     def kernel_times(self) -> dict:
         arr = (L.KernelTime * 64)()
         n = self.lib.fgpu_kernel_times(self.h, arr, 64)
@@ -1008,6 +1049,48 @@ class ReadScanner:
 
 
 _DEC = np.frombuffer(b"ACTG", dtype=np.uint8)
+
+
+def _tips_graph(out, fill):
+    """room for what `out` (an L.TipsOut whose n_* are set) needs, `fill()` run on it, and the graph as a dict"""
+    nodes, contigs = np.zeros(out.n_nodes, dtype=TIPS_NODE_DTYPE), np.zeros(out.n_contigs, dtype=TIPS_CONTIG_DTYPE)
+    first, pieces = np.zeros(out.n_contigs + 1, dtype=np.uint64), np.zeros(out.n_pieces, dtype=JOIN_PIECE_DTYPE)
+    out.nodes, out.nodes_cap = nodes.ctypes.data, len(nodes)
+    out.contigs, out.list_first, out.contigs_cap = contigs.ctypes.data, first.ctypes.data, len(contigs)
+    out.pieces, out.pieces_cap = pieces.ctypes.data, len(pieces)
+    fill()
+    return dict(nodes=nodes, contigs=contigs, lists=_lists_of(first, pieces))
+
+
+def _lists_of(first, pieces):
+    return [[(int(p["call"]), bool(p["flip"])) for p in pieces[int(a):int(b)]] for a, b in zip(first[:-1], first[1:])]
+
+
+def tips_plan(keys, recs, contigs, calls, k: int, read_length: int):
+    """fgpu_tips_plan, host only: which piece lists ContigGraph::deleteTipsAndClean leaves of a finished build (keys and JUNC_DTYPE records in map
+    order, the CONTIG_DTYPE and BUILD_DTYPE arrays of stage3_build) and which of them printContigs prints.  Returns (status, graph, records,
+    info): graph as Context.stage3_graph_take gives it, records = [(number, [(call, flip)])] in file order, info as Context.stage3_detip's;
+    graph and records are None unless status is PLAN_OK (0)."""
+    lib = L.load()
+    keys, recs = np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(recs, dtype=JUNC_DTYPE)
+    contigs, calls = np.ascontiguousarray(contigs, dtype=CONTIG_DTYPE), np.ascontiguousarray(calls, dtype=BUILD_DTYPE)
+    out, ti = L.TipsOut(), L.TipsInfo()
+    args = (keys.ctypes.data, recs.ctypes.data, len(keys), contigs.ctypes.data, calls.ctypes.data, len(contigs), int(k), int(read_length), C.byref(out), C.byref(ti))
+    status = lib.fgpu_tips_plan(*args)                                    # (no room: how much is needed)
+    if status not in (L.PLAN_OK, L.PLAN_SHORT):
+        return status, None, None, ti.as_dict()
+    first, number = np.zeros(out.n_print + 1, dtype=np.uint64), np.zeros(out.n_print, dtype=np.uint32)
+    pieces = np.zeros(out.n_print_pieces, dtype=JOIN_PIECE_DTYPE)
+    out.print_first, out.print_number, out.print_cap = first.ctypes.data, number.ctypes.data, len(number)
+    out.print_pieces, out.print_pieces_cap = pieces.ctypes.data, len(pieces)
+    state = {}
+
+    def fill():
+        state["status"] = lib.fgpu_tips_plan(*args)
+    graph = _tips_graph(out, fill)
+    if state["status"] != L.PLAN_OK:
+        return state["status"], None, None, ti.as_dict()
+    return L.PLAN_OK, graph, list(zip((int(v) for v in number), _lists_of(first, pieces))), ti.as_dict()
 
 
 def print_kmer(kmer: int, k: int) -> str:            # print_kmer / code2seq (utils/Kmer.cpp:217)

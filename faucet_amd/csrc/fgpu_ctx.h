@@ -468,6 +468,11 @@ struct fgpu_ctx {
     uint64_t s3f_bytes = 0;
     void* s3j_out = nullptr;              // fgpu_stage3_join's arrays until fgpu_stage3_join_take (stage3_join.hip): joined text, distances, coverages
     uint64_t s3j_totals[3] = {0, 0, 0};   // their entries: text words, distances, coverages
+    std::vector<fgpu_tips_node> s3t_nodes;        // fgpu_stage3_detip's graph until fgpu_stage3_graph_take (host memory: fgpu_tips_plan made it there)
+    std::vector<fgpu_tips_contig> s3t_contigs;
+    std::vector<uint64_t> s3t_first;              // contigs + 1 entries
+    std::vector<fgpu_join_piece> s3t_pieces;
+    bool s3t_have = false;
     uint64_t s3_mask = 0, s3_count = 0;
     bool s3_ready = false;
     DevBuf dl_entries, dl_stamps, dl_stamps_sorted, dl_idx, dl_idx_sorted, dl_keys, dl_recs, dl_tmp;   // junction download scratch
@@ -542,6 +547,8 @@ int fgpu_ensure(fgpu_ctx* ctx, DevBuf* b, uint64_t bytes);
 int fgpu_s3b_view(fgpu_ctx* ctx, const fgpu_contig** contigs, const fgpu_build_call** calls, const uint64_t** text);
 // ... its per-segment distances and its coverages (the arrays fgpu_contig.seg_first / cov_first index)
 int fgpu_s3b_lists(fgpu_ctx* ctx, const uint8_t** seg_dist, const uint8_t** cov);
+// the joined text of the last fgpu_stage3_join whose results are still on the device (stage3_join.hip), 0 if there is none
+int fgpu_s3j_text(fgpu_ctx* ctx, const uint64_t** text);
 int fgpu_ensure_b(fgpu_ctx* ctx, DevBuf* b, uint64_t bytes);   // a buffer whose size follows the batch: grown for the largest batch announced (ensure_scale)
 int fgpu_bg_join(fgpu_ctx* ctx);
 int fgpu_prof_begin(fgpu_ctx* ctx, const char* name);

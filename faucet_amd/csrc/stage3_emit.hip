@@ -1,5 +1,7 @@
 // stage3_emit.hip — Stage 3's first product on the device: the contigs of a build, joined, oriented and printed as FASTA where they lie
-// (fgpu_stage3_fasta, fgpu_stage3_fasta_take, fgpu_stage3_raw_contigs; include/faucet_gpu.h).
+// (fgpu_stage3_fasta, fgpu_stage3_fasta_take, fgpu_stage3_raw_contigs; include/faucet_gpu.h) -- and its second, the contigs after the first
+// cleaning step, printed from the strings fgpu_stage3_join left on the device (fgpu_stage3_fasta_joined, fgpu_stage3_detip,
+// fgpu_stage3_graph_take).
 //
 // What the reference does per record, ContigGraph::printContigs (src/ContigGraph.cpp:1532-1645):
 //   ContigJuncList::concatenate's sequence          utils/ContigJuncList.cpp:121   first.substr(0, len - k) + second
@@ -14,6 +16,9 @@
 //   k_emit_ascii   one block per 4 KiB of OUTPUT, one lane per 16 bytes, whatever the records' lengths: the block looks up its first
 //                  record once, keeps the byte offsets of the records its tile can touch in LDS, a lane inside a sequence expands 16 codes
 //                  and stores 16 bytes at once, a lane on a header or a record's edge goes byte by byte.
+// k_emit_canon and k_emit_ascii take a record as (first word, bases, number) from a view: EmitSeqView over k_emit_join's strings, EmitJoinedView over
+// fgpu_joined records and any text in the same layout -- a join's text is one, so fgpu_stage3_fasta_joined has no join kernel, and of the
+// sizes only the bytes (k_emit_sizes_joined).  Which lists are joined is the host's business again (tips_plan.cpp).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -27,6 +32,7 @@
 namespace {
 
 static_assert(sizeof(fgpu_fasta_seq) == 32 && sizeof(fgpu_raw_info) == 48, "the records as api.py and _lib.py lay them out");
+static_assert(sizeof(fgpu_tips_node) == 32 && sizeof(fgpu_tips_contig) == 32 && sizeof(fgpu_tips_info) == 112 && sizeof(fgpu_tips_out) == 136, "... likewise");
 
 constexpr uint32_t EMIT_TILE = 4096;             // bytes of output per block of k_emit_ascii: 256 lanes x 16 bytes
 constexpr uint32_t EMIT_TILE_RECORDS = 512;      // offsets kept per tile: a record has at least 11 bytes (">Contig1\n", a base, "\n"), so a tile touches at most 374
@@ -38,6 +44,25 @@ __device__ __forceinline__ uint32_t emit_digits(uint32_t v) {
     return d;
 }
 
+// What k_emit_canon and k_emit_ascii know of record i: where its 2-bit string begins, its bases and its number.  Two sources:
+struct EmitSeqView {                             // fgpu_stage3_fasta: the strings k_emit_join made of the records' pieces
+    const fgpu_fasta_seq* __restrict__ seqs;
+    const uint64_t* __restrict__ word0;
+    const uint64_t* __restrict__ joined;
+    int k;
+    __device__ __forceinline__ const uint64_t* words(uint64_t i) const { return joined + word0[i]; }
+    __device__ __forceinline__ uint32_t len(uint64_t i) const { return emit_joined_len(seqs[i], k); }
+    __device__ __forceinline__ uint32_t number(uint64_t i) const { return seqs[i].number; }
+};
+struct EmitJoinedView {                          // fgpu_stage3_fasta_joined: fgpu_stage3_join's strings where they lie -- already in this layout
+    const fgpu_joined* __restrict__ recs;
+    const uint32_t* __restrict__ numbers;
+    const uint64_t* __restrict__ text;
+    __device__ __forceinline__ const uint64_t* words(uint64_t i) const { return text + recs[i].text_word; }
+    __device__ __forceinline__ uint32_t len(uint64_t i) const { return recs[i].len; }
+    __device__ __forceinline__ uint32_t number(uint64_t i) const { return numbers[i]; }
+};
+
 __global__ void __launch_bounds__(256) k_emit_sizes(const fgpu_fasta_seq* __restrict__ seqs, uint64_t n, int k, uint64_t* __restrict__ words, uint64_t* __restrict__ bytes) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i > n) return;
@@ -46,6 +71,12 @@ __global__ void __launch_bounds__(256) k_emit_sizes(const fgpu_fasta_seq* __rest
     const uint32_t len = emit_joined_len(s, k);
     words[i] = (len + 31) >> 5;
     bytes[i] = 8ULL + emit_digits(s.number) + len + 1;
+}
+
+__global__ void __launch_bounds__(256) k_emit_sizes_joined(const fgpu_joined* __restrict__ recs, const uint32_t* __restrict__ numbers, uint64_t n, uint64_t* __restrict__ bytes) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    bytes[i] = i == n ? 0 : 8ULL + emit_digits(numbers[i]) + recs[i].len + 1;      // (entry n: the scan's total)
 }
 
 __global__ void __launch_bounds__(256) k_emit_join(const fgpu_fasta_seq* __restrict__ seqs, uint64_t n, int k, const uint64_t* __restrict__ text,
@@ -71,13 +102,13 @@ __global__ void __launch_bounds__(256) k_emit_join(const fgpu_fasta_seq* __restr
     joined[g] = w & emit_low_fields(len - pos);
 }
 
-__global__ void __launch_bounds__(256) k_emit_canon(const fgpu_fasta_seq* __restrict__ seqs, uint64_t n, int k, const uint64_t* __restrict__ word0,
-                                                    const uint64_t* __restrict__ joined, uint8_t* __restrict__ flipped) {
+template <class View>
+__global__ void __launch_bounds__(256) k_emit_canon(View view, uint64_t n, uint8_t* __restrict__ flipped) {
     const uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // one wave per record (uniform within the wave)
     if (i >= n) return;
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t len = emit_joined_len(seqs[i], k), words = (len + 31) >> 5;
-    const uint64_t* w = joined + word0[i];
+    const uint32_t len = view.len(i), words = (len + 31) >> 5;
+    const uint64_t* w = view.words(i);
     for (uint32_t j0 = 0; j0 < words; j0 += 64) {
         const uint32_t j = j0 + lane;
         uint64_t own = 0, other = 0;
@@ -106,15 +137,14 @@ struct EmitRecord {                              // what k_emit_ascii knows of t
     uint32_t len, number, digits;
     bool flip;
 };
-__device__ __forceinline__ EmitRecord emit_record(const fgpu_fasta_seq* __restrict__ seqs, uint64_t i, int k, const uint64_t* __restrict__ word0,
-                                                  const uint64_t* __restrict__ joined, const uint8_t* __restrict__ flipped, uint64_t first) {
-    const fgpu_fasta_seq s = seqs[i];
+template <class View>
+__device__ __forceinline__ EmitRecord emit_record(const View& view, uint64_t i, const uint8_t* __restrict__ flipped, uint64_t first) {
     EmitRecord r;
     r.first = first;
-    r.w = joined + word0[i];
-    r.len = emit_joined_len(s, k);
-    r.number = s.number;
-    r.digits = emit_digits(s.number);
+    r.w = view.words(i);
+    r.len = view.len(i);
+    r.number = view.number(i);
+    r.digits = emit_digits(r.number);
     r.flip = flipped[i] != 0;
     return r;
 }
@@ -131,9 +161,9 @@ __device__ __forceinline__ uint32_t emit_byte(const EmitRecord& r, uint32_t at) 
     return emit_letter((uint32_t)emit_oriented(r.w, r.len, r.flip, base) & 3);
 }
 
-__global__ void __launch_bounds__(256) k_emit_ascii(const fgpu_fasta_seq* __restrict__ seqs, uint64_t n, int k, const uint64_t* __restrict__ word0,
-                                                    const uint64_t* __restrict__ byte0, uint64_t n_bytes, const uint64_t* __restrict__ joined,
-                                                    const uint8_t* __restrict__ flipped, uint4* __restrict__ out) {
+template <class View>
+__global__ void __launch_bounds__(256) k_emit_ascii(View view, uint64_t n, const uint64_t* __restrict__ byte0, uint64_t n_bytes, const uint8_t* __restrict__ flipped,
+                                                    uint4* __restrict__ out) {
     __shared__ uint64_t first_of[EMIT_TILE_RECORDS];
     __shared__ uint64_t tile_first;
     const uint64_t tile = (uint64_t)blockIdx.x * EMIT_TILE;               // (< n_bytes by the grid)
@@ -149,7 +179,7 @@ __global__ void __launch_bounds__(256) k_emit_ascii(const fgpu_fasta_seq* __rest
         const uint32_t mid = (lo + hi) >> 1;
         if (first_of[mid] <= at) lo = mid; else hi = mid;
     }
-    EmitRecord r = emit_record(seqs, i0 + lo, k, word0, joined, flipped, first_of[lo]);
+    EmitRecord r = emit_record(view, i0 + lo, flipped, first_of[lo]);
     uint32_t v[4] = {0, 0, 0, 0};
     const uint64_t in = at - r.first, bases = 8 + r.digits;
     if (in >= bases && in + 16 <= bases + r.len) {                         // sixteen bases of one sequence
@@ -160,7 +190,7 @@ __global__ void __launch_bounds__(256) k_emit_ascii(const fgpu_fasta_seq* __rest
         for (uint32_t b = 0; b < 16 && at + b < n_bytes; b++) {            // (behind the last byte: zeros, in the buffer's own padding)
             while (lo + 1 < EMIT_TILE_RECORDS && first_of[lo + 1] <= at + b) {
                 lo++;
-                r = emit_record(seqs, i0 + lo, k, word0, joined, flipped, first_of[lo]);
+                r = emit_record(view, i0 + lo, flipped, first_of[lo]);
             }
             v[b >> 2] |= emit_byte(r, (uint32_t)(at + b - r.first)) << (8 * (b & 3));
         }
@@ -247,9 +277,9 @@ extern "C" int fgpu_stage3_fasta(fgpu_ctx* ctx, const fgpu_fasta_seq* seqs_host,
     if ((rc = emit_alloc(ctx, &out, (n_bytes + 15) & ~15ULL, "the file"))) return rc;      // (whole 16-byte stores)
     ctx->s3f_out = out;                          // (freed with the context from here on)
     FGPU_LAUNCH("s3f_join", k_emit_join, fgpu_blocks(n_words, 256), 256, (const fgpu_fasta_seq*)d_seqs, n, k, d_text, (const uint64_t*)d_word0, n_words, (uint64_t*)joined.p);
-    FGPU_LAUNCH("s3f_canon", k_emit_canon, fgpu_blocks(n, 4), 256, (const fgpu_fasta_seq*)d_seqs, n, k, (const uint64_t*)d_word0, (const uint64_t*)joined.p, d_flip);
-    FGPU_LAUNCH("s3f_ascii", k_emit_ascii, fgpu_blocks(n_bytes, EMIT_TILE), 256, (const fgpu_fasta_seq*)d_seqs, n, k, (const uint64_t*)d_word0, (const uint64_t*)d_byte0, n_bytes,
-                (const uint64_t*)joined.p, (const uint8_t*)d_flip, (uint4*)out);
+    const EmitSeqView view = {d_seqs, d_word0, (const uint64_t*)joined.p, k};
+    FGPU_LAUNCH("s3f_canon", k_emit_canon<EmitSeqView>, fgpu_blocks(n, 4), 256, view, n, d_flip);
+    FGPU_LAUNCH("s3f_ascii", k_emit_ascii<EmitSeqView>, fgpu_blocks(n_bytes, EMIT_TILE), 256, view, n, (const uint64_t*)d_byte0, n_bytes, (const uint8_t*)d_flip, (uint4*)out);
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
     *bytes = ctx->s3f_bytes = n_bytes;
     return FGPU_OK;
@@ -269,49 +299,184 @@ extern "C" int fgpu_stage3_fasta_take(fgpu_ctx* ctx, char* out, uint64_t bytes) 
     return FGPU_OK;
 }
 
+extern "C" int fgpu_stage3_fasta_joined(fgpu_ctx* ctx, const fgpu_joined* joined_host, const uint32_t* numbers_host, uint64_t n, const uint64_t* text_host,
+                                        uint64_t text_words, uint64_t* bytes) {
+    if (!ctx || !bytes || (n && (!joined_host || !numbers_host)) || (text_host == nullptr && text_words != 0) || n >= (1ULL << 32)) return FGPU_ERR_ARG;
+    if (ctx->phase != 0) { ctx->err = "fgpu_stage3_fasta_joined while a pass is open"; return FGPU_ERR_STATE; }
+    *bytes = 0;
+    const uint64_t* d_text = nullptr;
+    if (!text_host && n) {
+        if (!fgpu_s3j_text(ctx, &d_text)) { ctx->err = "fgpu_stage3_fasta_joined without a text: no fgpu_stage3_join whose results are still on the device"; return FGPU_ERR_STATE; }
+        text_words = ctx->s3j_totals[0];
+    }
+    for (uint64_t i = 0; i < n; i++) {           // every word the kernels will read lies in the text
+        const fgpu_joined& r = joined_host[i];
+        if (r.len < 1 || r.len >= (1u << 31) || r.text_word > text_words || ((uint64_t)r.len + 31) / 32 > text_words - r.text_word) {
+            ctx->err = "fgpu_stage3_fasta_joined: record " + std::to_string(i) + " reaches past the text, or has no bases or 2^31 and more";
+            return FGPU_ERR_ARG;
+        }
+    }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    emit_drop(ctx);
+    if (!n) return FGPU_OK;
+    int rc;
+    size_t scan_bytes = 0;
+    FGPU_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), ctx->stream));
+    EmitScratch work;
+    uint64_t at = 0;
+    const uint64_t o_recs = emit_take(at, n * sizeof(fgpu_joined)), o_num = emit_take(at, n * 4), o_cnt = emit_take(at, (n + 1) * 8), o_off = emit_take(at, (n + 1) * 8),
+                   o_scan = emit_take(at, scan_bytes), o_flip = emit_take(at, n), o_text = emit_take(at, text_host ? text_words * 8 : 0);
+    if ((rc = emit_alloc(ctx, &work.p, at, "the records"))) return rc;
+    char* wb = (char*)work.p;
+    fgpu_joined* d_recs = (fgpu_joined*)(wb + o_recs);
+    uint32_t* d_num = (uint32_t*)(wb + o_num);
+    uint64_t *d_bytes = (uint64_t*)(wb + o_cnt), *d_byte0 = (uint64_t*)(wb + o_off);
+    uint8_t* d_flip = (uint8_t*)(wb + o_flip);
+    FGPU_HIP(hipMemcpyAsync(d_recs, joined_host, n * sizeof(fgpu_joined), hipMemcpyHostToDevice, ctx->stream));
+    FGPU_HIP(hipMemcpyAsync(d_num, numbers_host, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (text_host) {
+        FGPU_HIP(hipMemcpyAsync(wb + o_text, text_host, text_words * 8, hipMemcpyHostToDevice, ctx->stream));
+        d_text = (const uint64_t*)(wb + o_text);
+    }
+    FGPU_LAUNCH("s3f_sizes_joined", k_emit_sizes_joined, fgpu_blocks(n + 1, 256), 256, (const fgpu_joined*)d_recs, (const uint32_t*)d_num, n, d_bytes);
+    FGPU_HIP(rocprim::exclusive_scan(wb + o_scan, scan_bytes, d_bytes, d_byte0, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), ctx->stream));
+    uint64_t n_bytes = 0;
+    FGPU_HIP(hipMemcpyAsync(&n_bytes, d_byte0 + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    void* out = nullptr;
+    if ((rc = emit_alloc(ctx, &out, (n_bytes + 15) & ~15ULL, "the file"))) return rc;      // (whole 16-byte stores)
+    ctx->s3f_out = out;                          // (freed with the context from here on)
+    const EmitJoinedView view = {d_recs, d_num, d_text};
+    FGPU_LAUNCH("s3f_canon_joined", k_emit_canon<EmitJoinedView>, fgpu_blocks(n, 4), 256, view, n, d_flip);
+    FGPU_LAUNCH("s3f_ascii_joined", k_emit_ascii<EmitJoinedView>, fgpu_blocks(n_bytes, EMIT_TILE), 256, view, n, (const uint64_t*)d_byte0, n_bytes, (const uint8_t*)d_flip, (uint4*)out);
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    *bytes = ctx->s3f_bytes = n_bytes;
+    return FGPU_OK;
+}
+
+namespace {
+
+struct EmitBuild {                               // the record arrays of the build and the map, on the host
+    std::vector<fgpu_contig> contigs;
+    std::vector<fgpu_build_call> calls;
+    std::vector<uint64_t> keys;
+    std::vector<fgpu_junction> recs;
+};
+// what fgpu_stage3_raw_contigs and fgpu_stage3_detip ask of the context, and the two record arrays of the build (no text, no list) brought over
+int emit_build_records(fgpu_ctx* ctx, const std::string& who, EmitBuild& b) {
+    const fgpu_contig* d_contigs = nullptr;
+    const fgpu_build_call* d_calls = nullptr;
+    if (!fgpu_s3b_view(ctx, &d_contigs, &d_calls, nullptr)) {
+        ctx->err = who + ": no fgpu_stage3_build whose results are still on the device (not run, or taken)";
+        return FGPU_ERR_ARG;
+    }
+    if (ctx->s3b_status != 0) {
+        ctx->err = who + ": the build stopped with status " + std::to_string(ctx->s3b_status) + " at call " + std::to_string(ctx->s3b_totals[0]) +
+                   ": the reference does not return from JunctionMap::buildContigGraph on this map";
+        return FGPU_ERR_ARG;
+    }
+    if (ctx->phase != 0) { ctx->err = who + " while a pass is open"; return FGPU_ERR_STATE; }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    const uint64_t n_calls = ctx->s3b_totals[0], nj = ctx->s3_count;
+    b.contigs.resize(n_calls); b.calls.resize(n_calls); b.keys.resize(nj); b.recs.resize(nj);
+    if (n_calls) {
+        FGPU_HIP(hipMemcpyAsync(b.contigs.data(), d_contigs, n_calls * sizeof(fgpu_contig), hipMemcpyDeviceToHost, ctx->stream));
+        FGPU_HIP(hipMemcpyAsync(b.calls.data(), d_calls, n_calls * sizeof(fgpu_build_call), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (nj) {                                    // the map as fgpu_stage3_set_junctions was handed it, in its order
+        const uint64_t* d_keys = (const uint64_t*)((const char*)ctx->s3_in.p + 64);
+        FGPU_HIP(hipMemcpyAsync(b.keys.data(), d_keys, nj * 8, hipMemcpyDeviceToHost, ctx->stream));
+        FGPU_HIP(hipMemcpyAsync(b.recs.data(), d_keys + nj, nj * sizeof(fgpu_junction), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    return FGPU_OK;
+}
+int emit_plan_failed(fgpu_ctx* ctx, const std::string& who, const char* plan, const char* unset, int st) {
+    ctx->err = st == FGPU_PLAN_UNSET ? who + ": on this graph " + unset + " (undefined in the reference)"
+                                     : who + ": the build's records are not a finished build of the map (" + plan + " status " + std::to_string(st) + ")";
+    return FGPU_ERR_STATE;
+}
+
+}  // namespace
+
 extern "C" int fgpu_stage3_raw_contigs(fgpu_ctx* ctx, int32_t read_length, uint64_t* bytes, fgpu_raw_info* info) {
     if (!ctx || !bytes) return FGPU_ERR_ARG;
     *bytes = 0;
     if (info) memset(info, 0, sizeof(*info));
-    const fgpu_contig* d_contigs = nullptr;
-    const fgpu_build_call* d_calls = nullptr;
-    if (!fgpu_s3b_view(ctx, &d_contigs, &d_calls, nullptr)) {
-        ctx->err = "fgpu_stage3_raw_contigs: no fgpu_stage3_build whose results are still on the device (not run, or taken)";
-        return FGPU_ERR_ARG;
-    }
-    if (ctx->s3b_status != 0) {
-        ctx->err = "fgpu_stage3_raw_contigs: the build stopped with status " + std::to_string(ctx->s3b_status) + " at call " + std::to_string(ctx->s3b_totals[0]) +
-                   ": the reference does not return from JunctionMap::buildContigGraph on this map";
-        return FGPU_ERR_ARG;
-    }
-    if (ctx->phase != 0) { ctx->err = "fgpu_stage3_raw_contigs while a pass is open"; return FGPU_ERR_STATE; }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    const uint64_t n_calls = ctx->s3b_totals[0], nj = ctx->s3_count;
-    std::vector<fgpu_contig> contigs(n_calls);
-    std::vector<fgpu_build_call> calls(n_calls);
-    std::vector<uint64_t> keys(nj);
-    std::vector<fgpu_junction> recs(nj);
-    if (n_calls) {
-        FGPU_HIP(hipMemcpyAsync(contigs.data(), d_contigs, n_calls * sizeof(fgpu_contig), hipMemcpyDeviceToHost, ctx->stream));
-        FGPU_HIP(hipMemcpyAsync(calls.data(), d_calls, n_calls * sizeof(fgpu_build_call), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (nj) {                                    // the map as fgpu_stage3_set_junctions was handed it, in its order
-        const uint64_t* d_keys = (const uint64_t*)((const char*)ctx->s3_in.p + 64);
-        FGPU_HIP(hipMemcpyAsync(keys.data(), d_keys, nj * 8, hipMemcpyDeviceToHost, ctx->stream));
-        FGPU_HIP(hipMemcpyAsync(recs.data(), d_keys + nj, nj * sizeof(fgpu_junction), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
+    EmitBuild b;
+    if (int rc = emit_build_records(ctx, "fgpu_stage3_raw_contigs", b)) return rc;
+    const uint64_t n_calls = b.contigs.size();
     std::vector<fgpu_fasta_seq> seqs(n_calls);
     uint64_t n = 0;
     fgpu_raw_info inf;
     memset(&inf, 0, sizeof(inf));
-    const int st = fgpu_raw_plan(keys.data(), recs.data(), nj, contigs.data(), calls.data(), n_calls, ctx->prm.k, read_length, seqs.data(), n_calls, &n, &inf);
-    if (st != FGPU_PLAN_OK) {
-        ctx->err = st == FGPU_PLAN_UNSET ? "fgpu_stage3_raw_contigs: on this graph ContigGraph::printContigs reads a contig pointer that was never set (undefined in the reference)"
-                                         : "fgpu_stage3_raw_contigs: the build's records are not a finished build of the map (fgpu_raw_plan status " + std::to_string(st) + ")";
-        return FGPU_ERR_STATE;
-    }
+    const int st = fgpu_raw_plan(b.keys.data(), b.recs.data(), b.keys.size(), b.contigs.data(), b.calls.data(), n_calls, ctx->prm.k, read_length, seqs.data(), n_calls, &n, &inf);
+    if (st != FGPU_PLAN_OK) return emit_plan_failed(ctx, "fgpu_stage3_raw_contigs", "fgpu_raw_plan", "ContigGraph::printContigs reads a contig pointer that was never set", st);
     if (int rc = fgpu_stage3_fasta(ctx, seqs.data(), n, nullptr, 0, bytes)) return rc;
     if (info) *info = inf;
+    return FGPU_OK;
+}
+
+extern "C" int fgpu_stage3_detip(fgpu_ctx* ctx, int32_t read_length, uint64_t* bytes, fgpu_tips_info* info) {
+    if (!ctx || !bytes) return FGPU_ERR_ARG;
+    *bytes = 0;
+    if (info) memset(info, 0, sizeof(*info));
+    EmitBuild b;
+    if (int rc = emit_build_records(ctx, "fgpu_stage3_detip", b)) return rc;
+    const uint64_t n_calls = b.contigs.size(), nj = b.keys.size();
+    // room that suffices unless a contig is copied (a call lies in one contig of the graph, a bubble's back in at most four records); asked again if not
+    std::vector<fgpu_tips_node> nodes(nj);
+    std::vector<fgpu_tips_contig> tigs(n_calls);
+    std::vector<uint64_t> list_first(n_calls + 1), print_first(n_calls + 1);
+    std::vector<fgpu_join_piece> pieces(n_calls), print_pieces(2 * n_calls);
+    std::vector<uint32_t> numbers(n_calls);
+    fgpu_tips_out out;
+    fgpu_tips_info inf;
+    int st = FGPU_PLAN_SHORT;
+    for (int pass = 0; pass < 2 && st == FGPU_PLAN_SHORT; pass++) {
+        if (pass) {
+            nodes.resize(out.n_nodes); tigs.resize(out.n_contigs); list_first.resize(out.n_contigs + 1); pieces.resize(out.n_pieces);
+            numbers.resize(out.n_print); print_first.resize(out.n_print + 1); print_pieces.resize(out.n_print_pieces);
+        }
+        memset(&out, 0, sizeof(out));
+        memset(&inf, 0, sizeof(inf));
+        out.nodes = nodes.data(); out.nodes_cap = nodes.size();
+        out.contigs = tigs.data(); out.list_first = list_first.data(); out.contigs_cap = tigs.size();
+        out.pieces = pieces.data(); out.pieces_cap = pieces.size();
+        out.print_first = print_first.data(); out.print_number = numbers.data(); out.print_cap = numbers.size();
+        out.print_pieces = print_pieces.data(); out.print_pieces_cap = print_pieces.size();
+        st = fgpu_tips_plan(b.keys.data(), b.recs.data(), nj, b.contigs.data(), b.calls.data(), n_calls, ctx->prm.k, read_length, &out, &inf);
+    }
+    if (st != FGPU_PLAN_OK) return emit_plan_failed(ctx, "fgpu_stage3_detip", "fgpu_tips_plan", "ContigGraph::deleteTipsAndClean or printContigs goes through a pointer that was never set or whose target is gone", st);
+    ctx->s3t_have = false;
+    std::vector<fgpu_joined> joined(out.n_print);
+    uint64_t totals[3];
+    if (int rc = fgpu_stage3_join(ctx, print_first.data(), out.n_print, print_pieces.data(), out.n_print_pieces, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, joined.data(), totals))
+        return rc;
+    if (int rc = fgpu_stage3_fasta_joined(ctx, joined.data(), numbers.data(), out.n_print, nullptr, 0, bytes)) return rc;
+    nodes.resize(out.n_nodes); tigs.resize(out.n_contigs); list_first.resize(out.n_contigs + 1); pieces.resize(out.n_pieces);
+    ctx->s3t_nodes.swap(nodes); ctx->s3t_contigs.swap(tigs); ctx->s3t_first.swap(list_first); ctx->s3t_pieces.swap(pieces);
+    ctx->s3t_have = true;
+    if (info) *info = inf;
+    return FGPU_OK;
+}
+
+extern "C" int fgpu_stage3_graph_take(fgpu_ctx* ctx, fgpu_tips_out* out) {
+    if (!ctx || !out) return FGPU_ERR_ARG;
+    out->n_nodes = out->n_contigs = out->n_pieces = out->n_print = out->n_print_pieces = 0;
+    if (!ctx->s3t_have) { ctx->err = "fgpu_stage3_graph_take: no fgpu_stage3_detip whose graph has not been taken"; return FGPU_ERR_STATE; }
+    const uint64_t nn = ctx->s3t_nodes.size(), nc = ctx->s3t_contigs.size(), np = ctx->s3t_pieces.size();
+    out->n_nodes = nn; out->n_contigs = nc; out->n_pieces = np;
+    if (out->nodes_cap < nn || out->contigs_cap < nc || out->pieces_cap < np || (nn && !out->nodes) || !out->list_first || (nc && !out->contigs) || (np && !out->pieces)) {
+        ctx->err = "fgpu_stage3_graph_take: an array is smaller than the graph (n_nodes, n_contigs, n_pieces say how large it is)";
+        return FGPU_ERR_ARG;
+    }
+    if (nn) memcpy(out->nodes, ctx->s3t_nodes.data(), nn * sizeof(fgpu_tips_node));
+    if (nc) memcpy(out->contigs, ctx->s3t_contigs.data(), nc * sizeof(fgpu_tips_contig));
+    memcpy(out->list_first, ctx->s3t_first.data(), (nc + 1) * 8);
+    if (np) memcpy(out->pieces, ctx->s3t_pieces.data(), np * sizeof(fgpu_join_piece));
+    std::vector<fgpu_tips_node>().swap(ctx->s3t_nodes); std::vector<fgpu_tips_contig>().swap(ctx->s3t_contigs);
+    std::vector<uint64_t>().swap(ctx->s3t_first); std::vector<fgpu_join_piece>().swap(ctx->s3t_pieces);
+    ctx->s3t_have = false;
     return FGPU_OK;
 }

@@ -134,6 +134,12 @@ int join_bad(fgpu_ctx* ctx, const std::string& what) {
 
 }  // namespace
 
+int fgpu_s3j_text(fgpu_ctx* ctx, const uint64_t** text) {
+    if (!ctx->s3j_out) return 0;
+    *text = (const uint64_t*)((const char*)ctx->s3j_out + join_layout(ctx->s3j_totals).text);
+    return 1;
+}
+
 extern "C" int fgpu_stage3_join(fgpu_ctx* ctx, const uint64_t* list_first, uint64_t n, const fgpu_join_piece* pieces, uint64_t n_pieces,
                                 const fgpu_contig* contigs_host, uint64_t n_contigs, const uint64_t* text_host, uint64_t text_words,
                                 const uint8_t* dist_host, uint64_t n_dist, const uint8_t* cov_host, uint64_t n_cov, fgpu_joined* out, uint64_t totals[3]) {

@@ -68,6 +68,8 @@
 #pragma weak fgpu_stage3_build
 #pragma weak fgpu_stage3_raw_contigs
 #pragma weak fgpu_stage3_fasta_take
+// ... and the one more of --detipped_contigs (ContigGraph::deleteTipsAndClean on that build)
+#pragma weak fgpu_stage3_detip
 
 using faucet_host::ReadSource;
 using faucet_host::TextSource;
@@ -98,6 +100,7 @@ struct Options {   // globals of src/Faucet.h:14-53
     int estimate_bits = 0;            // not a reference flag: -estimate_bits r, 2^r cells per level of the sketch (0: the library's default, 30)
     bool scan_kept = false;           // not a reference flag: --scan_kept, pass 2 scans the batches pass 1 kept; -read_scan_file may be left out
     bool raw_contigs = false;         // not a reference flag: --raw_contigs, <prefix>.raw_contigs.fasta (the file src/Faucet.cpp:314 would write) behind the scan outputs
+    bool detipped_contigs = false;    // not a reference flag: --detipped_contigs, <prefix>.detipped_contigs.fasta (what printContigs would write after the first deleteTipsAndClean of cleanGraph)
 };
 
 void argument_error() {   // src/Faucet.cpp:50-54
@@ -108,7 +111,8 @@ void argument_error() {   // src/Faucet.cpp:50-54
                     "-bloom_file <filename> -junctions_file <filename> --paired_ends --no_cleaning\n");
     fprintf(stderr, "Of this build: -gpus <n> -transport copy|rccl -batch_reads <n> -chunk_mb <n> --estimate -estimate_bits <r> "
                     "--scan_kept (pass 2 scans the reads pass 1 kept on the device: -read_scan_file may be left out) "
-                    "--raw_contigs (writes <prefix>.raw_contigs.fasta, the contigs of the graph build before any cleaning)\n");
+                    "--raw_contigs (writes <prefix>.raw_contigs.fasta, the contigs of the graph build before any cleaning)\n"
+                    "--detipped_contigs (writes <prefix>.detipped_contigs.fasta, the contigs after the first cleaning step, ContigGraph::deleteTipsAndClean)\n");
 }
 
 // src/Faucet.cpp:57-182 (with the missing `return 0` supplied and a bounds check on flag values)
@@ -145,6 +149,7 @@ int handle_arguments(int argc, char** argv, Options& o) {
         else if (a == "--estimate") o.estimate = true;
         else if (a == "--scan_kept") o.scan_kept = true;
         else if (a == "--raw_contigs") o.raw_contigs = true;
+        else if (a == "--detipped_contigs") o.detipped_contigs = true;
         else if (a == "-estimate_bits") { if (!val(v)) goto bad; o.estimate_bits = atoi(v); if (o.estimate_bits < FGPU_EST_MIN_BITS || o.estimate_bits > FGPU_EST_MAX_BITS) { fprintf(stderr, "-estimate_bits must be in %d..%d\n", FGPU_EST_MIN_BITS, FGPU_EST_MAX_BITS); return 1; } }
         else if (a == "--help" || a == "-h") { argument_error(); return 1; }
         else { fprintf(stderr, "Cannot parse tag %s\n", argv[i]); argument_error(); return 1; }
@@ -420,22 +425,43 @@ int write_raw_contigs(const Options& o, fgpu_ctx* ctx, const uint64_t* keys, con
     CHECK(fgpu_stage3_build(ctx, o.read_length, totals, &bi));
     clk.mark("  raw contigs: graph build");
     if (bi.status != 0) {      // the reference itself does not return from buildContigGraph on this map: no file
-        fprintf(stderr, "--raw_contigs: getContig call %llu of JunctionMap::buildContigGraph %s: the reference does not get as far as printing on this map, no %s.raw_contigs.fasta is written\n",
-                (unsigned long long)bi.stop_call, bi.status == 1 ? "trips an assert of the reference" : "never returns in the reference", o.file_prefix.c_str());
+        fprintf(stderr, "%s: getContig call %llu of JunctionMap::buildContigGraph %s: the reference does not get as far as printing on this map, no %s.%s.fasta is written\n",
+                o.raw_contigs ? "--raw_contigs" : "--detipped_contigs", (unsigned long long)bi.stop_call,
+                bi.status == 1 ? "trips an assert of the reference" : "never returns in the reference", o.file_prefix.c_str(), o.raw_contigs ? "raw_contigs" : "detipped_contigs");
         return 2;
     }
-    uint64_t bytes = 0;
-    fgpu_raw_info ri;
-    CHECK(fgpu_stage3_raw_contigs(ctx, o.read_length, &bytes, &ri));
-    std::vector<char> text(bytes ? bytes : 1);
-    CHECK(fgpu_stage3_fasta_take(ctx, text.data(), bytes));
-    const std::string path = o.file_prefix + ".raw_contigs.fasta";
-    FILE* f = fopen(path.c_str(), "wb");
-    if (!f || fwrite(text.data(), 1, bytes, f) != bytes || fclose(f) != 0) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 2; }
-    printf("Raw contigs: %llu records (%llu bubble, %llu off nodes, %llu isolated; %llu isolated below the read length left out) from %llu nodes, %llu bytes\n",
-           (unsigned long long)ri.records, (unsigned long long)ri.bubble_records, (unsigned long long)ri.node_contigs, (unsigned long long)ri.isolated_kept,
-           (unsigned long long)ri.isolated_dropped, (unsigned long long)ri.nodes, (unsigned long long)bytes);
-    clk.mark("  raw contigs: plan, emission, file");
+    auto write_file = [&](const std::string& path, uint64_t bytes) -> int {
+        std::vector<char> text(bytes ? bytes : 1);
+        CHECK(fgpu_stage3_fasta_take(ctx, text.data(), bytes));
+        FILE* f = fopen(path.c_str(), "wb");
+        if (!f || fwrite(text.data(), 1, bytes, f) != bytes || fclose(f) != 0) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 2; }
+        return 0;
+    };
+    if (o.raw_contigs) {
+        uint64_t bytes = 0;
+        fgpu_raw_info ri;
+        CHECK(fgpu_stage3_raw_contigs(ctx, o.read_length, &bytes, &ri));
+        if (int rc = write_file(o.file_prefix + ".raw_contigs.fasta", bytes)) return rc;
+        printf("Raw contigs: %llu records (%llu bubble, %llu off nodes, %llu isolated; %llu isolated below the read length left out) from %llu nodes, %llu bytes\n",
+               (unsigned long long)ri.records, (unsigned long long)ri.bubble_records, (unsigned long long)ri.node_contigs, (unsigned long long)ri.isolated_kept,
+               (unsigned long long)ri.isolated_dropped, (unsigned long long)ri.nodes, (unsigned long long)bytes);
+        clk.mark("  raw contigs: plan, emission, file");
+    }
+    if (o.detipped_contigs) {  // the first step of ContigGraph::cleanGraph (src/ContigGraph.cpp:211-215) on the same build, which is still on the device
+        uint64_t bytes = 0;
+        fgpu_tips_info ti;
+        if (fgpu_stage3_detip(ctx, o.read_length, &bytes, &ti) != FGPU_OK) {      // (a plan status other than OK among them: no file)
+            fprintf(stderr, "--detipped_contigs: %s: no %s.detipped_contigs.fasta is written\n", fgpu_last_error(ctx), o.file_prefix.c_str());
+            return 2;
+        }
+        if (int rc = write_file(o.file_prefix + ".detipped_contigs.fasta", bytes)) return rc;
+        printf("Detipped contigs: %llu tips deleted (and %llu back tips), %llu of %llu nodes left, %llu records (%llu bubble, %llu off nodes, %llu isolated; %llu isolated below "
+               "the read length left out), %llu bytes\n",
+               (unsigned long long)ti.tips, (unsigned long long)ti.back_tips, (unsigned long long)ti.print.nodes, (unsigned long long)ti.nodes_before,
+               (unsigned long long)ti.print.records, (unsigned long long)ti.print.bubble_records, (unsigned long long)ti.print.node_contigs,
+               (unsigned long long)ti.print.isolated_kept, (unsigned long long)ti.print.isolated_dropped, (unsigned long long)bytes);
+        clk.mark("  detipped contigs: plan, join, emission, file");
+    }
     return 0;
 }
 
@@ -524,7 +550,7 @@ int write_scan_outputs(const Options& o, fgpu_ctx* ctx, const fgpu_scan_stats& s
     printf("Weight of short pair filter: %f\n", short_pf.weight());
     if (o.paired_ends) printf("Weight of long pair filter: %f\n", long_pf.weight());
     printf("Number of junctions: %llu\n", (unsigned long long)order.size());
-    if (o.raw_contigs) return write_raw_contigs(o, ctx, keys.data(), recs.data(), order, clk);
+    if (o.raw_contigs || o.detipped_contigs) return write_raw_contigs(o, ctx, keys.data(), recs.data(), order, clk);
     return 0;
 }
 
@@ -1195,6 +1221,14 @@ int main(int argc, char** argv) {
             return 2;
         }
         if (o.just_load || o.from_junctions) { fprintf(stderr, "--raw_contigs needs the junction scan of this run: leave out --just_load_bloom and -junctions_file\n"); return 2; }
+    }
+    if (o.detipped_contigs) {    // ... likewise
+        if (!fgpu_stage3_set_junctions || !fgpu_stage3_build || !fgpu_stage3_detip || !fgpu_stage3_fasta_take) {
+            fprintf(stderr, "--detipped_contigs: the library this program is linked against lacks the entry points of the graph build and its first cleaning step "
+                            "(fgpu_stage3_set_junctions, fgpu_stage3_build, fgpu_stage3_detip, fgpu_stage3_fasta_take)\n");
+            return 2;
+        }
+        if (o.just_load || o.from_junctions) { fprintf(stderr, "--detipped_contigs needs the junction scan of this run: leave out --just_load_bloom and -junctions_file\n"); return 2; }
     }
     if (o.estimate && !(o.est_kmers_flag && o.est_sing_flag)) {     // pass 0, ahead of everything the two numbers decide (and of the lines that print them)
         if (o.k < 1 || o.k > 31) { fprintf(stderr, "k must be in 1..31 on this build\n"); return 1; }

@@ -1018,6 +1018,99 @@ int fgpu_stage3_join(fgpu_ctx* ctx, const uint64_t* list_first, uint64_t n, cons
                      const uint8_t* dist_host, uint64_t n_dist, const uint8_t* cov_host, uint64_t n_cov, fgpu_joined* out, uint64_t totals[3]);
 int fgpu_stage3_join_take(fgpu_ctx* ctx, uint64_t* text, uint64_t text_words, uint8_t* dist, uint64_t n_dist, uint8_t* cov, uint64_t n_cov);
 
+/* ---- Stage 3's first cleaning step: ContigGraph::deleteTipsAndClean on the build ----
+ * The first step of ContigGraph::cleanGraph (src/ContigGraph.cpp:211-215) on the graph fgpu_raw_plan makes, and printContigs behind it.
+ * Three layers, each callable alone.
+ *
+ * fgpu_tips_plan -- host only, no device, no text, no coverage list: WHICH piece lists the step leaves.  The graph is fgpu_raw_plan's, nodeMap
+ * a real std::unordered_map that took the same inserts, so that the two loops go over it in the reference's order and erase as they go
+ * (it = nodeMap.erase(it); nothing is inserted).  A contig is an ordered list of fgpu_join_piece; its length is the sum of the pieces' len
+ * minus (pieces - 1) k.
+ *   deleteTipsAndClean (:168-175): deleteTips, then validateNoneCollapsible only if deleteTips counted a tip; returns whether it did.
+ *   deleteTips (:575-615), per node: for i = 0..3, a contigs[i] that isTip while numPathsOut() > 1 (tested anew at every i) goes through
+ *     cutPath and deleteContig and is counted; a contigs[4] that isTip likewise, NOT counted; then isCollapsible -> collapseNode and the node
+ *     is erased, else testAndCutIfDegenerate -> the node is erased.
+ *   isTip (:324-330): fewer bases than read_length (size_t < int: the int goes to unsigned) and no node at the other end, or this node.
+ *   numPathsOut (src/ContigNode.cpp:217-225) counts coverages, of which a node has four: breakPath(4) (:280-283) clears contigs[4] only.
+ *   cutPath (:364-384): the contig forgets the node on the side Contig::getSide(node, index) names and the node breaks the path; a contig
+ *     whose two ends are the same node forgets both and the node breaks both paths.  deleteContig (:346-361) breaks what is left.
+ *   isCollapsible (:617-640): one path out, a back, a front (the FIRST contigs[0..3] that is set), neither with both ends on one node.
+ *   collapseNode (:1418-1467): back and the LAST contigs[0..3] that is set become back->concatenate(front, backSide, frontSide)
+ *     (src/Contig.cpp:83-109: back reversed if its side is 1, front if its side is 2 -- the list reversed, every flip toggled --, then the
+ *     lists appended; ends and indices are node1_p, ind1 of the oriented left and node2_p, ind2 of the oriented right, and setEnds
+ *     (:123-133) writes the result into those nodes' slots); with no node at either end the result becomes an isolated contig.
+ *   testAndCutIfDegenerate (:403-425): no path out -> cutPath(4); no back -> cutPath of every front.  It leaves contigs hanging on one node,
+ *     or on none: those are in no node's slot, are not isolated contigs, and are never printed.
+ *   validateNoneCollapsible (:709-736), per node: no path out and no back -> erased; isCollapsible -> collapseNode, erased;
+ *     testAndCutIfDegenerate -> erased.
+ * Then printContigs' two passes as fgpu_raw_plan walks them, the < 250 and >= read_length tests on joined lengths; a bubble record is the
+ * back's list as getNewConcatenatedContig (:1509-1530) orients it followed by the extension's.
+ * Outputs go into the arrays an fgpu_tips_out names; each n_* says how many entries are needed, whatever the room:
+ *   nodes       the nodes left, in map order: key, four coverages, per slot the number of a record of `contigs` or -1
+ *   contigs     the contigs in some node's slot (in order of first appearance), then the isolated ones in the list's order; contig c's list is
+ *               pieces[list_first[c] .. list_first[c + 1]): a CSR in fgpu_stage3_join's input form over the calls of the build
+ *   print       the records of the file in file order: print_pieces[print_first[r] .. print_first[r + 1]), print_number[r]
+ * Returns FGPU_PLAN_OK; FGPU_PLAN_UNSET wherever the reference would read or write through a pointer nobody set or that points to a node
+ * or contig that is gone (nothing is guessed); FGPU_PLAN_INPUT as fgpu_raw_plan; FGPU_PLAN_SHORT: an array has too little room (the n_*
+ * say how much is needed; nothing written is to be used).  With FGPU_PLAN_OK and FGPU_PLAN_SHORT `info` is filled.
+ *
+ * fgpu_stage3_fasta_joined -- the device: orient and print n strings that are joined already.  Record i is joined[i].len bases from word
+ * joined[i].text_word of the text (dist_first, cov_first, cov_sum, n_dist, n_cov are not read) and is numbered numbers[i].  text_host ==
+ * NULL: the text is the joined text of the last fgpu_stage3_join whose results are still on the device, read where it lies
+ * (FGPU_ERR_STATE if there is none) -- it is in the layout the printing kernels read, so nothing is copied; it is neither freed nor
+ * changed.  text_host != NULL: text_words words are uploaded first.  FGPU_ERR_ARG with nothing launched and earlier results untouched: a
+ * record that reaches past the text, a record of no bases or of 2^31 and more, n of 2^32 and more.  The file is fgpu_stage3_fasta's, record
+ * for record (canon_contig, ">Contig<number>"), and fgpu_stage3_fasta_take takes it; a file that was not taken is dropped.
+ *
+ * fgpu_stage3_detip -- all of it on a finished build that has not been taken and whose status is 0 (fgpu_stage3_raw_contigs'
+ * preconditions and messages): only the two record arrays of the build come to the host; fgpu_tips_plan; fgpu_stage3_join of the print
+ * records' lists over the build where it lies; fgpu_stage3_fasta_joined of the joined text where it lies.  A plan status other than
+ * FGPU_PLAN_OK is FGPU_ERR_STATE with a message.  THE CALL DROPS join results and a file that were not taken before it.  Afterwards
+ * fgpu_stage3_fasta_take gives the file (what printContigs writes after the first deleteTipsAndClean), fgpu_stage3_join_take the print
+ * records' strings, distances and coverages, fgpu_stage3_build_take the build, unchanged, and fgpu_stage3_graph_take the graph left.
+ *
+ * fgpu_stage3_graph_take -- copies the graph of the last fgpu_stage3_detip into the arrays `out` names (nodes, contigs, list_first,
+ * pieces and their caps; the print fields are not read) and forgets it; n_nodes, n_contigs, n_pieces are set whatever the room, and an
+ * array that is too small is FGPU_ERR_ARG: nothing is copied and the graph is still there (so caps of 0 ask for the sizes).
+ * FGPU_ERR_STATE if there is none.  list_first / pieces are valid input to fgpu_stage3_join on the same build: that is how a caller gets the
+ * sequences, distances, coverages and cov_sum of the cleaned graph's contigs for the next cleaning step. */
+typedef struct {
+    uint64_t key;
+    uint8_t  cov[4];
+    int32_t  slot[5];        /* record of fgpu_tips_out.contigs in contigs[0..4], -1: none */
+} fgpu_tips_node;
+typedef struct {
+    uint64_t node1, node2;   /* node1_p, node2_p as keys of nodeMap (has1 / has2 = 0: nullptr) */
+    uint32_t len;            /* joined bases */
+    uint8_t  has1, has2;
+    uint8_t  ind1, ind2;
+    uint8_t  isolated;       /* 1: an entry of isolated_contigs, in no node's slot */
+    uint8_t  reserved[7];
+} fgpu_tips_contig;
+typedef struct {
+    fgpu_tips_node*   nodes;        uint64_t nodes_cap, n_nodes;
+    fgpu_tips_contig* contigs;      uint64_t* list_first;  /* contigs_cap + 1 entries */  uint64_t contigs_cap, n_contigs;
+    fgpu_join_piece*  pieces;       uint64_t pieces_cap, n_pieces;
+    uint64_t*         print_first;  /* print_cap + 1 entries */  uint32_t* print_number;  uint64_t print_cap, n_print;
+    fgpu_join_piece*  print_pieces; uint64_t print_pieces_cap, n_print_pieces;
+} fgpu_tips_out;
+typedef struct {
+    uint64_t nodes_before;      /* entries of nodeMap before the step */
+    uint64_t tips;              /* what deleteTips returns */
+    uint64_t back_tips;         /* contigs[4] tips deleted, which it does not count */
+    uint64_t collapsed[2];      /* nodes collapseNode took out in deleteTips, in validateNoneCollapsible */
+    uint64_t degenerate[2];     /* nodes erased otherwise in the two loops */
+    uint32_t validated;         /* 1: validateNoneCollapsible ran */
+    uint32_t changed;           /* what deleteTipsAndClean returns */
+    fgpu_raw_info print;        /* the records of the file; nodes = the nodes left */
+} fgpu_tips_info;
+int fgpu_tips_plan(const uint64_t* keys, const fgpu_junction* recs, uint64_t n_junctions, const fgpu_contig* contigs, const fgpu_build_call* calls,
+                   uint64_t n_calls, int32_t k, int32_t read_length, fgpu_tips_out* out, fgpu_tips_info* info);
+int fgpu_stage3_fasta_joined(fgpu_ctx* ctx, const fgpu_joined* joined_host, const uint32_t* numbers_host, uint64_t n, const uint64_t* text_host,
+                             uint64_t text_words, uint64_t* bytes);
+int fgpu_stage3_detip(fgpu_ctx* ctx, int32_t read_length, uint64_t* bytes, fgpu_tips_info* info);
+int fgpu_stage3_graph_take(fgpu_ctx* ctx, fgpu_tips_out* out);
+
 /* ---- profiling --------------------------------------------------------------------------------- */
 typedef struct {
     char     name[48];
