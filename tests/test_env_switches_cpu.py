@@ -57,3 +57,28 @@ def test_retired_switches_are_named_nowhere_in_the_sources():
             continue
         found += [(os.path.relpath(path, ROOT), n) for n in sorted(set(retired.findall(_text(path))))]
     assert found == []
+
+
+# Switches no test sets, each with the reason.  Every other switch the sources read is set (or at least named) by some tests/test_*.py or by
+# tests/switch_child.py: "results never depend on them" is checked where a test can set them (tests/test_gpu_env_switches.py for most).
+NOT_SET_BY_ANY_TEST = {
+    "FAUCET_TRANSPORT": "the RCCL transport between ranks that share one device cannot run on a one-GPU box; fgpu_group_selftest covers it at world size 1",
+}
+
+
+def _named_by_the_tests():
+    me = os.path.abspath(__file__)
+    files = [p for p in glob.glob(os.path.join(ROOT, "tests", "test_*.py")) if os.path.abspath(p) != me] + [os.path.join(ROOT, "tests", "switch_child.py")]
+    names = set()
+    for path in files:
+        names.update(re.findall(r"\b" + NAME + r"\b", _text(path)))
+    return names
+
+
+def test_every_switch_is_set_by_a_test_or_listed_with_a_reason():
+    read, named = _read_from_the_environment(), _named_by_the_tests()
+    assert len(named) > 40                     # (the search itself still finds them)
+    assert all(reason.strip() for reason in NOT_SET_BY_ANY_TEST.values())
+    assert sorted(read - named - set(NOT_SET_BY_ANY_TEST)) == [], "read from the environment, set by no test and not listed in NOT_SET_BY_ANY_TEST"
+    assert sorted(set(NOT_SET_BY_ANY_TEST) & named) == [], "listed in NOT_SET_BY_ANY_TEST, but a test names it: the table is stale"
+    assert sorted(set(NOT_SET_BY_ANY_TEST) - read) == [], "listed in NOT_SET_BY_ANY_TEST, read nowhere"
