@@ -3,8 +3,8 @@
 the Stage-3 fixtures:
     make -C oracle ref && python tests/golden/make_detip_golden.py
 tests/golden/detip_driver.cpp (our own text: it includes the reference's headers; nodeMap and isolated_contigs are private, so its compile line
-carries -fno-access-control) is built against the compiled reference's objects under oracle/_ref/obj with the flags oracle/Makefile uses for
-ref_kat; the binary goes to oracle/_ref/ and is never committed.  For every fixture of tests/stage3_variants.py the driver reloads the map as
+carries -fno-access-control) is built by oracle/Makefile (target ref) against the compiled reference's objects under oracle/_ref/obj;
+the binary goes to oracle/_ref/ and is never committed.  For every fixture of tests/stage3_variants.py the driver reloads the map as
 tests/golden/raw_contigs_driver.cpp does (so the map's order is the stored raw_contigs_<name>.order.gz), builds the graph, runs the step, writes
 the graph as a table and prints the contigs.  Stored: detip_<name>.fasta.gz and detip_<name>.graph.gz (the table, and as its last line the counts
 the reference printed; tests/detip_golden.py says how it reads).  The 13 unvaried fixtures must return; a variant is kept only where the reference
@@ -28,7 +28,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 from tests import stage3_variants as V  # noqa: E402
 from tests.golden_util import Case  # noqa: E402
-from make_raw_contigs_golden import OUT, TIME_LIMIT, reference_tree  # noqa: E402
+from make_raw_contigs_golden import OUT, TIME_LIMIT  # noqa: E402
+from make_raw_contigs_golden import build_driver as raw_build_driver  # noqa: E402
 
 DRIVER = os.path.join(OUT, "detip_driver")
 
@@ -46,11 +47,7 @@ def check_sizes():
 
 
 def build_driver():
-    objs = [o for o in sorted(glob.glob(os.path.join(OUT, "obj", "*.o")))
-            if os.path.basename(o) not in ("Faucet.o", "Faucet_nomain.o", "binding.o", "wrap_shim.o")]
-    assert objs, "make -C oracle ref first"
-    subprocess.run(["g++", "-std=c++11", "-O1", "-w", "-fno-access-control", "-include", "vector", "-include", "cmath", "-I" + reference_tree(),
-                    os.path.join(HERE, "detip_driver.cpp")] + objs + ["-o", DRIVER], check=True)
+    raw_build_driver(DRIVER)
 
 
 def reference_files(c, bloom, lines, max_read_length):

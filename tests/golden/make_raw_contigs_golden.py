@@ -2,8 +2,8 @@
 """The reference's OWN <prefix>.raw_contigs.fasta (ContigGraph::printContigs on the graph JunctionMap::buildContigGraph returns,
 src/Faucet.cpp:314) for the Stage-3 fixtures:
     make -C oracle ref && python tests/golden/make_raw_contigs_golden.py
-tests/golden/raw_contigs_driver.cpp (our own text: it includes the reference's headers and calls public functions) is built against the
-compiled reference's objects under oracle/_ref/obj with the flags oracle/Makefile uses for ref_kat; the binary goes to oracle/_ref/ and is
+tests/golden/raw_contigs_driver.cpp (our own text: it includes the reference's headers and calls public functions) is built by
+oracle/Makefile (target ref) against the compiled reference's objects under oracle/_ref/obj; the binary goes to oracle/_ref/ and is
 never committed.  For every fixture of tests/stage3_variants.py the driver reloads the map with JunctionMap::buildFromFile, writes the map's
 iteration order (NOT the file's line order, and buildContigGraph depends on it), builds the graph and prints the contigs.  Stored:
 raw_contigs_<name>.fasta.gz and raw_contigs_<name>.order.gz (hex k-mers, one per line).  The 13 unvaried fixtures must return; a variant is
@@ -51,12 +51,9 @@ def check_sizes():
     assert not too_large, (limit, too_large)
 
 
-def build_driver():
-    objs = [o for o in sorted(glob.glob(os.path.join(OUT, "obj", "*.o")))
-            if os.path.basename(o) not in ("Faucet.o", "Faucet_nomain.o", "binding.o", "wrap_shim.o")]
-    assert objs, "make -C oracle ref first"
-    subprocess.run(["g++", "-std=c++11", "-O1", "-w", "-include", "vector", "-include", "cmath", "-I" + reference_tree(),
-                    os.path.join(HERE, "raw_contigs_driver.cpp")] + objs + ["-o", DRIVER], check=True)
+def build_driver(driver=DRIVER):
+    """oracle/Makefile holds the one recipe of both drivers"""
+    subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "REF=" + reference_tree(), os.path.relpath(driver, os.path.join(ROOT, "oracle"))], check=True)
 
 
 def reference_file(c, bloom, lines, max_read_length):

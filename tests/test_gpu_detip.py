@@ -24,6 +24,20 @@ def test_the_goldens_are_there():
     assert len(NAMES) == 28
 
 
+def device_table(ctx, info):
+    """the graph table with its counts line (tests/detip_golden.py) of the graph fgpu_stage3_detip left, taken with fgpu_stage3_graph_take: its
+    contigs' bases and coverages by a join over the build where it lies"""
+    graph = ctx.stage3_graph_take()
+    joined = ctx.stage3_join(graph["lists"]) if graph["lists"] else (np.zeros(0), [], [], [], [])
+    assert [len(s) for s in joined[1]] == [int(v) for v in graph["contigs"]["len"]]
+    nodes = [(int(n["key"]), [int(v) for v in n["cov"]], [int(v) for v in n["slot"]]) for n in graph["nodes"]]
+    contigs = [(int(t["node1"]) if t["has1"] else None, int(t["node2"]) if t["has2"] else None, int(t["len"]), int(t["ind1"]), int(t["ind2"]), int(t["isolated"]))
+               for t in graph["contigs"]]
+    table = D.table_of(nodes, contigs, [(len(s), float(a)) for s, a in zip(joined[1], joined[4])], info["changed"])
+    counts = "counts %d %d %d\n" % (info["tips"], info["print"]["nodes"], sum(info["collapsed"][1:] + info["degenerate"][1:]) if info["validated"] else -1)
+    return table + counts
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_detip_equals_the_references_file_and_graph(name):
     b, keys, recs = golden_build(name)[:3]
@@ -40,16 +54,7 @@ def test_detip_equals_the_references_file_and_graph(name):
     assert info["collapsed"] == [want["collapsed_0"], want["collapsed_1"]] and info["degenerate"] == [want["degenerate_0"], want["degenerate_1"]]
     assert {key: info["print"][key] for key in ("bubble_records", "node_contigs", "isolated_kept", "isolated_dropped")} == \
            {key: want[key] for key in ("bubble_records", "node_contigs", "isolated_kept", "isolated_dropped")}
-    # the graph left, its contigs' bases and coverages by a join over the build where it lies
-    graph = ctx.stage3_graph_take()
-    joined = ctx.stage3_join(graph["lists"]) if graph["lists"] else (np.zeros(0), [], [], [], [])
-    assert [len(s) for s in joined[1]] == [int(v) for v in graph["contigs"]["len"]]
-    nodes = [(int(n["key"]), [int(v) for v in n["cov"]], [int(v) for v in n["slot"]]) for n in graph["nodes"]]
-    contigs = [(int(t["node1"]) if t["has1"] else None, int(t["node2"]) if t["has2"] else None, int(t["len"]), int(t["ind1"]), int(t["ind2"]), int(t["isolated"]))
-               for t in graph["contigs"]]
-    table = D.table_of(nodes, contigs, [(len(s), float(a)) for s, a in zip(joined[1], joined[4])], info["changed"])
-    counts = "counts %d %d %d\n" % (info["tips"], info["print"]["nodes"], sum(info["collapsed"][1:] + info["degenerate"][1:]) if info["validated"] else -1)
-    assert table + counts == D.golden(name, "graph").decode()
+    assert device_table(ctx, info) == D.golden(name, "graph").decode()
     with pytest.raises(RuntimeError):                                          # taken: nothing left
         ctx.stage3_graph_take()
     again, info2 = ctx.stage3_detip(fx.max_read_length)                        # the build is still there, and unchanged

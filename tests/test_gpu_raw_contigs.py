@@ -221,8 +221,10 @@ def test_cli_raw_contigs(name, tmp_path):
     """`faucet --raw_contigs` writes <prefix>.raw_contigs.fasta behind the scan outputs: the restatement run in file order over the run's own
     .junctions and .bloom.  There is no reference file for this path -- the reference's main cannot print the file (src/Faucet.cpp:314 is
     commented out), and a map reloaded from .junctions iterates in another order than the one that was dumped -- so the tie to the reference is the
-    restatement, which tests/test_raw_contigs_ref_cpu.py pins to the compiled reference's own files.  Every other output file, and the exit
-    code, are those of a run without the flag."""
+    restatement, which tests/test_raw_contigs_ref_cpu.py pins to the compiled reference's own files on the stored fixtures and
+    tests/test_stage3_fuzz_cpu.py on maps made on the spot; tests/test_gpu_stage3_fuzz.py runs this command line on the reads behind those maps,
+    its scan files against faucet_ref's and its contig files against the restatement so pinned.  Every other output file, and the exit code, are
+    those of a run without the flag."""
     from tests.test_gpu_estimate_stream import output_files, written_input
     from tests.test_gpu_scan_kept_cli import run
     c = Case(name)

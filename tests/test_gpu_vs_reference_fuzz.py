@@ -3,6 +3,7 @@ tree as test infrastructure): the `faucet` command line and
 of tests/test_oracle_vs_reference_fuzz.py::random_run -- and every file both write (.bloom, .junctions in dump order, .short_pair_filter,
 .long_pair_filter) has to be the same bytes, and the scan's counters on stdout the same numbers."""
 import os
+import pathlib
 import re
 import subprocess
 
@@ -46,24 +47,32 @@ def cli_against_reference(path, args, tmp_path, cli_extra=(), env=None, writes=(
                            env=dict(os.environ, **(dict(FGPU_DEBUG_DELTA_CHECK="1") if cli_extra else {}), **(env or {})) if tag == "gpu" else None)
         outs[tag] = (r, d)
     (rr, dr), (rg, dg) = outs["ref"], outs["gpu"]
+    same_as_the_reference(rr.stdout, dr, rg, dg, args, writes)
+    return rr.stdout, rg.stdout
+
+
+def same_as_the_reference(ref_stdout, dr, rg, dg, args, writes=(".bloom", ".junctions"), own_files=(), own_lines=()):
+    """the comparison: `rg`, a finished run of the command line with `args` into directory `dg`, against the reference's stdout and its files
+    in `dr`.  `own_files`, `own_lines`: endings of files and beginnings of stdout lines that only the command line has (Stage-3 outputs the
+    reference's main does not write); everything else it writes or prints is held to the reference"""
+    dr, dg = pathlib.Path(dr), pathlib.Path(dg)
     assert rg.returncode == (0 if "--no_cleaning" in args else 3), rg.stderr[-2000:]      # (the reference goes on into its contig graph and may crash there)
     assert "merged in-map planes differ" not in rg.stderr, rg.stderr[-2000:]
-    mine = sorted(os.listdir(dg))
+    mine = sorted(f for f in os.listdir(dg) if not f.endswith(tuple(own_files) or ("\0",)))
     assert all(any(f.endswith(ext) for f in mine) for ext in writes), mine
     for f in mine:                                   # every file this build writes, the reference wrote too, with the same bytes
         assert os.path.exists(dr / f), f
         assert (dg / f).read_bytes() == (dr / f).read_bytes(), f
     for line in LINES:
-        want = [ln.strip() for ln in rr.stdout.splitlines() if ln.startswith(line)]
+        want = [ln.strip() for ln in ref_stdout.splitlines() if ln.startswith(line)]
         got = [ln.strip() for ln in rg.stdout.splitlines() if ln.startswith(line)]
         assert want == got, (line, want, got)
     assert re.search(r"Distinct junctions: \d+", rg.stdout)
     # ... and the log as a whole: what the command line prints is, line for line, what the reference prints up to the point where its
     # contig-graph stage begins (wall-clock numbers and the progress lines aside; the output prefix differs by construction)
-    a = [ln.replace(str(dr), "<prefix>") for ln in stdout_lines(rr.stdout)]
-    b = [ln.replace(str(dg), "<prefix>") for ln in stdout_lines(rg.stdout)]
+    a = [ln.replace(str(dr), "<prefix>") for ln in stdout_lines(ref_stdout)]
+    b = [ln.replace(str(dg), "<prefix>") for ln in stdout_lines(rg.stdout) if not ln.startswith(tuple(own_lines) or ("\0",))]
     assert b and b[-1].startswith("Number of junctions:") and a[:len(b)] == b, [x for x in zip(a, b) if x[0] != x[1]][:5]
-    return rr.stdout, rg.stdout
 
 
 @pytest.mark.parametrize("seed", range(100, 112))

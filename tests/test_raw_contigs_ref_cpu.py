@@ -49,20 +49,25 @@ def golden_order(name):
         return np.array([int(x, 16) for x in f.read().split()], dtype=np.uint64)
 
 
+def build_over(f, order, k):
+    """the Build of a Finder's map with its junctions in the order of the keys `order`, with the permuted keys and records"""
+    row = {int(x): r for r, x in enumerate(f.keys)}
+    perm = np.array([row[int(x)] for x in order], dtype=np.int64)
+    assert sorted(perm.tolist()) == list(range(len(f.keys)))
+    keys, recs = f.keys[perm], f.recs[perm]
+
+    def find_neighbor(alive, kmer, index):
+        a = np.empty(len(perm), dtype=bool)
+        a[perm] = alive
+        return f.find(a, kmer, index)
+    return G.build_contig_graph(find_neighbor, keys, recs["cov"], k), keys, recs
+
+
 def golden_build(name):
     """(Build, keys, records, Finder) of one fixture with its map in the golden order; made once, shared, left unchanged"""
     if name not in _golden_builds:
         fx, f = _fixture(name), finder_of(name)
-        row = {int(x): r for r, x in enumerate(f.keys)}
-        perm = np.array([row[int(x)] for x in golden_order(name)], dtype=np.int64)
-        assert sorted(perm.tolist()) == list(range(len(f.keys)))
-        keys, recs = f.keys[perm], f.recs[perm]
-
-        def find_neighbor(alive, kmer, index):
-            a = np.empty(len(perm), dtype=bool)
-            a[perm] = alive
-            return f.find(a, kmer, index)
-        _golden_builds[name] = (G.build_contig_graph(find_neighbor, keys, recs["cov"], fx.case.k), keys, recs, f)
+        _golden_builds[name] = (*build_over(f, golden_order(name), fx.case.k), f)
     return _golden_builds[name]
 
 

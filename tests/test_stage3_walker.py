@@ -33,6 +33,14 @@ def _map_of(lines):
     return keys, recs
 
 
+Params = collections.namedtuple("Params", "k j counters spacer max_read_length")        # what a Fixture's `case` is asked for, of a map that is no golden case
+
+
+def fixture_from(bloom, lines, k, n_hash, j, max_read_length, calls=None, spacer=100):
+    """a Fixture of (filter bytes, .junctions lines, k, hash count, j, max read length) made on the spot, no golden case behind it"""
+    return Fixture(Params(k, j, {"n_hash": n_hash}, spacer, max_read_length), np.asarray(bloom, dtype=np.uint8), *_map_of(lines), max_read_length, calls, lines)
+
+
 def _fixture(name):
     """a fixture's case, filter bytes, map (keys, recs, .junctions lines), max_read_length and the reference's calls; made once, shared, left unchanged"""
     if name not in _cache:
@@ -82,9 +90,14 @@ class _OracleProbe:
 
 
 def _device(name):
+    return device_of(_fixture(name))
+
+
+def device_of(fx):
+    """a context of the fixture's shape with its filter uploaded as bloo2"""
     from faucet_amd import _lib as L
     from faucet_amd import api
-    c, bloom = _fixture(name)[:2]
+    c, bloom = fx[:2]
     ctx = api.Context(c.k, len(bloom) * 8, c.counters["n_hash"], j=c.j, max_spacer_dist=c.spacer)
     ctx.bloom_upload(L.BLOO2, bloom)
     return ctx
