@@ -631,6 +631,8 @@ bool fgpu_walk_no_overlap();                                                    
 int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces);
 int fgpu_stage_scan_need(fgpu_ctx* ctx);                                           // whole batch: the need plane cleared, the hash plane there
 int fgpu_stage_scan_need_lookup(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi);      // words [w_lo, w_hi): snapshot planes and hashes
+// FGPU_DEBUG_DELTA_CHECK=1: a plane the per-lane form of a kernel has just made in scratch (on `st`) against the dense form's; differing words count as mismatches
+int fgpu_dbg_compare_planes(fgpu_ctx* ctx, hipStream_t st, const uint64_t* scratch, const uint64_t* plane, uint64_t n_words, const char* what, uint64_t batch);
 int fgpu_stage_scan_need_prewalk(fgpu_ctx* ctx, uint64_t w_lo, uint64_t w_hi);     // the pieces that start in those words: their need bits
 int fgpu_scan_refresh_planes(fgpu_ctx* ctx, BatchBufs* b);
 int fgpu_scan_build_cand(fgpu_ctx* ctx, BatchBufs* b);

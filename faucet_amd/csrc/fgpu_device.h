@@ -144,6 +144,8 @@ __device__ __forceinline__ uint64_t fd_mix(uint64_t x) {
 }
 
 __device__ __forceinline__ int fd_lane() { return (int)(threadIdx.x & 63); }
+// the wave's index in its block, as a value the compiler knows to be uniform: what is computed from it stays in scalar registers
+__device__ __forceinline__ uint32_t fd_wave() { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 // What the lanes of a wave counted, added to a counter by lane 0 (a sum of zero costs no atomic)
 __device__ __forceinline__ void wave_add(unsigned long long* dst, unsigned long long v) {

@@ -14,12 +14,17 @@
 //   cf0,cf1 / cb0,cb1  two bit-planes of the NbJCheckKmer increment (0..3) at (p, FORWARD) / (p, BACKWARD)
 // plus the piece list {start, windows} in stream (= processing) order.
 //
+// Two ways to keep a wave busy where only some positions have work: k_scan_valid and k_scan_flags gather the work masks of several words
+// and hand the set bits out densely, 64 items per round (dense_hits.h); k_scan_flags_sm, whose items are long chains of uneven length, runs
+// a state machine per lane over a pool the wave shares.  k_scan_valid_lane, a lane per position, is k_scan_valid's check
+// (FGPU_DEBUG_DELTA_CHECK=1).
+//
 // Roofline: random bit probes into bloo2 (Infinity-Cache / HBM); algorithmic bytes per k-mer:
 //   L/(L-k+1) B of bases + 64 B per bit test the reference semantics perform (validity, alternate extensions, jcheck).
 #include <algorithm>
 
 #include "fgpu_ctx.h"
-#include "fgpu_flags.h"
+#include "dense_hits.h"
 
 namespace {
 
@@ -35,10 +40,61 @@ __global__ void __launch_bounds__(256) k_scan_same(const uint64_t* __restrict__ 
     if (__ballot(differ) && fd_lane() == 0) *same = 0;
 }
 
-// fixed grid striding over the stream, lanes = consecutive positions; counters live in registers until the wave retires.
+// One getValidReads probe per window.  sure/same (optional): occurrences the load pass routed to bloo2 are in the filter by construction -- when
+// the batch is the load batch (same != 0) their answer is "present" without a probe; on a scan of the loaded reads that is three windows in
+// four.  The others -- the items -- pay the k-mer's two hashes and a chain of 1 to n_hash dependent probes with early exit: a wave takes
+// eight words at a time and hands the items out densely (dense_hits.h), so that a chain's latency and the hashes' instructions are paid per
+// 64 items, not per 64 positions.  Everything a round keeps is uniform in the wave: the masks of the windows that exist (ok), the sure words.
+__global__ void __launch_bounds__(256) k_scan_valid(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ bad,
+                                                    uint64_t T, uint64_t n_words, FdParams fp, const uint32_t* __restrict__ bloom,
+                                                    const uint64_t* __restrict__ sure, const uint32_t* __restrict__ same,
+                                                    uint64_t* __restrict__ valid, DevCounters* cnt) {
+    constexpr int U = 8;
+    unsigned long long n_ok = 0, n_reused = 0;      // lane 0 counts for its wave
+    const int lane = fd_lane();
+    const bool reuse = sure && *same != 0;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const uint64_t n_chunks = (n_words + U - 1) / U;
+    for (uint64_t chunk = (uint64_t)blockIdx.x * (blockDim.x >> 6) + fd_wave(); chunk < n_chunks; chunk += n_waves) {      // (uniform in the wave)
+        const uint64_t w0 = chunk * U;
+        uint64_t known[U], items[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t p = (w0 + u) * 64 + lane;
+            const bool ok = w0 + u < n_words && p < T && fd_window_ok(bad, p, fp.k);
+            const uint64_t okm = __ballot(ok);
+            known[u] = reuse && w0 + u < n_words ? okm & sure[w0 + u] : 0ULL;
+            items[u] = okm & ~known[u];
+            if (lane == 0) { n_ok += __popcll(okm); n_reused += __popcll(known[u]); }
+        }
+        const DenseItems<U> it(items);
+        DenseBits<U> probed;
+        for (int r = 0; r * 64 < it.total(); r++) {
+            const int t = r * 64 + lane;
+            bool v = false;
+            if (t < it.total()) {
+                int q, bit;
+                it.item(t, q, bit);
+                const uint64_t p = (w0 + (uint64_t)q) * 64 + (uint64_t)bit;
+                v = fd_bloom_contains_canon(bloom, fd_canon(fd_kmer_at(codes, p, fp.k), fp.k), fp.tai_mask, fp.n_hash);
+            }
+            probed.put(r, __ballot(v));
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t vm = known[u] | probed.word(it, u);
+            if (lane == 0 && w0 + u < n_words) valid[w0 + u] = vm;
+        }
+    }
+    block_add(&cnt->kmers, n_ok);
+    block_add(&cnt->valid_reused, n_reused);
+}
+
+// The per-lane form: fixed grid striding over the stream, lanes = consecutive positions; counters live in registers until the wave retires.
+// FGPU_DEBUG_DELTA_CHECK=1 runs it behind k_scan_valid into a plane and counters of its own and compares (fgpu_stage_scan_pure).
 // sure/same (optional): occurrences the load pass routed to bloo2 are in the filter by construction -- when the batch is the
 // load batch (same != 0) their answer is "present" without a probe.
-__global__ void __launch_bounds__(256) k_scan_valid(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ bad,
+__global__ void __launch_bounds__(256) k_scan_valid_lane(const uint64_t* __restrict__ codes, const uint64_t* __restrict__ bad,
                                                     uint64_t T, uint64_t n_words, FdParams fp, const uint32_t* __restrict__ bloom,
                                                     const uint64_t* __restrict__ sure, const uint32_t* __restrict__ same,
                                                     uint64_t* __restrict__ valid, DevCounters* cnt) {
@@ -240,22 +296,12 @@ __global__ void __launch_bounds__(256) k_scan_flags(const uint64_t* __restrict__
             }
         }
         uint64_t m[8];
-        int cum[9];
-        cum[0] = 0;
 #pragma unroll
-        for (int q = 0; q < 8; q++) {
-            m[q] = __shfl(mine, q, 64);
-            cum[q + 1] = cum[q] + __popcll(m[q]);
-        }
-        for (int t = lane; t < cum[8]; t += 64) {
-            // which mask holds item t (uniform bounds, per-lane t), which bit of it
-            int q = 0;
-            uint64_t mq = m[0];
-            int before = 0;
-#pragma unroll
-            for (int c = 1; c < 8; c++)
-                if (t >= cum[c]) { q = c; mq = m[c]; before = cum[c]; }
-            const int bit = select_bit(mq, t - before);
+        for (int q = 0; q < 8; q++) m[q] = __shfl(mine, q, 64);
+        const DenseItems<8> it(m);      // (dense_hits.h: the hand-out this kernel had first)
+        for (int t = lane; t < it.total(); t += 64) {
+            int q, bit;
+            it.item(t, q, bit);
             const uint64_t w = w_lo + chunk * 4 + (q & 3);
             const uint64_t pos = w * 64 + bit;
             const uint64_t km = fd_kmer_at(codes, pos, fp.k);
@@ -650,9 +696,30 @@ int fgpu_stage_scan_pure(fgpu_ctx* ctx, uint64_t* n_pieces, bool one_range) {
             FGPU_LAUNCH("scan_same", k_scan_same, fgpu_grid(ncw, 256), 256, (const uint64_t*)bb.codes.p, (const uint64_t*)kept->codes_p(), ncw,
                         (const uint64_t*)bb.bad.p, (const uint64_t*)kept->bad_p(), bb.n_words, (uint32_t*)bb.same.p);
     }
+    DevCounters dbg_before;      // (FGPU_DEBUG_DELTA_CHECK=1: the counters as the batch found them)
+    if (ctx->dbg_delta_check) FGPU_HIP(hipMemcpyAsync(&dbg_before, ctx->counters, sizeof(DevCounters), hipMemcpyDeviceToHost, ctx->stream));
     FGPU_LAUNCH("scan_valid", k_scan_valid, grid, 256, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p, bb.T, bb.n_words, ctx->fd,
                 (const uint32_t*)ctx->bloo2, kept ? (const uint64_t*)kept->sure.p : (const uint64_t*)nullptr,
                 kept ? (const uint32_t*)bb.same.p : (const uint32_t*)nullptr, (uint64_t*)bb.valid.p, ctx->counters);
+    if (ctx->dbg_delta_check) {      // the per-lane form behind the dense one: its plane word for word, its two counters
+        uint64_t* scratch = nullptr;
+        FGPU_HIP(hipMalloc(&scratch, bb.n_words * 8 + sizeof(DevCounters)));
+        DevCounters* scnt = (DevCounters*)(scratch + bb.n_words);
+        FGPU_HIP(hipMemsetAsync(scnt, 0, sizeof(DevCounters), ctx->stream));
+        hipLaunchKernelGGL(k_scan_valid_lane, dim3(grid), dim3(256), 0, ctx->stream, (const uint64_t*)bb.codes.p, (const uint64_t*)bb.bad.p, bb.T, bb.n_words, ctx->fd,
+                           (const uint32_t*)ctx->bloo2, kept ? (const uint64_t*)kept->sure.p : (const uint64_t*)nullptr,
+                           kept ? (const uint32_t*)bb.same.p : (const uint32_t*)nullptr, scratch, scnt);
+        DevCounters now, lane_form;
+        FGPU_HIP(hipMemcpyAsync(&now, ctx->counters, sizeof(DevCounters), hipMemcpyDeviceToHost, ctx->stream));
+        FGPU_HIP(hipMemcpyAsync(&lane_form, scnt, sizeof(DevCounters), hipMemcpyDeviceToHost, ctx->stream));
+        rc = fgpu_dbg_compare_planes(ctx, ctx->stream, scratch, (const uint64_t*)bb.valid.p, bb.n_words, "dense validity pass: valid plane against the per-lane pass's", bb.seq);
+        (void)hipFree(scratch);
+        if (rc) return rc;
+        if (now.kmers - dbg_before.kmers != lane_form.kmers || now.valid_reused - dbg_before.valid_reused != lane_form.valid_reused) {
+            ctx->refresh_mismatch++;
+            fprintf(stderr, "[fgpu] dense validity pass: counters differ from the per-lane pass's, batch %llu\n", (unsigned long long)bb.seq);
+        }
+    }
     const int check_segment = ctx->fd.k < 2 * ctx->fd.j + 2;   // otherwise a run of k windows already implies the length gate
     FGPU_LAUNCH("scan_pieces", k_scan_pieces, wgrid, 256, (const uint64_t*)bb.valid.p, (const uint64_t*)bb.bad.p, bb.n_words, ctx->fd,
                 check_segment, (unsigned long long*)bb.pm.p, (uint64_t*)bb.ps.p, ctx->counters);

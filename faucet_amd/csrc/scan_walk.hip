@@ -15,6 +15,7 @@
 //                      positions) register their k-mer's hash in a small window table, and so do the keys created since that snapshot
 //                      was taken (lists kept by k_delta_collect: the batches walked since, this batch's earlier windows)
 //   B  k_walk_link     every position: probe the window table; a hit unions the piece with the candidate's owner
+//                      (the filter's hits are resolved densely, 64 to a wave round: dense_hits.h; k_walk_link_lane, a lane per position, is its check)
 //   C  k_walk_cluster  flatten the union-find; list each cluster's members in ascending piece order
 //   D  k_walk_dyn      one thread per cluster replays its pieces IN ORDER against the live table; clusters are
 //                      disjoint in the keys they touch, so they run concurrently without changing any result
@@ -34,7 +35,7 @@
 #include <cstring>
 #include <algorithm>
 
-#include "fgpu_flags.h"
+#include "dense_hits.h"
 #include "walk_tables.h"
 
 namespace {
@@ -206,7 +207,95 @@ __global__ void __launch_bounds__(256) k_walk_register(Planes pl, FdParams fp, W
 }
 
 // ---- B: link every piece to the owners of the candidate k-mers that occur on it ---------------------
+__device__ __forceinline__ uint32_t wt_owner_unfiltered(const WTable& wt, uint32_t h32, uint64_t& slot) {   // the caller has seen the key's filter bit set
+    uint64_t s = (uint64_t)h32 & wt.mask;
+    for (uint64_t n = 0; n <= wt.mask; n++) {
+        const uint64_t w = wt.keys[s];
+        if ((w & W_EPOCH_MASK) != wt.epoch) return U_INF;
+        if ((uint32_t)(w >> W_OWNER_BITS) == h32) { slot = s; return (uint32_t)(w & W_OWNER_MASK); }
+        s = (s + 1) & wt.mask;
+    }
+    return U_INF;
+}
+
+constexpr int LINK_U = 4;      // words per wave and round (eight: 32 registers, and 225 us per launch where four take 209; profiles/dense_hits_ab.txt)
 __global__ void __launch_bounds__(256) k_walk_link(Planes pl, FdParams fp, WTable wt, uint32_t* parent, uint64_t lo, uint64_t hi,
+                                                   uint64_t pos_end, uint32_t* roots_state) {
+    // a fixed grid strides over the window, 256 U positions per block and round.  Phase 1, a lane per position: the loads of U positions per
+    // thread (hash, then filter word) are in flight together.  Phase 2: the few positions whose filter bit is set -- the ones that go on to a
+    // chain of dependent loads (table slot, piece of the position, its record, the union) -- are handed out densely over the wave's U words
+    // (dense_hits.h): one chain per 64 hits, not one per word that holds a hit.  The unions and the owner's atomicMin commute: their order is free.
+    constexpr int U = LINK_U;
+    const WinDesc wd = make_window(pl, lo, hi);
+    if (roots_state && blockIdx.x == 0 && threadIdx.x == 0) { roots_state[0] = 0; roots_state[1] = 0; }   // roots listed / handed out (k_walk_cluster, k_walk_dyn)
+    const int lane = fd_lane();
+    const uint64_t base0 = wd.lo & ~63ULL, lk_end = (pos_end + 63) & ~63ULL;
+    // (base and pos_end are the block's: every wave of the block makes the same trips)
+    for (uint64_t base = base0 + (uint64_t)blockIdx.x * (256 * U); base < pos_end; base += (uint64_t)gridDim.x * (256 * U)) {
+        const uint64_t wave_base = base + 64 * fd_wave();      // word u of this wave's round: positions wave_base + 256 u ...
+        uint32_t h[U];
+        bool act[U];
+        uint64_t fm[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t p = wave_base + (uint64_t)u * 256 + lane;
+            act[u] = p >= wd.lo && p < pos_end && ((pl.pm[p >> 6] >> (p & 63)) & 1ULL);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) h[u] = act[u] ? pl.kh[wave_base + (uint64_t)u * 256 + lane] : 0u;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t b = wt_filter_bit(wt, h[u]);
+            const bool f = act[u] && ((wt.bits[b >> 5] >> (b & 31)) & 1u);
+            fm[u] = __ballot(f);
+        }
+        const DenseItems<U> it(fm);
+        DenseBits<U> hits;
+        for (int r = 0; r * 64 < it.total(); r++) {
+            const int t = r * 64 + lane;
+            const bool have = t < it.total();
+            int q = 0, bit = 0;
+            if (have) it.item(t, q, bit);
+            uint32_t hq = 0;      // the item's hash, from the lane that loaded it
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint32_t v = (uint32_t)__shfl((int)h[u], bit, 64);
+                if (q == u) hq = v;
+            }
+            bool hit = false;
+            if (have) {
+                const uint64_t p = wave_base + (uint64_t)q * 256 + (uint64_t)bit;
+                uint64_t slot = 0;
+                uint32_t owner = wt_owner_unfiltered(wt, hq, slot);
+                if (owner != U_INF) {
+                    uint32_t li;
+                    uint2 pc;
+                    if (piece_in_window(pl, wd, p, li, pc)) {
+                        hit = true;
+                        if (owner == W_NO_OWNER) {   // a key created since the snapshot: the first piece it occurs on becomes its owner, the others join it
+                            const unsigned long long mine = (unsigned long long)(wt.epoch | ((uint64_t)hq << W_OWNER_BITS) | (uint64_t)li);
+                            owner = (uint32_t)(atomicMin((unsigned long long*)&wt.keys[slot], mine) & W_OWNER_MASK);
+                        }
+                        if (owner != li && owner != W_NO_OWNER) uf_union(parent, li, owner);
+                    }
+                }
+            }
+            hits.put(r, __ballot(hit));
+        }
+        // lk plane: the positions that hold a registered k-mer -- the only ones at which the walk has to ask the live table.  Every word of the
+        // window's range is written once, zeros included
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t m = hits.word(it, u);
+            const uint64_t pw = wave_base + (uint64_t)u * 256;
+            if (lane == 0 && pw < lk_end) pl.lk[pw >> 6] = m;
+        }
+    }
+}
+
+// The per-lane form of the link pass: a lane resolves its own hits, one position after another.  FGPU_DEBUG_DELTA_CHECK=1 runs it behind
+// k_walk_link and behind k_walk_link_sparse and compares the lk planes (walk_link).
+__global__ void __launch_bounds__(256) k_walk_link_lane(Planes pl, FdParams fp, WTable wt, uint32_t* parent, uint64_t lo, uint64_t hi,
                                                    uint64_t pos_end, uint32_t* roots_state) {
     // a fixed grid strides over the window, 1024 positions per block and round: the loads of four positions per thread (hash, then
     // filter word) are in flight together -- one position per thread left this kernel waiting on two dependent loads per 256-thread block
@@ -2650,6 +2739,21 @@ static int walk_dbg_compare(fgpu_ctx* ctx, hipStream_t st, const uint64_t* plane
     return FGPU_OK;
 }
 
+// ... for the pure stage's own kernels (scan_pure.hip): the full pass has been issued on `st` into scratch by the caller
+int fgpu_dbg_compare_planes(fgpu_ctx* ctx, hipStream_t st, const uint64_t* scratch, const uint64_t* plane, uint64_t n_words, const char* what, uint64_t batch) {
+    unsigned long long* out = nullptr;
+    FGPU_HIP(hipMalloc(&out, 32));
+    FGPU_HIP(hipMemsetAsync(out, 0, 32, st));
+    hipLaunchKernelGGL(k_dbg_diff, dim3(64), dim3(256), 0, st, scratch, plane, n_words, out, 0);
+    unsigned long long h[4] = {0, 0, 0, 0};
+    FGPU_HIP(hipMemcpyAsync(h, out, 32, hipMemcpyDeviceToHost, st));
+    FGPU_HIP(hipStreamSynchronize(st));
+    ctx->refresh_mismatch += h[0];
+    if (h[0]) fprintf(stderr, "[fgpu] %s: %llu words differ, batch %llu\n", what, h[0], (unsigned long long)batch);
+    (void)hipFree(out);
+    return FGPU_OK;
+}
+
 // Batches that were prepared before their turn (multi-GPU shards; scan_prepare / scan_walk_prepared) carry snapshot planes of a table that has
 // since been replaced or walked on by an unknown number of batches: made again here, behind the previous batch's walk.  (The preview -- need
 // plane and junction tests -- stays what it was: it is checked by the walk, not trusted.)  *cand_ok: see WalkBatch.
@@ -2763,25 +2867,28 @@ static int walk_register(fgpu_ctx* ctx, const WalkKnobs& kn, const WalkBatch& wb
 // Step B: every position against the window table -- or, for the first window of a prepared batch with a candidate plane, the plane's positions only.
 static int walk_link(fgpu_ctx* ctx, const WalkBatch& wb, const WalkWindow& w) {
     const BatchBufs& bb = wb.bb;
-    const unsigned full_grid = std::min(fgpu_blocks(w.pos_end - (w.lo & ~63ULL), 1024), 4096u);
+    const unsigned full_grid = std::min(fgpu_blocks(w.pos_end - (w.lo & ~63ULL), 256 * LINK_U), 4096u);
+    const unsigned lane_grid = std::min(fgpu_blocks(w.pos_end - (w.lo & ~63ULL), 1024), 4096u);
+    const uint64_t link_words = ((w.pos_end + 63) >> 6) - (w.lo >> 6);
+    uint64_t* const lk = (uint64_t*)bb.lk.p + (w.lo >> 6);
+    const char* what;
     if (!(wb.cand_ok && w.lo == 0)) {      // (lo > 0: the window registers what this batch's earlier windows created -- positions the plane does not know)
         FGPU_LAUNCH("walk_link", k_walk_link, full_grid, 256, wb.pl, ctx->fd, w.wt, w.uf_parent, w.lo, w.hi, w.pos_end, w.roots_state);
         if (ctx->refresh_snapshot) ctx->full_links++;
-        return FGPU_OK;
+        what = "dense link pass: lk plane against the per-lane pass's";
+    } else {
+        FGPU_LAUNCH("walk_link", k_walk_link_sparse, std::min(fgpu_blocks(link_words, 256), 4096u), 256, wb.pl, ctx->fd, w.wt, w.uf_parent, w.lo, w.hi, w.pos_end,
+                    w.roots_state, (const uint64_t*)bb.cand.p, (uint64_t*)bb.lk.p);
+        ctx->sparse_links++;
+        what = "sparse link pass: lk plane against the full pass's";
     }
-    const uint64_t link_words = ((w.pos_end + 63) >> 6) - (w.lo >> 6);
-    uint64_t* const lk = (uint64_t*)bb.lk.p + (w.lo >> 6);
-    FGPU_LAUNCH("walk_link", k_walk_link_sparse, std::min(fgpu_blocks(link_words, 256), 4096u), 256, wb.pl, ctx->fd, w.wt, w.uf_parent, w.lo, w.hi, w.pos_end,
-                w.roots_state, (const uint64_t*)bb.cand.p, (uint64_t*)bb.lk.p);
-    ctx->sparse_links++;
     if (!ctx->dbg_delta_check) return FGPU_OK;
-    const auto full = [&](uint64_t* scratch) {      // the sparse pass's plane is kept; the full pass makes its own in place (its unions are the same ones again)
+    const auto full = [&](uint64_t* scratch) {      // the cheap pass's plane is kept; the per-lane pass makes its own in place (its unions are the same ones again)
         const hipError_t e = hipMemcpyAsync(scratch, lk, link_words * 8, hipMemcpyDeviceToDevice, wb.walk_stream);
-        hipLaunchKernelGGL(k_walk_link, dim3(full_grid), dim3(256), 0, wb.walk_stream, wb.pl, ctx->fd, w.wt, w.uf_parent, w.lo, w.hi, w.pos_end, (uint32_t*)nullptr);
+        hipLaunchKernelGGL(k_walk_link_lane, dim3(lane_grid), dim3(256), 0, wb.walk_stream, wb.pl, ctx->fd, w.wt, w.uf_parent, w.lo, w.hi, w.pos_end, (uint32_t*)nullptr);
         return e;
     };
-    return walk_dbg_compare(ctx, wb.walk_stream, (const uint64_t*)lk, (const uint64_t*)nullptr, link_words, full, "sparse link pass: lk plane against the full pass's",
-                            bb.seq, w.lo);
+    return walk_dbg_compare(ctx, wb.walk_stream, (const uint64_t*)lk, (const uint64_t*)nullptr, link_words, full, what, bb.seq, w.lo);
 }
 
 // Who walks a window's large clusters: a rule of the host's, from the knobs and from what the scan has shown so far -- the counters as the
