@@ -1,8 +1,8 @@
-// api.hip — the extern "C" entry points of include/faucet_gpu.h.
+// api.hip — the extern "C" entry points of include/faucet_gpu.h, all but the scan pass' (scan_driver.hip) and the sliced load pass' (load_slices.hip).
 //
-// Thin: argument checks, state machine (idle -> loading -> idle -> scanning -> idle), buffer management and the
-// order in which the stages of pack.hip / load.hip / scan_pure.hip / scan_walk.hip / scan_harvest.hip are put on the stream.
-// (The fgpu_load_slice_* entry points of the filter-sliced pass 1 live with its stages, in load_slices.hip.)
+// Thin: argument checks, state machine (idle -> loading -> idle -> scanning -> idle), the context's life cycle, and the order in which the stages
+// of pack.hip / load.hip are put on the stream; the Bloom transfers, the probes, the diagnostics and profiling.  What this unit shares with the
+// scan pass' driver (fgpu_check_errors, fgpu_sync_all, fgpu_pull_counters, fgpu_stop_queue_recycle) is declared in fgpu_ctx.h.
 // There is no CPU path in this library: with no usable gfx950 device fgpu_create fails with FGPU_ERR_HIP.
 #include <cstdio>
 #include <algorithm>
@@ -13,9 +13,6 @@
 
 #include "fgpu_ctx.h"
 
-int fgpu_scan_export_impl(fgpu_ctx* ctx, void* dev_entries, uint64_t cap_entries, uint64_t* d_stamps, uint64_t* n_entries);
-int fgpu_scan_import_impl(fgpu_ctx* ctx, const void* dev_entries, uint64_t n);
-int fgpu_scan_download_impl(fgpu_ctx* ctx, uint64_t* keys_host, fgpu_junction* recs_host, uint64_t cap, uint64_t* n_out);
 
 static thread_local std::string g_create_error;   // (per thread: the ranks of a group create their contexts at the same time)
 
@@ -105,7 +102,7 @@ int fgpu_prof_collect(fgpu_ctx* ctx) {
     return FGPU_OK;
 }
 
-static int check_errors(fgpu_ctx* ctx) {
+int fgpu_check_errors(fgpu_ctx* ctx) {
     // device-side error flags (table overflow) are surfaced at the synchronising calls
     if (ctx->counters_host->error_flags & 1ULL) {
         // A batch created more records than the table had room for (it is kept below a quarter full BETWEEN batches).  While the scan's batches
@@ -147,7 +144,7 @@ static int check_errors(fgpu_ctx* ctx) {
 }
 
 // everything issued so far, on both streams, has completed
-static int sync_all(fgpu_ctx* ctx) {
+int fgpu_sync_all(fgpu_ctx* ctx) {
     if (int rc = fgpu_bg_join(ctx)) return rc;
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->wstream));
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->cstream));   // the side stream's last resets (nothing waits for them but the next window of their parity)
@@ -170,23 +167,17 @@ int fgpu_pull_counters(fgpu_ctx* ctx) {
         DevCounters& c = *ctx->counters_host;
         if (c.late_n[0] <= FGPU_LATE_CAP && c.late_n[2] != c.late_n[0]) c.error_flags |= 4ULL;
     }
-    return check_errors(ctx);
+    return fgpu_check_errors(ctx);
 }
 
 // the page-locked buffers of harvested lists go back to the pool (stop_queue.clear() would leak them)
-static void stop_queue_recycle(fgpu_ctx* ctx) {
+void fgpu_stop_queue_recycle(fgpu_ctx* ctx) {
     for (StopBatch& sb : ctx->stop_queue)
         if (sb.data) { StopBatch f; f.data = sb.data; f.cap = sb.cap; ctx->stop_pool.push_back(f); }
     ctx->stop_queue.clear();
 }
 
-static bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 
-static void journal_recycle(fgpu_ctx* ctx);
-static int journal_add(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads);
-static int scan_replay(fgpu_ctx* ctx);
-static int load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk, const fgpu_kept_reads* kr);
-static int scan_batch_from(fgpu_ctx* ctx, const fgpu_reads* reads, const ResidentBatch* kept);
 
 // ---- pass 1: what the plain pass' entry points (below) and the sliced pass' (load_slices.hip) share -----------------------------------------
 int fgpu_check_reads(fgpu_ctx* ctx, const fgpu_reads* r) {
@@ -243,6 +234,44 @@ int fgpu_load_pass_end(fgpu_ctx* ctx, fgpu_load_stats* stats) {
                        ctx->resident_count == ctx->pass_batches && !(ctx->prm.flags & FGPU_FLAG_MERCY);
     return FGPU_OK;
 }
+// One batch of the plain pass from a packed block, with or without its read offsets (fgpu_load_batch_packed, fgpu_load_batch_packed_reads below)
+static int load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk, const fgpu_kept_reads* kr) {
+    if (!ctx || !pk) return FGPU_ERR_ARG;
+    if (ctx->phase != 1) { ctx->err = "load_batch_packed outside load_begin/load_end"; return FGPU_ERR_STATE; }
+    if (ctx->shard_times || ctx->shard_planes) {
+        ctx->err = "load_batch_packed in the pass of a read shard (FGPU_LOAD_SHARD_TIMES / FGPU_LOAD_SHARD_PLANES): the fix-up reads the batches' own copies";
+        return FGPU_ERR_STATE;
+    }
+    if (!pk->block_dev) {                        // a batch without reads has no block
+        if (pk->T || pk->nbytes || pk->n_reads) { ctx->err = "load_batch_packed: a description without a block must be empty"; return FGPU_ERR_ARG; }
+        return FGPU_OK;
+    }
+    PackedBlock b;
+    b.buf.p = pk->block_dev;
+    b.buf.bytes = pk->nbytes;
+    b.T = pk->T;
+    b.n_words = (pk->T + 63) / 64;
+    b.n_reads = pk->n_reads;
+    if (!pk->T || pk->T > ctx->prm.max_batch_bases || pk->T >= 0xFFFFFF00ULL || pk->n_reads > pk->T || !pk->n_reads || pk->nbytes != fgpu_packed_bytes(b.n_words)) {
+        ctx->err = "load_batch_packed: a block of nbytes = 24 * (ceil(T / 64) + 8) + 16 for T stream positions (at most max_batch_bases) of 1 <= n_reads <= T reads";
+        return FGPU_ERR_ARG;
+    }
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    int rc = fgpu_packed_digest(ctx, &b, true);
+    if (rc) return rc;
+    const uint64_t* words = (const uint64_t*)b.buf.p;
+    if ((rc = fgpu_stage_load(ctx, words, words + 2 * (b.n_words + FGPU_PADW), b.T, b.n_words))) {
+        (void)hipStreamSynchronize(ctx->stream);   // the caller still owns the block and may free it: nothing queued reads it any more
+        return rc;
+    }
+    if ((rc = fgpu_resident_adopt(ctx, b, kr))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    ctx->pass_batches++;
+    ctx->load_stats.reads_processed += b.n_reads;
+    return FGPU_OK;
+}
 
 extern "C" {
 
@@ -267,9 +296,9 @@ int fgpu_create(const fgpu_params* p, fgpu_ctx** out) {
     if (p->k < 1 || p->k > 31) { g_create_error = "k must be in 1..31"; return FGPU_ERR_ARG; }
     if (p->j < 0 || p->j > 8) { g_create_error = "j must be in 0..8"; return FGPU_ERR_ARG; }
     if (p->n_hash < 1 || p->n_hash > 10) { g_create_error = "n_hash must be in 1..10"; return FGPU_ERR_ARG; }
-    if (!is_pow2(p->tai) || p->tai < 128) { g_create_error = "tai must be a power of two >= 128"; return FGPU_ERR_ARG; }
+    if (!fgpu_is_pow2(p->tai) || p->tai < 128) { g_create_error = "tai must be a power of two >= 128"; return FGPU_ERR_ARG; }
     if (p->max_spacer_dist < 1) { g_create_error = "max_spacer_dist must be >= 1"; return FGPU_ERR_ARG; }
-    if (p->junction_capacity && !is_pow2(p->junction_capacity)) { g_create_error = "junction_capacity must be a power of two"; return FGPU_ERR_ARG; }
+    if (p->junction_capacity && !fgpu_is_pow2(p->junction_capacity)) { g_create_error = "junction_capacity must be a power of two"; return FGPU_ERR_ARG; }
     // FGPU_CLI_TIMES=1: where the context's creation goes (stderr; the CLI's phase clock shows it as one line)
     const bool tell = getenv("FGPU_CLI_TIMES") != nullptr;
     const auto t_start = std::chrono::steady_clock::now();
@@ -336,10 +365,10 @@ int fgpu_create(const fgpu_params* p, fgpu_ctx** out) {
     // with the filter, 2^26 positions up to 2^30 filter bits, 2^28 from 2^32 on (config 5's walk stage 404 / 347 / 317 ms at 2^26 / 2^27 /
     // 2^28, config 4's 1 266 / 1 020 / 921 ms; config 2 settles at 2^25-2^26 whatever the bound).  The window table is 32 bytes per position
     // of the bound.
-    ctx->max_span = std::min<uint64_t>(std::max<uint64_t>(p->tai >> 4, FGPU_MAX_SPAN), 1ULL << 28);
+    ctx->span.max_span = std::min<uint64_t>(std::max<uint64_t>(p->tai >> 4, FGPU_MAX_SPAN), 1ULL << 28);
     if (const char* e = getenv("FGPU_MAX_SPAN_LOG2")) {   // experiment knob
         int l = atoi(e);
-        if (l >= 12 && l <= 28) ctx->max_span = 1ULL << l;
+        if (l >= 12 && l <= 28) ctx->span.max_span = 1ULL << l;
     }
     memset(&ctx->load_stats, 0, sizeof(ctx->load_stats));
     memset(&ctx->scan_stats, 0, sizeof(ctx->scan_stats));
@@ -438,7 +467,7 @@ void fgpu_destroy(fgpu_ctx* ctx) {
                     ctx->wbits, ctx->uf_parent, ctx->cl_count, ctx->cl_offset, ctx->cl_fill, ctx->cl_weight, ctx->ko_hk, ctx->ko_occ, ctx->ko_piece, ctx->cl_members, ctx->cl_roots, ctx->counters,
                     ctx->wdesc, ctx->s3c_out, ctx->s3b_out, ctx->s3f_out, ctx->s3j_out};
     for (void* p : ptrs) if (p) hipFree(p);
-    stop_queue_recycle(ctx);
+    fgpu_stop_queue_recycle(ctx);
     for (StopBatch& f : ctx->stop_pool) hipHostFree(f.data);
     ctx->stop_pool.clear();
     if (ctx->counters_host) hipHostFree(ctx->counters_host);
@@ -466,7 +495,7 @@ void fgpu_destroy(fgpu_ctx* ctx) {
 
 int fgpu_synchronize(fgpu_ctx* ctx) {
     if (!ctx) return FGPU_ERR_ARG;
-    if (int rc = sync_all(ctx)) return rc;
+    if (int rc = fgpu_sync_all(ctx)) return rc;
     return fgpu_offs_check_report(ctx);
 }
 
@@ -573,46 +602,6 @@ int fgpu_load_batch_packed_reads(fgpu_ctx* ctx, const fgpu_packed* pk, const fgp
     }
     return load_batch_packed(ctx, pk, pk->block_dev ? kr : nullptr);
 }
-
-}  // extern "C"
-static int load_batch_packed(fgpu_ctx* ctx, const fgpu_packed* pk, const fgpu_kept_reads* kr) {
-    if (!ctx || !pk) return FGPU_ERR_ARG;
-    if (ctx->phase != 1) { ctx->err = "load_batch_packed outside load_begin/load_end"; return FGPU_ERR_STATE; }
-    if (ctx->shard_times || ctx->shard_planes) {
-        ctx->err = "load_batch_packed in the pass of a read shard (FGPU_LOAD_SHARD_TIMES / FGPU_LOAD_SHARD_PLANES): the fix-up reads the batches' own copies";
-        return FGPU_ERR_STATE;
-    }
-    if (!pk->block_dev) {                        // a batch without reads has no block
-        if (pk->T || pk->nbytes || pk->n_reads) { ctx->err = "load_batch_packed: a description without a block must be empty"; return FGPU_ERR_ARG; }
-        return FGPU_OK;
-    }
-    PackedBlock b;
-    b.buf.p = pk->block_dev;
-    b.buf.bytes = pk->nbytes;
-    b.T = pk->T;
-    b.n_words = (pk->T + 63) / 64;
-    b.n_reads = pk->n_reads;
-    if (!pk->T || pk->T > ctx->prm.max_batch_bases || pk->T >= 0xFFFFFF00ULL || pk->n_reads > pk->T || !pk->n_reads || pk->nbytes != fgpu_packed_bytes(b.n_words)) {
-        ctx->err = "load_batch_packed: a block of nbytes = 24 * (ceil(T / 64) + 8) + 16 for T stream positions (at most max_batch_bases) of 1 <= n_reads <= T reads";
-        return FGPU_ERR_ARG;
-    }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    int rc = fgpu_packed_digest(ctx, &b, true);
-    if (rc) return rc;
-    const uint64_t* words = (const uint64_t*)b.buf.p;
-    if ((rc = fgpu_stage_load(ctx, words, words + 2 * (b.n_words + FGPU_PADW), b.T, b.n_words))) {
-        (void)hipStreamSynchronize(ctx->stream);   // the caller still owns the block and may free it: nothing queued reads it any more
-        return rc;
-    }
-    if ((rc = fgpu_resident_adopt(ctx, b, kr))) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    ctx->pass_batches++;
-    ctx->load_stats.reads_processed += b.n_reads;
-    return FGPU_OK;
-}
-extern "C" {
 
 int fgpu_presence_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
     if (!ctx) return FGPU_ERR_ARG;
@@ -727,856 +716,6 @@ int fgpu_bitmap_or(fgpu_ctx* ctx, void* dst_dev, const void* src_dev, uint64_t n
     return fgpu_util_or(ctx, dst_dev, src_dev, nbytes);
 }
 
-// ---- pass 2 --------------------------------------------------------------------------------------------------
-int fgpu_scan_resident_base(fgpu_ctx* ctx, uint64_t first_batch) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 0) { ctx->err = "scan_resident_base while a pass is open: between the load pass and fgpu_scan_begin"; return FGPU_ERR_STATE; }
-    ctx->scan_resident_base = first_batch;
-    return FGPU_OK;
-}
-
-int fgpu_scan_begin(fgpu_ctx* ctx) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 0) { ctx->err = "scan_begin while another pass is open"; return FGPU_ERR_STATE; }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    int rc = fgpu_bg_join(ctx);      // the walk's streams and events (made beside pass 1, fgpu_create)
-    if (rc) return rc;
-    if ((rc = fgpu_offs_check_report(ctx))) return rc;
-    if ((rc = fgpu_scan_alloc(ctx))) return rc;
-    if ((rc = fgpu_scan_reset(ctx))) return rc;
-    ctx->fixup_ready = false;   // the load pass' counters go with this reset
-    FGPU_HIP(hipMemsetAsync(ctx->counters, 0, sizeof(DevCounters), ctx->stream));
-    memset(&ctx->scan_stats, 0, sizeof(ctx->scan_stats));
-    memset(ctx->counters_host, 0, sizeof(DevCounters));
-    ctx->scan_windows = 0;
-    ctx->scan_pieces_seen = 0;
-    ctx->scan_piece_base = 0;
-    ctx->scan_imported = 0;
-    ctx->delta_next = 0;
-    journal_recycle(ctx);
-    ctx->journal_on = !(ctx->prm.flags & FGPU_FLAG_EAGER_FLAGS) && !ctx->eager_runtime;
-    ctx->eager_scan = ctx->lazy_failed = ctx->capacity_failed = false;
-    ctx->dl_keys_n = 0;
-    ctx->late_acc[0] = ctx->late_acc[1] = ctx->late_acc[2] = 0;
-    ctx->stops_delivered = 0;
-    ctx->lp_applied_seq = 0;
-    ctx->host_waits = 0;
-    ctx->host_wait_ms = 0;
-    ctx->wait_sites.clear();
-    if (ctx->short_pf) FGPU_HIP(hipMemsetAsync(ctx->short_pf, 0, ctx->short_pf_tai / 8, ctx->stream));   // a scan starts with empty pair filters
-    if ((rc = fgpu_long_pairs_reset(ctx))) return rc;
-    ctx->have_import = false;
-    ctx->journal_max_read_len = 0;
-    ctx->hint_in_table = false;
-    ctx->hint_gen = 0;
-    ctx->hint_n = ctx->hint_max_seq = 0;
-    ctx->delta_ready = false;
-    ctx->delta_keys = ctx->refresh_full = ctx->refresh_delta = ctx->refresh_mismatch = 0;
-    ctx->sparse_links = ctx->full_links = 0;
-    ctx->dbg_stall_us = getenv("FGPU_DEBUG_WALK_STALL_US") ? std::min(100000, std::max(0, atoi(getenv("FGPU_DEBUG_WALK_STALL_US")))) : 0;
-    ctx->dbg_delta_check = getenv("FGPU_DEBUG_DELTA_CHECK") != nullptr;
-    ctx->no_sparse_link = getenv("FGPU_NO_SPARSE_LINK") != nullptr;      // measurement aid: no candidate planes, every window of a prepared batch linked in full
-    // ranges of the pure stage's back half (scan_pure.hip): n >= 8 forces 2^n positions per range (tests), 0 one range per batch -- the schedule
-    // before there were ranges, also what FGPU_NO_OVERLAP=1 runs (the walk follows on the same stream); anything else: the default policy
-    ctx->scan_range_log2 = -1;
-    if (const char* e = getenv("FGPU_SCAN_RANGE_LOG2")) {
-        char* end = nullptr;
-        const long n = strtol(e, &end, 10);
-        if (end == e || *end || (n != 0 && (n < 8 || n > 40))) {      // (empty, not a number, 1..7, beyond 2^40: no silent meaning)
-            ctx->err = std::string("FGPU_SCAN_RANGE_LOG2=") + e + ": 0 (one range per batch) or 8..40 (ranges of 2^n positions)";
-            return FGPU_ERR_ARG;
-        }
-        ctx->scan_range_log2 = (int)n;
-    }
-    if (fgpu_walk_no_overlap()) ctx->scan_range_log2 = 0;
-    // calibrated upwards window by window; a context that has scanned before starts a quarter below where that scan ended up
-    const uint64_t start_span = std::max<uint64_t>(1ULL << 18, ctx->settled_span / 4);
-    ctx->window_span = ctx->prm.walk_window_span ? std::min<uint64_t>(std::max<uint64_t>(ctx->prm.walk_window_span, 64), ctx->max_span)
-                                                 : std::min<uint64_t>(start_span, ctx->max_span);
-    ctx->calib_left = 16;
-    ctx->calib_f = ctx->calib_p = 0;
-    ctx->adapt_followers = 0;
-    ctx->adapt_pieces = 0;
-    ctx->adapt_overflows = 0;
-    ctx->adapt_vote = 0;
-    ctx->calib_ovf = 0;
-    ctx->span_ceiling = ~0ULL;
-    ctx->repeats_seen_before = false;
-    ctx->walked_pieces = 0;
-    ctx->scan_batch_index = 0;
-    ctx->scan_batch_seq = 0;
-    for (BatchBufs* b : ctx->to_harvest) b->stops_pending = false;   // lists of an earlier scan nobody asked for
-    ctx->to_harvest.clear();
-    stop_queue_recycle(ctx);
-    for (BatchBufs* b : ctx->prepared) ctx->pool.push_back(b);
-    ctx->prepared.clear();
-    ctx->cur = &ctx->bb_default;
-    ctx->phase = 2;
-    return FGPU_OK;
-}
-
-// Adapt the scheduling window to the data.  Larger windows mean fewer launches and fuller kernels but longer
-// dependency chains inside the clusters; measured on config 2 the step time keeps falling until about a third of the
-// pieces queue behind an earlier piece of their cluster (2^21: 254 ms, 2^22: 225, 2^23: 213, 2^24: 207, 2^25: 205).
-// counters_host must be fresh with respect to the walks issued so far.
-static void adapt_window(fgpu_ctx* ctx) {
-    // Round 4.  On config 2 the share of queueing pieces is 0.25 / 0.43 / 0.58 at 2^24 / 2^25 / 2^26 positions and one batch's counters are a
-    // noisy sample of it, so the controller of rounds 1-3 moved the size up and down between batches for good -- and every move asked the
-    // host to wait for the next windows one by one, which keeps it from feeding the next batch's pure stage: 12 waits per step
-    // (scripts/timeline.py), 121.4-122.1 ms a step against 116.8-118.9 with any fixed size in that range (scripts/span_fixed_ab.sh).
-    // Now: both counts come from one snapshot of the device's counters (pieces counted behind their window's walks); growing on a share that
-    // is not clear-cut (0.15-1/3) has to be asked for by two batches running; growing waits for windows only beyond the largest size a batch
-    // of this context has been walked at, shrinking only towards a size it has not walked yet or when most pieces queue (the percolation
-    // case the waits are for).  The thresholds themselves are unchanged, and shrinking still acts at once: a wider dead band, decisions held
-    // back for a batch or two (shrinking included) and x4 steps were tried as well -- they walked config 4 at larger windows than suit it
-    // and config 3's repeats at a percolating size now and then (pass 2 of 170 ms at 310-360).
-    static const bool dbg_span = getenv("FGPU_DEBUG_SPAN") != nullptr;
-    const uint64_t f = ctx->counters_host->followers_seen - ctx->adapt_followers;
-    const uint64_t p = ctx->counters_host->walked_pieces - ctx->adapt_pieces;
-    if (p == 0 || ctx->prm.walk_window_span) return;      // (no window has been completed since the last look at the counters)
-    {
-        const uint64_t usual = std::min<uint64_t>(std::min<uint64_t>(ctx->max_span, FGPU_USUAL_SPAN), ctx->span_ceiling);
-        int want = 0;             // -1 smaller, +1 larger
-        bool clear = false;
-        if (f * 2 > p) { want = -1; clear = f * 5 > p * 4; }
-        else if (f * 3 < p) { want = 1; clear = f * 20 < p * 3; }
-        // too large is dear (a batch at a percolating size), too small is not: shrinking acts at once, growing on a clear share or the second time
-        const bool act = want < 0 || (want > 0 && (clear || ctx->adapt_vote > 0));
-        ctx->adapt_vote = act ? 0 : want;
-        if (want >= 0) ctx->proven_span = std::max(ctx->proven_span, ctx->window_span);
-        if (ctx->counters_host->ko_overflows > ctx->adapt_overflows && ctx->window_span > 4096) {
-            // a window's large clusters outgrew the tables of the large-cluster walks and were walked piece after piece by their one thread:
-            // far too large a window for this data
-            ctx->window_span = std::max<uint64_t>(4096, ctx->window_span / 4);
-            ctx->proven_span = std::min(ctx->proven_span, ctx->window_span);
-            ctx->span_ceiling = std::min(ctx->span_ceiling, ctx->window_span * 2);     // (this scan does not grow to that size again)
-            ctx->calib_ovf = ctx->counters_host->ko_overflows;
-            ctx->calib_left = 0;
-        }
-        else if (act && want < 0 && ctx->window_span > 4096) {
-            ctx->window_span /= 2;
-            // ... and look again window by window -- unless this context has walked a batch at the smaller size before and the share is not
-            // the percolation case (most pieces queueing) the looks are for
-            if (clear || ctx->window_span > ctx->proven_span) ctx->calib_left = 8;
-            ctx->proven_span = std::min(ctx->proven_span, ctx->window_span);
-        }
-        else if (act && want > 0 && ctx->window_span < usual) {
-            // clusters percolate at a sharp threshold (about one genome coverage per window): a whole batch at a size that turns out to be
-            // beyond it costs seconds, so the first windows at a size this context has not walked yet are looked at one by one
-            ctx->window_span = std::min<uint64_t>(ctx->window_span * 2, usual);
-            if (ctx->window_span > ctx->proven_span) ctx->calib_left = std::max(ctx->calib_left, 2);
-        }
-        else if (f * 16 < p && ctx->window_span < std::min<uint64_t>(ctx->max_span, ctx->span_ceiling)) ctx->window_span *= 2;   // thin coverage per window: see FGPU_MAX_SPAN
-    }
-    if (dbg_span) fprintf(stderr, "[span] batch: followers %llu of %llu pieces -> span %llu, looks %d, vote %d\n", (unsigned long long)f, (unsigned long long)p,
-                          (unsigned long long)ctx->window_span, ctx->calib_left, ctx->adapt_vote);
-    ctx->adapt_followers = ctx->counters_host->followers_seen;
-    ctx->adapt_pieces = ctx->counters_host->walked_pieces;
-    ctx->adapt_overflows = ctx->counters_host->ko_overflows;
-}
-
-// a batch's buffers (empty) with its events, made once
-static BatchBufs* new_batch(fgpu_ctx* ctx) {
-    BatchBufs* b = new BatchBufs();
-    ctx->all_batches.push_back(b);
-    hipEventCreateWithFlags(&b->pure_done, hipEventDisableTiming);
-    hipEventCreateWithFlags(&b->walk_done, hipEventDisableTiming);
-    bool all = true;
-    for (hipEvent_t& e : b->range_ev) all = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess && all;
-    if (!all) {      // without every range event the batch's back half stays one range (scan_range_plan looks at slot 0)
-        for (hipEvent_t& e : b->range_ev) { if (e) hipEventDestroy(e); e = nullptr; }
-        (void)hipGetLastError();
-    }
-    return b;
-}
-
-static BatchBufs* acquire_batch(fgpu_ctx* ctx) {
-    // FIFO over (at least) two BatchBufs, so that the one handed out was last walked two batches ago
-    BatchBufs* b;
-    // (at most FGPU_DELTA_RING: a batch registers the created-key lists of the FGPU_DELTA_RING - 1 batches before it)
-    static const size_t depth = getenv("FGPU_SCAN_BUFFERS") ? (size_t)std::min(FGPU_DELTA_RING, std::max(2, atoi(getenv("FGPU_SCAN_BUFFERS")))) : 2;
-    // The buffers handed out are the ones used `depth` batches ago -- NOT the oldest of the pool: a context that has walked a prepared shard
-    // keeps dozens of buffers, and a streaming scan that took them first in, first out let its pure stage run as far ahead of the walk as the
-    // pool is deep (nothing left to wait for), beyond what the created-key lists cover: keys missing from the snapshot planes, a wrong map
-    // (seen at config 4's size, 50 M reads streamed after a 60 M-read prepared shard: 9 887 records too many).  The streaming scan pushes every
-    // batch's buffers back at the end of the pool, so the one used `depth` batches ago sits `depth` from the end.
-    if (ctx->pool.size() >= depth) {
-        const size_t at = ctx->pool.size() - depth;
-        b = ctx->pool[at];
-        ctx->pool.erase(ctx->pool.begin() + at);
-    } else {
-        b = new_batch(ctx);
-    }
-    return b;
-}
-
-// after the walk of batch b has been issued: its lists become available (FGPU_FLAG_RECORD_STOPS)
-static void note_walked(fgpu_ctx* ctx, BatchBufs* b) {
-    if (!ctx->record_stops) return;
-    b->stops_pending = true;
-    ctx->to_harvest.push_back(b);
-}
-
-// one_range: the batch is prepared ahead of its turn -- nothing walks it beside its own pure stage, so its back half is not cut into ranges
-// The batch's stream comes into `b` from the text (reads: packed) or from a batch the load pass kept (kept: its planes copied, nothing packed
-// or compared -- fgpu_scan_batch_kept); everything behind that is common.
-static int scan_take_kept(fgpu_ctx* ctx, BatchBufs* b, const ResidentBatch* kept) {
-    b->T = kept->T; b->n_words = kept->n_words; b->n_reads = kept->n_reads;
-    b->d_offs = (const uint64_t*)kept->offs_p();
-    const uint64_t cb = 2 * (b->n_words + FGPU_PADW) * 8, bbytes = (b->n_words + FGPU_PADW) * 8;
-    int rc;
-    if ((rc = fgpu_ensure_b(ctx, &b->codes, cb)) || (rc = fgpu_ensure_b(ctx, &b->bad, bbytes))) return rc;
-    FGPU_HIP(hipMemcpyAsync(b->codes.p, kept->codes_p(), cb, hipMemcpyDeviceToDevice, ctx->stream));
-    FGPU_HIP(hipMemcpyAsync(b->bad.p, kept->bad_p(), bbytes, hipMemcpyDeviceToDevice, ctx->stream));
-    // the longest read bounds how far a piece reaches (max_piece_span): the text path's packing refills the counter, here the load pass' value
-    // seeds it, host copy and device copy (as the replay does from journal_max_read_len), before the first pure stage that needs it
-    if (ctx->counters_host->max_read_len < ctx->kept_max_read_len) {
-        ctx->kept_seed = ctx->kept_max_read_len;
-        ctx->counters_host->max_read_len = ctx->kept_seed;
-        FGPU_HIP(hipMemcpyAsync(&ctx->counters->max_read_len, &ctx->kept_seed, 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    return FGPU_OK;
-}
-
-static int scan_pure_into(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads, bool one_range = false, const ResidentBatch* kept = nullptr) {
-    if (b->stops_pending) {   // the buffers still hold the visit planes of an earlier batch: bring its lists to the host first
-        int hrc = fgpu_scan_harvest(ctx, b);
-        if (hrc) return hrc;      // (FGPU_INTERNAL_REPLAY: that batch's walk went wrong; the caller replays and comes back)
-    }
-    b->seq = ctx->scan_batch_seq++;
-    ctx->cur = b;
-    const double t_a = fgpu_host_now();
-    if (b->walk_pending) {   // the walk stream may still be reading this batch's planes
-        FGPU_HIP(fgpu_sync_event(ctx, b->walk_done));
-        b->walk_pending = false;
-    }
-    const double t_b = fgpu_host_now();
-    ctx->host_ms[0] += t_b - t_a;
-    int rc = kept ? scan_take_kept(ctx, b, kept) : fgpu_stage_pack(ctx, reads);
-    ctx->host_ms[1] += fgpu_host_now() - t_b;
-    if (!rc) rc = journal_add(ctx, b, reads);
-    uint64_t n_pieces = 0;
-    ctx->scan_take_kept = kept;
-    if (!rc) rc = fgpu_stage_scan_pure(ctx, &n_pieces, one_range);   // ends with the batch's only synchronisation (piece count)
-    ctx->scan_take_kept = nullptr;
-    if (!rc) ctx->journal_max_read_len = std::max<uint64_t>(ctx->journal_max_read_len, ctx->counters_host->max_read_len);
-    if (!rc) rc = check_errors(ctx);
-    if (!rc) ctx->scan_stats.reads_processed += b->n_reads;
-    if (!rc && b->pure_done) FGPU_HIP(hipEventRecord(b->pure_done, ctx->stream));
-    if (!rc && reads) rc = fgpu_host_batch_done(ctx, reads);
-    return rc;
-}
-
-// ---- the scan's journal: lazy junction tests without a caller-visible fall-back ---------------------------------------------------------
-// While a scan evaluates its junction tests lazily the packed form of every batch (codes + bad plane, 3 bits per base; the read offsets when
-// scanInputRead's lists are recorded) stays in HBM, up to an eighth of the device memory.  If the walk meets a preview it cannot repair
-// (never seen on real input, forced by FGPU_DEBUG_LAZY_FAIL=1) the library itself resets the junction map and scans the
-// journal again with every test evaluated: same results, nothing for the caller to do -- ReadScanner::scanReads has no such contract
-// either (src/ReadScanner.cpp:284-359).  A scan that outgrows the journal is first brought to a point where everything walked so far is
-// known to be good, then goes on with eager tests (which cannot fail that way) and without a journal.
-static void journal_recycle(fgpu_ctx* ctx) {
-    for (JournalBatch* j : ctx->journal) ctx->journal_pool.push_back(j);
-    ctx->journal.clear();
-    ctx->journal_bytes = 0;
-}
-
-static int journal_add(fgpu_ctx* ctx, BatchBufs* b, const fgpu_reads* reads) {
-    if (!ctx->journal_on || ctx->in_replay) return FGPU_OK;
-    const uint64_t cb = 2 * (b->n_words + FGPU_PADW) * 8, bbytes = (b->n_words + FGPU_PADW) * 8, ob = ctx->record_stops ? (b->n_reads + 1) * 8 : 0;
-    if (ctx->journal_bytes + cb + bbytes + ob > ctx->journal_budget) {
-        // no room: everything walked so far is checked (and scanned again if need be), the rest of the scan is eager
-        int rc = fgpu_pull_counters(ctx);
-        if (rc) return rc;
-        BatchBufs* const cur = ctx->cur;
-        // the batch being packed has already been folded into the device's longest-read maximum (fgpu_stage_pack) and is not in the journal:
-        // the replay restores that maximum from journal_max_read_len, so it has to know this batch's reads too
-        ctx->journal_max_read_len = std::max<uint64_t>(ctx->journal_max_read_len, ctx->counters_host->max_read_len);
-        if (ctx->lazy_failed && (rc = scan_replay(ctx))) return rc;
-        ctx->cur = cur;
-        ctx->journal_on = false;
-        ctx->eager_scan = true;
-        journal_recycle(ctx);
-        return FGPU_OK;
-    }
-    JournalBatch* j;
-    if (!ctx->journal_pool.empty()) { j = ctx->journal_pool.back(); ctx->journal_pool.pop_back(); }
-    else j = new JournalBatch();
-    int rc;
-    if ((rc = fgpu_ensure_b(ctx, &j->codes, cb)) || (rc = fgpu_ensure_b(ctx, &j->bad, bbytes)) || (ob && (rc = fgpu_ensure_b(ctx, &j->offs, ob)))) {
-        ctx->journal_pool.push_back(j);
-        return rc;
-    }
-    if (b->T) {
-        FGPU_HIP(hipMemcpyAsync(j->codes.p, b->codes.p, cb, hipMemcpyDeviceToDevice, ctx->stream));
-        FGPU_HIP(hipMemcpyAsync(j->bad.p, b->bad.p, bbytes, hipMemcpyDeviceToDevice, ctx->stream));
-        if (ob) FGPU_HIP(hipMemcpyAsync(j->offs.p, b->d_offs, ob, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    j->T = b->T; j->n_words = b->n_words; j->n_reads = b->n_reads; j->seq = b->seq;
-    ctx->journal.push_back(j);
-    ctx->journal_bytes += cb + bbytes + ob;
-    (void)reads;
-    return FGPU_OK;
-}
-
-// Reset the junction map and scan every journalled batch again with all junction tests evaluated.  On return everything the journal holds
-// has been walked; batches that were only prepared are walked as well (their turn has come: this is only reached from a walk or after one).
-static int scan_replay_once(fgpu_ctx* ctx);
-static int scan_replay(fgpu_ctx* ctx) {
-    for (int attempt = 0;; attempt++) {
-        const bool for_room = ctx->capacity_failed;
-        ctx->capacity_failed = false;
-        if (for_room) {
-            int rc = sync_all(ctx);
-            if (!rc) rc = fgpu_scan_regrow_empty(ctx, ctx->jcap * 4);
-            if (rc) { ctx->lazy_failed = false; return rc; }
-            ctx->capacity_replays++;
-        }
-        int rc = scan_replay_once(ctx);
-        // the replay itself ran out of room (its batches are walked with the table kept below a quarter full between them, so this takes a
-        // single batch that creates more than three times what the whole table held): once more, larger again.  (Noticed at the end of the
-        // replay or where it harvests the lists of a batch it has walked: fgpu_scan_harvest applies none of them once the flag is up.)
-        if (rc == FGPU_ERR_CAPACITY && (ctx->counters_host->error_flags & 1ULL) && ctx->jcap < (1ULL << 31) && attempt < 6) {
-            ctx->capacity_failed = true;
-            continue;
-        }
-        // The journal still holds every batch of the scan: it stays on, so that a later batch that outgrows the table is absorbed as well (the
-        // scan is eager from here on and cannot fail the lazy way again)
-        if (!rc && for_room) ctx->journal_on = true;
-        return rc;
-    }
-}
-
-static int scan_replay_once(fgpu_ctx* ctx) {
-    ctx->in_replay = true;
-    ctx->journal_on = false;
-    ctx->eager_scan = true;
-    ctx->lazy_failed = false;
-    int rc = sync_all(ctx);
-    for (BatchBufs* b : ctx->prepared) ctx->pool.push_back(b);
-    ctx->prepared.clear();
-    for (BatchBufs* b : ctx->to_harvest) b->stops_pending = false;
-    ctx->to_harvest.clear();
-    stop_queue_recycle(ctx);
-    if (!rc) rc = fgpu_scan_reset(ctx);
-    if (rc) { ctx->in_replay = false; return rc; }
-    {   // what fgpu_diag_late_flags reports of the voided attempt (everything has completed: sync_all above)
-        unsigned long long ln[3] = {0, 0, 0};
-        if (hipMemcpy(ln, ctx->counters->late_n, sizeof(ln), hipMemcpyDeviceToHost) == hipSuccess)
-            for (int i = 0; i < 3; i++) ctx->late_acc[i] += ln[i];
-    }
-    FGPU_HIP(hipMemsetAsync(ctx->counters, 0, sizeof(DevCounters), ctx->stream));
-    FGPU_HIP(hipMemcpyAsync(&ctx->counters->max_read_len, &ctx->journal_max_read_len, 8, hipMemcpyHostToDevice, ctx->stream));
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    const uint64_t reads_processed = ctx->scan_stats.reads_processed;
-    memset(&ctx->scan_stats, 0, sizeof(ctx->scan_stats));
-    ctx->scan_stats.reads_processed = reads_processed;
-    memset(ctx->counters_host, 0, sizeof(DevCounters));
-    ctx->scan_windows = 0;
-    ctx->scan_pieces_seen = 0;
-    ctx->scan_piece_base = 0;
-    ctx->scan_imported = 0;
-    ctx->delta_next = 0;
-    ctx->hint_in_table = false;
-    ctx->delta_ready = false;            // (the replay makes every batch's planes from scratch against the table as it stands)
-    ctx->window_span = ctx->prm.walk_window_span ? std::min<uint64_t>(std::max<uint64_t>(ctx->prm.walk_window_span, 64), ctx->max_span)
-                                                 : std::min<uint64_t>(std::max<uint64_t>(1ULL << 18, ctx->settled_span / 4), ctx->max_span);
-    ctx->calib_left = 16;
-    ctx->calib_f = ctx->calib_p = 0;
-    ctx->adapt_followers = ctx->adapt_pieces = ctx->adapt_overflows = 0;
-    ctx->adapt_vote = 0;
-    ctx->calib_ovf = 0;
-    ctx->span_ceiling = ~0ULL;
-    ctx->repeats_seen_before = false;
-    ctx->walked_pieces = 0;
-    ctx->scan_batch_index = 0;
-    memset(&ctx->carried, 0, sizeof(ctx->carried));
-    if (ctx->have_import) {   // the table the previous shard handed over comes first again
-        if ((rc = fgpu_scan_reserve(ctx, ctx->import_n)) || (rc = fgpu_scan_import_impl(ctx, ctx->import_copy.p, ctx->import_n))) { ctx->in_replay = false; return rc; }
-        FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-        ctx->scan_imported = ctx->import_n;
-        if (ctx->import_has_carried) {
-            ctx->carried = ctx->import_carried;
-            ctx->scan_piece_base = ctx->import_carried.reads_no_errors;
-        }
-    }
-    for (size_t i = 0; i < ctx->journal.size() && !rc; i++) {
-        JournalBatch* j = ctx->journal[i];
-        BatchBufs* b = acquire_batch(ctx);
-        if (b->stops_pending && (rc = fgpu_scan_harvest(ctx, b))) {   // lists of the replayed batch these buffers held two batches ago
-            ctx->pool.push_back(b);      // (FGPU_ERR_CAPACITY: a walk of this replay outgrew the table -- nothing of it applied; scan_replay goes again)
-            break;
-        }
-        if (b->walk_pending) {
-            FGPU_HIP(fgpu_sync_event(ctx, b->walk_done));
-            b->walk_pending = false;
-        }
-        b->seq = j->seq;
-        ctx->cur = b;
-        b->T = j->T; b->n_words = j->n_words; b->n_reads = j->n_reads;
-        b->d_offs = (const uint64_t*)j->offs.p;
-        if (b->T) {
-            const uint64_t cb = 2 * (b->n_words + FGPU_PADW) * 8, bbytes = (b->n_words + FGPU_PADW) * 8;
-            if ((rc = fgpu_ensure_b(ctx, &b->codes, cb)) || (rc = fgpu_ensure_b(ctx, &b->bad, bbytes))) break;
-            FGPU_HIP(hipMemcpyAsync(b->codes.p, j->codes.p, cb, hipMemcpyDeviceToDevice, ctx->stream));
-            FGPU_HIP(hipMemcpyAsync(b->bad.p, j->bad.p, bbytes, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        uint64_t n_pieces = 0;
-        rc = fgpu_stage_scan_pure(ctx, &n_pieces, true);      // (the replay: one range per batch)
-        if (!rc) rc = check_errors(ctx);
-        if (!rc && b->pure_done) FGPU_HIP(hipEventRecord(b->pure_done, ctx->stream));
-        if (!rc) rc = fgpu_scan_reserve(ctx, ctx->counters_host->n_junctions + ctx->scan_imported);
-        if (!rc) {
-            adapt_window(ctx);
-            rc = fgpu_stage_scan_walk(ctx, b->n_pieces);
-            ctx->walked_pieces += b->n_pieces;
-            if (!rc) note_walked(ctx, b);
-        }
-        ctx->pool.push_back(b);
-    }
-    ctx->cur = &ctx->bb_default;
-    if (!rc) rc = fgpu_pull_counters(ctx);     // (still in_replay: an overflow of the last walks is reported here, to scan_replay, not flagged for later)
-    ctx->in_replay = false;
-    ctx->scan_replays++;
-    return rc;
-}
-
-// every non-empty batch of the last load pass is resident with its read offsets (fgpu_scan_kept_state)
-static bool kept_complete(const fgpu_ctx* ctx) {
-    if (!ctx->keep_reads || ctx->phase == 1 || ctx->phase == 3 || ctx->resident_count != ctx->pass_batches) return false;
-    for (uint64_t i = 0; i < ctx->resident_count; i++)
-        if (!ctx->resident[i]->n_reads) return false;      // (a block adopted without its offsets: fgpu_load_batch_packed in such a pass)
-    return true;
-}
-
-int fgpu_scan_kept_state(fgpu_ctx* ctx, int* complete, uint64_t* n_batches, uint64_t* n_reads, uint64_t* bytes) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (complete) *complete = kept_complete(ctx) ? 1 : 0;
-    if (n_batches) *n_batches = ctx->resident_count;
-    if (n_reads) *n_reads = ctx->kept_reads_total;
-    if (bytes) *bytes = ctx->resident_bytes;
-    return FGPU_OK;
-}
-
-// kept batch i of the last load pass for a scan call `who`: after a plain pass every batch has to be there (fgpu_scan_kept_state); after a
-// sliced pass that keeps reads a rank holds offsets for the batches it packed or adopted them for, and is asked batch by batch
-static int kept_batch_at(fgpu_ctx* ctx, const char* who, uint64_t i, const ResidentBatch** out) {
-    const std::string w(who);
-    if (ctx->kept_sliced ? !ctx->keep_reads : !kept_complete(ctx)) {
-        ctx->err = w + ": the last load pass did not keep every batch with its reads (FGPU_LOAD_KEEP_READS, all batches inside the resident budget of " +
-                   std::to_string(ctx->resident_budget) + " bytes; " + std::to_string(ctx->resident_count) + " of " + std::to_string(ctx->pass_batches) + " batches are resident)";
-        return FGPU_ERR_STATE;
-    }
-    if (i >= ctx->resident_count) { ctx->err = w + ": no such batch (empty batches keep nothing)"; return FGPU_ERR_ARG; }
-    if (!ctx->resident[i]->n_reads) {
-        ctx->err = w + ": batch " + std::to_string(i) + " is resident without its read offsets (packed by another rank: fgpu_load_slice_adopt_reads brings them)";
-        return FGPU_ERR_STATE;
-    }
-    *out = ctx->resident[i];
-    return FGPU_OK;
-}
-
-int fgpu_scan_kept_range(fgpu_ctx* ctx, uint64_t lo, uint64_t hi, uint64_t max_read_len, int* complete) {
-    if (!ctx || !complete) return FGPU_ERR_ARG;
-    *complete = 0;
-    if (ctx->phase != 0) { ctx->err = "scan_kept_range while a pass is open: between the load pass and fgpu_scan_begin"; return FGPU_ERR_STATE; }
-    if (lo > hi) { ctx->err = "scan_kept_range: batches [lo, hi) with lo <= hi"; return FGPU_ERR_ARG; }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    if (ctx->stream) FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    if (int rc = fgpu_offs_check_report(ctx)) return rc;
-    if (!ctx->keep_reads || hi > ctx->resident_count || (!ctx->kept_sliced && !kept_complete(ctx))) return FGPU_OK;
-    for (uint64_t i = lo; i < hi; i++)
-        if (!ctx->resident[i]->n_reads) return FGPU_OK;
-    ctx->kept_max_read_len = std::max<uint64_t>(ctx->kept_max_read_len, max_read_len);      // the longest read of the PASS, over all ranks
-    *complete = 1;
-    return FGPU_OK;
-}
-
-int fgpu_scan_batch_kept(fgpu_ctx* ctx, uint64_t i, uint64_t* n_reads_out) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 2) { ctx->err = "scan_batch_kept outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
-    if (!ctx->prepared.empty()) { ctx->err = "scan_batch_kept while prepared batches are waiting: call fgpu_scan_walk_prepared first"; return FGPU_ERR_STATE; }
-    if (ctx->hint_in_table) { ctx->err = "the junction table holds a preview (fgpu_scan_import_hint): import the real table before walking"; return FGPU_ERR_STATE; }
-    const ResidentBatch* kept = nullptr;
-    if (int rc = kept_batch_at(ctx, "scan_batch_kept", i, &kept)) return rc;
-    if (n_reads_out) *n_reads_out = kept->n_reads;
-    return scan_batch_from(ctx, nullptr, kept);
-}
-
-int fgpu_scan_batch(fgpu_ctx* ctx, const fgpu_reads* reads) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 2) { ctx->err = "scan_batch outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
-    if (!ctx->prepared.empty()) { ctx->err = "scan_batch while prepared batches are waiting: call fgpu_scan_walk_prepared first"; return FGPU_ERR_STATE; }
-    if (ctx->hint_in_table) { ctx->err = "the junction table holds a preview (fgpu_scan_import_hint): import the real table before walking"; return FGPU_ERR_STATE; }
-    int rc = fgpu_check_reads(ctx, reads);
-    if (rc) return rc;
-    return scan_batch_from(ctx, reads, nullptr);
-}
-
-}  // extern "C"
-// pure stage + ordered walk of one batch, from its text (reads) or from a kept batch
-static int scan_batch_from(fgpu_ctx* ctx, const fgpu_reads* reads, const ResidentBatch* kept) {
-    int rc;
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    if (ctx->lazy_failed && (rc = scan_replay(ctx))) return rc;      // an earlier walk met a preview it could not repair: scan again, eagerly
-    BatchBufs* b = acquire_batch(ctx);
-    rc = scan_pure_into(ctx, b, reads, false, kept);          // main stream; overlaps the previous batch's walk on the walk stream
-    if (rc == FGPU_INTERNAL_REPLAY) {            // noticed while the buffers' previous lists were fetched: replay, then this batch from the start
-        ctx->cur = &ctx->bb_default;
-        ctx->pool.insert(ctx->pool.begin(), b);
-        if ((rc = scan_replay(ctx))) return rc;
-        b = acquire_batch(ctx);
-        rc = scan_pure_into(ctx, b, reads, false, kept);
-    }
-    if (!rc && ctx->lazy_failed) {
-        // noticed at this batch's own synchronisation: the batch is in the journal (prepared lazily); the replay scans it with the others
-        ctx->cur = &ctx->bb_default;
-        ctx->pool.push_back(b);
-        return scan_replay(ctx);
-    }
-    // records as of the pure stage's synchronisation (the previous walk may still be adding some): room for this batch's
-    if (!rc) rc = fgpu_scan_reserve(ctx, ctx->counters_host->n_junctions + ctx->scan_imported);
-    if (!rc) {
-        adapt_window(ctx);                       // counters as of the pure stage's synchronisation (the walk may lag one batch)
-        const double t_w = fgpu_host_now();
-        rc = fgpu_stage_scan_walk(ctx, b->n_pieces);
-        ctx->host_ms[5] += fgpu_host_now() - t_w;
-        ctx->walked_pieces += b->n_pieces;
-        if (!rc) note_walked(ctx, b);
-    }
-    ctx->cur = &ctx->bb_default;
-    ctx->pool.push_back(b);
-    return rc;
-}
-extern "C" {
-
-// the pure stage of one batch ahead of its walk, from its text (reads) or from a kept batch: the batch joins the prepared ones
-static int scan_prepare_from(fgpu_ctx* ctx, const fgpu_reads* reads, const ResidentBatch* kept) {
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    BatchBufs* b;
-    if (!ctx->pool.empty()) { b = ctx->pool.front(); ctx->pool.erase(ctx->pool.begin()); }
-    else b = new_batch(ctx);
-    int rc = scan_pure_into(ctx, b, reads, true, kept);
-    ctx->cur = &ctx->bb_default;
-    if (rc == FGPU_INTERNAL_REPLAY) {   // (only after walks of this scan: prepare-only scans never get here)
-        ctx->pool.insert(ctx->pool.begin(), b);
-        if ((rc = scan_replay(ctx))) return rc;
-        return scan_prepare_from(ctx, reads, kept);
-    }
-    if (rc) { ctx->pool.push_back(b); return rc; }
-    b->planes_gen = ctx->hint_in_table ? ctx->hint_gen : 0;      // what this batch's snapshot planes speak of
-    b->cand_gen = 0;
-    ctx->prepared.push_back(b);
-    return FGPU_OK;
-}
-
-int fgpu_scan_prepare(fgpu_ctx* ctx, const fgpu_reads* reads) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 2) { ctx->err = "scan_prepare outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
-    int rc = fgpu_check_reads(ctx, reads);
-    if (rc) return rc;
-    return scan_prepare_from(ctx, reads, nullptr);
-}
-
-int fgpu_scan_prepare_kept(fgpu_ctx* ctx, uint64_t i, uint64_t* n_reads_out) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 2) { ctx->err = "scan_prepare_kept outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
-    const ResidentBatch* kept = nullptr;
-    if (int rc = kept_batch_at(ctx, "scan_prepare_kept", i, &kept)) return rc;
-    if (n_reads_out) *n_reads_out = kept->n_reads;
-    return scan_prepare_from(ctx, nullptr, kept);
-}
-
-// Read shards: a FRESHER preview has taken the place of the one the batches were prepared against (fgpu_scan_import_hint again: the table the
-// shard below was handed, one hop before this shard's own arrives) -- the snapshot planes of every prepared batch are made again against it,
-// off the chain of walks.  When the real table arrives it differs from this preview by the keys ONE shard created, and the walk only has to
-// look for those (fgpu_scan_import_table).
-int fgpu_scan_refresh_prepared(fgpu_ctx* ctx) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 2) { ctx->err = "scan_refresh_prepared outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
-    if (!ctx->hint_in_table) { ctx->err = "scan_refresh_prepared without a preview in the table (fgpu_scan_import_hint)"; return FGPU_ERR_STATE; }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    const bool no_sparse = ctx->no_sparse_link;
-    for (BatchBufs* b : ctx->prepared) {
-        if (b->planes_gen != ctx->hint_gen) {
-            if (int rc = fgpu_scan_refresh_planes(ctx, b)) return rc;
-            b->planes_gen = ctx->hint_gen;
-            b->cand_gen = 0;
-        }
-        // ... and, while this rank still waits, the plane that lets its walk link a window by visiting candidates only (round 6, k_walk_link_sparse)
-        if (!no_sparse && b->cand_gen != ctx->hint_gen)
-            if (int rc = fgpu_scan_build_cand(ctx, b)) return rc;
-    }
-    ctx->launch_stream = ctx->stream;
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    return FGPU_OK;
-}
-
-int fgpu_scan_walk_prepared(fgpu_ctx* ctx) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 2) { ctx->err = "scan_walk_prepared outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
-    if (ctx->hint_in_table) { ctx->err = "the junction table holds a preview (fgpu_scan_import_hint): import the real table before walking"; return FGPU_ERR_STATE; }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    int rc = FGPU_OK;
-    if (ctx->lazy_failed) return scan_replay(ctx);      // (walks the prepared batches as well)
-    // The batches were prepared before their turn: their snapshot planes speak of a table that has since been replaced (the preview by the real
-    // table) and walked on, so they are made again by the walk stream right before every batch's walk (refresh_snapshot; making batch i + 1's
-    // beside batch i's walk instead was measured and is no faster: DESIGN.md section 10, profiles/r05_hop_refresh_ab.txt).
-    for (size_t i = 0; i < ctx->prepared.size() && !rc; i++) {
-        BatchBufs* b = ctx->prepared[i];
-        if (i > 0) {   // feedback for the window controller and for the size of the junction table between batches
-            if ((rc = fgpu_pull_counters(ctx))) break;                  // (the walk of batch i - 1 has finished; so have the planes of batch i)
-            if (ctx->lazy_failed) { ctx->cur = &ctx->bb_default; return scan_replay(ctx); }
-            if (!ctx->prm.walk_window_span) adapt_window(ctx);
-            if ((rc = fgpu_scan_reserve(ctx, ctx->counters_host->n_junctions + ctx->scan_imported))) break;
-        }
-        ctx->cur = b;
-        ctx->refresh_snapshot = true;
-        rc = fgpu_stage_scan_walk(ctx, b->n_pieces);
-        ctx->refresh_snapshot = false;
-        ctx->walked_pieces += b->n_pieces;
-        if (!rc) note_walked(ctx, b);
-    }
-    ctx->cur = &ctx->bb_default;
-    for (BatchBufs* b : ctx->prepared) ctx->pool.push_back(b);
-    ctx->prepared.clear();
-    return rc;
-}
-
-int fgpu_scan_set_eager(fgpu_ctx* ctx, int on) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 0) { ctx->err = "fgpu_scan_set_eager while a pass is open"; return FGPU_ERR_STATE; }
-    ctx->eager_runtime = on != 0;
-    return FGPU_OK;
-}
-
-// ---- the short pair filter on the device ---------------------------------------------------------------------------------
-int fgpu_scan_short_pairs(fgpu_ctx* ctx, uint64_t tai, int32_t n_hash, int32_t lists_to_host) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 0) { ctx->err = "fgpu_scan_short_pairs while a pass is open"; return FGPU_ERR_STATE; }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    if (ctx->short_pf) {
-        FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-        FGPU_HIP(hipFree(ctx->short_pf));
-        ctx->short_pf = nullptr;
-        ctx->short_pf_tai = 0;
-    }
-    if (!tai) return FGPU_OK;
-    if (!ctx->record_stops) { ctx->err = "fgpu_scan_short_pairs needs FGPU_FLAG_RECORD_STOPS"; return FGPU_ERR_STATE; }
-    if (!is_pow2(tai) || tai < 128 || n_hash < 1 || n_hash > 32) { ctx->err = "fgpu_scan_short_pairs: tai must be a power of two >= 128, n_hash 1..32"; return FGPU_ERR_ARG; }
-    FGPU_HIP(hipMalloc(&ctx->short_pf, tai / 8));
-    FGPU_HIP(hipMemsetAsync(ctx->short_pf, 0, tai / 8, ctx->stream));
-    ctx->short_pf_tai = tai;
-    ctx->short_pf_hashes = n_hash;
-    ctx->short_pf_lists_to_host = lists_to_host != 0;
-    return FGPU_OK;
-}
-
-int fgpu_scan_short_pairs_download(fgpu_ctx* ctx, uint8_t* out, uint64_t n_bytes) {
-    if (!ctx || !out) return FGPU_ERR_ARG;
-    if (!ctx->short_pf) { ctx->err = "fgpu_scan_short_pairs_download without fgpu_scan_short_pairs"; return FGPU_ERR_STATE; }
-    if (ctx->phase != 0) { ctx->err = "fgpu_scan_short_pairs_download while a pass is open"; return FGPU_ERR_STATE; }
-    if (n_bytes != ctx->short_pf_tai / 8) { ctx->err = "fgpu_scan_short_pairs_download: the filter has tai / 8 bytes"; return FGPU_ERR_ARG; }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    FGPU_HIP(hipMemcpyAsync(out, ctx->short_pf, n_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    return FGPU_OK;
-}
-
-int fgpu_scan_take_stops(fgpu_ctx* ctx, fgpu_stop* out, uint64_t cap, uint64_t* n_out, int64_t* batch_seq) {
-    if (!ctx || !n_out || !batch_seq) return FGPU_ERR_ARG;
-    if (!ctx->record_stops) { ctx->err = "fgpu_scan_take_stops needs FGPU_FLAG_RECORD_STOPS"; return FGPU_ERR_STATE; }
-    *n_out = 0;
-    *batch_seq = -1;
-    if (ctx->phase == 2 && ctx->lazy_failed) {
-        if (int rc = scan_replay(ctx)) return rc;
-    }
-    if (ctx->stop_queue.empty() && !ctx->to_harvest.empty()) {
-        FGPU_HIP(hipSetDevice(ctx->prm.device));
-        int rc = fgpu_scan_harvest(ctx, ctx->to_harvest.front());
-        if (rc == FGPU_INTERNAL_REPLAY && ctx->phase == 2) {
-            if ((rc = scan_replay(ctx))) return rc;
-            if (!ctx->to_harvest.empty()) rc = fgpu_scan_harvest(ctx, ctx->to_harvest.front());
-        }
-        if (rc) return rc;
-    }
-    if (ctx->stop_queue.empty()) return FGPU_OK;
-    StopBatch& sb = ctx->stop_queue.front();
-    *n_out = sb.n;
-    *batch_seq = (int64_t)sb.seq;
-    if (sb.n > cap || (sb.n && !out)) return FGPU_ERR_CAPACITY;
-    if (sb.n) memcpy(out, sb.data, sb.n * sizeof(fgpu_stop));
-    ctx->stops_delivered = sb.seq + 1;
-    if (sb.data) { StopBatch f; f.data = sb.data; f.cap = sb.cap; ctx->stop_pool.push_back(f); }
-    ctx->stop_queue.pop_front();
-    return FGPU_OK;
-}
-
-int fgpu_scan_end(fgpu_ctx* ctx, fgpu_scan_stats* stats) {
-    if (!ctx) return FGPU_ERR_ARG;
-    if (ctx->phase != 2) { ctx->err = "scan_end without scan_begin"; return FGPU_ERR_STATE; }
-    static const bool dbg_host = getenv("FGPU_DEBUG_HOST") != nullptr;
-    static const bool dbg_waits = getenv("FGPU_DEBUG_WAITS") != nullptr;
-    struct TellWaits {      // (at the very end of the call: the last walks and harvests are waited for inside it)
-        fgpu_ctx* c;
-        bool on;
-        ~TellWaits() {
-            if (!on) return;
-            for (const WaitSite& w : c->wait_sites) {
-                const char* f = strrchr(w.file, '/');
-                fprintf(stderr, "[waits] %-14s:%-5d %6llu times %9.2f ms\n", f ? f + 1 : w.file, w.line, (unsigned long long)w.n, w.ms);
-            }
-        }
-    } tell_waits{ctx, dbg_waits};
-    if (dbg_host) {
-        fprintf(stderr, "[host] scan: wait for the buffers' last walk %.2f ms, pack issue %.2f, pure stage issue (first half) %.2f, wait for the piece count %.2f, "
-                        "pure stage issue (second half) %.2f, walk issue %.2f\n", ctx->host_ms[0], ctx->host_ms[1], ctx->host_ms[2], ctx->host_ms[3], ctx->host_ms[4], ctx->host_ms[5]);
-        for (double& v : ctx->host_ms) v = 0;
-    }
-    int rc = fgpu_pull_counters(ctx);
-    if (!rc && ctx->lazy_failed) {                          // the last walks met a preview they could not repair: scan again before closing
-        rc = scan_replay(ctx);
-        if (!rc) rc = fgpu_pull_counters(ctx);
-    }
-    while (!rc && !ctx->to_harvest.empty()) rc = fgpu_scan_harvest(ctx, ctx->to_harvest.front());   // every walk has finished
-    if (!rc) rc = fgpu_long_pairs_close(ctx);              // the last batch of lists: its rounds' outcome, a first end left without a mate
-    ctx->phase = 0;
-    ctx->journal_on = false;
-    if (!rc && !ctx->prm.walk_window_span && ctx->scan_windows > 8) ctx->settled_span = ctx->window_span;
-    if (rc) return rc;
-    const DevCounters& c = *ctx->counters_host;
-    fgpu_scan_stats& s = ctx->scan_stats;
-    s.unambiguous_reads = c.segments + ctx->carried.unambiguous_reads;
-    s.reads_no_errors = c.pieces + ctx->carried.reads_no_errors;
-    s.nb_jcheck_kmer = c.nb_jcheck + ctx->carried.nb_jcheck_kmer;
-    s.nb_no_juncs = c.nb_no_juncs + ctx->carried.nb_no_juncs;
-    s.nb_processed = c.nb_processed + ctx->carried.nb_processed;
-    s.nb_skipped = c.nb_skipped + ctx->carried.nb_skipped;
-    s.n_junctions = c.n_junctions + ctx->scan_imported;
-    s.kmers = c.kmers + ctx->carried.kmers;
-    s.reads_processed += ctx->carried.reads_processed;
-    s.walk_windows = ctx->scan_windows;
-    s.walk_followers = c.followers;
-    s.walk_max_cluster = c.max_cluster;
-    s.flag_positions = c.flag_positions;
-    s.piece_positions = c.piece_positions;
-    s.valid_reused = c.valid_reused;
-    s.flags_filled = c.flags_filled;
-    s.walk_parallel = c.walk_parallel;
-    memset(&ctx->carried, 0, sizeof(ctx->carried));
-    if (stats) *stats = s;
-    return FGPU_OK;
-}
-
-int fgpu_scan_junction_count(fgpu_ctx* ctx, uint64_t* n) {
-    if (!ctx || !n) return FGPU_ERR_ARG;
-    if (int rc = sync_all(ctx)) return rc;
-    return fgpu_scan_download_impl(ctx, nullptr, nullptr, 0, n);
-}
-
-int fgpu_scan_download_junctions(fgpu_ctx* ctx, uint64_t* keys, fgpu_junction* recs, uint64_t cap, uint64_t* n_out) {
-    if (!ctx || !keys || !recs || !n_out) return FGPU_ERR_ARG;
-    if (!ctx->jkeys) { *n_out = 0; return FGPU_OK; }
-    if (int rc = sync_all(ctx)) return rc;
-    return fgpu_scan_download_impl(ctx, keys, recs, cap, n_out);
-}
-
-int fgpu_scan_table_entries(fgpu_ctx* ctx, uint64_t* n_entries) { return fgpu_scan_junction_count(ctx, n_entries); }
-
-int fgpu_scan_dump_order(fgpu_ctx* ctx, const uint64_t* rehash_counts, const uint64_t* rehash_buckets, uint64_t n_rehashes, uint64_t n, uint32_t* order) {
-    if (!ctx || !rehash_counts || !rehash_buckets || !n_rehashes || (n && !order)) return FGPU_ERR_ARG;
-    if (ctx->phase != 0) { ctx->err = "fgpu_scan_dump_order while a pass is open"; return FGPU_ERR_STATE; }
-    if (!ctx->dl_keys_n || n > ctx->dl_keys_n) { ctx->err = "fgpu_scan_dump_order works on the keys of the last fgpu_scan_download_junctions (at most that many)"; return FGPU_ERR_STATE; }
-    FGPU_HIP(hipSetDevice(ctx->prm.device));
-    return fgpu_scan_dump_order_impl(ctx, (const uint64_t*)ctx->dl_keys.p, rehash_counts, rehash_buckets, n_rehashes, n, order);
-}
-
-int fgpu_scan_export_table(fgpu_ctx* ctx, void* dev_buf, uint64_t buf_bytes, uint64_t* n_entries) {
-    if (!ctx || !dev_buf || !n_entries) return FGPU_ERR_ARG;
-    uint64_t n = 0;
-    int rc = sync_all(ctx);   // walks still running on the walk stream are part of the table
-    if (!rc) rc = fgpu_scan_junction_count(ctx, &n);
-    if (rc) return rc;
-    if (buf_bytes < n * FGPU_TABLE_ENTRY_BYTES) { ctx->err = "export buffer too small"; return FGPU_ERR_CAPACITY; }
-    if ((rc = fgpu_ensure(ctx, &ctx->export_stamps, n * 8 + 8))) return rc;
-    return fgpu_scan_export_impl(ctx, dev_buf, n, (uint64_t*)ctx->export_stamps.p, n_entries);
-}
-
-int fgpu_scan_import_table(fgpu_ctx* ctx, const void* dev_buf, uint64_t n_entries, const fgpu_scan_stats* carried) {
-    if (!ctx || (n_entries && !dev_buf)) return FGPU_ERR_ARG;
-    if (ctx->phase != 2) { ctx->err = "import_table outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
-    int rc = sync_all(ctx);
-    if (rc) return rc;
-    ctx->delta_ready = false;
-    if (ctx->hint_in_table) {   // the preview has done its work (the prepared batches' planes): the real table takes its place
-        if ((rc = fgpu_scan_clear_table(ctx))) return rc;
-        ctx->hint_in_table = false;
-        // If every prepared batch's planes speak of the newest preview and this table is a LATER STATE of it (the caller's promise, checked by
-        // counting: the entries with a creation stamp beyond the preview's are exactly the surplus), the walk merges the new keys into the planes
-        // through a filter of just those keys instead of probing the whole table's filter at every position again (22 -> ~7 ms per 25 M reads).
-        static const bool no_delta = getenv("FGPU_NO_DELTA_REFRESH") != nullptr;
-        bool all = ctx->hint_gen != 0 && !ctx->prepared.empty() && !no_delta && n_entries >= ctx->hint_n;
-        for (BatchBufs* b : ctx->prepared) all = all && b->planes_gen == ctx->hint_gen;
-        const uint64_t surplus = all ? n_entries - ctx->hint_n : 0;
-        if (all && surplus <= (1ULL << 23)) {
-            uint64_t bits = 1ULL << 20;      // (room for what this shard's own batches will add: they join the filter as they are walked)
-            // (32 bits of filter per new key, swept in round 6 on config 4's hop, 8 / 16 / 32 / 64 bits per key: the merge 16.4 / 14.4 / 13.0 / 13.9 ms, the
-            // link by the candidate plane -- which takes the filter's hits -- 11.6 / 9.7 / 8.7 / 8.2 ms, the hop 71.1 / 67.6 / 64.8 / 66.0 ms: false hits cost more than cache misses)
-            while (bits < 32 * surplus) bits <<= 1;
-            if ((rc = fgpu_ensure(ctx, &ctx->delta_filter, bits / 8))) return rc;
-            FGPU_HIP(hipMemsetAsync(ctx->delta_filter.p, 0, bits / 8, ctx->stream));
-            uint64_t max_seq = 0, newer = 0, digest[2] = {0, 0};
-            if ((rc = fgpu_scan_import_probe(ctx, dev_buf, n_entries, ctx->hint_max_seq, (uint32_t*)ctx->delta_filter.p, bits, &max_seq, &newer, digest))) return rc;
-            // a later state of the preview: as many newer entries as the surplus, AND the others are the preview's keys (their digest)
-            if (newer == surplus && digest[0] == ctx->hint_digest[0] && digest[1] == ctx->hint_digest[1]) {
-                ctx->delta_ready = true;
-                ctx->delta_filter_bits = bits;
-                ctx->delta_keys = newer;
-            }
-        }
-    }
-    if ((rc = fgpu_scan_reserve(ctx, ctx->counters_host->n_junctions + ctx->scan_imported + n_entries))) return rc;
-    rc = fgpu_scan_import_impl(ctx, dev_buf, n_entries);
-    if (rc) return rc;
-    if (ctx->journal_on) {   // a replay starts from this table again
-        if ((rc = fgpu_ensure(ctx, &ctx->import_copy, n_entries * FGPU_TABLE_ENTRY_BYTES + 16))) return rc;
-        if (n_entries) FGPU_HIP(hipMemcpyAsync(ctx->import_copy.p, dev_buf, n_entries * FGPU_TABLE_ENTRY_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
-        ctx->import_n = n_entries;
-        ctx->have_import = true;
-        ctx->import_has_carried = carried != nullptr;
-        if (carried) ctx->import_carried = *carried;
-    }
-    // the import runs on the main stream, the ordered walk on the walk stream behind events recorded BEFORE this call
-    // (end of each prepared batch's pure stage): without this wait the walk would start on a half-imported table
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    ctx->scan_imported += n_entries;
-    if (carried) ctx->carried = *carried;
-    // creation stamps of this shard must sort after everything imported
-    ctx->scan_piece_base = std::max<uint64_t>(ctx->scan_piece_base, carried ? carried->reads_no_errors : 0);
-    return FGPU_OK;
-}
-
-int fgpu_scan_import_hint(fgpu_ctx* ctx, const void* dev_buf, uint64_t n_entries) {
-    if (!ctx || (n_entries && !dev_buf)) return FGPU_ERR_ARG;
-    if (ctx->phase != 2) { ctx->err = "import_hint outside scan_begin/scan_end"; return FGPU_ERR_STATE; }
-    if (ctx->scan_windows || ctx->scan_imported) {
-        ctx->err = "import_hint comes before any walk and before the real table (batches prepared earlier have simply seen an empty table)";
-        return FGPU_ERR_STATE;
-    }
-    int rc = sync_all(ctx);
-    if (rc) return rc;
-    if (ctx->hint_in_table && (rc = fgpu_scan_clear_table(ctx))) return rc;      // a fresher preview takes the place of an older one
-    if ((rc = fgpu_scan_reserve(ctx, n_entries))) return rc;
-    if ((rc = fgpu_scan_import_impl(ctx, dev_buf, n_entries))) return rc;
-    uint64_t newer = 0;
-    ctx->hint_max_seq = 0;
-    if ((rc = fgpu_scan_import_probe(ctx, dev_buf, n_entries, ~0ULL, nullptr, 0, &ctx->hint_max_seq, &newer, ctx->hint_digest))) return rc;
-    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
-    ctx->hint_in_table = true;
-    ctx->hint_n = n_entries;
-    ctx->hint_gen++;
-    return FGPU_OK;
-}
-
 // ---- probes ----------------------------------------------------------------------------------------------------
 int fgpu_probe_hash(fgpu_ctx* ctx, const uint64_t* kmers_host, uint64_t n, uint64_t* canon_out, uint64_t* hA_out, uint64_t* hB_out) {
     if (!ctx || !kmers_host || !canon_out || !hA_out || !hB_out) return FGPU_ERR_ARG;
@@ -1657,7 +796,7 @@ int fgpu_diag_ko_trace(fgpu_ctx* ctx, uint64_t* out, uint64_t cap_records, uint6
     if (!ctx || !n) return FGPU_ERR_ARG;
     *n = 0;
     if (!ctx->ko_trace.p) return FGPU_OK;
-    if (int rc = sync_all(ctx)) return rc;
+    if (int rc = fgpu_sync_all(ctx)) return rc;
     unsigned long long cnt = 0;
     FGPU_HIP(hipMemcpy(&cnt, ctx->ko_trace.p, 8, hipMemcpyDeviceToHost));
     if (cnt > (1ULL << 21)) cnt = 1ULL << 21;
@@ -1672,7 +811,7 @@ int fgpu_diag_ko_stamps(fgpu_ctx* ctx, uint64_t* out, uint64_t cap_words, uint64
     if (!ctx || !n_pieces) return FGPU_ERR_ARG;
     *n_pieces = 0;
     if (!ctx->ko_trace.p || ctx->ko_trace.bytes < ((1ULL << 23) + 4096 * 1024) * 8) return FGPU_OK;
-    if (int rc = sync_all(ctx)) return rc;
+    if (int rc = fgpu_sync_all(ctx)) return rc;
     unsigned long long cnt = 0;
     FGPU_HIP(hipMemcpy(&cnt, (const char*)ctx->ko_trace.p + 8, 8, hipMemcpyDeviceToHost));
     if (cnt > 4096) cnt = 4096;

@@ -14,21 +14,11 @@
 #include <deque>
 
 #include "fgpu_device.h"
+#include "walk_span.h"
 
 // every per-position plane / code array carries this many padding words past ceil(T/64): kernels run
 // whole 256-thread blocks and funnel-read one word ahead
 #define FGPU_PADW 8
-// Scheduling windows of the ordered walk, in stream positions.  A window grows (x4, up to FGPU_MAX_SPAN) while fewer than a third of its
-// pieces queue behind another piece of their cluster and is halved above a half.  Since the walk takes its in-map bits from the batch's
-// snapshot planes and registers the keys created since then per window (round 2), a window's fixed costs -- the delta registrations, five
-// launches -- weigh more than the longer clusters of a larger window: config 2 measured 131.3 / 127.0 / 126.0 ms per step at 2^24 / 2^25 /
-// 2^26 positions (16 % / 27 % / 36 % of the pieces queueing; round 1's look-up kernel per window had its optimum at 2^24; round 4, with
-// dynamic cluster hand-out and no event brackets: 121.9 / 117.4 / 118.7 ms at 25 % / 43 % / 58 %).  How the size moves from batch to batch:
-// adapt_window (api.hip).  The window
-// tables are sized for the context's bound, FGPU_MAX_SPAN (2 GiB) for filters up to 2^30 bits, more for larger ones (fgpu_create).
-#define FGPU_USUAL_SPAN (1ULL << 26)
-#define FGPU_MAX_SPAN (1ULL << 26)
-
 // events per batch for the ranges of the pure stage's back half (BatchBufs::range_ev)
 #define FGPU_RANGE_EVENTS 16
 // ... and the shortest range the default policy cuts off: a range costs three launches, an event and the thin end of its junction-test kernel
@@ -368,9 +358,7 @@ struct fgpu_ctx {
     uint32_t* cl_members = nullptr;
     uint32_t* cl_roots = nullptr;      // per window: [0] leaders listed, [1] handed out, from word 16 on the list of the clusters' leaders (k_walk_dyn)
     void* wdesc = nullptr;           // device WinDesc of the window in flight
-    uint64_t window_span = 1ULL << 17;   // adaptive: stream positions per scheduling window
-    uint64_t max_span = FGPU_MAX_SPAN;   // upper bound of window_span (sizes the window table)
-    uint64_t settled_span = 0;       // window_span at the end of the context's previous scan (0: none yet): where the next one starts from
+    WalkSpan span;                   // the window-span controller: stream positions per scheduling window and how they move (walk_span.h)
     uint64_t scan_piece_base = 0;    // pieces walked by earlier batches (creation stamps)
     uint64_t scan_imported = 0;      // junction records imported from a previous shard
     bool hint_in_table = false;      // fgpu_scan_import_hint: the table holds a preview, not the state to walk on
@@ -402,17 +390,8 @@ struct fgpu_ctx {
     uint64_t scan_windows = 0;
     uint64_t scan_pieces_seen = 0;   // pieces counted by previous batches of this scan
 
-    uint64_t adapt_followers = 0, adapt_pieces = 0;   // window-span controller state
     double host_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // FGPU_DEBUG_HOST=1: where the host thread of a scan spends its time (see fgpu_scan_end)
-    bool repeats_seen_before = false;  // this scan's counters have shown repeats (kept while a lagging snapshot shows too few pieces to judge)
-    uint64_t calib_ovf = 0;            // ko_overflows as of the last look (a window whose large clusters outgrew the large-cluster walks' tables)
-    uint64_t span_ceiling = ~0ULL;     // a size at which that happened in this scan: the windows do not grow to it again
-    int adapt_vote = 0;                // what the last batch's counters asked for without getting it yet (-1 smaller, +1 larger)
-    uint64_t proven_span = 0;          // largest window size a batch of this context was walked at without most pieces queueing
-    uint64_t adapt_overflows = 0;
-    int calib_left = 0;              // windows the controller still waits for individually (start of a scan, after a bad batch)
-    uint64_t calib_f = 0, calib_p = 0;
-    unsigned long long* fb_host = nullptr;   // pinned: {followers, walked pieces} read back during calibration
+    unsigned long long* fb_host = nullptr;   // pinned: {followers, walked pieces, ko_overflows} read back during calibration
     fgpu_scan_stats carried = {};    // counters handed over by the previous shard (multi-GPU)
 
     BatchBufs bb_default;                 // the batch of load_batch / scan_batch
@@ -617,8 +596,12 @@ int fgpu_epoch_before_batch(fgpu_ctx* ctx, uint64_t span);
 int fgpu_epoch_after_batch(fgpu_ctx* ctx, uint64_t span);
 enum { FGPU_TAKE_OK = 0, FGPU_TAKE_NO_BUDGET, FGPU_TAKE_NO_MEMORY };
 int fgpu_resident_take(fgpu_ctx* ctx, const uint64_t (&parts)[5], bool budgeted, ResidentBatch** out, uint64_t* total);
-// what the sliced pass' entry points share with api.hip
+// what the sliced pass' entry points and the scan pass' driver (scan_driver.hip) share with api.hip
 int fgpu_pull_counters(fgpu_ctx* ctx);
+int fgpu_check_errors(fgpu_ctx* ctx);                        // the device's error flags as of the last copy of the counters: an error, or a replay noted for later
+int fgpu_sync_all(fgpu_ctx* ctx);                            // everything issued so far, on every stream, has completed
+void fgpu_stop_queue_recycle(fgpu_ctx* ctx);                 // harvested lists nobody took: their page-locked buffers go back to the pool
+static inline bool fgpu_is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 int fgpu_check_reads(fgpu_ctx* ctx, const fgpu_reads* r);
 void fgpu_load_pass_policy(fgpu_ctx* ctx);
 int fgpu_load_pass_counters(fgpu_ctx* ctx);
@@ -661,3 +644,6 @@ int fgpu_scan_reserve(fgpu_ctx* ctx, uint64_t records);
 int fgpu_scan_clear_table(fgpu_ctx* ctx);
 int fgpu_scan_dump_order_impl(fgpu_ctx* ctx, const uint64_t* d_keys, const uint64_t* counts, const uint64_t* buckets, uint64_t n_phases, uint64_t n, uint32_t* order_host);
 int fgpu_scan_regrow_empty(fgpu_ctx* ctx, uint64_t new_cap);
+int fgpu_scan_export_impl(fgpu_ctx* ctx, void* dev_entries, uint64_t cap_entries, uint64_t* d_stamps, uint64_t* n_entries);
+int fgpu_scan_import_impl(fgpu_ctx* ctx, const void* dev_entries, uint64_t n);
+int fgpu_scan_download_impl(fgpu_ctx* ctx, uint64_t* keys_host, fgpu_junction* recs_host, uint64_t cap, uint64_t* n_out);

@@ -612,7 +612,7 @@ static void scan_range_plan(const fgpu_ctx* ctx, const BatchBufs& bb, bool one_r
     *first = *further = whole;
     if (one_range || !bb.range_ev[0] || ctx->scan_range_log2 == 0) return;
     if (ctx->scan_range_log2 > 0) { *first = *further = 1ULL << ctx->scan_range_log2; return; }
-    const uint64_t span = ctx->window_span;      // (as of the previous batch's walk: the controller may move it before this batch's -- later waits, same results)
+    const uint64_t span = ctx->span.window_span;      // (as of the previous batch's walk: the controller may move it before this batch's -- later waits, same results)
     if (span >= bb.T || bb.T < 2 * FGPU_RANGE_MIN) return;
     const uint64_t n_windows = (bb.T + span - 1) / span;
     uint64_t m = (uint64_t)(2.0 * (double)bb.T / (3.0 * (double)span) + 0.5);

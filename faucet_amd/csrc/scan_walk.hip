@@ -2532,13 +2532,13 @@ int fgpu_scan_alloc(fgpu_ctx* ctx) {
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            while (ctx->max_span > FGPU_MAX_SPAN && 40ULL * ctx->max_span > free_b / 4) ctx->max_span >>= 1;
+            while (ctx->span.max_span > FGPU_MAX_SPAN && 40ULL * ctx->span.max_span > free_b / 4) ctx->span.max_span >>= 1;
         (void)hipGetLastError();
     }
     for (;;) {
-        while (ctx->max_span / (uint64_t)(ctx->fd.k + 1) + 2 >= W_OWNER_MASK) ctx->max_span >>= 1;   // piece indices of a window fit the table's owner field
-        ctx->wcap = 4 * ctx->max_span;
-        ctx->wmax = (uint32_t)(ctx->max_span / (uint64_t)(ctx->fd.k + 1) + 2);
+        while (ctx->span.max_span / (uint64_t)(ctx->fd.k + 1) + 2 >= W_OWNER_MASK) ctx->span.max_span >>= 1;   // piece indices of a window fit the table's owner field
+        ctx->wcap = 4 * ctx->span.max_span;
+        ctx->wmax = (uint32_t)(ctx->span.max_span / (uint64_t)(ctx->fd.k + 1) + 2);
         struct { void** p; uint64_t bytes; } want[] = {
             {(void**)&ctx->jkeys, ctx->jcap * 8}, {(void**)&ctx->jrecs, ctx->jcap * 32}, {(void**)&ctx->jstamps, ctx->jcap * 16}, {(void**)&ctx->jfilter, ctx->jcap * 2 / 8},
             {(void**)&ctx->wdesc, 64}, {(void**)&ctx->wkeys, ctx->wcap * 8},
@@ -2557,11 +2557,11 @@ int fgpu_scan_alloc(fgpu_ctx* ctx) {
         if (err == hipSuccess) return FGPU_OK;
         (void)hipGetLastError();
         for (auto& w : want) { if (*w.p) hipFree(*w.p); *w.p = nullptr; }
-        if (ctx->max_span <= FGPU_MAX_SPAN) {
+        if (ctx->span.max_span <= FGPU_MAX_SPAN) {
             ctx->err = std::string("the scan's tables do not fit the device (hipMalloc of ") + std::to_string(failed_bytes) + " bytes: " + hipGetErrorString(err) + ")";
             return FGPU_ERR_NOMEM;
         }
-        ctx->max_span >>= 1;                                                            // smaller windows: slower on thin coverage, same results
+        ctx->span.max_span >>= 1;                                                            // smaller windows: slower on thin coverage, same results
     }
 }
 
@@ -2909,8 +2909,8 @@ static LargeClusterRule large_cluster_rule(fgpu_ctx* ctx, const WalkKnobs& kn) {
     // (the windows grow from 62 to 22: what is left to k_walk_dyn no longer queues), while config 2 with the CLI's settings would pay 10 ms per
     // step for the lower bar (walk stage 52.6 -> 62.6 ms; scripts/ovw_thresholds.sh, gpurun_out/r04_ovw_thresholds2.txt).
     const bool repeats_seen = seen.walk_parallel * 50 > seen.walked_pieces ||
-                              (ctx->walk_ko_always && seen.walked_pieces < (1ULL << 17) && ctx->delta_next >= 2 && ctx->repeats_seen_before);   // (same lag: keep what the scan had found)
-    if (repeats_seen) ctx->repeats_seen_before = true;
+                              (ctx->walk_ko_always && seen.walked_pieces < (1ULL << 17) && ctx->delta_next >= 2 && ctx->span.repeats_seen_before);   // (same lag: keep what the scan had found)
+    if (repeats_seen) ctx->span.repeats_seen_before = true;
     const uint32_t ko_total = std::min<uint32_t>(ctx->walk_ko_weight, 0xFFFFu);
     const uint32_t ko_avg = kn.ko_avg >= 0 ? (uint32_t)kn.ko_avg : repeats_seen ? 8u : 12u;
     const uint32_t ko_total_rep = kn.ko_avg_min > 0 ? (uint32_t)kn.ko_avg_min : repeats_seen ? 16u : std::min<uint32_t>(255u, 3 * ko_total / 8);
@@ -3094,55 +3094,20 @@ static int walk_collect_and_reset(fgpu_ctx* ctx, const WalkBatch& wb, const Walk
     return FGPU_OK;
 }
 
-// Calibration: at the start of a scan (and again whenever a batch came out with most of its pieces queueing) the host
-// waits for the window it has just issued and looks at the share of pieces that had to queue behind an earlier piece of
-// their cluster.  High coverage makes clusters percolate -- 250x reads of a small genome were 20x slower with the 4 M
-// position windows that suit 50x data -- and a whole batch is too long to walk with the wrong size.
-// *span_now: the span of the windows that follow.
+// The look at a window just issued, while the controller still asks for looks (WalkSpan::after_window decides): the host waits for the window
+// and reads back the three counters.  *span_now: the span of the windows that follow.
 static int walk_span_look(fgpu_ctx* ctx, const WalkKnobs& kn, hipStream_t walk_stream, uint64_t* span_now) {
-    if (ctx->calib_left <= 0 || ctx->prm.walk_window_span) return FGPU_OK;
+    if (ctx->span.calib_left <= 0 || ctx->prm.walk_window_span) return FGPU_OK;
     FGPU_HIP(hipMemcpyAsync(ctx->fb_host, &ctx->counters->followers, 8, hipMemcpyDeviceToHost, walk_stream));
     FGPU_HIP(hipMemcpyAsync(ctx->fb_host + 1, &ctx->counters->walked_pieces, 8, hipMemcpyDeviceToHost, walk_stream));
     FGPU_HIP(hipMemcpyAsync(ctx->fb_host + 2, &ctx->counters->ko_overflows, 8, hipMemcpyDeviceToHost, walk_stream));
     FGPU_HIP(fgpu_sync_stream(ctx, walk_stream));
-    uint64_t span = *span_now;
-    const uint64_t f = ctx->fb_host[0] - ctx->calib_f, p = ctx->fb_host[1] - ctx->calib_p;
-    if (ctx->fb_host[2] > ctx->calib_ovf && span > 4096) {
-        // the window's large clusters outgrew the tables of the large-cluster walks (their pieces do not queue, so the share of
-        // followers says nothing about them) and were walked by one thread each: far too large a window for this data -- a quarter,
-        // and the next windows are looked at as well (round 4: read pairs inside repeats at 600x, a 36 MB file whose windows grew to
-        // 2^23 positions within its three batches: pass 2 2.0 s, 0.8 s with windows of 2^20)
-        ctx->calib_ovf = ctx->fb_host[2];
-        ctx->calib_f = ctx->fb_host[0];
-        ctx->calib_p = ctx->fb_host[1];
-        span = std::max<uint64_t>(4096, span / 4);
-        ctx->proven_span = std::min(ctx->proven_span, span);
-        ctx->calib_left = std::max(ctx->calib_left, 4);
-        ctx->span_ceiling = std::min(ctx->span_ceiling, span * 2);     // (this scan does not grow to that size again)
-        if (kn.dbg_span) fprintf(stderr, "[span] look: the large-cluster walks' tables overflowed -> span %llu, looks left %d\n", (unsigned long long)span, ctx->calib_left);
-    } else if (p >= 64) {
-        ctx->calib_f = ctx->fb_host[0];
-        ctx->calib_p = ctx->fb_host[1];
-        bool shrunk = false;
-        const uint64_t ceiling = std::min<uint64_t>(ctx->max_span, ctx->span_ceiling), usual = std::min<uint64_t>(ceiling, FGPU_USUAL_SPAN);
-        if (f * 2 > p && span > 4096) { span /= 2; shrunk = true; }
-        else if (f * 3 < p && span < usual) span = std::min<uint64_t>(span * 4, usual);
-        else if (f * 16 < p && span < ceiling) span = std::min<uint64_t>(span * 4, ceiling);
-        else ctx->calib_left = 1;          // settled
-        ctx->calib_left--;
-        // waiting for a window keeps the host from feeding the pure stage of the next batch: worth it while windows are small
-        // (a fraction of a millisecond each, and the wrong size hurts most there); from 2^22 positions on the per-batch
-        // controller (adapt_window, no waiting) takes over unless the last look said "too large"
-        if (!shrunk && span >= (1ULL << 22)) ctx->calib_left = 0;
-        if (kn.dbg_span) fprintf(stderr, "[span] look: followers %llu of %llu pieces -> span %llu, looks left %d\n", (unsigned long long)f, (unsigned long long)p,
-                                 (unsigned long long)span, ctx->calib_left);
-    }
-    *span_now = span;
+    ctx->span.after_window(ctx->fb_host[0], ctx->fb_host[1], ctx->fb_host[2], span_now, kn.dbg_span);
     return FGPU_OK;
 }
 
 // Walk the pieces of the current batch, scheduling window after scheduling window (position ranges of
-// ctx->window_span stream positions).  No host round trip: window extents are derived on the device.
+// ctx->span.window_span stream positions).  No host round trip: window extents are derived on the device.
 int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
     if (!n_pieces) return FGPU_OK;
     const WalkKnobs& kn = walk_knobs();
@@ -3161,9 +3126,9 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
         pl.sF = (unsigned long long*)bb.sF.p;
         pl.sB = (unsigned long long*)bb.sB.p;
     }
-    const uint64_t span = ctx->window_span;
+    const uint64_t span = ctx->span.window_span;
     const uint64_t ext = bb.max_piece_span;          // a piece that starts inside the window may reach this far beyond it
-    if (ctx->max_span + ext + 64 > ctx->wcap) {      // the per-position slot list of a window is sized for 4 x the largest span
+    if (ctx->span.max_span + ext + 64 > ctx->wcap) {      // the per-position slot list of a window is sized for 4 x the largest span
         ctx->err = "a read of " + std::to_string(ext) + " bases is longer than the walk's window tables allow";
         return FGPU_ERR_CAPACITY;
     }
@@ -3208,7 +3173,7 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
     // slower on the whole batch (hop of config 4 on 8 shards, 23 windows -> 14: k_walk_dyn 22.3 -> 22.6 ms, the link passes 12.7 -> 8.7, the hop
     // 69.1 -> 64.9 ms: profiles/r06_hop_sparse_link.txt).  The controller's own span is left as it is (it goes on voting from the counters; once it
     // asks for less than half a batch this rule no longer applies).
-    const bool whole_batch = wb.cand_ok && !ctx->prm.walk_window_span && ctx->calib_left <= 0 && span * 2 >= T && span < T && T <= ctx->max_span &&
+    const bool whole_batch = wb.cand_ok && !ctx->prm.walk_window_span && ctx->span.calib_left <= 0 && span * 2 >= T && span < T && T <= ctx->span.max_span &&
                              bb.n_pieces <= ctx->wmax;
     for (uint64_t lo = 0, step = 0; lo < T; lo += step) {
         step = whole_batch ? T : span_now;
@@ -3231,7 +3196,7 @@ int fgpu_stage_scan_walk(fgpu_ctx* ctx, uint64_t n_pieces) {
         FGPU_LAUNCH("walk_delta", k_delta_filter_add, 256, 256, (const uint32_t*)wb.created->list.p, (const unsigned long long*)wb.created->count.p,
                     (uint32_t*)ctx->delta_filter.p, ctx->delta_filter_bits - 1);
     ctx->delta_next++;
-    ctx->window_span = span_now;
+    ctx->span.window_span = span_now;
     ctx->prof_suppress = false;
     fgpu_prof_end(ctx, stage_tok);
     if (bb.walk_done) {

@@ -27,7 +27,7 @@ N_PAIRS = 15_000
 CUTS = (0, 40, 20_000, 24_000, 28_000, 30_000)
 CAPACITY = 1 << 10
 TRIGGERS = {"capacity": (CAPACITY, {}), "lazy": (0, {"FGPU_DEBUG_LAZY_FAIL": "2"}), "both": (CAPACITY, {"FGPU_DEBUG_LAZY_FAIL": "2"})}
-PATHS = ("stream", "prepared", "shard")
+PATHS = ("stream", "prepared", "stream_then_prepared", "shard")
 CONSUMERS = ("take_each", "take_at_end", "short_long_to_host", "long_not_to_host")
 
 
@@ -96,8 +96,8 @@ def _setup_consumer(ctx, consumer, d):
         ctx.scan_long_pairs(d["long"].tai, d["long"].n_hash, 2)
 
 
-def _scan(ctx, batches, path, consumer):
-    """one scan of `batches` on ctx (scan_begin already called); returns (taker, stats)"""
+def _scan(ctx, batches, path, consumer, capacity=0):
+    """one scan of `batches` on ctx (scan_begin already called; capacity: its junction_capacity, where it matters); returns (taker, stats)"""
     tk = _Taker(ctx, batches)
     during = consumer != "take_at_end"
     if path == "prepared":
@@ -108,6 +108,23 @@ def _scan(ctx, batches, path, consumer):
         ctx.scan_walk_prepared()
         if during:
             for _ in batches:                # the walks of the last batches may still run: lists taken mid-scan
+                tk.take()
+    elif path == "stream_then_prepared":
+        # The overflowing batch is walked by the streaming calls and nobody asks for lists before the next batch is PREPARED: the prepare finds
+        # the oldest buffers still holding lists, fetches them, sees the overflow there and has to replay before it can go on (scan_prepare_from's
+        # own replay: no other path reaches it).  The synchronisation lets the overflowing walk finish without anybody looking at its flags.
+        for b in batches[:2]:
+            ctx.scan_batch(b)
+        ctx.synchronize()
+        for i, b in enumerate(batches[2:]):
+            ctx.scan_prepare(b)
+            if i == 0 and capacity == CAPACITY and "FGPU_DEBUG_LAZY_FAIL" not in os.environ:
+                assert ctx.diag_scan_replays() >= 1, "the first prepare did not replay"
+            if during:
+                tk.take()
+        ctx.scan_walk_prepared()
+        if during:
+            for _ in batches:
                 tk.take()
     else:
         for b in batches:
@@ -169,7 +186,7 @@ def _run_cell(capacity, path, consumer):
         ctx.bloom_upload(L.BLOO2, d["b2"].bits())
         _setup_consumer(ctx, consumer, d)
         ctx.scan_begin()
-        tk, sst = _scan(ctx, batches, path, consumer)
+        tk, sst = _scan(ctx, batches, path, consumer, capacity)
         first = 0
     cell = (capacity, path, consumer)
     n_b = len(batches) - (1 if path == "shard" else 0)
@@ -217,9 +234,9 @@ def run_cells(trigger, paths, consumers):
 
 
 def test_lists_and_pair_filters_of_an_absorbed_overflow_equal_the_oracles():
-    """The default run's representative: the table overflows (trigger capacity), streaming and prepared, both pair filters on the device with
+    """The default run's representative: the table overflows (trigger capacity), streaming, prepared and prepared behind streamed batches, both pair filters on the device with
     lists also to the host and without; lists taken after every batch."""
-    failed = run_cells("capacity", ("stream", "prepared"), ("short_long_to_host", "long_not_to_host"))
+    failed = run_cells("capacity", ("stream", "prepared", "stream_then_prepared"), ("short_long_to_host", "long_not_to_host"))
     assert not failed, "\n".join(failed)
 
 
