@@ -99,6 +99,18 @@ class TipsInfo(C.Structure):
                     degenerate=[int(v) for v in self.degenerate], validated=int(self.validated), changed=int(self.changed), print=self.print.as_dict())
 
 
+class ChimeraInfo(C.Structure):
+    """fgpu_chimera_info: what ContigGraph::removeChimerasAndClean did, and what the file printed behind it holds"""
+    _fields_ = [("nodes_before", C.c_uint64), ("removed", C.c_uint64), ("cut_near", C.c_uint64), ("cut_far", C.c_uint64), ("cut_both", C.c_uint64),
+                ("collapsed", C.c_uint64 * 2), ("degenerate", C.c_uint64 * 2), ("collapsed_after_cut", C.c_uint64), ("skipped", C.c_uint64 * 6),
+                ("validated", C.c_uint32), ("changed", C.c_uint32), ("print", RawInfo)]
+
+    def as_dict(self):
+        return dict(nodes_before=int(self.nodes_before), removed=int(self.removed), cut_near=int(self.cut_near), cut_far=int(self.cut_far), cut_both=int(self.cut_both),
+                    collapsed=[int(v) for v in self.collapsed], degenerate=[int(v) for v in self.degenerate], collapsed_after_cut=int(self.collapsed_after_cut),
+                    skipped=[int(v) for v in self.skipped], validated=int(self.validated), changed=int(self.changed), print=self.print.as_dict())
+
+
 class TipsOut(C.Structure):
     """fgpu_tips_out: the arrays fgpu_tips_plan and fgpu_stage3_graph_take fill, their room, and how much was needed"""
     _fields_ = [("nodes", C.c_void_p), ("nodes_cap", C.c_uint64), ("n_nodes", C.c_uint64),
@@ -228,10 +240,14 @@ SIGNATURES = {
     "fgpu_stage3_raw_contigs": (C.c_int, [_vp, _i32, _P(_u64), _P(RawInfo)]),
     "fgpu_stage3_join": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _P(_u64)]),
     "fgpu_stage3_join_take": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64]),
+    "fgpu_stage3_build_totals": (C.c_int, [_vp, _P(_u64)]),
+    "fgpu_stage3_cov_calls": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp]),
     "fgpu_tips_plan": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _i32, _i32, _P(TipsOut), _P(TipsInfo)]),
     "fgpu_stage3_fasta_joined": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _P(_u64)]),
     "fgpu_stage3_detip": (C.c_int, [_vp, _i32, _P(_u64), _P(TipsInfo)]),
     "fgpu_stage3_graph_take": (C.c_int, [_vp, _P(TipsOut)]),
+    "fgpu_chimera_plan": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _i32, _i32, _P(TipsOut), _P(TipsInfo), _P(ChimeraInfo)]),
+    "fgpu_stage3_dechimera": (C.c_int, [_vp, _P(_u64), _P(ChimeraInfo)]),
     "fgpu_kernel_times": (C.c_int, [_vp, _P(KernelTime), C.c_int]),
     "fgpu_kernel_times_reset": (C.c_int, [_vp]),
     "fgpu_profile_enable": (C.c_int, [_vp, C.c_int]),

@@ -132,6 +132,7 @@ TIPS_CONTIG_DTYPE = np.dtype([("node1", "<u8"), ("node2", "<u8"), ("len", "<u4")
                               ("isolated", "u1"), ("reserved", "u1", (7,))])   # fgpu_tips_contig
 JOINED_DTYPE = np.dtype([("text_word", "<u8"), ("dist_first", "<u8"), ("cov_first", "<u8"), ("cov_sum", "<u8"), ("len", "<u4"), ("n_dist", "<u4"),
                          ("n_cov", "<u4"), ("reserved", "<u4")])   # fgpu_joined
+COV_SUMMARY_DTYPE = np.dtype([("sum", "<u8"), ("n", "<u4"), ("first", "u1"), ("last", "u1"), ("reserved", "u1", (2,))])   # fgpu_cov_summary (csrc/cov_summary.h)
 
 
 class _PinnedMemory:
@@ -857,6 +858,25 @@ class Context:
         covs = [jcov[int(j["cov_first"]):int(j["cov_first"]) + int(j["n_cov"])] for j in out]
         return out, strings, dists, covs, out["cov_sum"].astype(np.float64) / out["n_cov"].astype(np.float64)
 
+    def stage3_cov_calls(self, contigs=None, cov=None):
+        """What a cleaning step reads of every contig's coverage list (fgpu_stage3_cov_calls): a COV_SUMMARY_DTYPE array, per record the sum,
+        the number of entries, the first and the last entry; sum / n as float64 is ContigJuncList::getAvgCoverage.  contigs=None: the calls of the
+        last stage3_build(take=False), whose coverages are read where they lie on the device; otherwise a CONTIG_DTYPE array (cov_first and
+        n_cov are read) and the coverage bytes it indexes."""
+        if contigs is None:
+            if cov is not None:
+                raise ValueError("coverages without the records that index them")
+            totals = (C.c_uint64 * 4)()
+            self._c(self.lib.fgpu_stage3_build_totals(self.h, totals))        # (the library's own count: how many records the call writes)
+            out = np.zeros(int(totals[0]), dtype=COV_SUMMARY_DTYPE)
+            self._c(self.lib.fgpu_stage3_cov_calls(self.h, None, 0, None, 0, out.ctypes.data))
+            return out
+        contigs = np.ascontiguousarray(contigs, dtype=CONTIG_DTYPE)
+        cov = np.ascontiguousarray(cov, dtype=np.uint8)
+        out = np.zeros(len(contigs), dtype=COV_SUMMARY_DTYPE)
+        self._c(self.lib.fgpu_stage3_cov_calls(self.h, contigs.ctypes.data, len(contigs), cov.ctypes.data, len(cov), out.ctypes.data))
+        return out
+
     def stage3_fasta_joined(self, joined, numbers, text=None) -> bytes:
         """JOINED_DTYPE records oriented and printed on the device (fgpu_stage3_fasta_joined): record i is ">Contig<numbers[i]>\n", its len bases
         from word text_word of the text as canon_contig leaves them, and "\n".  text: the joined 2-bit words (stage3_join(raw=True)'s); None: the
@@ -894,6 +914,16 @@ class Context:
         ti = L.TipsInfo()
         self._c(self.lib.fgpu_stage3_detip(self.h, int(read_length), C.byref(nbytes), C.byref(ti)))
         return self.stage3_fasta_take(nbytes.value), ti.as_dict()
+
+    def stage3_dechimera(self):
+        """ContigGraph::removeChimerasAndClean (src/ContigGraph.cpp:177-184) on the live graph the last stage3_detip left, and printContigs behind
+        it (fgpu_stage3_dechimera): (the file's bytes, info = dict(nodes_before, removed, cut_near, cut_far, cut_both, collapsed, degenerate,
+        collapsed_after_cut, skipped, validated, changed, print)).  The build stays where it is; stage3_graph_take() gives the graph after the
+        step.  Join results and a file that were not taken before the call are dropped; a second call without a new stage3_detip is an error."""
+        nbytes = C.c_uint64(0)
+        ci = L.ChimeraInfo()
+        self._c(self.lib.fgpu_stage3_dechimera(self.h, C.byref(nbytes), C.byref(ci)))
+        return self.stage3_fasta_take(nbytes.value), ci.as_dict()
 
     def kernel_times(self) -> dict:
         arr = (L.KernelTime * 64)()
@@ -1091,6 +1121,38 @@ def tips_plan(keys, recs, contigs, calls, k: int, read_length: int):
     if state["status"] != L.PLAN_OK:
         return state["status"], None, None, ti.as_dict()
     return L.PLAN_OK, graph, list(zip((int(v) for v in number), _lists_of(first, pieces))), ti.as_dict()
+
+
+def chimera_plan(keys, recs, contigs, calls, cov_calls, k: int, read_length: int):
+    """fgpu_chimera_plan, host only: which piece lists ContigGraph::deleteTipsAndClean and then removeChimerasAndClean leave of a finished build
+    (tips_plan's arguments and cov_calls, one COV_SUMMARY_DTYPE record per call: Context.stage3_cov_calls' output) and which of them printContigs
+    prints.  Returns (status, graph, records, info, tips_info): graph and records as tips_plan gives them, after the second step; info as
+    Context.stage3_dechimera's; tips_info the first step's account (its print part is empty).  graph and records are None unless status is
+    PLAN_OK (0)."""
+    lib = L.load()
+    keys, recs = np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(recs, dtype=JUNC_DTYPE)
+    contigs, calls = np.ascontiguousarray(contigs, dtype=CONTIG_DTYPE), np.ascontiguousarray(calls, dtype=BUILD_DTYPE)
+    cov_calls = np.ascontiguousarray(cov_calls, dtype=COV_SUMMARY_DTYPE)
+    if len(cov_calls) != len(contigs):
+        raise ValueError("one coverage summary per call")
+    out, ti, ci = L.TipsOut(), L.TipsInfo(), L.ChimeraInfo()
+    args = (keys.ctypes.data, recs.ctypes.data, len(keys), contigs.ctypes.data, calls.ctypes.data, len(contigs), cov_calls.ctypes.data, int(k), int(read_length),
+            C.byref(out), C.byref(ti), C.byref(ci))
+    status = lib.fgpu_chimera_plan(*args)                                 # (no room: how much is needed)
+    if status not in (L.PLAN_OK, L.PLAN_SHORT):
+        return status, None, None, ci.as_dict(), ti.as_dict()
+    first, number = np.zeros(out.n_print + 1, dtype=np.uint64), np.zeros(out.n_print, dtype=np.uint32)
+    pieces = np.zeros(out.n_print_pieces, dtype=JOIN_PIECE_DTYPE)
+    out.print_first, out.print_number, out.print_cap = first.ctypes.data, number.ctypes.data, len(number)
+    out.print_pieces, out.print_pieces_cap = pieces.ctypes.data, len(pieces)
+    state = {}
+
+    def fill():
+        state["status"] = lib.fgpu_chimera_plan(*args)
+    graph = _tips_graph(out, fill)
+    if state["status"] != L.PLAN_OK:
+        return state["status"], None, None, ci.as_dict(), ti.as_dict()
+    return L.PLAN_OK, graph, list(zip((int(v) for v in number), _lists_of(first, pieces))), ci.as_dict(), ti.as_dict()
 
 
 def print_kmer(kmer: int, k: int) -> str:            # print_kmer / code2seq (utils/Kmer.cpp:217)

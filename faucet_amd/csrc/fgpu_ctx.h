@@ -6,12 +6,15 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/faucet_gpu.h"
 #include <deque>
+
+namespace fgpu_graph { struct CleanGraph; }      // clean_graph.h: the graph Stage 3's cleaning steps work on (host only)
 
 #include "fgpu_device.h"
 #include "walk_span.h"
@@ -447,11 +450,11 @@ struct fgpu_ctx {
     uint64_t s3f_bytes = 0;
     void* s3j_out = nullptr;              // fgpu_stage3_join's arrays until fgpu_stage3_join_take (stage3_join.hip): joined text, distances, coverages
     uint64_t s3j_totals[3] = {0, 0, 0};   // their entries: text words, distances, coverages
-    std::vector<fgpu_tips_node> s3t_nodes;        // fgpu_stage3_detip's graph until fgpu_stage3_graph_take (host memory: fgpu_tips_plan made it there)
-    std::vector<fgpu_tips_contig> s3t_contigs;
-    std::vector<uint64_t> s3t_first;              // contigs + 1 entries
-    std::vector<fgpu_join_piece> s3t_pieces;
-    bool s3t_have = false;
+    uint64_t s3b_serial = 0;              // which build s3b_out holds: counted up whenever a build's results are dropped for the next one
+    std::shared_ptr<fgpu_graph::CleanGraph> s3t_graph;   // the LIVE graph fgpu_stage3_detip left (clean_graph.h; host memory) until fgpu_stage3_graph_take:
+                                                         // the next cleaning step works on it
+    uint64_t s3t_serial = 0;              // ... the build it was made of
+    bool s3t_dechimered = false;          // ... fgpu_stage3_dechimera has run on it
     uint64_t s3_mask = 0, s3_count = 0;
     bool s3_ready = false;
     DevBuf dl_entries, dl_stamps, dl_stamps_sorted, dl_idx, dl_idx_sorted, dl_keys, dl_recs, dl_tmp;   // junction download scratch

@@ -1015,6 +1015,7 @@ void s3b_drop(fgpu_ctx* ctx) {                             // results nobody too
     if (ctx->s3b_out) { (void)hipFree(ctx->s3b_out); ctx->s3b_out = nullptr; }
     for (int i = 0; i < 4; i++) ctx->s3b_totals[i] = 0;
     ctx->s3b_have = false;
+    ctx->s3b_serial++;                                     // (whatever comes next is another build: a graph made of this one is stale)
 }
 struct S3bLayout { uint64_t contigs, calls, text, kmers, dist, cov, bytes; };
 S3bLayout s3b_layout(const uint64_t tot[4]) {
@@ -1044,6 +1045,14 @@ int fgpu_s3b_lists(fgpu_ctx* ctx, const uint8_t** seg_dist, const uint8_t** cov)
     if (seg_dist) *seg_dist = (const uint8_t*)(res + lay.dist);
     if (cov) *cov = (const uint8_t*)(res + lay.cov);
     return 1;
+}
+
+extern "C" int fgpu_stage3_build_totals(fgpu_ctx* ctx, uint64_t totals[4]) {
+    if (!ctx || !totals) return FGPU_ERR_ARG;
+    for (int i = 0; i < 4; i++) totals[i] = 0;
+    if (!ctx->s3b_have) { ctx->err = "fgpu_stage3_build_totals: no fgpu_stage3_build whose results are still on the device"; return FGPU_ERR_STATE; }
+    for (int i = 0; i < 4; i++) totals[i] = ctx->s3b_totals[i];
+    return FGPU_OK;
 }
 
 extern "C" int fgpu_stage3_build(fgpu_ctx* ctx, int32_t max_read_length, uint64_t totals[4], fgpu_build_info* info) {

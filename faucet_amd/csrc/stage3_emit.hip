@@ -1,7 +1,8 @@
 // stage3_emit.hip — Stage 3's first product on the device: the contigs of a build, joined, oriented and printed as FASTA where they lie
 // (fgpu_stage3_fasta, fgpu_stage3_fasta_take, fgpu_stage3_raw_contigs; include/faucet_gpu.h) -- and its second, the contigs after the first
 // cleaning step, printed from the strings fgpu_stage3_join left on the device (fgpu_stage3_fasta_joined, fgpu_stage3_detip,
-// fgpu_stage3_graph_take).
+// fgpu_stage3_graph_take), and likewise after the second step (fgpu_stage3_dechimera), which works on the graph the first one left: the
+// context keeps the live graph object (clean_graph.h) between the steps, and nothing of it is made again.
 //
 // What the reference does per record, ContigGraph::printContigs (src/ContigGraph.cpp:1532-1645):
 //   ContigJuncList::concatenate's sequence          utils/ContigJuncList.cpp:121   first.substr(0, len - k) + second
@@ -22,16 +23,18 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <memory>
 #include <rocprim/rocprim.hpp>
 #include <string>
 #include <vector>
 
+#include "clean_graph.h"
 #include "fgpu_ctx.h"
 #include "stage3_bits.h"
 
 namespace {
 
-static_assert(sizeof(fgpu_fasta_seq) == 32 && sizeof(fgpu_raw_info) == 48, "the records as api.py and _lib.py lay them out");
+static_assert(sizeof(fgpu_fasta_seq) == 32 && sizeof(fgpu_raw_info) == 48 && sizeof(fgpu_chimera_info) == 184, "the records as api.py and _lib.py lay them out");
 static_assert(sizeof(fgpu_tips_node) == 32 && sizeof(fgpu_tips_contig) == 32 && sizeof(fgpu_tips_info) == 112 && sizeof(fgpu_tips_out) == 136, "... likewise");
 
 constexpr uint32_t EMIT_TILE = 4096;             // bytes of output per block of k_emit_ascii: 256 lanes x 16 bytes
@@ -391,6 +394,36 @@ int emit_build_records(fgpu_ctx* ctx, const std::string& who, EmitBuild& b) {
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
     return FGPU_OK;
 }
+// the print records of a cleaned graph (clean_graph.h) on the host, and the file made of them on the device
+struct EmitPrint {
+    std::vector<uint64_t> first;
+    std::vector<uint32_t> numbers;
+    std::vector<fgpu_join_piece> pieces;
+    uint64_t n = 0, n_pieces = 0;
+    // printContigs' two passes: a plan status.  Room that suffices unless a contig is copied (a call lies in one contig of the graph, a bubble's
+    // back in at most four records); asked again if not
+    int of(fgpu_graph::CleanGraph& cg, uint64_t n_calls, fgpu_raw_info& info) {
+        first.resize(n_calls + 1); numbers.resize(n_calls); pieces.resize(2 * n_calls);
+        int st = FGPU_PLAN_SHORT;
+        for (int pass = 0; pass < 2 && st == FGPU_PLAN_SHORT; pass++) {
+            if (pass) { first.resize(n + 1); numbers.resize(n); pieces.resize(n_pieces); }
+            fgpu_tips_out out;
+            memset(&out, 0, sizeof(out));
+            out.print_first = first.data(); out.print_number = numbers.data(); out.print_cap = numbers.size();
+            out.print_pieces = pieces.data(); out.print_pieces_cap = pieces.size();
+            st = cg.print_records(&out, info);
+            n = out.n_print; n_pieces = out.n_print_pieces;
+        }
+        return st;
+    }
+    // fgpu_stage3_join of the records' lists over the build where it lies, fgpu_stage3_fasta_joined of the joined text where it lies
+    int emit(fgpu_ctx* ctx, uint64_t* bytes) {
+        std::vector<fgpu_joined> joined(n);
+        uint64_t totals[3];
+        if (int rc = fgpu_stage3_join(ctx, first.data(), n, pieces.data(), n_pieces, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, joined.data(), totals)) return rc;
+        return fgpu_stage3_fasta_joined(ctx, joined.data(), numbers.data(), n, nullptr, 0, bytes);
+    }
+};
 int emit_plan_failed(fgpu_ctx* ctx, const std::string& who, const char* plan, const char* unset, int st) {
     ctx->err = st == FGPU_PLAN_UNSET ? who + ": on this graph " + unset + " (undefined in the reference)"
                                      : who + ": the build's records are not a finished build of the map (" + plan + " status " + std::to_string(st) + ")";
@@ -423,40 +456,54 @@ extern "C" int fgpu_stage3_detip(fgpu_ctx* ctx, int32_t read_length, uint64_t* b
     if (info) memset(info, 0, sizeof(*info));
     EmitBuild b;
     if (int rc = emit_build_records(ctx, "fgpu_stage3_detip", b)) return rc;
-    const uint64_t n_calls = b.contigs.size(), nj = b.keys.size();
-    // room that suffices unless a contig is copied (a call lies in one contig of the graph, a bubble's back in at most four records); asked again if not
-    std::vector<fgpu_tips_node> nodes(nj);
-    std::vector<fgpu_tips_contig> tigs(n_calls);
-    std::vector<uint64_t> list_first(n_calls + 1), print_first(n_calls + 1);
-    std::vector<fgpu_join_piece> pieces(n_calls), print_pieces(2 * n_calls);
-    std::vector<uint32_t> numbers(n_calls);
-    fgpu_tips_out out;
+    const char* unset = "ContigGraph::deleteTipsAndClean or printContigs goes through a pointer that was never set or whose target is gone";
+    std::shared_ptr<fgpu_graph::CleanGraph> cg = std::make_shared<fgpu_graph::CleanGraph>();
     fgpu_tips_info inf;
-    int st = FGPU_PLAN_SHORT;
-    for (int pass = 0; pass < 2 && st == FGPU_PLAN_SHORT; pass++) {
-        if (pass) {
-            nodes.resize(out.n_nodes); tigs.resize(out.n_contigs); list_first.resize(out.n_contigs + 1); pieces.resize(out.n_pieces);
-            numbers.resize(out.n_print); print_first.resize(out.n_print + 1); print_pieces.resize(out.n_print_pieces);
-        }
-        memset(&out, 0, sizeof(out));
-        memset(&inf, 0, sizeof(inf));
-        out.nodes = nodes.data(); out.nodes_cap = nodes.size();
-        out.contigs = tigs.data(); out.list_first = list_first.data(); out.contigs_cap = tigs.size();
-        out.pieces = pieces.data(); out.pieces_cap = pieces.size();
-        out.print_first = print_first.data(); out.print_number = numbers.data(); out.print_cap = numbers.size();
-        out.print_pieces = print_pieces.data(); out.print_pieces_cap = print_pieces.size();
-        st = fgpu_tips_plan(b.keys.data(), b.recs.data(), nj, b.contigs.data(), b.calls.data(), n_calls, ctx->prm.k, read_length, &out, &inf);
+    memset(&inf, 0, sizeof(inf));
+    int st = cg->of_build(b.keys.data(), b.recs.data(), b.keys.size(), b.contigs.data(), b.calls.data(), b.contigs.size(), nullptr, ctx->prm.k, read_length);
+    if (st == FGPU_PLAN_OK) st = cg->delete_tips_and_clean(inf);
+    EmitPrint pr;
+    if (st == FGPU_PLAN_OK) st = pr.of(*cg, b.contigs.size(), inf.print);
+    if (st != FGPU_PLAN_OK) return emit_plan_failed(ctx, "fgpu_stage3_detip", "fgpu_tips_plan", unset, st);
+    ctx->s3t_graph.reset();
+    if (int rc = pr.emit(ctx, bytes)) return rc;
+    ctx->s3t_graph = cg;                         // alive from here on: the next step works on it, fgpu_stage3_graph_take serialises it
+    ctx->s3t_serial = ctx->s3b_serial;
+    ctx->s3t_dechimered = false;
+    if (info) *info = inf;
+    return FGPU_OK;
+}
+
+extern "C" int fgpu_stage3_dechimera(fgpu_ctx* ctx, uint64_t* bytes, fgpu_chimera_info* info) {
+    if (!ctx || !bytes) return FGPU_ERR_ARG;
+    *bytes = 0;
+    if (info) memset(info, 0, sizeof(*info));
+    const std::string who = "fgpu_stage3_dechimera";
+    if (!ctx->s3t_graph) { ctx->err = who + ": no fgpu_stage3_detip whose graph has not been taken"; return FGPU_ERR_STATE; }
+    if (ctx->s3t_dechimered) { ctx->err = who + ": the step has run on this graph (fgpu_stage3_detip makes a new one)"; return FGPU_ERR_STATE; }
+    if (!ctx->s3b_have || ctx->s3t_serial != ctx->s3b_serial) {
+        ctx->err = who + ": the build the graph was made of is no longer on the device (taken, or another build was made)";
+        return FGPU_ERR_STATE;
     }
-    if (st != FGPU_PLAN_OK) return emit_plan_failed(ctx, "fgpu_stage3_detip", "fgpu_tips_plan", "ContigGraph::deleteTipsAndClean or printContigs goes through a pointer that was never set or whose target is gone", st);
-    ctx->s3t_have = false;
-    std::vector<fgpu_joined> joined(out.n_print);
-    uint64_t totals[3];
-    if (int rc = fgpu_stage3_join(ctx, print_first.data(), out.n_print, print_pieces.data(), out.n_print_pieces, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, joined.data(), totals))
-        return rc;
-    if (int rc = fgpu_stage3_fasta_joined(ctx, joined.data(), numbers.data(), out.n_print, nullptr, 0, bytes)) return rc;
-    nodes.resize(out.n_nodes); tigs.resize(out.n_contigs); list_first.resize(out.n_contigs + 1); pieces.resize(out.n_pieces);
-    ctx->s3t_nodes.swap(nodes); ctx->s3t_contigs.swap(tigs); ctx->s3t_first.swap(list_first); ctx->s3t_pieces.swap(pieces);
-    ctx->s3t_have = true;
+    if (ctx->phase != 0) { ctx->err = who + " while a pass is open"; return FGPU_ERR_STATE; }
+    const uint64_t n_calls = ctx->s3b_totals[0];
+    std::vector<fgpu_cov_summary> cov(n_calls);
+    if (int rc = fgpu_stage3_cov_calls(ctx, nullptr, 0, nullptr, 0, cov.data())) return rc;
+    fgpu_graph::CleanGraph& cg = *ctx->s3t_graph;
+    fgpu_chimera_info inf;
+    memset(&inf, 0, sizeof(inf));
+    int st = cg.set_cov(cov.data(), n_calls);
+    if (st == FGPU_PLAN_OK) {
+        ctx->s3t_dechimered = true;
+        st = cg.remove_chimeras_and_clean(inf);
+    }
+    EmitPrint pr;
+    if (st == FGPU_PLAN_OK) st = pr.of(cg, n_calls, inf.print);
+    if (st != FGPU_PLAN_OK) {
+        ctx->s3t_graph.reset();                  // (a step that stopped half-way left a graph that is nobody's)
+        return emit_plan_failed(ctx, who, "fgpu_chimera_plan", "ContigGraph::removeChimerasAndClean or printContigs goes through a pointer that was never set or whose target is gone", st);
+    }
+    if (int rc = pr.emit(ctx, bytes)) return rc;
     if (info) *info = inf;
     return FGPU_OK;
 }
@@ -464,19 +511,20 @@ extern "C" int fgpu_stage3_detip(fgpu_ctx* ctx, int32_t read_length, uint64_t* b
 extern "C" int fgpu_stage3_graph_take(fgpu_ctx* ctx, fgpu_tips_out* out) {
     if (!ctx || !out) return FGPU_ERR_ARG;
     out->n_nodes = out->n_contigs = out->n_pieces = out->n_print = out->n_print_pieces = 0;
-    if (!ctx->s3t_have) { ctx->err = "fgpu_stage3_graph_take: no fgpu_stage3_detip whose graph has not been taken"; return FGPU_ERR_STATE; }
-    const uint64_t nn = ctx->s3t_nodes.size(), nc = ctx->s3t_contigs.size(), np = ctx->s3t_pieces.size();
+    if (!ctx->s3t_graph) { ctx->err = "fgpu_stage3_graph_take: no fgpu_stage3_detip whose graph has not been taken"; return FGPU_ERR_STATE; }
+    fgpu_tips_out need;
+    memset(&need, 0, sizeof(need));
+    ctx->s3t_graph->graph_records(&need);        // (no room: how large it is)
+    const uint64_t nn = need.n_nodes, nc = need.n_contigs, np = need.n_pieces;
     out->n_nodes = nn; out->n_contigs = nc; out->n_pieces = np;
     if (out->nodes_cap < nn || out->contigs_cap < nc || out->pieces_cap < np || (nn && !out->nodes) || !out->list_first || (nc && !out->contigs) || (np && !out->pieces)) {
         ctx->err = "fgpu_stage3_graph_take: an array is smaller than the graph (n_nodes, n_contigs, n_pieces say how large it is)";
         return FGPU_ERR_ARG;
     }
-    if (nn) memcpy(out->nodes, ctx->s3t_nodes.data(), nn * sizeof(fgpu_tips_node));
-    if (nc) memcpy(out->contigs, ctx->s3t_contigs.data(), nc * sizeof(fgpu_tips_contig));
-    memcpy(out->list_first, ctx->s3t_first.data(), (nc + 1) * 8);
-    if (np) memcpy(out->pieces, ctx->s3t_pieces.data(), np * sizeof(fgpu_join_piece));
-    std::vector<fgpu_tips_node>().swap(ctx->s3t_nodes); std::vector<fgpu_tips_contig>().swap(ctx->s3t_contigs);
-    std::vector<uint64_t>().swap(ctx->s3t_first); std::vector<fgpu_join_piece>().swap(ctx->s3t_pieces);
-    ctx->s3t_have = false;
+    fgpu_tips_out fill = *out;                   // (exactly the graph's room, so that nothing behind it is written)
+    fill.nodes_cap = nn; fill.contigs_cap = nc; fill.pieces_cap = np;
+    const int st = ctx->s3t_graph->graph_records(&fill);
+    if (st != FGPU_PLAN_OK) { ctx->err = "fgpu_stage3_graph_take: the graph did not fit the room it asked for"; return FGPU_ERR_INTERNAL; }
+    ctx->s3t_graph.reset();
     return FGPU_OK;
 }

@@ -15,11 +15,14 @@
 //   k_join_cov    eight lanes per list, a lane per eighth coverage entry: the minimum over the pieces whose oriented list reaches the entry
 //                 -- one inside a piece, two at a join, more where middle pieces hold a single entry -- and the list's sum by a reduction
 //                 over the eight (shuffles; no atomics)
+// And what a cleaning step reads of a contig's coverages before anything is joined (fgpu_stage3_cov_calls; cov_summary.h):
+//   k_cov_calls   four lanes per contig record: sum, size, first and last entry of its list, one 16-byte record each
 #include <hip/hip_runtime.h>
 
 #include <string>
 #include <vector>
 
+#include "cov_summary.h"
 #include "fgpu_ctx.h"
 #include "stage3_bits.h"
 
@@ -104,6 +107,34 @@ __global__ void __launch_bounds__(256) k_join_cov(JoinIn in, uint64_t n, uint8_t
     }
     for (int d = JOIN_COV_LANES / 2; d; d >>= 1) sum += __shfl_down(sum, d, JOIN_COV_LANES);
     if (lane == 0) sums[i] = sum;
+}
+
+// Lanes that share a call in k_cov_calls: the same distribution as above before anything is joined -- two entries on average, a few lists of
+// thousands -- so four lanes leave half of them busy on the common list and a long one costs a quarter of its entries per lane.
+constexpr uint32_t COV_CALL_LANES = 4;
+
+static_assert(sizeof(fgpu_cov_summary) == 16 && alignof(fgpu_cov_summary) == 8, "one record, one aligned 16-byte store");
+
+// One summary per contig record, read from the coverage array where it lies: a lane per fourth entry for the sum (shuffles; no atomics), the
+// group's first lane reads the two end entries and writes the record.  The host has checked that every record lies inside the array.
+__global__ void __launch_bounds__(256) k_cov_calls(const fgpu_contig* __restrict__ contigs, uint64_t n, const uint8_t* __restrict__ covs,
+                                                   fgpu_cov_summary* __restrict__ out) {
+    const uint64_t i = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / COV_CALL_LANES;    // (uniform within the group)
+    if (i >= n) return;
+    const uint32_t lane = threadIdx.x % COV_CALL_LANES;
+    const uint64_t first = contigs[i].cov_first;
+    const uint32_t n_cov = contigs[i].n_cov;
+    uint64_t sum = 0;
+    for (uint64_t j = lane; j < n_cov; j += COV_CALL_LANES) sum += covs[first + j];
+    for (int d = COV_CALL_LANES / 2; d; d >>= 1) sum += __shfl_down(sum, d, COV_CALL_LANES);
+    if (lane) return;
+    fgpu_cov_summary s;
+    s.sum = sum;
+    s.n = n_cov;
+    s.first = n_cov ? covs[first] : 0;
+    s.last = n_cov ? covs[first + n_cov - 1] : 0;
+    s.reserved[0] = s.reserved[1] = 0;
+    out[i] = s;
 }
 
 struct JoinScratch {                             // device memory of one call, gone when it returns
@@ -243,6 +274,49 @@ extern "C" int fgpu_stage3_join(fgpu_ctx* ctx, const uint64_t* list_first, uint6
     FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
     for (uint64_t i = 0; i < n; i++) out[i].cov_sum = cov_sums[i];
     for (int i = 0; i < 3; i++) totals[i] = ctx->s3j_totals[i] = tot[i];
+    return FGPU_OK;
+}
+
+extern "C" int fgpu_stage3_cov_calls(fgpu_ctx* ctx, const fgpu_contig* contigs_host, uint64_t n_contigs, const uint8_t* cov_host, uint64_t n_cov,
+                                     fgpu_cov_summary* out_host) {
+    if (!ctx) return FGPU_ERR_ARG;
+    auto bad = [&](const std::string& what) { ctx->err = "fgpu_stage3_cov_calls: " + what; return FGPU_ERR_ARG; };
+    if (ctx->phase != 0) { ctx->err = "fgpu_stage3_cov_calls while a pass is open"; return FGPU_ERR_STATE; }
+    const bool from_build = contigs_host == nullptr;
+    if (from_build ? (n_contigs || cov_host || n_cov) : (n_cov && !cov_host))
+        return bad(from_build ? "without contigs the calls are those of the build on the device: the other arrays must be NULL / 0" : "a coverage array of some entries is NULL");
+    FGPU_HIP(hipSetDevice(ctx->prm.device));
+    const fgpu_contig* d_contigs = nullptr;
+    const uint8_t* d_cov = nullptr;
+    if (from_build) {                            // (the build wrote these records and the array they index itself: nothing to check, nothing comes to the host)
+        if (!fgpu_s3b_view(ctx, &d_contigs, nullptr, nullptr) || !fgpu_s3b_lists(ctx, nullptr, &d_cov)) {
+            ctx->err = "fgpu_stage3_cov_calls without contigs: no fgpu_stage3_build whose results are still on the device";
+            return FGPU_ERR_STATE;
+        }
+        n_contigs = ctx->s3b_totals[0]; n_cov = ctx->s3b_totals[3];
+    }
+    if (n_contigs && !out_host) return bad("no room for the summaries");
+    for (uint64_t i = 0; !from_build && i < n_contigs; i++)     // every entry the kernel will read lies in the array
+        if (contigs_host[i].cov_first > n_cov || contigs_host[i].n_cov > n_cov - contigs_host[i].cov_first)
+            return bad("record " + std::to_string(i) + " reaches past the coverages");
+    if (!n_contigs) return FGPU_OK;
+    JoinScratch work;
+    uint64_t at = 0;
+    const uint64_t o_out = join_take(at, n_contigs * sizeof(fgpu_cov_summary)), o_contigs = join_take(at, from_build ? 0 : n_contigs * sizeof(fgpu_contig)),
+                   o_cov = join_take(at, from_build ? 0 : n_cov);
+    if (hipError_t e = hipMalloc(&work.p, at)) {
+        ctx->err = std::string("fgpu_stage3_cov_calls: hipMalloc of ") + std::to_string(at) + " bytes failed: " + hipGetErrorString(e);
+        return FGPU_ERR_NOMEM;
+    }
+    char* wb = (char*)work.p;
+    if (!from_build) {
+        FGPU_HIP(hipMemcpyAsync(wb + o_contigs, contigs_host, n_contigs * sizeof(fgpu_contig), hipMemcpyHostToDevice, ctx->stream));
+        if (n_cov) FGPU_HIP(hipMemcpyAsync(wb + o_cov, cov_host, n_cov, hipMemcpyHostToDevice, ctx->stream));
+        d_contigs = (const fgpu_contig*)(wb + o_contigs); d_cov = (const uint8_t*)(wb + o_cov);
+    }
+    FGPU_LAUNCH("s3j_cov_calls", k_cov_calls, fgpu_blocks(n_contigs, 256 / COV_CALL_LANES), 256, d_contigs, n_contigs, d_cov, (fgpu_cov_summary*)(wb + o_out));
+    FGPU_HIP(hipMemcpyAsync(out_host, wb + o_out, n_contigs * sizeof(fgpu_cov_summary), hipMemcpyDeviceToHost, ctx->stream));
+    FGPU_HIP(fgpu_sync_stream(ctx, ctx->stream));
     return FGPU_OK;
 }
 

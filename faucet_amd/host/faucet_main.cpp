@@ -70,6 +70,8 @@
 #pragma weak fgpu_stage3_fasta_take
 // ... and the one more of --detipped_contigs (ContigGraph::deleteTipsAndClean on that build)
 #pragma weak fgpu_stage3_detip
+// ... and of --dechimered_contigs (ContigGraph::removeChimerasAndClean on the graph that step left)
+#pragma weak fgpu_stage3_dechimera
 
 using faucet_host::ReadSource;
 using faucet_host::TextSource;
@@ -101,6 +103,7 @@ struct Options {   // globals of src/Faucet.h:14-53
     bool scan_kept = false;           // not a reference flag: --scan_kept, pass 2 scans the batches pass 1 kept; -read_scan_file may be left out
     bool raw_contigs = false;         // not a reference flag: --raw_contigs, <prefix>.raw_contigs.fasta (the file src/Faucet.cpp:314 would write) behind the scan outputs
     bool detipped_contigs = false;    // not a reference flag: --detipped_contigs, <prefix>.detipped_contigs.fasta (what printContigs would write after the first deleteTipsAndClean of cleanGraph)
+    bool dechimered_contigs = false;  // not a reference flag: --dechimered_contigs, <prefix>.dechimered_contigs.fasta (... after the removeChimerasAndClean behind it)
 };
 
 void argument_error() {   // src/Faucet.cpp:50-54
@@ -112,7 +115,8 @@ void argument_error() {   // src/Faucet.cpp:50-54
     fprintf(stderr, "Of this build: -gpus <n> -transport copy|rccl -batch_reads <n> -chunk_mb <n> --estimate -estimate_bits <r> "
                     "--scan_kept (pass 2 scans the reads pass 1 kept on the device: -read_scan_file may be left out) "
                     "--raw_contigs (writes <prefix>.raw_contigs.fasta, the contigs of the graph build before any cleaning)\n"
-                    "--detipped_contigs (writes <prefix>.detipped_contigs.fasta, the contigs after the first cleaning step, ContigGraph::deleteTipsAndClean)\n");
+                    "--detipped_contigs (writes <prefix>.detipped_contigs.fasta, the contigs after the first cleaning step, ContigGraph::deleteTipsAndClean)\n"
+                    "--dechimered_contigs (writes <prefix>.dechimered_contigs.fasta, the contigs after the second cleaning step, ContigGraph::removeChimerasAndClean)\n");
 }
 
 // src/Faucet.cpp:57-182 (with the missing `return 0` supplied and a bounds check on flag values)
@@ -150,6 +154,7 @@ int handle_arguments(int argc, char** argv, Options& o) {
         else if (a == "--scan_kept") o.scan_kept = true;
         else if (a == "--raw_contigs") o.raw_contigs = true;
         else if (a == "--detipped_contigs") o.detipped_contigs = true;
+        else if (a == "--dechimered_contigs") o.dechimered_contigs = true;
         else if (a == "-estimate_bits") { if (!val(v)) goto bad; o.estimate_bits = atoi(v); if (o.estimate_bits < FGPU_EST_MIN_BITS || o.estimate_bits > FGPU_EST_MAX_BITS) { fprintf(stderr, "-estimate_bits must be in %d..%d\n", FGPU_EST_MIN_BITS, FGPU_EST_MAX_BITS); return 1; } }
         else if (a == "--help" || a == "-h") { argument_error(); return 1; }
         else { fprintf(stderr, "Cannot parse tag %s\n", argv[i]); argument_error(); return 1; }
@@ -425,9 +430,9 @@ int write_raw_contigs(const Options& o, fgpu_ctx* ctx, const uint64_t* keys, con
     CHECK(fgpu_stage3_build(ctx, o.read_length, totals, &bi));
     clk.mark("  raw contigs: graph build");
     if (bi.status != 0) {      // the reference itself does not return from buildContigGraph on this map: no file
-        fprintf(stderr, "%s: getContig call %llu of JunctionMap::buildContigGraph %s: the reference does not get as far as printing on this map, no %s.%s.fasta is written\n",
-                o.raw_contigs ? "--raw_contigs" : "--detipped_contigs", (unsigned long long)bi.stop_call,
-                bi.status == 1 ? "trips an assert of the reference" : "never returns in the reference", o.file_prefix.c_str(), o.raw_contigs ? "raw_contigs" : "detipped_contigs");
+        const char* what = o.raw_contigs ? "raw_contigs" : o.detipped_contigs ? "detipped_contigs" : "dechimered_contigs";
+        fprintf(stderr, "--%s: getContig call %llu of JunctionMap::buildContigGraph %s: the reference does not get as far as printing on this map, no %s.%s.fasta is written\n",
+                what, (unsigned long long)bi.stop_call, bi.status == 1 ? "trips an assert of the reference" : "never returns in the reference", o.file_prefix.c_str(), what);
         return 2;
     }
     auto write_file = [&](const std::string& path, uint64_t bytes) -> int {
@@ -447,20 +452,35 @@ int write_raw_contigs(const Options& o, fgpu_ctx* ctx, const uint64_t* keys, con
                (unsigned long long)ri.isolated_dropped, (unsigned long long)ri.nodes, (unsigned long long)bytes);
         clk.mark("  raw contigs: plan, emission, file");
     }
-    if (o.detipped_contigs) {  // the first step of ContigGraph::cleanGraph (src/ContigGraph.cpp:211-215) on the same build, which is still on the device
+    if (o.detipped_contigs || o.dechimered_contigs) {  // the first step of ContigGraph::cleanGraph (src/ContigGraph.cpp:211-215) on the same build, which is still on the device
         uint64_t bytes = 0;
         fgpu_tips_info ti;
         if (fgpu_stage3_detip(ctx, o.read_length, &bytes, &ti) != FGPU_OK) {      // (a plan status other than OK among them: no file)
-            fprintf(stderr, "--detipped_contigs: %s: no %s.detipped_contigs.fasta is written\n", fgpu_last_error(ctx), o.file_prefix.c_str());
+            const char* what = o.detipped_contigs ? "detipped_contigs" : "dechimered_contigs";
+            fprintf(stderr, "--%s: %s: no %s.%s.fasta is written\n", what, fgpu_last_error(ctx), o.file_prefix.c_str(), what);
             return 2;
         }
-        if (int rc = write_file(o.file_prefix + ".detipped_contigs.fasta", bytes)) return rc;
-        printf("Detipped contigs: %llu tips deleted (and %llu back tips), %llu of %llu nodes left, %llu records (%llu bubble, %llu off nodes, %llu isolated; %llu isolated below "
-               "the read length left out), %llu bytes\n",
-               (unsigned long long)ti.tips, (unsigned long long)ti.back_tips, (unsigned long long)ti.print.nodes, (unsigned long long)ti.nodes_before,
-               (unsigned long long)ti.print.records, (unsigned long long)ti.print.bubble_records, (unsigned long long)ti.print.node_contigs,
-               (unsigned long long)ti.print.isolated_kept, (unsigned long long)ti.print.isolated_dropped, (unsigned long long)bytes);
-        clk.mark("  detipped contigs: plan, join, emission, file");
+        if (o.detipped_contigs) {                // (the step runs for the next one whether or not its own file is asked for)
+            if (int rc = write_file(o.file_prefix + ".detipped_contigs.fasta", bytes)) return rc;
+            printf("Detipped contigs: %llu tips deleted (and %llu back tips), %llu of %llu nodes left, %llu records (%llu bubble, %llu off nodes, %llu isolated; %llu isolated below "
+                   "the read length left out), %llu bytes\n",
+                   (unsigned long long)ti.tips, (unsigned long long)ti.back_tips, (unsigned long long)ti.print.nodes, (unsigned long long)ti.nodes_before,
+                   (unsigned long long)ti.print.records, (unsigned long long)ti.print.bubble_records, (unsigned long long)ti.print.node_contigs,
+                   (unsigned long long)ti.print.isolated_kept, (unsigned long long)ti.print.isolated_dropped, (unsigned long long)bytes);
+            clk.mark("  detipped contigs: plan, join, emission, file");
+        }
+    }
+    if (o.dechimered_contigs) {  // the second step (src/ContigGraph.cpp:218-220) on the graph the first one left, which the context kept alive
+        uint64_t bytes = 0;
+        fgpu_chimera_info ci;
+        if (fgpu_stage3_dechimera(ctx, &bytes, &ci) != FGPU_OK) {
+            fprintf(stderr, "--dechimered_contigs: %s: no %s.dechimered_contigs.fasta is written\n", fgpu_last_error(ctx), o.file_prefix.c_str());
+            return 2;
+        }
+        if (int rc = write_file(o.file_prefix + ".dechimered_contigs.fasta", bytes)) return rc;
+        printf("Dechimered contigs: %d chimeric extensions removed, %d of %d nodes left, %d records\n", (int)ci.removed, (int)ci.print.nodes, (int)ci.nodes_before,
+               (int)ci.print.records);
+        clk.mark("  dechimered contigs: summaries, plan step, join, emission, file");
     }
     return 0;
 }
@@ -550,7 +570,7 @@ int write_scan_outputs(const Options& o, fgpu_ctx* ctx, const fgpu_scan_stats& s
     printf("Weight of short pair filter: %f\n", short_pf.weight());
     if (o.paired_ends) printf("Weight of long pair filter: %f\n", long_pf.weight());
     printf("Number of junctions: %llu\n", (unsigned long long)order.size());
-    if (o.raw_contigs || o.detipped_contigs) return write_raw_contigs(o, ctx, keys.data(), recs.data(), order, clk);
+    if (o.raw_contigs || o.detipped_contigs || o.dechimered_contigs) return write_raw_contigs(o, ctx, keys.data(), recs.data(), order, clk);
     return 0;
 }
 
@@ -1229,6 +1249,14 @@ int main(int argc, char** argv) {
             return 2;
         }
         if (o.just_load || o.from_junctions) { fprintf(stderr, "--detipped_contigs needs the junction scan of this run: leave out --just_load_bloom and -junctions_file\n"); return 2; }
+    }
+    if (o.dechimered_contigs) {  // ... likewise
+        if (!fgpu_stage3_set_junctions || !fgpu_stage3_build || !fgpu_stage3_detip || !fgpu_stage3_dechimera || !fgpu_stage3_fasta_take) {
+            fprintf(stderr, "--dechimered_contigs: the library this program is linked against lacks the entry points of the graph build and its first two cleaning steps "
+                            "(fgpu_stage3_set_junctions, fgpu_stage3_build, fgpu_stage3_detip, fgpu_stage3_dechimera, fgpu_stage3_fasta_take)\n");
+            return 2;
+        }
+        if (o.just_load || o.from_junctions) { fprintf(stderr, "--dechimered_contigs needs the junction scan of this run: leave out --just_load_bloom and -junctions_file\n"); return 2; }
     }
     if (o.estimate && !(o.est_kmers_flag && o.est_sing_flag)) {     // pass 0, ahead of everything the two numbers decide (and of the lines that print them)
         if (o.k < 1 || o.k > 31) { fprintf(stderr, "k must be in 1..31 on this build\n"); return 1; }

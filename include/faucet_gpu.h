@@ -1018,6 +1018,30 @@ int fgpu_stage3_join(fgpu_ctx* ctx, const uint64_t* list_first, uint64_t n, cons
                      const uint8_t* dist_host, uint64_t n_dist, const uint8_t* cov_host, uint64_t n_cov, fgpu_joined* out, uint64_t totals[3]);
 int fgpu_stage3_join_take(fgpu_ctx* ctx, uint64_t* text, uint64_t text_words, uint8_t* dist, uint64_t n_dist, uint8_t* cov, uint64_t n_cov);
 
+/* ---- Stage 3's coverage summaries: what a cleaning step reads of a contig's coverages, without joining anything ----
+ * removeChimericExtensions (src/ContigGraph.cpp:642-707) and the steps behind it decide on ContigJuncList::getAvgCoverage
+ * (utils/ContigJuncList.cpp:162-172) of a few contigs per node.  A coverage list enters that, and ContigJuncList::concatenate (:107-123) and
+ * reverse (:98-103), through four numbers -- sum, entries, first entry, last entry: struct fgpu_cov_summary, 16 bytes, defined with its two
+ * operations in faucet_amd/csrc/cov_summary.h (concatenate: m = min(A.last, B.first); sum = A.sum + B.sum - A.last - B.first + m; n = A.n + B.n
+ * - 1; first = A.n == 1 ? m : A.first; last = B.n == 1 ? m : B.last.  reverse swaps first and last.  concatenate is associative).  So the
+ * average of any contig of a cleaned graph is a fold over its piece list of the summaries of the build's calls, which is all the device has
+ * to hand over: no string, distance or coverage of a joined contig is made for it.
+ * fgpu_stage3_cov_calls: one summary per contig record into out_host[0 .. n).  contigs_host == NULL: the records are the calls of the last
+ * fgpu_stage3_build whose results are still on the device (FGPU_ERR_STATE if there is none; out_host has room for totals[0] records), and its
+ * records and coverages are read where they lie: the build wrote both itself, so nothing of it comes to the host.  The build is neither freed nor changed.
+ * n_contigs, cov_host and n_cov must then be 0 / NULL.  contigs_host != NULL: n_contigs records (cov_first and n_cov are read, nothing else)
+ * and the n_cov coverage bytes they index, in fgpu_stage3_contigs_take's layout, are uploaded first; the records may lie in any order and
+ * may share entries.  A record of no entries gives (0, 0, 0, 0).  FGPU_ERR_ARG with a message and nothing launched: a record that reaches
+ * past the coverages, a coverage array of some entries that is NULL, records and no out_host.  Nothing stays on the device.
+ * The record's layout, for a caller that does not include cov_summary.h (C++): 16 bytes, 8-byte aligned -- uint64_t sum at 0, uint32_t n at 8,
+ * uint8_t first at 12, uint8_t last at 13, two reserved bytes (0).
+ * fgpu_stage3_build_totals: the four totals of the last fgpu_stage3_build whose results are still on the device (calls, text words, segments,
+ * coverages; totals[0] is how many records the on-device form of fgpu_stage3_cov_calls writes); FGPU_ERR_STATE if there is none. */
+struct fgpu_cov_summary;
+int fgpu_stage3_build_totals(fgpu_ctx* ctx, uint64_t totals[4]);
+int fgpu_stage3_cov_calls(fgpu_ctx* ctx, const fgpu_contig* contigs_host, uint64_t n_contigs, const uint8_t* cov_host, uint64_t n_cov,
+                          struct fgpu_cov_summary* out_host);
+
 /* ---- Stage 3's first cleaning step: ContigGraph::deleteTipsAndClean on the build ----
  * The first step of ContigGraph::cleanGraph (src/ContigGraph.cpp:211-215) on the graph fgpu_raw_plan makes, and printContigs behind it.
  * Three layers, each callable alone.
@@ -1110,6 +1134,54 @@ int fgpu_stage3_fasta_joined(fgpu_ctx* ctx, const fgpu_joined* joined_host, cons
                              uint64_t text_words, uint64_t* bytes);
 int fgpu_stage3_detip(fgpu_ctx* ctx, int32_t read_length, uint64_t* bytes, fgpu_tips_info* info);
 int fgpu_stage3_graph_take(fgpu_ctx* ctx, fgpu_tips_out* out);
+
+/* ---- Stage 3's second cleaning step: ContigGraph::removeChimerasAndClean on the detipped graph ----
+ * The second step of ContigGraph::cleanGraph (src/ContigGraph.cpp:218-220), on the graph the first one left -- the SAME graph object
+ * (faucet_amd/csrc/clean_graph.h): nothing is made again between the steps -- and printContigs behind it.  The first step whose decisions read
+ * coverages: Contig::getAvgCoverage of a node's two extreme extensions and of its far node's, each the sum / n of an fgpu_cov_summary that
+ * collapseNode folds as it folds the piece lists (the section on coverage summaries above).
+ *   removeChimerasAndClean (:177-184): removeChimericExtensions(150), then validateNoneCollapsible only if it counted one; returns whether.
+ *   removeChimericExtensions (:642-707), per node in map order:
+ *     more than one path out: (P, Q) = getMinMaxForwardExtensions(node, "coverage") (:295-320: over getIndicesOut(), the indices with cov > 0
+ *       in order, the contig of the FIRST smallest and the LAST largest average -- std::minmax_element).  far = P->otherEndNode(node); the node
+ *       is left alone if far is null or the node itself, if far->indexOf(P) == 4 or if far has fewer than two paths out.  (P2, Q2) likewise
+ *       at far; ratio1 = avg(Q) / avg(P), ratio2 = avg(Q2) / avg(P2), in double, a zero average following IEEE.  If P has fewer than 150
+ *       bases, ratio1 >= 3 and P == P2: ratio1 > ratio2 -> cutPath(node, indexOf(P)); ratio2 > ratio1 -> cutPath(far, indexOf(P)); otherwise
+ *       both and deleteContig(P).  Then isCollapsible(node) -> collapseNode, the node erased.  Counted.
+ *     at most one path out: isCollapsible -> collapseNode, the node erased.
+ * fgpu_chimera_plan -- host only, no device: from the build (fgpu_tips_plan's arguments and cov_calls, one fgpu_cov_summary per call:
+ * fgpu_stage3_cov_calls' output) the graph, deleteTipsAndClean, removeChimerasAndClean, and printContigs' two passes.  `out` is filled as
+ * fgpu_tips_plan fills it, with the graph left and the print records after the second step; tips_info (may be NULL) is the first step's
+ * account without its print part.  Statuses are fgpu_tips_plan's; a call with a summary of no entries is FGPU_PLAN_INPUT; a covered slot
+ * without a contig, or an indexOf that throws, is FGPU_PLAN_UNSET.
+ * fgpu_stage3_dechimera -- the step on the LIVE graph of the last fgpu_stage3_detip (FGPU_ERR_STATE with a message if there is none, if its
+ * graph has been taken, or if the step has run on it already): fgpu_stage3_cov_calls on the build where it lies; the summaries folded into the
+ * live contigs; removeChimerasAndClean; fgpu_stage3_join of the print records; fgpu_stage3_fasta_joined of the joined text where it lies.
+ * Join results and a file that were not taken before it are dropped.  Afterwards fgpu_stage3_fasta_take gives the file (printContigs after the
+ * two steps), fgpu_stage3_join_take the records' strings, distances and coverages, fgpu_stage3_graph_take the graph after the step and
+ * fgpu_stage3_build_take the build, unchanged.  A plan status other than FGPU_PLAN_OK is FGPU_ERR_STATE with a message. */
+#define FGPU_CHIMERA_SKIP_NO_FAR    0   /* P has no far node, or it is the node itself */
+#define FGPU_CHIMERA_SKIP_BACK      1   /* P sits in the far node's slot 4 */
+#define FGPU_CHIMERA_SKIP_FAR_PATHS 2   /* the far node has fewer than two paths out */
+#define FGPU_CHIMERA_SKIP_LONG      3   /* P has 150 bases or more */
+#define FGPU_CHIMERA_SKIP_RATIO     4   /* ... is short, and ratio1 is below 3 (or no number) */
+#define FGPU_CHIMERA_SKIP_OTHER_P   5   /* ... and ratio1 is 3 or more, but P is not the far node's lowest extension */
+typedef struct {
+    uint64_t nodes_before;         /* entries of nodeMap before the step */
+    uint64_t removed;              /* what removeChimericExtensions returns */
+    uint64_t cut_near, cut_far, cut_both;   /* ... by outcome: cut at the node, at the far node, at both and P deleted */
+    uint64_t collapsed[2];         /* nodes collapseNode took out in the loop, in validateNoneCollapsible */
+    uint64_t degenerate[2];        /* nodes erased otherwise (the loop erases none) */
+    uint64_t collapsed_after_cut;  /* ... of collapsed[0]: right behind a cut at the same node; the rest had one path out when the loop came to them */
+    uint64_t skipped[6];           /* nodes with more than one path out that were left alone, by FGPU_CHIMERA_SKIP_* */
+    uint32_t validated;            /* 1: validateNoneCollapsible ran */
+    uint32_t changed;              /* what removeChimerasAndClean returns */
+    fgpu_raw_info print;           /* the records of the file; nodes = the nodes left */
+} fgpu_chimera_info;
+int fgpu_chimera_plan(const uint64_t* keys, const fgpu_junction* recs, uint64_t n_junctions, const fgpu_contig* contigs, const fgpu_build_call* calls,
+                      uint64_t n_calls, const struct fgpu_cov_summary* cov_calls, int32_t k, int32_t read_length, fgpu_tips_out* out,
+                      fgpu_tips_info* tips_info, fgpu_chimera_info* info);
+int fgpu_stage3_dechimera(fgpu_ctx* ctx, uint64_t* bytes, fgpu_chimera_info* info);
 
 /* ---- profiling --------------------------------------------------------------------------------- */
 typedef struct {
