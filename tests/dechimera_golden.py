@@ -8,6 +8,7 @@ The graph table (tests/golden/chimera_driver.cpp writes it) is the detip goldens
 import gzip
 import json
 import os
+import re
 import struct
 import subprocess
 
@@ -48,9 +49,10 @@ def compile_check(exe, sanitize):
 
 
 class Plan(D.Plan):
-    """what chimera_plan_check printed: tests/detip_golden.Plan with info over INFO_KEYS and tips_info, the first step's account, over TIPS_KEYS"""
+    """what chimera_plan_check printed (`text`): tests/detip_golden.Plan with info over INFO_KEYS and tips_info, the first step's account, over TIPS_KEYS"""
 
     def __init__(self, text):
+        self.text = text
         lines = text.splitlines()
         super().__init__("\n".join(lines[:4] + lines[5:]))
         self.info = dict(zip(INFO_KEYS, (int(v) for v in lines[3].split()[1:])))
@@ -68,14 +70,39 @@ def summaries_of(calls):
     return out
 
 
-def run_check(exe, path, keys, recs, contigs, calls, covs, k, read_length, cap=NO_LIMIT):
+def run_check(exe, path, keys, recs, contigs, calls, covs, k, read_length, cap=NO_LIMIT, mode=("plan",)):
+    """mode: ("plan",) or ("live",) or ("live", <refusal>) -- the Plan of what the program printed (a Live in live mode)"""
     with open(path, "wb") as f:
         f.write(struct.pack("<QQiiQ", len(keys), len(contigs), k, read_length, cap))
         for a in (np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(recs), contigs, calls, covs):
             f.write(a.tobytes())
-    r = subprocess.run([exe, "plan", path], capture_output=True, text=True, timeout=120, env=dict(os.environ, **SANITIZER_ENV))
+    r = subprocess.run([exe, mode[0], path, *mode[1:]], capture_output=True, text=True, timeout=120, env=dict(os.environ, **SANITIZER_ENV))
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr and r.returncode == 0, (r.returncode, r.stderr[-3000:])
-    return Plan(r.stdout)
+    return Plan(r.stdout) if mode[0] == "plan" else Live(r.stdout)
+
+
+class Live(Plan):
+    """what `chimera_plan_check live` printed: `text`, its output without the S0, S and refused lines (what `plan` prints); s0 [(summary, pieces)]
+    right behind set_cov and s [summary] behind the step, per contig the graph holds, summary = (sum, n, first, last); refused: the words behind
+    "refused", or None"""
+
+    def __init__(self, text):
+        lines = text.splitlines(keepends=True)
+        own = [ln for ln in lines if ln.split(" ", 1)[0] in ("S0", "S", "refused")]
+        self.text = "".join(ln for ln in lines if ln.split(" ", 1)[0] not in ("S0", "S", "refused"))
+        super().__init__(self.text)
+        self.s0, self.s, self.refused = [], [], None
+        for ln in own:
+            head, _, tail = ln.partition(":")
+            f = head.split()
+            if f[0] == "refused":
+                self.refused = f[1:]
+                continue
+            which = self.s0 if f[0] == "S0" else self.s
+            assert int(f[1]) == len(which), ln
+            v = [int(x) for x in tail.split()]
+            summary = tuple(int(x) for x in f[2:6])
+            which.append((summary, list(zip(v[::2], (bool(x) for x in v[1::2])))) if f[0] == "S0" else summary)
 
 
 def run_fold(exe, path, lines):
@@ -86,6 +113,15 @@ def run_fold(exe, path, lines):
     r = subprocess.run([exe, "fold", path], capture_output=True, text=True, timeout=120, env=dict(os.environ, **SANITIZER_ENV))
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr and r.returncode == 0, (r.returncode, r.stderr[-3000:])
     return [(int(a), int(b), int(c), int(d), e) for a, b, c, d, e in (ln.split() for ln in r.stdout.splitlines())]
+
+
+def counts_said(said):
+    """the counts line from what tests/golden/chimera_driver.cpp's run printed: the reference's own sentences behind "== chimeras" (the one place
+    that reads them: tests/golden/make_chimera_golden.py and tests/stage3_fuzz_cases.py both come here)"""
+    said = said.split("== chimeras\n", 1)[1]
+    chim = re.search(r"removed (\d+) chimeric contigs\.\s+(\d+) nodes left", said)
+    removed = re.search(r"removed (\d+) collapsible nodes\.\s+(\d+) nodes left", said)
+    return "counts %s %s %s\n" % (chim.group(1), removed.group(2) if removed else chim.group(2), removed.group(1) if removed else -1)
 
 
 def counts_line(info):

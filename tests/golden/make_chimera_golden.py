@@ -3,8 +3,8 @@
 (src/ContigGraph.cpp:168-184), for the Stage-3 fixtures:
     make -C oracle ref && python tests/golden/make_chimera_golden.py
 tests/golden/chimera_driver.cpp (our own text: it includes the reference's headers; nodeMap and isolated_contigs are private, so its compile line
-carries -fno-access-control) is built here with g++ against the compiled reference's objects under oracle/_ref/obj, as make_join_golden.py builds
-its driver; the binary goes to oracle/_ref/ and is never committed.  For every fixture of tests/stage3_variants.py the driver reloads the map as
+carries -fno-access-control) is built by oracle/Makefile's recipe (`make ref` builds it too), as the two other Stage-3 drivers are; the binary
+goes to oracle/_ref/ and is never committed.  For every fixture of tests/stage3_variants.py the driver reloads the map as
 tests/golden/raw_contigs_driver.cpp does, builds the graph, runs the two steps, writes the graph as a table and prints the contigs.  Stored:
 dechimera_<name>.fasta.gz and dechimera_<name>.graph.gz (the table, and as its last line the counts the reference printed;
 tests/dechimera_golden.py says how it reads) and dechimera_summary.json.  A variant is kept only where the reference exits 0 within the time
@@ -18,7 +18,6 @@ import glob
 import gzip
 import json
 import os
-import re
 import subprocess
 import sys
 import tempfile
@@ -28,8 +27,10 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 from tests import stage3_variants as V  # noqa: E402
+from tests.dechimera_golden import counts_said  # noqa: E402
 from tests.golden_util import Case  # noqa: E402
-from make_raw_contigs_golden import OUT, TIME_LIMIT, reference_tree  # noqa: E402
+from make_raw_contigs_golden import OUT, TIME_LIMIT  # noqa: E402
+from make_raw_contigs_golden import build_driver as raw_build_driver  # noqa: E402
 
 DRIVER = os.path.join(OUT, "chimera_driver")
 REQUIRED = ("cut_near", "cut_far", "cut_both", "collapse_right_behind_a_cut", "collapse_of_a_node_met_with_one_path", "skipped_p_in_slot_4",
@@ -48,12 +49,9 @@ def check_sizes():
     assert not too_large, (limit, too_large)
 
 
-def build_driver(driver=DRIVER):
-    objs = [o for o in sorted(glob.glob(os.path.join(OUT, "obj", "*.o")))
-            if os.path.basename(o) not in ("Faucet.o", "Faucet_nomain.o", "binding.o", "wrap_shim.o")]
-    assert objs, "make -C oracle ref first"
-    subprocess.run(["g++", "-std=c++11", "-O1", "-w", "-fno-access-control", "-include", "vector", "-include", "cmath", "-I" + reference_tree(),
-                    os.path.join(HERE, "chimera_driver.cpp")] + objs + ["-o", driver], check=True)
+def build_driver():
+    """oracle/Makefile holds the one recipe of the three drivers"""
+    raw_build_driver(DRIVER)
 
 
 def reference_files(c, bloom, lines, max_read_length, driver=DRIVER):
@@ -69,11 +67,7 @@ def reference_files(c, bloom, lines, max_read_length, driver=DRIVER):
             return None, "no return within %d s" % TIME_LIMIT
         if r.returncode != 0:
             return None, "exit %d" % r.returncode
-        said = r.stdout.decode(errors="replace").split("== chimeras\n", 1)[1]
-        chim = re.search(r"removed (\d+) chimeric contigs\.\s+(\d+) nodes left", said)
-        removed = re.search(r"removed (\d+) collapsible nodes\.\s+(\d+) nodes left", said)
-        counts = "counts %s %s %s\n" % (chim.group(1), removed.group(2) if removed else chim.group(2), removed.group(1) if removed else -1)
-        return open(fa, "rb").read(), open(gr).read() + counts
+        return open(fa, "rb").read(), open(gr).read() + counts_said(r.stdout.decode(errors="replace"))
 
 
 def reached_by(kept):

@@ -1,7 +1,8 @@
 """Stage-3 inputs made on the spot: from a case id to (reads file, arguments), all seeded, to the map the compiled reference's `faucet_ref`
-writes on those reads (.bloom, .junctions), and to what the reference's own Stage 3 says of that map (oracle/_ref/raw_contigs_driver and
-detip_driver, tests/golden/*.cpp built by `make -C oracle ref`).  Nothing is stored but the list of ids (tests/golden/stage3_fuzz_ids.json, written
-by tests/golden/make_stage3_fuzz_list.py, which also says which candidates the reference did not return on and why).
+writes on those reads (.bloom, .junctions), and to what the reference's own Stage 3 says of that map (oracle/_ref/raw_contigs_driver,
+detip_driver and, asked apart by chimera_answers, chimera_driver: tests/golden/*.cpp built by `make -C oracle ref`).  Nothing is stored but the
+list of ids (tests/golden/stage3_fuzz_ids.json, written by tests/golden/make_stage3_fuzz_list.py, which also says which candidates the reference
+did not return on and why).
 
 A case id is "<family>-<seed>" or "<family>-<seed>__<kind>": kind is a recipe of tests/stage3_variants.py (drop30, shift, mrl10) applied to the
 reference's own files before they go to the drivers -- the maps the contig-graph stage thins.  Families:
@@ -32,7 +33,7 @@ from tests.golden_util import GOLDEN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref")
-REF_BIN, RAW_DRIVER, DETIP_DRIVER = (os.path.join(REF, n) for n in ("faucet_ref", "raw_contigs_driver", "detip_driver"))
+REF_BIN, RAW_DRIVER, DETIP_DRIVER, CHIMERA_DRIVER = (os.path.join(REF, n) for n in ("faucet_ref", "raw_contigs_driver", "detip_driver", "chimera_driver"))
 LIST = os.path.join(GOLDEN, "stage3_fuzz_ids.json")
 FAMILIES = ("rand", "tandem", "runs", "hairpin", "circle")
 LOW_K = (8, 12, 15, 20, 21, 24, 31)
@@ -51,6 +52,11 @@ class NotReturned(Exception):
 
 def binaries_built():
     return all(os.path.exists(p) for p in (REF_BIN, RAW_DRIVER, DETIP_DRIVER))
+
+
+def chimera_driver_built():
+    """asked apart from binaries_built(): an oracle/_ref from before the driver had a recipe there still serves the tests of the two other drivers"""
+    return binaries_built() and os.path.exists(CHIMERA_DRIVER)
 
 
 def listed():
@@ -181,8 +187,20 @@ def answers_of(m):
     return Answers(raw, order, detip, table)
 
 
+def chimera_answers_of(m):
+    """what the reference says of a Map after removeChimerasAndClean behind deleteTipsAndClean (oracle/_ref/chimera_driver): (its contig file, its graph
+    table with the counts line; tests/dechimera_golden.py says how it reads)"""
+    from tests.dechimera_golden import counts_said
+    with tempfile.TemporaryDirectory() as td:
+        said = _driver(CHIMERA_DRIVER, m, td, ["chimera.fasta", "chimera.graph"])
+        with open(os.path.join(td, "chimera.fasta"), "rb") as f:
+            fasta = f.read()
+        with open(os.path.join(td, "chimera.graph")) as f:
+            return fasta, f.read() + counts_said(said)
+
+
 # ---- one run of the reference per id and process -----------------------------------------------------------------------------------------------
-_made, _runs = {}, {}
+_made, _runs, _chimera = {}, {}, {}
 _scratch = []
 
 
@@ -204,6 +222,19 @@ def case_of(case_id):
     if isinstance(_made[case_id], NotReturned):
         raise _made[case_id]
     return _made[case_id]
+
+
+def chimera_answers(case_id):
+    """(fasta bytes, graph table with its counts line) of the chimera driver on an id's Map; made once, shared, left unchanged.  NotReturned as
+    case_of"""
+    if case_id not in _chimera:
+        try:
+            _chimera[case_id] = chimera_answers_of(case_of(case_id)[3])
+        except NotReturned as e:
+            _chimera[case_id] = e
+    if isinstance(_chimera[case_id], NotReturned):
+        raise _chimera[case_id]
+    return _chimera[case_id]
 
 
 def reference_stdout(case_id):

@@ -6,7 +6,15 @@ tests/graph_build_ref.py gives with the map in the order the reference's reloade
 restated in plain Python over whole coverage lists, writes the same files and gives the same account.  The summary operations of
 faucet_amd/csrc/cov_summary.h, through the same program, against what the compiled reference's ContigJuncList made of the hand-made lists
 (tests/golden/join_concat.json.gz).  fgpu_tips_plan, now a few lines over the same header, against the detip goldens through the library.  Where
-oracle/_ref is built, the compiled reference is asked on the spot about 24 seeded maps (tests/chimera_cases.py).  No GPU.
+oracle/_ref is built, the compiled reference (oracle/_ref/chimera_driver) is asked on the spot about 24 seeded maps (tests/chimera_cases.py).  No GPU.
+
+The LIVE graph: fgpu_stage3_dechimera does not run fgpu_chimera_plan -- it works on the CleanGraph fgpu_stage3_detip left, which was built without
+summaries, detipped, serialised, and only then given the summaries by CleanGraph::set_cov, a fold over every surviving piece list.  The same program's
+`live` mode does just that, in that order, under the same sanitizers: its output has to be `plan`'s byte for byte on the goldens, the seeded orders and
+the 24 seeded maps (where it also has to write the driver's two files), and every summary of a live contig (S lines: right behind set_cov, and behind
+the step) has to be that of the coverage list tests/detip_ref.join makes of the contig's piece list from the calls' whole lists.  The inputs are
+counted to be able to tell: contigs with a flipped piece that reads differently backwards, long lists; what set_cov refuses is asked through mode
+arguments of the program.
 
 FGPU_PLAN_UNSET: among the 28 goldens, the 18 variants the reference does not return on (it stops in buildContigGraph on all of them, before
 either step) and the 67 seeded maps there is none on which the compiled reference aborts INSIDE this step, so the status is checked on a map
@@ -26,6 +34,7 @@ from tests import dechimera_plan_ref as R
 from tests import detip_golden as D
 from tests import detip_ref as J
 from tests import raw_contigs_ref as P
+from tests import stage3_fuzz_cases as S
 from tests.golden_util import Case
 from tests.join_cases import cases
 from tests.test_contig_ref_cpu import UNVARIED
@@ -83,10 +92,10 @@ def plan_exe(tmp_path_factory):
     return G.compile_check(str(tmp_path_factory.mktemp("chimera_plan") / "chimera_plan_check"), sanitize=True)
 
 
-def run(plan_exe, tmp_path, b, keys, recs, k, read_length, covs=None, contigs=None, calls=None, cap=G.NO_LIMIT):
+def run(plan_exe, tmp_path, b, keys, recs, k, read_length, covs=None, contigs=None, calls=None, cap=G.NO_LIMIT, mode=("plan",)):
     c, cl, _ = P.arrays_of(b.calls)
     return G.run_check(plan_exe, str(tmp_path / "plan.bin"), keys, recs, c if contigs is None else contigs, cl if calls is None else calls,
-                       G.summaries_of(b.calls) if covs is None else covs, k, read_length, cap)
+                       G.summaries_of(b.calls) if covs is None else covs, k, read_length, cap, mode)
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -173,6 +182,99 @@ def test_the_plan_program_on_short_room_on_arrays_that_are_no_build_and_where_th
     assert calm.info["skipped_4"] > 0 and calm.info["skipped_5"] == 0
 
 
+# ---- the live graph: the device's path (of_build without summaries, detip, the first step's records, set_cov, the step) as a program ----
+def summary_of(cov):
+    return (sum(cov), len(cov), cov[0], cov[-1])
+
+
+def live_and_plan(plan_exe, tmp_path, b, keys, recs, k, read_length):
+    """(`live`'s output, `plan`'s) over one build, after the two checks every input gets: live's output without its S lines IS plan's, byte for
+    byte (status, sizes, both accounts, the N, C and P lines), and every S line -- right behind set_cov over the list it stands beside, behind
+    the step over the contig record of its number -- is the summary of the coverage list tests/detip_ref.join makes of that piece list from
+    the calls' WHOLE lists"""
+    plan = run(plan_exe, tmp_path, b, keys, recs, k, read_length)
+    lv = run(plan_exe, tmp_path, b, keys, recs, k, read_length, mode=("live",))
+    assert lv.text == plan.text and lv.refused is None
+    if plan.status != 0:
+        assert not lv.s
+        return lv, plan
+    triples = D.triples_of(b.calls)
+    before = J.join(triples, [pl for _, pl in lv.s0], k) if lv.s0 else []
+    assert [s for s, _ in lv.s0] == [summary_of(j[2]) for j in before]
+    after = J.join(triples, [t[6] for t in lv.contigs], k) if lv.contigs else []
+    assert lv.s == [summary_of(j[2]) for j in after]
+    # a contig the step left alone is the same list with the same summary before and behind it
+    was = {tuple(pl): s for s, pl in lv.s0}
+    assert all(was[tuple(t[6])] == s for t, s in zip(lv.contigs, lv.s) if tuple(t[6]) in was)
+    return lv, plan
+
+
+def telling(lv, calls):
+    """(contigs of the graph the step left that have more than one piece and hold a flipped piece whose own summary has n >= 2 and first != last --
+    the ones a fold that forgets to reverse gets wrong --, the longest piece list, lists with a single-entry piece, ... with one not at an end, and
+    the first count again over the lists set_cov folded: the detipped graph, ahead of the step)"""
+    covs = G.summaries_of(calls)
+    asym = lambda c: int(covs[c]["n"]) >= 2 and int(covs[c]["first"]) != int(covs[c]["last"])      # noqa: E731
+    lists = [t[6] for t in lv.contigs]
+    single = [pl for pl in lists if len(pl) > 1 and any(int(covs[c]["n"]) == 1 for c, _ in pl)]
+    return (sum(1 for pl in lists if len(pl) > 1 and any(fl and asym(c) for c, fl in pl)), max(map(len, lists), default=0), len(single),
+            sum(1 for pl in single if any(int(covs[c]["n"]) == 1 for c, _ in pl[1:-1])),
+            sum(1 for _, pl in lv.s0 if len(pl) > 1 and any(fl and asym(c) for c, fl in pl)))
+
+
+_told = {}
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_the_live_graph_gives_the_plans_output_and_folds_every_summary_right(plan_exe, tmp_path, name):
+    b, keys, recs = build_in(name, "golden")
+    fx = _fixture(name)
+    lv, plan = live_and_plan(plan_exe, tmp_path, b, keys, recs, fx.case.k, fx.max_read_length)
+    assert lv.status == 0 and G.files_of_plan(lv, b.calls, fx.case.k) == (G.golden(name, "fasta"), G.golden(name, "graph").decode())
+    _told[name] = telling(lv, b.calls)
+
+
+def test_the_goldens_can_tell_a_wrong_fold(plan_exe, tmp_path):
+    """a fold that is wrong in first, last or sum shows in an S line only on a list with a flipped piece that reads differently backwards: the
+    goldens hold at least 100 such contigs behind the step (160 when this was written) and a list of at least 20 pieces (29)"""
+    for name in NAMES:
+        if name not in _told:
+            b, keys, recs = build_in(name, "golden")
+            fx = _fixture(name)
+            _told[name] = telling(run(plan_exe, tmp_path, b, keys, recs, fx.case.k, fx.max_read_length, mode=("live",)), b.calls)
+    flipped, longest, single, interior, folded = (f([_told[n][i] for n in NAMES]) for i, f in enumerate((sum, max, sum, sum, sum)))
+    print("contigs with a flipped asymmetric piece", flipped, "longest list", longest, "lists with a single-entry piece", single, "interior", interior,
+          "flipped asymmetric when set_cov folded", folded, "fixtures without one", [n for n in NAMES if not _told[n][4]])
+    assert flipped >= 100 and longest >= 20, (flipped, longest)
+
+
+@pytest.mark.parametrize("name, order", [(name, o) for name in UNVARIED for o in ORDERS[1:]])
+def test_the_live_graph_on_seeded_orders(plan_exe, tmp_path, name, order):
+    b, keys, recs = build_in(name, order)
+    fx = _fixture(name)
+    live_and_plan(plan_exe, tmp_path, b, keys, recs, fx.case.k, fx.max_read_length)
+
+
+def test_the_live_graph_refuses_what_it_cannot_fold(plan_exe, tmp_path):
+    name = "s3_k8"
+    b, keys, recs = build_in(name, "golden")
+    fx = _fixture(name)
+    k, mrl = fx.case.k, fx.max_read_length
+    full = run(plan_exe, tmp_path, b, keys, recs, k, mrl, mode=("live",))
+    assert full.status == 0 and full.info["removed"] and full.s and any(len(t[6]) > 1 for t in full.contigs)
+    # removeChimerasAndClean on a graph that was never given summaries: FGPU_PLAN_INPUT (2)
+    never = run(plan_exe, tmp_path, b, keys, recs, k, mrl, mode=("live", "no_summaries"))
+    assert never.refused == ["2"] and never.status == 2 and not any(never.info.values()) and not never.s0 and not never.s
+    # set_cov with one summary of no entries: FGPU_PLAN_INPUT, the graph still without summaries -- and nothing was written: the right summaries
+    # behind it give what they give alone, S lines included
+    zero = run(plan_exe, tmp_path, b, keys, recs, k, mrl, mode=("live", "zero_entries"))
+    assert zero.refused == ["2", "have_cov", "0"]
+    assert (zero.text, zero.s0, zero.s) == (full.text, full.s0, full.s)
+    # set_cov with n_calls one short of a call some list names: FGPU_PLAN_INPUT, the graph still without summaries
+    short = run(plan_exe, tmp_path, b, keys, recs, k, mrl, mode=("live", "short_calls"))
+    assert short.refused == ["2", "have_cov", "0", "named", "1"] and short.status == 2 and not short.s0 and not short.s
+
+
 def test_tips_plan_through_the_library_still_writes_the_detip_goldens():
     """the refactor: fgpu_tips_plan over clean_graph.h gives what it gave (tests/test_detip_plan_cpu.py holds the stand-alone program to the same)"""
     from faucet_amd import api
@@ -250,38 +352,19 @@ def test_cli_dechimered_contigs_without_the_entry_points_exits_2_before_any_inpu
 
 
 # ---- the compiled reference, asked on the spot ----
-def _spot_driver(tmp_path_factory):
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    import make_chimera_golden as M
-    driver = str(tmp_path_factory.mktemp("chimera_driver") / "chimera_driver")
-    M.build_driver(driver)
-    return M, driver
+driver_built = pytest.mark.skipif(not os.path.exists(S.CHIMERA_DRIVER), reason="oracle/_ref/chimera_driver was not built (make -C oracle ref)")
 
 
-def _reference_is_here():
-    """the compiled reference's objects AND the tree whose headers the driver includes (oracle/_ref may have travelled without it)"""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    from make_raw_contigs_golden import reference_tree
-    return os.path.isdir(os.path.join(ROOT, "oracle", "_ref", "obj")) and os.path.isfile(os.path.join(reference_tree(), "src", "ContigGraph.h"))
-
-
-@pytest.mark.skipif(not _reference_is_here(), reason="the compiled reference's objects (oracle/_ref/obj) and its source tree are there where the reference is mounted "
-                    "(make -C oracle ref)")
-def test_the_compiled_reference_asked_on_the_spot_about_seeded_maps(plan_exe, tmp_path_factory, tmp_path):
-    """24 maps none of this was written against (tests/chimera_cases.py): the driver is built here and now, and the restatement and the plan program
-    have to write its files; the ids on which the validation behind the step erases a node say so in the reference's own count line"""
-    from tests import stage3_fuzz_cases as S
+@driver_built
+def test_the_compiled_reference_asked_on_the_spot_about_seeded_maps(plan_exe, tmp_path):
+    """24 maps none of this was written against (tests/chimera_cases.py): oracle/_ref/chimera_driver is asked here and now, and the restatement and the
+    plan program have to write its files; the ids on which the validation behind the step erases a node say so in the reference's own count line"""
     from tests.test_stage3_fuzz_cpu import account_of
-    if not S.binaries_built():
-        pytest.skip("oracle/_ref/faucet_ref and the Stage-3 drivers are not built")
-    M, driver = _spot_driver(tmp_path_factory)
     erased = []
     for case_id in chimera_cases.SPOT_IDS:
         a = account_of(case_id)
         m = a.map
-        fasta, table = _reference(M, driver, m)
+        fasta, table = S.chimera_answers(case_id)
         nodes, contigs, records, info, tips_info, _ = restated(a.build.calls, a.keys, a.recs, m.k, m.max_read_length)
         assert G.files_of(nodes, contigs, records, info, tips_info["changed"], a.build.calls, m.k) == (fasta, table), case_id
         plan = run(plan_exe, tmp_path, a.build, a.keys, a.recs, m.k, m.max_read_length)
@@ -292,11 +375,24 @@ def test_the_compiled_reference_asked_on_the_spot_about_seeded_maps(plan_exe, tm
     assert erased == chimera_cases.VALIDATION_IDS
 
 
-def _reference(M, driver, m):
-    """(fasta bytes, graph table with its counts line) of the chimera driver on a tests/stage3_fuzz_cases.Map"""
-    class Shape:
-        counters = {"n_hash": m.n_hash}
-        k, j = m.k, m.j
-    fasta, table = M.reference_files(Shape, m.bloom, m.lines, m.max_read_length, driver)
-    assert fasta is not None, table
-    return fasta, table
+@pytest.mark.skipif(not S.chimera_driver_built(), reason="oracle/_ref/faucet_ref and the three Stage-3 drivers were not built (make -C oracle ref)")
+@pytest.mark.parametrize("case_id", chimera_cases.SPOT_IDS)
+def test_the_live_graph_writes_the_references_files_on_seeded_maps(plan_exe, tmp_path, case_id):
+    """the device's path on the maps where it is hardest: on the VALIDATION_IDS the validation behind the step erases a node ON THE LIVE GRAPH,
+    as many as the reference's own count line says, and each of them holds at least 20 contigs that can tell a wrong fold (22 to 188 when this was
+    written)"""
+    from tests.test_stage3_fuzz_cpu import account_of
+    a = account_of(case_id)
+    m = a.map
+    lv, plan = live_and_plan(plan_exe, tmp_path, a.build, a.keys, a.recs, m.k, m.max_read_length)
+    fasta, table = S.chimera_answers(case_id)
+    assert lv.status == 0 and G.files_of_plan(lv, a.build.calls, m.k) == (fasta, table)
+    told = telling(lv, a.build.calls)
+    print(case_id, "contigs with a flipped asymmetric piece", told[0], "longest list", told[1], "lists with a single-entry piece", told[2], "interior", told[3],
+          "flipped asymmetric when set_cov folded", told[4])
+    if case_id in chimera_cases.VALIDATION_IDS:
+        erased = lv.info["collapsed_1"] + lv.info["degenerate_1"]
+        assert lv.info["validated"] and erased > 0 and erased == int(table.splitlines()[-1].split()[3])
+        assert told[0] >= 20, told
+    if case_id == chimera_cases.LONGEST_LIST_ID:
+        assert told[1] >= 20, told                                             # (37 pieces when this was written)

@@ -52,6 +52,16 @@ def restated(m, ans, order=None):
     return Account(m, ans, b, keys, recs, raw, raw_info, plan, detip, table)
 
 
+def dechimered(a):
+    """the restatement of the next step, removeChimerasAndClean (tests/dechimera_plan_ref.py), over an Account's build in the Account's order: (the
+    file after the two steps, the step's account over tests/dechimera_golden.INFO_KEYS and more); not part of the Account, so that only who asks
+    pays for it"""
+    from tests import dechimera_plan_ref
+    from tests import detip_ref
+    records, info = dechimera_plan_ref.plan(a.build.calls, a.keys, a.recs["cov"], a.map.k, a.map.max_read_length)[2:4]
+    return D.fasta_of(records, detip_ref.join(D.triples_of(a.build.calls), [p for _, p in records], a.map.k) if records else []), info
+
+
 def classes_of(a):
     """the classes of the module's docstring an id reaches, from the reference's own files and the restatement's account of the map"""
     seqs = a.answers.raw_fasta.decode().split("\n")[1::2]
