@@ -111,6 +111,17 @@ class ChimeraInfo(C.Structure):
                     skipped=[int(v) for v in self.skipped], validated=int(self.validated), changed=int(self.changed), print=self.print.as_dict())
 
 
+class FastgInfo(C.Structure):
+    """fgpu_fastg_info: ContigGraph::printGraph's counts"""
+    _fields_ = [(n, C.c_uint64) for n in ("node_records", "isolated_printed", "isolated_listed", "nodes")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+FASTG_PRIMED, FASTG_TILE, FASTG_NAME_STRIDE = 0x80000000, 4096, 64
+
+
 class TipsOut(C.Structure):
     """fgpu_tips_out: the arrays fgpu_tips_plan and fgpu_stage3_graph_take fill, their room, and how much was needed"""
     _fields_ = [("nodes", C.c_void_p), ("nodes_cap", C.c_uint64), ("n_nodes", C.c_uint64),
@@ -248,6 +259,10 @@ SIGNATURES = {
     "fgpu_stage3_graph_take": (C.c_int, [_vp, _P(TipsOut)]),
     "fgpu_chimera_plan": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _i32, _i32, _P(TipsOut), _P(TipsInfo), _P(ChimeraInfo)]),
     "fgpu_stage3_dechimera": (C.c_int, [_vp, _P(_u64), _P(ChimeraInfo)]),
+    "fgpu_stage3_fastg": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _P(_u64)]),
+    "fgpu_stage3_raw_graph": (C.c_int, [_vp, _i32, _P(_u64), _P(FastgInfo)]),
+    "fgpu_stage3_graph_fastg": (C.c_int, [_vp, _P(_u64), _P(FastgInfo)]),
+    "fgpu_diag_fastg_times": (C.c_int, [_vp, _P(_f64)]),
     "fgpu_kernel_times": (C.c_int, [_vp, _P(KernelTime), C.c_int]),
     "fgpu_kernel_times_reset": (C.c_int, [_vp]),
     "fgpu_profile_enable": (C.c_int, [_vp, C.c_int]),

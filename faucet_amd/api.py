@@ -133,6 +133,8 @@ TIPS_CONTIG_DTYPE = np.dtype([("node1", "<u8"), ("node2", "<u8"), ("len", "<u4")
 JOINED_DTYPE = np.dtype([("text_word", "<u8"), ("dist_first", "<u8"), ("cov_first", "<u8"), ("cov_sum", "<u8"), ("len", "<u4"), ("n_dist", "<u4"),
                          ("n_cov", "<u4"), ("reserved", "<u4")])   # fgpu_joined
 COV_SUMMARY_DTYPE = np.dtype([("sum", "<u8"), ("n", "<u4"), ("first", "u1"), ("last", "u1"), ("reserved", "u1", (2,))])   # fgpu_cov_summary (csrc/cov_summary.h)
+FASTG_REC_DTYPE = np.dtype([("tig", "<u8"), ("text_word", "<u8"), ("cov_sum", "<u8"), ("len", "<u4"), ("cov_n", "<u4")])   # fgpu_fastg_rec
+FASTG_PRIMED, FASTG_TILE = L.FASTG_PRIMED, L.FASTG_TILE   # a primed neighbour entry; bytes of output per workgroup of the text kernel
 
 
 class _PinnedMemory:
@@ -924,6 +926,50 @@ class Context:
         ci = L.ChimeraInfo()
         self._c(self.lib.fgpu_stage3_dechimera(self.h, C.byref(nbytes), C.byref(ci)))
         return self.stage3_fasta_take(nbytes.value), ci.as_dict()
+
+    def stage3_fastg(self, recs, neighbours, text=None) -> bytes:
+        """FASTG_REC_DTYPE records printed as ContigGraph::printGraph prints contigs (fgpu_stage3_fastg): per record the primed header, its len
+        bases from word text_word of the text, the other header, and the reverse complement.  neighbours: per record (primed header's, other
+        header's), each a list of at most four (record, primed).  text: joined 2-bit words (stage3_join(raw=True)'s); None: the joined text the
+        last fgpu_stage3_join left on the device, read where it lies."""
+        recs = np.ascontiguousarray(recs, dtype=FASTG_REC_DTYPE)
+        if len(neighbours) != len(recs):
+            raise ValueError("two neighbour lists per record")
+        flat = [lst for pair in neighbours for lst in pair]
+        first = np.zeros(2 * len(recs) + 1, dtype=np.uint64)
+        first[1:] = np.cumsum([len(lst) for lst in flat], dtype=np.uint64)
+        nbr = np.array([int(r) | (FASTG_PRIMED if p else 0) for lst in flat for r, p in lst], dtype=np.uint32)
+        return self.stage3_fastg_csr(recs, first, nbr, text)
+
+    def stage3_fastg_csr(self, recs, first, nbr, text=None) -> bytes:
+        """stage3_fastg with the neighbour lists as the library takes them: first (2 n + 1 uint64), nbr (uint32, record | FASTG_PRIMED)"""
+        recs = np.ascontiguousarray(recs, dtype=FASTG_REC_DTYPE)
+        first, nbr = np.ascontiguousarray(first, dtype=np.uint64), np.ascontiguousarray(nbr, dtype=np.uint32)
+        if text is not None:
+            text = np.ascontiguousarray(text, dtype=np.uint64)
+        nbytes = C.c_uint64(0)
+        self._c(self.lib.fgpu_stage3_fastg(self.h, recs.ctypes.data, len(recs), first.ctypes.data, nbr.ctypes.data if len(nbr) else None, len(nbr),
+                                           None if text is None else text.ctypes.data, 0 if text is None else len(text), C.byref(nbytes)))
+        return self.stage3_fasta_take(nbytes.value)
+
+    def stage3_raw_graph(self, read_length: int):
+        """the reference's <prefix>.raw_graph.fastg (ContigGraph::printGraph on the graph of buildContigGraph, src/Faucet.cpp:313) of the build
+        stage3_build(max_read_length, take=False) left on the device (fgpu_stage3_raw_graph): (the file's bytes, info = dict(node_records,
+        isolated_printed, isolated_listed, nodes)).  The build and a live graph stay as they are.  Join results and a file that were not taken
+        before the call are dropped."""
+        nbytes = C.c_uint64(0)
+        fi = L.FastgInfo()
+        self._c(self.lib.fgpu_stage3_raw_graph(self.h, int(read_length), C.byref(nbytes), C.byref(fi)))
+        return self.stage3_fasta_take(nbytes.value), fi.as_dict()
+
+    def stage3_graph_fastg(self):
+        """ContigGraph::printGraph on the live graph the last stage3_detip or stage3_dechimera left (fgpu_stage3_graph_fastg): (the file's bytes,
+        info as stage3_raw_graph's).  The graph is not changed and the call may be repeated.  Join results and a file that were not taken before
+        the call are dropped."""
+        nbytes = C.c_uint64(0)
+        fi = L.FastgInfo()
+        self._c(self.lib.fgpu_stage3_graph_fastg(self.h, C.byref(nbytes), C.byref(fi)))
+        return self.stage3_fasta_take(nbytes.value), fi.as_dict()
 
     def kernel_times(self) -> dict:
         arr = (L.KernelTime * 64)()

@@ -18,9 +18,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfaucet_gpu.so")
 CLI = os.path.join(HERE, "faucet")
-HIP_SOURCES = ["api.hip", "pack.hip", "load.hip", "load_slices.hip", "estimate.hip", "scan_driver.hip", "scan_pure.hip", "scan_walk.hip", "scan_table.hip", "scan_harvest.hip", "diag.hip", "text.hip", "stage3.hip", "stage3_emit.hip", "stage3_join.hip", "pairs.hip", "group.hip"]
+HIP_SOURCES = ["api.hip", "pack.hip", "load.hip", "load_slices.hip", "estimate.hip", "scan_driver.hip", "scan_pure.hip", "scan_walk.hip", "scan_table.hip", "scan_harvest.hip", "diag.hip", "text.hip", "stage3.hip", "stage3_emit.hip", "stage3_fastg.hip", "stage3_join.hip", "pairs.hip", "group.hip"]
 CPP_SOURCES = ["sizing.cpp", "raw_plan.cpp", "tips_plan.cpp"]
-HEADERS = ["fgpu_ctx.h", "fgpu_device.h", "fgpu_flags.h", "dense_hits.h", "load_common.h", "walk_tables.h", "walk_span.h", "stage3_bits.h", "build_graph.h", "clean_graph.h", "cov_summary.h", os.path.join(ROOT, "include", "faucet_gpu.h")]
+HEADERS = ["fgpu_ctx.h", "fgpu_device.h", "fgpu_flags.h", "dense_hits.h", "load_common.h", "walk_tables.h", "walk_span.h", "stage3_bits.h", "build_graph.h", "clean_graph.h", "cov_summary.h", "fastg_name.h", os.path.join(ROOT, "include", "faucet_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value"] + os.environ.get("FGPU_EXTRA_CXXFLAGS", "").split()
 

@@ -14,6 +14,8 @@
 //   testAndCutIfDegenerate                         src/ContigGraph.cpp:403-425
 //   validateNoneCollapsible                        src/ContigGraph.cpp:709-736
 //   printAndMarkBubbleContigs, printUnmarkedUnitigs  src/ContigGraph.cpp:1543-1580, :1605-1645 (as raw_plan.cpp walks them)
+//   printGraph, ContigIterator                     src/ContigGraph.cpp:1470-1503, src/ContigIterator.cpp
+//   Contig::getNeighbors, getFastGNeighbors        src/Contig.cpp:290-302, src/ContigNode.cpp:179-202
 // Wherever the reference would go through a pointer to a node that was erased or a contig that was deleted, or with an index that is none,
 // the answer is FGPU_PLAN_UNSET.
 #ifndef FGPU_CLEAN_GRAPH_H
@@ -58,6 +60,13 @@ struct Room {                // an output array: written while there is room, co
     Room(T* o, uint64_t c) : out(o), cap(o ? c : 0) {}
     void put(const T& v) { if (n < cap) out[n] = v; n++; }
     bool fits() const { return !n || n <= cap; }
+};
+
+struct FastgPlan {            // what ContigGraph::printGraph writes, in file order (CleanGraph::fastg_records)
+    std::vector<int64_t> tig;            // per record: the contig, as a number of CleanGraph::tigs (its piece list, length and summary are there)
+    std::vector<uint64_t> nbr_first;     // 2 records + 1: the neighbours of record r's primed header are nbr[nbr_first[2r] .. nbr_first[2r + 1]),
+    std::vector<uint32_t> nbr;           // those of its other header nbr[nbr_first[2r + 1] .. nbr_first[2r + 2]); an entry: record | FGPU_FASTG_PRIMED
+    fgpu_fastg_info info = {0, 0, 0, 0};
 };
 
 struct CleanGraph {
@@ -492,6 +501,79 @@ struct CleanGraph {
         out->n_print = print_number.n; out->n_print_pieces = print_pieces.n;
         const bool fits = (!print_number.n || (print_number.n <= print_number.cap && print_first.n <= print_first.cap)) && print_pieces.fits();
         return fits ? FGPU_PLAN_OK : FGPU_PLAN_SHORT;
+    }
+
+    // ---- printGraph's walk over the graph as it stands (ContigIterator, then isolated_contigs): the FASTG records in file order.  Reads only:
+    // the graph is not changed, not even its `unset` mark.  FGPU_PLAN_OK; FGPU_PLAN_UNSET wherever the reference would go through a pointer that is
+    // null or gone, or asks Contig::getSide(node, index) for an end the contig does not have; FGPU_PLAN_INPUT: the graph knows no coverages, or
+    // a neighbour is a contig the walk prints nowhere (its first end's slot does not hold it: no step leaves such a graph; the reference would
+    // print its name, this plan has no record to name) -- FGPU_PLAN_UNSET comes first where the graph holds both
+    int fastg_records(FastgPlan& out) const {
+        out = FastgPlan();
+        if (!have_cov) return FGPU_PLAN_INPUT;
+        std::vector<int64_t> record_of(tigs.size(), NONE);
+        auto live = [&](int64_t c) { return c != NONE && tigs[c].alive; };
+        auto record = [&](int64_t c) {
+            if (record_of[c] == NONE) record_of[c] = (int64_t)out.tig.size();
+            out.tig.push_back(c);
+        };
+        for (const auto& kv : g.node_map) {                              // ContigIterator::findNextContig
+            const uint64_t node = kv.first;
+            for (int index = 0; index < 5; index++) {
+                const int64_t c = kv.second.contigs[index];
+                if (c == NONE) continue;
+                if (!live(c)) return FGPU_PLAN_UNSET;
+                const Tig& t = tigs[c];
+                if (!t.has1 || !t.has2) { record(c); continue; }         // one side is a sink: always
+                if (t.node1 == t.node2) {                                // both ends on one node: at the lower index
+                    if (index == std::min(t.ind1, t.ind2)) record(c);
+                    continue;
+                }
+                const int s = side_at(t, node, index);
+                if (s < 0) return FGPU_PLAN_UNSET;
+                if (s == 1) record(c);
+            }
+        }
+        out.info.node_records = out.tig.size();
+        out.info.nodes = g.node_map.size();
+        out.info.isolated_listed = isolated.size();
+        for (int64_t c : isolated) {
+            if (!live(c)) return FGPU_PLAN_UNSET;
+            if (tigs[c].len >= (uint64_t)(int64_t)read_length) {         // (size_t >= int: the int goes to unsigned)
+                record(c);
+                out.info.isolated_printed++;
+            }
+        }
+        // Contig::getNeighbors: the primed header's (RC) through node1_p and ind1, the other's through node2_p and ind2
+        int status = FGPU_PLAN_OK;
+        bool nowhere = false;
+        auto neighbours = [&](bool has, uint64_t key, int ind) {
+            if (has) {
+                const auto at = g.node_map.find(key);
+                if (at == g.node_map.end()) { status = FGPU_PLAN_UNSET; return; }
+                const Node& nd = at->second;
+                for (int i = ind == 4 ? 0 : 4; i < (ind == 4 ? 4 : 5); i++) {          // ContigNode::getFastGNeighbors
+                    const int64_t c = nd.contigs[i];
+                    if (c == NONE) continue;
+                    if (!live(c)) { status = FGPU_PLAN_UNSET; return; }
+                    const int s = side_at(tigs[c], key, i);
+                    if (s < 0) { status = FGPU_PLAN_UNSET; return; }
+                    if (record_of[c] == NONE) { nowhere = true; continue; }     // (what is undefined elsewhere in the graph comes first: the walk goes on)
+                    out.nbr.push_back((uint32_t)record_of[c] | (s == 2 ? FGPU_FASTG_PRIMED : 0u));
+                }
+            }
+        };
+        if (out.tig.size() >= (uint64_t)FGPU_FASTG_PRIMED) return FGPU_PLAN_INPUT;
+        out.nbr_first.push_back(0);
+        for (int64_t c : out.tig) {
+            const Tig& t = tigs[c];
+            neighbours(t.has1, t.node1, t.ind1);
+            out.nbr_first.push_back(out.nbr.size());
+            neighbours(t.has2, t.node2, t.ind2);
+            out.nbr_first.push_back(out.nbr.size());
+            if (status != FGPU_PLAN_OK) return status;
+        }
+        return nowhere ? FGPU_PLAN_INPUT : FGPU_PLAN_OK;
     }
 
     // ---- the graph as it stands, into out's nodes, contigs, list_first and pieces (n_nodes, n_contigs, n_pieces are set whatever the room).

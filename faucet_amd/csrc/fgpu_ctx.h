@@ -455,6 +455,7 @@ struct fgpu_ctx {
                                                          // the next cleaning step works on it
     uint64_t s3t_serial = 0;              // ... the build it was made of
     bool s3t_dechimered = false;          // ... fgpu_stage3_dechimera has run on it
+    double s3g_ms[6] = {0, 0, 0, 0, 0, 0};   // the last fgpu_stage3_raw_graph / _graph_fastg by parts, host clock (fgpu_diag_fastg_times)
     uint64_t s3_mask = 0, s3_count = 0;
     bool s3_ready = false;
     DevBuf dl_entries, dl_stamps, dl_stamps_sorted, dl_idx, dl_idx_sorted, dl_keys, dl_recs, dl_tmp;   // junction download scratch

@@ -2,7 +2,9 @@
 // (fgpu_stage3_fasta, fgpu_stage3_fasta_take, fgpu_stage3_raw_contigs; include/faucet_gpu.h) -- and its second, the contigs after the first
 // cleaning step, printed from the strings fgpu_stage3_join left on the device (fgpu_stage3_fasta_joined, fgpu_stage3_detip,
 // fgpu_stage3_graph_take), and likewise after the second step (fgpu_stage3_dechimera), which works on the graph the first one left: the
-// context keeps the live graph object (clean_graph.h) between the steps, and nothing of it is made again.
+// context keeps the live graph object (clean_graph.h) between the steps, and nothing of it is made again.  The graph itself as FASTG
+// (fgpu_stage3_raw_graph, fgpu_stage3_graph_fastg, at the end of this file) is put together here too: the walk is clean_graph.h's, the kernels
+// stage3_fastg.hip's.
 //
 // What the reference does per record, ContigGraph::printContigs (src/ContigGraph.cpp:1532-1645):
 //   ContigJuncList::concatenate's sequence          utils/ContigJuncList.cpp:121   first.substr(0, len - k) + second
@@ -527,4 +529,96 @@ extern "C" int fgpu_stage3_graph_take(fgpu_ctx* ctx, fgpu_tips_out* out) {
     if (st != FGPU_PLAN_OK) { ctx->err = "fgpu_stage3_graph_take: the graph did not fit the room it asked for"; return FGPU_ERR_INTERNAL; }
     ctx->s3t_graph.reset();
     return FGPU_OK;
+}
+
+namespace {
+
+// ContigGraph::printGraph of a graph that knows its coverages: the walk (CleanGraph::fastg_records), fgpu_stage3_join of the records' lists over
+// the build where it lies, fgpu_stage3_fastg of the joined text where it lies.  The graph is read only.
+int emit_fastg(fgpu_ctx* ctx, const std::string& who, const fgpu_graph::CleanGraph& cg, uint64_t* bytes, fgpu_fastg_info* info) {
+    fgpu_graph::FastgPlan plan;
+    double t0 = fgpu_host_now();
+    const int st = cg.fastg_records(plan);
+    ctx->s3g_ms[3] = fgpu_host_now() - t0;
+    if (st != FGPU_PLAN_OK)
+        return emit_plan_failed(ctx, who, "the FASTG walk's", "ContigGraph::printGraph goes through a pointer that was never set or whose target is gone, or asks a contig for an end it does not have", st);
+    const uint64_t n = plan.tig.size();
+    t0 = fgpu_host_now();
+    std::vector<uint64_t> first(n + 1, 0);
+    std::vector<fgpu_join_piece> pieces;
+    for (uint64_t r = 0; r < n; r++) {
+        const auto& list = cg.tigs[plan.tig[r]].list;
+        pieces.insert(pieces.end(), list.begin(), list.end());
+        first[r + 1] = pieces.size();
+    }
+    std::vector<fgpu_joined> joined(n);
+    uint64_t totals[3];
+    if (int rc = fgpu_stage3_join(ctx, first.data(), n, pieces.data(), pieces.size(), nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, joined.data(), totals)) return rc;
+    ctx->s3g_ms[4] = fgpu_host_now() - t0;
+    t0 = fgpu_host_now();
+    std::vector<fgpu_fastg_rec> recs(n);
+    for (uint64_t r = 0; r < n; r++) {
+        const fgpu_cov_summary& cov = cg.tigs[plan.tig[r]].cov;
+        recs[r] = fgpu_fastg_rec{(uint64_t)plan.tig[r], joined[r].text_word, cov.sum, joined[r].len, cov.n};
+    }
+    if (int rc = fgpu_stage3_fastg(ctx, recs.data(), n, plan.nbr_first.data(), plan.nbr.data(), plan.nbr.size(), nullptr, 0, bytes)) return rc;
+    ctx->s3g_ms[5] = fgpu_host_now() - t0;
+    if (info) *info = plan.info;
+    return FGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int fgpu_diag_fastg_times(fgpu_ctx* ctx, double ms[6]) {
+    if (!ctx || !ms) return FGPU_ERR_ARG;
+    memcpy(ms, ctx->s3g_ms, sizeof(ctx->s3g_ms));
+    return FGPU_OK;
+}
+
+extern "C" int fgpu_stage3_raw_graph(fgpu_ctx* ctx, int32_t read_length, uint64_t* bytes, fgpu_fastg_info* info) {
+    if (!ctx || !bytes) return FGPU_ERR_ARG;
+    *bytes = 0;
+    if (info) memset(info, 0, sizeof(*info));
+    const std::string who = "fgpu_stage3_raw_graph";
+    EmitBuild b;
+    memset(ctx->s3g_ms, 0, sizeof(ctx->s3g_ms));
+    double t0 = fgpu_host_now();
+    if (int rc = emit_build_records(ctx, who, b)) return rc;
+    ctx->s3g_ms[0] = fgpu_host_now() - t0;
+    t0 = fgpu_host_now();
+    const uint64_t n_calls = b.contigs.size();
+    std::vector<fgpu_cov_summary> cov(n_calls + 1);                  // (one more: an empty build's graph still has to know that it was given them)
+    if (int rc = fgpu_stage3_cov_calls(ctx, nullptr, 0, nullptr, 0, cov.data())) return rc;
+    ctx->s3g_ms[1] = fgpu_host_now() - t0;
+    t0 = fgpu_host_now();
+    fgpu_graph::CleanGraph cg;                                       // this call's own: a live graph, if there is one, is another object
+    const int st = cg.of_build(b.keys.data(), b.recs.data(), b.keys.size(), b.contigs.data(), b.calls.data(), n_calls, cov.data(), ctx->prm.k, read_length);
+    ctx->s3g_ms[2] = fgpu_host_now() - t0;
+    if (st != FGPU_PLAN_OK) return emit_plan_failed(ctx, who, "the graph's", "JunctionMap::buildContigGraph leaves a pointer unset", st);
+    return emit_fastg(ctx, who, cg, bytes, info);
+}
+
+extern "C" int fgpu_stage3_graph_fastg(fgpu_ctx* ctx, uint64_t* bytes, fgpu_fastg_info* info) {
+    if (!ctx || !bytes) return FGPU_ERR_ARG;
+    *bytes = 0;
+    if (info) memset(info, 0, sizeof(*info));
+    const std::string who = "fgpu_stage3_graph_fastg";
+    if (!ctx->s3t_graph) { ctx->err = who + ": no fgpu_stage3_detip whose graph has not been taken"; return FGPU_ERR_STATE; }
+    if (!ctx->s3b_have || ctx->s3t_serial != ctx->s3b_serial) {
+        ctx->err = who + ": the build the graph was made of is no longer on the device (taken, or another build was made)";
+        return FGPU_ERR_STATE;
+    }
+    if (ctx->phase != 0) { ctx->err = who + " while a pass is open"; return FGPU_ERR_STATE; }
+    fgpu_graph::CleanGraph& cg = *ctx->s3t_graph;
+    memset(ctx->s3g_ms, 0, sizeof(ctx->s3g_ms));
+    if (!cg.have_cov) {                                              // what fgpu_stage3_dechimera would give it, and gives it again
+        const double t0 = fgpu_host_now();
+        const uint64_t n_calls = ctx->s3b_totals[0];
+        std::vector<fgpu_cov_summary> cov(n_calls);
+        if (int rc = fgpu_stage3_cov_calls(ctx, nullptr, 0, nullptr, 0, cov.data())) return rc;
+        const int st = cg.set_cov(cov.data(), n_calls);
+        if (st != FGPU_PLAN_OK) return emit_plan_failed(ctx, who, "the summaries'", "", st);
+        ctx->s3g_ms[1] = fgpu_host_now() - t0;
+    }
+    return emit_fastg(ctx, who, cg, bytes, info);
 }

@@ -72,6 +72,9 @@
 #pragma weak fgpu_stage3_detip
 // ... and of --dechimered_contigs (ContigGraph::removeChimerasAndClean on the graph that step left)
 #pragma weak fgpu_stage3_dechimera
+// ... and the two of --raw_graph, --detipped_graph and --dechimered_graph (ContigGraph::printGraph on the build's graph and on the live one)
+#pragma weak fgpu_stage3_raw_graph
+#pragma weak fgpu_stage3_graph_fastg
 
 using faucet_host::ReadSource;
 using faucet_host::TextSource;
@@ -103,6 +106,9 @@ struct Options {   // globals of src/Faucet.h:14-53
     bool scan_kept = false;           // not a reference flag: --scan_kept, pass 2 scans the batches pass 1 kept; -read_scan_file may be left out
     bool raw_contigs = false;         // not a reference flag: --raw_contigs, <prefix>.raw_contigs.fasta (the file src/Faucet.cpp:314 would write) behind the scan outputs
     bool detipped_contigs = false;    // not a reference flag: --detipped_contigs, <prefix>.detipped_contigs.fasta (what printContigs would write after the first deleteTipsAndClean of cleanGraph)
+    bool raw_graph = false;           // not a reference flag: --raw_graph, <prefix>.raw_graph.fastg (the file src/Faucet.cpp:313 would write: ContigGraph::printGraph behind the build)
+    bool detipped_graph = false;      // not a reference flag: --detipped_graph, <prefix>.detipped_graph.fastg (printGraph after the first deleteTipsAndClean)
+    bool dechimered_graph = false;    // not a reference flag: --dechimered_graph, <prefix>.dechimered_graph.fastg (... after the removeChimerasAndClean behind it)
     bool dechimered_contigs = false;  // not a reference flag: --dechimered_contigs, <prefix>.dechimered_contigs.fasta (... after the removeChimerasAndClean behind it)
 };
 
@@ -116,7 +122,10 @@ void argument_error() {   // src/Faucet.cpp:50-54
                     "--scan_kept (pass 2 scans the reads pass 1 kept on the device: -read_scan_file may be left out) "
                     "--raw_contigs (writes <prefix>.raw_contigs.fasta, the contigs of the graph build before any cleaning)\n"
                     "--detipped_contigs (writes <prefix>.detipped_contigs.fasta, the contigs after the first cleaning step, ContigGraph::deleteTipsAndClean)\n"
-                    "--dechimered_contigs (writes <prefix>.dechimered_contigs.fasta, the contigs after the second cleaning step, ContigGraph::removeChimerasAndClean)\n");
+                    "--dechimered_contigs (writes <prefix>.dechimered_contigs.fasta, the contigs after the second cleaning step, ContigGraph::removeChimerasAndClean)\n"
+                    "--raw_graph (writes <prefix>.raw_graph.fastg, the graph build before any cleaning as ContigGraph::printGraph prints it: two strands per contig, headers that name the neighbours)\n"
+                    "--detipped_graph (writes <prefix>.detipped_graph.fastg, the graph after the first cleaning step)\n"
+                    "--dechimered_graph (writes <prefix>.dechimered_graph.fastg, the graph after the second cleaning step)\n");
 }
 
 // src/Faucet.cpp:57-182 (with the missing `return 0` supplied and a bounds check on flag values)
@@ -155,6 +164,9 @@ int handle_arguments(int argc, char** argv, Options& o) {
         else if (a == "--raw_contigs") o.raw_contigs = true;
         else if (a == "--detipped_contigs") o.detipped_contigs = true;
         else if (a == "--dechimered_contigs") o.dechimered_contigs = true;
+        else if (a == "--raw_graph") o.raw_graph = true;
+        else if (a == "--detipped_graph") o.detipped_graph = true;
+        else if (a == "--dechimered_graph") o.dechimered_graph = true;
         else if (a == "-estimate_bits") { if (!val(v)) goto bad; o.estimate_bits = atoi(v); if (o.estimate_bits < FGPU_EST_MIN_BITS || o.estimate_bits > FGPU_EST_MAX_BITS) { fprintf(stderr, "-estimate_bits must be in %d..%d\n", FGPU_EST_MIN_BITS, FGPU_EST_MAX_BITS); return 1; } }
         else if (a == "--help" || a == "-h") { argument_error(); return 1; }
         else { fprintf(stderr, "Cannot parse tag %s\n", argv[i]); argument_error(); return 1; }
@@ -430,18 +442,49 @@ int write_raw_contigs(const Options& o, fgpu_ctx* ctx, const uint64_t* keys, con
     CHECK(fgpu_stage3_build(ctx, o.read_length, totals, &bi));
     clk.mark("  raw contigs: graph build");
     if (bi.status != 0) {      // the reference itself does not return from buildContigGraph on this map: no file
-        const char* what = o.raw_contigs ? "raw_contigs" : o.detipped_contigs ? "detipped_contigs" : "dechimered_contigs";
-        fprintf(stderr, "--%s: getContig call %llu of JunctionMap::buildContigGraph %s: the reference does not get as far as printing on this map, no %s.%s.fasta is written\n",
-                what, (unsigned long long)bi.stop_call, bi.status == 1 ? "trips an assert of the reference" : "never returns in the reference", o.file_prefix.c_str(), what);
+        const char* what = o.raw_graph ? "raw_graph" : o.raw_contigs ? "raw_contigs" : o.detipped_graph ? "detipped_graph" : o.detipped_contigs ? "detipped_contigs"
+                           : o.dechimered_graph ? "dechimered_graph" : "dechimered_contigs";
+        const char* kind = strstr(what, "graph") ? "fastg" : "fasta";
+        fprintf(stderr, "--%s: getContig call %llu of JunctionMap::buildContigGraph %s: the reference does not get as far as printing on this map, no %s.%s.%s is written\n",
+                what, (unsigned long long)bi.stop_call, bi.status == 1 ? "trips an assert of the reference" : "never returns in the reference", o.file_prefix.c_str(), what, kind);
         return 2;
     }
-    auto write_file = [&](const std::string& path, uint64_t bytes) -> int {
-        std::vector<char> text(bytes ? bytes : 1);
+    // a file leaves the device right behind the call that made it: the next Stage-3 call drops what was not taken
+    auto take_file = [&](std::vector<char>& text, uint64_t bytes) -> int {
+        text.assign(bytes ? bytes : 1, 0);
         CHECK(fgpu_stage3_fasta_take(ctx, text.data(), bytes));
+        return 0;
+    };
+    auto put_file = [&](const std::string& path, const std::vector<char>& text, uint64_t bytes) -> int {
         FILE* f = fopen(path.c_str(), "wb");
         if (!f || fwrite(text.data(), 1, bytes, f) != bytes || fclose(f) != 0) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 2; }
         return 0;
     };
+    auto write_file = [&](const std::string& path, uint64_t bytes) -> int {
+        std::vector<char> text;
+        if (int rc = take_file(text, bytes)) return rc;
+        return put_file(path, text, bytes);
+    };
+    // ContigGraph::printGraph (src/ContigGraph.cpp:1470-1503) and its four lines, ahead of printContigs as src/Faucet.cpp:313-314 and :325-326 have them
+    auto write_graph = [&](const char* what, int call_rc, uint64_t bytes, const fgpu_fastg_info& gi) -> int {
+        if (call_rc != FGPU_OK) {
+            fprintf(stderr, "--%s: %s: no %s.%s.fastg is written\n", what, fgpu_last_error(ctx), o.file_prefix.c_str(), what);
+            return 2;
+        }
+        printf("Printing unitig FASTG.\n");
+        if (int rc = write_file(o.file_prefix + "." + what + ".fastg", bytes)) return rc;
+        printf("printed %d node-connected unitigs\n", (int)gi.node_records);
+        printf("printed %d isolated contigs\n", (int)gi.isolated_listed);       // (the whole list, as the reference counts)
+        printf("Done printing graph.\n");
+        return 0;
+    };
+    if (o.raw_graph) {
+        uint64_t bytes = 0;
+        fgpu_fastg_info gi;
+        const int call_rc = fgpu_stage3_raw_graph(ctx, o.read_length, &bytes, &gi);
+        if (int rc = write_graph("raw_graph", call_rc, bytes, gi)) return rc;
+        clk.mark("  raw graph: summaries, plan, join, emission, file");
+    }
     if (o.raw_contigs) {
         uint64_t bytes = 0;
         fgpu_raw_info ri;
@@ -452,16 +495,27 @@ int write_raw_contigs(const Options& o, fgpu_ctx* ctx, const uint64_t* keys, con
                (unsigned long long)ri.isolated_dropped, (unsigned long long)ri.nodes, (unsigned long long)bytes);
         clk.mark("  raw contigs: plan, emission, file");
     }
-    if (o.detipped_contigs || o.dechimered_contigs) {  // the first step of ContigGraph::cleanGraph (src/ContigGraph.cpp:211-215) on the same build, which is still on the device
+    if (o.detipped_contigs || o.dechimered_contigs || o.detipped_graph || o.dechimered_graph) {  // the first step of ContigGraph::cleanGraph (src/ContigGraph.cpp:211-215) on the same build, which is still on the device
         uint64_t bytes = 0;
         fgpu_tips_info ti;
         if (fgpu_stage3_detip(ctx, o.read_length, &bytes, &ti) != FGPU_OK) {      // (a plan status other than OK among them: no file)
-            const char* what = o.detipped_contigs ? "detipped_contigs" : "dechimered_contigs";
-            fprintf(stderr, "--%s: %s: no %s.%s.fasta is written\n", what, fgpu_last_error(ctx), o.file_prefix.c_str(), what);
+            const char* what = o.detipped_graph ? "detipped_graph" : o.detipped_contigs ? "detipped_contigs" : o.dechimered_graph ? "dechimered_graph" : "dechimered_contigs";
+            fprintf(stderr, "--%s: %s: no %s.%s.%s is written\n", what, fgpu_last_error(ctx), o.file_prefix.c_str(), what, strstr(what, "graph") ? "fastg" : "fasta");
             return 2;
         }
-        if (o.detipped_contigs) {                // (the step runs for the next one whether or not its own file is asked for)
-            if (int rc = write_file(o.file_prefix + ".detipped_contigs.fasta", bytes)) return rc;
+        std::vector<char> contigs_text;          // (the step runs for the next one whether or not its own file is asked for)
+        if (o.detipped_contigs) {
+            if (int rc = take_file(contigs_text, bytes)) return rc;
+        }
+        if (o.detipped_graph) {                  // the live graph the step left, printed before its contigs are; the graph stays as it is
+            uint64_t graph_bytes = 0;
+            fgpu_fastg_info gi;
+            const int call_rc = fgpu_stage3_graph_fastg(ctx, &graph_bytes, &gi);
+            if (int rc = write_graph("detipped_graph", call_rc, graph_bytes, gi)) return rc;
+            clk.mark("  detipped graph: summaries, plan, join, emission, file");
+        }
+        if (o.detipped_contigs) {
+            if (int rc = put_file(o.file_prefix + ".detipped_contigs.fasta", contigs_text, bytes)) return rc;
             printf("Detipped contigs: %llu tips deleted (and %llu back tips), %llu of %llu nodes left, %llu records (%llu bubble, %llu off nodes, %llu isolated; %llu isolated below "
                    "the read length left out), %llu bytes\n",
                    (unsigned long long)ti.tips, (unsigned long long)ti.back_tips, (unsigned long long)ti.print.nodes, (unsigned long long)ti.nodes_before,
@@ -470,17 +524,31 @@ int write_raw_contigs(const Options& o, fgpu_ctx* ctx, const uint64_t* keys, con
             clk.mark("  detipped contigs: plan, join, emission, file");
         }
     }
-    if (o.dechimered_contigs) {  // the second step (src/ContigGraph.cpp:218-220) on the graph the first one left, which the context kept alive
+    if (o.dechimered_contigs || o.dechimered_graph) {  // the second step (src/ContigGraph.cpp:218-220) on the graph the first one left, which the context kept alive
         uint64_t bytes = 0;
         fgpu_chimera_info ci;
         if (fgpu_stage3_dechimera(ctx, &bytes, &ci) != FGPU_OK) {
-            fprintf(stderr, "--dechimered_contigs: %s: no %s.dechimered_contigs.fasta is written\n", fgpu_last_error(ctx), o.file_prefix.c_str());
+            const char* what = o.dechimered_graph ? "dechimered_graph" : "dechimered_contigs";
+            fprintf(stderr, "--%s: %s: no %s.%s.%s is written\n", what, fgpu_last_error(ctx), o.file_prefix.c_str(), what, o.dechimered_graph ? "fastg" : "fasta");
             return 2;
         }
-        if (int rc = write_file(o.file_prefix + ".dechimered_contigs.fasta", bytes)) return rc;
-        printf("Dechimered contigs: %d chimeric extensions removed, %d of %d nodes left, %d records\n", (int)ci.removed, (int)ci.print.nodes, (int)ci.nodes_before,
-               (int)ci.print.records);
-        clk.mark("  dechimered contigs: summaries, plan step, join, emission, file");
+        std::vector<char> contigs_text;
+        if (o.dechimered_contigs) {
+            if (int rc = take_file(contigs_text, bytes)) return rc;
+        }
+        if (o.dechimered_graph) {
+            uint64_t graph_bytes = 0;
+            fgpu_fastg_info gi;
+            const int call_rc = fgpu_stage3_graph_fastg(ctx, &graph_bytes, &gi);
+            if (int rc = write_graph("dechimered_graph", call_rc, graph_bytes, gi)) return rc;
+            clk.mark("  dechimered graph: plan, join, emission, file");
+        }
+        if (o.dechimered_contigs) {
+            if (int rc = put_file(o.file_prefix + ".dechimered_contigs.fasta", contigs_text, bytes)) return rc;
+            printf("Dechimered contigs: %d chimeric extensions removed, %d of %d nodes left, %d records\n", (int)ci.removed, (int)ci.print.nodes, (int)ci.nodes_before,
+                   (int)ci.print.records);
+            clk.mark("  dechimered contigs: summaries, plan step, join, emission, file");
+        }
     }
     return 0;
 }
@@ -570,7 +638,7 @@ int write_scan_outputs(const Options& o, fgpu_ctx* ctx, const fgpu_scan_stats& s
     printf("Weight of short pair filter: %f\n", short_pf.weight());
     if (o.paired_ends) printf("Weight of long pair filter: %f\n", long_pf.weight());
     printf("Number of junctions: %llu\n", (unsigned long long)order.size());
-    if (o.raw_contigs || o.detipped_contigs || o.dechimered_contigs) return write_raw_contigs(o, ctx, keys.data(), recs.data(), order, clk);
+    if (o.raw_contigs || o.detipped_contigs || o.dechimered_contigs || o.raw_graph || o.detipped_graph || o.dechimered_graph) return write_raw_contigs(o, ctx, keys.data(), recs.data(), order, clk);
     return 0;
 }
 
@@ -1257,6 +1325,22 @@ int main(int argc, char** argv) {
             return 2;
         }
         if (o.just_load || o.from_junctions) { fprintf(stderr, "--dechimered_contigs needs the junction scan of this run: leave out --just_load_bloom and -junctions_file\n"); return 2; }
+    }
+    struct { bool on; const char* flag; bool missing; const char* entries; } graph_flags[] = {   // ... likewise
+        {o.raw_graph, "--raw_graph", !fgpu_stage3_set_junctions || !fgpu_stage3_build || !fgpu_stage3_raw_graph || !fgpu_stage3_fasta_take,
+         "fgpu_stage3_set_junctions, fgpu_stage3_build, fgpu_stage3_raw_graph, fgpu_stage3_fasta_take"},
+        {o.detipped_graph, "--detipped_graph", !fgpu_stage3_set_junctions || !fgpu_stage3_build || !fgpu_stage3_detip || !fgpu_stage3_graph_fastg || !fgpu_stage3_fasta_take,
+         "fgpu_stage3_set_junctions, fgpu_stage3_build, fgpu_stage3_detip, fgpu_stage3_graph_fastg, fgpu_stage3_fasta_take"},
+        {o.dechimered_graph, "--dechimered_graph",
+         !fgpu_stage3_set_junctions || !fgpu_stage3_build || !fgpu_stage3_detip || !fgpu_stage3_dechimera || !fgpu_stage3_graph_fastg || !fgpu_stage3_fasta_take,
+         "fgpu_stage3_set_junctions, fgpu_stage3_build, fgpu_stage3_detip, fgpu_stage3_dechimera, fgpu_stage3_graph_fastg, fgpu_stage3_fasta_take"}};
+    for (const auto& g : graph_flags) {
+        if (!g.on) continue;
+        if (g.missing) {
+            fprintf(stderr, "%s: the library this program is linked against lacks the entry points of the graph build, its cleaning steps and the graph's FASTG (%s)\n", g.flag, g.entries);
+            return 2;
+        }
+        if (o.just_load || o.from_junctions) { fprintf(stderr, "%s needs the junction scan of this run: leave out --just_load_bloom and -junctions_file\n", g.flag); return 2; }
     }
     if (o.estimate && !(o.est_kmers_flag && o.est_sing_flag)) {     // pass 0, ahead of everything the two numbers decide (and of the lines that print them)
         if (o.k < 1 || o.k > 31) { fprintf(stderr, "k must be in 1..31 on this build\n"); return 1; }

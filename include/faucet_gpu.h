@@ -1183,6 +1183,74 @@ int fgpu_chimera_plan(const uint64_t* keys, const fgpu_junction* recs, uint64_t 
                       fgpu_tips_info* tips_info, fgpu_chimera_info* info);
 int fgpu_stage3_dechimera(fgpu_ctx* ctx, uint64_t* bytes, fgpu_chimera_info* info);
 
+/* ---- Stage 3's graph as FASTG: ContigGraph::printGraph on the device ----
+ * The other half of what the reference ends with (src/Faucet.cpp:325-326, and commented out behind the build, :313-314): who is connected to
+ * whom, which printContigs' files cannot say (they fold bubbles and canonicalise).  ContigGraph::printGraph (src/ContigGraph.cpp:1470-1503)
+ * writes four lines per contig -- getFastGHeader(true), getSeq(), getFastGHeader(false), revcomp_string(getSeq()): the PRIMED header goes
+ * with the forward sequence, and nothing is canonicalised.
+ *   which contigs  ContigIterator (src/ContigIterator.cpp) over nodeMap in the container's order and contigs[0..4]: a contig with a null end
+ *     wherever it is met; one whose ends are the same node at the slot getMinIndex() names; any other where Contig::getSide(node, index) is 1.
+ *     Then isolated_contigs in list order, those of at least read_length bases (size_t >= int).
+ *   name    Contig::getFastGName (src/Contig.cpp:378-385): NODE_<this>_length_<bases>_cov_<getAvgCoverage()>, and ' when RC.  <this> is a heap
+ *     address there; here it is 0x and the contig's index in the live graph's contig array in hexadecimal: unique, unchanged for a contig
+ *     that survives a step (the files of one run can be laid side by side), and of the reference's shape.  The coverage goes through
+ *     operator<< of a double, which is printf's %g: six significant digits of (double) sum / (double) n, trailing zeros stripped, exponent
+ *     form below 1e-4, glibc's digit for digit (faucet_amd/csrc/fastg_name.h: integers only, shared by the kernel and the host).
+ *   header  getFastGHeader (:387-411): '>' name, then ';' without neighbours, else ':' and the neighbours' names joined by ',' and closed by
+ *     ';'.  The neighbours of the header with RC = false are node2_p->getFastGNeighbors(ind2), those of the primed one
+ *     node1_p->getFastGNeighbors(ind1) (src/ContigNode.cpp:179-202: index 4 gives the set slots 0..3 in order, any other index slot 4 if
+ *     set); a neighbour is primed iff its getSide(thatNode, slot) is 2 -- under BOTH headers: the flag is not inverted for the primed one.
+ *
+ * fgpu_stage3_fastg -- the device: print n records that are joined already, over a text in fgpu_stage3_join's layout.  Record i is
+ * recs[i].len bases from word recs[i].text_word; its headers' neighbours are nbr[nbr_first[2i] .. nbr_first[2i + 1]) (primed header, first
+ * line) and nbr[nbr_first[2i + 1] .. nbr_first[2i + 2]), each entry a record's index, | FGPU_FASTG_PRIMED for a primed name.  text_host ==
+ * NULL: the joined text of the last fgpu_stage3_join whose results are still on the device, read where it lies (FGPU_ERR_STATE if there is
+ * none); text_host != NULL: text_words words are uploaded first.  FGPU_ERR_ARG with a message, nothing launched and earlier results
+ * untouched: a record that reaches past the text, a record of no bases or of 2^31 and more, a summary of no entries or with sum > 255 n,
+ * n of 2^31 and more, a neighbour CSR that is not one (nbr_first[0] != 0, descending, more than four entries in a list, nbr_first[2n] !=
+ * n_nbr), a neighbour index >= n.  Three kernels (faucet_amd/csrc/stage3_fastg.hip): the names, one lane per record; the sizes, scanned by
+ * rocPRIM; the text by tiles of FGPU_FASTG_TILE bytes of OUTPUT, the second strand read from the same 2-bit string.  The file stays on the
+ * device, *bytes says how long it is (0 for n == 0), and fgpu_stage3_fasta_take takes it: it is THE file slot of the context, so a file that
+ * was not taken before the call is dropped, as every Stage-3 call drops it.
+ *
+ * fgpu_stage3_raw_graph -- <prefix>.raw_graph.fastg (src/Faucet.cpp:313) on a finished build that has not been taken and whose status is 0
+ * (fgpu_stage3_raw_contigs' preconditions and messages): the graph is made with fgpu_stage3_cov_calls' summaries, walked (a plan status
+ * other than FGPU_PLAN_OK is FGPU_ERR_STATE with a message), the records' piece lists joined by fgpu_stage3_join over the build where it
+ * lies, and printed.  The build is left as it was found, and so is a live graph.  Join results and a file that were not taken before the
+ * call are dropped.
+ *
+ * fgpu_stage3_graph_fastg -- the same of the LIVE graph of the last fgpu_stage3_detip or fgpu_stage3_dechimera: FGPU_ERR_STATE with a
+ * message if there is none, if it was taken, or if its build is gone.  A graph that has no summaries yet is given them (what
+ * fgpu_stage3_dechimera would give it); nothing else of it changes: an fgpu_stage3_dechimera behind the call behaves as if it had not been
+ * made, and the call may be made again.  Join results and a file that were not taken before the call are dropped.
+ *
+ * info: printGraph's counts -- "printed %d node-connected unitigs" is node_records, "printed %d isolated contigs" is isolated_listed, the size
+ * of the whole list, not the number printed. */
+#define FGPU_FASTG_PRIMED 0x80000000u
+#define FGPU_FASTG_TILE   4096          /* bytes of output per workgroup of the text kernel */
+typedef struct {
+    uint64_t tig;          /* <this>: printed as 0x and hexadecimal */
+    uint64_t text_word;    /* first word of the record's 2-bit string in the text */
+    uint64_t cov_sum;      /* getAvgCoverage = (double) cov_sum / (double) cov_n */
+    uint32_t len;          /* bases */
+    uint32_t cov_n;
+} fgpu_fastg_rec;
+typedef struct {
+    uint64_t node_records;      /* records ContigIterator gave */
+    uint64_t isolated_printed;  /* isolated contigs of at least read_length bases */
+    uint64_t isolated_listed;   /* entries of isolated_contigs */
+    uint64_t nodes;             /* entries of nodeMap */
+} fgpu_fastg_info;
+int fgpu_stage3_fastg(fgpu_ctx* ctx, const fgpu_fastg_rec* recs, uint64_t n, const uint64_t* nbr_first, const uint32_t* nbr, uint64_t n_nbr,
+                      const uint64_t* text_host, uint64_t text_words, uint64_t* bytes);
+int fgpu_stage3_raw_graph(fgpu_ctx* ctx, int32_t read_length, uint64_t* bytes, fgpu_fastg_info* info);
+int fgpu_stage3_graph_fastg(fgpu_ctx* ctx, uint64_t* bytes, fgpu_fastg_info* info);
+/* The last fgpu_stage3_raw_graph / fgpu_stage3_graph_fastg of the context by parts, host clock, ms (measurement; 0 for a part the call did not
+ * have): [0] the build's record arrays and the map to the host, [1] the summaries (fgpu_stage3_cov_calls, and folding them into a live graph),
+ * [2] the graph made of the build, [3] the walk (CleanGraph::fastg_records), [4] the records' lists and fgpu_stage3_join, [5] fgpu_stage3_fastg:
+ * its checks, the records' way to the device, the three kernels. */
+int fgpu_diag_fastg_times(fgpu_ctx* ctx, double ms[6]);
+
 /* ---- profiling --------------------------------------------------------------------------------- */
 typedef struct {
     char     name[48];
